@@ -3,12 +3,16 @@ evaluations per ray), BASELINE.json's metric on its config 2 (Sapien single-scen
 weak-scaled multi-GPU form of it (config 3: every rank renders a 640x480 frame of ray batches, rendered pixels
 are exchanged with one RCCL all-gather).
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One step = one pass of NeRF.forward over one synthetic 307,200-ray frame per GPU, inputs already resident in HBM.
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the headline; `--full` adds
+everything else: the live roofline of the timed region, clock / power samples, the informational legs (configs 1, 3, 4
+and 5, non-default constructor arguments) and the CPU baseline with its PSNR check.  `--dump-outputs DIR` writes the
+last timed step's outputs (both levels' rgb / acc / depth) as DIR/<name>.npy; the inputs are seeded, so two builds of
+the project can be compared output for output.
 """
 import argparse
 import json
@@ -526,6 +530,25 @@ def train_leg(dev, rank, world, distributed, steps=24, n_rays=4096):
         return {"error": f"{type(e).__name__}: {e}"}
 
 
+DUMP_LIMIT_BYTES = 60 * 2**20   # --dump-outputs stays under 64 MB in all, .npy headers included
+
+
+def dump_outputs(outdir, arrays):
+    """Write each tensor of `arrays` as outdir/<name>.npy in float32 (float64 stays float64).  Over DUMP_LIMIT_BYTES in all, every
+    array keeps the same fixed, seeded sample of its rows (sorted, so a row of one array still pairs with the same row of another)."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: v.detach().cpu() for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == torch.float64 else v.float() for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_LIMIT_BYTES and v.dim() > 0 and v.shape[0] > 1:
+            keep = max(1, v.shape[0] * DUMP_LIMIT_BYTES // total)
+            v = v[torch.randperm(v.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+        np.save(os.path.join(outdir, name + ".npy"), v.contiguous().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -533,14 +556,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: live roofline of the timed region, "
+                    "clock / power samples, the informational legs and the CPU baseline (the --no-* options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline and its PSNR check")
     ap.add_argument("--no-alt", action="store_true", help="(no-op since round 3: the split-bf16 engine was removed; kept for old command lines)")
-    ap.add_argument("--sharded-leg", action="store_true", help="(default now) kept for old command lines: the sharded-frame leg always runs")
-    ap.add_argument("--no-sharded-leg", action="store_true", help="skip the informational BASELINE config 3 leg (one frame sharded over the ranks + RCCL all-gather)")
-    ap.add_argument("--no-train-leg", action="store_true", help="skip the extra (informational) articulated training-step timing")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the informational BASELINE config 1 / config 4 render legs")
+    ap.add_argument("--sharded-leg", action="store_true", help="kept for old command lines: with --full the sharded-frame leg always runs")
+    ap.add_argument("--no-sharded-leg", action="store_true", help="(with --full) skip the informational BASELINE config 3 leg (one frame sharded over the ranks + RCCL all-gather)")
+    ap.add_argument("--no-train-leg", action="store_true", help="(with --full) skip the extra (informational) articulated training-step timing")
+    ap.add_argument("--no-extra-legs", action="store_true", help="(with --full) skip the informational BASELINE config 1 / config 4 render legs")
     ap.add_argument("--literal", action="store_true", help="A/B: aon_set_bottleneck_fold(0) -- the reference-literal two-layer bottleneck + view layer of rounds 1-4")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -575,6 +603,7 @@ def main():
     distributed = dist.is_available() and dist.is_initialized()
 
     marks = []   # per timed step: (begin, rendered, gathered) events on torch's current stream (recording is asynchronous)
+    last = {}    # what the latest step handed back: both levels of this rank's frame, and the gathered fine level
 
     def step():
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -584,6 +613,7 @@ def main():
         res = all_gather_pixels(out[1], counts=[n_rays] * world) if distributed else out[1]   # one RCCL all-gather of 20 B/ray; (world*n, .) rank-major
         ev[2].record()
         marks.append(ev)
+        last["levels"], last["gathered"] = out, res
         return res
 
     def fence():
@@ -597,15 +627,25 @@ def main():
             step()
         fence()
         marks.clear()
-        ops.profile_begin()
-        with GpuStateSampler(local_rank, enabled=rank == 0) as gpu_state:
+        if args.full:   # the library's per-kernel-class HIP-event timers: the live roofline of this region
+            ops.profile_begin()
+        with GpuStateSampler(local_rank, enabled=rank == 0 and args.full) as gpu_state:
             t0 = time.perf_counter()
             for _ in range(args.steps):
                 fine = step()
             fence()
             dt = time.perf_counter() - t0
-        mlp_ms, mlp_launches, mlp_samples = ops.profile_end()
-        headline_classes = ops.profile_classes()
+        if args.full:
+            mlp_ms, mlp_launches, mlp_samples = ops.profile_end()
+            headline_classes = ops.profile_classes()
+
+    if args.dump_outputs and rank == 0:
+        arrays = {}
+        for lvl, name in enumerate(("coarse", "fine")):
+            arrays.update({f"{name}_{k}": v for k, v in zip(("rgb", "acc", "depth"), last["levels"][lvl])})
+        if distributed:
+            arrays.update({f"gathered_fine_{k}": v for k, v in zip(("rgb", "acc", "depth"), last["gathered"])})
+        dump_outputs(args.dump_outputs, arrays)
 
     dt_local = dt
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -632,7 +672,7 @@ def main():
     # BASELINE config 3 literally (informational, never `value`): ONE 640x480 frame, contiguous ray ranges sharded over the
     # ranks, fine-level pixels all-gathered (RCCL) -- strong scaling of a single frame, where `value` above is weak scaling.
     sharded = None
-    if not args.no_sharded_leg:
+    if args.full and not args.no_sharded_leg:
         own_group = False
         # RCCL prints a version banner on C-level stdout when it comes up; this script's stdout carries ONE JSON line, so file
         # descriptor 1 points at stderr while the leg runs (the banner would otherwise land behind the JSON at exit)
@@ -702,17 +742,15 @@ def main():
             os.dup2(saved_fd, 1)
             os.close(saved_fd)
 
-    train = None if args.no_train_leg else train_leg(dev, rank, world, distributed)
+    train = train_leg(dev, rank, world, distributed) if args.full and not args.no_train_leg else None
     # BASELINE configs 1 and 4 on this rank's GPU (informational, never `value`)
-    config1 = None if args.no_extra_legs else render_leg(dev, "config1", 240, 320)
-    art_render = None if args.no_extra_legs else render_leg(dev, "art", 240, 320)
-    other_ctor = None if args.no_extra_legs else other_constructor_leg(dev)
+    extra = args.full and not args.no_extra_legs
+    config1 = render_leg(dev, "config1", 240, 320) if extra else None
+    art_render = render_leg(dev, "art", 240, 320) if extra else None
+    other_ctor = other_constructor_leg(dev) if extra else None
 
     if rank == 0:
         rays_per_s = world * n_rays * args.steps / dt
-        flop_ex = 2 * executed(VAN_MAC, fold, ops.view_bias_enabled())       # what the kernel executes per network evaluation
-        mlp_tflops = mlp_samples * flop_ex / (mlp_ms * 1e-3) / 1e12 if mlp_ms > 0 else 0.0
-        mlp_tflops_lit = mlp_samples * FLOP_PER_SAMPLE / (mlp_ms * 1e-3) / 1e12 if mlp_ms > 0 else 0.0
         res = {
             "metric": "rays/sec (64c+128f samples)", "value": rays_per_s, "unit": "rays/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -723,55 +761,61 @@ def main():
                        "rays_per_gpu": n_rays, "evals_per_ray": EVALS_PER_RAY,
                        "exchange": "RCCL all_gather of (rgb,acc,depth)=20 B/ray" if world > 1 else "none"},
             "multi_gpu": diag,
-            "gpu_state": gpu_state.summary(),
             "bottleneck_fold": fold,
             "view_bias": bool(ops.view_bias_enabled()),
-            "roofline": {"bound": "mfma", "kernel": "aon::mlp_fwd_kernel<true,false,fold,view-bias> (fused encode+MLP, fp32 MFMA)",
-                         "achieved": mlp_tflops, "peak": PEAK_FP32_MATRIX_TFLOPS, "unit": "TFLOP/s",
-                         "frac": mlp_tflops / PEAK_FP32_MATRIX_TFLOPS, "traffic": None,
-                         "peak_measured": PEAK_FP32_MATRIX_MEASURED_TFLOPS, "frac_of_peak_measured": mlp_tflops / PEAK_FP32_MATRIX_MEASURED_TFLOPS,
-                         "achieved_reference_literal": mlp_tflops_lit, "frac_reference_literal": mlp_tflops_lit / PEAK_FP32_MATRIX_TFLOPS,
-                         "launches": mlp_launches, "avg_launch_ms": mlp_ms / max(mlp_launches, 1),
-                         "flop_per_sample": flop_ex, "flop_per_sample_reference_literal": FLOP_PER_SAMPLE,
-                         "note": "achieved / frac price the FLOPs the kernel EXECUTES (bottleneck_layer folded into views_linear[0] when bottleneck_fold: "
-                                 "65,536 MACs per sample fewer than the reference's graph; the view-encoding columns of that layer as a per-ray bias when "
-                                 "view_bias: 3,584 fewer); *_reference_literal price the reference's 1,186,816 FLOP per "
-                                 "sample against the same time and can exceed the executed fraction",
-                         "whole_path_frac": rays_per_s / world * EVALS_PER_RAY * flop_ex / (PEAK_FP32_MATRIX_TFLOPS * 1e12),
-                         "whole_path_frac_reference_literal": rays_per_s / world * EVALS_PER_RAY * FLOP_PER_SAMPLE / (PEAK_FP32_MATRIX_TFLOPS * 1e12)},
         }
-        res["roofline"].update(pmc_traffic())
-        res["hbm_kernels"] = pmc_traffic_ray_kernels(per_ray_rooflines(headline_classes))   # the non-GEMM kernels of the same timed region (>= 50 % of HBM peak each)
-        if config1 is not None:
-            res["config1"] = config1
-        if art_render is not None:
-            res["art_render"] = art_render
-        if other_ctor is not None:
-            res["other_constructor_arguments"] = other_ctor
-        if sharded is not None:
-            res["sharded_frame"] = sharded
-        if train is not None:
-            res["train_step"] = train
-        # the informational legs' headline scalars, where the driver's parser keeps them (they survived only in the truncated tail)
-        lifted = {}
-        if train is not None and "error" not in train:
-            lifted.update({"config5_train_step_ms": train["ms_per_step"], "config5_train_step_frac_executed": train["roofline"]["frac"],
-                           "config5_train_step_frac_reference_literal": train["roofline"]["frac_reference_literal"],
-                           "config5_train_rays_per_s": train["rays_per_s"]})
-        if config1 is not None and "error" not in config1:
-            lifted.update({"config1_rays_per_s": config1.get("value"), "config1_frac_executed": (config1.get("roofline") or {}).get("frac")})
-        if art_render is not None and "error" not in art_render:
-            lifted.update({"config4_art_render_rays_per_s": art_render.get("value"), "config4_art_render_frac_executed": (art_render.get("roofline") or {}).get("frac")})
-        if sharded is not None and "error" not in sharded:
-            lifted.update({"config3_sharded_frame_rays_per_s": sharded["rays_per_s"]})
-        res["config"]["informational"] = lifted
-        if world == 1 and not args.no_cpu_baseline:
-            rays_cpu = {k: v.cpu() for k, v in rays.items()}
-            base, ref_rgb, (a, b) = cpu_baseline(sd, rays_cpu)
-            res["cpu_baseline"] = base
-            mse = torch.mean((fine[0][:n_rays][a:b].cpu() - ref_rgb) ** 2).item()
-            res["psnr_vs_oracle_db"] = float(-10.0 * torch.log10(torch.tensor(max(mse, 1e-20))))
-            res["speedup_vs_cpu"] = rays_per_s / base["value"]
+        if args.full:   # the live roofline of the timed region, its clock / power samples, the informational legs and the CPU baseline
+            flop_ex = 2 * executed(VAN_MAC, fold, ops.view_bias_enabled())       # what the kernel executes per network evaluation
+            mlp_tflops = mlp_samples * flop_ex / (mlp_ms * 1e-3) / 1e12 if mlp_ms > 0 else 0.0
+            mlp_tflops_lit = mlp_samples * FLOP_PER_SAMPLE / (mlp_ms * 1e-3) / 1e12 if mlp_ms > 0 else 0.0
+            res.update({
+                "gpu_state": gpu_state.summary(),
+                "roofline": {"bound": "mfma", "kernel": "aon::mlp_fwd_kernel<true,false,fold,view-bias> (fused encode+MLP, fp32 MFMA)",
+                             "achieved": mlp_tflops, "peak": PEAK_FP32_MATRIX_TFLOPS, "unit": "TFLOP/s",
+                             "frac": mlp_tflops / PEAK_FP32_MATRIX_TFLOPS, "traffic": None,
+                             "peak_measured": PEAK_FP32_MATRIX_MEASURED_TFLOPS, "frac_of_peak_measured": mlp_tflops / PEAK_FP32_MATRIX_MEASURED_TFLOPS,
+                             "achieved_reference_literal": mlp_tflops_lit, "frac_reference_literal": mlp_tflops_lit / PEAK_FP32_MATRIX_TFLOPS,
+                             "launches": mlp_launches, "avg_launch_ms": mlp_ms / max(mlp_launches, 1),
+                             "flop_per_sample": flop_ex, "flop_per_sample_reference_literal": FLOP_PER_SAMPLE,
+                             "note": "achieved / frac price the FLOPs the kernel EXECUTES (bottleneck_layer folded into views_linear[0] when bottleneck_fold: "
+                                     "65,536 MACs per sample fewer than the reference's graph; the view-encoding columns of that layer as a per-ray bias when "
+                                     "view_bias: 3,584 fewer); *_reference_literal price the reference's 1,186,816 FLOP per "
+                                     "sample against the same time and can exceed the executed fraction",
+                             "whole_path_frac": rays_per_s / world * EVALS_PER_RAY * flop_ex / (PEAK_FP32_MATRIX_TFLOPS * 1e12),
+                             "whole_path_frac_reference_literal": rays_per_s / world * EVALS_PER_RAY * FLOP_PER_SAMPLE / (PEAK_FP32_MATRIX_TFLOPS * 1e12)},
+            })
+            res["roofline"].update(pmc_traffic())
+            res["hbm_kernels"] = pmc_traffic_ray_kernels(per_ray_rooflines(headline_classes))   # the non-GEMM kernels of the same timed region (>= 50 % of HBM peak each)
+            if config1 is not None:
+                res["config1"] = config1
+            if art_render is not None:
+                res["art_render"] = art_render
+            if other_ctor is not None:
+                res["other_constructor_arguments"] = other_ctor
+            if sharded is not None:
+                res["sharded_frame"] = sharded
+            if train is not None:
+                res["train_step"] = train
+            # the informational legs' headline scalars, where the driver's parser keeps them (they survived only in the truncated tail)
+            lifted = {}
+            if train is not None and "error" not in train:
+                lifted.update({"config5_train_step_ms": train["ms_per_step"], "config5_train_step_frac_executed": train["roofline"]["frac"],
+                               "config5_train_step_frac_reference_literal": train["roofline"]["frac_reference_literal"],
+                               "config5_train_rays_per_s": train["rays_per_s"]})
+            if config1 is not None and "error" not in config1:
+                lifted.update({"config1_rays_per_s": config1.get("value"), "config1_frac_executed": (config1.get("roofline") or {}).get("frac")})
+            if art_render is not None and "error" not in art_render:
+                lifted.update({"config4_art_render_rays_per_s": art_render.get("value"), "config4_art_render_frac_executed": (art_render.get("roofline") or {}).get("frac")})
+            if sharded is not None and "error" not in sharded:
+                lifted.update({"config3_sharded_frame_rays_per_s": sharded["rays_per_s"]})
+            res["config"]["informational"] = lifted
+            if world == 1 and not args.no_cpu_baseline:
+                rays_cpu = {k: v.cpu() for k, v in rays.items()}
+                base, ref_rgb, (a, b) = cpu_baseline(sd, rays_cpu)
+                res["cpu_baseline"] = base
+                mse = torch.mean((fine[0][:n_rays][a:b].cpu() - ref_rgb) ** 2).item()
+                res["psnr_vs_oracle_db"] = float(-10.0 * torch.log10(torch.tensor(max(mse, 1e-20))))
+                res["speedup_vs_cpu"] = rays_per_s / base["value"]
         print(json.dumps(res), flush=True)
     if distributed:
         dist.barrier()

@@ -14,7 +14,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-alt", "--no-train-leg", "--no-extra-legs"]
+FLAGS = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-alt", "--no-train-leg", "--no-extra-legs"]
 
 
 def _run(cmd):

@@ -13,12 +13,12 @@ mkdir -p $OUT $SUM
 cd /tmp && export TMPDIR=/tmp
 run() { timeout 600 "$@"; }
 # 1. headline render bench: per-kernel durations
-run rocprofv3 --kernel-trace --stats -d $OUT/stats -o $TAG -- python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train-leg --no-extra-legs --no-alt > $OUT/stats_run.log 2>&1
+run rocprofv3 --kernel-trace --stats -d $OUT/stats -o $TAG -- python $REPO/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-train-leg --no-extra-legs --no-alt > $OUT/stats_run.log 2>&1
 # 2. counters, one pass per group
-run rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o $TAG -- python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-train-leg --no-extra-legs --no-alt > $OUT/pmc_fetch.log 2>&1
-run rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o $TAG -- python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-train-leg --no-extra-legs --no-alt > $OUT/pmc_write.log 2>&1
-run rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES -d $OUT/pmc_sq -o $TAG -- python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-train-leg --no-extra-legs --no-alt > $OUT/pmc_sq.log 2>&1
-run rocprofv3 --kernel-trace --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY -d $OUT/pmc_sq2 -o $TAG -- python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-train-leg --no-extra-legs --no-alt > $OUT/pmc_sq2.log 2>&1
+run rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o $TAG -- python $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-train-leg --no-extra-legs --no-alt > $OUT/pmc_fetch.log 2>&1
+run rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o $TAG -- python $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-train-leg --no-extra-legs --no-alt > $OUT/pmc_write.log 2>&1
+run rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES -d $OUT/pmc_sq -o $TAG -- python $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-train-leg --no-extra-legs --no-alt > $OUT/pmc_sq.log 2>&1
+run rocprofv3 --kernel-trace --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY -d $OUT/pmc_sq2 -o $TAG -- python $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-train-leg --no-extra-legs --no-alt > $OUT/pmc_sq2.log 2>&1
 # 3. training steps (BASELINE config 5 per GPU, and the reference's vanilla batch).  Kernel statistics with the two levels'
 #    backward SERIALISED on one stream (--no-overlap): on the product's two library streams kernels of the two levels share the
 #    CUs and their individual durations stretch (likewise --late-heads: the early head reductions wait for compute units beside the chain and

@@ -83,6 +83,8 @@ _SIGS = {
     "aon_adam_step": (_i, [_p, _p, _p, _p, _l, C.c_double, C.c_double, C.c_double, C.c_double, _l, _p]),
     "aon_code_library_fwd": (_i, [_p, _p, _p, _p, _p, _p]),
     "aon_code_library_bwd": (_i, [_p, _p, _p, _p, _p, _p]),
+    "aon_ssim_workspace_bytes": (_l, [_i, _p, _p]),
+    "aon_ssim": (_i, [_i, _p, _p, _p, _p, _p, _l, _p, _p]),
     "aon_art_pack_step": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "aon_vanilla_pack_step": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
     "aon_set_bwd_early_heads": (_i, [_i]),

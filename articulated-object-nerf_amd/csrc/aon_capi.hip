@@ -87,6 +87,8 @@ hipError_t launch_train_loss(bool backward, const float* rgb_c, const float* rgb
                              float reg_scale, float* stats, float* loss, const float* go, float* d_rgb_c, float* d_rgb_f, float* const* d_lat, hipStream_t stream);
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps, int64_t step, hipStream_t stream);
 hipError_t launch_code_library(bool backward, const float* const* src, const int64_t* const* idx, const int* rows, const int* dim, float* const* dst, hipStream_t stream);
+int64_t ssim_workspace_bytes(int n, const int* h, const int* w);
+hipError_t launch_ssim(int n, const float* const* x, const float* const* y, const int* h, const int* w, double* part, float* out, hipStream_t stream);
 hipError_t launch_raygen(const float* c2w, int H, int W, float focal, const float* directions, int64_t pix_begin,
                          int64_t pix_end, float* rays_o, float* viewdirs, float* rays_d, hipStream_t stream);
 hipError_t launch_ray_directions(int H, int W, float focal, float* out, hipStream_t stream);
@@ -714,6 +716,33 @@ int aon_code_library_fwd(const float* const* tables_host, const int64_t* const* 
 int aon_code_library_bwd(const float* const* g_rows_host, const int64_t* const* ids_host, const int* rows_host, const int* dims_host, float* const* g_tables_host,
                          void* stream) {
   return code_library_call(true, g_rows_host, ids_host, rows_host, dims_host, g_tables_host, stream, "aon_code_library_bwd");
+}
+
+// ---- test-epoch SSIM (csrc/aon_metrics.hip) ----
+static const char* ssim_sizes_ok(int n_images, const int* h_host, const int* w_host) {
+  if (!h_host || !w_host) return "null size array";
+  for (int i = 0; i < n_images; ++i)
+    if (h_host[i] < 11 || w_host[i] < 11 || h_host[i] > 32768 || w_host[i] > 32768)
+      return "every image needs 11 <= h, w <= 32768 (the 11 x 11 window is applied without padding)";
+  return nullptr;
+}
+int64_t aon_ssim_workspace_bytes(int n_images, const int* h_host, const int* w_host) {
+  if (n_images < 0) return fail(AON_E_INVALID, "aon_ssim_workspace_bytes: n_images < 0");
+  if (n_images == 0) return 0;
+  if (const char* msg = ssim_sizes_ok(n_images, h_host, w_host)) return fail(AON_E_INVALID, msg);
+  return aon::ssim_workspace_bytes(n_images, h_host, w_host);
+}
+int aon_ssim(int n_images, const float* const* preds_host, const float* const* gts_host, const int* h_host, const int* w_host, void* workspace,
+             int64_t workspace_bytes, float* out, void* stream) {
+  if (n_images < 0) return fail(AON_E_INVALID, "aon_ssim: n_images < 0");
+  if (n_images == 0) return AON_OK;
+  if (!preds_host || !gts_host || !out || !workspace) return fail(AON_E_INVALID, "aon_ssim: null pointer");
+  if (reinterpret_cast<uintptr_t>(workspace) & 7) return fail(AON_E_INVALID, "aon_ssim: workspace is not 8-byte aligned");
+  for (int i = 0; i < n_images; ++i)
+    if (!preds_host[i] || !gts_host[i]) return fail(AON_E_INVALID, "aon_ssim: null image pointer");
+  if (const char* msg = ssim_sizes_ok(n_images, h_host, w_host)) return fail(AON_E_INVALID, msg);
+  if (workspace_bytes < aon::ssim_workspace_bytes(n_images, h_host, w_host)) return fail(AON_E_WORKSPACE, "aon_ssim: workspace too small");
+  return check(aon::launch_ssim(n_images, preds_host, gts_host, h_host, w_host, static_cast<double*>(workspace), out, (hipStream_t)stream), "aon_ssim");
 }
 
 int aon_profile_begin(void) {

@@ -63,6 +63,19 @@ class LitModel(torch.nn.Module):
         m = self.psnr_each(preds, gts).mean().item()
         return {"name": "PSNR", "mean": m, "test": m}
 
+    @torch.no_grad()
+    def ssim_each(self, preds, gts):
+        """interface.py:102-111: piqa's SSIM() of each (h, w, 3) pair clipped to [0,1], as one HIP call over the whole list -> (n,)."""
+        from ..ops import ssim
+
+        return ssim(preds, gts)
+
+    @torch.no_grad()
+    def ssim(self, preds, gts, i_train=None, i_val=None, i_test=None):
+        """interface.py:142-157: {"name": "SSIM", "mean": m, "test": m} over per-image SSIMs."""
+        m = self.ssim_each(preds, gts).mean().item()
+        return {"name": "SSIM", "mean": m, "test": m}
+
 
 def get_obj_rgbs_from_segmap(all_segmap, all_pred_img, all_pred_target):
     """models/utils.py:102-109: per image, the predicted / target colours of the pixels inside the instance mask."""
@@ -125,9 +138,9 @@ for _name in ("__getitem__", "__iter__", "__len__", "__repr__", "__eq__", "__ne_
 
 class Harness(LitModel):
     """What the two LightningModules of the reference share once Lightning is removed: the ``self.log`` sink, the
-    learning-rate rule of ``optimizer_step`` (model.py:391-419 == model_autodecoder.py:607-636) and the PSNR half of
-    ``test_epoch_end`` (model.py:450-485, model_autodecoder.py:665-701; SSIM / LPIPS need third-party networks and are
-    out of scope)."""
+    learning-rate rule of ``optimizer_step`` (model.py:391-419 == model_autodecoder.py:607-636) and the PSNR / SSIM part
+    of ``test_epoch_end`` (model.py:450-485, model_autodecoder.py:665-701; LPIPS needs pretrained VGG weights and is out of
+    scope)."""
 
     lr_init, lr_final, lr_delay_steps, lr_delay_mult = 5.0e-4, 5.0e-6, 2500, 0.01
 
@@ -184,8 +197,9 @@ class Harness(LitModel):
 
     @torch.no_grad()
     def test_epoch_end(self, outputs, image_sizes, out_dir=None, name="image"):
-        """Gather the per-image test outputs over ranks, PSNR over whole images and over object pixels, and (rank 0,
-        when ``out_dir`` is given) the JPEG dump + results.json of the reference."""
+        """Gather the per-image test outputs over ranks, PSNR and SSIM over whole images, PSNR over object pixels, and
+        (rank 0, when ``out_dir`` is given) the JPEG dump + results.json of the reference.  Returns (psnr, psnr_obj); the
+        SSIM dict is logged as ``test/ssim`` and written to results.json."""
         from ..utils import store_image, write_stats
 
         self.finish_fit()
@@ -193,12 +207,14 @@ class Harness(LitModel):
         masks = self.alter_gather_cat(outputs, "instance_mask", image_sizes)
         targets = self.alter_gather_cat(outputs, "target", image_sizes)
         psnr = self.psnr(rgbs, targets)
+        ssim = self.ssim(rgbs, targets)
         objs, obj_targets = get_obj_rgbs_from_segmap(masks, rgbs, targets)
         psnr_obj = self.psnr(objs, obj_targets)
         psnr_obj["name"] = "PSNR_obj"
         self.log("test/psnr", psnr["test"])
+        self.log("test/ssim", ssim["test"])
         self.log("test/psnr_obj", psnr_obj["test"])
         if out_dir is not None and (not dist.is_initialized() or dist.get_rank() == 0):
             store_image(out_dir, rgbs, name)
-            write_stats(os.path.join(out_dir, "results.json"), psnr, psnr_obj)
+            write_stats(os.path.join(out_dir, "results.json"), psnr, ssim, psnr_obj)
         return psnr, psnr_obj

@@ -1399,3 +1399,47 @@ def code_library_bwd(g_rows, ids, shapes, outs=None):
     with torch.cuda.device(dev):
         check(lib.aon_code_library_bwd(_ptr_array(gr), idp, rows, dims, _ptr_array(outs), _stream()), "aon_code_library_bwd")
     return outs
+
+
+# ------------------------------------------------------------------ test-epoch metrics
+def ssim(preds, gts, image_sizes=None) -> torch.Tensor:
+    """piqa's SSIM() with its defaults for each (pred, gt) pair, both clipped to [0,1] (LitModel.ssim_each, interface.py:102-111), all images in
+    one call -> (n,) float32 on the device.  Each image is an (h, w, 3) fp32 cuda tensor, or (h*w, 3) with `image_sizes` = [(h, w), ...]; h, w >= 11
+    (the window is applied without padding).  fp64 window statistics and a fixed-order reduction: the same bits on every call and in any batch."""
+    preds, gts = list(preds), list(gts)
+    if len(preds) != len(gts):
+        raise ValueError(f"ssim: {len(preds)} predictions but {len(gts)} targets")
+    if image_sizes is not None and len(image_sizes) != len(preds):
+        raise ValueError(f"ssim: {len(image_sizes)} image sizes for {len(preds)} images")
+    ps, gs, hs, ws = [], [], [], []
+    for i, (p, g) in enumerate(zip(preds, gts)):
+        p, g = _f32(p, f"preds[{i}]"), _f32(g, f"gts[{i}]")
+        if p.shape != g.shape:
+            raise ValueError(f"ssim: image {i}: prediction {tuple(p.shape)} and target {tuple(g.shape)} differ")
+        if image_sizes is not None:
+            h, w = (int(v) for v in image_sizes[i])
+        elif p.dim() == 3:
+            h, w = int(p.shape[0]), int(p.shape[1])
+        else:
+            raise ValueError(f"ssim: image {i} has shape {tuple(p.shape)}: give (h, w, 3) images or image_sizes")
+        if p.numel() != h * w * 3 or p.shape[-1] != 3:
+            raise ValueError(f"ssim: image {i} of shape {tuple(p.shape)} is not an ({h}, {w}, 3) image")
+        if g.device != p.device or (ps and p.device != ps[0].device):
+            raise ValueError("ssim: images on different devices")
+        ps.append(p)
+        gs.append(g)
+        hs.append(h)
+        ws.append(w)
+    n = len(ps)
+    if n == 0:
+        return torch.empty(0, dtype=torch.float32, device="cuda")
+    hh, wh = (C.c_int * n)(*hs), (C.c_int * n)(*ws)
+    nbytes = int(lib.aon_ssim_workspace_bytes(n, hh, wh))
+    if nbytes < 0:
+        check(nbytes, "aon_ssim_workspace_bytes")
+    dev = ps[0].device
+    ws_t = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.aon_ssim(n, _ptr_array(ps), _ptr_array(gs), hh, wh, _ptr(ws_t), nbytes, _ptr(out), _stream()), "aon_ssim")
+    return out

@@ -77,7 +77,7 @@ def main():
     # test split: 19 poses on the spheric path, articulation code i of the 19-row interpolated table (code_library.py:41-71)
     outs = [lit.test_step(collate(test[i], dev), i) for i in range(len(test))]
     psnr, psnr_obj = lit.test_epoch_end(outs, test.image_sizes, out_dir=os.path.join(args.exp_dir, "render"))
-    print(json.dumps({"test_psnr": psnr["test"], "test_psnr_obj": psnr_obj["test"], "images": len(outs)}))
+    print(json.dumps({"test_psnr": psnr["test"], "test_ssim": lit.logged["test/ssim"][-1], "test_psnr_obj": psnr_obj["test"], "images": len(outs)}))
     return log, psnr
 
 

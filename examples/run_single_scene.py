@@ -74,7 +74,7 @@ def main():
     save_checkpoint(os.path.join(args.exp_dir, "last.ckpt"), lit, opt, epoch=0)
     outs = [lit.test_step({k: v.unsqueeze(0) for k, v in test[i].items()}, i) for i in range(len(test))]
     psnr, psnr_obj = lit.test_epoch_end(outs, test.image_sizes, out_dir=os.path.join(args.exp_dir, "render"))
-    print(json.dumps({"test_psnr": psnr["test"], "test_psnr_obj": psnr_obj["test"], "ckpt": os.path.join(args.exp_dir, "last.ckpt")}))
+    print(json.dumps({"test_psnr": psnr["test"], "test_ssim": lit.logged["test/ssim"][-1], "test_psnr_obj": psnr_obj["test"], "ckpt": os.path.join(args.exp_dir, "last.ckpt")}))
     return log, psnr
 
 

@@ -24,7 +24,8 @@ extern "C" {
 #endif
 
 #define AON_ABI_VERSION 5   /* 5: + aon_adam_step, aon_code_library_fwd / _bwd, aon_art_pack_step, aon_vanilla_pack_step, aon_stream_form, aon_declare_stream_form; a packed pointer this process never
-                               packed or declared is refused (AON_E_INVALID / HIP "invalid value") instead of being taken to have the default form */
+                               packed or declared is refused (AON_E_INVALID / HIP "invalid value") instead of being taken to have the default form;
+                               later additions that change no existing call, so the version stays: aon_ssim, aon_ssim_workspace_bytes */
 
 #define AON_OK 0
 #define AON_E_INVALID (-1)    /* null pointer, negative size, unsupported geometry */
@@ -79,6 +80,17 @@ int aon_code_library_fwd(const float* const* tables_host, const int64_t* const* 
                          void* stream);
 int aon_code_library_bwd(const float* const* g_rows_host, const int64_t* const* ids_host, const int* rows_host, const int* dims_host, float* const* g_tables_host,
                          void* stream);
+
+/* ---- test-epoch SSIM: LitModel.ssim_each (models/interface.py:102-111), piqa's SSIM() with its defaults ----
+ * out[i] (one fp32 per image, device) = the SSIM of preds_host[i] against gts_host[i], each an (h_host[i], w_host[i], 3) HWC fp32 image clipped
+ * to [0,1] on load: 11-tap Gaussian window with sigma 1.5, no padding ((h-10) x (w-10) map per channel), c1 = 0.01^2, c2 = 0.03^2, the mean of the
+ * map over its pixels and the 3 channels.  Window statistics in fp64, reduced in a fixed order without atomics: the same bits on every run and
+ * whether an image is sent alone or in a batch.  All images of one call in two launches per 32 images.  preds_host / gts_host / h_host / w_host:
+ * HOST arrays of n_images entries (device pointers to the images); 11 <= h, w <= 32768; n_images == 0 is a no-op.
+ * workspace: device scratch of at least aon_ssim_workspace_bytes(n_images, h_host, w_host) bytes, 8-byte aligned (fp64 partials). */
+int64_t aon_ssim_workspace_bytes(int n_images, const int* h_host, const int* w_host);
+int aon_ssim(int n_images, const float* const* preds_host, const float* const* gts_host, const int* h_host, const int* w_host, void* workspace,
+             int64_t workspace_bytes, float* out, void* stream);
 
 /* Everything a training step of a TWO-level articulated model packs, in one call (round 6): aon_pack_art_mlp_deg + aon_art_prepare_deg +
  * aon_pack_art_mlp_bwd_deg for the coarse and the fine network -- every element computed by the same code on the same operands, the same

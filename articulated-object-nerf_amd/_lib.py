@@ -85,6 +85,11 @@ _SIGS = {
     "aon_code_library_bwd": (_i, [_p, _p, _p, _p, _p, _p]),
     "aon_ssim_workspace_bytes": (_l, [_i, _p, _p]),
     "aon_ssim": (_i, [_i, _p, _p, _p, _p, _p, _l, _p, _p]),
+    "aon_density_grid": (_i, [_p, _p, _p, _p, _l, _l, _i, _p, _p]),
+    "aon_art_density_grid": (_i, [_p, _p, _p, _p, _p, _l, _l, _i, _p, _p]),
+    "aon_marching_cubes_workspace_bytes": (_l, [_p]),
+    "aon_marching_cubes_count": (_i, [_p, _p, _f, _p, _l, _p, _p]),
+    "aon_marching_cubes": (_i, [_p, _p, _f, _p, _p, _p, _l, _p, _l, _p, _l, _p]),
     "aon_art_pack_step": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "aon_vanilla_pack_step": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
     "aon_set_bwd_early_heads": (_i, [_i]),

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "aon_fold.h"
@@ -89,6 +90,14 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, 
 hipError_t launch_code_library(bool backward, const float* const* src, const int64_t* const* idx, const int* rows, const int* dim, float* const* dst, hipStream_t stream);
 int64_t ssim_workspace_bytes(int n, const int* h, const int* w);
 hipError_t launch_ssim(int n, const float* const* x, const float* const* y, const int* h, const int* w, double* part, float* out, hipStream_t stream);
+hipError_t launch_density_grid(const char* packed, const int64_t* dims, const float* lo, const float* step, int64_t g_begin, int64_t g_end,
+                               int act, float* out, hipStream_t stream);
+hipError_t launch_art_density_grid(const char* packed, const float* small, const int64_t* dims, const float* lo, const float* step,
+                                   int64_t g_begin, int64_t g_end, int act, float* out, hipStream_t stream);
+int64_t mc_workspace_bytes(const int64_t* dims);
+hipError_t launch_mc_count(const float* grid, const int64_t* dims, float level, void* ws, hipStream_t stream, int64_t* counts2_host);
+hipError_t launch_mc(const float* grid, const int64_t* dims, float level, const float* lo, const float* step, void* ws, float* verts, int64_t vcap,
+                     int* faces, int64_t fcap, hipStream_t stream);
 hipError_t launch_raygen(const float* c2w, int H, int W, float focal, const float* directions, int64_t pix_begin,
                          int64_t pix_end, float* rays_o, float* viewdirs, float* rays_d, hipStream_t stream);
 hipError_t launch_ray_directions(int H, int W, float focal, float* out, hipStream_t stream);
@@ -743,6 +752,70 @@ int aon_ssim(int n_images, const float* const* preds_host, const float* const* g
   if (const char* msg = ssim_sizes_ok(n_images, h_host, w_host)) return fail(AON_E_INVALID, msg);
   if (workspace_bytes < aon::ssim_workspace_bytes(n_images, h_host, w_host)) return fail(AON_E_WORKSPACE, "aon_ssim: workspace too small");
   return check(aon::launch_ssim(n_images, preds_host, gts_host, h_host, w_host, static_cast<double*>(workspace), out, (hipStream_t)stream), "aon_ssim");
+}
+
+// ---- mesh extraction: density on a grid (aon_mlp.hip, aon_mlp_art.hip) and marching cubes (aon_mesh.hip) ----
+static const char* grid_args_bad(const int64_t* dims3_host, const float* lo3_host, const float* step3_host, int64_t g_begin, int64_t g_end, int act) {
+  if (!dims3_host || !lo3_host || !step3_host) return "null grid argument";
+  for (int a = 0; a < 3; ++a)
+    if (dims3_host[a] < 1 || dims3_host[a] > (int64_t)1 << 24) return "every grid dimension must be in [1, 2^24] (its indices are exact in fp32)";
+  if (dims3_host[0] > INT64_MAX / dims3_host[1] / dims3_host[2]) return "grid too large";
+  const int64_t P = dims3_host[0] * dims3_host[1] * dims3_host[2];
+  if (g_begin < 0 || g_end < g_begin || g_end > P) return "need 0 <= g_begin <= g_end <= nx * ny * nz";
+  if (g_end - g_begin > (int64_t)INT32_MAX * 64) return "too many points for one call";
+  if (act < 0 || act > 2) return "act must be 0 (raw), 1 (relu) or 2 (softplus(raw - 1))";
+  return nullptr;
+}
+int aon_density_grid(const void* packed, const int64_t* dims3_host, const float* lo3_host, const float* step3_host, int64_t g_begin, int64_t g_end,
+                     int act, float* out, void* stream) {
+  if (const char* msg = grid_args_bad(dims3_host, lo3_host, step3_host, g_begin, g_end, act)) return fail(AON_E_INVALID, (std::string("aon_density_grid: ") + msg).c_str());
+  if (g_end == g_begin) return AON_OK;
+  if (!packed || !out) return fail(AON_E_INVALID, "aon_density_grid: null pointer");
+  return check(aon::launch_density_grid(static_cast<const char*>(packed), dims3_host, lo3_host, step3_host, g_begin, g_end, act, out, (hipStream_t)stream),
+               "aon_density_grid");
+}
+int aon_art_density_grid(const void* packed, const void* small, const int64_t* dims3_host, const float* lo3_host, const float* step3_host, int64_t g_begin,
+                         int64_t g_end, int act, float* out, void* stream) {
+  if (const char* msg = grid_args_bad(dims3_host, lo3_host, step3_host, g_begin, g_end, act)) return fail(AON_E_INVALID, (std::string("aon_art_density_grid: ") + msg).c_str());
+  if (g_end == g_begin) return AON_OK;
+  if (!packed || !small || !out) return fail(AON_E_INVALID, "aon_art_density_grid: null pointer");
+  if (forms_differ(packed, small)) return fail(AON_E_INVALID, kFormsMsg);
+  return check(aon::launch_art_density_grid(static_cast<const char*>(packed), static_cast<const float*>(small), dims3_host, lo3_host, step3_host, g_begin,
+                                            g_end, act, out, (hipStream_t)stream), "aon_art_density_grid");
+}
+static const char* mc_dims_bad(const int64_t* dims3_host) {
+  if (!dims3_host) return "null dims";
+  for (int a = 0; a < 3; ++a)
+    if (dims3_host[a] < 2 || dims3_host[a] > (int64_t)1 << 24) return "every grid dimension must be in [2, 2^24]";
+  if (dims3_host[0] > ((int64_t)1 << 40) / dims3_host[1] / dims3_host[2]) return "grid too large (more than 2^40 points)";
+  return nullptr;
+}
+int64_t aon_marching_cubes_workspace_bytes(const int64_t* dims3_host) {
+  if (const char* msg = mc_dims_bad(dims3_host)) return fail(AON_E_INVALID, (std::string("aon_marching_cubes_workspace_bytes: ") + msg).c_str());
+  return aon::mc_workspace_bytes(dims3_host);
+}
+int aon_marching_cubes_count(const float* grid, const int64_t* dims3_host, float level, void* workspace, int64_t workspace_bytes, int64_t* counts2_host,
+                             void* stream) {
+  if (const char* msg = mc_dims_bad(dims3_host)) return fail(AON_E_INVALID, (std::string("aon_marching_cubes_count: ") + msg).c_str());
+  if (!grid || !workspace || !counts2_host) return fail(AON_E_INVALID, "aon_marching_cubes_count: null pointer");
+  if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(AON_E_INVALID, "aon_marching_cubes_count: workspace is not 16-byte aligned");
+  if (workspace_bytes < aon::mc_workspace_bytes(dims3_host)) return fail(AON_E_WORKSPACE, "aon_marching_cubes_count: workspace too small");
+  if (int rc = check(aon::launch_mc_count(grid, dims3_host, level, workspace, (hipStream_t)stream, counts2_host), "aon_marching_cubes_count"); rc != AON_OK)
+    return rc;
+  if (counts2_host[0] > INT32_MAX)
+    return fail(AON_E_INVALID, "aon_marching_cubes_count: more than 2^31 - 1 vertices (faces hold int32 vertex ids): use a coarser grid");
+  return AON_OK;
+}
+int aon_marching_cubes(const float* grid, const int64_t* dims3_host, float level, const float* lo3_host, const float* step3_host, void* workspace,
+                       int64_t workspace_bytes, float* verts, int64_t n_verts, int32_t* faces, int64_t n_faces, void* stream) {
+  if (const char* msg = mc_dims_bad(dims3_host)) return fail(AON_E_INVALID, (std::string("aon_marching_cubes: ") + msg).c_str());
+  if (!grid || !workspace || !lo3_host || !step3_host) return fail(AON_E_INVALID, "aon_marching_cubes: null pointer");
+  if (n_verts < 0 || n_faces < 0 || n_verts > INT32_MAX) return fail(AON_E_INVALID, "aon_marching_cubes: bad output size");
+  if ((n_verts > 0 && !verts) || (n_faces > 0 && !faces)) return fail(AON_E_INVALID, "aon_marching_cubes: null output");
+  if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(AON_E_INVALID, "aon_marching_cubes: workspace is not 16-byte aligned");
+  if (workspace_bytes < aon::mc_workspace_bytes(dims3_host)) return fail(AON_E_WORKSPACE, "aon_marching_cubes: workspace too small");
+  return check(aon::launch_mc(grid, dims3_host, level, lo3_host, step3_host, workspace, verts, n_verts, faces, n_faces, (hipStream_t)stream),
+               "aon_marching_cubes");
 }
 
 int aon_profile_begin(void) {

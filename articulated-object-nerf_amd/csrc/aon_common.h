@@ -64,6 +64,28 @@ __device__ __forceinline__ float cos_f32(float x) {
   return ((q + 1) & 2) ? -res : res;
 }
 
+// torch Softplus(beta=1, threshold=20): x > 20 ? x : log1p(exp(x)), written as max(x, 0) + log1p(z), z = exp(-|x|) in (0, 1]
+// (above 20 the second term is below half an ulp of x: the threshold needs no branch).  log1p(z) = z * P(z) with P the degree-10
+// Chebyshev interpolant of log1p(z)/z on [0, 1] (1.1e-7 relative in fp32 Horner form, tests/diag/diag_sigmoid.py checks the
+// function on the device); z straight from the transcendental unit.  ~20 instructions against ~70 with the library expf and
+// log1pf, which had the articulated compositing at twice the vanilla kernel's instruction count.  NaN stays NaN (through z),
+// +inf -> +inf, -inf -> 0.
+__device__ __forceinline__ float softplus_f32(float x) {
+  const float z = __builtin_amdgcn_exp2f(__fmul_rn(__builtin_fabsf(x), -1.44269502162933349609375f));
+  float p = 0.001986696617677808f;
+  p = __builtin_fmaf(p, z, -0.013187826611101627f);
+  p = __builtin_fmaf(p, z, 0.041006576269865036f);
+  p = __builtin_fmaf(p, z, -0.08188041299581528f);
+  p = __builtin_fmaf(p, z, 0.12377995997667313f);
+  p = __builtin_fmaf(p, z, -0.16087622940540314f);
+  p = __builtin_fmaf(p, z, 0.19885820150375366f);
+  p = __builtin_fmaf(p, z, -0.24986496567726135f);
+  p = __builtin_fmaf(p, z, 0.33332496881484985f);
+  p = __builtin_fmaf(p, z, -0.4999997913837433f);
+  p = __builtin_fmaf(p, z, 1.0f);
+  return __fadd_rn(__builtin_fmaxf(x, 0.f), __fmul_rn(z, p));
+}
+
 // ------------------------------------------------------------------------------------------------
 // Packed-weight stream of one vanilla NeRFMLP (models/vanilla_nerf/model.py:39-120).
 //

@@ -541,4 +541,81 @@ hipError_t launch_mlp_fwd_enc(const char* packed, const float* samples_enc, cons
   return launch_mlp_t<false, false>(args, stream);
 }
 
+// ---------------------------------------------------------------------------------------------
+// density on a grid (aon_density_grid, mesh extraction)
+// ---------------------------------------------------------------------------------------------
+// The stream truncated after layer 7: chunks 0 .. 59, which the literal and the folded forms share (aon_common.h).  The prefetch of the
+// next pass's first pair wraps at chunk 58 here (first_wrapping_chunk), not at the end of the view branch.
+struct VanillaTrunkNet {
+  static constexpr int kSlotBytes = kPairSlotBytes;
+  static constexpr bool kPair = true;
+  static constexpr int kNumChunks = kChBott;
+  static constexpr int chunk_bytes(int) { return kBigChunkBytes; }
+};
+
+// (GridArgs, grid_point, grid_activation, grid_store: aon_mlp_core.h)
+
+// encode -> trunk -> density head of mlp_fwd_kernel, the same operations in the same order (the same bits as its raw sigma), on points
+// generated from the grid; no view encoding, view branch or rgb head.  One wave = 32 grid points, as there.
+__global__ void __launch_bounds__(256) density_grid_kernel(GridArgs args) {
+  using Net = VanillaTrunkNet;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* sm = reinterpret_cast<float*>(smem + kRingBytes);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int m = lane & 31, h = lane >> 5;
+  {
+    const f32x4* src = reinterpret_cast<const f32x4*>(args.packed + kStreamBytes);
+    f32x4* dst = reinterpret_cast<f32x4*>(sm);
+    for (int i = tid; i < kSmallFloats / 4; i += 256) dst[i] = src[i];
+  }
+  Pipe p;
+  pipe_init<Net>(p, args.packed, smem, wave, lane);  // also publishes the small block
+  for (int pass = blockIdx.x; pass < args.npass; pass += gridDim.x) {
+    const int64_t l0 = (int64_t)pass * 128 + wave * 32;
+    const int64_t l = l0 + m;
+    float x[3];
+    grid_point(args, l < args.total ? l : args.total - 1, x);
+    f32x16 E[2];
+    encode_pos(x, h, E);
+    f32x16 X[8], Y[8];
+    init_bias(X, sm + kSmBias + 0 * 256, h);
+    chunk_mma<Net, kChL0 + 0, 8, 16>(p, E[0], X);
+    chunk_mma<Net, kChL0 + 1, 8, 16>(p, E[1], X);
+    relu_tiles(X);
+    init_bias(Y, sm + kSmBias + 1 * 256, h); dense_layer<Net, kChL1 + 0, 8, 8>(p, X, Y); relu_tiles(Y);
+    init_bias(X, sm + kSmBias + 2 * 256, h); dense_layer<Net, kChL1 + 8, 8, 8>(p, Y, X); relu_tiles(X);
+    init_bias(Y, sm + kSmBias + 3 * 256, h); dense_layer<Net, kChL1 + 16, 8, 8>(p, X, Y); relu_tiles(Y);
+    init_bias(X, sm + kSmBias + 4 * 256, h); dense_layer<Net, kChL1 + 24, 8, 8>(p, Y, X); relu_tiles(X);
+    init_bias(Y, sm + kSmBias + 5 * 256, h);
+    dense_layer<Net, kChL5, 8, 8>(p, X, Y);
+    chunk_mma<Net, kChL5 + 8, 8, 16>(p, E[0], Y);
+    chunk_mma<Net, kChL5 + 9, 8, 16>(p, E[1], Y);
+    relu_tiles(Y);
+    init_bias(X, sm + kSmBias + 6 * 256, h); dense_layer<Net, kChL6, 8, 8>(p, Y, X); relu_tiles(X);
+    init_bias(Y, sm + kSmBias + 7 * 256, h); dense_layer<Net, kChL7, 8, 8>(p, X, Y); relu_tiles(Y);
+    float sigma = head_partial<8>(Y, sm + kSmWSigma, h);
+    sigma = sigma + __shfl_xor(sigma, 32) + sm[kSmBSigma];
+    grid_store(args.out, l0, args.total, lane, grid_activation(sigma, args.act));
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last prefetched chunk must land before the LDS is released
+}
+
+hipError_t launch_density_grid(const char* packed, const int64_t* dims, const float* lo, const float* step, int64_t g_begin, int64_t g_end,
+                               int act, float* out, hipStream_t stream) {
+  if (stream_form(packed) == kFormUnknown) return hipErrorInvalidValue;   // never packed / declared (mlp_fwd refuses it too)
+  GridArgs a{};
+  a.packed = packed; a.ny = dims[1]; a.nz = dims[2]; a.g_begin = g_begin; a.total = g_end - g_begin;
+  for (int i = 0; i < 3; ++i) { a.lo[i] = lo[i]; a.step[i] = step[i]; }
+  a.act = act; a.out = out; a.npass = (int)((a.total + 127) / 128);
+  static DeviceOnce lds_once;
+  if (hipError_t e = set_max_lds(&density_grid_kernel, kLdsBytes, lds_once); e != hipSuccess) return e;
+  const int cus = num_cus();
+  if (cus <= 0) return hipErrorInvalidDevice;
+  const int grid = a.npass < cus ? a.npass : cus;
+  if (grid <= 0) return hipSuccess;
+  density_grid_kernel<<<dim3(grid), dim3(256), kLdsBytes, stream>>>(a);
+  return hipGetLastError();
+}
+
 }  // namespace aon

@@ -589,6 +589,106 @@ hipError_t launch_art_mlp_fwd_pos(const char* packed, const float* small, const 
   return launch_art_t<false, false>(args, stream);
 }
 
+// ---- density on a grid (aon_art_density_grid): deformation MLP -> encoding of x' -> trunk -> density head ----
+// The stream truncated after layer 7: chunks 0 .. 71, which the literal and the folded forms share (aon_art_common.h); the prefetch of the
+// next pass's first pair wraps at chunk 70.
+struct ArtTrunkNet {
+  static constexpr int kSlotBytes = kPairSlotBytes;
+  static constexpr bool kPair = true;
+  static constexpr int kNumChunks = kAChBott;
+  static constexpr int chunk_bytes(int c) { return c < kAChT0 ? kSmallChunkBytes : kBigChunkBytes; }
+};
+
+// art_mlp_fwd_kernel's operations up to its raw sigma, in the same order (the same bits), on points generated from the grid (grid_point)
+__global__ void __launch_bounds__(256) art_density_grid_kernel(GridArgs args) {
+  using Net = ArtTrunkNet;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* sm = reinterpret_cast<float*>(smem + kRingBytes);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int m = lane & 31, h = lane >> 5;
+  {
+    const f32x4* src = reinterpret_cast<const f32x4*>(args.small);
+    f32x4* dst = reinterpret_cast<f32x4*>(sm);
+    for (int i = tid; i < kASmallFloats / 4; i += 256) dst[i] = src[i];
+  }
+  Pipe p;
+  pipe_init<Net>(p, args.packed, smem, wave, lane);  // also publishes the small block
+  for (int pass = blockIdx.x; pass < args.npass; pass += gridDim.x) {
+    const int64_t l0 = (int64_t)pass * 128 + wave * 32;
+    const int64_t l = l0 + m;
+    float x[3];
+    grid_point(args, l < args.total ? l : args.total - 1, x);
+    // deformation MLP (model_autodecoder.py:196-205)
+    f32x16 H0[4], H1[4];
+    init_bias(H0, sm + kA_BD0, h);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+          const f32x4 w = *reinterpret_cast<const f32x4*>(sm + kA_WD0 + a * 128 + 32 * t + 8 * gq + 4 * h);
+#pragma unroll
+          for (int cc = 0; cc < 4; ++cc) H0[t][4 * gq + cc] = __builtin_fmaf(w[cc], x[a], H0[t][4 * gq + cc]);
+        }
+      }
+    }
+    relu_tiles(H0);
+    init_bias(H1, sm + kA_BD + 0 * 128, h); dense_layer<Net, kAChD1 + 0, 4, 4>(p, H0, H1); relu_tiles(H1);
+    init_bias(H0, sm + kA_BD + 1 * 128, h); dense_layer<Net, kAChD1 + 4, 4, 4>(p, H1, H0); relu_tiles(H0);
+    init_bias(H1, sm + kA_BD + 2 * 128, h); dense_layer<Net, kAChD1 + 8, 4, 4>(p, H0, H1); relu_tiles(H1);
+    float xd[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {  // x' = deformation_layer(h) + pos   (:205)
+      float v = head_partial<4>(H1, sm + kA_WDL + a * 128, h);
+      v = v + __shfl_xor(v, 32) + sm[kA_BDL + a];
+      xd[a] = __fadd_rn(v, x[a]);
+    }
+    f32x16 E[2];
+    encode_pos_scaled(xd, h, sm + kA_ESC, E);
+    // trunk (:212-217) and density_layer (:219)
+    f32x16 X[8], Y[8];
+    init_bias(X, sm + kA_BT + 0 * 256, h);
+    chunk_mma<Net, kAChT0 + 0, 8, 16>(p, E[0], X);
+    chunk_mma<Net, kAChT0 + 1, 8, 16>(p, E[1], X);
+    relu_tiles(X);
+    init_bias(Y, sm + kA_BT + 1 * 256, h); dense_layer<Net, kAChT1 + 0, 8, 8>(p, X, Y); relu_tiles(Y);
+    init_bias(X, sm + kA_BT + 2 * 256, h); dense_layer<Net, kAChT1 + 8, 8, 8>(p, Y, X); relu_tiles(X);
+    init_bias(Y, sm + kA_BT + 3 * 256, h); dense_layer<Net, kAChT1 + 16, 8, 8>(p, X, Y); relu_tiles(Y);
+    init_bias(X, sm + kA_BT + 4 * 256, h); dense_layer<Net, kAChT1 + 24, 8, 8>(p, Y, X); relu_tiles(X);
+    init_bias(Y, sm + kA_BT + 5 * 256, h);
+    dense_layer<Net, kAChT5, 8, 8>(p, X, Y);
+    chunk_mma<Net, kAChT5 + 8, 8, 16>(p, E[0], Y);
+    chunk_mma<Net, kAChT5 + 9, 8, 16>(p, E[1], Y);
+    relu_tiles(Y);
+    init_bias(X, sm + kA_BT + 6 * 256, h); dense_layer<Net, kAChT6, 8, 8>(p, Y, X); relu_tiles(X);
+    init_bias(Y, sm + kA_BT + 7 * 256, h); dense_layer<Net, kAChT7, 8, 8>(p, X, Y); relu_tiles(Y);
+    float sigma = head_partial<8>(Y, sm + kA_WSIG, h);
+    sigma = sigma + __shfl_xor(sigma, 32) + sm[kA_BSIG];
+    grid_store(args.out, l0, args.total, lane, grid_activation(sigma, args.act));
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last prefetched chunk must land before the LDS is released
+}
+
+hipError_t launch_art_density_grid(const char* packed, const float* small, const int64_t* dims, const float* lo, const float* step,
+                                   int64_t g_begin, int64_t g_end, int act, float* out, hipStream_t stream) {
+  const int form = stream_form(packed);
+  if (form == kFormUnknown || stream_form(small) != form) return hipErrorInvalidValue;   // as launch_art_t
+  GridArgs a{};
+  a.packed = packed; a.small = small; a.ny = dims[1]; a.nz = dims[2]; a.g_begin = g_begin; a.total = g_end - g_begin;
+  for (int i = 0; i < 3; ++i) { a.lo[i] = lo[i]; a.step[i] = step[i]; }
+  a.act = act; a.out = out; a.npass = (int)((a.total + 127) / 128);
+  static DeviceOnce lds_once;
+  if (hipError_t e = set_max_lds(&art_density_grid_kernel, kALdsBytes, lds_once); e != hipSuccess) return e;
+  const int cus = num_cus();
+  if (cus <= 0) return hipErrorInvalidDevice;
+  const int grid = a.npass < cus ? a.npass : cus;
+  if (grid <= 0) return hipSuccess;
+  art_density_grid_kernel<<<dim3(grid), dim3(256), kALdsBytes, stream>>>(a);
+  return hipGetLastError();
+}
+
 int64_t art_stream_bytes() { return kAStreamBytes; }
 int64_t art_small_bytes() { return (int64_t)kASmallFloats * 4; }
 

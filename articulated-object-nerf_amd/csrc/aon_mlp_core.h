@@ -661,4 +661,53 @@ __device__ __forceinline__ int viewenc_col(int q, int cc, int h) {
   return -1;
 }
 
+// ---- density on a grid (density_grid_kernel, art_density_grid_kernel) ----
+struct GridArgs {
+  const char* packed;      // the network's forward stream (either form: the grid kernels read chunks both forms share)
+  const float* small;      // articulated: the per-call block (aon_art_prepare); vanilla: null (the small block follows the stream)
+  int64_t ny, nz;          // grid dimensions (nx only bounds g_end, checked by the caller)
+  int64_t g_begin, total;  // the call covers grid points g_begin .. g_begin + total - 1; out[l] <- point g_begin + l
+  float lo[3], step[3];
+  int act;
+  float* out;
+  int npass;               // ceil(total / 128)
+};
+
+// Point l of a call (0 <= l < total) is grid point g = g_begin + l, C order over (nx, ny, nz) with k fastest; its coordinates are
+// lo_a + idx_a * step_a, multiply then add, each rounded (a torch expression gives the same bits).
+__device__ __forceinline__ void grid_point(const GridArgs& a, int64_t l, float (&x)[3]) {
+  const int64_t g = a.g_begin + l;
+  const int64_t nyz = a.ny * a.nz;
+  const int64_t i = g / nyz, r = g - i * nyz;
+  const int64_t j = r / a.nz, k = r - j * a.nz;
+  x[0] = __fadd_rn(a.lo[0], __fmul_rn((float)i, a.step[0]));
+  x[1] = __fadd_rn(a.lo[1], __fmul_rn((float)j, a.step[1]));
+  x[2] = __fadd_rn(a.lo[2], __fmul_rn((float)k, a.step[2]));
+}
+
+// act 0: raw, 1: relu (model.py:187), 2: softplus(raw - 1) (model_autodecoder.py:318-323, the compositing kernels' act 2)
+__device__ __forceinline__ float grid_activation(float raw, int act) {
+  if (act == 1) return relu1(raw);
+  if (act == 2) return softplus_f32(__fadd_rn(raw, -1.0f));
+  return raw;
+}
+
+// every lane holds the value of its sample m (both half-waves): lanes 4q (q < 8) gather samples 4q .. 4q + 3 and store them as one 16-byte
+// word when the four are in range and `out` is 16-byte aligned, one float at a time otherwise (the ragged end of a call, an unaligned slab)
+__device__ __forceinline__ void grid_store(float* out, int64_t l0, int64_t total, int lane, float v) {
+  const int src = (lane & 7) * 4;
+  const float v0 = __shfl(v, src), v1 = __shfl(v, src + 1), v2 = __shfl(v, src + 2), v3 = __shfl(v, src + 3);
+  if (lane >= 8) return;
+  const int64_t l = l0 + src;
+  if (l + 3 < total && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
+    f32x4 o; o[0] = v0; o[1] = v1; o[2] = v2; o[3] = v3;
+    *reinterpret_cast<f32x4*>(out + l) = o;
+  } else {
+    if (l < total) out[l] = v0;
+    if (l + 1 < total) out[l + 1] = v1;
+    if (l + 2 < total) out[l + 2] = v2;
+    if (l + 3 < total) out[l + 3] = v3;
+  }
+}
+
 }  // namespace aon

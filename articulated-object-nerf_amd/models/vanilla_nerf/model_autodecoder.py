@@ -202,6 +202,24 @@ class NeRF_AE_Art(nn.Module):
                                   opts=self._opts, noise=noise)
         return [tuple(o) for o in outs]
 
+    def _level_mlp(self, level: str):
+        if level not in ("coarse", "fine"):
+            raise ValueError(f"level must be 'coarse' or 'fine', got {level!r}")
+        if level == "fine" and self.num_levels < 2:
+            raise ValueError("a one-level NeRF_AE_Art has no fine network")
+        return self.fine_mlp if level == "fine" else self.coarse_mlp
+
+    @torch.no_grad()
+    def density_grid(self, bounds, resolution, latents: dict, level: str = "fine") -> torch.Tensor:
+        """softplus(raw - 1) density (model_autodecoder.py:318-323) of the `level` network under `latents` (the code library's "density",
+        "color", "articulation" rows) at the points of a grid spanning bounds = (lo, hi) with `resolution` points per axis -> (nx, ny, nz)
+        fp32, C order (ops.grid_points).  One fused launch at every encoding degree set (ops.density_grid)."""
+        if float(self.density_bias) != -1.0:
+            raise NotImplementedError("the grid kernel's articulated activation is softplus(raw - 1): density_bias must be -1.0")
+        mlp = self._level_mlp(level)
+        lo, hi = bounds
+        return ops.density_grid(mlp.packed(), ops._dims3(resolution), lo, hi, ops.ACT_ARTICULATED, small=mlp.prepared(latents))
+
 
 # --------------------------------------------------------------------------------------------------------------------
 from collections import defaultdict  # noqa: E402
@@ -289,3 +307,18 @@ class LitNeRF_AutoDecoder(Harness):
 
     def configure_optimizers(self):
         return build_adam([self.model, self.code_library], self.lr_init)   # (model_autodecoder.py:604-606; one arena, one launch: LitNeRF)
+
+    @torch.no_grad()
+    def extract_meshes(self, instance_id: int = 0, resolution: int = 256, bounds=(-1.0, 1.0), threshold: float | None = None, level: str = "fine",
+                       color: bool = False) -> list:
+        """One mesh per articulation state of the test epoch: the 19 rows of get_interpolated_articulations (the 10 learned codes and the
+        mid-points of neighbours) with the shape / appearance codes of `instance_id` (mesh.extract_mesh for the arguments)."""
+        from ...mesh import extract_mesh
+
+        dev = next(self.model.parameters()).device
+        iid = torch.tensor([int(instance_id)], dtype=torch.int64, device=dev)
+        shape = self.code_library.embedding_instance_shape(iid)
+        app = self.code_library.embedding_instance_appearance(iid)
+        table = self.code_library.get_interpolated_articulations(max_interpolations=2, device=dev)
+        return [extract_mesh(self.model, bounds, resolution, threshold=threshold, level=level, color=color,
+                             latents={"density": shape, "color": app, "articulation": table[a: a + 1]}) for a in range(table.shape[0])]

@@ -1443,3 +1443,105 @@ def ssim(preds, gts, image_sizes=None) -> torch.Tensor:
     with torch.cuda.device(dev):
         check(lib.aon_ssim(n, _ptr_array(ps), _ptr_array(gs), hh, wh, _ptr(ws_t), nbytes, _ptr(out), _stream()), "aon_ssim")
     return out
+
+
+# ------------------------------------------------------------------ mesh extraction
+def _vec3(v, name: str) -> list:
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().tolist()
+    if isinstance(v, (int, float)):
+        v = [v, v, v]
+    v = [float(x) for x in v]
+    if len(v) != 3:
+        raise ValueError(f"{name}: expected a number or 3 numbers, got {v}")
+    return v
+
+
+def _dims3(dims, name: str = "dims") -> list:
+    if isinstance(dims, int):
+        dims = (dims, dims, dims)
+    dims = [int(d) for d in dims]
+    if len(dims) != 3:
+        raise ValueError(f"{name}: expected an int or 3 ints, got {dims}")
+    return dims
+
+
+def grid_step(dims, lo, hi):
+    """fp32 (lo, step) of an (nx, ny, nz) grid spanning [lo, hi] per axis: step = (hi - lo) / (n - 1) in fp32 (0 for n == 1).  Point
+    (i, j, k) lies at lo + idx * step, multiply then add, each rounded to fp32 (grid_points builds the same values)."""
+    dims, lo, hi = _dims3(dims), _vec3(lo, "lo"), _vec3(hi, "hi")
+    lo32 = torch.tensor(lo, dtype=torch.float32)
+    hi32 = torch.tensor(hi, dtype=torch.float32)
+    den = torch.tensor([max(n - 1, 1) for n in dims], dtype=torch.float32)
+    step = (hi32 - lo32) / den
+    step = torch.where(torch.tensor([n > 1 for n in dims]), step, torch.zeros_like(step))
+    return lo32, step
+
+
+def grid_points(dims, lo, hi, g_begin: int = 0, g_end: int | None = None, device="cuda") -> torch.Tensor:
+    """(g_end - g_begin, 3) fp32 coordinates of grid points g_begin .. g_end - 1 (C order, k fastest), the values the grid kernels use."""
+    dims = _dims3(dims)
+    lo32, step = grid_step(dims, lo, hi)
+    P = dims[0] * dims[1] * dims[2]
+    g_end = P if g_end is None else int(g_end)
+    g = torch.arange(int(g_begin), g_end, dtype=torch.int64, device=device)
+    idx = torch.stack([g // (dims[1] * dims[2]), (g // dims[2]) % dims[1], g % dims[2]], -1).to(torch.float32)
+    return lo32.to(device) + idx * step.to(device)
+
+
+def density_grid(packed, dims, lo, hi, act: int = ACT_NONE, small=None, g_begin: int = 0, g_end: int | None = None, out=None) -> torch.Tensor:
+    """Density of a packed network at the points of an (nx, ny, nz) grid spanning [lo, hi] (grid_points), one fused launch: the trunk of
+    mlp_fwd / art_mlp_fwd_pos and the density head, nothing of the view branch.  act 0: raw, 1: relu (vanilla), 2: softplus(raw - 1)
+    (articulated).  `small` (art_prepare's per-call block) selects the articulated network.  Vanilla streams must be packed at the default
+    degrees (0, 10, 4); NeRF.density_grid routes other geometries to the per-point path.  Returns (nx, ny, nz) for the whole grid, else the
+    (g_end - g_begin,) points of the slab (written into `out` when given)."""
+    dims = _dims3(dims)
+    lo32, step = grid_step(dims, lo, hi)
+    P = dims[0] * dims[1] * dims[2]
+    whole = g_begin == 0 and (g_end is None or g_end == P)
+    g_end = P if g_end is None else int(g_end)
+    n = g_end - int(g_begin)
+    if not isinstance(packed, torch.Tensor) or not packed.is_cuda:
+        raise RuntimeError("density_grid: packed must be a cuda tensor of ops.pack_vanilla_mlp / ops.pack_art_mlp")
+    dev = packed.device
+    if out is None:
+        out = torch.empty(max(n, 0), dtype=torch.float32, device=dev)
+    else:
+        out = _f32(out, "out")
+        if out.numel() != n:
+            raise ValueError(f"density_grid: out holds {out.numel()} values for {n} points")
+    d = (C.c_int64 * 3)(*dims)
+    lo_h, st_h = (C.c_float * 3)(*lo32.tolist()), (C.c_float * 3)(*step.tolist())
+    with torch.cuda.device(dev):
+        if small is None:
+            check(lib.aon_density_grid(_pk(packed), d, lo_h, st_h, int(g_begin), g_end, int(act), _ptr(out), _stream()), "aon_density_grid")
+        else:
+            check(lib.aon_art_density_grid(_pk(packed), _pk(small), d, lo_h, st_h, int(g_begin), g_end, int(act), _ptr(out), _stream()),
+                  "aon_art_density_grid")
+    return out.view(*dims) if whole else out
+
+
+def marching_cubes(grid, level: float, lo, hi):
+    """Marching cubes on an (nx, ny, nz) fp32 cuda grid spanning [lo, hi] (grid_points' coordinates) -> (verts (V, 3) fp32, faces (F, 3) int32).
+    Inside is value > level; vertices shared and ordered by (owning grid point, axis), faces by (cell, table order), normals from high values
+    to low; the same bits on every call (include/aon_hip.h)."""
+    g = _f32(grid, "grid")
+    if g.dim() != 3:
+        raise ValueError(f"marching_cubes: expected an (nx, ny, nz) grid, got shape {tuple(g.shape)}")
+    dims = list(g.shape)
+    lo32, step = grid_step(dims, lo, hi)
+    d = (C.c_int64 * 3)(*dims)
+    nbytes = int(lib.aon_marching_cubes_workspace_bytes(d))
+    if nbytes < 0:
+        check(nbytes, "aon_marching_cubes_workspace_bytes")
+    dev = g.device
+    ws = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.float32, device=dev)
+    counts = (C.c_int64 * 2)()
+    with torch.cuda.device(dev):
+        check(lib.aon_marching_cubes_count(_ptr(g), d, C.c_float(level), _ptr(ws), nbytes, counts, _stream()), "aon_marching_cubes_count")
+        V, F = int(counts[0]), int(counts[1])
+        verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+        check(lib.aon_marching_cubes(_ptr(g), d, C.c_float(level), (C.c_float * 3)(*lo32.tolist()), (C.c_float * 3)(*step.tolist()), _ptr(ws),
+                                     nbytes, _ptr(verts), V, _ptr(faces), F, _stream()), "aon_marching_cubes")
+    return verts, faces

@@ -25,7 +25,8 @@ extern "C" {
 
 #define AON_ABI_VERSION 5   /* 5: + aon_adam_step, aon_code_library_fwd / _bwd, aon_art_pack_step, aon_vanilla_pack_step, aon_stream_form, aon_declare_stream_form; a packed pointer this process never
                                packed or declared is refused (AON_E_INVALID / HIP "invalid value") instead of being taken to have the default form;
-                               later additions that change no existing call, so the version stays: aon_ssim, aon_ssim_workspace_bytes */
+                               later additions that change no existing call, so the version stays: aon_ssim, aon_ssim_workspace_bytes,
+                               aon_density_grid, aon_art_density_grid, aon_marching_cubes_workspace_bytes, aon_marching_cubes_count, aon_marching_cubes */
 
 #define AON_OK 0
 #define AON_E_INVALID (-1)    /* null pointer, negative size, unsupported geometry */
@@ -91,6 +92,30 @@ int aon_code_library_bwd(const float* const* g_rows_host, const int64_t* const* 
 int64_t aon_ssim_workspace_bytes(int n_images, const int* h_host, const int* w_host);
 int aon_ssim(int n_images, const float* const* preds_host, const float* const* gts_host, const int* h_host, const int* w_host, void* workspace,
              int64_t workspace_bytes, float* out, void* stream);
+
+/* ---- mesh extraction: density on a grid and marching cubes ----
+ * aon_density_grid / aon_art_density_grid: out[l] (fp32, device) = the density of grid point g = g_begin + l for g_begin <= g < g_end, where point
+ * (i, j, k) of an (nx, ny, nz) grid (dims3_host) has g = (i ny + j) nz + k and coordinates x_a = lo_a + idx_a step_a (fp32 multiply, then fp32 add,
+ * no FMA; lo3_host / step3_host: host arrays).  The network runs as in aon_mlp_fwd / aon_art_mlp_fwd_pos up to the density head -- the same bits
+ * as their raw sigma -- and stops there (no view branch).  act 0: raw, 1: relu(raw), 2: softplus(raw - 1) (the compositing kernels' act 2).
+ * packed: a forward stream of either form (aon_pack_vanilla_mlp at the default degrees 0, 10, 4: the kernel encodes with those scales;
+ * aon_pack_art_mlp[_deg] + aon_art_prepare[_deg] for the articulated one).  Stores are 16-byte words where `out` is 16-byte aligned. */
+int aon_density_grid(const void* packed, const int64_t* dims3_host, const float* lo3_host, const float* step3_host, int64_t g_begin, int64_t g_end,
+                     int act, float* out, void* stream);
+int aon_art_density_grid(const void* packed, const void* small, const int64_t* dims3_host, const float* lo3_host, const float* step3_host, int64_t g_begin,
+                         int64_t g_end, int act, float* out, void* stream);
+/* Marching cubes on an (nx, ny, nz) fp32 grid (C order, device), every dimension >= 2: a point is inside iff value > level (NaN: outside); vertices
+ * on the grid edges with exactly one inside endpoint, shared, ordered by (owning point's linear index, axis x < y < z); faces (int32 vertex ids)
+ * from the classic 256-case table, ordered by (cell, table order), normals from high values to low.  No atomics: the same bits on every run.
+ * aon_marching_cubes_count writes (V, F) to counts2_host and synchronises `stream`; aon_marching_cubes writes verts (V, 3) and faces (F, 3) --
+ * n_verts / n_faces are the capacities of the two buffers; it recomputes the classification, so it needs only the same grid and level.
+ * workspace: device scratch of aon_marching_cubes_workspace_bytes(dims3_host) bytes, 16-byte aligned (about 4 bytes per grid point).
+ * More than 2^31 - 1 vertices: AON_E_INVALID from the count call. */
+int64_t aon_marching_cubes_workspace_bytes(const int64_t* dims3_host);
+int aon_marching_cubes_count(const float* grid, const int64_t* dims3_host, float level, void* workspace, int64_t workspace_bytes, int64_t* counts2_host,
+                             void* stream);
+int aon_marching_cubes(const float* grid, const int64_t* dims3_host, float level, const float* lo3_host, const float* step3_host, void* workspace,
+                       int64_t workspace_bytes, float* verts, int64_t n_verts, int32_t* faces, int64_t n_faces, void* stream);
 
 /* Everything a training step of a TWO-level articulated model packs, in one call (round 6): aon_pack_art_mlp_deg + aon_art_prepare_deg +
  * aon_pack_art_mlp_bwd_deg for the coarse and the fine network -- every element computed by the same code on the same operands, the same

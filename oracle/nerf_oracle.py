@@ -128,13 +128,17 @@ def nerf_mlp(sd: dict, prefix: str, x_enc, view_enc, netdepth: int | None = None
 # --------------------------------------------------------------------------------------------------
 # R8  alpha compositing                                     models/vanilla_nerf/helper.py:157-195
 # --------------------------------------------------------------------------------------------------
-def volumetric_rendering(rgb, density, t_vals, dirs, white_bkgd):
+def volumetric_rendering(rgb, density, t_vals, dirs, white_bkgd, far_alpha=None):
     """helper.py:157-195.  rgb (N,S,3), density (N,S,1) (already activated), t_vals (N,S), dirs (N,3)
-    -> comp_rgb (N,3), acc (N,), weights (N,S), depth (N,)."""
+    -> comp_rgb (N,3), acc (N,), weights (N,S), depth (N,).  ``far_alpha`` (test aid, not in the reference): None keeps the
+    reference's alpha of the 1e10-long last interval (a step function of the sign of the far sample's raw sigma, helper.py:163);
+    0.0 or 1.0 forces it, so a ray whose far sigma sits at that step can be evaluated on either side of it."""
     eps = 1e-10
     dists = torch.cat([t_vals[..., 1:] - t_vals[..., :-1], torch.full_like(t_vals[..., :1], 1e10)], dim=-1)
     dists = dists * torch.norm(dirs[..., None, :], dim=-1)
     alpha = 1.0 - torch.exp(-density[..., 0] * dists)
+    if far_alpha is not None:
+        alpha = torch.cat([alpha[..., :-1], torch.full_like(alpha[..., -1:], float(far_alpha))], dim=-1)
     trans = torch.cat([torch.ones_like(alpha[..., :1]), torch.cumprod(1.0 - alpha[..., :-1] + eps, dim=-1)], dim=-1)
     weights = alpha * trans
     comp_rgb = (weights[..., None] * rgb).sum(dim=-2)
@@ -257,11 +261,12 @@ def aten_sum_model(x) -> "np.float32":
 # --------------------------------------------------------------------------------------------------
 def nerf_forward(sd, rays, randomized, white_bkgd, near, far, num_levels=2, min_deg_point=0,
                  max_deg_point=10, deg_view=4, num_coarse_samples=64, num_fine_samples=128,
-                 t_rand=None, u=None, return_aux=False, lindisp=False, noise_std=0.0, noise=None, skip_layer=4):
+                 t_rand=None, u=None, return_aux=False, lindisp=False, noise_std=0.0, noise=None, skip_layer=4, far_alpha=None):
     """model.py:147-199.  ``sd`` uses the reference's key names ('coarse_mlp.pts_linears.0.weight', ...).
     Returns [(comp_rgb, acc, depth)_coarse, (comp_rgb, acc, depth)_fine]; with ``return_aux`` also a
     dict of intermediates per level (t_vals, raw_rgb, raw_sigma, weights).  ``noise``: per-level (N,S,1) tensors replacing
-    ``torch.rand_like(raw_sigma)`` (:184)."""
+    ``torch.rand_like(raw_sigma)`` (:184).  ``far_alpha``: None, or one entry per level (None / 0.0 / 1.0) handed to
+    volumetric_rendering."""
     ret, aux = [], []
     t_vals = weights = None
     for i_level in range(num_levels):
@@ -281,7 +286,8 @@ def nerf_forward(sd, rays, randomized, white_bkgd, near, far, num_levels=2, min_
             raw_sigma = raw_sigma + noise[i_level].reshape(raw_sigma.shape) * noise_std
         rgb = torch.sigmoid(raw_rgb)
         sigma = F.relu(raw_sigma)
-        comp_rgb, acc, weights, depth = volumetric_rendering(rgb, sigma, t_vals, rays["rays_d"], white_bkgd)
+        comp_rgb, acc, weights, depth = volumetric_rendering(rgb, sigma, t_vals, rays["rays_d"], white_bkgd,
+                                                             None if far_alpha is None else far_alpha[i_level])
         ret.append((comp_rgb, acc, depth))
         aux.append({"t_vals": t_vals, "raw_rgb": raw_rgb, "raw_sigma": raw_sigma, "weights": weights})
     return (ret, aux) if return_aux else ret

@@ -2,7 +2,7 @@
 
 Runs only in the build container (needs /root/reference), like make_golden.py, whose stubs and torch.rand patches it reuses:
 
-    python tests/golden/make_golden_full.py [--only g19_config2_frame,g20_config4_frame,g21_config5_step,g22_trajectory,g22_trajectory_art,g23_steps32]
+    python tests/golden/make_golden_full.py [--only g19_config2_frame,g20_config4_frame,g21_config5_step,g22_trajectory,g22_trajectory_art,g23_steps32,g25_harness]
 
 Rounds 3-5 held BASELINE configs 2, 4 and 5 at their full sizes against the ORACLE evaluated live on the GPU host (fp32 and fp64 CPU
 runs inside the GPU suite: minutes of host time, and one link more than needed -- the reference pins the oracle only on 64..1,024-ray
@@ -501,6 +501,152 @@ def main():
                 arrs[f"{kind}|{name}|mean_drift32_full"] = np.float64((p32[name] - p64[name]).abs().mean().item())
             print(f"g23 {kind}: 2 x {STEPS32} steps took {time.time() - t0:.0f} s; loss {c32[0][0]:.6f} -> {c32[-1][0]:.6f} (fp64 {c64[-1][0]:.6f})", flush=True)
         mg.save("g23_steps32", **arrs)
+
+    # ---------------- G25: the evaluation harness (validation / test steps, chunking, test-epoch PSNRs) ----------------
+    if want("g25_harness"):
+        g25_harness(LitNeRF, LitNeRF_AutoDecoder, NeRF, NeRF_AE_Art, CodeLibraryArticulated, get_ray_directions, get_rays, syn, orc)
+
+
+def g25_harness(LitNeRF, LitNeRF_AutoDecoder, NeRF, NeRF_AE_Art, CodeLibraryArticulated, get_ray_directions, get_rays, syn, orc):
+    """G25: the reference's harness methods called UNBOUND on a stand-in object (as lit_like does for training_step): LitNeRF /
+    LitNeRF_AutoDecoder ``validation_step`` (-> ``render_rays``) and ``test_step`` (-> ``render_rays_test``) on DataLoader-form batches
+    (leading dim 1, the keys the reference's datasets yield), and the PSNR part of ``test_epoch_end`` -- ``LitModel.alter_gather_cat`` at
+    world 1 (all_gather = identity), ``psnr`` / ``psnr_each`` and ``get_obj_rgbs_from_segmap`` -- over two test images of different sizes.
+    Smooth fields of G15.  Stored per call: every output key's shape and fp32 values, the per-ray distance to the same call in fp64
+    (``*_spread_*``), every logged value in order; per vanilla ray set the far-plane margin (as G19).  Case a: 40x60 rays, chunk 1000
+    (the last chunk ragged); b: the same batch, chunk 4096; c: 23 rays, chunk 7.  Articulated: articulation_id 5, an interpolated
+    (mid-point) row of the test table.  The stand-in's random_batch = -1 keeps the wandb image branch shut."""
+    import io
+    import models.interface as ref_interface
+    import models.vanilla_nerf.model_autodecoder as ref_ad
+    from models.utils import get_obj_rgbs_from_segmap
+
+    LitModel = ref_interface.LitModel
+    ref_ad.dist = types.SimpleNamespace(get_rank=lambda: 0)          # model_autodecoder.py:579 (world 1, rank 0)
+    t0 = time.time()
+    H, W, H2, W2 = 40, 60, 24, 36
+    pose, pose2 = syn.look_at_pose(4.0, 60, 20), syn.look_at_pose(4.0, 20, 35)
+
+    def dataset_rays(h, w, c2w):
+        dirs = get_ray_directions(h, w, syn.focal_from_fovy(h))
+        ro, vd, rd, _ = get_rays(dirs, c2w, output_view_dirs=True, output_radii=True)
+        return {"rays_o": ro.contiguous(), "rays_d": vd.contiguous(), "viewdirs": rd.contiguous()}   # sapien.py:152-156
+
+    def image_batch(h, w, c2w, seed):
+        rays = dataset_rays(h, w, c2w)
+        yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+        mask = (((yy - 0.45 * h) / (0.3 * h)) ** 2 + ((xx - 0.55 * w) / (0.3 * w)) ** 2 <= 1.0).reshape(-1)
+        target = syn.seeded_uniform(seed, h * w, 3)
+        target = torch.where(mask[:, None], 0.6 * target + 0.3, target)      # the object region differs from the rest of the image
+        return dict(rays, target=target, instance_mask=mask)
+
+    img1, img2 = image_batch(H, W, pose, 2501), image_batch(H2, W2, pose2, 2502)
+    small = {k: v[torch.arange(5, H * W, 97)[:23]].contiguous() for k, v in img1.items()}
+    assert small["rays_o"].shape[0] == 23
+    arrs = dict(H=H, W=W, H2=H2, W2=W2, near=2.0, far=6.0)
+    for name, b in (("img1", img1), ("img2", img2), ("small", small)):
+        for k, v in b.items():
+            arrs[f"{name}_{k}"] = v
+
+    van_sd = syn.make_smooth_nerf_state_dict()
+    art_sd = syn.make_art_state_dict(seed=5, density_scale=2.0)
+    lib_sd = syn.make_code_library_state(seed=0, n_max_objs=2)
+    hp2 = types.SimpleNamespace(N_max_objs=2, N_obj_code_length=128)
+    with torch.no_grad():
+        for name, b in (("img1", img1), ("img2", img2), ("small", small)):
+            _, aux = orc.nerf_forward(van_sd, b, False, True, 2.0, 6.0, return_aux=True)
+            arrs[f"{name}_margin"] = torch.stack([a["raw_sigma"][:, -1, 0].abs() for a in aux]).min(0).values
+
+    ids = dict(instance_id=1, articulation_id=5, deg=np.float32(np.deg2rad(30.0)))
+    arrs.update({"art_" + k: v for k, v in ids.items()})
+
+    def stand_in(kind, dtype, chunk, h, w):
+        cls = LitNeRF if kind == "van" else LitNeRF_AutoDecoder
+        obj = object.__new__(cls)
+        torch.nn.Module.__init__(obj)
+        with default_dtype(dtype):
+            if kind == "van":
+                obj.model = NeRF().to(dtype)
+                obj.model.load_state_dict(cast(van_sd, dtype), strict=True)
+            else:
+                obj.model = NeRF_AE_Art().to(dtype)
+                obj.model.load_state_dict(cast(art_sd, dtype), strict=True)
+                obj.code_library = CodeLibraryArticulated(hp2).to(dtype)
+                obj.code_library.load_state_dict(cast(lib_sd, dtype))
+        obj.model.eval()
+        obj.white_bkgd, obj.near, obj.far, obj.randomized = True, 2.0, 6.0, False
+        obj.hparams = types.SimpleNamespace(chunk=chunk, img_wh=(w, h))
+        obj.random_batch = -1
+        obj.logged = []
+        obj.log = lambda name, value, **kw: obj.logged.append((name, float(value)))
+        obj.all_gather = lambda t: t               # Lightning's all_gather at world size 1
+        return obj
+
+    def loader_batch(kind, b, dtype, h, w):
+        """One DataLoader item (batch_size=1): every tensor gains a leading dim of 1."""
+        out = {k: (v.to(dtype) if v.is_floating_point() else v).unsqueeze(0) for k, v in b.items()}
+        if kind == "art":
+            out["img_wh"] = torch.tensor([[w, h]])                                          # sapien_multi.py:434
+            out["deg"] = torch.tensor([ids["deg"]], dtype=dtype)                             # :433
+            out["instance_id"] = torch.tensor([ids["instance_id"]])                          # :435
+            out["articulation_id"] = torch.tensor([ids["articulation_id"]])                  # :436
+        return out
+
+    def call(kind, method, b, chunk, h, w):
+        """The reference's ``method`` in fp32 and fp64 on fresh copies of the batch (the steps squeeze it in place)."""
+        cls = LitNeRF if kind == "van" else LitNeRF_AutoDecoder
+        res = []
+        for dtype in (torch.float32, torch.float64):
+            obj = stand_in(kind, dtype, chunk, h, w)
+            with torch.no_grad(), contextlib.redirect_stdout(io.StringIO()):
+                out = getattr(cls, method)(obj, loader_batch(kind, b, dtype, h, w), 0)
+            res.append((dict(out), obj.logged))
+        return res
+
+    outputs = {}
+    for kind in ("van", "art"):
+        for case, b, chunk, (h, w) in (("a", img1, 1000, (H, W)), ("b", img1, 4096, (H, W)), ("c", small, 7, (1, 23)), ("img2", img2, 1000, (H2, W2))):
+            for method, tag in (("validation_step", "val"), ("test_step", "test")):
+                if case == "img2" and tag == "val":
+                    continue
+                (o32, log32), (o64, _) = call(kind, method, b, chunk, h, w)
+                pre = f"{kind}_{case}_{tag}"
+                for k, v in o32.items():
+                    arrs[f"{pre}_shape_{k}"] = np.asarray(v.shape)
+                    if tag == "test" and k in ("target", "instance_mask"):
+                        assert torch.equal(v, b[k]), (pre, k)      # the batch's own tensors, squeezed: the shapes are what is stored
+                        continue
+                    arrs[f"{pre}_out_{k}"] = v.float()
+                    s = (v.double() - o64[k]).abs()
+                    arrs[f"{pre}_spread_{k}"] = (s.amax(dim=-1) if s.dim() > 1 else s).float()
+                names = []
+                for name, value in log32:
+                    names.append(name)
+                    arrs.setdefault(f"{pre}_log_{name.replace('/', '_')}", []).append(value)
+                arrs[f"{pre}_log_order"] = np.asarray([0 if n == "val/psnr" else 1 for n in names], dtype=np.int64)   # 0: val/psnr, 1: val/psnr_obj
+                if tag == "test":
+                    outputs[(kind, case)] = o32
+        # test_epoch_end's PSNR part over two images of different sizes (model.py:466-482, model_autodecoder.py:666-682)
+        obj = stand_in(kind, torch.float32, 1000, H, W)
+        outs, sizes = [outputs[(kind, "a")], outputs[(kind, "img2")]], [(H, W), (H2, W2)]
+        with contextlib.redirect_stdout(io.StringIO()):
+            rgbs = LitModel.alter_gather_cat(obj, outs, "rgb", sizes)
+            masks = LitModel.alter_gather_cat(obj, outs, "instance_mask", sizes)
+            targets = LitModel.alter_gather_cat(obj, outs, "target", sizes)
+            psnr = LitModel.psnr(obj, rgbs, targets, None, None, None)
+            objs, obj_targets = get_obj_rgbs_from_segmap(masks, rgbs, targets)
+            psnr_obj = LitModel.psnr(obj, objs, obj_targets, None, None, None)
+        for i, (r, m, t) in enumerate(zip(rgbs, masks, targets)):
+            arrs[f"{kind}_epoch_shape_rgb{i}"], arrs[f"{kind}_epoch_shape_mask{i}"] = np.asarray(r.shape), np.asarray(m.shape)
+            assert torch.equal(t.reshape(-1, 3), (img1 if i == 0 else img2)["target"])
+        arrs[f"{kind}_epoch_psnr_each"] = LitModel.psnr_each(obj, rgbs, targets).double()
+        arrs[f"{kind}_epoch_psnr_obj_each"] = LitModel.psnr_each(obj, objs, obj_targets).double()
+        arrs[f"{kind}_epoch_psnr"], arrs[f"{kind}_epoch_psnr_obj"] = np.float64(psnr["test"]), np.float64(psnr_obj["test"])
+        print(f"g25 {kind}: test/psnr {psnr['test']:.4f}, test/psnr_obj {psnr_obj['test']:.4f}")
+    for k in [k for k in arrs if "_log_val_" in k]:
+        arrs[k] = np.asarray(arrs[k], dtype=np.float64)
+    mg.save("g25_harness", **arrs)
+    print(f"g25 took {time.time() - t0:.0f} s")
 
 
 if __name__ == "__main__":

@@ -13,6 +13,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import nerf_oracle as orc  # noqa: E402  (checker only)
+from _far_branch import check_far_branch  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -84,6 +85,8 @@ def test_literal_form_still_meets_the_reference_bars(ops, dev, golden, nerf_sd):
         ok &= a["raw_sigma"][:, -1, 0].abs() > 2e-2
     for lvl in (0, 1):
         torch.testing.assert_close(out[lvl][0].cpu()[ok], ref[lvl][0][ok], rtol=0, atol=1e-5 if lvl == 0 else 2e-4)
+    check_far_branch([tuple(x.cpu() for x in lvl) for lvl in out], nerf_sd, {k: g8[k] for k in ("rays_o", "rays_d", "viewdirs")}, ~ok,
+                     [(1e-5, None, None), (2e-4, None, None)], False, True, g8["near"], g8["far"], label="literal form")
     del syn
 
 

@@ -11,6 +11,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import nerf_oracle as orc  # noqa: E402  (checker only)
+from _far_branch import check_far_branch  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -102,6 +103,9 @@ def test_forward_sweep(dev, seed, n):
             assert not bad.any(), (lvl, (acc - ref[lvl][1]).abs()[bad].max().item())
             if lvl == 0:
                 assert psnr(rgb[robust], ref[lvl][0][robust]) >= 70.0
+    if not art:   # the rays left out above, at the same bars and widening (tests/_far_branch.py)
+        check_far_branch([tuple(x.cpu() for x in lvl) for lvl in out], sd, rays_cpu, ~robust, [(2e-4, 2e-4, None)] * 2, randomized, white,
+                         near, far, widen=3.0, label=f"fuzz forward seed {seed}", **draws)
 
 
 @pytest.mark.parametrize("seed,n", [(0, 1), (1, 5), (2, 33), (3, 100), (4, 130), (5, 200)])
@@ -214,6 +218,9 @@ def test_forward_sweep_constructor_arguments(dev, seed):
             spread = (ref[lvl][0].double() - ref64[lvl][0]).abs().max(dim=-1).values.float()
             bad = robust & (err > 5e-5 + 3 * spread)
             assert not bad.any(), (lvl, err[bad].max().item(), spread[bad].max().item(), kw)
+    if not art:
+        check_far_branch([tuple(x.cpu() for x in lvl) for lvl in out], sd, rays_cpu, ~robust, [(5e-5, None, None)] * 2, randomized, white,
+                         near, far, widen=3.0, label=f"fuzz constructor seed {seed}", noise=noise, **draws, **kw, **gk)
 
 
 @pytest.mark.parametrize("seed", range(int(__import__("os").environ.get("AON_FUZZ_TRAIN_SEEDS", "8"))))

@@ -19,6 +19,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import nerf_oracle as orc  # noqa: E402  (checker only)
+from _far_branch import check_far_branch  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -572,6 +573,9 @@ def test_nerf_forward_vs_oracle_and_golden(dev, golden, nerf_sd, white):
         if (~ok).any():
             bad = (rgb[~ok] - g[f"{tag}_{name}_rgb"][~ok]).abs().amax(-1)
             assert ((bad <= 1e-5) | (bad >= 1e-3)).all(), bad
+    # the rays left out above, both levels at once: on one branch of that step, the same one at both levels (tests/_far_branch.py)
+    check_far_branch([tuple(x.cpu() for x in lvl) for lvl in out], nerf_sd, rays_cpu, ~ok, [(1e-5, 1e-5, 2e-4)] * 2, False, white,
+                     g["near"], g["far"], label=f"G8 {tag}")
 
 
 RND_ATOL = 1e-5   # measured on MI355X (round 3): see the printed maxima
@@ -597,6 +601,8 @@ def test_nerf_forward_randomized(dev, golden, nerf_sd):
         # round 3: the bound follows the measured level like the deterministic case (round 2 still carried round 1's 2e-4)
         torch.testing.assert_close(rgb[ok], ref[lvl][0][ok], rtol=0, atol=RND_ATOL)
         torch.testing.assert_close(rgb[ok], g[f"rnd_{name}_rgb"][ok], rtol=0, atol=RND_ATOL)
+    check_far_branch([tuple(x.cpu() for x in lvl) for lvl in out], nerf_sd, rays_cpu, ~ok, [(RND_ATOL, None, None)] * 2, True, True,
+                     g["near"], g["far"], label="G8 rnd", t_rand=g["t_rand"], u=g["u"])
     # without supplied draws the module draws its own: different result, still a valid render
     with torch.no_grad():
         out2 = model(rays, True, True, g["near"], g["far"])
@@ -668,6 +674,7 @@ def test_config1_coarse_only_frame_vs_oracle(ops, dev, nerf_sd):
     torch.testing.assert_close(got[1][ok], ref[0][1][ok], rtol=0, atol=1e-5)
     torch.testing.assert_close(got[2][ok], ref[0][2][ok], rtol=0, atol=2e-4)
     assert _psnr(got[0], ref[0][0]) >= 70.0
+    check_far_branch([tuple(got)], nerf_sd, rays_cpu, ~ok, [(1e-5, 1e-5, 2e-4)], False, True, 2.0, 6.0, label="config 1")
 
 
 def test_full_frame_properties(ops, dev, nerf_sd, golden):
@@ -733,6 +740,9 @@ def test_full_frame_properties(ops, dev, nerf_sd, golden):
             assert not bad.any(), (lvl, name, err[bad].max().item(), spread[bad].max().item())
         assert widened <= 0.01 * int(ok.sum()), (lvl, widened)
         assert _psnr(got[0], g[f"ref_{lname}_rgb"]) >= 70.0
+    # the rays of the fixture left out above (margin <= 2e-2), at the same bars and the same 3x spread widening
+    check_far_branch([tuple(x.cpu() for x in lvl) for lvl in sub], nerf_sd, {k: g[k] for k in ("rays_o", "rays_d", "viewdirs")}, ~ok,
+                     [(1e-5, 1e-5, 2e-4)] * 2, False, True, 2.0, 6.0, widen=3.0, label="G19 config 2")
 
 
 def test_volumetric_rendering_nocs_branch(dev, golden):

@@ -90,6 +90,11 @@ _SIGS = {
     "aon_marching_cubes_workspace_bytes": (_l, [_p]),
     "aon_marching_cubes_count": (_i, [_p, _p, _f, _p, _l, _p, _p]),
     "aon_marching_cubes": (_i, [_p, _p, _f, _p, _p, _p, _l, _p, _l, _p, _l, _p]),
+    "aon_occupancy_bytes": (_l, [_p]),
+    "aon_occupancy_build": (_i, [_p, _p, _f, _i, _p, _p]),
+    "aon_render_occ_workspace_bytes": (_l, [_l, _p]),
+    "aon_render_fwd_occ": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p]),
+    "aon_art_render_fwd_occ": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p]),
     "aon_art_pack_step": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "aon_vanilla_pack_step": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
     "aon_set_bwd_early_heads": (_i, [_i]),
@@ -158,6 +163,11 @@ class RenderOptsC(C.Structure):
                 ("noise_c", C.c_void_p), ("noise_f", C.c_void_p),
                 ("rgb_scale", C.c_float), ("rgb_shift", C.c_float), ("sigma_bias", C.c_float),
                 ("min_deg_point", C.c_int32), ("max_deg_point", C.c_int32), ("deg_view", C.c_int32)]
+
+
+class OccupancyC(C.Structure):
+    """aon_occupancy (include/aon_hip.h)."""
+    _fields_ = [("bits", C.c_void_p), ("cells", C.c_int64 * 3), ("lo", C.c_float * 3), ("step", C.c_float * 3)]
 
 
 for _name, (_res, _args) in _SIGS.items():

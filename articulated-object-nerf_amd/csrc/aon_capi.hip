@@ -3,6 +3,7 @@
 #include "aon_common.h"
 
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -120,6 +121,15 @@ hipError_t launch_composite_pdf(const float* raw, const float* t_coarse, const f
 hipError_t launch_sample_pdf_n(const float* bins, const float* weights, int64_t w_stride, const float* t_coarse, const float* u,
                                int64_t u_stride, int64_t n_rays, int nb, int nf, int nt, float* samples, float* t_fine, hipStream_t stream);
 int64_t sample_pdf_n_lds_bytes(int nb, int nf, int nt, int* P_out);
+hipError_t launch_occ_build(const float* dens, const int64_t* dims, float thr, int dilate, uint32_t* bits, hipStream_t stream);
+int64_t occ_list_bytes(int64_t total);
+hipError_t launch_occ_compact(const OccGrid& G, const float* rays_o, const float* rays_d, const float* t_vals, int64_t n, int S, float* raw,
+                              char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out, hipStream_t stream);
+hipError_t launch_mlp_fwd_gather(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_vals,
+                                 int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias, const int* idx, const int64_t* count);
+hipError_t launch_art_mlp_fwd_gather(const char* packed, const float* small, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                     const float* t_vals, int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias,
+                                     const int* idx, const int64_t* count);
 }  // namespace aon
 
 namespace {
@@ -244,10 +254,11 @@ struct Ws {
   float* raw;   // n*Sf*4 (coarse raw uses the first n*Sc*4)
   float* coords; float* enc; float* venc;   // other_degrees only: n*Sf*3, n*Sf*63, n*27
   float* vbias;   // n*128: the level's per-ray view bias (vanilla, folded form; launch_view_bias) -- both levels in turn
+  char* occ;      // [occupancy] the level's sample list, tile counts and list length (aon::occ_list_bytes of n*Sf) -- both levels in turn
   int64_t bytes;
 };
 
-Ws carve(char* base, int64_t n, const Geo& g) {
+Ws carve(char* base, int64_t n, const Geo& g, bool occ = false) {
   Ws w{};
   int64_t off = 0;
   w.t_c = reinterpret_cast<float*>(base + off); off += align_up(n * g.Sc * 4, 256);
@@ -261,6 +272,7 @@ Ws carve(char* base, int64_t n, const Geo& g) {
   } else {
     w.vbias = reinterpret_cast<float*>(base + off); off += align_up(n * (int64_t)aon::kCondWidth * 4, 256);
   }
+  if (occ) { w.occ = base + off; off += aon::occ_list_bytes(n * g.Sf); }
   w.bytes = off;
   return w;
 }
@@ -874,8 +886,18 @@ struct NetRef {
   const float* small;  // articulated only
 };
 
+// An occupancy grid handed to aon_render_fwd_occ / aon_art_render_fwd_occ: the kernels' view of it, and the
+// caller's per-level tally of samples run through the MLP (or null)
+struct OccCtx {
+  aon::OccGrid grid;
+  int64_t* tally;
+};
+
+// occ: mark the level's samples, compact the occupied ones into a list (aon_occ.hip) and run the MLP on that list alone (the GATHER
+// instances); the empty samples' records hold the zero-density sentinel.  Same view bias, same kernel arithmetic per sample.
 static hipError_t launch_net(const NetRef& net, const float* o, const float* d, const float* v, const float* t, int64_t n, int S,
-                             float* raw, hipStream_t stream, const Geo* g = nullptr, const Ws* w = nullptr) {
+                             float* raw, hipStream_t stream, const Geo* g = nullptr, const Ws* w = nullptr, const OccCtx* occ = nullptr,
+                             int level = 0) {
   if (g && g->other_degrees) {
     // NeRF(min_deg_point, max_deg_point, deg_view) with at most 10 / 4 levels: the encodings are computed by the stage kernels in
     // the fused kernel's 63 / 27-slot layout (zeros in the missing levels' slots, matched by zero weights in the packed stream,
@@ -894,6 +916,17 @@ static hipError_t launch_net(const NetRef& net, const float* o, const float* d, 
     if (e != hipSuccess) return e;
     vbias = w->vbias;
   }
+  if (occ) {
+    const int* idx = nullptr;
+    const int64_t* count = nullptr;
+    if (hipError_t e = aon::launch_occ_compact(occ->grid, o, d, t, n, S, raw, w->occ, occ->tally ? occ->tally + level : nullptr, &idx, &count, stream);
+        e != hipSuccess)
+      return e;
+    MlpTimer timer(stream, n * S);
+    if (net.articulated)
+      return aon::launch_art_mlp_fwd_gather(static_cast<const char*>(net.packed), net.small, o, d, v, t, n, S, raw, stream, vbias, idx, count);
+    return aon::launch_mlp_fwd_gather(static_cast<const char*>(net.packed), o, d, v, t, n, S, raw, stream, vbias, idx, count);
+  }
   MlpTimer timer(stream, n * S);
   if (net.articulated)
     return aon::launch_art_mlp_fwd(static_cast<const char*>(net.packed), net.small, o, d, v, t, n, S, raw, stream, vbias);
@@ -904,7 +937,7 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
                        const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
                        const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
                        float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, hipStream_t stream,
-                       const aon_render_opts* opts) {
+                       const aon_render_opts* opts, const OccCtx* occ = nullptr) {
   Geo g;
   if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
   if (n_rays < 0 || (num_levels != 1 && num_levels != 2)) return fail(AON_E_INVALID, "render: bad size / num_levels");
@@ -920,17 +953,24 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
   const bool art = coarse.articulated;
   if (art) g.other_degrees = false;   // the articulated kernels carry their degrees in the packed stream and the small block (aon_*_deg)
   const bool fuse_coarse = num_levels == 2 && g.default_sizes && g_fuse_coarse.load(std::memory_order_relaxed) != 0;
+  const bool with_occ = occ != nullptr;
 
-  // largest chunk the workspace admits
+  // largest chunk the workspace admits ([occupancy] and whose sample indices fit the int32 list)
   int64_t chunk = n_rays;
-  if (carve(nullptr, chunk, g).bytes > workspace_bytes) {
-    const int64_t per_ray = (int64_t)(g.Sc + g.Sc + g.Sf + 4 * g.Sf + (g.other_degrees ? (3 + aon::kPosEnc) * g.Sf + aon::kViewEnc : aon::kCondWidth)) * 4;
-    const int64_t slack = g.other_degrees ? 7 * 256 : 5 * 256;
+  if (with_occ && chunk > INT32_MAX / g.Sf) chunk = INT32_MAX / g.Sf;
+  if (carve(nullptr, chunk, g, with_occ).bytes > workspace_bytes) {
+    const int64_t per_ray = (int64_t)(g.Sc + g.Sc + g.Sf + 4 * g.Sf + (g.other_degrees ? (3 + aon::kPosEnc) * g.Sf + aon::kViewEnc : aon::kCondWidth) +
+                                      (with_occ ? g.Sf + 2 * (g.Sf / 1024 + 1) : 0)) * 4;
+    const int64_t slack = (g.other_degrees ? 7 * 256 : 5 * 256) + (with_occ ? 4 * 256 : 0);
     chunk = (workspace_bytes - slack) / per_ray;
-    while (chunk > 0 && carve(nullptr, chunk, g).bytes > workspace_bytes) --chunk;
-    if (chunk < 1) return fail(AON_E_WORKSPACE, "render: workspace smaller than aon_render_workspace_bytes(1)");
+    while (chunk > 0 && carve(nullptr, chunk, g, with_occ).bytes > workspace_bytes) --chunk;
+    if (chunk < 1) return fail(AON_E_WORKSPACE, with_occ ? "render: workspace smaller than aon_render_occ_workspace_bytes(1)"
+                                                         : "render: workspace smaller than aon_render_workspace_bytes(1)");
   }
-  const Ws w = carve(static_cast<char*>(workspace), chunk, g);
+  const Ws w = carve(static_cast<char*>(workspace), chunk, g, with_occ);
+  if (with_occ && occ->tally) {
+    if (int rc = check(hipMemsetAsync(occ->tally, 0, 2 * sizeof(int64_t), stream), who); rc != AON_OK) return rc;
+  }
 
   for (int64_t r0 = 0; r0 < n_rays; r0 += chunk) {
     const int64_t n = n_rays - r0 < chunk ? n_rays - r0 : chunk;
@@ -946,7 +986,7 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
                                                g.lindisp, g.inv_near, g.inv_far), who);
     }
     if (rc) return rc;
-    rc = check(launch_net(coarse, o, d, v, w.t_c, n, g.Sc, w.raw, stream, &g, &w), who);
+    rc = check(launch_net(coarse, o, d, v, w.t_c, n, g.Sc, w.raw, stream, &g, &w, occ, 0), who);
     if (rc) return rc;
     if (fuse_coarse) {
       // compositing + the fine level's sampling (model.py:162-173) in one kernel: the coarse weights stay in registers
@@ -968,7 +1008,7 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
                                                             w.t_f, stream), who);
       if (rc) return rc;
     }
-    rc = check(launch_net(fine, o, d, v, w.t_f, n, g.Sf, w.raw, stream, &g, &w), who);
+    rc = check(launch_net(fine, o, d, v, w.t_f, n, g.Sf, w.raw, stream, &g, &w, occ, 1), who);
     if (rc) return rc;
     {
       KTimer timer(kComposite, stream, n);
@@ -995,6 +1035,70 @@ int aon_render_fwd(const void* packed_coarse, const void* packed_fine, const flo
                    float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream) {
   return aon_render_fwd_ex(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
                            u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, nullptr);
+}
+
+// ---- occupancy-grid accelerated inference (aon_occ.hip) ----
+static const char* occ_cells_bad(const int64_t* cells3) {
+  if (!cells3) return "null cell counts";
+  for (int a = 0; a < 3; ++a)
+    if (cells3[a] < 1 || cells3[a] > (int64_t)1 << 24) return "every cell count must be in [1, 2^24]";
+  if (cells3[0] > ((int64_t)1 << 40) / cells3[1] / cells3[2]) return "grid too large (more than 2^40 cells)";
+  return nullptr;
+}
+int64_t aon_occupancy_bytes(const int64_t* cells3_host) {
+  if (const char* msg = occ_cells_bad(cells3_host)) return fail(AON_E_INVALID, (std::string("aon_occupancy_bytes: ") + msg).c_str());
+  return (cells3_host[0] * cells3_host[1] * cells3_host[2] + 31) / 32 * 4;
+}
+int aon_occupancy_build(const float* density, const int64_t* dims3_host, float threshold, int dilate, uint32_t* bits, void* stream) {
+  if (!dims3_host) return fail(AON_E_INVALID, "aon_occupancy_build: null dims");
+  const int64_t cells[3] = {dims3_host[0] - 1, dims3_host[1] - 1, dims3_host[2] - 1};
+  if (const char* msg = occ_cells_bad(cells)) return fail(AON_E_INVALID, (std::string("aon_occupancy_build: every dimension must be >= 2; ") + msg).c_str());
+  if (dilate < 0 || dilate > 8) return fail(AON_E_INVALID, "aon_occupancy_build: dilate must be in [0, 8]");
+  if (threshold != threshold) return fail(AON_E_INVALID, "aon_occupancy_build: threshold is NaN");
+  if (!density || !bits) return fail(AON_E_INVALID, "aon_occupancy_build: null pointer");
+  return check(aon::launch_occ_build(density, dims3_host, threshold, dilate, bits, (hipStream_t)stream), "aon_occupancy_build");
+}
+static const char* occ_grid_bad(const aon_occupancy* occ, aon::OccGrid& G) {
+  if (!occ || !occ->bits) return "null occupancy grid";
+  if (const char* msg = occ_cells_bad(occ->cells)) return msg;
+  G.bits = occ->bits;
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(occ->lo[a]) || !std::isfinite(occ->step[a]) || !(occ->step[a] > 0.f)) return "occupancy lo must be finite and step finite and > 0";
+    G.cells[a] = occ->cells[a]; G.lo[a] = occ->lo[a]; G.step[a] = occ->step[a];
+    const float span = (float)occ->cells[a] * occ->step[a];   // the last grid point: multiply, then add (ops.grid_points)
+    G.hi[a] = occ->lo[a] + span;
+    if (!std::isfinite(G.hi[a])) return "occupancy box not finite";
+  }
+  return nullptr;
+}
+// the inference-only limits of the occupancy path, checked before any launch
+static const char* occ_opts_bad(const aon_render_opts* opts, bool art, const float* t_rand) {
+  Geo g;
+  if (const char* bad = make_geo(opts, g)) return bad;
+  if (t_rand) return "occupancy rendering is inference only: t_rand (randomized sampling) is refused";
+  if (g.noise_std > 0.f && (g.noise[0] || g.noise[1])) return "occupancy rendering is inference only: density noise is refused";
+  if (!art && g.other_degrees) return "occupancy rendering needs the default encoding degrees (0, 10, 4) of the vanilla network";
+  return nullptr;
+}
+int64_t aon_render_occ_workspace_bytes(int64_t n_rays, const aon_render_opts* opts) {
+  if (n_rays < 1) n_rays = 1;
+  Geo g;
+  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
+  if (n_rays > INT32_MAX / g.Sf) n_rays = INT32_MAX / g.Sf;
+  return carve(nullptr, n_rays, g, true).bytes;
+}
+int aon_render_fwd_occ(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                       const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                       const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                       float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                       const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev) {
+  OccCtx ctx{};
+  if (const char* bad = occ_grid_bad(occ, ctx.grid)) return fail(AON_E_INVALID, (std::string("aon_render_fwd_occ: ") + bad).c_str());
+  if (const char* bad = occ_opts_bad(opts, false, t_rand)) return fail(AON_E_INVALID, (std::string("aon_render_fwd_occ: ") + bad).c_str());
+  ctx.tally = occupied_dev;
+  const NetRef c{false, packed_coarse, nullptr}, f{false, packed_fine, nullptr};
+  return render_impl("aon_render_fwd_occ", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
+                     u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, &ctx);
 }
 
 // ---- training step in two calls (aon_render_fwd_train + aon_render_bwd) ----
@@ -1907,6 +2011,20 @@ int aon_art_render_fwd_ex(const void* packed_coarse, const void* small_coarse, c
   const NetRef c{true, packed_coarse, static_cast<const float*>(small_coarse)}, f{true, packed_fine, static_cast<const float*>(small_fine)};
   return render_impl("aon_art_render_fwd", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
                      u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts);
+}
+int aon_art_render_fwd_occ(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                           const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                           int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                           float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                           int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
+                           int64_t* occupied_dev) {
+  OccCtx ctx{};
+  if (const char* bad = occ_grid_bad(occ, ctx.grid)) return fail(AON_E_INVALID, (std::string("aon_art_render_fwd_occ: ") + bad).c_str());
+  if (const char* bad = occ_opts_bad(opts, true, t_rand)) return fail(AON_E_INVALID, (std::string("aon_art_render_fwd_occ: ") + bad).c_str());
+  ctx.tally = occupied_dev;
+  const NetRef c{true, packed_coarse, static_cast<const float*>(small_coarse)}, f{true, packed_fine, static_cast<const float*>(small_fine)};
+  return render_impl("aon_art_render_fwd_occ", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
+                     u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, &ctx);
 }
 int aon_art_render_fwd(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
                        const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,

@@ -227,6 +227,40 @@ struct TrainSeg {
 };
 
 // ------------------------------------------------------------------------------------------------
+// Exclusive prefix over the threads of a 256-thread workgroup, and the total (integers: exact, so the order of the sums does not
+// matter).  `red`: __shared__ T[4].  Marching cubes (aon_mesh.hip) and the occupancy compaction (aon_occ.hip) scan with it.
+template <class T>
+__device__ __forceinline__ T block_excl_scan(T v, T& total, T* red) {
+  constexpr int kThreads = 256;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  T x = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const T y = __shfl_up(x, d);
+    if (lane >= d) x += y;
+  }
+  if (lane == 63) red[wave] = x;
+  __syncthreads();
+  T base = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < kThreads / 64; ++w) {
+    const T t = red[w];
+    if (w < wave) base += t;
+    total += t;
+  }
+  __syncthreads();   // `red` may be reused
+  return base + x - v;
+}
+
+// An occupancy grid as the kernels see it (aon_occupancy, include/aon_hip.h; aon_occ.hip): hi = lo + cells * step, multiply then add
+struct OccGrid {
+  const uint32_t* bits;
+  int64_t cells[3];
+  float lo[3], step[3], hi[3];
+};
+
+// ------------------------------------------------------------------------------------------------
 // Host side.  A kernel's dynamic-LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) is a per-DEVICE function
 // attribute and the CU count is a per-device property: both are remembered per device ordinal, lock-free (a racing
 // second thread merely repeats an idempotent call), so a process that drives cuda:0 and later cuda:1 launches correctly

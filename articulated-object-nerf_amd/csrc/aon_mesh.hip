@@ -115,29 +115,7 @@ __device__ __forceinline__ int mc_ntri(int cs) {   // triangles of a case (the t
   return n;
 }
 
-// exclusive prefix over the 256 threads of a workgroup, and the total (integers: exact, so the order of the sums does not matter)
-template <class T>
-__device__ __forceinline__ T block_excl_scan(T v, T& total, T* red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  T x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T y = __shfl_up(x, d);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) red[wave] = x;
-  __syncthreads();
-  T base = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kMcThreads / 64; ++w) {
-    const T t = red[w];
-    if (w < wave) base += t;
-    total += t;
-  }
-  __syncthreads();   // `red` may be reused
-  return base + x - v;
-}
+// (block_excl_scan: aon_common.h)
 
 // (a) per point: flags = owned-edge bits (x: 1, y: 2, z: 4) | case << 3 (0 when the point names no cell); lvoff = vertex offset in the tile
 __global__ __launch_bounds__(kMcThreads) void mc_classify_kernel(McGrid G, uint16_t* __restrict__ flags, uint16_t* __restrict__ lvoff,

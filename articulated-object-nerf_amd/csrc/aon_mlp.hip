@@ -128,8 +128,14 @@ struct MlpSeg {
   int64_t total;             // n_rays*S
   int S;
   int npass;                 // ceil(total/128)
-  float* planes;             // [TRAIN] kPlRows x Np activation planes, step-major (aon_mlp_core.h)
-  u32x4* masks;              // [TRAIN] kMaskLayers x (Np*2) ReLU bit masks
+  union {
+    float* planes;             // [TRAIN] kPlRows x Np activation planes, step-major (aon_mlp_core.h)
+    const int* gather_idx;     // [GATHER] ascending sample indices of the segment (< total)
+  };
+  union {
+    u32x4* masks;              // [TRAIN] kMaskLayers x (Np*2) ReLU bit masks
+    const int64_t* gather_count;   // [GATHER] number of entries of gather_idx (device)
+  };
   int64_t Np;                // npass * 128
   const float* view_bias;    // [VB] (n_rays,128): b' + W_v0[:, 256:] ve of the ray (view_bias_kernel)
 };
@@ -146,9 +152,11 @@ constexpr int kLdsBytes = kRingBytes + (int)kSmallBytes;
 // VB (folded form only): the view layer's accumulators start from the ray's b' + W_v0[:, 256:] ve, fetched from `view_bias` while the last
 // chunk of layer 7 runs, instead of from b' followed by the view-encoding chunk -- same bits (aon_common.h), 56 MFMAs, 12 sines and a
 // 16 KiB chunk fewer per pass; the inference kernel no longer carries the 16 registers of the view encoding through the trunk.
-template <bool ENC_IN_KERNEL, bool TRAIN, bool FOLD, bool VB = false>
+// GATHER (inference on the in-kernel encodings only): the samples of a pass come from an occupancy list (aon_mlp_core.h).
+template <bool ENC_IN_KERNEL, bool TRAIN, bool FOLD, bool VB = false, bool GATHER = false>
 __global__ void __launch_bounds__(256) mlp_fwd_kernel(MlpArgs args) {
   static_assert(FOLD || !VB, "the per-ray view bias belongs to the folded form");
+  static_assert(!GATHER || (ENC_IN_KERNEL && !TRAIN), "the occupancy list serves the inference kernel on in-kernel encodings");
   using Net = std::conditional_t<VB, VanillaFoldVbNet, std::conditional_t<FOLD, VanillaFoldNet, VanillaNet>>;
   // <false, true>: training on caller-encoded inputs (other encoding degrees in the padded 63 / 27-slot layout): where the
   // in-kernel form re-encodes from x[] / vd[], this one re-reads the encodings.
@@ -160,7 +168,9 @@ __global__ void __launch_bounds__(256) mlp_fwd_kernel(MlpArgs args) {
   const int m = lane & 31, h = lane >> 5;
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);   // the step base of the training planes is wave-uniform: keep it scalar
 
-  const int npass0 = args.seg[0].npass;
+  // [GATHER] one segment; its pass count is the occupancy list's
+  const int64_t listed = GATHER ? *args.seg[0].gather_count : 0;
+  const int npass0 = GATHER ? (int)((listed + 127) / 128) : args.seg[0].npass;
   int cur = (int)blockIdx.x >= npass0 ? 1 : 0;               // segment of this workgroup's first pass
   auto load_small = [&](const char* packed) {  // resident small vectors -> LDS (visible after the next workgroup barrier)
     const f32x4* src = reinterpret_cast<const f32x4*>(packed + kStreamBytes);
@@ -172,7 +182,7 @@ __global__ void __launch_bounds__(256) mlp_fwd_kernel(MlpArgs args) {
   Pipe p;
   pipe_init<Net>(p, args.seg[cur].packed, smem, wave, lane);  // also publishes the small block just written to LDS
 
-  for (int gpass = blockIdx.x; gpass < args.npass_total; gpass += gridDim.x) {
+  for (int gpass = blockIdx.x; gpass < (GATHER ? npass0 : args.npass_total); gpass += gridDim.x) {
     const int si = gpass >= npass0 ? 1 : 0;
     if (si != cur) {   // (workgroup-uniform, at most once per launch) the other network's biases / head weights replace the resident block
       __syncthreads();
@@ -185,11 +195,18 @@ __global__ void __launch_bounds__(256) mlp_fwd_kernel(MlpArgs args) {
     {   // weight stream of this pass, and of this workgroup's next one (its first chunk pair is fetched during this pass's last chunk)
       const int nxt = gpass + (int)gridDim.x;
       p.stream = sg.packed;
-      p.next_stream = args.seg[(nxt >= npass0 && nxt < args.npass_total) ? 1 : si].packed;
+      p.next_stream = args.seg[(nxt >= npass0 && nxt < (GATHER ? npass0 : args.npass_total)) ? 1 : si].packed;
     }
-    const int64_t g = (int64_t)pass * 128 + wave * 32 + m;
-    const bool valid = g < sg.total;
-    const int64_t gc = valid ? g : sg.total - 1;
+    int64_t g = (int64_t)pass * 128 + wave * 32 + m;
+    bool valid;
+    int64_t gc;
+    if constexpr (GATHER) {   // the listed sample: everything below (ray, t, view bias, the record's address) follows it
+      valid = g < listed;
+      g = gc = sg.gather_idx[valid ? g : listed - 1];
+    } else {
+      valid = g < sg.total;
+      gc = valid ? g : sg.total - 1;
+    }
     const int64_t ray = gc / sg.S;
 
     // ---- encode: E[0..1] = 63-wide positional encoding, V = 27-wide view encoding, accumulator layout ----
@@ -398,20 +415,20 @@ int num_cus() {  // CUs of the CURRENT device, cached per device ordinal (ops.py
   return cus;
 }
 
-template <bool ENC, bool TRAIN, bool FOLD, bool VB = false>
+template <bool ENC, bool TRAIN, bool FOLD, bool VB = false, bool GATHER = false>
 static hipError_t launch_mlp_tf(const MlpArgs& args, hipStream_t stream) {
   static DeviceOnce lds_once;  // one per template instance
-  if (hipError_t e = set_max_lds(&mlp_fwd_kernel<ENC, TRAIN, FOLD, VB>, kLdsBytes, lds_once); e != hipSuccess) return e;
+  if (hipError_t e = set_max_lds(&mlp_fwd_kernel<ENC, TRAIN, FOLD, VB, GATHER>, kLdsBytes, lds_once); e != hipSuccess) return e;
   const int g_num_cus = num_cus();
   if (g_num_cus <= 0) return hipErrorInvalidDevice;
-  const int grid = args.npass_total < g_num_cus ? args.npass_total : g_num_cus;
+  const int grid = args.npass_total < g_num_cus ? args.npass_total : g_num_cus;   // [GATHER] npass_total: the passes of a full list
   if (grid <= 0) return hipSuccess;
-  mlp_fwd_kernel<ENC, TRAIN, FOLD, VB><<<dim3(grid), dim3(256), kLdsBytes, stream>>>(args);
+  mlp_fwd_kernel<ENC, TRAIN, FOLD, VB, GATHER><<<dim3(grid), dim3(256), kLdsBytes, stream>>>(args);
   return hipGetLastError();
 }
 
 // the kernel of the form the launch's streams were packed in; the segments of one launch must agree
-template <bool ENC, bool TRAIN>
+template <bool ENC, bool TRAIN, bool GATHER = false>
 static hipError_t launch_mlp_t(const MlpArgs& args, hipStream_t stream) {
   const int form = stream_form(args.seg[0].packed);
   if (form == kFormUnknown) return hipErrorInvalidValue;   // never packed / declared (a copy): refuse instead of guessing
@@ -421,11 +438,12 @@ static hipError_t launch_mlp_t(const MlpArgs& args, hipStream_t stream) {
   if (args.seg[1].npass > 0 && (args.seg[1].view_bias != nullptr) != vb) return hipErrorInvalidValue;
   if (vb && form != kFormFolded) return hipErrorInvalidValue;
   if constexpr (ENC) {
-    if (vb) return launch_mlp_tf<ENC, TRAIN, true, true>(args, stream);
+    if (vb) return launch_mlp_tf<ENC, TRAIN, true, true, GATHER>(args, stream);
   } else {
     if (vb) return hipErrorInvalidValue;
   }
-  return form == kFormFolded ? launch_mlp_tf<ENC, TRAIN, true>(args, stream) : launch_mlp_tf<ENC, TRAIN, false>(args, stream);
+  return form == kFormFolded ? launch_mlp_tf<ENC, TRAIN, true, false, GATHER>(args, stream)
+                             : launch_mlp_tf<ENC, TRAIN, false, false, GATHER>(args, stream);
 }
 
 // b' + W_v0[:, 256:] ve per ray, the head of the view layer's accumulation chains (aon_common.h): the fused multiply-adds the view-encoding
@@ -487,6 +505,18 @@ hipError_t launch_mlp_fwd(const char* packed, const float* rays_o, const float* 
   a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)((a.total + 127) / 128);
   args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
   return launch_mlp_t<true, false>(args, stream);
+}
+
+// launch_mlp_fwd on the samples of an occupancy list (aon_mlp_core.h): idx / count stay on the device
+hipError_t launch_mlp_fwd_gather(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_vals,
+                                 int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias, const int* idx, const int64_t* count) {
+  MlpArgs args{};
+  MlpSeg& a = args.seg[0];
+  a.packed = packed; a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.t_vals = t_vals; a.view_bias = view_bias;
+  a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)((a.total + 127) / 128);
+  a.gather_idx = idx; a.gather_count = count;
+  args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
+  return launch_mlp_t<true, false, true>(args, stream);
 }
 
 hipError_t launch_mlp_fwd_train2(const TrainSeg* segs, int nsegs, hipStream_t stream);

@@ -202,8 +202,14 @@ struct ArtSeg {
   int64_t total;
   int S;
   int npass;
-  float* planes;          // [TRAIN] kAPlRows x Np
-  u32x4* masks;           // [TRAIN] kAMaskLayers x (Np*2)
+  union {
+    float* planes;          // [TRAIN] kAPlRows x Np
+    const int* gather_idx;  // [GATHER] ascending sample indices of the segment (< total; aon_mlp_core.h)
+  };
+  union {
+    u32x4* masks;           // [TRAIN] kAMaskLayers x (Np*2)
+    const int64_t* gather_count;   // [GATHER] number of entries of gather_idx (device)
+  };
   int64_t Np;
   const float* view_bias; // [VB] (n_rays,128): views_linear.0's effective bias + W_v0[:, 256:283] ve of the ray (launch_art_view_bias)
 };
@@ -215,9 +221,11 @@ struct ArtMlpArgs {
 // FOLD: stream and per-call block are the folded form's (aon_art_common.h): views_linear.0 reads the post-ReLU layer-7 output through W';
 // no bottleneck layer and, [TRAIN], no bottleneck rows in the planes (rows kAPlBot .. kAPlBot + 255 stay unwritten).
 // VB (folded form, in-kernel ray cast): views_linear.0's accumulators start from the ray's bias + view-encoding term (see mlp_fwd_kernel).
-template <bool POS_IN_KERNEL, bool TRAIN, bool FOLD, bool VB = false>
+// GATHER (inference, in-kernel ray cast): the samples of a pass come from an occupancy list (aon_mlp_core.h).
+template <bool POS_IN_KERNEL, bool TRAIN, bool FOLD, bool VB = false, bool GATHER = false>
 __global__ void __launch_bounds__(256) art_mlp_fwd_kernel(ArtMlpArgs args) {
   static_assert((FOLD && POS_IN_KERNEL) || !VB, "the per-ray view bias belongs to the folded form of the whole-path kernels");
+  static_assert(!GATHER || (POS_IN_KERNEL && !TRAIN), "the occupancy list serves the inference kernel with the in-kernel ray cast");
   using Net = std::conditional_t<VB, ArtFoldVbNet, std::conditional_t<FOLD, ArtFoldNet, ArtNet>>;
   constexpr int kV0 = FOLD ? kAChFV0 : kAChV0, kV1 = (FOLD ? kAChFV1 : kAChV1) - (VB ? 1 : 0);
   static_assert(!TRAIN || POS_IN_KERNEL, "the training path encodes the view direction from vd[], which only the in-kernel ray cast fills");
@@ -227,7 +235,9 @@ __global__ void __launch_bounds__(256) art_mlp_fwd_kernel(ArtMlpArgs args) {
   const int lane = tid & 63, wave = tid >> 6;
   const int m = lane & 31, h = lane >> 5;
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);   // the step base of the training planes is wave-uniform: keep it scalar
-  const int npass0 = args.seg[0].npass;
+  // [GATHER] one segment; its pass count is the occupancy list's
+  const int64_t listed = GATHER ? *args.seg[0].gather_count : 0;
+  const int npass0 = GATHER ? (int)((listed + 127) / 128) : args.seg[0].npass;
   int cur = (int)blockIdx.x >= npass0 ? 1 : 0;               // segment of this workgroup's first pass
   auto load_small = [&](const float* small) {
     const f32x4* src = reinterpret_cast<const f32x4*>(small);
@@ -238,7 +248,7 @@ __global__ void __launch_bounds__(256) art_mlp_fwd_kernel(ArtMlpArgs args) {
   Pipe p;
   pipe_init<Net>(p, args.seg[cur].packed, smem, wave, lane);  // also publishes the small block just written to LDS
 
-  for (int gpass = blockIdx.x; gpass < args.npass_total; gpass += gridDim.x) {
+  for (int gpass = blockIdx.x; gpass < (GATHER ? npass0 : args.npass_total); gpass += gridDim.x) {
     const int si = gpass >= npass0 ? 1 : 0;
     if (si != cur) {   // (workgroup-uniform, at most once per launch) the other network's biases / head weights replace the resident block
       __syncthreads();
@@ -251,11 +261,18 @@ __global__ void __launch_bounds__(256) art_mlp_fwd_kernel(ArtMlpArgs args) {
     {   // weight stream of this pass, and of this workgroup's next one (its first chunk pair is fetched during this pass's last chunk)
       const int nxt = gpass + (int)gridDim.x;
       p.stream = sg.packed;
-      p.next_stream = args.seg[(nxt >= npass0 && nxt < args.npass_total) ? 1 : si].packed;
+      p.next_stream = args.seg[(nxt >= npass0 && nxt < (GATHER ? npass0 : args.npass_total)) ? 1 : si].packed;
     }
-    const int64_t g = (int64_t)pass * 128 + wave * 32 + m;
-    const bool valid = g < sg.total;
-    const int64_t gc = valid ? g : sg.total - 1;
+    int64_t g = (int64_t)pass * 128 + wave * 32 + m;
+    bool valid;
+    int64_t gc;
+    if constexpr (GATHER) {   // the listed sample: everything below (ray, t, view bias, the record's address) follows it
+      valid = g < listed;
+      g = gc = sg.gather_idx[valid ? g : listed - 1];
+    } else {
+      valid = g < sg.total;
+      gc = valid ? g : sg.total - 1;
+    }
     const int64_t ray = gc / sg.S;
     float x[3], vd[3] = {0.f, 0.f, 0.f};
     f32x16 V;
@@ -502,20 +519,20 @@ hipError_t launch_pack_prepare_art2(const float* const* const params[2], const f
 
 int num_cus();  // aon_mlp.hip
 
-template <bool POS, bool TRAIN, bool FOLD, bool VB = false>
+template <bool POS, bool TRAIN, bool FOLD, bool VB = false, bool GATHER = false>
 static hipError_t launch_art_tf(const ArtMlpArgs& args, hipStream_t stream) {
   static DeviceOnce lds_once;
-  if (hipError_t e = set_max_lds(&art_mlp_fwd_kernel<POS, TRAIN, FOLD, VB>, kALdsBytes, lds_once); e != hipSuccess) return e;
+  if (hipError_t e = set_max_lds(&art_mlp_fwd_kernel<POS, TRAIN, FOLD, VB, GATHER>, kALdsBytes, lds_once); e != hipSuccess) return e;
   const int cus = num_cus();
   if (cus <= 0) return hipErrorInvalidDevice;
   const int grid = args.npass_total < cus ? args.npass_total : cus;
   if (grid <= 0) return hipSuccess;
-  art_mlp_fwd_kernel<POS, TRAIN, FOLD, VB><<<dim3(grid), dim3(256), kALdsBytes, stream>>>(args);
+  art_mlp_fwd_kernel<POS, TRAIN, FOLD, VB, GATHER><<<dim3(grid), dim3(256), kALdsBytes, stream>>>(args);
   return hipGetLastError();
 }
 
 // the kernel of the form the launch's streams AND per-call blocks were made in; everything in one launch must agree
-template <bool POS, bool TRAIN>
+template <bool POS, bool TRAIN, bool GATHER = false>
 static hipError_t launch_art_t(const ArtMlpArgs& args, hipStream_t stream) {
   const int form = stream_form(args.seg[0].packed);
   if (form == kFormUnknown) return hipErrorInvalidValue;   // never packed / declared (a copy): refuse instead of guessing
@@ -525,11 +542,12 @@ static hipError_t launch_art_t(const ArtMlpArgs& args, hipStream_t stream) {
   if (args.seg[1].npass > 0 && (args.seg[1].view_bias != nullptr) != vb) return hipErrorInvalidValue;
   if (vb && form != kFormFolded) return hipErrorInvalidValue;
   if constexpr (POS) {
-    if (vb) return launch_art_tf<POS, TRAIN, true, true>(args, stream);
+    if (vb) return launch_art_tf<POS, TRAIN, true, true, GATHER>(args, stream);
   } else {
     if (vb) return hipErrorInvalidValue;
   }
-  return form == kFormFolded ? launch_art_tf<POS, TRAIN, true>(args, stream) : launch_art_tf<POS, TRAIN, false>(args, stream);
+  return form == kFormFolded ? launch_art_tf<POS, TRAIN, true, false, GATHER>(args, stream)
+                             : launch_art_tf<POS, TRAIN, false, false, GATHER>(args, stream);
 }
 
 hipError_t launch_view_bias_raw(const float* chunk, const float* bias_vec, const float* viewdirs, int64_t n_rays, float* out, hipStream_t stream);   // aon_mlp.hip
@@ -550,6 +568,19 @@ hipError_t launch_art_mlp_fwd(const char* packed, const float* small, const floa
   a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)((a.total + 127) / 128);
   args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
   return launch_art_t<true, false>(args, stream);
+}
+
+// launch_art_mlp_fwd on the samples of an occupancy list (aon_mlp_core.h): idx / count stay on the device
+hipError_t launch_art_mlp_fwd_gather(const char* packed, const float* small, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                     const float* t_vals, int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias,
+                                     const int* idx, const int64_t* count) {
+  ArtMlpArgs args{};
+  ArtSeg& a = args.seg[0];
+  a.packed = packed; a.small = small; a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.t_vals = t_vals; a.view_bias = view_bias;
+  a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)((a.total + 127) / 128);
+  a.gather_idx = idx; a.gather_count = count;
+  args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
+  return launch_art_t<true, false, true>(args, stream);
 }
 
 hipError_t launch_art_mlp_fwd_train2(const TrainSeg* segs, int nsegs, hipStream_t stream);

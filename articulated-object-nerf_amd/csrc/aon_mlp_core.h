@@ -661,6 +661,13 @@ __device__ __forceinline__ int viewenc_col(int q, int cc, int h) {
   return -1;
 }
 
+// ---- occupancy-grid inference (GATHER instances of mlp_fwd_kernel / art_mlp_fwd_kernel; aon_occ.hip) ----
+// Pass p of a GATHER launch evaluates samples idx[128 p .. 128 p + 127] of its one segment instead of 128 p .. 128 p + 127: ray, t, the
+// view bias and the raw record's address all follow the listed index.  The list's length is read from device memory (*count, written by
+// occ_scan_kernel on the same stream), so the launch needs no host synchronisation: it starts enough workgroups for the whole segment
+// and the persistent loop stops at ceil(*count / 128) passes.  idx / count share the segment's slots of the training planes / decision
+// bits (MlpSeg, ArtSeg), which an inference launch never reads: the kernel arguments keep their layout.
+
 // ---- density on a grid (density_grid_kernel, art_density_grid_kernel) ----
 struct GridArgs {
   const char* packed;      // the network's forward stream (either form: the grid kernels read chunks both forms share)

@@ -136,9 +136,23 @@ class NeRF_AE_Art(nn.Module):
         self.coarse_mlp = NeRFMLP(min_deg_point, max_deg_point, deg_view)
         self.fine_mlp = NeRFMLP(min_deg_point, max_deg_point, deg_view)
 
-    def forward(self, rays, randomized, white_bkgd, near, far, latents, train=True, t_rand=None, u=None, noise=None):
+    def forward(self, rays, randomized, white_bkgd, near, far, latents, train=True, t_rand=None, u=None, noise=None, occupancy=None):
+        """``occupancy`` (ops.OccupancyGrid built under the same latents, occupancy.build_occupancy): inference that skips every sample in an
+        empty cell of the grid; refused with randomized sampling or grad mode.  None: the exact path."""
         rays_o = rays["rays_o"]
         n = rays_o.shape[0]
+        if occupancy is not None:
+            if randomized:
+                raise ValueError("occupancy rendering is inference only: randomized=True is refused")
+            if torch.is_grad_enabled():
+                raise RuntimeError("occupancy rendering is inference only: call it under torch.no_grad()")
+            if self.noise_std > 0:
+                raise NotImplementedError("occupancy rendering takes no density noise (noise_std > 0)")
+            two = self.num_levels == 2
+            outs, _ = ops.art_render_fwd_occ(self.coarse_mlp.packed(), self.coarse_mlp.prepared(latents), self.fine_mlp.packed() if two else None,
+                                             self.fine_mlp.prepared(latents) if two else None, rays_o, rays["rays_d"], rays["viewdirs"], near, far,
+                                             white_bkgd, occupancy, self.num_levels, u, opts=self._opts)
+            return [tuple(o) for o in outs]
         # the stratified / inverse-CDF draws may ride in the batch dict (keys "aon_t_rand", "aon_u": an extension, namespaced so that a user batch carrying its own "u" / "t_rand" is never misread -- the reference's forward
         # ignores extra keys, model.py:299-306 -- that makes a harness run reproducible: tests/test_hip_long_training.py)
         if t_rand is None:
@@ -307,6 +321,22 @@ class LitNeRF_AutoDecoder(Harness):
 
     def configure_optimizers(self):
         return build_adam([self.model, self.code_library], self.lr_init)   # (model_autodecoder.py:604-606; one arena, one launch: LitNeRF)
+
+    @torch.no_grad()
+    def build_occupancies(self, instance_id: int = 0, bounds=(-1.2, 1.2), resolution=128, threshold: float = 0.01, dilate: int = 1,
+                          level: str = "fine") -> list:
+        """One occupancy grid per articulation state of the test epoch (the rows of get_interpolated_articulations, as extract_meshes) with the
+        shape / appearance codes of `instance_id`: the density depends on the latents (occupancy.build_occupancy for the arguments).  Grid a
+        goes with latents {"density": shape, "color": app, "articulation": table[a: a + 1]}."""
+        from ...occupancy import build_occupancy
+
+        dev = next(self.model.parameters()).device
+        iid = torch.tensor([int(instance_id)], dtype=torch.int64, device=dev)
+        shape = self.code_library.embedding_instance_shape(iid)
+        app = self.code_library.embedding_instance_appearance(iid)
+        table = self.code_library.get_interpolated_articulations(max_interpolations=2, device=dev)
+        return [build_occupancy(self.model, bounds, resolution, threshold, dilate, level=level,
+                                latents={"density": shape, "color": app, "articulation": table[a: a + 1]}) for a in range(table.shape[0])]
 
     @torch.no_grad()
     def extract_meshes(self, instance_id: int = 0, resolution: int = 256, bounds=(-1.0, 1.0), threshold: float | None = None, level: str = "fine",

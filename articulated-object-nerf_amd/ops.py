@@ -1545,3 +1545,121 @@ def marching_cubes(grid, level: float, lo, hi):
         check(lib.aon_marching_cubes(_ptr(g), d, C.c_float(level), (C.c_float * 3)(*lo32.tolist()), (C.c_float * 3)(*step.tolist()), _ptr(ws),
                                      nbytes, _ptr(verts), V, _ptr(faces), F, _stream()), "aon_marching_cubes")
     return verts, faces
+
+
+# ------------------------------------------------------------------ occupancy-grid accelerated inference
+class OccupancyGrid:
+    """A bitfield of the cells of a density grid that may hold matter (occupancy_grid): ``bits`` (int32 cuda tensor holding the uint32 words,
+    bit c & 31 of word c >> 5 for cell c in C order), ``cells`` (3 ints), fp32 ``lo`` / ``step`` (grid_step's values; the box ends at the last
+    grid point lo + cells * step) and the ``threshold`` / ``dilate`` it was built with."""
+
+    def __init__(self, bits: torch.Tensor, cells, lo, step, threshold: float, dilate: int):
+        self.bits, self.cells = bits, [int(c) for c in cells]
+        self.lo = torch.as_tensor(lo, dtype=torch.float32).cpu()
+        self.step = torch.as_tensor(step, dtype=torch.float32).cpu()
+        self.threshold, self.dilate = float(threshold), int(dilate)
+
+    @property
+    def device(self):
+        return self.bits.device
+
+    def c_struct(self):
+        st = _lib.OccupancyC()
+        st.bits = self.bits.data_ptr()
+        for a in range(3):
+            st.cells[a], st.lo[a], st.step[a] = self.cells[a], float(self.lo[a]), float(self.step[a])
+        return st
+
+    def occupied(self) -> torch.Tensor:
+        """(cx, cy, cz) bool tensor of the cells' bits (for inspection and tests)."""
+        n = self.cells[0] * self.cells[1] * self.cells[2]
+        w = self.bits.to(torch.int64) & 0xFFFFFFFF
+        sh = torch.arange(32, device=w.device, dtype=torch.int64)
+        b = ((w[:, None] >> sh) & 1).reshape(-1)[:n].to(torch.bool)
+        return b.view(*self.cells)
+
+    def occupied_fraction(self) -> float:
+        return float(self.occupied().float().mean())
+
+
+def occupancy_grid(density, lo, hi, threshold: float = 0.01, dilate: int = 1) -> OccupancyGrid:
+    """Occupancy bitfield of an ACTIVATED (nx, ny, nz) density grid spanning [lo, hi] (grid_points' coordinates), one launch: a cell (named by
+    its lowest corner) is occupied iff one of its 8 corner densities is above `threshold` or NaN, then dilated by `dilate` cells (Chebyshev)."""
+    d = _f32(density, "density")
+    if d.dim() != 3:
+        raise ValueError(f"occupancy_grid: expected an (nx, ny, nz) density grid, got shape {tuple(d.shape)}")
+    dims = list(d.shape)
+    if min(dims) < 2:
+        raise ValueError(f"occupancy_grid: every dimension must be >= 2 (cells = points - 1), got {dims}")
+    threshold, dilate = float(threshold), int(dilate)
+    if threshold != threshold or not 0 <= dilate <= 8:
+        raise ValueError("occupancy_grid: threshold must not be NaN and dilate must be in [0, 8]")
+    lo32, step = grid_step(dims, lo, hi)
+    if not bool((step > 0).all()):
+        raise ValueError(f"occupancy_grid: need lo < hi on every axis, got lo={lo}, hi={hi}")
+    cells = [n - 1 for n in dims]
+    nbytes = int(lib.aon_occupancy_bytes((C.c_int64 * 3)(*cells)))
+    if nbytes < 0:
+        check(nbytes, "aon_occupancy_bytes")
+    bits = torch.empty(nbytes // 4, dtype=torch.int32, device=d.device)
+    with torch.cuda.device(d.device):
+        check(lib.aon_occupancy_build(_ptr(d), (C.c_int64 * 3)(*dims), C.c_float(threshold), dilate, _ptr(bits), _stream()), "aon_occupancy_build")
+    return OccupancyGrid(bits, cells, lo32, step, threshold, dilate)
+
+
+_OCC_WS_CACHE: dict = {}
+
+
+def _occ_workspace(device, n_rays: int, st, workspace_bytes):
+    if workspace_bytes is not None:   # (tests: a workspace small enough to force chunking)
+        return torch.empty(int(workspace_bytes), dtype=torch.uint8, device=device)
+    need = int(lib.aon_render_occ_workspace_bytes(min(n_rays, MAX_CHUNK_RAYS), C.byref(st)))
+    if need < 0:
+        check(need, "aon_render_occ_workspace_bytes")
+    key = str(device)
+    ws = _OCC_WS_CACHE.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        _OCC_WS_CACHE[key] = ws
+    return ws
+
+
+def _occ_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, num_levels, u, opts, workspace_bytes):
+    if not isinstance(grid, OccupancyGrid):
+        raise TypeError(f"{name}: grid must be an ops.OccupancyGrid (ops.occupancy_grid), got {type(grid)}")
+    if num_levels not in (1, 2):
+        raise ValueError(f"{name}: num_levels must be 1 or 2")
+    o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
+    n, dev = o.shape[0], o.device
+    if grid.device != dev:
+        raise ValueError(f"{name}: the grid is on {grid.device}, the rays on {dev}")
+    op = _opts(opts)
+    if op.noise_std > 0:
+        raise ValueError(f"{name}: inference only, density noise (noise_std > 0) is refused")
+    uu, us = _u_args(u, n, dev, op.num_fine_samples) if num_levels == 2 else (None, 0)
+    outs = [tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in ((n, 3), (n,), (n,))) for _ in range(num_levels)]
+    fine = outs[1] if num_levels == 2 else (None, None, None)
+    st, keep = op.c_struct(near, far)
+    occ = grid.c_struct()
+    occupied = torch.zeros(2, dtype=torch.int64, device=dev)
+    ws = _occ_workspace(dev, n, st, workspace_bytes)
+    with torch.cuda.device(dev):
+        check(getattr(lib, name)(*packs, _ptr(o), _ptr(d), _ptr(v), n, float(near), float(far), int(bool(white_bkgd)), num_levels, None, _ptr(uu), us,
+                                 _ptr(outs[0][0]), _ptr(outs[0][1]), _ptr(outs[0][2]), _ptr(fine[0]), _ptr(fine[1]), _ptr(fine[2]),
+                                 _ptr(ws), ws.numel(), _stream(), C.byref(st), C.byref(occ), _ptr(occupied)), name)
+    return [tuple(x) for x in outs], occupied
+
+
+def render_fwd_occ(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid: OccupancyGrid, num_levels=2, u=None,
+                   opts=None, workspace_bytes=None):
+    """render_fwd (inference: no t_rand, no noise) with every sample in an empty cell of `grid` skipped: zero density, no MLP evaluation.
+    Returns (levels, occupied): the level tuples of render_fwd, and an int64 (2,) cuda tensor with the samples each level ran through the MLP."""
+    return _occ_call("aon_render_fwd_occ", (_pk(packed_coarse), _pk(packed_fine)), rays_o, rays_d, viewdirs, near, far, white_bkgd, grid,
+                     num_levels, u, opts, workspace_bytes)
+
+
+def art_render_fwd_occ(packed_c, small_c, packed_f, small_f, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid: OccupancyGrid, num_levels=2,
+                       u=None, opts=None, workspace_bytes=None):
+    """art_render_fwd with the occupancy skip of render_fwd_occ -> (levels, occupied)."""
+    return _occ_call("aon_art_render_fwd_occ", (_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f)), rays_o, rays_d, viewdirs, near, far,
+                     white_bkgd, grid, num_levels, u, opts, workspace_bytes)

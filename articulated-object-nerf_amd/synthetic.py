@@ -206,3 +206,22 @@ def random_rays(n: int, seed: int = 0, radius: float = 4.0):
     d = torch.from_numpy(d.astype(np.float32))
     d = d / torch.norm(d, dim=-1, keepdim=True)
     return {"rays_o": o, "rays_d": d, "viewdirs": d.clone()}
+
+
+def sparsify_nerf_(model, empty_fraction: float = 0.8, bound: float = 4.0, levels: int = 3):
+    """In place: a NeRF of these weights with the sparse density of an object in empty space (the occupancy-grid tests and benchmark,
+    DESIGN.md section 4.9).  The position encoding's levels >= `levels` are cut from both networks (zero columns of pts_linears.0 and the
+    skip layer pts_linears.5: the random weights' density is white noise at the top frequencies, 2^9 cycles per unit, which no grid of
+    corner samples bounds -- a trained object is not like that), then density_layer.bias is shifted so that `empty_fraction` of the grid
+    points of [-bound, bound]^3 have relu density <= 0.01."""
+    from . import ops
+
+    cut = [3 + 3 * lv + a + s for lv in range(levels, 10) for a in range(3) for s in (0, 30)]
+    with torch.no_grad():
+        for mlp in (model.coarse_mlp, model.fine_mlp):
+            mlp.pts_linears[0].weight[:, cut] = 0.0
+            mlp.pts_linears[5].weight[:, [256 + c for c in cut]] = 0.0
+            raw = ops.density_grid(mlp.packed(), (65, 65, 65), -bound, bound, ops.ACT_NONE)
+            q = torch.quantile(raw.reshape(-1)[::7].double(), empty_fraction).item()
+            mlp.density_layer.bias += 0.01 - q
+    return model

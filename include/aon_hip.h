@@ -26,7 +26,8 @@ extern "C" {
 #define AON_ABI_VERSION 5   /* 5: + aon_adam_step, aon_code_library_fwd / _bwd, aon_art_pack_step, aon_vanilla_pack_step, aon_stream_form, aon_declare_stream_form; a packed pointer this process never
                                packed or declared is refused (AON_E_INVALID / HIP "invalid value") instead of being taken to have the default form;
                                later additions that change no existing call, so the version stays: aon_ssim, aon_ssim_workspace_bytes,
-                               aon_density_grid, aon_art_density_grid, aon_marching_cubes_workspace_bytes, aon_marching_cubes_count, aon_marching_cubes */
+                               aon_density_grid, aon_art_density_grid, aon_marching_cubes_workspace_bytes, aon_marching_cubes_count, aon_marching_cubes,
+                               aon_occupancy_bytes, aon_occupancy_build, aon_render_occ_workspace_bytes, aon_render_fwd_occ, aon_art_render_fwd_occ */
 
 #define AON_OK 0
 #define AON_E_INVALID (-1)    /* null pointer, negative size, unsupported geometry */
@@ -523,6 +524,37 @@ int aon_art_render_fwd_ex(const void* packed_coarse, const void* small_coarse, c
                           int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
                           float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
                           int64_t workspace_bytes, void* stream, const aon_render_opts* opts);
+/* ---- occupancy-grid accelerated inference ----
+ * A bitfield of the cells of a density grid (aon_density_grid over [lo, hi], dims (nx, ny, nz)) that may hold matter: (nx-1, ny-1, nz-1)
+ * cells, cell (i, j, k) named by its lowest corner, bit c = (i (ny-1) + j) (nz-1) + k, bit c & 31 of uint32 word c >> 5.
+ * aon_occupancy_build: a cell is occupied iff one of its 8 corner densities is above `threshold` or NaN; the result is dilated by
+ *   `dilate` (0 .. 8) cells, a Chebyshev max filter.  `density`: the ACTIVATED (nx, ny, nz) grid; `bits`: aon_occupancy_bytes(cells) bytes.
+ * aon_render_fwd_occ / aon_art_render_fwd_occ: aon_render_fwd_ex / aon_art_render_fwd_ex (same arguments) with every sample in an empty
+ *   cell skipped: the MLP never runs on it and its raw record is (0, 0, 0, -inf), i.e. zero density under both activations.  Sample x =
+ *   o + t d lies in cell floor((x_a - lo_a) / step_a) per axis (fp32, IEEE division), clamped to cells_a - 1; a coordinate outside
+ *   [lo_a, lo_a + cells_a step_a] or NaN is empty.  Inference only: t_rand, density noise and other encoding degrees of a vanilla network
+ *   are refused (AON_E_INVALID).  `occupied_dev` (device, (2,) int64, or NULL) receives the samples each level ran through the MLP.
+ *   Stream-ordered, no synchronisation.  workspace: aon_render_occ_workspace_bytes(n_rays, opts) bytes for one chunk of n_rays. */
+typedef struct aon_occupancy {
+  const uint32_t* bits;   /* device */
+  int64_t cells[3];       /* nx-1, ny-1, nz-1 */
+  float lo[3];
+  float step[3];          /* > 0 */
+} aon_occupancy;
+int64_t aon_occupancy_bytes(const int64_t* cells3_host);
+int aon_occupancy_build(const float* density, const int64_t* dims3_host, float threshold, int dilate, uint32_t* bits, void* stream);
+int64_t aon_render_occ_workspace_bytes(int64_t n_rays, const aon_render_opts* opts);
+int aon_render_fwd_occ(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                       const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                       const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                       float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                       const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev);
+int aon_art_render_fwd_occ(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                           const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                           int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                           float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                           int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
+                           int64_t* occupied_dev);
 /* training twins: the SAME opts (sizes, noise pointers, activation scalars) must be handed to the forward, the backward and the
  * two size queries of one step */
 int64_t aon_train_workspace_bytes_ex(int64_t n_rays, int articulated, int num_levels, const aon_render_opts* opts);

@@ -95,6 +95,10 @@ _SIGS = {
     "aon_render_occ_workspace_bytes": (_l, [_l, _p]),
     "aon_render_fwd_occ": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p]),
     "aon_art_render_fwd_occ": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p]),
+    "aon_render_stop_workspace_bytes": (_l, [_l, _p]),
+    "aon_render_fwd_stop": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _f, _i, _p]),
+    "aon_art_render_fwd_stop": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p,
+                                     _f, _i, _p]),
     "aon_art_pack_step": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "aon_vanilla_pack_step": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
     "aon_set_bwd_early_heads": (_i, [_i]),

@@ -126,10 +126,20 @@ int64_t occ_list_bytes(int64_t total);
 hipError_t launch_occ_compact(const OccGrid& G, const float* rays_o, const float* rays_d, const float* t_vals, int64_t n, int S, float* raw,
                               char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out, hipStream_t stream);
 hipError_t launch_mlp_fwd_gather(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_vals,
-                                 int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias, const int* idx, const int64_t* count);
+                                 int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias, const int* idx, const int64_t* count,
+                                 int64_t max_listed = 0);
 hipError_t launch_art_mlp_fwd_gather(const char* packed, const float* small, const float* rays_o, const float* rays_d, const float* viewdirs,
                                      const float* t_vals, int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias,
-                                     const int* idx, const int64_t* count);
+                                     const int* idx, const int64_t* count, int64_t max_listed = 0);
+int64_t occ_stop_state_bytes(int64_t n);
+hipError_t launch_occ_stop_init(char* state, int64_t n, int S, hipStream_t stream);
+hipError_t launch_occ_stop_store(const char* state, int value, int* dst, int64_t n, int stride, hipStream_t stream);
+hipError_t launch_occ_tally_set(int64_t* tally, int64_t v0, int64_t v1, hipStream_t stream);
+hipError_t launch_occ_compact_round(const OccGrid& G, const float* rays_o, const float* rays_d, const float* t_vals, int64_t n, int S, int s0, int s1,
+                                    const char* state, float* raw, char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out,
+                                    hipStream_t stream);
+hipError_t launch_occ_depth(const float* raw, const float* t_vals, const float* dirs, int64_t n, int S, int s0, int s1, const ActParams& ap,
+                            float tau_stop, char* state, hipStream_t stream);
 }  // namespace aon
 
 namespace {
@@ -255,10 +265,11 @@ struct Ws {
   float* coords; float* enc; float* venc;   // other_degrees only: n*Sf*3, n*Sf*63, n*27
   float* vbias;   // n*128: the level's per-ray view bias (vanilla, folded form; launch_view_bias) -- both levels in turn
   char* occ;      // [occupancy] the level's sample list, tile counts and list length (aon::occ_list_bytes of n*Sf) -- both levels in turn
+  char* stop;     // [early termination] the level's per-ray tau and stop index (aon::occ_stop_state_bytes of n) -- both levels in turn
   int64_t bytes;
 };
 
-Ws carve(char* base, int64_t n, const Geo& g, bool occ = false) {
+Ws carve(char* base, int64_t n, const Geo& g, bool occ = false, bool stop = false) {
   Ws w{};
   int64_t off = 0;
   w.t_c = reinterpret_cast<float*>(base + off); off += align_up(n * g.Sc * 4, 256);
@@ -273,6 +284,7 @@ Ws carve(char* base, int64_t n, const Geo& g, bool occ = false) {
     w.vbias = reinterpret_cast<float*>(base + off); off += align_up(n * (int64_t)aon::kCondWidth * 4, 256);
   }
   if (occ) { w.occ = base + off; off += aon::occ_list_bytes(n * g.Sf); }
+  if (stop) { w.stop = base + off; off += aon::occ_stop_state_bytes(n); }
   w.bytes = off;
   return w;
 }
@@ -888,9 +900,15 @@ struct NetRef {
 
 // An occupancy grid handed to aon_render_fwd_occ / aon_art_render_fwd_occ: the kernels' view of it, and the
 // caller's per-level tally of samples run through the MLP (or null)
+// [early termination, DESIGN.md section 4.10] rounds: the level runs front to back in rounds of R samples and a ray stops once its optical
+// depth reaches tau_stop; grid.bits may then be null (no grid: every live sample is listed).  stop_dev: the caller's (n_rays, 2) map or null
 struct OccCtx {
   aon::OccGrid grid;
   int64_t* tally;
+  bool rounds;
+  float tau_stop;
+  int R;
+  int32_t* stop_dev;
 };
 
 // occ: mark the level's samples, compact the occupied ones into a list (aon_occ.hip) and run the MLP on that list alone (the GATHER
@@ -915,6 +933,32 @@ static hipError_t launch_net(const NetRef& net, const float* o, const float* d, 
                                          : aon::launch_view_bias(static_cast<const char*>(net.packed), v, n, w->vbias, stream);
     if (e != hipSuccess) return e;
     vbias = w->vbias;
+  }
+  if (occ && occ->rounds) {
+    // per round: mark -> scan -> emit -> the GATHER launch on the round's list -> the live rays' optical depth; all stream-ordered
+    if (hipError_t e = aon::launch_occ_stop_init(w->stop, n, S, stream); e != hipSuccess) return e;
+    const int R = occ->R < S ? occ->R : S;
+    const aon::ActParams ap = g->act(net.articulated, level, 0);   // (no noise on this path)
+    for (int s0 = 0; s0 < S; s0 += R) {
+      const int s1 = s0 + R < S ? s0 + R : S;
+      const int* idx = nullptr;
+      const int64_t* count = nullptr;
+      if (hipError_t e = aon::launch_occ_compact_round(occ->grid, o, d, t, n, S, s0, s1, w->stop, raw, w->occ, occ->tally ? occ->tally + level : nullptr,
+                                                       &idx, &count, stream);
+          e != hipSuccess)
+        return e;
+      {
+        MlpTimer timer(stream, n * (s1 - s0));
+        const hipError_t e = net.articulated ? aon::launch_art_mlp_fwd_gather(static_cast<const char*>(net.packed), net.small, o, d, v, t, n, S, raw, stream,
+                                                                              vbias, idx, count, n * (s1 - s0))
+                                             : aon::launch_mlp_fwd_gather(static_cast<const char*>(net.packed), o, d, v, t, n, S, raw, stream, vbias, idx,
+                                                                          count, n * (s1 - s0));
+        if (e != hipSuccess) return e;
+      }
+      if (s1 < S)   // the last round (sample S-1 and its 1e10 interval) decides nothing
+        if (hipError_t e = aon::launch_occ_depth(raw, t, d, n, S, s0, s1, ap, occ->tau_stop, w->stop, stream); e != hipSuccess) return e;
+    }
+    return hipSuccess;
   }
   if (occ) {
     const int* idx = nullptr;
@@ -954,20 +998,22 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
   if (art) g.other_degrees = false;   // the articulated kernels carry their degrees in the packed stream and the small block (aon_*_deg)
   const bool fuse_coarse = num_levels == 2 && g.default_sizes && g_fuse_coarse.load(std::memory_order_relaxed) != 0;
   const bool with_occ = occ != nullptr;
+  const bool with_stop = with_occ && occ->rounds;
 
   // largest chunk the workspace admits ([occupancy] and whose sample indices fit the int32 list)
   int64_t chunk = n_rays;
   if (with_occ && chunk > INT32_MAX / g.Sf) chunk = INT32_MAX / g.Sf;
-  if (carve(nullptr, chunk, g, with_occ).bytes > workspace_bytes) {
+  if (carve(nullptr, chunk, g, with_occ, with_stop).bytes > workspace_bytes) {
     const int64_t per_ray = (int64_t)(g.Sc + g.Sc + g.Sf + 4 * g.Sf + (g.other_degrees ? (3 + aon::kPosEnc) * g.Sf + aon::kViewEnc : aon::kCondWidth) +
-                                      (with_occ ? g.Sf + 2 * (g.Sf / 1024 + 1) : 0)) * 4;
-    const int64_t slack = (g.other_degrees ? 7 * 256 : 5 * 256) + (with_occ ? 4 * 256 : 0);
+                                      (with_occ ? g.Sf + 2 * (g.Sf / 1024 + 1) : 0) + (with_stop ? 2 : 0)) * 4;
+    const int64_t slack = (g.other_degrees ? 7 * 256 : 5 * 256) + (with_occ ? 4 * 256 : 0) + (with_stop ? 2 * 256 : 0);
     chunk = (workspace_bytes - slack) / per_ray;
-    while (chunk > 0 && carve(nullptr, chunk, g, with_occ).bytes > workspace_bytes) --chunk;
-    if (chunk < 1) return fail(AON_E_WORKSPACE, with_occ ? "render: workspace smaller than aon_render_occ_workspace_bytes(1)"
+    while (chunk > 0 && carve(nullptr, chunk, g, with_occ, with_stop).bytes > workspace_bytes) --chunk;
+    if (chunk < 1) return fail(AON_E_WORKSPACE, with_stop ? "render: workspace smaller than aon_render_stop_workspace_bytes(1)"
+                                                : with_occ ? "render: workspace smaller than aon_render_occ_workspace_bytes(1)"
                                                          : "render: workspace smaller than aon_render_workspace_bytes(1)");
   }
-  const Ws w = carve(static_cast<char*>(workspace), chunk, g, with_occ);
+  const Ws w = carve(static_cast<char*>(workspace), chunk, g, with_occ, with_stop);
   if (with_occ && occ->tally) {
     if (int rc = check(hipMemsetAsync(occ->tally, 0, 2 * sizeof(int64_t), stream), who); rc != AON_OK) return rc;
   }
@@ -988,6 +1034,10 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
     if (rc) return rc;
     rc = check(launch_net(coarse, o, d, v, w.t_c, n, g.Sc, w.raw, stream, &g, &w, occ, 0), who);
     if (rc) return rc;
+    if (with_stop && occ->stop_dev) {
+      rc = check(aon::launch_occ_stop_store(w.stop, 0, occ->stop_dev + r0 * 2, n, 2, stream), who);
+      if (rc) return rc;
+    }
     if (fuse_coarse) {
       // compositing + the fine level's sampling (model.py:162-173) in one kernel: the coarse weights stay in registers
       KTimer timer(kCompositePdf, stream, n);
@@ -1010,6 +1060,10 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
     }
     rc = check(launch_net(fine, o, d, v, w.t_f, n, g.Sf, w.raw, stream, &g, &w, occ, 1), who);
     if (rc) return rc;
+    if (with_stop && occ->stop_dev) {
+      rc = check(aon::launch_occ_stop_store(w.stop, 0, occ->stop_dev + r0 * 2 + 1, n, 2, stream), who);
+      if (rc) return rc;
+    }
     {
       KTimer timer(kComposite, stream, n);
       rc = check(aon::launch_composite(w.raw, 4, w.raw + 3, 4, w.t_f, d, n, g.Sf, white_bkgd, g.act(art, 1, r0), rgb_f + r0 * 3, acc_f + r0,
@@ -1099,6 +1153,59 @@ int aon_render_fwd_occ(const void* packed_coarse, const void* packed_fine, const
   const NetRef c{false, packed_coarse, nullptr}, f{false, packed_fine, nullptr};
   return render_impl("aon_render_fwd_occ", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
                      u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, &ctx);
+}
+
+// ---- early ray termination on the occupancy renders ----
+int64_t aon_render_stop_workspace_bytes(int64_t n_rays, const aon_render_opts* opts) {
+  if (n_rays < 1) n_rays = 1;
+  Geo g;
+  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
+  if (n_rays > INT32_MAX / g.Sf) n_rays = INT32_MAX / g.Sf;
+  return carve(nullptr, n_rays, g, true, true).bytes;
+}
+// the checks and the eps == 0 route shared by aon_render_fwd_stop / aon_art_render_fwd_stop
+static int render_stop(const char* who, const NetRef& c, const NetRef& f, const float* rays_o, const float* rays_d, const float* viewdirs,
+                       int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels, const float* t_rand, const float* u,
+                       int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                       int64_t workspace_bytes, hipStream_t stream, const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev,
+                       float eps, int round_samples, int32_t* stop_dev) {
+  OccCtx ctx{};
+  if (occ)
+    if (const char* bad = occ_grid_bad(occ, ctx.grid)) return fail(AON_E_INVALID, (std::string(who) + ": " + bad).c_str());
+  if (const char* bad = occ_opts_bad(opts, c.articulated, t_rand)) return fail(AON_E_INVALID, (std::string(who) + ": " + bad).c_str());
+  if (!(eps >= 0.f && eps < 1.f)) return fail(AON_E_INVALID, (std::string(who) + ": eps must be in [0, 1)").c_str());
+  if (round_samples < 1) return fail(AON_E_INVALID, (std::string(who) + ": round_samples must be >= 1").c_str());
+  ctx.tally = occupied_dev;
+  if (eps == 0.f) {   // off: today's single-launch paths, and the bookkeeping of a render in which no ray stopped
+    const int rc = render_impl(who, c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c,
+                               depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, opts, occ ? &ctx : nullptr);
+    if (rc != AON_OK || n_rays == 0) return rc;
+    Geo g;
+    (void)make_geo(opts, g);
+    if (!occ && occupied_dev)
+      if (int r2 = check(aon::launch_occ_tally_set(occupied_dev, n_rays * g.Sc, num_levels == 2 ? n_rays * g.Sf : 0, stream), who); r2 != AON_OK) return r2;
+    if (stop_dev)
+      for (int l = 0; l < num_levels; ++l)
+        if (int r2 = check(aon::launch_occ_stop_store(nullptr, g.S(l), stop_dev + l, n_rays, 2, stream), who); r2 != AON_OK) return r2;
+    return AON_OK;
+  }
+  ctx.rounds = true;
+  ctx.tau_stop = (float)(-std::log((double)eps));   // fp64, rounded once
+  ctx.R = round_samples;
+  ctx.stop_dev = stop_dev;
+  return render_impl(who, c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c,
+                     rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, opts, &ctx);
+}
+int aon_render_fwd_stop(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                        const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                        const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                        float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                        const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev, float eps, int round_samples,
+                        int32_t* stop_dev) {
+  const NetRef c{false, packed_coarse, nullptr}, f{false, packed_fine, nullptr};
+  return render_stop("aon_render_fwd_stop", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c,
+                     acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, occ, occupied_dev, eps,
+                     round_samples, stop_dev);
 }
 
 // ---- training step in two calls (aon_render_fwd_train + aon_render_bwd) ----
@@ -2025,6 +2132,17 @@ int aon_art_render_fwd_occ(const void* packed_coarse, const void* small_coarse, 
   const NetRef c{true, packed_coarse, static_cast<const float*>(small_coarse)}, f{true, packed_fine, static_cast<const float*>(small_fine)};
   return render_impl("aon_art_render_fwd_occ", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
                      u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, &ctx);
+}
+int aon_art_render_fwd_stop(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                            const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                            int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                            float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                            int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
+                            int64_t* occupied_dev, float eps, int round_samples, int32_t* stop_dev) {
+  const NetRef c{true, packed_coarse, static_cast<const float*>(small_coarse)}, f{true, packed_fine, static_cast<const float*>(small_fine)};
+  return render_stop("aon_art_render_fwd_stop", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride,
+                     rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, occ, occupied_dev, eps,
+                     round_samples, stop_dev);
 }
 int aon_art_render_fwd(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
                        const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,

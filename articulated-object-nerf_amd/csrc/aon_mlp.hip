@@ -507,13 +507,15 @@ hipError_t launch_mlp_fwd(const char* packed, const float* rays_o, const float* 
   return launch_mlp_t<true, false>(args, stream);
 }
 
-// launch_mlp_fwd on the samples of an occupancy list (aon_mlp_core.h): idx / count stay on the device
+// launch_mlp_fwd on the samples of an occupancy list (aon_mlp_core.h): idx / count stay on the device.  max_listed > 0: an upper bound of
+// *count below n_rays * S (a round of the early-termination loop lists a sub-range of every ray), which only sizes the grid.
 hipError_t launch_mlp_fwd_gather(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_vals,
-                                 int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias, const int* idx, const int64_t* count) {
+                                 int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias, const int* idx, const int64_t* count,
+                                 int64_t max_listed) {
   MlpArgs args{};
   MlpSeg& a = args.seg[0];
   a.packed = packed; a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.t_vals = t_vals; a.view_bias = view_bias;
-  a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)((a.total + 127) / 128);
+  a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)(((max_listed > 0 ? max_listed : a.total) + 127) / 128);
   a.gather_idx = idx; a.gather_count = count;
   args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
   return launch_mlp_t<true, false, true>(args, stream);

@@ -180,4 +180,181 @@ hipError_t launch_occ_compact(const OccGrid& G, const float* rays_o, const float
   return hipGetLastError();
 }
 
+// ---- early ray termination (tests/_stop_ref.py is an independent numpy copy) ----
+// A level is evaluated front to back in rounds of R consecutive sample indices; round k covers [kR, min(S, (k+1)R)) of every ray.  Per ray:
+// tau (fp32, 0 at the start of the level) and stop (int32, S at the start).  After round k's MLP launch a ray with stop == S adds
+// sigma_i * delta_i of the round's samples to tau in ascending i -- one sequential fp32 chain, every multiply and add rounded -- with
+// sigma_i / delta_i as composite_kernel (aon_render.hip) forms them, and stops (stop = (k+1)R) when tau >= tau_stop = fp32(-ln eps).
+// In a later round a sample i >= stop[ray] is DEAD: the sentinel record, not listed.  The last round decides nothing (no depth launch).
+struct OccRound {
+  const int* stop;   // (n,)
+  int s0, s1;        // the round's sample indices [s0, s1) of every ray
+  int64_t count;     // n * (s1 - s0)
+};
+
+// tile slot q -> ray q / (s1 - s0), sample s0 + q % (s1 - s0); a null grid: every cell occupied
+__device__ __forceinline__ int occ_round_flags(const OccGrid& G, const OccSamples& s, const OccRound& rd, int64_t q0, bool (&occ)[4], int64_t (&gi)[4]) {
+  const int w = rd.s1 - rd.s0;
+  int n = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int64_t q = q0 + r;
+    occ[r] = false;
+    gi[r] = -1;
+    if (q >= rd.count) continue;
+    const int64_t ray = q / w;
+    const int i = rd.s0 + (int)(q - ray * w);
+    const int64_t g = ray * s.S + i;
+    gi[r] = g;
+    if (rd.stop[ray] <= i) continue;   // dead: behind the ray's stop
+    if (G.bits) {
+      const float t = s.t_vals[g];
+      float x[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) x[a] = __fadd_rn(s.rays_o[ray * 3 + a], __fmul_rn(t, s.rays_d[ray * 3 + a]));
+      occ[r] = occ_lookup(G, x);
+    } else {
+      occ[r] = true;
+    }
+    n += occ[r] ? 1 : 0;
+  }
+  return n;
+}
+
+__global__ __launch_bounds__(kOccThreads) void occ_mark_round_kernel(OccGrid G, OccSamples s, OccRound rd, f32x4* __restrict__ raw,
+                                                                     int* __restrict__ tile_counts) {
+  __shared__ int red[kOccThreads / 64];
+  const int64_t q0 = (int64_t)blockIdx.x * kOccTile + 4 * threadIdx.x;
+  bool occ[4];
+  int64_t gi[4];
+  const int n = occ_round_flags(G, s, rd, q0, occ, gi);
+  f32x4 sentinel;
+  sentinel[0] = 0.f; sentinel[1] = 0.f; sentinel[2] = 0.f; sentinel[3] = -__builtin_huge_valf();
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (gi[r] >= 0 && !occ[r]) raw[gi[r]] = sentinel;
+  int tot;
+  block_excl_scan<int>(n, tot, red);
+  if (threadIdx.x == 0) tile_counts[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(kOccThreads) void occ_emit_round_kernel(OccGrid G, OccSamples s, OccRound rd, const int* __restrict__ offs,
+                                                                     int* __restrict__ idx) {
+  __shared__ int red[kOccThreads / 64];
+  const int64_t q0 = (int64_t)blockIdx.x * kOccTile + 4 * threadIdx.x;
+  bool occ[4];
+  int64_t gi[4];
+  const int n = occ_round_flags(G, s, rd, q0, occ, gi);
+  int tot;
+  int run = offs[blockIdx.x] + block_excl_scan<int>(n, tot, red);
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (occ[r]) idx[run++] = (int)gi[r];   // ascending: q ascends with (ray, i)
+}
+
+// tau[ray] = 0, stop[ray] = S
+__global__ __launch_bounds__(kOccThreads) void occ_stop_init_kernel(float* __restrict__ tau, int* __restrict__ stop, int64_t n, int S) {
+  const int64_t ray = (int64_t)blockIdx.x * kOccThreads + threadIdx.x;
+  if (ray < n) { tau[ray] = 0.f; stop[ray] = S; }
+}
+
+// dst[ray * stride] = src ? src[ray] : value (the caller's (n_rays, 2) stop map, one level's column)
+__global__ __launch_bounds__(kOccThreads) void occ_stop_store_kernel(const int* __restrict__ src, int value, int* __restrict__ dst, int64_t n, int stride) {
+  const int64_t ray = (int64_t)blockIdx.x * kOccThreads + threadIdx.x;
+  if (ray < n) dst[ray * stride] = src ? src[ray] : value;
+}
+
+// The optical depth of a round: one wavefront per live ray.  The lanes fetch the round's records (one contiguous 16 B x (s1 - s0) run per
+// ray) and t values and form sigma_i * delta_i in parallel; the sum is then taken in ascending i by one lane-by-lane chain, the bits of a
+// sequential loop.  A stopped ray's wave leaves at once, so the cost follows the live rays.
+__global__ __launch_bounds__(kOccThreads) void occ_depth_kernel(const f32x4* __restrict__ raw, const float* __restrict__ t_vals,
+                                                                const float* __restrict__ dirs, int64_t n, int S, int s0, int s1, ActParams ap,
+                                                                float tau_stop, float* __restrict__ tau, int* __restrict__ stop) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ray = (int64_t)blockIdx.x * (kOccThreads / 64) + (threadIdx.x >> 6);
+  if (ray >= n) return;              // wave-uniform
+  if (stop[ray] != S) return;        // stopped in an earlier round
+  const float dn = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dirs[ray * 3], dirs[ray * 3]), __fmul_rn(dirs[ray * 3 + 1], dirs[ray * 3 + 1])),
+                                        __fmul_rn(dirs[ray * 3 + 2], dirs[ray * 3 + 2])));
+  const float* tv = t_vals + ray * S;
+  float acc = tau[ray];
+  for (int base = s0; base < s1; base += 64) {
+    const int i = base + lane;
+    float p = 0.f;
+    if (i < s1) {
+      float sg = raw[ray * S + i][3];
+      if (ap.act == 1) sg = __builtin_fmaxf(sg, 0.f);
+      else if (ap.act == 2) sg = softplus_f32(__fadd_rn(sg, ap.sigma_bias));
+      const float dist = i < S - 1 ? __fmul_rn(__fsub_rn(tv[i + 1], tv[i]), dn) : __fmul_rn(1e10f, dn);
+      p = __fmul_rn(sg, dist);
+    }
+    const int cnt = s1 - base < 64 ? s1 - base : 64;
+    for (int j = 0; j < cnt; ++j) acc = __fadd_rn(acc, __shfl(p, j));
+  }
+  if (lane == 0) {
+    tau[ray] = acc;
+    if (acc >= tau_stop) stop[ray] = s1;   // NaN compares false: never stops
+  }
+}
+
+// the per-level tally of a render that lists every sample (eps == 0 without a grid)
+__global__ void occ_tally_set_kernel(int64_t* __restrict__ tally, int64_t v0, int64_t v1) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) { tally[0] = v0; tally[1] = v1; }
+}
+hipError_t launch_occ_tally_set(int64_t* tally, int64_t v0, int64_t v1, hipStream_t stream) {
+  occ_tally_set_kernel<<<dim3(1), dim3(64), 0, stream>>>(tally, v0, v1);
+  return hipGetLastError();
+}
+
+int64_t occ_stop_state_bytes(int64_t n) { return (n * 4 + 255) / 256 * 256 * 2; }   // tau, stop
+
+hipError_t launch_occ_stop_init(char* state, int64_t n, int S, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  float* tau = reinterpret_cast<float*>(state);
+  int* stop = reinterpret_cast<int*>(state + (n * 4 + 255) / 256 * 256);
+  occ_stop_init_kernel<<<dim3((unsigned)((n + kOccThreads - 1) / kOccThreads)), dim3(kOccThreads), 0, stream>>>(tau, stop, n, S);
+  return hipGetLastError();
+}
+
+// state == nullptr: fill with `value`
+hipError_t launch_occ_stop_store(const char* state, int value, int* dst, int64_t n, int stride, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  const int* stop = state ? reinterpret_cast<const int*>(state + (n * 4 + 255) / 256 * 256) : nullptr;
+  occ_stop_store_kernel<<<dim3((unsigned)((n + kOccThreads - 1) / kOccThreads)), dim3(kOccThreads), 0, stream>>>(stop, value, dst, n, stride);
+  return hipGetLastError();
+}
+
+// launch_occ_compact over the sub-range [s0, s1) of every ray, minus the dead samples.  G.bits == nullptr: no grid.
+hipError_t launch_occ_compact_round(const OccGrid& G, const float* rays_o, const float* rays_d, const float* t_vals, int64_t n, int S, int s0, int s1,
+                                    const char* state, float* raw, char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out,
+                                    hipStream_t stream) {
+  const OccSamples s{rays_o, rays_d, t_vals, n * S, S};
+  const OccRound rd{reinterpret_cast<const int*>(state + (n * 4 + 255) / 256 * 256), s0, s1, n * (s1 - s0)};
+  const int64_t tiles = (rd.count + kOccTile - 1) / kOccTile;
+  const int64_t full_tiles = (s.total + kOccTile - 1) / kOccTile;   // the buffers keep launch_occ_compact's layout
+  int* idx = reinterpret_cast<int*>(ws);
+  int* counts = reinterpret_cast<int*>(ws + (s.total * 4 + 255) / 256 * 256);
+  int* offs = counts + (full_tiles * 4 + 255) / 256 * 64;
+  int64_t* count = reinterpret_cast<int64_t*>(offs + (full_tiles * 4 + 255) / 256 * 64);
+  *idx_out = idx; *count_out = count;
+  if (tiles == 0) return hipMemsetAsync(count, 0, 8, stream);
+  occ_mark_round_kernel<<<dim3((unsigned)tiles), dim3(kOccThreads), 0, stream>>>(G, s, rd, reinterpret_cast<f32x4*>(raw), counts);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  occ_scan_kernel<<<dim3(1), dim3(kOccThreads), 0, stream>>>(counts, tiles, offs, count, tally);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  occ_emit_round_kernel<<<dim3((unsigned)tiles), dim3(kOccThreads), 0, stream>>>(G, s, rd, offs, idx);
+  return hipGetLastError();
+}
+
+hipError_t launch_occ_depth(const float* raw, const float* t_vals, const float* dirs, int64_t n, int S, int s0, int s1, const ActParams& ap,
+                            float tau_stop, char* state, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  float* tau = reinterpret_cast<float*>(state);
+  int* stop = reinterpret_cast<int*>(state + (n * 4 + 255) / 256 * 256);
+  constexpr int kRays = kOccThreads / 64;
+  occ_depth_kernel<<<dim3((unsigned)((n + kRays - 1) / kRays)), dim3(kOccThreads), 0, stream>>>(reinterpret_cast<const f32x4*>(raw), t_vals, dirs, n, S,
+                                                                                               s0, s1, ap, tau_stop, tau, stop);
+  return hipGetLastError();
+}
+
 }  // namespace aon

@@ -270,13 +270,15 @@ class NeRF(nn.Module):
             ret.append((comp, acc, depth))
         return ret
 
-    def forward(self, rays, randomized, white_bkgd, near, far, t_rand=None, u=None, noise=None, occupancy=None):
+    def forward(self, rays, randomized, white_bkgd, near, far, t_rand=None, u=None, noise=None, occupancy=None, early_stop=None):
         """``occupancy`` (ops.OccupancyGrid, occupancy.build_occupancy): inference that skips every sample in an empty cell of the grid
-        (DESIGN.md section 4.9); refused with randomized sampling or grad mode.  None: the exact path."""
+        (DESIGN.md section 4.9); refused with randomized sampling or grad mode.  None: the exact path.
+        ``early_stop`` (eps in [0, 1), with or without a grid): a ray stops once its transmittance has fallen to eps (DESIGN.md section
+        4.10); the same refusals.  None: no termination."""
         rays_o = rays["rays_o"]
         n = rays_o.shape[0]
-        if occupancy is not None:
-            return self._forward_occupancy(rays, randomized, white_bkgd, near, far, u, occupancy)
+        if occupancy is not None or early_stop is not None:
+            return self._forward_occupancy(rays, randomized, white_bkgd, near, far, u, occupancy, early_stop)
         # the stratified / inverse-CDF draws may ride in the batch dict (keys "aon_t_rand", "aon_u": an extension, namespaced so that a user batch carrying its own "u" / "t_rand" is never misread -- the reference's forward
         # ignores extra keys, model.py:299-306 -- that makes a harness run reproducible: tests/test_hip_long_training.py)
         if t_rand is None:
@@ -345,7 +347,7 @@ class NeRF(nn.Module):
                               white_bkgd, self.num_levels, t_rand, u, opts=self._opts, noise=noise)
         return [tuple(o) for o in outs]
 
-    def _forward_occupancy(self, rays, randomized, white_bkgd, near, far, u, occupancy):
+    def _forward_occupancy(self, rays, randomized, white_bkgd, near, far, u, occupancy, early_stop=None):
         if randomized:
             raise ValueError("occupancy rendering is inference only: randomized=True is refused")
         if torch.is_grad_enabled():
@@ -354,6 +356,11 @@ class NeRF(nn.Module):
             raise NotImplementedError("occupancy rendering serves the default network geometry and encoding degrees with 1 or 2 levels")
         if self.noise_std > 0:
             raise NotImplementedError("occupancy rendering takes no density noise (noise_std > 0)")
+        if early_stop is not None:
+            outs, _, _ = ops.render_fwd_stop(self.coarse_mlp.packed(), self.fine_mlp.packed() if self.num_levels == 2 else None, rays["rays_o"],
+                                             rays["rays_d"], rays["viewdirs"], near, far, white_bkgd, occupancy, early_stop,
+                                             num_levels=self.num_levels, u=u, opts=self._opts)
+            return [tuple(o) for o in outs]
         outs, _ = ops.render_fwd_occ(self.coarse_mlp.packed(), self.fine_mlp.packed() if self.num_levels == 2 else None, rays["rays_o"],
                                      rays["rays_d"], rays["viewdirs"], near, far, white_bkgd, occupancy, self.num_levels, u, opts=self._opts)
         return [tuple(o) for o in outs]

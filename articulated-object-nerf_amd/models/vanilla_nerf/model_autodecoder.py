@@ -136,12 +136,15 @@ class NeRF_AE_Art(nn.Module):
         self.coarse_mlp = NeRFMLP(min_deg_point, max_deg_point, deg_view)
         self.fine_mlp = NeRFMLP(min_deg_point, max_deg_point, deg_view)
 
-    def forward(self, rays, randomized, white_bkgd, near, far, latents, train=True, t_rand=None, u=None, noise=None, occupancy=None):
+    def forward(self, rays, randomized, white_bkgd, near, far, latents, train=True, t_rand=None, u=None, noise=None, occupancy=None,
+                early_stop=None):
         """``occupancy`` (ops.OccupancyGrid built under the same latents, occupancy.build_occupancy): inference that skips every sample in an
-        empty cell of the grid; refused with randomized sampling or grad mode.  None: the exact path."""
+        empty cell of the grid; refused with randomized sampling or grad mode.  None: the exact path.
+        ``early_stop`` (eps in [0, 1), with or without a grid): a ray stops once its transmittance has fallen to eps (DESIGN.md section
+        4.10); the same refusals.  None: no termination."""
         rays_o = rays["rays_o"]
         n = rays_o.shape[0]
-        if occupancy is not None:
+        if occupancy is not None or early_stop is not None:
             if randomized:
                 raise ValueError("occupancy rendering is inference only: randomized=True is refused")
             if torch.is_grad_enabled():
@@ -149,6 +152,11 @@ class NeRF_AE_Art(nn.Module):
             if self.noise_std > 0:
                 raise NotImplementedError("occupancy rendering takes no density noise (noise_std > 0)")
             two = self.num_levels == 2
+            if early_stop is not None:
+                outs, _, _ = ops.art_render_fwd_stop(self.coarse_mlp.packed(), self.coarse_mlp.prepared(latents), self.fine_mlp.packed() if two else None,
+                                                     self.fine_mlp.prepared(latents) if two else None, rays_o, rays["rays_d"], rays["viewdirs"], near,
+                                                     far, white_bkgd, occupancy, early_stop, num_levels=self.num_levels, u=u, opts=self._opts)
+                return [tuple(o) for o in outs]
             outs, _ = ops.art_render_fwd_occ(self.coarse_mlp.packed(), self.coarse_mlp.prepared(latents), self.fine_mlp.packed() if two else None,
                                              self.fine_mlp.prepared(latents) if two else None, rays_o, rays["rays_d"], rays["viewdirs"], near, far,
                                              white_bkgd, occupancy, self.num_levels, u, opts=self._opts)

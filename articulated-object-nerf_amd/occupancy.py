@@ -42,11 +42,16 @@ def build_occupancy(model, bounds, resolution=128, threshold: float = 0.01, dila
 
 
 @torch.no_grad()
-def render_image(model, c2w, H: int, W: int, focal: float, near: float, far: float, grid: ops.OccupancyGrid, latents: dict | None = None,
-                 chunk: int = ops.MAX_CHUNK_RAYS, white_bkgd: bool = True) -> dict:
+def render_image(model, c2w, H: int, W: int, focal: float, near: float, far: float, grid: ops.OccupancyGrid | None, latents: dict | None = None,
+                 chunk: int = ops.MAX_CHUNK_RAYS, white_bkgd: bool = True, early_stop: float | None = None, round_samples: int | None = None) -> dict:
     """One H x W view through the occupancy path (deterministic sampling, both levels of the model) -> {"rgb": (H, W, 3), "acc": (H, W),
-    "depth": (H, W) of the last level, "occupied": [samples run through the MLP per level] (python ints), "samples": [n * S per level]}."""
-    dev = grid.device
+    "depth": (H, W) of the last level, "occupied": [samples run through the MLP per level] (python ints), "samples": [n * S per level]}.
+    ``early_stop`` (eps in [0, 1)): rays stop once their transmittance has fallen to eps, in rounds of
+    ``round_samples`` samples (None: ops.DEFAULT_ROUND_SAMPLES); the dict gains "stop", the (H, W) int32 map of the last level's stop
+    index (S: the ray ran to its end) -- a heat map of the frame's cost.  `grid` may then be None."""
+    if grid is None and early_stop is None:
+        raise ValueError("render_image: needs a grid, early_stop, or both")
+    dev = grid.device if grid is not None else next(model.parameters()).device
     rays_o, viewdirs = ops.raygen(c2w, H, W, focal, device=dev)
     n = H * W
     art = _is_articulated(model)
@@ -62,15 +67,26 @@ def render_image(model, c2w, H: int, W: int, focal: float, near: float, far: flo
     if art:
         sc = model.coarse_mlp.prepared(latents)
         sf = model.fine_mlp.prepared(latents) if L == 2 else None
+    stop = torch.empty((n,), dtype=torch.int32, device=dev) if early_stop is not None else None
     for b in range(0, n, chunk):
         e = min(n, b + chunk)
         o, v = rays_o[b:e], viewdirs[b:e]
-        if art:
+        if early_stop is not None:
+            if art:
+                outs, occ, st = ops.art_render_fwd_stop(pc, sc, pf, sf, o, v, v, near, far, white_bkgd, grid, early_stop, round_samples, L,
+                                                        opts=model._opts)
+            else:
+                outs, occ, st = ops.render_fwd_stop(pc, pf, o, v, v, near, far, white_bkgd, grid, early_stop, round_samples, L, opts=model._opts)
+            stop[b:e] = st[:, L - 1]
+        elif art:
             outs, occ = ops.art_render_fwd_occ(pc, sc, pf, sf, o, v, v, near, far, white_bkgd, grid, L, opts=model._opts)
         else:
             outs, occ = ops.render_fwd_occ(pc, pf, o, v, v, near, far, white_bkgd, grid, L, opts=model._opts)
         rgb[b:e], acc[b:e], depth[b:e] = outs[-1]
         occupied += occ
     S = [model._opts.Sc, model._opts.Sf]
-    return {"rgb": rgb.view(H, W, 3), "acc": acc.view(H, W), "depth": depth.view(H, W), "occupied": [int(x) for x in occupied.tolist()][:L],
-            "samples": [n * S[lvl] for lvl in range(L)]}
+    out = {"rgb": rgb.view(H, W, 3), "acc": acc.view(H, W), "depth": depth.view(H, W), "occupied": [int(x) for x in occupied.tolist()][:L],
+           "samples": [n * S[lvl] for lvl in range(L)]}
+    if stop is not None:
+        out["stop"] = stop.view(H, W)
+    return out

@@ -1663,3 +1663,73 @@ def art_render_fwd_occ(packed_c, small_c, packed_f, small_f, rays_o, rays_d, vie
     """art_render_fwd with the occupancy skip of render_fwd_occ -> (levels, occupied)."""
     return _occ_call("aon_art_render_fwd_occ", (_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f)), rays_o, rays_d, viewdirs, near, far,
                      white_bkgd, grid, num_levels, u, opts, workspace_bytes)
+
+
+# ------------------------------------------------------------------ early ray termination (DESIGN.md section 4.10)
+DEFAULT_ROUND_SAMPLES = 48   # measured: DESIGN.md section 4.10
+
+
+def _stop_workspace(device, n_rays: int, st, workspace_bytes):
+    if workspace_bytes is not None:
+        return torch.empty(int(workspace_bytes), dtype=torch.uint8, device=device)
+    need = int(lib.aon_render_stop_workspace_bytes(min(n_rays, MAX_CHUNK_RAYS), C.byref(st)))
+    if need < 0:
+        check(need, "aon_render_stop_workspace_bytes")
+    key = str(device)
+    ws = _OCC_WS_CACHE.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        _OCC_WS_CACHE[key] = ws
+    return ws
+
+
+def _stop_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, eps, round_samples, num_levels, u, opts, workspace_bytes):
+    if grid is not None and not isinstance(grid, OccupancyGrid):
+        raise TypeError(f"{name}: grid must be an ops.OccupancyGrid (ops.occupancy_grid) or None, got {type(grid)}")
+    if num_levels not in (1, 2):
+        raise ValueError(f"{name}: num_levels must be 1 or 2")
+    eps = float(eps)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"{name}: eps must be in [0, 1), got {eps}")
+    R = DEFAULT_ROUND_SAMPLES if round_samples is None else int(round_samples)
+    if R < 1:
+        raise ValueError(f"{name}: round_samples must be >= 1, got {R}")
+    o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
+    n, dev = o.shape[0], o.device
+    if grid is not None and grid.device != dev:
+        raise ValueError(f"{name}: the grid is on {grid.device}, the rays on {dev}")
+    op = _opts(opts)
+    if op.noise_std > 0:
+        raise ValueError(f"{name}: inference only, density noise (noise_std > 0) is refused")
+    uu, us = _u_args(u, n, dev, op.num_fine_samples) if num_levels == 2 else (None, 0)
+    outs = [tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in ((n, 3), (n,), (n,))) for _ in range(num_levels)]
+    fine = outs[1] if num_levels == 2 else (None, None, None)
+    st, keep = op.c_struct(near, far)
+    occ = grid.c_struct() if grid is not None else None
+    occupied = torch.zeros(2, dtype=torch.int64, device=dev)
+    stop = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+    ws = _stop_workspace(dev, n, st, workspace_bytes)
+    with torch.cuda.device(dev):
+        check(getattr(lib, name)(*packs, _ptr(o), _ptr(d), _ptr(v), n, float(near), float(far), int(bool(white_bkgd)), num_levels, None, _ptr(uu), us,
+                                 _ptr(outs[0][0]), _ptr(outs[0][1]), _ptr(outs[0][2]), _ptr(fine[0]), _ptr(fine[1]), _ptr(fine[2]),
+                                 _ptr(ws), ws.numel(), _stream(), C.byref(st), C.byref(occ) if occ is not None else None, _ptr(occupied),
+                                 C.c_float(eps), R, _ptr(stop)), name)
+    return [tuple(x) for x in outs], occupied, stop
+
+
+def render_fwd_stop(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, eps, round_samples=None, num_levels=2,
+                    u=None, opts=None, workspace_bytes=None):
+    """render_fwd_occ with early ray termination: each level runs front to back in rounds of `round_samples` sample indices (default
+    DEFAULT_ROUND_SAMPLES) and a ray whose optical depth has reached -ln(eps) after a round is stopped; its remaining samples get zero density
+    and never reach the MLP.  `grid` may be None (termination alone); eps == 0 is off (the bits of render_fwd_occ / render_fwd).
+    Returns (levels, occupied, stop): the level tuples, the int64 (2,) samples each level ran through the MLP, and the int32 (n, 2) per-level
+    stop index of every ray (S of the level: never stopped; a level that was not run: 0)."""
+    return _stop_call("aon_render_fwd_stop", (_pk(packed_coarse), _pk(packed_fine)), rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, eps,
+                      round_samples, num_levels, u, opts, workspace_bytes)
+
+
+def art_render_fwd_stop(packed_c, small_c, packed_f, small_f, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, eps, round_samples=None,
+                        num_levels=2, u=None, opts=None, workspace_bytes=None):
+    """art_render_fwd with the occupancy skip and early termination of render_fwd_stop -> (levels, occupied, stop)."""
+    return _stop_call("aon_art_render_fwd_stop", (_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f)), rays_o, rays_d, viewdirs, near, far,
+                      white_bkgd, grid, eps, round_samples, num_levels, u, opts, workspace_bytes)

@@ -27,7 +27,8 @@ extern "C" {
                                packed or declared is refused (AON_E_INVALID / HIP "invalid value") instead of being taken to have the default form;
                                later additions that change no existing call, so the version stays: aon_ssim, aon_ssim_workspace_bytes,
                                aon_density_grid, aon_art_density_grid, aon_marching_cubes_workspace_bytes, aon_marching_cubes_count, aon_marching_cubes,
-                               aon_occupancy_bytes, aon_occupancy_build, aon_render_occ_workspace_bytes, aon_render_fwd_occ, aon_art_render_fwd_occ */
+                               aon_occupancy_bytes, aon_occupancy_build, aon_render_occ_workspace_bytes, aon_render_fwd_occ, aon_art_render_fwd_occ,
+                               aon_render_stop_workspace_bytes, aon_render_fwd_stop, aon_art_render_fwd_stop */
 
 #define AON_OK 0
 #define AON_E_INVALID (-1)    /* null pointer, negative size, unsupported geometry */
@@ -555,6 +556,30 @@ int aon_art_render_fwd_occ(const void* packed_coarse, const void* small_coarse, 
                            float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
                            int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
                            int64_t* occupied_dev);
+/* ---- early ray termination on the occupancy renders ----
+ * aon_render_fwd_stop / aon_art_render_fwd_stop: the _occ calls (same arguments) with each level evaluated front to back in rounds of
+ *   `round_samples` (R >= 1) consecutive sample indices.  After round k a ray whose optical depth tau = sum sigma_i delta_i (one sequential
+ *   fp32 chain over i < (k+1) R, sigma / delta as the compositing kernel forms them) has reached tau_stop = fp32(-ln eps) is stopped at
+ *   (k+1) R: its remaining samples get the record (0, 0, 0, -inf) and never reach the MLP.  The last round decides nothing.  The level's rgb
+ *   and acc then differ from the unterminated level's by at most eps + S 1e-10, depth by at most far times that.  eps in [0, 1); eps == 0 is
+ *   off: the single-launch path of the _occ call (or of aon_render_fwd_ex when `occ` is NULL), the same bits.  `occ` may be NULL (termination
+ *   without a grid).  `stop_dev` (device, (n_rays, 2) int32, or NULL) receives each ray's stop index per level (S: never stopped; the column
+ *   of a level that was not run is left alone).  `occupied_dev` counts the samples run through the MLP.  eps outside [0, 1) or NaN and
+ *   round_samples < 1 are refused (AON_E_INVALID), as is what the _occ calls refuse.  Stream-ordered, no synchronisation.
+ *   workspace: aon_render_stop_workspace_bytes(n_rays, opts) bytes for one chunk of n_rays. */
+int64_t aon_render_stop_workspace_bytes(int64_t n_rays, const aon_render_opts* opts);
+int aon_render_fwd_stop(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                        const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                        const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                        float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                        const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev, float eps, int round_samples,
+                        int32_t* stop_dev);
+int aon_art_render_fwd_stop(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                            const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                            int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                            float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                            int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
+                            int64_t* occupied_dev, float eps, int round_samples, int32_t* stop_dev);
 /* training twins: the SAME opts (sizes, noise pointers, activation scalars) must be handed to the forward, the backward and the
  * two size queries of one step */
 int64_t aon_train_workspace_bytes_ex(int64_t n_rays, int articulated, int num_levels, const aon_render_opts* opts);

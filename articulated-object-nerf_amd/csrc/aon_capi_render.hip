@@ -1,0 +1,416 @@
+// extern "C" surface, whole-path inference: render_impl for both networks, occupancy-grid acceleration and early ray termination.
+#include "aon_capi_util.h"
+
+using namespace aon::capi;
+
+namespace {
+
+// workspace layout for a chunk of n rays
+struct Ws {
+  float* t_c;   // n*Sc
+  float* w_c;   // n*Sc
+  float* t_f;   // n*Sf
+  float* raw;   // n*Sf*4 (coarse raw uses the first n*Sc*4)
+  float* coords; float* enc; float* venc;   // other_degrees only: n*Sf*3, n*Sf*63, n*27
+  float* vbias;   // n*128: the level's per-ray view bias (vanilla, folded form; launch_view_bias) -- both levels in turn
+  char* occ;      // [occupancy] the level's sample list, tile counts and list length (aon::occ_list_bytes of n*Sf) -- both levels in turn
+  char* stop;     // [early termination] the level's per-ray tau and stop index (aon::occ_stop_state_bytes of n) -- both levels in turn
+  int64_t bytes;
+};
+
+Ws carve(char* base, int64_t n, const Geo& g, bool occ = false, bool stop = false) {
+  Ws w{};
+  int64_t off = 0;
+  w.t_c = reinterpret_cast<float*>(base + off); off += align_up(n * g.Sc * 4, 256);
+  w.w_c = reinterpret_cast<float*>(base + off); off += align_up(n * g.Sc * 4, 256);
+  w.t_f = reinterpret_cast<float*>(base + off); off += align_up(n * g.Sf * 4, 256);
+  w.raw = reinterpret_cast<float*>(base + off); off += align_up(n * g.Sf * 16, 256);
+  if (g.other_degrees) {
+    w.coords = reinterpret_cast<float*>(base + off); off += align_up(n * g.Sf * 12, 256);
+    w.enc = reinterpret_cast<float*>(base + off); off += align_up(n * g.Sf * (int64_t)aon::kPosEnc * 4, 256);
+    w.venc = reinterpret_cast<float*>(base + off); off += align_up(n * (int64_t)aon::kViewEnc * 4, 256);
+  } else {
+    w.vbias = reinterpret_cast<float*>(base + off); off += align_up(n * (int64_t)aon::kCondWidth * 4, 256);
+  }
+  if (occ) { w.occ = base + off; off += aon::occ_list_bytes(n * g.Sf); }
+  if (stop) { w.stop = base + off; off += aon::occ_stop_state_bytes(n); }
+  w.bytes = off;
+  return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t aon_render_workspace_bytes_ex(int64_t n_rays, const aon_render_opts* opts) {
+  if (n_rays < 1) n_rays = 1;
+  Geo g;
+  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
+  return carve(nullptr, n_rays, g).bytes;
+}
+int64_t aon_render_workspace_bytes(int64_t n_rays) { return aon_render_workspace_bytes_ex(n_rays, nullptr); }
+
+// Whole-path orchestration shared by the vanilla and the articulated network (NeRF.forward, model.py:147-199;
+// NeRF_AE_Art.forward, model_autodecoder.py:278-337): only the MLP launch and the output activation differ.
+
+struct NetRef {
+  bool articulated;
+  const void* packed;
+  const float* small;  // articulated only
+};
+
+// An occupancy grid handed to aon_render_fwd_occ / aon_art_render_fwd_occ: the kernels' view of it, and the
+// caller's per-level tally of samples run through the MLP (or null)
+// [early termination, DESIGN.md section 4.10] rounds: the level runs front to back in rounds of R samples and a ray stops once its optical
+// depth reaches tau_stop; grid.bits may then be null (no grid: every live sample is listed).  stop_dev: the caller's (n_rays, 2) map or null
+struct OccCtx {
+  aon::OccGrid grid;
+  int64_t* tally;
+  bool rounds;
+  float tau_stop;
+  int R;
+  int32_t* stop_dev;
+};
+
+// occ: mark the level's samples, compact the occupied ones into a list (aon_occ.hip) and run the MLP on that list alone (the GATHER
+// instances); the empty samples' records hold the zero-density sentinel.  Same view bias, same kernel arithmetic per sample.
+static hipError_t launch_net(const NetRef& net, const float* o, const float* d, const float* v, const float* t, int64_t n, int S,
+                             float* raw, hipStream_t stream, const Geo* g = nullptr, const Ws* w = nullptr, const OccCtx* occ = nullptr,
+                             int level = 0) {
+  if (g && g->other_degrees) {
+    // NeRF(min_deg_point, max_deg_point, deg_view) with at most 10 / 4 levels: the encodings are computed by the stage kernels in
+    // the fused kernel's 63 / 27-slot layout (zeros in the missing levels' slots, matched by zero weights in the packed stream,
+    // aon_pack_vanilla_mlp_deg) and the MLP runs as NeRFMLP.forward(x, condition) on them: 252 B/sample of extra HBM traffic
+    // against 1.19 MFLOP/sample
+    if (hipError_t e = aon::launch_cast_rays(t, o, d, n, S, w->coords, stream); e != hipSuccess) return e;
+    if (hipError_t e = aon::launch_pos_enc(w->coords, n * S, g->min_deg, g->max_deg, w->enc, stream, aon::kPosEnc, 10); e != hipSuccess) return e;
+    if (hipError_t e = aon::launch_pos_enc(v, n, 0, g->deg_view, w->venc, stream, aon::kViewEnc, 4); e != hipSuccess) return e;
+    MlpTimer timer(stream, n * S);
+    return aon::launch_mlp_fwd_enc(static_cast<const char*>(net.packed), w->enc, w->venc, n, S, raw, stream);
+  }
+  const float* vbias = nullptr;
+  if (w && w->vbias && g_view_bias.load(std::memory_order_relaxed) != 0 && aon::stream_form(net.packed) == aon::kFormFolded) {
+    const hipError_t e = net.articulated ? aon::launch_art_view_bias(static_cast<const char*>(net.packed), net.small, v, n, w->vbias, stream)
+                                         : aon::launch_view_bias(static_cast<const char*>(net.packed), v, n, w->vbias, stream);
+    if (e != hipSuccess) return e;
+    vbias = w->vbias;
+  }
+  if (occ && occ->rounds) {
+    // per round: mark -> scan -> emit -> the GATHER launch on the round's list -> the live rays' optical depth; all stream-ordered
+    if (hipError_t e = aon::launch_occ_stop_init(w->stop, n, S, stream); e != hipSuccess) return e;
+    const int R = occ->R < S ? occ->R : S;
+    const aon::ActParams ap = g->act(net.articulated, level, 0);   // (no noise on this path)
+    for (int s0 = 0; s0 < S; s0 += R) {
+      const int s1 = s0 + R < S ? s0 + R : S;
+      const int* idx = nullptr;
+      const int64_t* count = nullptr;
+      if (hipError_t e = aon::launch_occ_compact_round(occ->grid, o, d, t, n, S, s0, s1, w->stop, raw, w->occ, occ->tally ? occ->tally + level : nullptr,
+                                                       &idx, &count, stream);
+          e != hipSuccess)
+        return e;
+      {
+        MlpTimer timer(stream, n * (s1 - s0));
+        const hipError_t e = net.articulated ? aon::launch_art_mlp_fwd_gather(static_cast<const char*>(net.packed), net.small, o, d, v, t, n, S, raw, stream,
+                                                                              vbias, idx, count, n * (s1 - s0))
+                                             : aon::launch_mlp_fwd_gather(static_cast<const char*>(net.packed), o, d, v, t, n, S, raw, stream, vbias, idx,
+                                                                          count, n * (s1 - s0));
+        if (e != hipSuccess) return e;
+      }
+      if (s1 < S)   // the last round (sample S-1 and its 1e10 interval) decides nothing
+        if (hipError_t e = aon::launch_occ_depth(raw, t, d, n, S, s0, s1, ap, occ->tau_stop, w->stop, stream); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  if (occ) {
+    const int* idx = nullptr;
+    const int64_t* count = nullptr;
+    if (hipError_t e = aon::launch_occ_compact(occ->grid, o, d, t, n, S, raw, w->occ, occ->tally ? occ->tally + level : nullptr, &idx, &count, stream);
+        e != hipSuccess)
+      return e;
+    MlpTimer timer(stream, n * S);
+    if (net.articulated)
+      return aon::launch_art_mlp_fwd_gather(static_cast<const char*>(net.packed), net.small, o, d, v, t, n, S, raw, stream, vbias, idx, count);
+    return aon::launch_mlp_fwd_gather(static_cast<const char*>(net.packed), o, d, v, t, n, S, raw, stream, vbias, idx, count);
+  }
+  MlpTimer timer(stream, n * S);
+  if (net.articulated)
+    return aon::launch_art_mlp_fwd(static_cast<const char*>(net.packed), net.small, o, d, v, t, n, S, raw, stream, vbias);
+  return aon::launch_mlp_fwd(static_cast<const char*>(net.packed), o, d, v, t, n, S, raw, stream, vbias);
+}
+
+static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine, const float* rays_o, const float* rays_d,
+                       const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                       const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                       float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, hipStream_t stream,
+                       const aon_render_opts* opts, const OccCtx* occ = nullptr) {
+  Geo g;
+  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
+  if (n_rays < 0 || (num_levels != 1 && num_levels != 2)) return fail(AON_E_INVALID, "render: bad size / num_levels");
+  if (n_rays == 0) return AON_OK;
+  if (!coarse.packed || !rays_o || !rays_d || !viewdirs || !rgb_c || !acc_c || !depth_c || !workspace)
+    return fail(AON_E_INVALID, "render: null pointer");
+  if (num_levels == 2 && (!fine.packed || !rgb_f || !acc_f || !depth_f || !u))
+    return fail(AON_E_INVALID, "render: null fine-level pointer");
+  if (coarse.articulated && (!coarse.small || (num_levels == 2 && !fine.small))) return fail(AON_E_INVALID, "render: null latent block");
+  if (coarse.articulated && (forms_differ(coarse.packed, coarse.small) || (num_levels == 2 && forms_differ(fine.packed, fine.small)))) return fail(AON_E_INVALID, kFormsMsg);
+  if (num_levels == 2 && u_stride != 0 && u_stride < g.nf) return fail(AON_E_INVALID, "render: bad u_stride");
+  if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(AON_E_INVALID, "render: workspace must be 256-byte aligned");
+  const bool art = coarse.articulated;
+  if (art) g.other_degrees = false;   // the articulated kernels carry their degrees in the packed stream and the small block (aon_*_deg)
+  const bool fuse_coarse = num_levels == 2 && g.default_sizes && g_fuse_coarse.load(std::memory_order_relaxed) != 0;
+  const bool with_occ = occ != nullptr;
+  const bool with_stop = with_occ && occ->rounds;
+
+  // largest chunk the workspace admits ([occupancy] and whose sample indices fit the int32 list)
+  int64_t chunk = n_rays;
+  if (with_occ && chunk > INT32_MAX / g.Sf) chunk = INT32_MAX / g.Sf;
+  if (carve(nullptr, chunk, g, with_occ, with_stop).bytes > workspace_bytes) {
+    const int64_t per_ray = (int64_t)(g.Sc + g.Sc + g.Sf + 4 * g.Sf + (g.other_degrees ? (3 + aon::kPosEnc) * g.Sf + aon::kViewEnc : aon::kCondWidth) +
+                                      (with_occ ? g.Sf + 2 * (g.Sf / 1024 + 1) : 0) + (with_stop ? 2 : 0)) * 4;
+    const int64_t slack = (g.other_degrees ? 7 * 256 : 5 * 256) + (with_occ ? 4 * 256 : 0) + (with_stop ? 2 * 256 : 0);
+    chunk = (workspace_bytes - slack) / per_ray;
+    while (chunk > 0 && carve(nullptr, chunk, g, with_occ, with_stop).bytes > workspace_bytes) --chunk;
+    if (chunk < 1) return fail(AON_E_WORKSPACE, with_stop ? "render: workspace smaller than aon_render_stop_workspace_bytes(1)"
+                                                : with_occ ? "render: workspace smaller than aon_render_occ_workspace_bytes(1)"
+                                                         : "render: workspace smaller than aon_render_workspace_bytes(1)");
+  }
+  const Ws w = carve(static_cast<char*>(workspace), chunk, g, with_occ, with_stop);
+  if (with_occ && occ->tally) {
+    if (int rc = check(hipMemsetAsync(occ->tally, 0, 2 * sizeof(int64_t), stream), who); rc != AON_OK) return rc;
+  }
+
+  for (int64_t r0 = 0; r0 < n_rays; r0 += chunk) {
+    const int64_t n = n_rays - r0 < chunk ? n_rays - r0 : chunk;
+    const float* o = rays_o + r0 * 3;
+    const float* d = rays_d + r0 * 3;
+    const float* v = viewdirs + r0 * 3;
+    const float* uu = u_stride ? u + r0 * u_stride : u;
+    int rc;
+    // level 0 (model.py:150-160, :175-197)
+    {
+      KTimer timer(kSampleT, stream, n);
+      rc = check(aon::launch_sample_along_rays(o, d, n, g.Sc, near_, far_, t_rand ? t_rand + r0 * g.Sc : nullptr, w.t_c, nullptr, stream,
+                                               g.lindisp, g.inv_near, g.inv_far), who);
+    }
+    if (rc) return rc;
+    rc = check(launch_net(coarse, o, d, v, w.t_c, n, g.Sc, w.raw, stream, &g, &w, occ, 0), who);
+    if (rc) return rc;
+    if (with_stop && occ->stop_dev) {
+      rc = check(aon::launch_occ_stop_store(w.stop, 0, occ->stop_dev + r0 * 2, n, 2, stream), who);
+      if (rc) return rc;
+    }
+    if (fuse_coarse) {
+      // compositing + the fine level's sampling (model.py:162-173) in one kernel: the coarse weights stay in registers
+      KTimer timer(kCompositePdf, stream, n);
+      rc = check(aon::launch_composite_pdf(w.raw, w.t_c, d, n, white_bkgd, g.act(art, 0, r0), uu, u_stride, rgb_c + r0 * 3,
+                                           acc_c + r0, depth_c + r0, nullptr, w.t_f, stream), who);
+    } else {
+      KTimer timer(kComposite, stream, n);
+      rc = check(aon::launch_composite(w.raw, 4, w.raw + 3, 4, w.t_c, d, n, g.Sc, white_bkgd, g.act(art, 0, r0), rgb_c + r0 * 3, acc_c + r0,
+                                       depth_c + r0, num_levels == 2 ? w.w_c : nullptr, stream), who);
+    }
+    if (rc) return rc;
+    if (num_levels == 1) continue;
+    // level 1 (model.py:162-173, :175-197)
+    if (!fuse_coarse) {
+      KTimer timer(kSamplePdf, stream, n);
+      rc = check(g.default_sizes ? aon::launch_sample_pdf(nullptr, w.w_c + 1, kSc, w.t_c, uu, u_stride, n, nullptr, w.t_f, stream)
+                                 : aon::launch_sample_pdf_n(nullptr, w.w_c + 1, g.Sc, w.t_c, uu, u_stride, n, g.Sc - 1, g.nf, g.Sc, nullptr,
+                                                            w.t_f, stream), who);
+      if (rc) return rc;
+    }
+    rc = check(launch_net(fine, o, d, v, w.t_f, n, g.Sf, w.raw, stream, &g, &w, occ, 1), who);
+    if (rc) return rc;
+    if (with_stop && occ->stop_dev) {
+      rc = check(aon::launch_occ_stop_store(w.stop, 0, occ->stop_dev + r0 * 2 + 1, n, 2, stream), who);
+      if (rc) return rc;
+    }
+    {
+      KTimer timer(kComposite, stream, n);
+      rc = check(aon::launch_composite(w.raw, 4, w.raw + 3, 4, w.t_f, d, n, g.Sf, white_bkgd, g.act(art, 1, r0), rgb_f + r0 * 3, acc_f + r0,
+                                       depth_f + r0, nullptr, stream), who);
+    }
+    if (rc) return rc;
+  }
+  return AON_OK;
+}
+
+int aon_render_fwd_ex(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                      const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                      const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                      float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                      const aon_render_opts* opts) {
+  const NetRef c{false, packed_coarse, nullptr}, f{false, packed_fine, nullptr};
+  return render_impl("aon_render_fwd", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
+                     u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts);
+}
+int aon_render_fwd(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                   const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                   const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                   float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream) {
+  return aon_render_fwd_ex(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
+                           u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, nullptr);
+}
+
+// ---- occupancy-grid accelerated inference (aon_occ.hip) ----
+static const char* occ_cells_bad(const int64_t* cells3) {
+  if (!cells3) return "null cell counts";
+  for (int a = 0; a < 3; ++a)
+    if (cells3[a] < 1 || cells3[a] > (int64_t)1 << 24) return "every cell count must be in [1, 2^24]";
+  if (cells3[0] > ((int64_t)1 << 40) / cells3[1] / cells3[2]) return "grid too large (more than 2^40 cells)";
+  return nullptr;
+}
+int64_t aon_occupancy_bytes(const int64_t* cells3_host) {
+  if (const char* msg = occ_cells_bad(cells3_host)) return fail(AON_E_INVALID, (std::string("aon_occupancy_bytes: ") + msg).c_str());
+  return (cells3_host[0] * cells3_host[1] * cells3_host[2] + 31) / 32 * 4;
+}
+int aon_occupancy_build(const float* density, const int64_t* dims3_host, float threshold, int dilate, uint32_t* bits, void* stream) {
+  if (!dims3_host) return fail(AON_E_INVALID, "aon_occupancy_build: null dims");
+  const int64_t cells[3] = {dims3_host[0] - 1, dims3_host[1] - 1, dims3_host[2] - 1};
+  if (const char* msg = occ_cells_bad(cells)) return fail(AON_E_INVALID, (std::string("aon_occupancy_build: every dimension must be >= 2; ") + msg).c_str());
+  if (dilate < 0 || dilate > 8) return fail(AON_E_INVALID, "aon_occupancy_build: dilate must be in [0, 8]");
+  if (threshold != threshold) return fail(AON_E_INVALID, "aon_occupancy_build: threshold is NaN");
+  if (!density || !bits) return fail(AON_E_INVALID, "aon_occupancy_build: null pointer");
+  return check(aon::launch_occ_build(density, dims3_host, threshold, dilate, bits, (hipStream_t)stream), "aon_occupancy_build");
+}
+static const char* occ_grid_bad(const aon_occupancy* occ, aon::OccGrid& G) {
+  if (!occ || !occ->bits) return "null occupancy grid";
+  if (const char* msg = occ_cells_bad(occ->cells)) return msg;
+  G.bits = occ->bits;
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(occ->lo[a]) || !std::isfinite(occ->step[a]) || !(occ->step[a] > 0.f)) return "occupancy lo must be finite and step finite and > 0";
+    G.cells[a] = occ->cells[a]; G.lo[a] = occ->lo[a]; G.step[a] = occ->step[a];
+    const float span = (float)occ->cells[a] * occ->step[a];   // the last grid point: multiply, then add (ops.grid_points)
+    G.hi[a] = occ->lo[a] + span;
+    if (!std::isfinite(G.hi[a])) return "occupancy box not finite";
+  }
+  return nullptr;
+}
+// the inference-only limits of the occupancy path, checked before any launch
+static const char* occ_opts_bad(const aon_render_opts* opts, bool art, const float* t_rand) {
+  Geo g;
+  if (const char* bad = make_geo(opts, g)) return bad;
+  if (t_rand) return "occupancy rendering is inference only: t_rand (randomized sampling) is refused";
+  if (g.noise_std > 0.f && (g.noise[0] || g.noise[1])) return "occupancy rendering is inference only: density noise is refused";
+  if (!art && g.other_degrees) return "occupancy rendering needs the default encoding degrees (0, 10, 4) of the vanilla network";
+  return nullptr;
+}
+int64_t aon_render_occ_workspace_bytes(int64_t n_rays, const aon_render_opts* opts) {
+  if (n_rays < 1) n_rays = 1;
+  Geo g;
+  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
+  if (n_rays > INT32_MAX / g.Sf) n_rays = INT32_MAX / g.Sf;
+  return carve(nullptr, n_rays, g, true).bytes;
+}
+int aon_render_fwd_occ(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                       const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                       const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                       float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                       const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev) {
+  OccCtx ctx{};
+  if (const char* bad = occ_grid_bad(occ, ctx.grid)) return fail(AON_E_INVALID, (std::string("aon_render_fwd_occ: ") + bad).c_str());
+  if (const char* bad = occ_opts_bad(opts, false, t_rand)) return fail(AON_E_INVALID, (std::string("aon_render_fwd_occ: ") + bad).c_str());
+  ctx.tally = occupied_dev;
+  const NetRef c{false, packed_coarse, nullptr}, f{false, packed_fine, nullptr};
+  return render_impl("aon_render_fwd_occ", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
+                     u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, &ctx);
+}
+
+// ---- early ray termination on the occupancy renders ----
+int64_t aon_render_stop_workspace_bytes(int64_t n_rays, const aon_render_opts* opts) {
+  if (n_rays < 1) n_rays = 1;
+  Geo g;
+  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
+  if (n_rays > INT32_MAX / g.Sf) n_rays = INT32_MAX / g.Sf;
+  return carve(nullptr, n_rays, g, true, true).bytes;
+}
+// the checks and the eps == 0 route shared by aon_render_fwd_stop / aon_art_render_fwd_stop
+static int render_stop(const char* who, const NetRef& c, const NetRef& f, const float* rays_o, const float* rays_d, const float* viewdirs,
+                       int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels, const float* t_rand, const float* u,
+                       int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                       int64_t workspace_bytes, hipStream_t stream, const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev,
+                       float eps, int round_samples, int32_t* stop_dev) {
+  OccCtx ctx{};
+  if (occ)
+    if (const char* bad = occ_grid_bad(occ, ctx.grid)) return fail(AON_E_INVALID, (std::string(who) + ": " + bad).c_str());
+  if (const char* bad = occ_opts_bad(opts, c.articulated, t_rand)) return fail(AON_E_INVALID, (std::string(who) + ": " + bad).c_str());
+  if (!(eps >= 0.f && eps < 1.f)) return fail(AON_E_INVALID, (std::string(who) + ": eps must be in [0, 1)").c_str());
+  if (round_samples < 1) return fail(AON_E_INVALID, (std::string(who) + ": round_samples must be >= 1").c_str());
+  ctx.tally = occupied_dev;
+  if (eps == 0.f) {   // off: today's single-launch paths, and the bookkeeping of a render in which no ray stopped
+    const int rc = render_impl(who, c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c,
+                               depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, opts, occ ? &ctx : nullptr);
+    if (rc != AON_OK || n_rays == 0) return rc;
+    Geo g;
+    (void)make_geo(opts, g);
+    if (!occ && occupied_dev)
+      if (int r2 = check(aon::launch_occ_tally_set(occupied_dev, n_rays * g.Sc, num_levels == 2 ? n_rays * g.Sf : 0, stream), who); r2 != AON_OK) return r2;
+    if (stop_dev)
+      for (int l = 0; l < num_levels; ++l)
+        if (int r2 = check(aon::launch_occ_stop_store(nullptr, g.S(l), stop_dev + l, n_rays, 2, stream), who); r2 != AON_OK) return r2;
+    return AON_OK;
+  }
+  ctx.rounds = true;
+  ctx.tau_stop = (float)(-std::log((double)eps));   // fp64, rounded once
+  ctx.R = round_samples;
+  ctx.stop_dev = stop_dev;
+  return render_impl(who, c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c,
+                     rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, opts, &ctx);
+}
+int aon_render_fwd_stop(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                        const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                        const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                        float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                        const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev, float eps, int round_samples,
+                        int32_t* stop_dev) {
+  const NetRef c{false, packed_coarse, nullptr}, f{false, packed_fine, nullptr};
+  return render_stop("aon_render_fwd_stop", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c,
+                     acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, occ, occupied_dev, eps,
+                     round_samples, stop_dev);
+}
+
+int aon_art_render_fwd_ex(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                          const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                          int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                          float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                          int64_t workspace_bytes, void* stream, const aon_render_opts* opts) {
+  const NetRef c{true, packed_coarse, static_cast<const float*>(small_coarse)}, f{true, packed_fine, static_cast<const float*>(small_fine)};
+  return render_impl("aon_art_render_fwd", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
+                     u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts);
+}
+int aon_art_render_fwd_occ(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                           const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                           int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                           float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                           int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
+                           int64_t* occupied_dev) {
+  OccCtx ctx{};
+  if (const char* bad = occ_grid_bad(occ, ctx.grid)) return fail(AON_E_INVALID, (std::string("aon_art_render_fwd_occ: ") + bad).c_str());
+  if (const char* bad = occ_opts_bad(opts, true, t_rand)) return fail(AON_E_INVALID, (std::string("aon_art_render_fwd_occ: ") + bad).c_str());
+  ctx.tally = occupied_dev;
+  const NetRef c{true, packed_coarse, static_cast<const float*>(small_coarse)}, f{true, packed_fine, static_cast<const float*>(small_fine)};
+  return render_impl("aon_art_render_fwd_occ", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
+                     u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, &ctx);
+}
+int aon_art_render_fwd_stop(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                            const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                            int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                            float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                            int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
+                            int64_t* occupied_dev, float eps, int round_samples, int32_t* stop_dev) {
+  const NetRef c{true, packed_coarse, static_cast<const float*>(small_coarse)}, f{true, packed_fine, static_cast<const float*>(small_fine)};
+  return render_stop("aon_art_render_fwd_stop", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride,
+                     rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, occ, occupied_dev, eps,
+                     round_samples, stop_dev);
+}
+int aon_art_render_fwd(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                       const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                       int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                       float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  return aon_art_render_fwd_ex(packed_coarse, small_coarse, packed_fine, small_fine, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd,
+                               num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream,
+                               nullptr);
+}
+
+}  // extern "C"

@@ -1,0 +1,111 @@
+// What the translation units of the extern "C" surface (aon_capi*.hip) share: the error record, the argument checks, the sampler /
+// activation geometry of a call and the live profiler.  The state is defined once, in aon_capi.hip.  Hidden visibility: none of this is
+// part of the library's interface.
+#pragma once
+#include "../../include/aon_hip.h"
+#include "aon_launch.h"
+
+#include <atomic>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+namespace aon {
+namespace capi __attribute__((visibility("hidden"))) {
+
+extern thread_local char g_err[256];
+
+int fail(int code, const char* msg);
+int check(hipError_t e, const char* where);
+
+constexpr int kSc = 65, kSf = 193;
+
+// round 5: the articulated calls take a packed stream AND a per-call block; both carry a form (bottleneck folded / literal, aon_fold.h)
+extern const char* const kFormsMsg;
+extern const char* const kNullBwdMsg;
+// (an unknown pointer -- a copy nobody declared -- differs from everything, itself included)
+inline bool forms_differ(const void* a, const void* b) {
+  return a && b && (aon::stream_form(a) != aon::stream_form(b) || aon::stream_form(a) == aon::kFormUnknown);
+}
+
+// process-wide switches read by more than one file; every call reads them ONCE
+extern std::atomic<int> g_fuse_coarse;   // aon_set_coarse_fusion
+extern std::atomic<int> g_view_bias;     // aon_set_view_bias
+
+// Optional live timing of the path's kernels with HIP events on the LAUNCH stream (torch.cuda.Event would only see torch's
+// current stream), by kernel class; bench.py turns the totals into roofline figures.  Off unless aon_profile_begin() was
+// called: one mutex-guarded branch per launch otherwise.
+enum KClass { kMlpFwd = AON_PROF_MLP_FWD, kBwdChain = AON_PROF_BWD_CHAIN, kWgrad = AON_PROF_WGRAD, kComposite = AON_PROF_COMPOSITE,
+              kSamplePdf = AON_PROF_SAMPLE_PDF, kCompositeBwd = AON_PROF_COMPOSITE_BWD, kCompositePdf = AON_PROF_COMPOSITE_PDF, kSampleT = AON_PROF_SAMPLE_T,
+              kNumClasses = AON_PROF_NUM_CLASSES };
+
+struct Profiler {
+  std::mutex mu;
+  bool on = false;
+  struct Rec { int cls; hipEvent_t start, stop; };
+  std::vector<hipEvent_t> pool;
+  size_t used = 0;
+  std::vector<Rec> recs;
+  int64_t units[kNumClasses] = {};
+  // totals of the last completed aon_profile_end()
+  double last_ms[kNumClasses] = {};
+  int64_t last_launches[kNumClasses] = {};
+  int64_t last_units[kNumClasses] = {};
+};
+extern Profiler g_prof;
+
+struct KTimer {
+  hipEvent_t stop = nullptr;
+  hipStream_t stream;
+  KTimer(int cls, hipStream_t s, int64_t units) : stream(s) {
+    std::lock_guard<std::mutex> lk(g_prof.mu);
+    if (!g_prof.on) return;
+    while (g_prof.used + 2 > g_prof.pool.size()) {
+      hipEvent_t e;
+      if (hipEventCreate(&e) != hipSuccess) return;
+      g_prof.pool.push_back(e);
+    }
+    hipEvent_t start = g_prof.pool[g_prof.used];
+    stop = g_prof.pool[g_prof.used + 1];
+    g_prof.used += 2;
+    g_prof.recs.push_back({cls, start, stop});
+    g_prof.units[cls] += units;
+    (void)hipEventRecord(start, stream);
+  }
+  ~KTimer() { if (stop) (void)hipEventRecord(stop, stream); }
+};
+struct MlpTimer : KTimer {
+  MlpTimer(hipStream_t s, int64_t samples) : KTimer(kMlpFwd, s, samples) {}
+};
+
+inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+// The sampler / activation geometry of one call: aon_render_opts resolved against the reference's defaults.
+struct Geo {
+  int Sc, Sf, nf;          // t values of level 0 / level 1, draws of the inverse CDF
+  bool default_sizes;      // 65 / 193: the specialised per-ray kernels apply
+  int lindisp; float inv_near, inv_far;
+  const float* noise[2]; float noise_std;
+  float rgb_scale, rgb_shift, sigma_bias;
+  int min_deg, max_deg, deg_view;   // encoding degrees of a vanilla network on the fused kernels
+  bool other_degrees;               // != (0, 10, 4): encodings computed outside the MLP kernel, in its padded 63 / 27 layout
+  int S(int l) const { return l == 0 ? Sc : Sf; }
+  aon::ActParams act(bool art, int level, int64_t ray0) const {
+    aon::ActParams ap{art ? AON_ACT_ARTICULATED : AON_ACT_VANILLA, rgb_scale, rgb_shift, sigma_bias, nullptr, noise_std};
+    if (noise[level] && noise_std > 0.f) ap.noise = noise[level] + ray0 * S(level);
+    return ap;
+  }
+};
+
+// returns nullptr when fine, else what is wrong
+// `general_engine`: the aon_grender_* entry points take the network's degrees from aon_mlp_geometry and ignore the degree fields of
+// aon_render_opts, so those fields are neither validated against the fused kernels' limits nor turned into `other_degrees` there (a C
+// caller who fills them to match a (1, 12, 5) geometry used to get AON_E_INVALID from the general engine: ADVICE r3).
+const char* make_geo(const aon_render_opts* o, Geo& g, bool general_engine = false);
+
+}  // namespace capi
+}  // namespace aon

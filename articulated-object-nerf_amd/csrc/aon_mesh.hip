@@ -21,7 +21,7 @@
 //       tile offsets, in-tile offsets and lower-axis bits; no per-edge index array exists.
 // The eight corner reads of a cell go through the L1 / L2 caches (each value is read by up to 8 cells of the same and the neighbouring
 // rows); at 4 + 4 bytes of workspace per point the whole extraction moves a few bytes per grid point (DESIGN 4.7 gives the measured rate).
-#include "aon_common.h"
+#include "aon_launch.h"
 
 namespace aon {
 

@@ -14,7 +14,7 @@
 // its valid pixels to ONE fp64 partial in a fixed tree order.  Launch 2: one workgroup per image sums that image's partials in a fixed
 // order and writes the mean.  No atomics: the same image gives the same bits on every run and in any batch (its tiles and partial
 // offsets relative to the image are independent of the other images).
-#include "aon_common.h"
+#include "aon_launch.h"
 
 #include <cmath>
 

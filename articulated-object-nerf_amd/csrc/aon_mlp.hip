@@ -19,7 +19,7 @@
 //     read their A operands with conflict-free ds_read_b128 (4 MFMA steps per read).
 //   * per 128-sample pass a wave issues ~9.3k MFMAs (64 cycles each) against ~2.4k ds_read_b128 and a few
 //     hundred VALU ops (bias init, ReLU, heads), so the kernel is bound by the fp32 matrix pipe.
-#include "aon_fold.h"
+#include "aon_launch.h"
 #include "aon_mlp_core.h"
 
 namespace aon {
@@ -520,8 +520,6 @@ hipError_t launch_mlp_fwd_gather(const char* packed, const float* rays_o, const 
   args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
   return launch_mlp_t<true, false, true>(args, stream);
 }
-
-hipError_t launch_mlp_fwd_train2(const TrainSeg* segs, int nsegs, hipStream_t stream);
 
 // Training forward: as launch_mlp_fwd, plus the activation planes (kPlRows x Np floats, Np = 128*ceil(n*S/128)).
 // np_total: the padded sample count of the WHOLE batch when this launch covers a ray range of it starting on a pass boundary

@@ -12,7 +12,7 @@
 //   * the 3->128 first deformation layer and the 128->3 deformation head are VALU work on register tiles;
 //     the deformed point is encoded in registers exactly like the vanilla path.
 #include "aon_art_common.h"
-#include "aon_fold.h"
+#include "aon_launch.h"
 
 namespace aon {
 
@@ -517,8 +517,6 @@ hipError_t launch_pack_prepare_art2(const float* const* const params[2], const f
   return hipGetLastError();
 }
 
-int num_cus();  // aon_mlp.hip
-
 template <bool POS, bool TRAIN, bool FOLD, bool VB = false, bool GATHER = false>
 static hipError_t launch_art_tf(const ArtMlpArgs& args, hipStream_t stream) {
   static DeviceOnce lds_once;
@@ -549,8 +547,6 @@ static hipError_t launch_art_t(const ArtMlpArgs& args, hipStream_t stream) {
   return form == kFormFolded ? launch_art_tf<POS, TRAIN, true, false, GATHER>(args, stream)
                              : launch_art_tf<POS, TRAIN, false, false, GATHER>(args, stream);
 }
-
-hipError_t launch_view_bias_raw(const float* chunk, const float* bias_vec, const float* viewdirs, int64_t n_rays, float* out, hipStream_t stream);   // aon_mlp.hip
 
 // views_linear.0's effective bias (per-call block: appearance latent and W_v0[:, :256] b_b folded in) + its view-encoding term, per ray
 hipError_t launch_art_view_bias(const char* packed, const float* small, const float* viewdirs, int64_t n_rays, float* out, hipStream_t stream) {
@@ -583,8 +579,6 @@ hipError_t launch_art_mlp_fwd_gather(const char* packed, const float* small, con
   args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
   return launch_art_t<true, false, true>(args, stream);
 }
-
-hipError_t launch_art_mlp_fwd_train2(const TrainSeg* segs, int nsegs, hipStream_t stream);
 
 hipError_t launch_art_mlp_fwd_train(const char* packed, const float* small, const float* rays_o, const float* rays_d,
                                     const float* viewdirs, const float* t_vals, int64_t n_rays, int S, float* raw, float* planes,

@@ -21,7 +21,7 @@
 //   (b) scan: ONE workgroup turns the tile counts into exclusive offsets and the total, which it writes to the device counter the gather
 //       MLP launch reads its pass count from (no host synchronisation) and adds to the caller's per-level tally;
 //   (c) emit: the lookup again, and the ascending list of occupied sample indices at the scanned offsets.
-#include "aon_common.h"
+#include "aon_launch.h"
 
 namespace aon {
 

@@ -6,7 +6,7 @@
 // Why: torch's fused Adam walks 83 tensors as three multi_tensor_apply launches of ~44 us each (0.34 TB/s over 45 MB), the embedding
 // backward is a fill + a scatter per table; with parameters, gradients and both moments as views into four flat buffers the whole update
 // is one grid-stride pass at HBM rate (profiles/r06_step_timeline.txt).
-#include "aon_common.h"
+#include "aon_launch.h"
 
 #include <cmath>
 
@@ -51,8 +51,6 @@ __global__ void __launch_bounds__(256) adam_arena_kernel(AdamArgs a, int vec) {
   }
   for (int64_t t = (n4 << 2) + tid; t < a.n; t += stride) adam_one(a.p[t], a.g[t], a.m[t], a.v[t], a);   // the last n % 4 (or an unaligned range)
 }
-
-int num_cus();
 
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps, int64_t step,
                        hipStream_t stream) {

@@ -7,6 +7,7 @@
 // ray's samples so every load/store of a per-ray sample buffer is a contiguous burst, and the transmittance product / CDF sum /
 // merge are wavefront scans and shuffles (no LDS round trip except the 64-entry CDF table the binary search gathers from and
 // the 193-slot row the merge scatters into).  The coarse level's compositing and the fine level's sampling are one kernel.
+#include "aon_launch.h"
 #include "aon_ray_core.h"
 
 namespace aon {

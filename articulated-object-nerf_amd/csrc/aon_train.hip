@@ -16,7 +16,7 @@
 #include <atomic>
 #define AON_WGRAD_KERNELS
 #define AON_CHAIN_STAGE_MASKED   // see BwdSideOf (aon_mlp_core.h)
-#include "aon_fold.h"
+#include "aon_launch.h"
 #include "aon_wgrad.h"
 
 namespace aon {
@@ -386,8 +386,6 @@ __global__ void __launch_bounds__(256) mlp_bwd_chain_kernel(BwdArgs args) {
 // ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
-int num_cus();  // aon_mlp.hip
-
 // The form packed is the process default at the time of the call (aon_set_bottleneck_fold), remembered for `packed` (stream_form).
 void vanilla_fold_jobs_bwd(const float* const* params, float* packed, int view_size, FoldGemm jobs[2]) {
   float* Wf = packed + kBwFOffWf / 4;
@@ -466,8 +464,7 @@ void set_wgrad_probe(long long* buf) { g_wgrad_probe.store(buf, std::memory_orde
 // The plan (workspace offsets of every partial) is a pure function of the arguments: the two phases of a level compute the same one.
 hipError_t run_wgrad_plan(const WgLayerDesc* layers, int nlayers, const HeadDesc* heads, int nheads, const HeadOut* outs, const int* out_head, int nouts,
                           const float* planes, const float* dplanes, int rows_total, int64_t Np, float* ws, hipStream_t stream, const WgAux* aux,
-                          int phase, int n_early, const WgPost* post, hipStream_t* post_stream, ReduceArgs* defer_reduce, int* defer_blocks) {
-  if (post_stream) *post_stream = stream;
+                          int phase, int n_early, hipEvent_t wait_first, ReduceArgs* defer_reduce, int* defer_blocks) {
   static DeviceOnce lds_once;
   if (hipError_t e = set_max_lds(&wgrad_grouped_kernel, kWgLdsBytes, lds_once); e != hipSuccess) return e;
   const int cus = num_cus();
@@ -518,23 +515,14 @@ hipError_t run_wgrad_plan(const WgLayerDesc* layers, int nlayers, const HeadDesc
   }
   if (err != hipSuccess) return err;
   if (defer_reduce) {   // the caller launches this level's second stage itself, together with the other level's (launch_wgrad_reduce2)
-    if (post || !defer_blocks) return hipErrorInvalidValue;
+    if (wait_first || !defer_blocks) return hipErrorInvalidValue;
     *defer_reduce = R;
     *defer_blocks = plan.reduce_blocks + nouts;
     return hipSuccess;
   }
-  hipStream_t ps = stream;
-  if (post) {
-    if (post->wait_first)
-      if (hipError_t e = hipStreamWaitEvent(stream, post->wait_first, 0); e != hipSuccess) return e;
-    if (post->side) {   // the second stage and everything behind it on the side stream, ordered behind the grouped kernel
-      if (hipError_t e = hipEventRecord(post->side->fork, stream); e != hipSuccess) return e;
-      if (hipError_t e = hipStreamWaitEvent(post->side->stream, post->side->fork, 0); e != hipSuccess) return e;
-      ps = post->side->stream;
-    }
-  }
-  if (post_stream) *post_stream = ps;
-  wgrad_reduce_kernel<<<dim3(plan.reduce_blocks + nouts), dim3(256), 0, ps>>>(R);
+  if (wait_first)
+    if (hipError_t e = hipStreamWaitEvent(stream, wait_first, 0); e != hipSuccess) return e;
+  wgrad_reduce_kernel<<<dim3(plan.reduce_blocks + nouts), dim3(256), 0, stream>>>(R);
   return hipGetLastError();
 }
 
@@ -607,15 +595,14 @@ struct VanillaWgDeferred {
   int n_unfold;           // 3 (folded form) or 0
   FoldGemm unfold[3];
 };
-constexpr int kVanillaWgDeferredBytes = 4096;   // (aon_capi.hip keeps two of these on its stack)
-static_assert(sizeof(VanillaWgDeferred) <= kVanillaWgDeferredBytes && alignof(VanillaWgDeferred) <= 16, "VanillaWgDeferred outgrew its storage in aon_capi.hip");
-int vanilla_wgrad_deferred_bytes() { return (int)sizeof(VanillaWgDeferred); }   // (aon_capi.hip checks its storage against this)
+static_assert(sizeof(VanillaWgDeferred) <= kVanillaWgDeferredBytes && alignof(VanillaWgDeferred) <= 16, "VanillaWgDeferred outgrew its storage in train_bwd_impl (aon_launch.h)");
+int vanilla_wgrad_deferred_bytes() { return (int)sizeof(VanillaWgDeferred); }
 
 hipError_t launch_vanilla_wgrad(const float* planes, const float* dplanes, const float* d_raw, int64_t Np, float* const* grads,
-                                float* ws, hipStream_t stream, const WgAux* aux, const void* packed_bwd, int phase, const WgPost* post,
+                                float* ws, hipStream_t stream, const WgAux* aux, const void* packed_bwd, int phase, hipEvent_t wait_first,
                                 VanillaWgDeferred* defer) {
   WgLayerDesc L[kWgMaxJobs];
-  if (defer && (phase == kWgEarly || post)) return hipErrorInvalidValue;
+  if (defer && (phase == kWgEarly || wait_first)) return hipErrorInvalidValue;
   if (packed_bwd && stream_form(packed_bwd) == kFormUnknown) return hipErrorInvalidValue;   // (a copy nobody declared)
   const bool fold = packed_bwd && stream_form(packed_bwd) == kFormFolded;
   float* fold_tmp = fold ? wgrad_fold_tmp(ws) : nullptr;
@@ -625,12 +612,12 @@ hipError_t launch_vanilla_wgrad(const float* planes, const float* dplanes, const
   const HeadOut O[4] = {{0, 256, 3, 1, 256, 1, grads[20]}, {0, 128, 0, 3, 128, 1, grads[22]}, {0, 1, 3, 1, 1, 1, grads[21]}, {0, 1, 0, 3, 1, 1, grads[23]}};
   const int OH[4] = {0, 1, 2, 2};
   // all three head jobs (density head on H7, rgb head on HV, the sums of d_raw) are independent of the chain: n_early = 3
-  if (hipError_t e = run_wgrad_plan(L, n, H, 3, O, OH, 4, planes, dplanes, kPlRows, Np, ws, stream, aux, phase, 3, phase == kWgEarly ? nullptr : post, nullptr,
+  if (hipError_t e = run_wgrad_plan(L, n, H, 3, O, OH, 4, planes, dplanes, kPlRows, Np, ws, stream, aux, phase, 3, phase == kWgEarly ? nullptr : wait_first,
                                     defer ? &defer->reduce : nullptr, defer ? &defer->reduce_blocks : nullptr); e != hipSuccess) return e;
   if (defer) defer->n_unfold = 0;
   if (!fold || phase == kWgEarly) return hipSuccess;
   const float* raw = reinterpret_cast<const float*>(static_cast<const char*>(packed_bwd) + kBwFOffWv);
-  // (grads[16]'s row stride is the 27-slot layout's here: other view degrees write a slot-layout temporary first, aon_render_bwd_ex)
+  // (grads[16]'s row stride is the 27-slot layout's here: other view degrees write a slot-layout temporary first, train_bwd_impl)
   if (defer) {
     defer->n_unfold = 3;
     unfold_view_jobs(fold_tmp, grads[17], raw, 256, raw + 128 * 256, raw + 128 * 256 + 256 * 256, grads[16], 256 + kViewEnc, grads[18], grads[19], defer->unfold);
@@ -654,8 +641,6 @@ hipError_t launch_vanilla_wgrad_post2(const VanillaWgDeferred* d0, const Vanilla
 // Host-only view of the plan a level would run on `cus` compute units (tests/test_abi_cpu.py checks its invariants without a
 // GPU): per job (kind, first workgroup, workgroups that own a step of it, steps of the job, partial offset in floats, partial count);
 // `line`: {W, G} of the work line.
-int art_wgrad_layers(float* const* grads, WgLayerDesc* L, int Lp, int Lv, float* enc_tmp, float* fold_tmp);   // aon_train_art.hip
-
 // (the host-only plan views describe the plan of the process's current default form)
 static int plan_layers(bool art, float* const* grads, WgLayerDesc* L) {
   float* fold_tmp = fold_default() == kFormFolded ? reinterpret_cast<float*>((uintptr_t)0x100000) : nullptr;   // never dereferenced

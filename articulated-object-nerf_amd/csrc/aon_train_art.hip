@@ -10,7 +10,7 @@
 //   * every latent is broadcast to all samples, so  dW[:, latent cols] = db (x) latent  and  d latent = W[:, cols]^T db:
 //     both come from the bias gradients, no per-sample work.
 #include "aon_art_common.h"
-#include "aon_fold.h"
+#include "aon_launch.h"
 #include "aon_wgrad.h"
 
 namespace aon {
@@ -489,8 +489,6 @@ __global__ void __launch_bounds__(1024) art_finish2_kernel(ArtFinishArgs a0, Art
 // ---------------------------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------------------------
-int num_cus();
-
 // The form packed is the process default at the time of the call (aon_set_bottleneck_fold), remembered for `packed` (stream_form).
 FoldGemm art_fold_job_bwd(const float* const* params, float* packed, int view_levels) {
   return FoldGemm{params[26], 256 + 3 + 6 * view_levels + 128, 1, params[34], 256, 1, packed + kABwFOffWf / 4, 256, 128, 256, 256, nullptr, nullptr};
@@ -567,11 +565,6 @@ hipError_t launch_art_bwd_chain(const char* packed_bwd, const float* small, cons
   return launch_art_bwd_chain2(&one, 1, stream);
 }
 
-hipError_t run_wgrad_plan(const WgLayerDesc* layers, int nlayers, const HeadDesc* heads, int nheads, const HeadOut* outs, const int* out_head, int nouts,
-                          const float* planes, const float* dplanes, int rows_total, int64_t Np, float* ws, hipStream_t stream, const WgAux* aux,
-                          int phase, int n_early, const WgPost* post, hipStream_t* post_stream, ReduceArgs* defer_reduce, int* defer_blocks);   // aon_train.hip
-hipError_t launch_wgrad_reduce2(const ReduceArgs& a0, int n0, const ReduceArgs& a1, int n1, hipStream_t stream);   // aon_train.hip
-
 // the weight-gradient jobs of one articulated level.  Lp / Lv: frequency levels of the network (10 / 4 by default).  With other degrees
 // the three encoding-fed column blocks come out in the kernels' 63 / 27-slot layout into `enc_tmp` (256 x 64 | 256 x 64 | 128 x 32
 // floats) and lose the empty slots afterwards (art_remap_enc_kernel); the row strides of the concatenating layers follow P and V.
@@ -608,7 +601,6 @@ int art_wgrad_layers(float* const* grads, WgLayerDesc* L, int Lp, int Lv, float*
   return n;
 }
 int art_wgrad_layers(float* const* grads, WgLayerDesc* L) { return art_wgrad_layers(grads, L, 10, 4, nullptr, nullptr); }
-float* wgrad_fold_tmp(float* ws);   // aon_train.hip
 
 // dst[r * ldd + col_off + c] = src[r * lds + slot(c)] for the c < 3 + 6 L columns of an encoding with L levels, taken out of the kernels'
 // Lfull-level slot layout [x ; first block of 3 Lfull ; shifted block of 3 Lfull]
@@ -625,7 +617,7 @@ __global__ void art_remap_enc_kernel(const float* __restrict__ src, int lds, flo
 // articulation 32); params / latents: the forward's inputs (needed for the latent-column products).
 // Round 6: a level's second stage NOT launched by its own call but handed back, so that the two levels' grouped kernels run back to back
 // and ONE second stage serves both (launch_art_wgrad_post2): reduce -> un-folding products -> finishing kernel were three launches in a
-// row per level with the chip all but idle, level 0's in front of level 1's grouped kernel.  Opaque to the C ABI layer (kArtWgDeferredBytes).
+// row per level with the chip all but idle, level 0's in front of level 1's grouped kernel.  Opaque to the C ABI layer (kArtWgDeferredBytes, aon_launch.h).
 struct ArtWgDeferred {
   ReduceArgs reduce;
   int reduce_blocks;
@@ -634,14 +626,13 @@ struct ArtWgDeferred {
   ArtFinishArgs finish;
   int finish_blocks;
 };
-constexpr int kArtWgDeferredBytes = 4096;   // (aon_capi.hip keeps two of these on its stack)
-static_assert(sizeof(ArtWgDeferred) <= kArtWgDeferredBytes && alignof(ArtWgDeferred) <= 16, "ArtWgDeferred outgrew its storage in aon_capi.hip");
-int art_wgrad_deferred_bytes() { return (int)sizeof(ArtWgDeferred); }   // (aon_capi.hip checks its storage against this: the constant is repeated there)
+static_assert(sizeof(ArtWgDeferred) <= kArtWgDeferredBytes && alignof(ArtWgDeferred) <= 16, "ArtWgDeferred outgrew its storage in train_bwd_impl (aon_launch.h)");
+int art_wgrad_deferred_bytes() { return (int)sizeof(ArtWgDeferred); }
 
 hipError_t launch_art_wgrad(const float* planes, const float* dplanes, const float* d_raw, const float* dxp, int64_t Np,
                             const float* const* params, const float* shape, const float* app, const float* art,
                             float* const* grads, float* g_shape, float* g_app, float* g_art, float* ws, hipStream_t stream, const WgAux* aux,
-                            int Lp, int Lv, const void* packed_bwd, int phase, bool accumulate_latents, const WgPost* post, ArtWgDeferred* defer) {
+                            int Lp, int Lv, const void* packed_bwd, int phase, bool accumulate_latents, ArtWgDeferred* defer) {
   // packed_bwd: the transposed stream the chain of these planes ran with -- its FORM says whether the planes carry bottleneck rows (null: literal)
   if (packed_bwd && stream_form(packed_bwd) == kFormUnknown) return hipErrorInvalidValue;   // (a copy nobody declared)
   const bool fold = packed_bwd && stream_form(packed_bwd) == kFormFolded;
@@ -664,14 +655,11 @@ hipError_t launch_art_wgrad(const float* planes, const float* dplanes, const flo
                         {0, 128, 0, 3, 1, 163, grads[0]},  {0, 128, 4, 1, 1, 1, grads[1]}};
   const int OH[8] = {0, 1, 2, 2, 3, 4, 5, 5};
   // head jobs 0..2 (density head on H7, rgb head on V3, the sums of d_raw) read forward planes and d_raw only: independent of the chain
-  hipStream_t caller_stream = stream;
-  if (defer && (phase == kWgEarly || post || !dflt)) return hipErrorInvalidValue;   // (other degrees: remap launches between the stages; not deferred)
-  if (hipError_t e = run_wgrad_plan(L, n, H, 6, O, OH, 8, planes, dplanes, kAPlRows, Np, ws, stream, aux, phase, 3, phase == kWgEarly ? nullptr : post, &stream,
+  if (defer && (phase == kWgEarly || !dflt)) return hipErrorInvalidValue;   // (other degrees: remap launches between the stages; not deferred)
+  if (hipError_t e = run_wgrad_plan(L, n, H, 6, O, OH, 8, planes, dplanes, kAPlRows, Np, ws, stream, aux, phase, 3, nullptr,
                                     defer ? &defer->reduce : nullptr, defer ? &defer->reduce_blocks : nullptr); e != hipSuccess)
     return e;
   if (phase == kWgEarly) return hipSuccess;
-  // (from here on `stream` is the stream of the second stage: the caller's, or the side stream of `post`)
-  (void)caller_stream;
   if (!dflt) {
     auto remap = [&](const float* src, int lds, float* dst, int ldd, int col_off, int rows, int Lx, int Lfull) {
       const int tot = rows * (3 + 6 * Lx);
@@ -717,9 +705,7 @@ hipError_t launch_art_wgrad(const float* planes, const float* dplanes, const flo
     return hipSuccess;
   }
   art_finish_kernel<<<dim3(blk), dim3(1024), 0, stream>>>(F);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  if (post && post->side) return hipEventRecord(post->side->join, stream);   // the caller (or the next level's second stage) waits for this
-  return hipSuccess;
+  return hipGetLastError();
 }
 
 // The deferred second stages of two levels: ONE reduce launch, ONE launch of the (up to) six un-folding products, then the finishing

@@ -19,6 +19,7 @@
 //     a deterministic second stage (fixed order, no atomics) sums the partials.  ~8x fewer partial bytes than round 2, which
 //     split EVERY layer over all 256 workgroups.
 #pragma once
+#include "aon_launch.h"
 #include "aon_mlp_core.h"
 
 namespace aon {
@@ -632,25 +633,6 @@ inline void head_segments(int64_t Np, int& nseg, int64_t& seg_len) {
   seg_len = ((Np + nseg - 1) / nseg + 31) / 32 * 32;
   nseg = (int)((Np + seg_len - 1) / seg_len);
 }
-
-// An optional side stream for the head reductions of a level (with its fork / join events): they are HBM-bound plane-row sums
-// with a small register / LDS footprint, so their workgroups fit next to the weight-gradient workgroups (384 of the 512 registers
-// per SIMD, 144 of the 160 KB of LDS) and run in their shadow instead of behind them.  Null: everything on one stream.
-struct WgAux {
-  hipStream_t stream;
-  hipEvent_t fork, join;
-};
-
-// Round 6: what follows a level's grouped kernel -- the second stage, the un-folding products, the latent columns (three launches of 15-60 us
-// in a row) -- may run on a side stream (`side`), beside the NEXT level's head reductions and grouped kernel instead of in front of them;
-// `wait_first`: an event the second stage of THIS level waits for first (the other level's finishing kernels, whose latent gradients this
-// level's are added to).  The caller orders its stream behind `side->join` before it reads any result.
-struct WgPost {
-  const WgAux* side;
-  hipEvent_t wait_first;
-};
-
-enum : int { kWgAll = 0, kWgEarly = 1, kWgRest = 2 };   // phases of a level's weight-gradient call (run_wgrad_plan)
 
 struct HeadDesc {
   const float* plane; int row; int rows;   // plane == null: record sums only (rows = 1)

@@ -63,23 +63,30 @@ class NeRFMLP(nn.Module):
     # 2.4 MB): no version/pointer key can go stale, so `p.data.copy_()`, `dist.broadcast(p.data)`, EMA or clipping code
     # that mutates parameters without bumping `p._version` is seen exactly as nn.Linear would see it.  `fresh=True`
     # (training) writes into a new buffer, because autograd saves the stream for backward and a later forward must not
-    # overwrite what an earlier graph still needs; inference reuses one buffer per stream kind (stream-ordered).
+    # overwrite what an earlier graph still needs; inference reuses one buffer per stream kind and per (device, torch stream) the call
+    # is made on (stream-ordered; `_stream_buffer`).
     _PACKERS = {"fwd": "pack_vanilla_mlp", "bwd": "pack_vanilla_mlp_bwd"}
 
     def _pack(self, kind: str, fresh: bool, out: torch.Tensor | None = None) -> torch.Tensor:
         params = dict(self.named_parameters())
         dev = next(iter(params.values())).device
-        if out is None:
-            out = None if fresh else self._streams.get(kind)
-        if out is not None and out.device != dev:
-            out = None
+        if out is None and not fresh:
+            out = self._stream_buffer(kind, dev)
         if not self.geometry.is_default:   # other degrees on the fused kernels (fits_fused_inference): zero-weight slots
             out = getattr(ops, self._PACKERS[kind])(params, out=out, degrees=(self.min_deg_point, self.max_deg_point, self.deg_view))
         else:
             out = getattr(ops, self._PACKERS[kind])(params, out=out)
-        if not fresh:
-            self._streams[kind] = out
         return out
+
+    _BYTES = {"fwd": "aon_mlp_packed_bytes", "bwd": "aon_bwd_packed_bytes"}
+
+    def _stream_buffer(self, kind: str, dev) -> torch.Tensor:
+        """The module's inference buffer of `kind` for `dev`'s current stream (ops.StreamCache: one per (device, stream), so renders of one
+        model on two streams never re-pack into a buffer the other stream's kernels still read)."""
+        cache = self._streams.get(kind)
+        if cache is None:
+            cache = self._streams[kind] = ops.StreamCache(register=False)
+        return ops._scratch(cache, dev, int(getattr(ops.lib, self._BYTES[kind])()))
 
     def packed(self, fresh: bool = False) -> torch.Tensor:
         """Forward weight stream of the fp32 kernels."""

@@ -60,7 +60,6 @@ class NeRFMLP(nn.Module):
                 list(self.views_linear)[1:] + [self.bottleneck_layer, self.density_layer, self.rgb_layer]:
             init.xavier_uniform_(m.weight)  # views_linear[0] keeps the default init, like the reference (:147-151)
         self._streams = {}
-        self._small = None
 
     # weight streams are rebuilt from the live parameters on every call (see vanilla NeRFMLP._pack: nothing can go stale)
     _PACKERS = {"fwd": "pack_art_mlp", "bwd": "pack_art_mlp_bwd"}
@@ -68,14 +67,18 @@ class NeRFMLP(nn.Module):
     def _pack(self, kind: str, fresh: bool, out: torch.Tensor | None = None) -> torch.Tensor:
         params = dict(self.named_parameters())
         dev = next(iter(params.values())).device
-        if out is None:
-            out = None if fresh else self._streams.get(kind)
-        if out is not None and out.device != dev:
-            out = None
-        out = getattr(ops, self._PACKERS[kind])(params, out=out, degrees=self.degrees)
-        if not fresh:
-            self._streams[kind] = out
-        return out
+        if out is None and not fresh:
+            out = self._stream_buffer(kind, dev)
+        return getattr(ops, self._PACKERS[kind])(params, out=out, degrees=self.degrees)
+
+    _BYTES = {"fwd": "aon_art_packed_bytes", "bwd": "aon_art_bwd_packed_bytes", "small": "aon_art_small_bytes"}
+
+    def _stream_buffer(self, kind: str, dev) -> torch.Tensor:
+        """The module's inference buffer of `kind` for `dev`'s current stream (one per (device, stream): see vanilla NeRFMLP._stream_buffer)."""
+        cache = self._streams.get(kind)
+        if cache is None:
+            cache = self._streams[kind] = ops.StreamCache(register=False)
+        return ops._scratch(cache, dev, int(getattr(ops.lib, self._BYTES[kind])()))
 
     def packed(self, fresh: bool = False) -> torch.Tensor:
         return self._pack("fwd", fresh)
@@ -94,9 +97,7 @@ class NeRFMLP(nn.Module):
         """Per-call latent-folded block (cheap: ~0.1 MFLOP); always rebuilt because latents are call arguments."""
         params = dict(self.named_parameters())
         dev = next(iter(params.values())).device
-        out = self._small if (self._small is not None and self._small.device == dev) else None
-        self._small = ops.art_prepare(params, latents, out=out, degrees=self.degrees)
-        return self._small
+        return ops.art_prepare(params, latents, out=self._stream_buffer("small", dev), degrees=self.degrees)
 
     def forward(self, pos, condition, latents):
         if self.embed_deg:

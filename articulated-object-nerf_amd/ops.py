@@ -5,6 +5,7 @@ stream.  CPU tensors are rejected: there is no host fallback.
 """
 from __future__ import annotations
 
+import collections as _collections
 import ctypes as C
 
 import torch
@@ -17,6 +18,62 @@ ACT_NONE, ACT_VANILLA, ACT_ARTICULATED = 0, 1, 2
 
 def _stream() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+STREAM_CACHE_ENTRIES = 8      # (device, stream) entries one scratch cache keeps, least recently used dropped first (as _TRAIN_POOL_SIZES)
+_STREAM_CACHES: list = []     # every module-level StreamCache: release_workspaces() clears them all
+
+
+class StreamCache:
+    """Scratch buffers of the whole-path calls, ONE per (device index, stream handle).  Plain Python, no torch and no library call
+    (tests/test_stream_cache_cpu.py drives it with fake handles): `get(key, need, alloc)` returns the key's buffer when it holds `need`
+    bytes (`.numel()`), else `alloc(need)`, which replaces that key's entry alone.
+
+    Why per stream: a workspace is written and read by the kernels of ONE call, so two calls in flight on two streams of a device must
+    never share one (keyed by the device alone, they overwrote each other's t / weights / sample records and -- occupancy and early-stop
+    paths -- the int32 gather lists the MLP kernel indexes with).  Why no record_stream: `alloc` runs with the key's stream current and
+    the buffer is only ever handed back to that stream, so torch's caching allocator owns the block for the stream that uses it; an entry
+    dropped here (grown, evicted, release_workspaces()) is reused by that stream in order, or by another one only after the allocator has
+    seen it idle."""
+
+    def __init__(self, max_entries: int = STREAM_CACHE_ENTRIES, register: bool = True):
+        self.max_entries = int(max_entries)
+        self._entries: "_collections.OrderedDict" = _collections.OrderedDict()
+        if register:
+            _STREAM_CACHES.append(self)
+
+    def get(self, key, need: int, alloc):
+        buf = self._entries.get(key)
+        if buf is None or buf.numel() < need:
+            buf = self._entries[key] = alloc(need)
+        self._entries.move_to_end(key)
+        while len(self._entries) > self.max_entries:
+            self._entries.popitem(last=False)
+        return buf
+
+    def clear(self) -> None:
+        self._entries.clear()
+
+    def values(self):
+        return list(self._entries.values())
+
+    def __len__(self) -> int:
+        return len(self._entries)
+
+
+def stream_key(device) -> tuple:
+    """(device index, handle of torch's current stream on it): the key of every StreamCache."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"workspace requested on {dev}; the HIP path needs a cuda (ROCm) device and has no CPU fallback")
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    return idx, torch.cuda.current_stream(idx).cuda_stream
+
+
+def _scratch(cache: StreamCache, device, need: int) -> torch.Tensor:
+    """`need` bytes of `cache` for a call on `device`'s current stream."""
+    # (torch's allocator takes the block for the current stream of `device`: the stream of the key)
+    return cache.get(stream_key(device), need, lambda nbytes: torch.empty(nbytes, dtype=torch.uint8, device=device))
 
 
 def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -467,7 +524,7 @@ def set_coarse_fusion(on: bool) -> None:
 
 
 # ------------------------------------------------------------------ R9 whole path
-_WS_CACHE: dict = {}
+_WS_CACHE = StreamCache()
 # rays rendered per internal chunk: a whole 640x480 frame (307,200 rays) in one pass -- 4,892 B/ray of per-ray buffers (sample
 # records, t, weights, the per-ray view bias) = 1.5 GB of the 288 GB, so that every per-ray kernel is ONE launch per frame (round 2: 65,536-ray chunks, five 30-60 us launches
 # each of which spent a fifth of its time ramping up and draining)
@@ -481,12 +538,7 @@ def _workspace(device, n_rays: int, st=None) -> torch.Tensor:
     need = int(lib.aon_render_workspace_bytes_ex(min(n_rays, chunk), None if st is None else C.byref(st)))
     if need < 0:
         check(need, "aon_render_workspace_bytes_ex")
-    key = str(device)
-    ws = _WS_CACHE.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
-        _WS_CACHE[key] = ws
-    return ws
+    return _scratch(_WS_CACHE, device, need)
 
 
 def _check_noise(noise, n, op, num_levels):
@@ -803,7 +855,7 @@ def mlp_bwd_chain(packed_bwd, packed_fwd, d_raw, masks, plane_shape):
     return dplanes
 
 
-_WG_WS: dict = {}
+_WG_WS = StreamCache()
 
 
 def vanilla_wgrad(planes, dplanes, d_raw, packed_bwd):
@@ -813,11 +865,7 @@ def vanilla_wgrad(planes, dplanes, d_raw, packed_bwd):
     if packed_bwd is None:
         raise ValueError("vanilla_wgrad: pass the transposed stream (pack_vanilla_mlp_bwd) the backward chain of these planes ran with")
     dev = planes.device
-    key = str(dev)
-    need = int(lib.aon_wgrad_workspace_bytes())
-    if key not in _WG_WS or _WG_WS[key].numel() < need:
-        _WG_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    ws = _WG_WS[key]
+    ws = _scratch(_WG_WS, dev, int(lib.aon_wgrad_workspace_bytes()))
     grads = {name: torch.empty(VANILLA_PARAM_SHAPES[name], dtype=torch.float32, device=dev) for name in VANILLA_PARAM_ORDER}
     arr = (C.c_void_p * len(VANILLA_PARAM_ORDER))(*[grads[n].data_ptr() for n in VANILLA_PARAM_ORDER])
     with torch.cuda.device(dev):
@@ -866,11 +914,7 @@ def art_wgrad(planes, dplanes, d_raw, dxp, params: dict, latents: dict, degrees=
     if packed_bwd is None:
         raise ValueError("art_wgrad: pass packed_bwd= the transposed stream (pack_art_mlp_bwd) the backward chain of these planes ran with")
     dev = planes.device
-    key = str(dev)
-    need = int(lib.aon_wgrad_workspace_bytes())
-    if key not in _WG_WS or _WG_WS[key].numel() < need:
-        _WG_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    ws = _WG_WS[key]
+    ws = _scratch(_WG_WS, dev, int(lib.aon_wgrad_workspace_bytes()))
     tensors, parr = _art_param_array(params, degrees)
     shape, app, art = _latent(latents, "density", 128), _latent(latents, "color", 128), _latent(latents, "articulation", 32)
     shapes = art_param_shapes(degrees)
@@ -957,8 +1001,6 @@ def set_fwd_merge(on: bool) -> None:
 # reserved INSIDE the timed loop of every run of tools/train_bench.py; when the stall fell on an early step the device ran dry and the run
 # averaged 33-40 ms per step instead of 30.4, tools/slowmode_probe.sh).  A pooled buffer is only handed to the stream it was returned on;
 # at most two per (device, size) are kept; release_workspaces() drops them.
-import collections as _collections
-
 _TRAIN_POOL: "_collections.OrderedDict" = _collections.OrderedDict()
 _TRAIN_POOL_KEEP = 2          # buffers kept per (device, size)
 _TRAIN_POOL_SIZES = 6         # distinct (device, size) keys kept, least recently returned dropped first (a loop whose ray count changes every
@@ -1220,7 +1262,7 @@ def gmlp_fwd(geom: MlpGeometry, params: dict, samples_enc, viewdirs_enc):
 # the default-width network gets ~2,400-ray chunks of 193 samples = 460 k-row GEMMs: still hundreds of 128-row tiles per launch.
 G_WS_BUDGET_BYTES = 2 << 30
 G_CHUNK_RAYS = 8192            # upper bound on rays per chunk
-_GWS_CACHE: dict = {}
+_GWS_CACHE = StreamCache()
 
 
 def _grender_chunk_rays(gst, st, n: int) -> tuple[int, int]:
@@ -1251,11 +1293,7 @@ def grender_fwd(geom: MlpGeometry, params_c: dict, params_f, rays_o, rays_d, vie
     tc, arr_c = _gmlp_param_array(geom, params_c)
     tf, arr_f = _gmlp_param_array(geom, params_f) if num_levels == 2 else (None, None)
     _, need = _grender_chunk_rays(gst, st, n)
-    key = str(dev)
-    ws = _GWS_CACHE.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        _GWS_CACHE[key] = ws
+    ws = _scratch(_GWS_CACHE, dev, need)
     with torch.cuda.device(dev):
         check(lib.aon_grender_fwd(C.byref(gst), arr_c, arr_f, _ptr(o), _ptr(d), _ptr(v), n, float(near), float(far), int(bool(white_bkgd)), num_levels,
                                   _ptr(tr), _ptr(uu), us, _ptr(outs[0][0]), _ptr(outs[0][1]), _ptr(outs[0][2]), _ptr(fine[0]), _ptr(fine[1]),
@@ -1313,14 +1351,14 @@ def grender_bwd(geom: MlpGeometry, ws, params_per_level, rays_d, white_bkgd, num
 
 
 def release_workspaces() -> None:
-    """Drop the per-device workspace caches of the inference calls (fused path: up to 1.35 GB, or 3.3 GB with materialised
-    encodings; layer-wise engine: G_WS_BUDGET_BYTES = 2 GB) back to torch's caching allocator.  They are re-made on the
-    next call; and the pool of training workspaces / scratch buffers (`_TRAIN_POOL`: up to two of each size in use, 26 GB per pair at
-    4096 articulated rays)."""
+    """Drop the per-(device, stream) workspace caches of the inference calls (fused path: up to 1.35 GB, or 3.3 GB with materialised
+    encodings; layer-wise engine: G_WS_BUDGET_BYTES = 2 GB; occupancy / early-stop renders; the stage-level weight gradients) back to
+    torch's caching allocator.  They are re-made on the next call; and the pool of training workspaces / scratch buffers (`_TRAIN_POOL`:
+    up to two of each size in use, 26 GB per pair at 4096 articulated rays).  The per-model packed inference buffers (NeRFMLP._streams)
+    belong to their module and are not touched."""
     _TRAIN_POOL.clear()
-    _WS_CACHE.clear()
-    _GWS_CACHE.clear()
-    _WG_WS.clear()
+    for cache in _STREAM_CACHES:     # _WS_CACHE, _GWS_CACHE, _OCC_WS_CACHE, _WG_WS
+        cache.clear()
 
 
 # ------------------------------------------------------------------ measurement aid
@@ -1607,7 +1645,7 @@ def occupancy_grid(density, lo, hi, threshold: float = 0.01, dilate: int = 1) ->
     return OccupancyGrid(bits, cells, lo32, step, threshold, dilate)
 
 
-_OCC_WS_CACHE: dict = {}
+_OCC_WS_CACHE = StreamCache()
 
 
 def _occ_workspace(device, n_rays: int, st, workspace_bytes):
@@ -1616,12 +1654,7 @@ def _occ_workspace(device, n_rays: int, st, workspace_bytes):
     need = int(lib.aon_render_occ_workspace_bytes(min(n_rays, MAX_CHUNK_RAYS), C.byref(st)))
     if need < 0:
         check(need, "aon_render_occ_workspace_bytes")
-    key = str(device)
-    ws = _OCC_WS_CACHE.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
-        _OCC_WS_CACHE[key] = ws
-    return ws
+    return _scratch(_OCC_WS_CACHE, device, need)
 
 
 def _occ_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, num_levels, u, opts, workspace_bytes):
@@ -1675,12 +1708,7 @@ def _stop_workspace(device, n_rays: int, st, workspace_bytes):
     need = int(lib.aon_render_stop_workspace_bytes(min(n_rays, MAX_CHUNK_RAYS), C.byref(st)))
     if need < 0:
         check(need, "aon_render_stop_workspace_bytes")
-    key = str(device)
-    ws = _OCC_WS_CACHE.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
-        _OCC_WS_CACHE[key] = ws
-    return ws
+    return _scratch(_OCC_WS_CACHE, device, need)
 
 
 def _stop_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, eps, round_samples, num_levels, u, opts, workspace_bytes):

@@ -150,6 +150,16 @@ _SIGS = {
     "aon_grender_train_scratch_bytes": (_l, [_p, _l, _i, _p]),
     "aon_grender_fwd_train": (_i, [_p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p]),
     "aon_grender_bwd": (_i, [_p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p]),
+    # per-ray near / far from a ray-box intersection (aon_ray_bounds last)
+    "aon_ray_limits_box": (_i, [_p, _p, _l, _p, _p, _p, _p, _p]),
+    "aon_ray_limits_workspace_bytes": (_l, [_l]),
+    "aon_ray_limits": (_i, [_p, _p, _l, _p, _p, _p, _p, _p, _p, _l, _p]),
+    "aon_sample_along_rays_bounds": (_i, [_p, _p, _l, _i, _p, _p, _i, _p, _p, _p, _p]),
+    "aon_render_fwd_bounds": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _f, _i, _p, _p]),
+    "aon_art_render_fwd_bounds": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p,
+                                       _f, _i, _p, _p]),
+    "aon_render_fwd_train_bounds": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p]),
+    "aon_art_render_fwd_train_bounds": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p]),
 }
 
 
@@ -172,6 +182,11 @@ class RenderOptsC(C.Structure):
 class OccupancyC(C.Structure):
     """aon_occupancy (include/aon_hip.h)."""
     _fields_ = [("bits", C.c_void_p), ("cells", C.c_int64 * 3), ("lo", C.c_float * 3), ("step", C.c_float * 3)]
+
+
+class RayBoundsC(C.Structure):
+    """aon_ray_bounds (include/aon_hip.h)."""
+    _fields_ = [("near_ray", C.c_void_p), ("far_ray", C.c_void_p), ("live", C.c_void_p)]
 
 
 for _name, (_res, _args) in _SIGS.items():

@@ -73,6 +73,7 @@ def _check_not_released(ctx):
 class RenderVanilla(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, packs, opts, noise, *params):
+        # near / far: numbers, or per-ray tensors -- data like the rays: non-differentiable inputs, no gradient returned.
         # packs: [(packed_fwd, packed_bwd)] per level; params: 24 tensors per level in ops.VANILLA_PARAM_ORDER.  The whole
         # forward is ONE C call (aon_render_fwd_train); the backward chain reads the forward stream for its head weights.
         ctx.rays_d = rays_d

@@ -216,6 +216,43 @@ int aon_sample_along_rays_ex(const float* rays_o, const float* rays_d, int64_t n
                                              lindisp != 0, inv_near, inv_far), "aon_sample_along_rays_ex");
 }
 
+// ---- per-ray near / far (aon_bounds.hip) ----
+static const char* box_bad(const float* lo3, const float* hi3) {
+  if (!lo3 || !hi3) return "null box";
+  for (int a = 0; a < 3; ++a)
+    if (lo3[a] != lo3[a] || hi3[a] != hi3[a]) return "box bound is NaN";
+  return nullptr;
+}
+int aon_ray_limits_box(const float* rays_o, const float* rays_d, int64_t n_rays, const float* lo3_host, const float* hi3_host, float* near_ray,
+                       float* far_ray, void* stream) {
+  if (n_rays < 0) return fail(AON_E_INVALID, "aon_ray_limits_box: bad size");
+  if (const char* bad = box_bad(lo3_host, hi3_host)) return fail(AON_E_INVALID, (std::string("aon_ray_limits_box: ") + bad).c_str());
+  if (n_rays == 0) return AON_OK;
+  if (!rays_o || !rays_d || !near_ray || !far_ray) return fail(AON_E_INVALID, "aon_ray_limits_box: null pointer");
+  return check(aon::launch_ray_limits(rays_o, rays_d, n_rays, lo3_host, hi3_host, near_ray, far_ray, nullptr, nullptr, (hipStream_t)stream),
+               "aon_ray_limits_box");
+}
+int64_t aon_ray_limits_workspace_bytes(int64_t n_rays) { return aon::ray_limits_workspace_bytes(n_rays < 1 ? 1 : n_rays); }
+int aon_ray_limits(const float* rays_o, const float* rays_d, int64_t n_rays, const float* lo3_host, const float* hi3_host, float* near_ray,
+                   float* far_ray, uint8_t* live, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (n_rays < 0) return fail(AON_E_INVALID, "aon_ray_limits: bad size");
+  if (const char* bad = box_bad(lo3_host, hi3_host)) return fail(AON_E_INVALID, (std::string("aon_ray_limits: ") + bad).c_str());
+  if (n_rays == 0) return AON_OK;
+  if (!rays_o || !rays_d || !near_ray || !far_ray || !workspace) return fail(AON_E_INVALID, "aon_ray_limits: null pointer");
+  if (reinterpret_cast<uintptr_t>(workspace) & 3) return fail(AON_E_INVALID, "aon_ray_limits: workspace must be 4-byte aligned");
+  if (workspace_bytes < aon::ray_limits_workspace_bytes(n_rays)) return fail(AON_E_WORKSPACE, "aon_ray_limits: workspace smaller than aon_ray_limits_workspace_bytes()");
+  return check(aon::launch_ray_limits(rays_o, rays_d, n_rays, lo3_host, hi3_host, near_ray, far_ray, live, static_cast<char*>(workspace),
+                                      (hipStream_t)stream), "aon_ray_limits");
+}
+int aon_sample_along_rays_bounds(const float* rays_o, const float* rays_d, int64_t n_rays, int S, const float* near_ray, const float* far_ray,
+                                 int lindisp, const float* t_rand, float* t_vals, float* coords, void* stream) {
+  if (n_rays < 0 || S < 2) return fail(AON_E_INVALID, "aon_sample_along_rays_bounds: bad size");
+  if (n_rays == 0) return AON_OK;
+  if (!t_vals || !near_ray || !far_ray || (coords && (!rays_o || !rays_d))) return fail(AON_E_INVALID, "aon_sample_along_rays_bounds: null pointer");
+  return check(aon::launch_sample_along_rays(rays_o, rays_d, n_rays, S, 0.f, 0.f, t_rand, t_vals, coords, (hipStream_t)stream, lindisp != 0, 0.f, 0.f,
+                                             near_ray, far_ray), "aon_sample_along_rays_bounds");
+}
+
 int aon_composite_ex(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* t_vals, const float* dirs,
                      int64_t n_rays, int S, int white_bkgd, int act, const aon_render_opts* opts, float* comp_rgb, float* acc,
                      float* depth, float* weights, void* stream) {

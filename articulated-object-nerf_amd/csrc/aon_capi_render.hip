@@ -76,7 +76,7 @@ struct OccCtx {
 // instances); the empty samples' records hold the zero-density sentinel.  Same view bias, same kernel arithmetic per sample.
 static hipError_t launch_net(const NetRef& net, const float* o, const float* d, const float* v, const float* t, int64_t n, int S,
                              float* raw, hipStream_t stream, const Geo* g = nullptr, const Ws* w = nullptr, const OccCtx* occ = nullptr,
-                             int level = 0) {
+                             int level = 0, const uint8_t* live = nullptr) {
   if (g && g->other_degrees) {
     // NeRF(min_deg_point, max_deg_point, deg_view) with at most 10 / 4 levels: the encodings are computed by the stage kernels in
     // the fused kernel's 63 / 27-slot layout (zeros in the missing levels' slots, matched by zero weights in the packed stream,
@@ -105,7 +105,7 @@ static hipError_t launch_net(const NetRef& net, const float* o, const float* d, 
       const int* idx = nullptr;
       const int64_t* count = nullptr;
       if (hipError_t e = aon::launch_occ_compact_round(occ->grid, o, d, t, n, S, s0, s1, w->stop, raw, w->occ, occ->tally ? occ->tally + level : nullptr,
-                                                       &idx, &count, stream);
+                                                       &idx, &count, stream, live);
           e != hipSuccess)
         return e;
       {
@@ -124,7 +124,8 @@ static hipError_t launch_net(const NetRef& net, const float* o, const float* d, 
   if (occ) {
     const int* idx = nullptr;
     const int64_t* count = nullptr;
-    if (hipError_t e = aon::launch_occ_compact(occ->grid, o, d, t, n, S, raw, w->occ, occ->tally ? occ->tally + level : nullptr, &idx, &count, stream);
+    if (hipError_t e = aon::launch_occ_compact(occ->grid, o, d, t, n, S, raw, w->occ, occ->tally ? occ->tally + level : nullptr, &idx, &count, stream,
+                                                live);
         e != hipSuccess)
       return e;
     MlpTimer timer(stream, n * S);
@@ -142,7 +143,7 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
                        const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
                        const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
                        float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, hipStream_t stream,
-                       const aon_render_opts* opts, const OccCtx* occ = nullptr) {
+                       const aon_render_opts* opts, const OccCtx* occ = nullptr, const aon_ray_bounds* bounds = nullptr) {
   Geo g;
   if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
   if (n_rays < 0 || (num_levels != 1 && num_levels != 2)) return fail(AON_E_INVALID, "render: bad size / num_levels");
@@ -185,15 +186,19 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
     const float* d = rays_d + r0 * 3;
     const float* v = viewdirs + r0 * 3;
     const float* uu = u_stride ? u + r0 * u_stride : u;
+    // [per-ray bounds, DESIGN.md section 4.11] the chunk's near / far / live
+    const float* near_ray = bounds ? bounds->near_ray + r0 : nullptr;
+    const float* far_ray = bounds ? bounds->far_ray + r0 : nullptr;
+    const uint8_t* live = bounds && bounds->live ? bounds->live + r0 : nullptr;
     int rc;
     // level 0 (model.py:150-160, :175-197)
     {
       KTimer timer(kSampleT, stream, n);
       rc = check(aon::launch_sample_along_rays(o, d, n, g.Sc, near_, far_, t_rand ? t_rand + r0 * g.Sc : nullptr, w.t_c, nullptr, stream,
-                                               g.lindisp, g.inv_near, g.inv_far), who);
+                                               g.lindisp, g.inv_near, g.inv_far, near_ray, far_ray), who);
     }
     if (rc) return rc;
-    rc = check(launch_net(coarse, o, d, v, w.t_c, n, g.Sc, w.raw, stream, &g, &w, occ, 0), who);
+    rc = check(launch_net(coarse, o, d, v, w.t_c, n, g.Sc, w.raw, stream, &g, &w, occ, 0, live), who);
     if (rc) return rc;
     if (with_stop && occ->stop_dev) {
       rc = check(aon::launch_occ_stop_store(w.stop, 0, occ->stop_dev + r0 * 2, n, 2, stream), who);
@@ -219,7 +224,7 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
                                                             w.t_f, stream), who);
       if (rc) return rc;
     }
-    rc = check(launch_net(fine, o, d, v, w.t_f, n, g.Sf, w.raw, stream, &g, &w, occ, 1), who);
+    rc = check(launch_net(fine, o, d, v, w.t_f, n, g.Sf, w.raw, stream, &g, &w, occ, 1, live), who);
     if (rc) return rc;
     if (with_stop && occ->stop_dev) {
       rc = check(aon::launch_occ_stop_store(w.stop, 0, occ->stop_dev + r0 * 2 + 1, n, 2, stream), who);
@@ -329,21 +334,29 @@ static int render_stop(const char* who, const NetRef& c, const NetRef& f, const 
                        int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels, const float* t_rand, const float* u,
                        int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
                        int64_t workspace_bytes, hipStream_t stream, const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev,
-                       float eps, int round_samples, int32_t* stop_dev) {
+                       float eps, int round_samples, int32_t* stop_dev, const aon_ray_bounds* bounds = nullptr) {
   OccCtx ctx{};
+  if (bounds) {
+    if (!bounds->near_ray || !bounds->far_ray) return fail(AON_E_INVALID, (std::string(who) + ": null near_ray / far_ray in bounds").c_str());
+    if (bounds->live && t_rand) return fail(AON_E_INVALID, (std::string(who) + ": ray_live is inference only: t_rand (randomized sampling) is refused").c_str());
+  }
   if (occ)
     if (const char* bad = occ_grid_bad(occ, ctx.grid)) return fail(AON_E_INVALID, (std::string(who) + ": " + bad).c_str());
-  if (const char* bad = occ_opts_bad(opts, c.articulated, t_rand)) return fail(AON_E_INVALID, (std::string(who) + ": " + bad).c_str());
+  // the compaction path (mark / scan / emit and the GATHER launches): a grid, early termination or a ray mask
+  const bool compact = occ || (bounds && bounds->live) || eps != 0.f;
+  // (bounds alone: aon_render_fwd_ex with per-ray planes, and that call's rules -- t_rand, noise and other degrees are its to take)
+  if (!bounds || compact)
+    if (const char* bad = occ_opts_bad(opts, c.articulated, t_rand)) return fail(AON_E_INVALID, (std::string(who) + ": " + bad).c_str());
   if (!(eps >= 0.f && eps < 1.f)) return fail(AON_E_INVALID, (std::string(who) + ": eps must be in [0, 1)").c_str());
   if (round_samples < 1) return fail(AON_E_INVALID, (std::string(who) + ": round_samples must be >= 1").c_str());
   ctx.tally = occupied_dev;
   if (eps == 0.f) {   // off: today's single-launch paths, and the bookkeeping of a render in which no ray stopped
     const int rc = render_impl(who, c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c,
-                               depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, opts, occ ? &ctx : nullptr);
+                               depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, opts, compact ? &ctx : nullptr, bounds);
     if (rc != AON_OK || n_rays == 0) return rc;
     Geo g;
     (void)make_geo(opts, g);
-    if (!occ && occupied_dev)
+    if (!compact && occupied_dev)
       if (int r2 = check(aon::launch_occ_tally_set(occupied_dev, n_rays * g.Sc, num_levels == 2 ? n_rays * g.Sf : 0, stream), who); r2 != AON_OK) return r2;
     if (stop_dev)
       for (int l = 0; l < num_levels; ++l)
@@ -355,7 +368,7 @@ static int render_stop(const char* who, const NetRef& c, const NetRef& f, const 
   ctx.R = round_samples;
   ctx.stop_dev = stop_dev;
   return render_impl(who, c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c,
-                     rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, opts, &ctx);
+                     rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, opts, &ctx, bounds);
 }
 int aon_render_fwd_stop(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
                         const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
@@ -411,6 +424,32 @@ int aon_art_render_fwd(const void* packed_coarse, const void* small_coarse, cons
   return aon_art_render_fwd_ex(packed_coarse, small_coarse, packed_fine, small_fine, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd,
                                num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream,
                                nullptr);
+}
+
+
+// ---- per-ray near / far (NeRF.forward / NeRF_AE_Art.forward called with the (N, 1) tensors of
+// helper.get_ray_limits, model.py:147-160, model_autodecoder.py:278-291) ----
+int aon_render_fwd_bounds(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                          const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                          const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                          float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                          const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev, float eps, int round_samples,
+                          int32_t* stop_dev, const aon_ray_bounds* bounds) {
+  const NetRef c{false, packed_coarse, nullptr}, f{false, packed_fine, nullptr};
+  return render_stop(bounds ? "aon_render_fwd_bounds" : "aon_render_fwd_stop", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd,
+                     num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream,
+                     opts, occ, occupied_dev, eps, round_samples, stop_dev, bounds);
+}
+int aon_art_render_fwd_bounds(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                              const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                              int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                              float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                              int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
+                              int64_t* occupied_dev, float eps, int round_samples, int32_t* stop_dev, const aon_ray_bounds* bounds) {
+  const NetRef c{true, packed_coarse, static_cast<const float*>(small_coarse)}, f{true, packed_fine, static_cast<const float*>(small_fine)};
+  return render_stop(bounds ? "aon_art_render_fwd_bounds" : "aon_art_render_fwd_stop", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_,
+                     white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes,
+                     (hipStream_t)stream, opts, occ, occupied_dev, eps, round_samples, stop_dev, bounds);
 }
 
 }  // extern "C"

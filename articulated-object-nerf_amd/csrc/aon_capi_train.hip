@@ -217,7 +217,12 @@ struct TrainNet {   // one level's network handles
 int train_fwd_impl(const char* who, bool art, const TrainNet* nets, const float* rays_o, const float* rays_d, const float* viewdirs,
                    int64_t n, float near_, float far_, int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride,
                    float* const* rgb, float* const* acc, float* const* depth, void* workspace, int64_t workspace_bytes, hipStream_t stream,
-                   const aon_render_opts* opts) {
+                   const aon_render_opts* opts, const aon_ray_bounds* bounds = nullptr) {
+  // [per-ray bounds, DESIGN.md section 4.11] level 0's t from near_ray / far_ray; the backward reads t from the workspace and does not change
+  if (bounds && (!bounds->near_ray || !bounds->far_ray)) return fail(AON_E_INVALID, (std::string(who) + ": null near_ray / far_ray in bounds").c_str());
+  if (bounds && bounds->live) return fail(AON_E_INVALID, (std::string(who) + ": ray_live is inference only (bounds->live must be NULL)").c_str());
+  const float* near_ray = bounds ? bounds->near_ray : nullptr;
+  const float* far_ray = bounds ? bounds->far_ray : nullptr;
   Geo g;
   if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
   if (g.Sf > 512) return fail(AON_E_INVALID, "train forward: more than 512 samples per ray at the fine level");
@@ -258,7 +263,7 @@ int train_fwd_impl(const char* who, bool art, const TrainNet* nets, const float*
       if (l == 0) {
         KTimer timer(kSampleT, st, nk);
         rc = check(aon::launch_sample_along_rays(o, d, nk, g.Sc, near_, far_, t_rand ? t_rand + r0 * g.Sc : nullptr, t, nullptr, st, g.lindisp, g.inv_near,
-                                                 g.inv_far), who);
+                                                 g.inv_far, near_ray ? near_ray + r0 : nullptr, far_ray ? far_ray + r0 : nullptr), who);
       } else if (!fuse) {
         KTimer timer(kSamplePdf, st, nk);
         const float* wc = w.w_c + r0 * g.Sc; const float* tc = w.lvl[0].t + r0 * g.Sc;
@@ -347,7 +352,7 @@ int train_fwd_impl(const char* who, bool art, const TrainNet* nets, const float*
       {   // stratified t of the whole batch
         KTimer timer(kSampleT, stream, n);
         if (int rc = check(aon::launch_sample_along_rays(rays_o, rays_d, n, g.Sc, near_, far_, t_rand, w.lvl[0].t, nullptr, stream, g.lindisp, g.inv_near,
-                                                         g.inv_far), who)) return rc;
+                                                         g.inv_far, near_ray, far_ray), who)) return rc;
       }
       const aon::TrainSeg cA = seg_of(R[0], 0), fA = seg_of(R[0], 1), cB = seg_of(R[1], 0), fB = seg_of(R[1], 1);
       if (int rc = mlp(&cA, 1)) return rc;
@@ -645,6 +650,27 @@ int aon_art_render_fwd_train(const void* packed_coarse, const void* small_coarse
   return aon_art_render_fwd_train_ex(packed_coarse, small_coarse, packed_fine, small_fine, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd,
                                      num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes,
                                      stream, nullptr);
+}
+
+// per-ray near / far under grad mode (model.py:147-160, model_autodecoder.py:278-291 with (N, 1) tensors)
+int aon_render_fwd_train_bounds(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels, const float* t_rand, const float* u,
+                                int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f,
+                                void* workspace, int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_ray_bounds* bounds) {
+  const TrainNet nets[2] = {{packed_coarse, nullptr, nullptr}, {packed_fine, nullptr, nullptr}};
+  float* const rgb[2] = {rgb_c, rgb_f}; float* const acc[2] = {acc_c, acc_f}; float* const dep[2] = {depth_c, depth_f};
+  return train_fwd_impl(bounds ? "aon_render_fwd_train_bounds" : "aon_render_fwd_train", false, nets, rays_o, rays_d, viewdirs, n_rays, near_, far_,
+                        white_bkgd, num_levels, t_rand, u, u_stride, rgb, acc, dep, workspace, workspace_bytes, (hipStream_t)stream, opts, bounds);
+}
+int aon_art_render_fwd_train_bounds(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                                    const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                                    int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                                    float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                                    int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_ray_bounds* bounds) {
+  const TrainNet nets[2] = {{packed_coarse, static_cast<const float*>(small_coarse), nullptr}, {packed_fine, static_cast<const float*>(small_fine), nullptr}};
+  float* const rgb[2] = {rgb_c, rgb_f}; float* const acc[2] = {acc_c, acc_f}; float* const dep[2] = {depth_c, depth_f};
+  return train_fwd_impl(bounds ? "aon_art_render_fwd_train_bounds" : "aon_art_render_fwd_train", true, nets, rays_o, rays_d, viewdirs, n_rays, near_,
+                        far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb, acc, dep, workspace, workspace_bytes, (hipStream_t)stream, opts, bounds);
 }
 
 int aon_render_bwd(const void* packed_bwd_coarse, const void* packed_fwd_coarse, const void* packed_bwd_fine, const void* packed_fwd_fine,

@@ -131,7 +131,7 @@ hipError_t launch_cast_rays(const float* t_vals, const float* o, const float* d,
                             hipStream_t stream);
 hipError_t launch_sample_along_rays(const float* rays_o, const float* rays_d, int64_t n_rays, int S, float near, float far,
                                     const float* t_rand, float* t_vals, float* coords, hipStream_t stream, int lindisp = 0,
-                                    float inv_near = 0.f, float inv_far = 0.f);
+                                    float inv_near = 0.f, float inv_far = 0.f, const float* near_ray = nullptr, const float* far_ray = nullptr);
 hipError_t launch_pos_enc(const float* x, int64_t n, int min_deg, int max_deg, float* out, hipStream_t stream, int ld = 0, int levels_out = 0);
 hipError_t launch_composite(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* t_vals,
                             const float* dirs, int64_t n_rays, int S, int white_bkgd, const ActParams& ap, float* comp_rgb,
@@ -165,16 +165,24 @@ hipError_t launch_mc(const float* grid, const int64_t* dims, float level, const 
 // ---- aon_occ.hip ----
 hipError_t launch_occ_build(const float* dens, const int64_t* dims, float thr, int dilate, uint32_t* bits, hipStream_t stream);
 int64_t occ_list_bytes(int64_t total);
+// ray_live (n bytes, or null: every ray is live): a dead ray's samples get the sentinel record and are not listed.  G.bits == nullptr: no grid
 hipError_t launch_occ_compact(const OccGrid& G, const float* rays_o, const float* rays_d, const float* t_vals, int64_t n, int S, float* raw,
-                              char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out, hipStream_t stream);
+                              char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out, hipStream_t stream,
+                              const uint8_t* ray_live = nullptr);
 int64_t occ_stop_state_bytes(int64_t n);
 hipError_t launch_occ_stop_init(char* state, int64_t n, int S, hipStream_t stream);
 hipError_t launch_occ_stop_store(const char* state, int value, int* dst, int64_t n, int stride, hipStream_t stream);
 hipError_t launch_occ_tally_set(int64_t* tally, int64_t v0, int64_t v1, hipStream_t stream);
 hipError_t launch_occ_compact_round(const OccGrid& G, const float* rays_o, const float* rays_d, const float* t_vals, int64_t n, int S, int s0, int s1,
                                     const char* state, float* raw, char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out,
-                                    hipStream_t stream);
+                                    hipStream_t stream, const uint8_t* ray_live = nullptr);
 hipError_t launch_occ_depth(const float* raw, const float* t_vals, const float* dirs, int64_t n, int S, int s0, int s1, const ActParams& ap,
                             float tau_stop, char* state, hipStream_t stream);
+
+
+// ---- aon_bounds.hip: per-ray near / far from a ray-box intersection ----
+int64_t ray_limits_workspace_bytes(int64_t n);
+hipError_t launch_ray_limits(const float* rays_o, const float* rays_d, int64_t n, const float* lo3, const float* hi3, float* near, float* far,
+                             uint8_t* live, char* ws, hipStream_t stream);
 
 }  // namespace aon

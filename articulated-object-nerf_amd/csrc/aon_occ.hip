@@ -1,7 +1,8 @@
 // Occupancy-grid accelerated inference (aon_occupancy_build, aon_render_fwd_occ / aon_art_render_fwd_occ): a bitfield of the cells of a
 // density grid that may hold matter, and per render level the list of samples that fall into occupied cells.  The MLP then runs only on
 // that list (the GATHER instances of mlp_fwd_kernel / art_mlp_fwd_kernel); every other sample gets the sentinel record below.  No atomics:
-// the same bits on every run.
+// the same bits on every run.  An optional ray mask: the samples of a ray whose `ray_live` byte is 0 are EMPTY
+// whatever the grid says; the grid itself may be null (every cell occupied: the mask alone decides).
 //
 // Convention (tests/_occ_ref.py is an independent numpy copy):
 //   * the grid is built from a density grid of (nx, ny, nz) points x_a = lo_a + idx_a step_a (ops.grid_points); it has (nx-1, ny-1, nz-1)
@@ -77,6 +78,7 @@ __device__ __forceinline__ bool occ_lookup(const OccGrid& G, const float (&x)[3]
 struct OccSamples {
   const float* rays_o; const float* rays_d; const float* t_vals;   // (n,3), (n,3), (n,S)
   int64_t total; int S;                                             // n * S <= INT32_MAX (the caller's chunking)
+  const uint8_t* ray_live;                                          // (n,) or null: a dead ray's samples are EMPTY
 };
 
 __device__ __forceinline__ int occ_tile_flags(const OccGrid& G, const OccSamples& s, int64_t g0, bool (&occ)[4]) {
@@ -87,11 +89,16 @@ __device__ __forceinline__ int occ_tile_flags(const OccGrid& G, const OccSamples
     occ[r] = false;
     if (g >= s.total) continue;
     const int64_t ray = g / s.S;
-    const float t = s.t_vals[g];
-    float x[3];
+    if (s.ray_live && !s.ray_live[ray]) continue;   // dead ray
+    if (G.bits) {
+      const float t = s.t_vals[g];
+      float x[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) x[a] = __fadd_rn(s.rays_o[ray * 3 + a], __fmul_rn(t, s.rays_d[ray * 3 + a]));   // helper.cast_rays
-    occ[r] = occ_lookup(G, x);
+      for (int a = 0; a < 3; ++a) x[a] = __fadd_rn(s.rays_o[ray * 3 + a], __fmul_rn(t, s.rays_d[ray * 3 + a]));   // helper.cast_rays
+      occ[r] = occ_lookup(G, x);
+    } else {
+      occ[r] = true;   // a null grid: every cell occupied
+    }
     n += occ[r] ? 1 : 0;
   }
   return n;
@@ -163,8 +170,9 @@ int64_t occ_list_bytes(int64_t total) {   // per chunk and level: sample list, t
 
 // raw: (total, 4) records; ws: occ_list_bytes(total) bytes, 256-byte aligned -> idx (total int32) and the counter (int64) for the gather launch
 hipError_t launch_occ_compact(const OccGrid& G, const float* rays_o, const float* rays_d, const float* t_vals, int64_t n, int S, float* raw,
-                              char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out, hipStream_t stream) {
-  const OccSamples s{rays_o, rays_d, t_vals, n * S, S};
+                              char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out, hipStream_t stream,
+                              const uint8_t* ray_live) {
+  const OccSamples s{rays_o, rays_d, t_vals, n * S, S, ray_live};
   const int64_t tiles = (s.total + kOccTile - 1) / kOccTile;
   int* idx = reinterpret_cast<int*>(ws);
   int* counts = reinterpret_cast<int*>(ws + (s.total * 4 + 255) / 256 * 256);
@@ -207,6 +215,7 @@ __device__ __forceinline__ int occ_round_flags(const OccGrid& G, const OccSample
     const int64_t g = ray * s.S + i;
     gi[r] = g;
     if (rd.stop[ray] <= i) continue;   // dead: behind the ray's stop
+    if (s.ray_live && !s.ray_live[ray]) continue;   // dead ray
     if (G.bits) {
       const float t = s.t_vals[g];
       float x[3];
@@ -327,8 +336,8 @@ hipError_t launch_occ_stop_store(const char* state, int value, int* dst, int64_t
 // launch_occ_compact over the sub-range [s0, s1) of every ray, minus the dead samples.  G.bits == nullptr: no grid.
 hipError_t launch_occ_compact_round(const OccGrid& G, const float* rays_o, const float* rays_d, const float* t_vals, int64_t n, int S, int s0, int s1,
                                     const char* state, float* raw, char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out,
-                                    hipStream_t stream) {
-  const OccSamples s{rays_o, rays_d, t_vals, n * S, S};
+                                    hipStream_t stream, const uint8_t* ray_live) {
+  const OccSamples s{rays_o, rays_d, t_vals, n * S, S, ray_live};
   const OccRound rd{reinterpret_cast<const int*>(state + (n * 4 + 255) / 256 * 256), s0, s1, n * (s1 - s0)};
   const int64_t tiles = (rd.count + kOccTile - 1) / kOccTile;
   const int64_t full_tiles = (s.total + kOccTile - 1) / kOccTile;   // the buffers keep launch_occ_compact's layout

@@ -220,13 +220,96 @@ __global__ void sample_t4_kernel(int64_t total, int S, TRange tr, const float* _
   }
 }
 
+// Per-ray planes: near[ray] / far[ray] as helper.sample_along_rays sees (N, 1) tensors, the same rounded
+// operations per element; under lindisp `1.0 / tensor` is an fp32 IEEE reciprocal of the element (the scalar path above takes the
+// caller's double-precision values instead).
+__device__ __forceinline__ TRange ray_range(const float* __restrict__ near_ray, const float* __restrict__ far_ray, int64_t ray, int lindisp) {
+  TRange r;
+  r.near = near_ray[ray]; r.far = far_ray[ray];
+  r.inv_near = lindisp ? __fdiv_rn(1.0f, r.near) : 0.f;
+  r.inv_far = lindisp ? __fdiv_rn(1.0f, r.far) : 0.f;
+  r.lindisp = lindisp;
+  return r;
+}
+
+__global__ void sample_along_rays_bounds_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d, int64_t n_rays, int S,
+                                                const float* __restrict__ near_ray, const float* __restrict__ far_ray, int lindisp,
+                                                const float* __restrict__ t_rand, float* __restrict__ t_vals, float* __restrict__ coords) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_rays * S) return;
+  const int64_t ray = g / S;
+  const int s = (int)(g - ray * S);
+  const TRange tr = ray_range(near_ray, far_ray, ray, lindisp);
+  float t = coarse_t(s, S, tr);
+  if (t_rand) {
+    const float lo = s == 0 ? t : __fmul_rn(0.5f, __fadd_rn(t, coarse_t(s - 1, S, tr)));
+    const float hi = s == S - 1 ? t : __fmul_rn(0.5f, __fadd_rn(coarse_t(s + 1, S, tr), t));
+    t = __fadd_rn(lo, __fmul_rn(__fsub_rn(hi, lo), t_rand[g]));
+  }
+  t_vals[g] = t;
+  if (coords) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) coords[g * 3 + a] = __fadd_rn(rays_o[ray * 3 + a], __fmul_rn(t, rays_d[ray * 3 + a]));
+  }
+}
+
+// sample_t4_kernel with per-ray planes: a thread's four elements may straddle two rays (S >= 2: never three)
+__global__ void sample_t4_bounds_kernel(int64_t total, int S, const float* __restrict__ near_ray, const float* __restrict__ far_ray, int lindisp,
+                                        const float* __restrict__ t_rand, float* __restrict__ t_vals) {
+  const int64_t g0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (g0 >= total) return;
+  int64_t ray = g0 / S;
+  int s = (int)(g0 - ray * S);
+  float r[4] = {0.f, 0.f, 0.f, 0.f};
+  const bool full = g0 + 4 <= total;
+  if (t_rand) {
+    if (full) {
+      const float4 q = *reinterpret_cast<const float4*>(t_rand + g0);
+      r[0] = q.x; r[1] = q.y; r[2] = q.z; r[3] = q.w;
+    } else {
+      for (int e = 0; e < 4; ++e) if (g0 + e < total) r[e] = t_rand[g0 + e];
+    }
+  }
+  TRange tr = ray_range(near_ray, far_ray, ray, lindisp);
+  float v[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float t = coarse_t(s, S, tr);
+    if (t_rand) {
+      const float lo = s == 0 ? t : __fmul_rn(0.5f, __fadd_rn(t, coarse_t(s - 1, S, tr)));
+      const float hi = s == S - 1 ? t : __fmul_rn(0.5f, __fadd_rn(coarse_t(s + 1, S, tr), t));
+      t = __fadd_rn(lo, __fmul_rn(__fsub_rn(hi, lo), r[e]));
+    }
+    v[e] = t;
+    if (++s == S && g0 + e + 1 < total) {   // the next element opens the next ray (which exists: it is below `total`)
+      s = 0;
+      tr = ray_range(near_ray, far_ray, ++ray, lindisp);
+    }
+  }
+  if (full) {
+    *reinterpret_cast<float4*>(t_vals + g0) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    for (int e = 0; e < 4; ++e) if (g0 + e < total) t_vals[g0 + e] = v[e];
+  }
+}
+
 hipError_t launch_sample_along_rays(const float* rays_o, const float* rays_d, int64_t n_rays, int S, float near,
                                     float far, const float* t_rand, float* t_vals, float* coords, hipStream_t stream,
-                                    int lindisp, float inv_near, float inv_far) {
+                                    int lindisp, float inv_near, float inv_far, const float* near_ray, const float* far_ray) {
   const int64_t n = n_rays * S;
   if (n <= 0) return hipSuccess;
   const TRange tr{near, far, inv_near, inv_far, lindisp};
   const bool aligned = (reinterpret_cast<uintptr_t>(t_vals) & 15) == 0 && (reinterpret_cast<uintptr_t>(t_rand) & 15) == 0;
+  if (near_ray) {   // per-ray planes: the scalars are ignored
+    if (!coords && aligned) {
+      const int64_t threads = (n + 3) / 4;
+      sample_t4_bounds_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream>>>(n, S, near_ray, far_ray, lindisp, t_rand, t_vals);
+      return hipGetLastError();
+    }
+    sample_along_rays_bounds_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(rays_o, rays_d, n_rays, S, near_ray, far_ray, lindisp,
+                                                                                                t_rand, t_vals, coords);
+    return hipGetLastError();
+  }
   if (!coords && aligned) {
     const int64_t threads = (n + 3) / 4;
     sample_t4_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream>>>(n, S, tr, t_rand, t_vals);

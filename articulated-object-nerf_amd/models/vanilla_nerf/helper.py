@@ -76,8 +76,26 @@ def cast_rays(t_vals, origins, directions):
     return ops.cast_rays(t_vals, origins, directions)
 
 
+def get_ray_limits_box(rays_o, rays_d, box_side_length):
+    """helper.py:42-102 -> (near, far), each (..., 1): the distances at which a ray enters / leaves the cube of side ``box_side_length``
+    centred on the origin; (-1, -2) for a ray that misses it.  ``box_side_length`` may also be a (lo, hi) pair (an extension)."""
+    near, far = ops.ray_limits_box(rays_o, rays_d, box_side_length)
+    shape = tuple(rays_o.shape[:-1]) + (1,)
+    return near.reshape(shape), far.reshape(shape)
+
+
+def get_ray_limits(rays_o, rays_d, box_side_length=2):
+    """helper.py:29-39 -> (near, far), each (..., 1): get_ray_limits_box with the rays that miss the box given the smallest near / largest
+    far of those that hit it, negatives clamped to 0 -- without the reference's host round trip.  The ``ray_live`` mask of the same call
+    (which rays have anything to render): ``ops.ray_limits``."""
+    near, far, _ = ops.ray_limits(rays_o, rays_d, box_side_length)
+    shape = tuple(rays_o.shape[:-1]) + (1,)
+    return near.reshape(shape), far.reshape(shape)
+
+
 def sample_along_rays(rays_o, rays_d, num_samples, near, far, randomized, lindisp, t_rand=None):
-    """helper.py:106-133 -> (t_vals (N,num_samples+1), coords (N,num_samples+1,3))"""
+    """helper.py:106-133 -> (t_vals (N,num_samples+1), coords (N,num_samples+1,3)).  ``near`` / ``far``: numbers, or the (N, 1) tensors of
+    get_ray_limits (the reference takes them by broadcasting)."""
     if randomized and t_rand is None:
         t_rand = torch.rand((rays_o.shape[0], num_samples + 1), device=rays_o.device)
     return ops.sample_along_rays(rays_o, rays_d, num_samples, near, far, t_rand if randomized else None, lindisp=bool(lindisp))

@@ -277,15 +277,20 @@ class NeRF(nn.Module):
             ret.append((comp, acc, depth))
         return ret
 
-    def forward(self, rays, randomized, white_bkgd, near, far, t_rand=None, u=None, noise=None, occupancy=None, early_stop=None):
+    def forward(self, rays, randomized, white_bkgd, near, far, t_rand=None, u=None, noise=None, occupancy=None, early_stop=None, ray_live=None):
         """``occupancy`` (ops.OccupancyGrid, occupancy.build_occupancy): inference that skips every sample in an empty cell of the grid
         (DESIGN.md section 4.9); refused with randomized sampling or grad mode.  None: the exact path.
         ``early_stop`` (eps in [0, 1), with or without a grid): a ray stops once its transmittance has fallen to eps (DESIGN.md section
-        4.10); the same refusals.  None: no termination."""
+        4.10); the same refusals.  None: no termination.
+        ``near`` / ``far``: numbers, or the (N, 1) tensors of helper.get_ray_limits, as the reference's forward takes them (DESIGN.md section
+        4.11).  ``ray_live`` ((N,) uint8, ops.ray_limits): inference only; a dead ray runs no MLP and returns the background."""
         rays_o = rays["rays_o"]
         n = rays_o.shape[0]
+        per_ray = isinstance(near, torch.Tensor) or isinstance(far, torch.Tensor)
+        if ray_live is not None and (randomized or torch.is_grad_enabled() or self.num_levels > 2):
+            raise ValueError("ray_live is inference only: randomized=False, under torch.no_grad(), one or two levels")
         if occupancy is not None or early_stop is not None:
-            return self._forward_occupancy(rays, randomized, white_bkgd, near, far, u, occupancy, early_stop)
+            return self._forward_occupancy(rays, randomized, white_bkgd, near, far, u, occupancy, early_stop, ray_live)
         # the stratified / inverse-CDF draws may ride in the batch dict (keys "aon_t_rand", "aon_u": an extension, namespaced so that a user batch carrying its own "u" / "t_rand" is never misread -- the reference's forward
         # ignores extra keys, model.py:299-306 -- that makes a harness run reproducible: tests/test_hip_long_training.py)
         if t_rand is None:
@@ -307,6 +312,9 @@ class NeRF(nn.Module):
             return self._forward_many_levels(rays, randomized, white_bkgd, near, far, t_rand, u, noise, training=training)
         layerwise = self._general or not self._fused_inference or (training and not self._fused_training and not self.coarse_mlp.geometry.is_default)
         if layerwise:
+            if per_ray or ray_live is not None:
+                raise ValueError("per-ray near / far tensors and ray_live are served by the fused kernels only: this network's geometry runs on the "
+                                 "layer-wise engine, which takes scalar near / far")
             geom = self.coarse_mlp.geometry
             mlps = [self.coarse_mlp, self.fine_mlp][: self.num_levels]
             if training:
@@ -342,7 +350,7 @@ class NeRF(nn.Module):
                 torch.cuda.current_stream(rays_o.device).wait_event(bwd_ready)
             params = [p for m in mlps for p in m.ordered_params()]
             try:
-                flat = RenderVanilla.apply(rays_o, rays["rays_d"], rays["viewdirs"], float(near), float(far), bool(white_bkgd),
+                flat = RenderVanilla.apply(rays_o, rays["rays_d"], rays["viewdirs"], *[x.detach() if isinstance(x, torch.Tensor) else float(x) for x in (near, far)], bool(white_bkgd),
                                            self.num_levels, t_rand, u, packs, self._opts, noise, *params)
             finally:
                 if bwd_ready is not None:   # (behind the forward's launches: free by then; also when the forward raised)
@@ -351,10 +359,10 @@ class NeRF(nn.Module):
         coarse = self.coarse_mlp.packed()
         fine = self.fine_mlp.packed() if self.num_levels == 2 else None
         outs = ops.render_fwd(coarse, fine, rays_o, rays["rays_d"], rays["viewdirs"], near, far,
-                              white_bkgd, self.num_levels, t_rand, u, opts=self._opts, noise=noise)
+                              white_bkgd, self.num_levels, t_rand, u, opts=self._opts, noise=noise, ray_live=ray_live)
         return [tuple(o) for o in outs]
 
-    def _forward_occupancy(self, rays, randomized, white_bkgd, near, far, u, occupancy, early_stop=None):
+    def _forward_occupancy(self, rays, randomized, white_bkgd, near, far, u, occupancy, early_stop=None, ray_live=None):
         if randomized:
             raise ValueError("occupancy rendering is inference only: randomized=True is refused")
         if torch.is_grad_enabled():
@@ -366,10 +374,11 @@ class NeRF(nn.Module):
         if early_stop is not None:
             outs, _, _ = ops.render_fwd_stop(self.coarse_mlp.packed(), self.fine_mlp.packed() if self.num_levels == 2 else None, rays["rays_o"],
                                              rays["rays_d"], rays["viewdirs"], near, far, white_bkgd, occupancy, early_stop,
-                                             num_levels=self.num_levels, u=u, opts=self._opts)
+                                             num_levels=self.num_levels, u=u, opts=self._opts, ray_live=ray_live)
             return [tuple(o) for o in outs]
         outs, _ = ops.render_fwd_occ(self.coarse_mlp.packed(), self.fine_mlp.packed() if self.num_levels == 2 else None, rays["rays_o"],
-                                     rays["rays_d"], rays["viewdirs"], near, far, white_bkgd, occupancy, self.num_levels, u, opts=self._opts)
+                                     rays["rays_d"], rays["viewdirs"], near, far, white_bkgd, occupancy, self.num_levels, u, opts=self._opts,
+                                     ray_live=ray_live)
         return [tuple(o) for o in outs]
 
     def _level_mlp(self, level: str):
@@ -414,6 +423,12 @@ from . import helper
 from ..interface import Harness
 
 
+def _ray_box_limits(ray_box, batch):
+    """LitNeRF / LitNeRF_AutoDecoder(ray_box=...): (near, far, live) of ALL rays of `batch` -- the reference's min / max fallback for the
+    rays that miss the box is a property of the ray set, so an image's limits are computed once, before its chunk loop."""
+    return ops.ray_limits(batch["rays_o"], batch["rays_d"], ray_box)
+
+
 def _fused_adam(params) -> bool:
     """torch.optim.Adam's fused form when every parameter lives on a GPU (AON_FUSED_ADAM=0 in the environment: the foreach form, A/B)."""
     import os
@@ -447,17 +462,23 @@ class LitNeRF(Harness):
 
     def __init__(self, hparams=None, lr_init: float = 5.0e-4, lr_final: float = 5.0e-6, lr_delay_steps: int = 2500,
                  lr_delay_mult: float = 0.01, randomized: bool = True, near: float = 2.0, far: float = 6.0, white_bkgd: bool = True,
-                 model_kwargs: dict | None = None):
+                 model_kwargs: dict | None = None, ray_box=None):
         super().__init__()
         self._init_harness(hparams, dict(chunk=3840, run_max_steps=100000, img_wh=(640, 480)))  # opt.py:103,112,17
         self.lr_init, self.lr_final, self.lr_delay_steps, self.lr_delay_mult = lr_init, lr_final, lr_delay_steps, lr_delay_mult
         self.randomized, self.near, self.far, self.white_bkgd = randomized, near, far, white_bkgd
+        # ray_box (a side length, or (lo, hi)): per-ray near / far from the rays' intersection with that box (helper.get_ray_limits, the
+        # reference's near_obj / far_obj) instead of the scalars; None: the scalars, as before
+        self.ray_box = ray_box
         # the reference builds NeRF() (model.py:218); `model_kwargs` hands its constructor arguments through (sample counts, degrees, ...)
         self.model = NeRF(**(model_kwargs or {}))
 
     def training_step(self, batch, batch_idx):
         batch = {k: (v if k == "obj_idx" else v.squeeze(0)) for k, v in batch.items()}
-        rendered = self.model(batch, self.randomized, self.white_bkgd, self.near, self.far)
+        near, far = self.near, self.far
+        if self.ray_box is not None:
+            near, far, _ = _ray_box_limits(self.ray_box, batch)
+        rendered = self.model(batch, self.randomized, self.white_bkgd, near, far)
         # model.py:271-279: loss0 + loss1 and the three logged values -- one launch forward, one backward (helper.train_loss)
         loss, stats = helper.train_loss(rendered, batch["target"])
         self.log("train/psnr1", stats[5])
@@ -469,9 +490,14 @@ class LitNeRF(Harness):
     def render_rays(self, batch, batch_idx):
         B = batch["rays_o"].shape[0]
         ret = defaultdict(list)
+        limits = _ray_box_limits(self.ray_box, batch) if self.ray_box is not None else None
         for i in range(0, B, self.hparams.chunk):
             chunk = {k: (v if k == "obj_idx" else v[i: i + self.hparams.chunk]) for k, v in batch.items()}
-            out = self.model(chunk, False, self.white_bkgd, self.near, self.far)
+            if limits is not None:
+                near, far, live = (x[i: i + self.hparams.chunk] for x in limits)
+                out = self.model(chunk, False, self.white_bkgd, near, far, ray_live=live)
+            else:
+                out = self.model(chunk, False, self.white_bkgd, self.near, self.far)
             ret["comp_rgb"] += [out[1][0]]
             ret["acc"] += [out[1][1]]
             ret["depth"] += [out[1][2]]
@@ -483,9 +509,14 @@ class LitNeRF(Harness):
     def render_rays_test(self, batch, batch_idx):
         B = batch["rays_o"].shape[0]
         rgb = []
+        limits = _ray_box_limits(self.ray_box, batch) if self.ray_box is not None else None
         for i in range(0, B, self.hparams.chunk):
             chunk = {k: v[i: i + self.hparams.chunk] for k, v in batch.items()}
-            rgb.append(self.model(chunk, False, self.white_bkgd, self.near, self.far)[1][0])
+            if limits is not None:
+                near, far, live = (x[i: i + self.hparams.chunk] for x in limits)
+                rgb.append(self.model(chunk, False, self.white_bkgd, near, far, ray_live=live)[1][0])
+            else:
+                rgb.append(self.model(chunk, False, self.white_bkgd, self.near, self.far)[1][0])
         return {"target": batch["target"], "instance_mask": batch["instance_mask"], "rgb": torch.cat(rgb, 0)}
 
     def validation_step(self, batch, batch_idx):

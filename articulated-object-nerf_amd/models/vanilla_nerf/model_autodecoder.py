@@ -138,13 +138,17 @@ class NeRF_AE_Art(nn.Module):
         self.fine_mlp = NeRFMLP(min_deg_point, max_deg_point, deg_view)
 
     def forward(self, rays, randomized, white_bkgd, near, far, latents, train=True, t_rand=None, u=None, noise=None, occupancy=None,
-                early_stop=None):
+                early_stop=None, ray_live=None):
         """``occupancy`` (ops.OccupancyGrid built under the same latents, occupancy.build_occupancy): inference that skips every sample in an
         empty cell of the grid; refused with randomized sampling or grad mode.  None: the exact path.
         ``early_stop`` (eps in [0, 1), with or without a grid): a ray stops once its transmittance has fallen to eps (DESIGN.md section
-        4.10); the same refusals.  None: no termination."""
+        4.10); the same refusals.  None: no termination.
+        ``near`` / ``far``: numbers, or the (N, 1) tensors of helper.get_ray_limits, as the reference's forward takes them (DESIGN.md section
+        4.11).  ``ray_live`` ((N,) uint8, ops.ray_limits): inference only; a dead ray runs no MLP and returns the background."""
         rays_o = rays["rays_o"]
         n = rays_o.shape[0]
+        if ray_live is not None and (randomized or torch.is_grad_enabled()):
+            raise ValueError("ray_live is inference only: randomized=False, under torch.no_grad()")
         if occupancy is not None or early_stop is not None:
             if randomized:
                 raise ValueError("occupancy rendering is inference only: randomized=True is refused")
@@ -156,11 +160,12 @@ class NeRF_AE_Art(nn.Module):
             if early_stop is not None:
                 outs, _, _ = ops.art_render_fwd_stop(self.coarse_mlp.packed(), self.coarse_mlp.prepared(latents), self.fine_mlp.packed() if two else None,
                                                      self.fine_mlp.prepared(latents) if two else None, rays_o, rays["rays_d"], rays["viewdirs"], near,
-                                                     far, white_bkgd, occupancy, early_stop, num_levels=self.num_levels, u=u, opts=self._opts)
+                                                     far, white_bkgd, occupancy, early_stop, num_levels=self.num_levels, u=u, opts=self._opts,
+                                                     ray_live=ray_live)
                 return [tuple(o) for o in outs]
             outs, _ = ops.art_render_fwd_occ(self.coarse_mlp.packed(), self.coarse_mlp.prepared(latents), self.fine_mlp.packed() if two else None,
                                              self.fine_mlp.prepared(latents) if two else None, rays_o, rays["rays_d"], rays["viewdirs"], near, far,
-                                             white_bkgd, occupancy, self.num_levels, u, opts=self._opts)
+                                             white_bkgd, occupancy, self.num_levels, u, opts=self._opts, ray_live=ray_live)
             return [tuple(o) for o in outs]
         # the stratified / inverse-CDF draws may ride in the batch dict (keys "aon_t_rand", "aon_u": an extension, namespaced so that a user batch carrying its own "u" / "t_rand" is never misread -- the reference's forward
         # ignores extra keys, model.py:299-306 -- that makes a harness run reproducible: tests/test_hip_long_training.py)
@@ -210,7 +215,7 @@ class NeRF_AE_Art(nn.Module):
                 torch.cuda.current_stream(rays_o.device).wait_event(bwd_ready)
             params = [p for mlp in mlps for p in mlp.ordered_params()]
             try:
-                flat = RenderArticulated.apply(rays_o, rays["rays_d"], rays["viewdirs"], float(near), float(far), bool(white_bkgd),
+                flat = RenderArticulated.apply(rays_o, rays["rays_d"], rays["viewdirs"], *[x.detach() if isinstance(x, torch.Tensor) else float(x) for x in (near, far)], bool(white_bkgd),
                                                self.num_levels, t_rand, u, packs, self._opts, noise, latents["density"], latents["color"],
                                                latents["articulation"], *params)
             finally:
@@ -222,7 +227,7 @@ class NeRF_AE_Art(nn.Module):
         pf = self.fine_mlp.packed() if two else None
         outs = ops.art_render_fwd(pc, self.coarse_mlp.prepared(latents), pf, self.fine_mlp.prepared(latents) if two else None,
                                   rays_o, rays["rays_d"], rays["viewdirs"], near, far, white_bkgd, self.num_levels, t_rand, u,
-                                  opts=self._opts, noise=noise)
+                                  opts=self._opts, noise=noise, ray_live=ray_live)
         return [tuple(o) for o in outs]
 
     def _level_mlp(self, level: str):
@@ -250,7 +255,7 @@ from collections import defaultdict  # noqa: E402
 from . import helper  # noqa: E402
 from ..code_library import CodeLibraryArticulated  # noqa: E402
 from ..interface import Harness  # noqa: E402
-from .model import build_adam, pack_aside_mode, packed_bwd_aside, run_aside  # noqa: E402
+from .model import _ray_box_limits, build_adam, pack_aside_mode, packed_bwd_aside, run_aside  # noqa: E402
 
 _SCALAR_KEYS = ("deg", "instance_id", "articulation_id")
 
@@ -266,11 +271,12 @@ class LitNeRF_AutoDecoder(Harness):
 
     def __init__(self, hparams=None, lr_init: float = 5.0e-4, lr_final: float = 5.0e-6, lr_delay_steps: int = 2500,
                  lr_delay_mult: float = 0.01, randomized: bool = True, near: float = 2.0, far: float = 6.0, white_bkgd: bool = True,
-                 model_kwargs: dict | None = None):
+                 model_kwargs: dict | None = None, ray_box=None):
         super().__init__()
         self._init_harness(hparams, dict(chunk=3840, run_max_steps=100000, img_wh=(320, 240), N_max_objs=1, N_obj_code_length=128))
         self.lr_init, self.lr_final, self.lr_delay_steps, self.lr_delay_mult = lr_init, lr_final, lr_delay_steps, lr_delay_mult
         self.randomized, self.near, self.far, self.white_bkgd = randomized, near, far, white_bkgd
+        self.ray_box = ray_box   # per-ray near / far from this box (a side length, or (lo, hi)); None: the scalars (LitNeRF)
         self.model = NeRF_AE_Art(**(model_kwargs or {}))   # the reference builds NeRF_AE_Art() (model_autodecoder.py:352)
         self.code_library = CodeLibraryArticulated(self.hparams)
 
@@ -284,7 +290,10 @@ class LitNeRF_AutoDecoder(Harness):
     def training_step(self, batch, batch_idx):
         batch = self._unbatch(batch)
         latents = self.code_library(batch)
-        rendered = self.model(batch, self.randomized, self.white_bkgd, self.near, self.far, latents)
+        near, far = self.near, self.far
+        if self.ray_box is not None:
+            near, far, _ = _ray_box_limits(self.ray_box, batch)
+        rendered = self.model(batch, self.randomized, self.white_bkgd, near, far, latents)
         # model_autodecoder.py:455-477: loss1 + loss0 + 1e-4 * (mean ||shape|| + mean ||appearance|| + mean ||articulation||) and the four
         # logged values -- one launch forward, one backward (helper.train_loss) where torch runs ~47
         loss, stats = helper.train_loss(rendered, batch["target"], (latents["density"], latents["color"], latents["articulation"]), 1e-4)
@@ -297,9 +306,14 @@ class LitNeRF_AutoDecoder(Harness):
     def _render_chunks(self, batch, latents, skip=()):
         B = batch["rays_o"].shape[0]
         ret = defaultdict(list)
+        limits = _ray_box_limits(self.ray_box, batch) if self.ray_box is not None else None   # of the whole image, before the chunk loop
         for i in range(0, B, self.hparams.chunk):
             chunk = {k: v[i: i + self.hparams.chunk] for k, v in batch.items() if k not in skip and k not in _SCALAR_KEYS}
-            out = self.model(chunk, False, self.white_bkgd, self.near, self.far, latents)
+            if limits is not None:
+                near, far, live = (x[i: i + self.hparams.chunk] for x in limits)
+                out = self.model(chunk, False, self.white_bkgd, near, far, latents, ray_live=live)
+            else:
+                out = self.model(chunk, False, self.white_bkgd, self.near, self.far, latents)
             ret["comp_rgb"] += [out[1][0]]
             ret["acc"] += [out[1][1]]
             ret["depth"] += [out[1][2]]

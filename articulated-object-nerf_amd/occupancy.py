@@ -43,14 +43,23 @@ def build_occupancy(model, bounds, resolution=128, threshold: float = 0.01, dila
 
 @torch.no_grad()
 def render_image(model, c2w, H: int, W: int, focal: float, near: float, far: float, grid: ops.OccupancyGrid | None, latents: dict | None = None,
-                 chunk: int = ops.MAX_CHUNK_RAYS, white_bkgd: bool = True, early_stop: float | None = None, round_samples: int | None = None) -> dict:
+                 chunk: int = ops.MAX_CHUNK_RAYS, white_bkgd: bool = True, early_stop: float | None = None, round_samples: int | None = None,
+                 ray_bounds: bool = False, box=None) -> dict:
     """One H x W view through the occupancy path (deterministic sampling, both levels of the model) -> {"rgb": (H, W, 3), "acc": (H, W),
     "depth": (H, W) of the last level, "occupied": [samples run through the MLP per level] (python ints), "samples": [n * S per level]}.
     ``early_stop`` (eps in [0, 1)): rays stop once their transmittance has fallen to eps, in rounds of
     ``round_samples`` samples (None: ops.DEFAULT_ROUND_SAMPLES); the dict gains "stop", the (H, W) int32 map of the last level's stop
-    index (S: the ray ran to its end) -- a heat map of the frame's cost.  `grid` may then be None."""
-    if grid is None and early_stop is None:
-        raise ValueError("render_image: needs a grid, early_stop, or both")
+    index (S: the ray ran to its end) -- a heat map of the frame's cost.  `grid` may then be None.
+    ``ray_bounds``: per-ray near / far from the rays' intersection with the grid's box (lo, lo + cells * step) -- or
+    with ``box`` (a side length, or (lo, hi)) when there is no grid -- computed once over the whole image, and the rays that miss it skipped
+    (``ray_live``); the scalar `near` / `far` are then ignored.  The dict gains "live", the number of live rays."""
+    if ray_bounds:
+        if box is None:
+            if grid is None:
+                raise ValueError("render_image: ray_bounds without a grid needs box=")
+            box = (grid.lo.tolist(), (grid.lo + torch.tensor(grid.cells, dtype=torch.float32) * grid.step).tolist())   # multiply, then add: the last grid point
+    elif grid is None and early_stop is None:
+        raise ValueError("render_image: needs a grid, early_stop, ray_bounds, or a combination")
     dev = grid.device if grid is not None else next(model.parameters()).device
     rays_o, viewdirs = ops.raygen(c2w, H, W, focal, device=dev)
     n = H * W
@@ -68,10 +77,21 @@ def render_image(model, c2w, H: int, W: int, focal: float, near: float, far: flo
         sc = model.coarse_mlp.prepared(latents)
         sf = model.fine_mlp.prepared(latents) if L == 2 else None
     stop = torch.empty((n,), dtype=torch.int32, device=dev) if early_stop is not None else None
+    limits = ops.ray_limits(rays_o, viewdirs, box) if ray_bounds else None
     for b in range(0, n, chunk):
         e = min(n, b + chunk)
         o, v = rays_o[b:e], viewdirs[b:e]
-        if early_stop is not None:
+        if limits is not None:
+            pn, pfar, live = (x[b:e] for x in limits)
+            if art:
+                outs, occ, st = ops.art_render_fwd_stop(pc, sc, pf, sf, o, v, v, pn, pfar, white_bkgd, grid, early_stop or 0.0, round_samples, L,
+                                                        opts=model._opts, ray_live=live)
+            else:
+                outs, occ, st = ops.render_fwd_stop(pc, pf, o, v, v, pn, pfar, white_bkgd, grid, early_stop or 0.0, round_samples, L,
+                                                    opts=model._opts, ray_live=live)
+            if stop is not None:
+                stop[b:e] = st[:, L - 1]
+        elif early_stop is not None:
             if art:
                 outs, occ, st = ops.art_render_fwd_stop(pc, sc, pf, sf, o, v, v, near, far, white_bkgd, grid, early_stop, round_samples, L,
                                                         opts=model._opts)
@@ -89,4 +109,6 @@ def render_image(model, c2w, H: int, W: int, focal: float, near: float, far: flo
            "samples": [n * S[lvl] for lvl in range(L)]}
     if stop is not None:
         out["stop"] = stop.view(H, W)
+    if limits is not None:
+        out["live"] = int(limits[2].sum())
     return out

@@ -219,16 +219,91 @@ def cast_rays(t_vals, origins, directions):
     return coords
 
 
-def sample_along_rays(rays_o, rays_d, num_samples: int, near: float, far: float, t_rand=None, want_coords=True, lindisp=False):
+# ------------------------------------------------------------------ per-ray near / far from a ray-box intersection
+_LIMITS_WS = StreamCache()
+
+
+def _box3(box):
+    """A side length (the reference's cube, +-side / 2: helper.py:53-63) or (lo, hi), each a number or 3 numbers -> two float[3]."""
+    if isinstance(box, (int, float)):
+        half = box / 2                       # Python double, rounded to fp32 once: torch.tensor([bb_min, bb_max], dtype=float32)
+        lo, hi = [-1 * half] * 3, [1 * half] * 3
+    else:
+        lo, hi = _vec3(box[0], "box lo"), _vec3(box[1], "box hi")
+    return (C.c_float * 3)(*lo), (C.c_float * 3)(*hi)
+
+
+def ray_limits_box(rays_o, rays_d, box):
+    """helper.get_ray_limits_box (helper.py:42-102) for `box` (a side length, or (lo, hi)) -> (near, far), each (N, 1): the entry / exit
+    distances, (-1, -2) for the rays the reference marks invalid; its NaNs (origin on a face the ray is parallel to) included."""
+    o, d = _f32(rays_o.detach(), "rays_o").reshape(-1, 3), _f32(rays_d.detach(), "rays_d").reshape(-1, 3)
+    n = o.shape[0]
+    lo, hi = _box3(box)
+    near, far = torch.empty((n, 1), dtype=torch.float32, device=o.device), torch.empty((n, 1), dtype=torch.float32, device=o.device)
+    with torch.cuda.device(o.device):
+        check(lib.aon_ray_limits_box(_ptr(o), _ptr(d), n, lo, hi, _ptr(near), _ptr(far), _stream()), "aon_ray_limits_box")
+    return near, far
+
+
+def ray_limits(rays_o, rays_d, box=2):
+    """helper.get_ray_limits (helper.py:29-39) without its host round trip -> (near, far, live): near / far (N, 1) with the invalid rays
+    patched by min(near) / max(far) of the valid ones and negatives clamped to 0; live (N,) uint8, 1 iff the ray was valid and far > near
+    after the clamp (`ray_live=` of the inference renders).  The min / max belong to the ray set: one call per image, not per chunk."""
+    o, d = _f32(rays_o.detach(), "rays_o").reshape(-1, 3), _f32(rays_d.detach(), "rays_d").reshape(-1, 3)
+    n, dev = o.shape[0], o.device
+    lo, hi = _box3(box)
+    near, far = torch.empty((n, 1), dtype=torch.float32, device=dev), torch.empty((n, 1), dtype=torch.float32, device=dev)
+    live = torch.empty((n,), dtype=torch.uint8, device=dev)
+    ws = _scratch(_LIMITS_WS, dev, int(lib.aon_ray_limits_workspace_bytes(n)))
+    with torch.cuda.device(dev):
+        check(lib.aon_ray_limits(_ptr(o), _ptr(d), n, lo, hi, _ptr(near), _ptr(far), _ptr(live), _ptr(ws), ws.numel(), _stream()), "aon_ray_limits")
+    return near, far, live
+
+
+def _ray_bounds(near, far, n: int, dev, ray_live=None):
+    """near / far of a whole-path call: two numbers -> (near, far, None, ()); a tensor of N elements ((N,) or (N, 1)) for either, or a
+    `ray_live` mask -> (placeholders, placeholders, aon_ray_bounds, tensors to keep alive).  The tensors are data: detached."""
+    per_ray = isinstance(near, torch.Tensor) or isinstance(far, torch.Tensor)
+    if not per_ray and ray_live is None:
+        return float(near), float(far), None, ()
+
+    def vec(x, name):
+        if not isinstance(x, torch.Tensor):
+            return torch.full((n,), float(x), dtype=torch.float32, device=dev)
+        t = _f32(x.detach(), name).reshape(-1)
+        if t.numel() == 1 and n != 1:
+            t = t.expand(n).contiguous()
+        if t.numel() != n or t.device != dev:
+            raise ValueError(f"{name}: a per-ray tensor must hold one value per ray ({n}) on {dev}, got shape {tuple(x.shape)} on {x.device}")
+        return t
+
+    nt, ft = vec(near, "near"), vec(far, "far")
+    lv = None
+    if ray_live is not None:
+        if not isinstance(ray_live, torch.Tensor) or not ray_live.is_cuda or ray_live.dtype not in (torch.uint8, torch.bool):
+            raise TypeError("ray_live: expected a uint8 / bool cuda tensor (ops.ray_limits)")
+        lv = ray_live.reshape(-1).to(torch.uint8).contiguous()
+        if lv.numel() != n or lv.device != dev:
+            raise ValueError(f"ray_live must hold one byte per ray ({n}) on {dev}")
+    st = _lib.RayBoundsC(nt.data_ptr(), ft.data_ptr(), None if lv is None else lv.data_ptr())
+    return 1.0, 1.0, st, (nt, ft, lv)
+
+
+def sample_along_rays(rays_o, rays_d, num_samples: int, near, far, t_rand=None, want_coords=True, lindisp=False):
+    """``near`` / ``far``: numbers, or tensors of N elements (helper.py:106-133 takes the (N, 1) tensors of get_ray_limits by broadcasting)."""
     o, d = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d")
     n, S = o.shape[0], num_samples + 1
+    near, far, bounds, keep = _ray_bounds(near, far, n, o.device)
     tr = None if t_rand is None else _f32(t_rand, "t_rand")
     if tr is not None and tuple(tr.shape) != (n, S):
         raise ValueError(f"t_rand must be ({n},{S}), got {tuple(tr.shape)}")
     t_vals = torch.empty((n, S), dtype=torch.float32, device=o.device)
     coords = torch.empty((n, S, 3), dtype=torch.float32, device=o.device) if want_coords else None
     with torch.cuda.device(o.device):
-        if lindisp:   # helper.py:117 evaluates 1.0 / near in Python double precision; ctypes rounds it to fp32 once, as torch does
+        if bounds is not None:
+            check(lib.aon_sample_along_rays_bounds(_ptr(o), _ptr(d), n, S, _ptr(keep[0]), _ptr(keep[1]), int(bool(lindisp)), _ptr(tr), _ptr(t_vals),
+                                                   _ptr(coords), _stream()), "aon_sample_along_rays_bounds")
+        elif lindisp:   # helper.py:117 evaluates 1.0 / near in Python double precision; ctypes rounds it to fp32 once, as torch does
             check(lib.aon_sample_along_rays_ex(_ptr(o), _ptr(d), n, S, float(near), float(far), 1, 1.0 / near, 1.0 / far, _ptr(tr),
                                                _ptr(t_vals), _ptr(coords), _stream()), "aon_sample_along_rays_ex")
         else:
@@ -554,9 +629,14 @@ def _check_noise(noise, n, op, num_levels):
 
 
 def render_fwd(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels=2, t_rand=None, u=None,
-               opts=None, noise=None):
+               opts=None, noise=None, ray_live=None, workspace_bytes=None):
     """NeRF.forward: returns [(rgb, acc, depth)_coarse, (rgb, acc, depth)_fine] (fine omitted if num_levels == 1).
-    ``opts`` (RenderOpts): non-default sample counts / lindisp / noise_std; ``noise``: per-level (n,S) uniform draws."""
+    ``opts`` (RenderOpts): non-default sample counts / lindisp / noise_std; ``noise``: per-level (n,S) uniform draws.
+    ``near`` / ``far``: numbers, or per-ray tensors of N elements; ``ray_live`` (N,) uint8: dead rays run no MLP and composite to the
+    background (inference only)."""
+    if isinstance(near, torch.Tensor) or isinstance(far, torch.Tensor) or ray_live is not None:
+        return _stop_call("aon_render_fwd_stop", (_pk(packed_coarse), _pk(packed_fine)), rays_o, rays_d, viewdirs, near, far, white_bkgd, None, 0.0,
+                          None, num_levels, u, opts, workspace_bytes, t_rand=t_rand, noise=noise, ray_live=ray_live, want_stats=False)[0]
     o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
     n, dev = o.shape[0], o.device
     op = _opts(opts)
@@ -743,8 +823,12 @@ def art_mlp_fwd_pos(packed, small, pos, viewdirs_enc):
 
 
 def art_render_fwd(packed_c, small_c, packed_f, small_f, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels=2,
-                   t_rand=None, u=None, opts=None, noise=None):
-    """NeRF_AE_Art.forward: [(rgb, acc, depth)_coarse, (rgb, acc, depth)_fine]."""
+                   t_rand=None, u=None, opts=None, noise=None, ray_live=None, workspace_bytes=None):
+    """NeRF_AE_Art.forward: [(rgb, acc, depth)_coarse, (rgb, acc, depth)_fine].  Per-ray ``near`` / ``far`` / ``ray_live``: as render_fwd."""
+    if isinstance(near, torch.Tensor) or isinstance(far, torch.Tensor) or ray_live is not None:
+        return _stop_call("aon_art_render_fwd_stop", (_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f)), rays_o, rays_d, viewdirs, near, far,
+                          white_bkgd, None, 0.0, None, num_levels, u, opts, workspace_bytes, t_rand=t_rand, noise=noise, ray_live=ray_live,
+                          want_stats=False)[0]
     o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
     n, dev = o.shape[0], o.device
     op = _opts(opts)
@@ -1071,13 +1155,19 @@ def render_fwd_train(packed_c, packed_f, rays_o, rays_d, viewdirs, near, far, wh
         raise ValueError(f"t_rand must be ({n},{op.Sc})")
     uu, us = _u_args(u, n, dev, op.num_fine_samples) if num_levels == 2 else (None, 0)
     outs, fine = _level_outs(n, dev, num_levels)
+    near, far, bounds, bkeep = _ray_bounds(near, far, n, dev)     # per-ray near / far: non-differentiable data
     st, keep = op.c_struct(near, far, _check_noise(noise, n, op, num_levels))
     ws = train_workspace(dev, n, art, num_levels, st)
     common = (_ptr(o), _ptr(d), _ptr(v), n, float(near), float(far), int(bool(white_bkgd)), num_levels, _ptr(tr), _ptr(uu), us,
               _ptr(outs[0][0]), _ptr(outs[0][1]), _ptr(outs[0][2]), _ptr(fine[0]), _ptr(fine[1]), _ptr(fine[2]), _ptr(ws), ws.numel(), _stream(),
               C.byref(st))
     with torch.cuda.device(dev):
-        if art:
+        if bounds is not None and art:
+            check(lib.aon_art_render_fwd_train_bounds(_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f), *common, C.byref(bounds)),
+                  "aon_art_render_fwd_train_bounds")
+        elif bounds is not None:
+            check(lib.aon_render_fwd_train_bounds(_pk(packed_c), _pk(packed_f), *common, C.byref(bounds)), "aon_render_fwd_train_bounds")
+        elif art:
             check(lib.aon_art_render_fwd_train_ex(_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f), *common), "aon_art_render_fwd_train")
         else:
             check(lib.aon_render_fwd_train_ex(_pk(packed_c), _pk(packed_f), *common), "aon_render_fwd_train")
@@ -1657,9 +1747,12 @@ def _occ_workspace(device, n_rays: int, st, workspace_bytes):
     return _scratch(_OCC_WS_CACHE, device, need)
 
 
-def _occ_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, num_levels, u, opts, workspace_bytes):
+def _occ_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, num_levels, u, opts, workspace_bytes, ray_live=None):
     if not isinstance(grid, OccupancyGrid):
         raise TypeError(f"{name}: grid must be an ops.OccupancyGrid (ops.occupancy_grid), got {type(grid)}")
+    if isinstance(near, torch.Tensor) or isinstance(far, torch.Tensor) or ray_live is not None:
+        return _stop_call(name.replace("_occ", "_stop"), packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, 0.0, None, num_levels, u, opts,
+                          workspace_bytes, ray_live=ray_live)[:2]
     if num_levels not in (1, 2):
         raise ValueError(f"{name}: num_levels must be 1 or 2")
     o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
@@ -1684,18 +1777,19 @@ def _occ_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid
 
 
 def render_fwd_occ(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid: OccupancyGrid, num_levels=2, u=None,
-                   opts=None, workspace_bytes=None):
+                   opts=None, workspace_bytes=None, ray_live=None):
     """render_fwd (inference: no t_rand, no noise) with every sample in an empty cell of `grid` skipped: zero density, no MLP evaluation.
-    Returns (levels, occupied): the level tuples of render_fwd, and an int64 (2,) cuda tensor with the samples each level ran through the MLP."""
+    Returns (levels, occupied): the level tuples of render_fwd, and an int64 (2,) cuda tensor with the samples each level ran through the MLP.
+    Per-ray ``near`` / ``far`` / ``ray_live``: as render_fwd."""
     return _occ_call("aon_render_fwd_occ", (_pk(packed_coarse), _pk(packed_fine)), rays_o, rays_d, viewdirs, near, far, white_bkgd, grid,
-                     num_levels, u, opts, workspace_bytes)
+                     num_levels, u, opts, workspace_bytes, ray_live)
 
 
 def art_render_fwd_occ(packed_c, small_c, packed_f, small_f, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid: OccupancyGrid, num_levels=2,
-                       u=None, opts=None, workspace_bytes=None):
+                       u=None, opts=None, workspace_bytes=None, ray_live=None):
     """art_render_fwd with the occupancy skip of render_fwd_occ -> (levels, occupied)."""
     return _occ_call("aon_art_render_fwd_occ", (_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f)), rays_o, rays_d, viewdirs, near, far,
-                     white_bkgd, grid, num_levels, u, opts, workspace_bytes)
+                     white_bkgd, grid, num_levels, u, opts, workspace_bytes, ray_live)
 
 
 # ------------------------------------------------------------------ early ray termination (DESIGN.md section 4.10)
@@ -1711,7 +1805,11 @@ def _stop_workspace(device, n_rays: int, st, workspace_bytes):
     return _scratch(_OCC_WS_CACHE, device, need)
 
 
-def _stop_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, eps, round_samples, num_levels, u, opts, workspace_bytes):
+def _stop_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, eps, round_samples, num_levels, u, opts, workspace_bytes,
+               t_rand=None, noise=None, ray_live=None, want_stats=True):
+    """``want_stats=False`` (render_fwd / art_render_fwd with per-ray planes): no tally, no stop map -- NULL for both, nothing launched for them.
+    The _stop C calls; with per-ray near / far tensors or a `ray_live` mask, their _bounds forms (which also serve render_fwd /
+    render_fwd_occ with bounds: no grid and eps == 0 without a mask is aon_render_fwd_ex with per-ray planes, t_rand / noise allowed)."""
     if grid is not None and not isinstance(grid, OccupancyGrid):
         raise TypeError(f"{name}: grid must be an ops.OccupancyGrid (ops.occupancy_grid) or None, got {type(grid)}")
     if num_levels not in (1, 2):
@@ -1727,37 +1825,49 @@ def _stop_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, gri
     if grid is not None and grid.device != dev:
         raise ValueError(f"{name}: the grid is on {grid.device}, the rays on {dev}")
     op = _opts(opts)
-    if op.noise_std > 0:
-        raise ValueError(f"{name}: inference only, density noise (noise_std > 0) is refused")
+    near, far, bounds, bkeep = _ray_bounds(near, far, n, dev, ray_live)
+    plain = bounds is not None and grid is None and eps == 0.0 and ray_live is None     # aon_render_fwd_ex with per-ray planes
+    if not plain and (op.noise_std > 0 or t_rand is not None):
+        raise ValueError(f"{name}: inference only, density noise (noise_std > 0) and t_rand are refused")
+    tr = None if t_rand is None else _f32(t_rand, "t_rand")
+    if tr is not None and tuple(tr.shape) != (n, op.Sc):
+        raise ValueError(f"t_rand must be ({n},{op.Sc})")
     uu, us = _u_args(u, n, dev, op.num_fine_samples) if num_levels == 2 else (None, 0)
     outs = [tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in ((n, 3), (n,), (n,))) for _ in range(num_levels)]
     fine = outs[1] if num_levels == 2 else (None, None, None)
-    st, keep = op.c_struct(near, far)
+    st, keep = op.c_struct(near, far, _check_noise(noise, n, op, num_levels) if plain else None)
     occ = grid.c_struct() if grid is not None else None
-    occupied = torch.zeros(2, dtype=torch.int64, device=dev)
-    stop = torch.zeros((n, 2), dtype=torch.int32, device=dev)
-    ws = _stop_workspace(dev, n, st, workspace_bytes)
+    occupied = torch.zeros(2, dtype=torch.int64, device=dev) if want_stats else None
+    stop = torch.zeros((n, 2), dtype=torch.int32, device=dev) if want_stats else None
+    if plain:
+        ws = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=dev) if workspace_bytes is not None else _workspace(dev, n, st)
+    else:
+        ws = _stop_workspace(dev, n, st, workspace_bytes)
+    extra = ()
+    if bounds is not None:
+        name, extra = name.replace("_stop", "_bounds"), (C.byref(bounds),)
     with torch.cuda.device(dev):
-        check(getattr(lib, name)(*packs, _ptr(o), _ptr(d), _ptr(v), n, float(near), float(far), int(bool(white_bkgd)), num_levels, None, _ptr(uu), us,
+        check(getattr(lib, name)(*packs, _ptr(o), _ptr(d), _ptr(v), n, float(near), float(far), int(bool(white_bkgd)), num_levels, _ptr(tr) if tr is not None else None,
+                                 _ptr(uu), us,
                                  _ptr(outs[0][0]), _ptr(outs[0][1]), _ptr(outs[0][2]), _ptr(fine[0]), _ptr(fine[1]), _ptr(fine[2]),
                                  _ptr(ws), ws.numel(), _stream(), C.byref(st), C.byref(occ) if occ is not None else None, _ptr(occupied),
-                                 C.c_float(eps), R, _ptr(stop)), name)
+                                 C.c_float(eps), R, _ptr(stop), *extra), name)
     return [tuple(x) for x in outs], occupied, stop
 
 
 def render_fwd_stop(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, eps, round_samples=None, num_levels=2,
-                    u=None, opts=None, workspace_bytes=None):
+                    u=None, opts=None, workspace_bytes=None, ray_live=None):
     """render_fwd_occ with early ray termination: each level runs front to back in rounds of `round_samples` sample indices (default
     DEFAULT_ROUND_SAMPLES) and a ray whose optical depth has reached -ln(eps) after a round is stopped; its remaining samples get zero density
     and never reach the MLP.  `grid` may be None (termination alone); eps == 0 is off (the bits of render_fwd_occ / render_fwd).
     Returns (levels, occupied, stop): the level tuples, the int64 (2,) samples each level ran through the MLP, and the int32 (n, 2) per-level
     stop index of every ray (S of the level: never stopped; a level that was not run: 0)."""
     return _stop_call("aon_render_fwd_stop", (_pk(packed_coarse), _pk(packed_fine)), rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, eps,
-                      round_samples, num_levels, u, opts, workspace_bytes)
+                      round_samples, num_levels, u, opts, workspace_bytes, ray_live=ray_live)
 
 
 def art_render_fwd_stop(packed_c, small_c, packed_f, small_f, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, eps, round_samples=None,
-                        num_levels=2, u=None, opts=None, workspace_bytes=None):
+                        num_levels=2, u=None, opts=None, workspace_bytes=None, ray_live=None):
     """art_render_fwd with the occupancy skip and early termination of render_fwd_stop -> (levels, occupied, stop)."""
     return _stop_call("aon_art_render_fwd_stop", (_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f)), rays_o, rays_d, viewdirs, near, far,
-                      white_bkgd, grid, eps, round_samples, num_levels, u, opts, workspace_bytes)
+                      white_bkgd, grid, eps, round_samples, num_levels, u, opts, workspace_bytes, ray_live=ray_live)

@@ -53,6 +53,8 @@ def main():
     ap.add_argument("--threshold", type=float, default=0.01)
     ap.add_argument("--early-stop", type=float, default=None, metavar="EPS",
                     help="also render grid + early ray termination: a ray stops once its transmittance has fallen to EPS")
+    ap.add_argument("--ray-bounds", action="store_true",
+                    help="also render grid + per-ray near / far from the grid's box, rays that miss it skipped (DESIGN.md section 4.11)")
     args = ap.parse_args()
 
     from aon_amd.datasets.sapien import SapienDataset
@@ -96,6 +98,23 @@ def main():
                 rep["views"][-1].update({"psnr_stop": psnr(times["stop"][1], gt), "psnr_stop_vs_exact": psnr(times["stop"][1], times["exact"][1]),
                                          "skipped_coarse_stop": 1 - ran[0].item() / (n * 65), "skipped_fine_stop": 1 - ran[1].item() / (n * 193),
                                          "rays_stopped": float((stop[:, 1] < 193).float().mean()), "wall_s_stop": times["stop"][0]})
+            if args.ray_bounds:
+                box = ([-args.bound] * 3, [args.bound] * 3)
+
+                def bounded():
+                    near, far, live = ops.ray_limits(rays["rays_o"], rays["rays_d"], box)
+                    return ops.render_fwd_occ(model.coarse_mlp.packed(), model.fine_mlp.packed(), rays["rays_o"], rays["rays_d"], rays["viewdirs"],
+                                              near, far, True, grid, ray_live=live) + (live,)
+
+                bounded()   # warm-up
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                outs, ran, live = bounded()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                rep["views"][-1].update({"psnr_bounds": psnr(outs[-1][0], gt), "psnr_bounds_vs_exact": psnr(outs[-1][0], times["exact"][1]),
+                                         "skipped_coarse_bounds": 1 - ran[0].item() / (n * 65), "skipped_fine_bounds": 1 - ran[1].item() / (n * 193),
+                                         "rays_live": float(live.float().mean()), "wall_s_bounds": dt})
     print(json.dumps(rep, indent=1))
 
 

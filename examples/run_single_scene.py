@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--exp_dir", default="ckpts/demo")
     ap.add_argument("--resume", default=None)
     ap.add_argument("--seed", type=int, default=0, help="torch / numpy / random seed (model init, ray batches, stratified draws)")
+    ap.add_argument("--ray-box", type=float, default=None, metavar="SIDE",
+                    help="per-ray near / far from the rays' intersection with the cube of this side length around the origin (DESIGN.md section 4.11)")
     args = ap.parse_args()
     import random as _random
     _random.seed(args.seed); np.random.seed(args.seed); torch.manual_seed(args.seed)
@@ -50,7 +52,7 @@ def main():
     test = SapienDataset(args.root_dir, "test", tuple(args.img_wh), white_back=True, eval_inference="render", device=dev)
 
     lit = LitNeRF({"chunk": 65536, "img_wh": tuple(args.img_wh), "run_max_steps": args.steps},
-                  near=train.near, far=train.far, white_bkgd=True).to(dev)
+                  near=train.near, far=train.far, white_bkgd=True, ray_box=args.ray_box).to(dev)
     opt = lit.configure_optimizers()
     if args.resume:
         load_checkpoint(args.resume, lit, opt)

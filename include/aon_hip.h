@@ -658,6 +658,67 @@ int aon_grender_bwd(const aon_mlp_geometry* geom, const float* const* params_coa
                     float* const* grads_fine_host, void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
                     void* stream, const aon_render_opts* opts);
 
+/* ---- per-ray near / far from a ray-box intersection ----
+ * Additive: no existing call changes, the ABI version stays.  With scalar near_ / far_ every call keeps its path and its bits.
+ * aon_ray_limits_box: helper.get_ray_limits_box (helper.py:42-102) for the axis-aligned box [lo3, hi3] (the reference's cube is
+ *   +-box_side_length / 2): per ray the entry / exit distances, (-1, -2) for a ray the reference marks invalid; operation by operation
+ *   the reference's fp32 arithmetic (1 / d one IEEE division, (bound - o) * inv un-fused, NaN-propagating max / min), so a NaN of the
+ *   reference (origin on a face the ray is parallel to) is a NaN here.  near_ray / far_ray: device, (n_rays,) each.
+ * aon_ray_limits: helper.get_ray_limits (helper.py:29-39) without its host round trip: a ray is valid iff far > near; invalid rays get
+ *   min(near) / max(far) over the valid ones (left as they are when no ray is valid), then negatives are clamped to 0.  `live` (device,
+ *   (n_rays,) bytes, or NULL) receives 1 iff the ray was valid and far > near after the clamp.  The min / max belong to the ray SET: call it
+ *   once over all rays of an image, not per chunk.  workspace: aon_ray_limits_workspace_bytes(n_rays) bytes, 4-byte aligned.
+ * aon_sample_along_rays_bounds: helper.sample_along_rays (helper.py:106-133) with (N, 1) near / far tensors: aon_sample_along_rays_ex
+ *   with the planes of ray r read from near_ray[r] / far_ray[r]; under lindisp 1 / near is an fp32 IEEE reciprocal of the element, as
+ *   `1.0 / tensor` is. */
+int aon_ray_limits_box(const float* rays_o, const float* rays_d, int64_t n_rays, const float* lo3_host, const float* hi3_host,
+                       float* near_ray, float* far_ray, void* stream);
+int64_t aon_ray_limits_workspace_bytes(int64_t n_rays);
+int aon_ray_limits(const float* rays_o, const float* rays_d, int64_t n_rays, const float* lo3_host, const float* hi3_host,
+                   float* near_ray, float* far_ray, uint8_t* live /* nullable */, void* workspace, int64_t workspace_bytes, void* stream);
+int aon_sample_along_rays_bounds(const float* rays_o, const float* rays_d, int64_t n_rays, int S, const float* near_ray,
+                                 const float* far_ray, int lindisp, const float* t_rand, float* t_vals, float* coords, void* stream);
+/* Whole path with per-ray planes (NeRF.forward / NeRF_AE_Art.forward handed the (N, 1) tensors of helper.get_ray_limits, model.py:147-160,
+ * model_autodecoder.py:278-291).  The _stop calls' arguments plus `bounds`:
+ *   bounds == NULL: the _stop call itself.  Otherwise level 0's t comes from near_ray / far_ray and the scalars near_ / far_ (and
+ *   opts->inv_near / inv_far) are ignored; everything downstream consumes t per ray and is unchanged.
+ *   bounds->live (nullable): a ray whose byte is 0 is DEAD -- all its samples get the record (0, 0, 0, -inf) and none reaches the MLP, so it
+ *   composites to the background with acc = 0, depth = 0.  It routes the call through the compaction path even without a grid or eps.
+ *   Without a grid, eps and live the call is aon_render_fwd_ex / aon_art_render_fwd_ex with per-ray planes and follows THAT call's rules
+ *   (t_rand, noise and other degrees allowed; workspace aon_render_workspace_bytes_ex); otherwise the _occ / _stop rules and workspace query
+ *   apply.  Refused before any launch (AON_E_INVALID): NULL near_ray / far_ray inside a non-NULL bounds; live together with t_rand; whatever
+ *   the underlying call refuses.  A chunked call offsets near_ray / far_ray / live by the chunk's first ray.
+ * The training forms are the _train_ex calls plus `bounds`; bounds->live must be NULL there (AON_E_INVALID otherwise), t_rand is allowed.
+ *   The backward entry points are unchanged: they read t from the workspace.  The layer-wise engine (aon_grender_*) has no bounds form. */
+typedef struct aon_ray_bounds {
+  const float* near_ray;   /* device, (n_rays,) */
+  const float* far_ray;    /* device, (n_rays,) */
+  const uint8_t* live;     /* device, (n_rays,) bytes, or NULL: every ray is live */
+} aon_ray_bounds;
+int aon_render_fwd_bounds(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                          const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                          const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                          float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                          const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev, float eps, int round_samples,
+                          int32_t* stop_dev, const aon_ray_bounds* bounds);
+int aon_art_render_fwd_bounds(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                              const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                              int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                              float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                              int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
+                              int64_t* occupied_dev, float eps, int round_samples, int32_t* stop_dev, const aon_ray_bounds* bounds);
+int aon_render_fwd_train_bounds(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                                const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                                const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                                float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                                const aon_render_opts* opts, const aon_ray_bounds* bounds);
+int aon_art_render_fwd_train_bounds(const void* packed_coarse, const void* small_coarse, const void* packed_fine,
+                                    const void* small_fine, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                    int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels, const float* t_rand,
+                                    const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c, float* rgb_f,
+                                    float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                                    const aon_render_opts* opts, const aon_ray_bounds* bounds);
+
 /* ---- measurement aid (no reference counterpart) ----
  * Between aon_profile_begin() and aon_profile_end() every launch of the path's kernels made through this library is
  * bracketed by HIP events recorded on the LAUNCH stream, by kernel class.  aon_profile_end() waits for those events

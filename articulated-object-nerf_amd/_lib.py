@@ -27,7 +27,30 @@ if not os.path.exists(LIB_PATH):
 lib = C.CDLL(LIB_PATH)
 
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
+# The whole-path forwards (one C call from rays to composited levels) share one argument list, csrc/aon_capi_util.h's PathCall, between a
+# network prefix and the suffixes of the form
+_PATH = ([_p, _p, _p, _l]          # rays_o, rays_d, viewdirs, n_rays
+         + [_f, _f, _i, _i]        # near, far, white_bkgd, num_levels
+         + [_p, _p, _l]            # t_rand, u, u_stride
+         + [_p] * 6                # rgb, acc, depth of the coarse and of the fine level
+         + [_p, _l, _p])           # workspace, workspace_bytes, stream
+_VANILLA, _ART, _GENERAL = [_p] * 2, [_p] * 4, [_p] * 3   # packed c/f | packed, small c/f | aon_mlp_geometry, parameter arrays c/f
+_OPTS, _OCC, _STOP, _BOUNDS = [_p], [_p, _p], [_f, _i, _p], [_p]   # opts | grid, tally | eps, round_samples, stop map | aon_ray_bounds
+
+
+def _path_sigs():
+    sigs = {"aon_grender_fwd": _GENERAL + _PATH + _OPTS, "aon_grender_fwd_train": _GENERAL + _PATH + _OPTS}
+    for net, prefix in (("aon_", _VANILLA), ("aon_art_", _ART)):
+        head = prefix + _PATH
+        sigs.update({net + "render_fwd": head, net + "render_fwd_ex": head + _OPTS, net + "render_fwd_occ": head + _OPTS + _OCC,
+                     net + "render_fwd_stop": head + _OPTS + _OCC + _STOP, net + "render_fwd_bounds": head + _OPTS + _OCC + _STOP + _BOUNDS,
+                     net + "render_fwd_train": head, net + "render_fwd_train_ex": head + _OPTS,
+                     net + "render_fwd_train_bounds": head + _OPTS + _BOUNDS})
+    return {name: (_i, args) for name, args in sigs.items()}
+
+
 _SIGS = {
+    **_path_sigs(),
     "aon_abi_version": (_i, []),
     "aon_last_error": (C.c_char_p, []),
     "aon_raygen": (_i, [_p, _i, _i, _f, _l, _l, _p, _p, _p, _p]),
@@ -54,7 +77,6 @@ _SIGS = {
     "aon_pack_art_mlp_bwd_deg": (_i, [_p, _i, _i, _i, _p, _p]),
     "aon_art_mlp_fwd": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _p, _p]),
     "aon_art_mlp_fwd_pos": (_i, [_p, _p, _p, _p, _l, _i, _p, _p]),
-    "aon_art_render_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p]),
     "aon_train_plane_rows": (_l, []),
     "aon_bwd_packed_bytes": (_l, []),
     "aon_wgrad_workspace_bytes": (_l, []),
@@ -93,12 +115,7 @@ _SIGS = {
     "aon_occupancy_bytes": (_l, [_p]),
     "aon_occupancy_build": (_i, [_p, _p, _f, _i, _p, _p]),
     "aon_render_occ_workspace_bytes": (_l, [_l, _p]),
-    "aon_render_fwd_occ": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p]),
-    "aon_art_render_fwd_occ": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p]),
     "aon_render_stop_workspace_bytes": (_l, [_l, _p]),
-    "aon_render_fwd_stop": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _f, _i, _p]),
-    "aon_art_render_fwd_stop": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p,
-                                     _f, _i, _p]),
     "aon_art_pack_step": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "aon_vanilla_pack_step": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
     "aon_set_bwd_early_heads": (_i, [_i]),
@@ -112,9 +129,7 @@ _SIGS = {
     "aon_set_wgrad_probe": (_i, [_p]),
     "aon_train_workspace_bytes": (_l, [_l, _i, _i]),
     "aon_train_scratch_bytes": (_l, [_l, _i, _i]),
-    "aon_render_fwd_train": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p]),
     "aon_render_bwd": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p]),
-    "aon_art_render_fwd_train": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p]),
     "aon_art_render_bwd": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p]),
     "aon_profile_begin": (_i, []),
     "aon_profile_end": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -122,7 +137,6 @@ _SIGS = {
     "aon_composite_pdf": (_i, [_p, _p, _p, _l, _i, _i, _p, _l, _p, _p, _p, _p, _p, _p]),
     "aon_set_coarse_fusion": (_i, [_i]),
     "aon_render_workspace_bytes": (_l, [_l]),
-    "aon_render_fwd": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p]),
     # constructor arguments beyond the defaults (aon_render_opts; the *_ex forms take the struct pointer last)
     "aon_render_opts_init": (None, [_p]),
     "aon_pack_vanilla_mlp_deg": (_i, [_p, _i, _i, _i, _p, _p]),
@@ -131,13 +145,9 @@ _SIGS = {
     "aon_composite_ex": (_i, [_p, _i, _p, _i, _p, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "aon_sample_pdf_n": (_i, [_p, _p, _l, _p, _p, _l, _l, _i, _i, _i, _p, _p, _p]),
     "aon_render_workspace_bytes_ex": (_l, [_l, _p]),
-    "aon_render_fwd_ex": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p]),
-    "aon_art_render_fwd_ex": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p]),
     "aon_train_workspace_bytes_ex": (_l, [_l, _i, _i, _p]),
     "aon_train_scratch_bytes_ex": (_l, [_l, _i, _i, _p]),
-    "aon_render_fwd_train_ex": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p]),
     "aon_render_bwd_ex": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p]),
-    "aon_art_render_fwd_train_ex": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p]),
     "aon_art_render_bwd_ex": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p]),
     # NeRFMLP of any constructor geometry (aon_mlp_geometry first)
     "aon_mlp_geometry_init": (None, [_p]),
@@ -145,21 +155,14 @@ _SIGS = {
     "aon_gmlp_workspace_bytes": (_l, [_p, _l]),
     "aon_gmlp_fwd": (_i, [_p, _p, _p, _p, _l, _i, _p, _p, _p, _l, _p]),
     "aon_grender_workspace_bytes": (_l, [_p, _l, _p]),
-    "aon_grender_fwd": (_i, [_p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p]),
     "aon_grender_train_workspace_bytes": (_l, [_p, _l, _i, _p]),
     "aon_grender_train_scratch_bytes": (_l, [_p, _l, _i, _p]),
-    "aon_grender_fwd_train": (_i, [_p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p]),
     "aon_grender_bwd": (_i, [_p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p]),
-    # per-ray near / far from a ray-box intersection (aon_ray_bounds last)
+    # per-ray near / far from a ray-box intersection
     "aon_ray_limits_box": (_i, [_p, _p, _l, _p, _p, _p, _p, _p]),
     "aon_ray_limits_workspace_bytes": (_l, [_l]),
     "aon_ray_limits": (_i, [_p, _p, _l, _p, _p, _p, _p, _p, _p, _l, _p]),
     "aon_sample_along_rays_bounds": (_i, [_p, _p, _l, _i, _p, _p, _i, _p, _p, _p, _p]),
-    "aon_render_fwd_bounds": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _f, _i, _p, _p]),
-    "aon_art_render_fwd_bounds": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p,
-                                       _f, _i, _p, _p]),
-    "aon_render_fwd_train_bounds": (_i, [_p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p]),
-    "aon_art_render_fwd_train_bounds": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _f, _f, _i, _i, _p, _p, _l, _p, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p]),
 }
 
 

@@ -315,20 +315,17 @@ int aon_grender_fwd(const aon_mlp_geometry* geom, const float* const* params_coa
                     float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream_,
                     const aon_render_opts* opts) {
   const char* who = "aon_grender_fwd";
-  hipStream_t stream = (hipStream_t)stream_;
+  const PathCall c = path_call(rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f,
+                               acc_f, depth_f, workspace, workspace_bytes, stream_, opts);
+  const hipStream_t stream = c.stream;
   GG g; Geo geo;
   if (const char* bad = make_gg(geom, g)) return fail(AON_E_INVALID, bad);
   if (const char* bad = whole_path_ok(g)) return fail(AON_E_INVALID, bad);
   if (const char* bad = make_geo(opts, geo, true)) return fail(AON_E_INVALID, bad);
-  if (n_rays < 0 || (num_levels != 1 && num_levels != 2)) return fail(AON_E_INVALID, "aon_grender_fwd: bad size / num_levels");
-  if (n_rays == 0) return AON_OK;
+  if (int rc = path_call_check(who, c, geo, true)) return rc == kPathEmpty ? AON_OK : rc;
   if (int rc = check_params(g, params_coarse_host, "aon_grender_fwd: null parameter pointer")) return rc;
   if (num_levels == 2)
     if (int rc = check_params(g, params_fine_host, "aon_grender_fwd: null parameter pointer")) return rc;
-  if (!rays_o || !rays_d || !viewdirs || !rgb_c || !acc_c || !depth_c || !workspace) return fail(AON_E_INVALID, "aon_grender_fwd: null pointer");
-  if (num_levels == 2 && (!rgb_f || !acc_f || !depth_f || !u || (u_stride != 0 && u_stride < geo.nf)))
-    return fail(AON_E_INVALID, "aon_grender_fwd: null fine-level pointer / bad u_stride");
-  if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(AON_E_INVALID, "aon_grender_fwd: workspace must be 256-byte aligned");
   int64_t chunk = n_rays;
   if (carve_grender(nullptr, g, geo, chunk).bytes > workspace_bytes) {
     const int64_t one = carve_grender(nullptr, g, geo, 1).bytes, two = carve_grender(nullptr, g, geo, 1025).bytes;
@@ -343,9 +340,6 @@ int aon_grender_fwd(const aon_mlp_geometry* geom, const float* const* params_coa
     const int64_t n = n_rays - r0 < chunk ? n_rays - r0 : chunk;
     const float* o = rays_o + r0 * 3; const float* d = rays_d + r0 * 3; const float* v = viewdirs + r0 * 3;
     const float* uu = u_stride ? u + r0 * u_stride : u;
-    float* rgb[2] = {rgb_c + r0 * 3, rgb_f ? rgb_f + r0 * 3 : nullptr};
-    float* acc[2] = {acc_c + r0, acc_f ? acc_f + r0 : nullptr};
-    float* dep[2] = {depth_c + r0, depth_f ? depth_f + r0 : nullptr};
     for (int l = 0; l < num_levels; ++l) {
       const int S = geo.S(l);
       float* t = l == 0 ? w.t_c : w.t_f;
@@ -365,7 +359,7 @@ int aon_grender_fwd(const aon_mlp_geometry* geom, const float* const* params_coa
       if ((rc = gmlp_forward(g, params[l], w.acts, n, S, w.raw, 4, w.raw + 3, 4, stream, who))) return rc;
       {
         KTimer timer(kComposite, stream, n);
-        rc = check(aon::launch_composite(w.raw, 4, w.raw + 3, 4, t, d, n, S, white_bkgd, geo.act(false, l, r0), rgb[l], acc[l], dep[l],
+        rc = check(aon::launch_composite(w.raw, 4, w.raw + 3, 4, t, d, n, S, white_bkgd, geo.act(false, l, r0), c.rgb[l] + r0 * 3, c.acc[l] + r0, c.depth[l] + r0,
                                          (l == 0 && num_levels == 2) ? w.w_c : nullptr, stream), who);
       }
       if (rc) return rc;
@@ -393,24 +387,21 @@ int aon_grender_fwd_train(const aon_mlp_geometry* geom, const float* const* para
                           float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
                           int64_t workspace_bytes, void* stream_, const aon_render_opts* opts) {
   const char* who = "aon_grender_fwd_train";
-  hipStream_t stream = (hipStream_t)stream_;
+  const PathCall c = path_call(rays_o, rays_d, viewdirs, n, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f,
+                               depth_f, workspace, workspace_bytes, stream_, opts);
+  const hipStream_t stream = c.stream;
   GG g; Geo geo;
   if (const char* bad = make_gg(geom, g)) return fail(AON_E_INVALID, bad);
   if (const char* bad = whole_path_ok(g)) return fail(AON_E_INVALID, bad);
   if (const char* bad = make_geo(opts, geo, true)) return fail(AON_E_INVALID, bad);
   if (geo.Sf > 512) return fail(AON_E_INVALID, "aon_grender_fwd_train: more than 512 samples per ray at the fine level");
-  if (n <= 0 || (num_levels != 1 && num_levels != 2)) return fail(AON_E_INVALID, "aon_grender_fwd_train: bad size / num_levels");
+  if (int rc = path_call_check(who, c, geo, false)) return rc;
   if (int rc = check_params(g, params_coarse_host, "aon_grender_fwd_train: null parameter pointer")) return rc;
   if (num_levels == 2)
     if (int rc = check_params(g, params_fine_host, "aon_grender_fwd_train: null parameter pointer")) return rc;
-  if (!rays_o || !rays_d || !viewdirs || !rgb_c || !acc_c || !depth_c || !workspace) return fail(AON_E_INVALID, "aon_grender_fwd_train: null pointer");
-  if (num_levels == 2 && (!rgb_f || !acc_f || !depth_f || !u || (u_stride != 0 && u_stride < geo.nf)))
-    return fail(AON_E_INVALID, "aon_grender_fwd_train: null fine-level pointer / bad u_stride");
-  if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(AON_E_INVALID, "aon_grender_fwd_train: workspace must be 256-byte aligned");
   const GTrainWs w = carve_gtrain(workspace, g, geo, n, num_levels);
   if (w.bytes > workspace_bytes) return fail(AON_E_WORKSPACE, "aon_grender_fwd_train: workspace smaller than aon_grender_train_workspace_bytes()");
   const float* const* params[2] = {params_coarse_host, params_fine_host};
-  float* rgb[2] = {rgb_c, rgb_f}; float* acc[2] = {acc_c, acc_f}; float* dep[2] = {depth_c, depth_f};
   for (int l = 0; l < num_levels; ++l) {
     const GTrainLevel& L = w.lvl[l];
     int rc;
@@ -429,7 +420,7 @@ int aon_grender_fwd_train(const aon_mlp_geometry* geom, const float* const* para
     if ((rc = gmlp_forward(g, params[l], L.acts, n, L.S, L.raw, 4, L.raw + 3, 4, stream, who))) return rc;
     {
       KTimer timer(kComposite, stream, n);
-      rc = check(aon::launch_composite(L.raw, 4, L.raw + 3, 4, L.t, rays_d, n, L.S, white_bkgd, geo.act(false, l, 0), rgb[l], acc[l], dep[l],
+      rc = check(aon::launch_composite(L.raw, 4, L.raw + 3, 4, L.t, rays_d, n, L.S, white_bkgd, geo.act(false, l, 0), c.rgb[l], c.acc[l], c.depth[l],
                                        (l == 0 && num_levels == 2) ? w.w_c : nullptr, stream), who);
     }
     if (rc) return rc;

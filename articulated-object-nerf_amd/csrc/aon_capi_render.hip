@@ -42,12 +42,15 @@ Ws carve(char* base, int64_t n, const Geo& g, bool occ = false, bool stop = fals
 
 extern "C" {
 
-int64_t aon_render_workspace_bytes_ex(int64_t n_rays, const aon_render_opts* opts) {
-  if (n_rays < 1) n_rays = 1;
+// the workspace-size queries: one chunk of n_rays (at least one; [occupancy] at most what the int32 sample list indexes)
+static int64_t workspace_query(int64_t n_rays, const aon_render_opts* opts, bool occ, bool stop) {
   Geo g;
   if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
-  return carve(nullptr, n_rays, g).bytes;
+  if (n_rays < 1) n_rays = 1;
+  if (occ && n_rays > INT32_MAX / g.Sf) n_rays = INT32_MAX / g.Sf;
+  return carve(nullptr, n_rays, g, occ, stop).bytes;
 }
+int64_t aon_render_workspace_bytes_ex(int64_t n_rays, const aon_render_opts* opts) { return workspace_query(n_rays, opts, false, false); }
 int64_t aon_render_workspace_bytes(int64_t n_rays) { return aon_render_workspace_bytes_ex(n_rays, nullptr); }
 
 // Whole-path orchestration shared by the vanilla and the articulated network (NeRF.forward, model.py:147-199;
@@ -58,6 +61,13 @@ struct NetRef {
   const void* packed;
   const float* small;  // articulated only
 };
+struct Nets { NetRef c, f; };   // coarse, fine
+static Nets vanilla_nets(const void* packed_coarse, const void* packed_fine) {
+  return {{false, packed_coarse, nullptr}, {false, packed_fine, nullptr}};
+}
+static Nets art_nets(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine) {
+  return {{true, packed_coarse, static_cast<const float*>(small_coarse)}, {true, packed_fine, static_cast<const float*>(small_fine)}};
+}
 
 // An occupancy grid handed to aon_render_fwd_occ / aon_art_render_fwd_occ: the kernels' view of it, and the
 // caller's per-level tally of samples run through the MLP (or null)
@@ -139,23 +149,17 @@ static hipError_t launch_net(const NetRef& net, const float* o, const float* d, 
   return aon::launch_mlp_fwd(static_cast<const char*>(net.packed), o, d, v, t, n, S, raw, stream, vbias);
 }
 
-static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine, const float* rays_o, const float* rays_d,
-                       const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
-                       const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
-                       float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, hipStream_t stream,
-                       const aon_render_opts* opts, const OccCtx* occ = nullptr, const aon_ray_bounds* bounds = nullptr) {
+static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine, const PathCall& c, const OccCtx* occ = nullptr) {
   Geo g;
-  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
-  if (n_rays < 0 || (num_levels != 1 && num_levels != 2)) return fail(AON_E_INVALID, "render: bad size / num_levels");
-  if (n_rays == 0) return AON_OK;
-  if (!coarse.packed || !rays_o || !rays_d || !viewdirs || !rgb_c || !acc_c || !depth_c || !workspace)
-    return fail(AON_E_INVALID, "render: null pointer");
-  if (num_levels == 2 && (!fine.packed || !rgb_f || !acc_f || !depth_f || !u))
-    return fail(AON_E_INVALID, "render: null fine-level pointer");
-  if (coarse.articulated && (!coarse.small || (num_levels == 2 && !fine.small))) return fail(AON_E_INVALID, "render: null latent block");
+  if (const char* bad = make_geo(c.opts, g)) return fail(AON_E_INVALID, bad);
+  if (int rc = path_call_check(who, c, g, true)) return rc == kPathEmpty ? AON_OK : rc;
+  const int64_t n_rays = c.n_rays;
+  const int num_levels = c.num_levels;
+  const hipStream_t stream = c.stream;
+  auto bad = [&](const char* what) { return fail(AON_E_INVALID, (std::string(who) + ": " + what).c_str()); };
+  if (!coarse.packed || (num_levels == 2 && !fine.packed)) return bad("null pointer");
+  if (coarse.articulated && (!coarse.small || (num_levels == 2 && !fine.small))) return bad("null latent block");
   if (coarse.articulated && (forms_differ(coarse.packed, coarse.small) || (num_levels == 2 && forms_differ(fine.packed, fine.small)))) return fail(AON_E_INVALID, kFormsMsg);
-  if (num_levels == 2 && u_stride != 0 && u_stride < g.nf) return fail(AON_E_INVALID, "render: bad u_stride");
-  if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(AON_E_INVALID, "render: workspace must be 256-byte aligned");
   const bool art = coarse.articulated;
   if (art) g.other_degrees = false;   // the articulated kernels carry their degrees in the packed stream and the small block (aon_*_deg)
   const bool fuse_coarse = num_levels == 2 && g.default_sizes && g_fuse_coarse.load(std::memory_order_relaxed) != 0;
@@ -165,36 +169,36 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
   // largest chunk the workspace admits ([occupancy] and whose sample indices fit the int32 list)
   int64_t chunk = n_rays;
   if (with_occ && chunk > INT32_MAX / g.Sf) chunk = INT32_MAX / g.Sf;
-  if (carve(nullptr, chunk, g, with_occ, with_stop).bytes > workspace_bytes) {
+  if (carve(nullptr, chunk, g, with_occ, with_stop).bytes > c.workspace_bytes) {
     const int64_t per_ray = (int64_t)(g.Sc + g.Sc + g.Sf + 4 * g.Sf + (g.other_degrees ? (3 + aon::kPosEnc) * g.Sf + aon::kViewEnc : aon::kCondWidth) +
                                       (with_occ ? g.Sf + 2 * (g.Sf / 1024 + 1) : 0) + (with_stop ? 2 : 0)) * 4;
     const int64_t slack = (g.other_degrees ? 7 * 256 : 5 * 256) + (with_occ ? 4 * 256 : 0) + (with_stop ? 2 * 256 : 0);
-    chunk = (workspace_bytes - slack) / per_ray;
-    while (chunk > 0 && carve(nullptr, chunk, g, with_occ, with_stop).bytes > workspace_bytes) --chunk;
+    chunk = (c.workspace_bytes - slack) / per_ray;
+    while (chunk > 0 && carve(nullptr, chunk, g, with_occ, with_stop).bytes > c.workspace_bytes) --chunk;
     if (chunk < 1) return fail(AON_E_WORKSPACE, with_stop ? "render: workspace smaller than aon_render_stop_workspace_bytes(1)"
                                                 : with_occ ? "render: workspace smaller than aon_render_occ_workspace_bytes(1)"
                                                          : "render: workspace smaller than aon_render_workspace_bytes(1)");
   }
-  const Ws w = carve(static_cast<char*>(workspace), chunk, g, with_occ, with_stop);
+  const Ws w = carve(static_cast<char*>(c.workspace), chunk, g, with_occ, with_stop);
   if (with_occ && occ->tally) {
     if (int rc = check(hipMemsetAsync(occ->tally, 0, 2 * sizeof(int64_t), stream), who); rc != AON_OK) return rc;
   }
 
   for (int64_t r0 = 0; r0 < n_rays; r0 += chunk) {
     const int64_t n = n_rays - r0 < chunk ? n_rays - r0 : chunk;
-    const float* o = rays_o + r0 * 3;
-    const float* d = rays_d + r0 * 3;
-    const float* v = viewdirs + r0 * 3;
-    const float* uu = u_stride ? u + r0 * u_stride : u;
+    const float* o = c.rays_o + r0 * 3;
+    const float* d = c.rays_d + r0 * 3;
+    const float* v = c.viewdirs + r0 * 3;
+    const float* uu = c.u_stride ? c.u + r0 * c.u_stride : c.u;
     // [per-ray bounds, DESIGN.md section 4.11] the chunk's near / far / live
-    const float* near_ray = bounds ? bounds->near_ray + r0 : nullptr;
-    const float* far_ray = bounds ? bounds->far_ray + r0 : nullptr;
-    const uint8_t* live = bounds && bounds->live ? bounds->live + r0 : nullptr;
+    const float* near_ray = c.bounds ? c.bounds->near_ray + r0 : nullptr;
+    const float* far_ray = c.bounds ? c.bounds->far_ray + r0 : nullptr;
+    const uint8_t* live = c.bounds && c.bounds->live ? c.bounds->live + r0 : nullptr;
     int rc;
     // level 0 (model.py:150-160, :175-197)
     {
       KTimer timer(kSampleT, stream, n);
-      rc = check(aon::launch_sample_along_rays(o, d, n, g.Sc, near_, far_, t_rand ? t_rand + r0 * g.Sc : nullptr, w.t_c, nullptr, stream,
+      rc = check(aon::launch_sample_along_rays(o, d, n, g.Sc, c.near_, c.far_, c.t_rand ? c.t_rand + r0 * g.Sc : nullptr, w.t_c, nullptr, stream,
                                                g.lindisp, g.inv_near, g.inv_far, near_ray, far_ray), who);
     }
     if (rc) return rc;
@@ -207,20 +211,20 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
     if (fuse_coarse) {
       // compositing + the fine level's sampling (model.py:162-173) in one kernel: the coarse weights stay in registers
       KTimer timer(kCompositePdf, stream, n);
-      rc = check(aon::launch_composite_pdf(w.raw, w.t_c, d, n, white_bkgd, g.act(art, 0, r0), uu, u_stride, rgb_c + r0 * 3,
-                                           acc_c + r0, depth_c + r0, nullptr, w.t_f, stream), who);
+      rc = check(aon::launch_composite_pdf(w.raw, w.t_c, d, n, c.white_bkgd, g.act(art, 0, r0), uu, c.u_stride, c.rgb[0] + r0 * 3,
+                                           c.acc[0] + r0, c.depth[0] + r0, nullptr, w.t_f, stream), who);
     } else {
       KTimer timer(kComposite, stream, n);
-      rc = check(aon::launch_composite(w.raw, 4, w.raw + 3, 4, w.t_c, d, n, g.Sc, white_bkgd, g.act(art, 0, r0), rgb_c + r0 * 3, acc_c + r0,
-                                       depth_c + r0, num_levels == 2 ? w.w_c : nullptr, stream), who);
+      rc = check(aon::launch_composite(w.raw, 4, w.raw + 3, 4, w.t_c, d, n, g.Sc, c.white_bkgd, g.act(art, 0, r0), c.rgb[0] + r0 * 3, c.acc[0] + r0,
+                                       c.depth[0] + r0, num_levels == 2 ? w.w_c : nullptr, stream), who);
     }
     if (rc) return rc;
     if (num_levels == 1) continue;
     // level 1 (model.py:162-173, :175-197)
     if (!fuse_coarse) {
       KTimer timer(kSamplePdf, stream, n);
-      rc = check(g.default_sizes ? aon::launch_sample_pdf(nullptr, w.w_c + 1, kSc, w.t_c, uu, u_stride, n, nullptr, w.t_f, stream)
-                                 : aon::launch_sample_pdf_n(nullptr, w.w_c + 1, g.Sc, w.t_c, uu, u_stride, n, g.Sc - 1, g.nf, g.Sc, nullptr,
+      rc = check(g.default_sizes ? aon::launch_sample_pdf(nullptr, w.w_c + 1, kSc, w.t_c, uu, c.u_stride, n, nullptr, w.t_f, stream)
+                                 : aon::launch_sample_pdf_n(nullptr, w.w_c + 1, g.Sc, w.t_c, uu, c.u_stride, n, g.Sc - 1, g.nf, g.Sc, nullptr,
                                                             w.t_f, stream), who);
       if (rc) return rc;
     }
@@ -232,29 +236,12 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
     }
     {
       KTimer timer(kComposite, stream, n);
-      rc = check(aon::launch_composite(w.raw, 4, w.raw + 3, 4, w.t_f, d, n, g.Sf, white_bkgd, g.act(art, 1, r0), rgb_f + r0 * 3, acc_f + r0,
-                                       depth_f + r0, nullptr, stream), who);
+      rc = check(aon::launch_composite(w.raw, 4, w.raw + 3, 4, w.t_f, d, n, g.Sf, c.white_bkgd, g.act(art, 1, r0), c.rgb[1] + r0 * 3, c.acc[1] + r0,
+                                       c.depth[1] + r0, nullptr, stream), who);
     }
     if (rc) return rc;
   }
   return AON_OK;
-}
-
-int aon_render_fwd_ex(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
-                      const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
-                      const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
-                      float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
-                      const aon_render_opts* opts) {
-  const NetRef c{false, packed_coarse, nullptr}, f{false, packed_fine, nullptr};
-  return render_impl("aon_render_fwd", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
-                     u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts);
-}
-int aon_render_fwd(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
-                   const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
-                   const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
-                   float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream) {
-  return aon_render_fwd_ex(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
-                           u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, nullptr);
 }
 
 // ---- occupancy-grid accelerated inference (aon_occ.hip) ----
@@ -300,75 +287,75 @@ static const char* occ_opts_bad(const aon_render_opts* opts, bool art, const flo
   if (!art && g.other_degrees) return "occupancy rendering needs the default encoding degrees (0, 10, 4) of the vanilla network";
   return nullptr;
 }
-int64_t aon_render_occ_workspace_bytes(int64_t n_rays, const aon_render_opts* opts) {
-  if (n_rays < 1) n_rays = 1;
-  Geo g;
-  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
-  if (n_rays > INT32_MAX / g.Sf) n_rays = INT32_MAX / g.Sf;
-  return carve(nullptr, n_rays, g, true).bytes;
-}
-int aon_render_fwd_occ(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
-                       const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
-                       const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
-                       float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
-                       const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev) {
-  OccCtx ctx{};
-  if (const char* bad = occ_grid_bad(occ, ctx.grid)) return fail(AON_E_INVALID, (std::string("aon_render_fwd_occ: ") + bad).c_str());
-  if (const char* bad = occ_opts_bad(opts, false, t_rand)) return fail(AON_E_INVALID, (std::string("aon_render_fwd_occ: ") + bad).c_str());
-  ctx.tally = occupied_dev;
-  const NetRef c{false, packed_coarse, nullptr}, f{false, packed_fine, nullptr};
-  return render_impl("aon_render_fwd_occ", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
-                     u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, &ctx);
-}
+int64_t aon_render_occ_workspace_bytes(int64_t n_rays, const aon_render_opts* opts) { return workspace_query(n_rays, opts, true, false); }
 
 // ---- early ray termination on the occupancy renders ----
-int64_t aon_render_stop_workspace_bytes(int64_t n_rays, const aon_render_opts* opts) {
-  if (n_rays < 1) n_rays = 1;
-  Geo g;
-  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
-  if (n_rays > INT32_MAX / g.Sf) n_rays = INT32_MAX / g.Sf;
-  return carve(nullptr, n_rays, g, true, true).bytes;
-}
-// the checks and the eps == 0 route shared by aon_render_fwd_stop / aon_art_render_fwd_stop
-static int render_stop(const char* who, const NetRef& c, const NetRef& f, const float* rays_o, const float* rays_d, const float* viewdirs,
-                       int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels, const float* t_rand, const float* u,
-                       int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
-                       int64_t workspace_bytes, hipStream_t stream, const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev,
-                       float eps, int round_samples, int32_t* stop_dev, const aon_ray_bounds* bounds = nullptr) {
+int64_t aon_render_stop_workspace_bytes(int64_t n_rays, const aon_render_opts* opts) { return workspace_query(n_rays, opts, true, true); }
+
+// The checks and the eps == 0 route shared by the _occ, _stop and _bounds forms of both networks.  need_grid: the _occ forms, which have no
+// eps / round_samples arguments (they pass 0 / 1) and refuse a null grid.
+static int render_stop(const char* who, const Nets& nets, const PathCall& c, const aon_occupancy* occ, int64_t* occupied_dev, float eps,
+                       int round_samples, int32_t* stop_dev, bool need_grid = false) {
+  auto bad = [&](const char* what) { return fail(AON_E_INVALID, (std::string(who) + ": " + what).c_str()); };
+  const aon_ray_bounds* bounds = c.bounds;
   OccCtx ctx{};
-  if (bounds) {
-    if (!bounds->near_ray || !bounds->far_ray) return fail(AON_E_INVALID, (std::string(who) + ": null near_ray / far_ray in bounds").c_str());
-    if (bounds->live && t_rand) return fail(AON_E_INVALID, (std::string(who) + ": ray_live is inference only: t_rand (randomized sampling) is refused").c_str());
-  }
-  if (occ)
-    if (const char* bad = occ_grid_bad(occ, ctx.grid)) return fail(AON_E_INVALID, (std::string(who) + ": " + bad).c_str());
+  if (bounds && bounds->live && c.t_rand) return bad("ray_live is inference only: t_rand (randomized sampling) is refused");
+  if (occ || need_grid)
+    if (const char* msg = occ_grid_bad(occ, ctx.grid)) return bad(msg);
   // the compaction path (mark / scan / emit and the GATHER launches): a grid, early termination or a ray mask
   const bool compact = occ || (bounds && bounds->live) || eps != 0.f;
   // (bounds alone: aon_render_fwd_ex with per-ray planes, and that call's rules -- t_rand, noise and other degrees are its to take)
   if (!bounds || compact)
-    if (const char* bad = occ_opts_bad(opts, c.articulated, t_rand)) return fail(AON_E_INVALID, (std::string(who) + ": " + bad).c_str());
-  if (!(eps >= 0.f && eps < 1.f)) return fail(AON_E_INVALID, (std::string(who) + ": eps must be in [0, 1)").c_str());
-  if (round_samples < 1) return fail(AON_E_INVALID, (std::string(who) + ": round_samples must be >= 1").c_str());
+    if (const char* msg = occ_opts_bad(c.opts, nets.c.articulated, c.t_rand)) return bad(msg);
+  if (!(eps >= 0.f && eps < 1.f)) return bad("eps must be in [0, 1)");
+  if (round_samples < 1) return bad("round_samples must be >= 1");
   ctx.tally = occupied_dev;
   if (eps == 0.f) {   // off: today's single-launch paths, and the bookkeeping of a render in which no ray stopped
-    const int rc = render_impl(who, c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c,
-                               depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, opts, compact ? &ctx : nullptr, bounds);
-    if (rc != AON_OK || n_rays == 0) return rc;
+    const int rc = render_impl(who, nets.c, nets.f, c, compact ? &ctx : nullptr);
+    if (rc != AON_OK || c.n_rays == 0) return rc;
     Geo g;
-    (void)make_geo(opts, g);
+    (void)make_geo(c.opts, g);
     if (!compact && occupied_dev)
-      if (int r2 = check(aon::launch_occ_tally_set(occupied_dev, n_rays * g.Sc, num_levels == 2 ? n_rays * g.Sf : 0, stream), who); r2 != AON_OK) return r2;
+      if (int r2 = check(aon::launch_occ_tally_set(occupied_dev, c.n_rays * g.Sc, c.num_levels == 2 ? c.n_rays * g.Sf : 0, c.stream), who); r2 != AON_OK) return r2;
     if (stop_dev)
-      for (int l = 0; l < num_levels; ++l)
-        if (int r2 = check(aon::launch_occ_stop_store(nullptr, g.S(l), stop_dev + l, n_rays, 2, stream), who); r2 != AON_OK) return r2;
+      for (int l = 0; l < c.num_levels; ++l)
+        if (int r2 = check(aon::launch_occ_stop_store(nullptr, g.S(l), stop_dev + l, c.n_rays, 2, c.stream), who); r2 != AON_OK) return r2;
     return AON_OK;
   }
   ctx.rounds = true;
   ctx.tau_stop = (float)(-std::log((double)eps));   // fp64, rounded once
   ctx.R = round_samples;
   ctx.stop_dev = stop_dev;
-  return render_impl(who, c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c,
-                     rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, opts, &ctx, bounds);
+  return render_impl(who, nets.c, nets.f, c, &ctx);
+}
+
+// ---- the exported whole-path forwards: each lists its parameters once (the ABI) and builds the call record ----
+int aon_render_fwd_ex(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                      const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                      const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                      float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                      const aon_render_opts* opts) {
+  const Nets nets = vanilla_nets(packed_coarse, packed_fine);
+  return render_impl("aon_render_fwd", nets.c, nets.f,
+                     path_call(rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f,
+                               acc_f, depth_f, workspace, workspace_bytes, stream, opts));
+}
+int aon_render_fwd(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                   const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                   const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                   float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream) {
+  return aon_render_fwd_ex(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
+                           u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, nullptr);
+}
+int aon_render_fwd_occ(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                       const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                       const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                       float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                       const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev) {
+  return render_stop("aon_render_fwd_occ", vanilla_nets(packed_coarse, packed_fine),
+                     path_call(rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f,
+                               acc_f, depth_f, workspace, workspace_bytes, stream, opts),
+                     occ, occupied_dev, 0.f, 1, nullptr, true);
 }
 int aon_render_fwd_stop(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
                         const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
@@ -376,10 +363,23 @@ int aon_render_fwd_stop(const void* packed_coarse, const void* packed_fine, cons
                         float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
                         const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev, float eps, int round_samples,
                         int32_t* stop_dev) {
-  const NetRef c{false, packed_coarse, nullptr}, f{false, packed_fine, nullptr};
-  return render_stop("aon_render_fwd_stop", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c,
-                     acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, occ, occupied_dev, eps,
-                     round_samples, stop_dev);
+  return render_stop("aon_render_fwd_stop", vanilla_nets(packed_coarse, packed_fine),
+                     path_call(rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f,
+                               acc_f, depth_f, workspace, workspace_bytes, stream, opts),
+                     occ, occupied_dev, eps, round_samples, stop_dev);
+}
+// per-ray near / far (NeRF.forward / NeRF_AE_Art.forward called with the (N, 1) tensors of helper.get_ray_limits,
+// model.py:147-160, model_autodecoder.py:278-291); bounds == NULL is the _stop call
+int aon_render_fwd_bounds(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
+                          const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
+                          const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                          float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                          const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev, float eps, int round_samples,
+                          int32_t* stop_dev, const aon_ray_bounds* bounds) {
+  return render_stop(bounds ? "aon_render_fwd_bounds" : "aon_render_fwd_stop", vanilla_nets(packed_coarse, packed_fine),
+                     path_call(rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f,
+                               acc_f, depth_f, workspace, workspace_bytes, stream, opts, bounds),
+                     occ, occupied_dev, eps, round_samples, stop_dev);
 }
 
 int aon_art_render_fwd_ex(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
@@ -387,34 +387,10 @@ int aon_art_render_fwd_ex(const void* packed_coarse, const void* small_coarse, c
                           int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
                           float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
                           int64_t workspace_bytes, void* stream, const aon_render_opts* opts) {
-  const NetRef c{true, packed_coarse, static_cast<const float*>(small_coarse)}, f{true, packed_fine, static_cast<const float*>(small_fine)};
-  return render_impl("aon_art_render_fwd", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
-                     u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts);
-}
-int aon_art_render_fwd_occ(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
-                           const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
-                           int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
-                           float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
-                           int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
-                           int64_t* occupied_dev) {
-  OccCtx ctx{};
-  if (const char* bad = occ_grid_bad(occ, ctx.grid)) return fail(AON_E_INVALID, (std::string("aon_art_render_fwd_occ: ") + bad).c_str());
-  if (const char* bad = occ_opts_bad(opts, true, t_rand)) return fail(AON_E_INVALID, (std::string("aon_art_render_fwd_occ: ") + bad).c_str());
-  ctx.tally = occupied_dev;
-  const NetRef c{true, packed_coarse, static_cast<const float*>(small_coarse)}, f{true, packed_fine, static_cast<const float*>(small_fine)};
-  return render_impl("aon_art_render_fwd_occ", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
-                     u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, &ctx);
-}
-int aon_art_render_fwd_stop(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
-                            const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
-                            int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
-                            float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
-                            int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
-                            int64_t* occupied_dev, float eps, int round_samples, int32_t* stop_dev) {
-  const NetRef c{true, packed_coarse, static_cast<const float*>(small_coarse)}, f{true, packed_fine, static_cast<const float*>(small_fine)};
-  return render_stop("aon_art_render_fwd_stop", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride,
-                     rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream, opts, occ, occupied_dev, eps,
-                     round_samples, stop_dev);
+  const Nets nets = art_nets(packed_coarse, small_coarse, packed_fine, small_fine);
+  return render_impl("aon_art_render_fwd", nets.c, nets.f,
+                     path_call(rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f,
+                               acc_f, depth_f, workspace, workspace_bytes, stream, opts));
 }
 int aon_art_render_fwd(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
                        const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
@@ -425,20 +401,27 @@ int aon_art_render_fwd(const void* packed_coarse, const void* small_coarse, cons
                                num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream,
                                nullptr);
 }
-
-
-// ---- per-ray near / far (NeRF.forward / NeRF_AE_Art.forward called with the (N, 1) tensors of
-// helper.get_ray_limits, model.py:147-160, model_autodecoder.py:278-291) ----
-int aon_render_fwd_bounds(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
-                          const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
-                          const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
-                          float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
-                          const aon_render_opts* opts, const aon_occupancy* occ, int64_t* occupied_dev, float eps, int round_samples,
-                          int32_t* stop_dev, const aon_ray_bounds* bounds) {
-  const NetRef c{false, packed_coarse, nullptr}, f{false, packed_fine, nullptr};
-  return render_stop(bounds ? "aon_render_fwd_bounds" : "aon_render_fwd_stop", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd,
-                     num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, (hipStream_t)stream,
-                     opts, occ, occupied_dev, eps, round_samples, stop_dev, bounds);
+int aon_art_render_fwd_occ(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                           const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                           int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                           float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                           int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
+                           int64_t* occupied_dev) {
+  return render_stop("aon_art_render_fwd_occ", art_nets(packed_coarse, small_coarse, packed_fine, small_fine),
+                     path_call(rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f,
+                               acc_f, depth_f, workspace, workspace_bytes, stream, opts),
+                     occ, occupied_dev, 0.f, 1, nullptr, true);
+}
+int aon_art_render_fwd_stop(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                            const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                            int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                            float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                            int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
+                            int64_t* occupied_dev, float eps, int round_samples, int32_t* stop_dev) {
+  return render_stop("aon_art_render_fwd_stop", art_nets(packed_coarse, small_coarse, packed_fine, small_fine),
+                     path_call(rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f,
+                               acc_f, depth_f, workspace, workspace_bytes, stream, opts),
+                     occ, occupied_dev, eps, round_samples, stop_dev);
 }
 int aon_art_render_fwd_bounds(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
                               const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
@@ -446,10 +429,10 @@ int aon_art_render_fwd_bounds(const void* packed_coarse, const void* small_coars
                               float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
                               int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_occupancy* occ,
                               int64_t* occupied_dev, float eps, int round_samples, int32_t* stop_dev, const aon_ray_bounds* bounds) {
-  const NetRef c{true, packed_coarse, static_cast<const float*>(small_coarse)}, f{true, packed_fine, static_cast<const float*>(small_fine)};
-  return render_stop(bounds ? "aon_art_render_fwd_bounds" : "aon_art_render_fwd_stop", c, f, rays_o, rays_d, viewdirs, n_rays, near_, far_,
-                     white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes,
-                     (hipStream_t)stream, opts, occ, occupied_dev, eps, round_samples, stop_dev, bounds);
+  return render_stop(bounds ? "aon_art_render_fwd_bounds" : "aon_art_render_fwd_stop", art_nets(packed_coarse, small_coarse, packed_fine, small_fine),
+                     path_call(rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f,
+                               acc_f, depth_f, workspace, workspace_bytes, stream, opts, bounds),
+                     occ, occupied_dev, eps, round_samples, stop_dev);
 }
 
 }  // extern "C"

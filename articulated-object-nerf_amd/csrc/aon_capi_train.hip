@@ -214,31 +214,33 @@ struct TrainNet {   // one level's network handles
   const void* packed_fwd; const float* small; const void* packed_bwd;
 };
 
-int train_fwd_impl(const char* who, bool art, const TrainNet* nets, const float* rays_o, const float* rays_d, const float* viewdirs,
-                   int64_t n, float near_, float far_, int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride,
-                   float* const* rgb, float* const* acc, float* const* depth, void* workspace, int64_t workspace_bytes, hipStream_t stream,
-                   const aon_render_opts* opts, const aon_ray_bounds* bounds = nullptr) {
+int train_fwd_impl(const char* who, bool art, const TrainNet* nets, const PathCall& c) {
+  auto bad = [&](const char* what) { return fail(AON_E_INVALID, (std::string(who) + ": " + what).c_str()); };
   // [per-ray bounds, DESIGN.md section 4.11] level 0's t from near_ray / far_ray; the backward reads t from the workspace and does not change
-  if (bounds && (!bounds->near_ray || !bounds->far_ray)) return fail(AON_E_INVALID, (std::string(who) + ": null near_ray / far_ray in bounds").c_str());
-  if (bounds && bounds->live) return fail(AON_E_INVALID, (std::string(who) + ": ray_live is inference only (bounds->live must be NULL)").c_str());
-  const float* near_ray = bounds ? bounds->near_ray : nullptr;
-  const float* far_ray = bounds ? bounds->far_ray : nullptr;
+  if (c.bounds && c.bounds->live) return bad("ray_live is inference only (bounds->live must be NULL)");
   Geo g;
-  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
-  if (g.Sf > 512) return fail(AON_E_INVALID, "train forward: more than 512 samples per ray at the fine level");
+  if (const char* msg = make_geo(c.opts, g)) return fail(AON_E_INVALID, msg);
+  if (g.Sf > 512) return bad("more than 512 samples per ray at the fine level");
   if (art) g.other_degrees = false;   // (as in render_impl: no stage-kernel encodings for the articulated network)
-  if (n <= 0 || (num_levels != 1 && num_levels != 2)) return fail(AON_E_INVALID, "train forward: bad size / num_levels");
-  if (!rays_o || !rays_d || !viewdirs || !workspace) return fail(AON_E_INVALID, "train forward: null pointer");
-  if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(AON_E_INVALID, "train forward: workspace must be 256-byte aligned");
-  const TrainWs w = carve_train(static_cast<char*>(workspace), n, art, num_levels, g);
-  if (w.bytes > workspace_bytes) return fail(AON_E_WORKSPACE, "train forward: workspace smaller than aon_train_workspace_bytes()");
-  if (num_levels == 2 && (!u || (u_stride != 0 && u_stride < g.nf))) return fail(AON_E_INVALID, "train forward: bad u / u_stride");
+  if (int rc = path_call_check(who, c, g, false)) return rc;
+  // (the record's fields under the names the schedules below use)
+  const float* near_ray = c.bounds ? c.bounds->near_ray : nullptr;
+  const float* far_ray = c.bounds ? c.bounds->far_ray : nullptr;
+  const float* rays_o = c.rays_o; const float* rays_d = c.rays_d; const float* viewdirs = c.viewdirs;
+  const float* t_rand = c.t_rand; const float* u = c.u;
+  const int64_t n = c.n_rays, u_stride = c.u_stride;
+  const int num_levels = c.num_levels, white_bkgd = c.white_bkgd;
+  const float near_ = c.near_, far_ = c.far_;
+  float* const* rgb = c.rgb; float* const* acc = c.acc; float* const* depth = c.depth;
+  const hipStream_t stream = c.stream;
+  const TrainWs w = carve_train(static_cast<char*>(c.workspace), n, art, num_levels, g);
+  if (w.bytes > c.workspace_bytes) return fail(AON_E_WORKSPACE, (std::string(who) + ": workspace smaller than aon_train_workspace_bytes()").c_str());
   const bool fuse = num_levels == 2 && g.default_sizes && g_fuse_coarse.load(std::memory_order_relaxed) != 0;
   for (int l = 0; l < num_levels; ++l)
-    if (!nets[l].packed_fwd || (art && !nets[l].small) || !rgb[l] || !acc[l] || !depth[l]) return fail(AON_E_INVALID, "train forward: null level pointer");
+    if (!nets[l].packed_fwd || (art && !nets[l].small)) return bad("null level pointer");
   for (int l = 0; l < num_levels; ++l)
     if ((art && forms_differ(nets[l].packed_fwd, nets[l].small)) || forms_differ(nets[l].packed_fwd, nets[0].packed_fwd))
-      return fail(AON_E_INVALID, "train forward: the levels' streams / per-call blocks were made in different forms (aon_set_bottleneck_fold changed in between)");
+      return bad("the levels' streams / per-call blocks were made in different forms (aon_set_bottleneck_fold changed in between)");
   const int64_t rows = art ? aon::kAPlRows : aon::kPlRows;
   // the view-encoding term of the first view layer as a per-ray bias (aon_set_view_bias): both levels' biases of the whole batch up front
   const bool use_vb = !g.other_degrees && g_view_bias.load(std::memory_order_relaxed) != 0 && aon::stream_form(nets[0].packed_fwd) == aon::kFormFolded;
@@ -595,34 +597,44 @@ int aon_set_fwd_overlap(int on) {
   return AON_OK;
 }
 
-int64_t aon_train_workspace_bytes_ex(int64_t n_rays, int articulated, int num_levels, const aon_render_opts* opts) {
-  if (n_rays < 1) n_rays = 1;
+// the workspace-size queries: the forward's workspace or the backward's scratch for n_rays (at least one) of the levels in use
+static int64_t train_bytes_query(int64_t n_rays, int articulated, int num_levels, const aon_render_opts* opts, bool scratch) {
   Geo g;
   if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
-  return carve_train(nullptr, n_rays, articulated != 0, num_levels == 1 ? 1 : 2, g).bytes;
+  if (n_rays < 1) n_rays = 1;
+  const int levels = num_levels == 1 ? 1 : 2;
+  return scratch ? carve_scratch(nullptr, n_rays, articulated != 0, levels, g).bytes : carve_train(nullptr, n_rays, articulated != 0, levels, g).bytes;
+}
+int64_t aon_train_workspace_bytes_ex(int64_t n_rays, int articulated, int num_levels, const aon_render_opts* opts) {
+  return train_bytes_query(n_rays, articulated, num_levels, opts, false);
 }
 int64_t aon_train_workspace_bytes(int64_t n_rays, int articulated, int num_levels) {
   return aon_train_workspace_bytes_ex(n_rays, articulated, num_levels, nullptr);
 }
-
 int64_t aon_train_scratch_bytes_ex(int64_t n_rays, int articulated, int num_levels, const aon_render_opts* opts) {
-  if (n_rays < 1) n_rays = 1;
-  Geo g;
-  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
-  return carve_scratch(nullptr, n_rays, articulated != 0, num_levels == 1 ? 1 : 2, g).bytes;
+  return train_bytes_query(n_rays, articulated, num_levels, opts, true);
 }
 int64_t aon_train_scratch_bytes(int64_t n_rays, int articulated, int num_levels) {
   return aon_train_scratch_bytes_ex(n_rays, articulated, num_levels, nullptr);
 }
 
+// ---- the exported training forwards: each lists its parameters once (the ABI) and builds the call record; _ex is _bounds without bounds ----
+// per-ray near / far under grad mode: DESIGN.md section 4.11; model.py:147-160, model_autodecoder.py:278-291 with (N, 1) tensors
+int aon_render_fwd_train_bounds(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels, const float* t_rand, const float* u,
+                                int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f,
+                                void* workspace, int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_ray_bounds* bounds) {
+  const TrainNet nets[2] = {{packed_coarse, nullptr, nullptr}, {packed_fine, nullptr, nullptr}};
+  return train_fwd_impl(bounds ? "aon_render_fwd_train_bounds" : "aon_render_fwd_train", false, nets,
+                        path_call(rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f,
+                                  acc_f, depth_f, workspace, workspace_bytes, stream, opts, bounds));
+}
 int aon_render_fwd_train_ex(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d, const float* viewdirs,
                             int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels, const float* t_rand, const float* u,
                             int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f,
                             void* workspace, int64_t workspace_bytes, void* stream, const aon_render_opts* opts) {
-  const TrainNet nets[2] = {{packed_coarse, nullptr, nullptr}, {packed_fine, nullptr, nullptr}};
-  float* const rgb[2] = {rgb_c, rgb_f}; float* const acc[2] = {acc_c, acc_f}; float* const dep[2] = {depth_c, depth_f};
-  return train_fwd_impl("aon_render_fwd_train", false, nets, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
-                        u_stride, rgb, acc, dep, workspace, workspace_bytes, (hipStream_t)stream, opts);
+  return aon_render_fwd_train_bounds(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
+                                     u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, opts, nullptr);
 }
 int aon_render_fwd_train(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d, const float* viewdirs,
                          int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels, const float* t_rand, const float* u,
@@ -632,15 +644,24 @@ int aon_render_fwd_train(const void* packed_coarse, const void* packed_fine, con
                                  u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes, stream, nullptr);
 }
 
+int aon_art_render_fwd_train_bounds(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
+                                    const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
+                                    int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
+                                    float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
+                                    int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_ray_bounds* bounds) {
+  const TrainNet nets[2] = {{packed_coarse, static_cast<const float*>(small_coarse), nullptr}, {packed_fine, static_cast<const float*>(small_fine), nullptr}};
+  return train_fwd_impl(bounds ? "aon_art_render_fwd_train_bounds" : "aon_art_render_fwd_train", true, nets,
+                        path_call(rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f,
+                                  acc_f, depth_f, workspace, workspace_bytes, stream, opts, bounds));
+}
 int aon_art_render_fwd_train_ex(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
                                 const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
                                 int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
                                 float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
                                 int64_t workspace_bytes, void* stream, const aon_render_opts* opts) {
-  const TrainNet nets[2] = {{packed_coarse, static_cast<const float*>(small_coarse), nullptr}, {packed_fine, static_cast<const float*>(small_fine), nullptr}};
-  float* const rgb[2] = {rgb_c, rgb_f}; float* const acc[2] = {acc_c, acc_f}; float* const dep[2] = {depth_c, depth_f};
-  return train_fwd_impl("aon_art_render_fwd_train", true, nets, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u,
-                        u_stride, rgb, acc, dep, workspace, workspace_bytes, (hipStream_t)stream, opts);
+  return aon_art_render_fwd_train_bounds(packed_coarse, small_coarse, packed_fine, small_fine, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd,
+                                         num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes,
+                                         stream, opts, nullptr);
 }
 int aon_art_render_fwd_train(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
                              const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
@@ -650,27 +671,6 @@ int aon_art_render_fwd_train(const void* packed_coarse, const void* small_coarse
   return aon_art_render_fwd_train_ex(packed_coarse, small_coarse, packed_fine, small_fine, rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd,
                                      num_levels, t_rand, u, u_stride, rgb_c, acc_c, depth_c, rgb_f, acc_f, depth_f, workspace, workspace_bytes,
                                      stream, nullptr);
-}
-
-// per-ray near / far under grad mode (model.py:147-160, model_autodecoder.py:278-291 with (N, 1) tensors)
-int aon_render_fwd_train_bounds(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d, const float* viewdirs,
-                                int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels, const float* t_rand, const float* u,
-                                int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f,
-                                void* workspace, int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_ray_bounds* bounds) {
-  const TrainNet nets[2] = {{packed_coarse, nullptr, nullptr}, {packed_fine, nullptr, nullptr}};
-  float* const rgb[2] = {rgb_c, rgb_f}; float* const acc[2] = {acc_c, acc_f}; float* const dep[2] = {depth_c, depth_f};
-  return train_fwd_impl(bounds ? "aon_render_fwd_train_bounds" : "aon_render_fwd_train", false, nets, rays_o, rays_d, viewdirs, n_rays, near_, far_,
-                        white_bkgd, num_levels, t_rand, u, u_stride, rgb, acc, dep, workspace, workspace_bytes, (hipStream_t)stream, opts, bounds);
-}
-int aon_art_render_fwd_train_bounds(const void* packed_coarse, const void* small_coarse, const void* packed_fine, const void* small_fine,
-                                    const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_,
-                                    int white_bkgd, int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c,
-                                    float* acc_c, float* depth_c, float* rgb_f, float* acc_f, float* depth_f, void* workspace,
-                                    int64_t workspace_bytes, void* stream, const aon_render_opts* opts, const aon_ray_bounds* bounds) {
-  const TrainNet nets[2] = {{packed_coarse, static_cast<const float*>(small_coarse), nullptr}, {packed_fine, static_cast<const float*>(small_fine), nullptr}};
-  float* const rgb[2] = {rgb_c, rgb_f}; float* const acc[2] = {acc_c, acc_f}; float* const dep[2] = {depth_c, depth_f};
-  return train_fwd_impl(bounds ? "aon_art_render_fwd_train_bounds" : "aon_art_render_fwd_train", true, nets, rays_o, rays_d, viewdirs, n_rays, near_,
-                        far_, white_bkgd, num_levels, t_rand, u, u_stride, rgb, acc, dep, workspace, workspace_bytes, (hipStream_t)stream, opts, bounds);
 }
 
 int aon_render_bwd(const void* packed_bwd_coarse, const void* packed_fwd_coarse, const void* packed_bwd_fine, const void* packed_fwd_fine,

@@ -107,5 +107,42 @@ struct Geo {
 // caller who fills them to match a (1, 12, 5) geometry used to get AON_E_INVALID from the general engine: ADVICE r3).
 const char* make_geo(const aon_render_opts* o, Geo& g, bool general_engine = false);
 
+// The call record of the whole-path forward entry points: what aon_render_fwd* / aon_art_render_fwd* /
+// aon_*render_fwd_train* / aon_grender_fwd* have in common.  An exported function lists its parameters once -- that list is the ABI --
+// builds the record with path_call() and passes the record on; nothing behind it takes those parameters by position again.
+struct PathCall {
+  const float* rays_o; const float* rays_d; const float* viewdirs; int64_t n_rays;
+  float near_, far_; int white_bkgd, num_levels;
+  const float* t_rand; const float* u; int64_t u_stride;
+  float* rgb[2]; float* acc[2]; float* depth[2];   // per level
+  void* workspace; int64_t workspace_bytes; hipStream_t stream;
+  const aon_render_opts* opts;
+  const aon_ray_bounds* bounds;   // per-ray near / far / live or null
+};
+// (the one function that takes the ABI's list: in the exported functions' order, so a call site reads as its own parameter list)
+inline PathCall path_call(const float* rays_o, const float* rays_d, const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd,
+                          int num_levels, const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,
+                          float* rgb_f, float* acc_f, float* depth_f, void* workspace, int64_t workspace_bytes, void* stream,
+                          const aon_render_opts* opts, const aon_ray_bounds* bounds = nullptr) {
+  return PathCall{rays_o, rays_d, viewdirs, n_rays, near_, far_, white_bkgd, num_levels, t_rand, u, u_stride, {rgb_c, rgb_f}, {acc_c, acc_f},
+                  {depth_c, depth_f}, workspace, workspace_bytes, static_cast<hipStream_t>(stream), opts, bounds};
+}
+
+// The pointer / size checks every whole-path forward makes, before any launch: AON_OK, a failure code (the text carries `who`), or
+// kPathEmpty for a call without rays where the entry point takes that as a successful no-op (`empty_ok`; the training forwards refuse it).
+// The network handles are the caller's to check.
+constexpr int kPathEmpty = 1;
+inline int path_call_check(const char* who, const PathCall& c, const Geo& g, bool empty_ok) {
+  auto bad = [&](const char* what) { return fail(AON_E_INVALID, (std::string(who) + ": " + what).c_str()); };
+  if (c.n_rays < 0 || (c.n_rays == 0 && !empty_ok) || (c.num_levels != 1 && c.num_levels != 2)) return bad("bad size / num_levels");
+  if (c.n_rays == 0) return kPathEmpty;
+  if (!c.rays_o || !c.rays_d || !c.viewdirs || !c.rgb[0] || !c.acc[0] || !c.depth[0] || !c.workspace) return bad("null pointer");
+  if (c.num_levels == 2 && (!c.rgb[1] || !c.acc[1] || !c.depth[1] || !c.u)) return bad("null fine-level pointer");
+  if (c.num_levels == 2 && c.u_stride != 0 && c.u_stride < g.nf) return bad("bad u_stride");
+  if (reinterpret_cast<uintptr_t>(c.workspace) & 255) return bad("workspace must be 256-byte aligned");
+  if (c.bounds && (!c.bounds->near_ray || !c.bounds->far_ray)) return bad("null near_ray / far_ray in bounds");
+  return AON_OK;
+}
+
 }  // namespace capi
 }  // namespace aon

@@ -628,35 +628,58 @@ def _check_noise(noise, n, op, num_levels):
     return out
 
 
+def _level_outs(n, dev, num_levels):
+    outs = [(torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.float32, device=dev),
+             torch.empty((n,), dtype=torch.float32, device=dev)) for _ in range(num_levels)]
+    return outs, (outs[1] if num_levels == 2 else (None, None, None))
+
+
+class _PathCall:
+    """The prologue of every whole-path forward, and the Python side of csrc/aon_capi_util.h's PathCall: the
+    conversions and shape checks of the common arguments, the per-level outputs and the aon_render_opts struct.  `args(ws)` is the C
+    argument list from rays_o up to and including opts, the same for every form; a call is `getattr(lib, name)(*packs, *pc.args(ws),
+    *extra)`.  The object holds every tensor those pointers refer to: keep it until the call has returned.
+    ``per_ray``: the caller takes near / far tensors (and a `ray_live` mask) -> `bounds` is the aon_ray_bounds struct or None."""
+
+    def __init__(self, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, opts, noise, per_ray=False, ray_live=None):
+        o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
+        self.n, self.dev = n, dev = o.shape[0], o.device
+        self.op = op = _opts(opts)
+        near, far, self.bounds, bkeep = _ray_bounds(near, far, n, dev, ray_live) if per_ray else (float(near), float(far), None, ())
+        tr = None if t_rand is None else _f32(t_rand, "t_rand")
+        if tr is not None and tuple(tr.shape) != (n, op.Sc):
+            raise ValueError(f"t_rand must be ({n},{op.Sc})")
+        self.uu, us = _u_args(u, n, dev, op.num_fine_samples) if num_levels == 2 else (None, 0)
+        self.outs, fine = _level_outs(n, dev, num_levels)
+        self.st, self.noise_keep = op.c_struct(near, far, _check_noise(noise, n, op, num_levels))
+        self._keep = (o, d, v, tr, bkeep)
+        self._head = (_ptr(o), _ptr(d), _ptr(v), n, float(near), float(far), int(bool(white_bkgd)), num_levels, _ptr(tr), _ptr(self.uu), us,
+                      *(_ptr(x) for x in self.outs[0]), *(_ptr(x) for x in fine))
+
+    def args(self, ws):
+        return (*self._head, _ptr(ws), ws.numel(), _stream(), C.byref(self.st))
+
+
+def _render_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, opts, noise, ray_live, workspace_bytes):
+    """render_fwd / art_render_fwd: `name` is the C stem ("aon_render_fwd" / "aon_art_render_fwd"), `packs` its network pointers."""
+    if isinstance(near, torch.Tensor) or isinstance(far, torch.Tensor) or ray_live is not None:
+        return _stop_call(name + "_stop", packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, None, 0.0, None, num_levels, u, opts, workspace_bytes,
+                          t_rand=t_rand, noise=noise, ray_live=ray_live, want_stats=False)[0]
+    pc = _PathCall(rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, opts, noise)
+    ws = _workspace(pc.dev, pc.n, pc.st)
+    with torch.cuda.device(pc.dev):
+        check(getattr(lib, name + "_ex")(*packs, *pc.args(ws)), name)
+    return pc.outs
+
+
 def render_fwd(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels=2, t_rand=None, u=None,
                opts=None, noise=None, ray_live=None, workspace_bytes=None):
     """NeRF.forward: returns [(rgb, acc, depth)_coarse, (rgb, acc, depth)_fine] (fine omitted if num_levels == 1).
     ``opts`` (RenderOpts): non-default sample counts / lindisp / noise_std; ``noise``: per-level (n,S) uniform draws.
     ``near`` / ``far``: numbers, or per-ray tensors of N elements; ``ray_live`` (N,) uint8: dead rays run no MLP and composite to the
     background (inference only)."""
-    if isinstance(near, torch.Tensor) or isinstance(far, torch.Tensor) or ray_live is not None:
-        return _stop_call("aon_render_fwd_stop", (_pk(packed_coarse), _pk(packed_fine)), rays_o, rays_d, viewdirs, near, far, white_bkgd, None, 0.0,
-                          None, num_levels, u, opts, workspace_bytes, t_rand=t_rand, noise=noise, ray_live=ray_live, want_stats=False)[0]
-    o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
-    n, dev = o.shape[0], o.device
-    op = _opts(opts)
-    tr = None if t_rand is None else _f32(t_rand, "t_rand")
-    if tr is not None and tuple(tr.shape) != (n, op.Sc):
-        raise ValueError(f"t_rand must be ({n},{op.Sc})")
-    uu, us = _u_args(u, n, dev, op.num_fine_samples) if num_levels == 2 else (None, 0)
-    outs = []
-    for _ in range(num_levels):
-        outs.append((torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.float32, device=dev),
-                     torch.empty((n,), dtype=torch.float32, device=dev)))
-    fine = outs[1] if num_levels == 2 else (None, None, None)
-    st, keep = op.c_struct(near, far, _check_noise(noise, n, op, num_levels))
-    ws = _workspace(dev, n, st)
-    with torch.cuda.device(dev):
-        check(lib.aon_render_fwd_ex(_pk(packed_coarse), _pk(packed_fine), _ptr(o), _ptr(d), _ptr(v), n, float(near), float(far),
-                                    int(bool(white_bkgd)), num_levels, _ptr(tr), _ptr(uu), us,
-                                    _ptr(outs[0][0]), _ptr(outs[0][1]), _ptr(outs[0][2]), _ptr(fine[0]), _ptr(fine[1]), _ptr(fine[2]),
-                                    _ptr(ws), ws.numel(), _stream(), C.byref(st)), "aon_render_fwd")
-    return outs
+    return _render_call("aon_render_fwd", (_pk(packed_coarse), _pk(packed_fine)), rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u,
+                        opts, noise, ray_live, workspace_bytes)
 
 
 # ------------------------------------------------------------------ R10/R11 articulated network
@@ -825,30 +848,8 @@ def art_mlp_fwd_pos(packed, small, pos, viewdirs_enc):
 def art_render_fwd(packed_c, small_c, packed_f, small_f, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels=2,
                    t_rand=None, u=None, opts=None, noise=None, ray_live=None, workspace_bytes=None):
     """NeRF_AE_Art.forward: [(rgb, acc, depth)_coarse, (rgb, acc, depth)_fine].  Per-ray ``near`` / ``far`` / ``ray_live``: as render_fwd."""
-    if isinstance(near, torch.Tensor) or isinstance(far, torch.Tensor) or ray_live is not None:
-        return _stop_call("aon_art_render_fwd_stop", (_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f)), rays_o, rays_d, viewdirs, near, far,
-                          white_bkgd, None, 0.0, None, num_levels, u, opts, workspace_bytes, t_rand=t_rand, noise=noise, ray_live=ray_live,
-                          want_stats=False)[0]
-    o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
-    n, dev = o.shape[0], o.device
-    op = _opts(opts)
-    tr = None if t_rand is None else _f32(t_rand, "t_rand")
-    if tr is not None and tuple(tr.shape) != (n, op.Sc):
-        raise ValueError(f"t_rand must be ({n},{op.Sc})")
-    uu, us = _u_args(u, n, dev, op.num_fine_samples) if num_levels == 2 else (None, 0)
-    outs = []
-    for _ in range(num_levels):
-        outs.append((torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.float32, device=dev),
-                     torch.empty((n,), dtype=torch.float32, device=dev)))
-    fine = outs[1] if num_levels == 2 else (None, None, None)
-    st, keep = op.c_struct(near, far, _check_noise(noise, n, op, num_levels))
-    ws = _workspace(dev, n, st)
-    with torch.cuda.device(dev):
-        check(lib.aon_art_render_fwd_ex(_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f), _ptr(o), _ptr(d), _ptr(v), n,
-                 float(near), float(far), int(bool(white_bkgd)), num_levels, _ptr(tr), _ptr(uu), us,
-                 _ptr(outs[0][0]), _ptr(outs[0][1]), _ptr(outs[0][2]), _ptr(fine[0]), _ptr(fine[1]), _ptr(fine[2]),
-                 _ptr(ws), ws.numel(), _stream(), C.byref(st)), "aon_art_render_fwd")
-    return outs
+    return _render_call("aon_art_render_fwd", (_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f)), rays_o, rays_d, viewdirs, near, far, white_bkgd,
+                        num_levels, t_rand, u, opts, noise, ray_live, workspace_bytes)
 
 
 # ------------------------------------------------------------------ R14 training (vanilla)
@@ -1136,42 +1137,20 @@ def train_scratch(device, n_rays: int, articulated: bool, num_levels: int = 2, s
                       "aon_train_scratch_bytes_ex", device)
 
 
-def _level_outs(n, dev, num_levels):
-    outs = [(torch.empty((n, 3), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.float32, device=dev),
-             torch.empty((n,), dtype=torch.float32, device=dev)) for _ in range(num_levels)]
-    return outs, (outs[1] if num_levels == 2 else (None, None, None))
-
-
 def render_fwd_train(packed_c, packed_f, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, small_c=None, small_f=None,
                      opts=None, noise=None):
     """NeRF.forward / NeRF_AE_Art.forward (small blocks given) under grad mode in ONE C call -> (outs, workspace, geometry).
     ``geometry`` = (aon_render_opts struct, tensors it points at): the backward of this forward must be given the same one."""
-    o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
-    n, dev = o.shape[0], o.device
     art = small_c is not None
-    op = _opts(opts)
-    tr = None if t_rand is None else _f32(t_rand, "t_rand")
-    if tr is not None and tuple(tr.shape) != (n, op.Sc):
-        raise ValueError(f"t_rand must be ({n},{op.Sc})")
-    uu, us = _u_args(u, n, dev, op.num_fine_samples) if num_levels == 2 else (None, 0)
-    outs, fine = _level_outs(n, dev, num_levels)
-    near, far, bounds, bkeep = _ray_bounds(near, far, n, dev)     # per-ray near / far: non-differentiable data (DESIGN.md section 4.11)
-    st, keep = op.c_struct(near, far, _check_noise(noise, n, op, num_levels))
-    ws = train_workspace(dev, n, art, num_levels, st)
-    common = (_ptr(o), _ptr(d), _ptr(v), n, float(near), float(far), int(bool(white_bkgd)), num_levels, _ptr(tr), _ptr(uu), us,
-              _ptr(outs[0][0]), _ptr(outs[0][1]), _ptr(outs[0][2]), _ptr(fine[0]), _ptr(fine[1]), _ptr(fine[2]), _ptr(ws), ws.numel(), _stream(),
-              C.byref(st))
-    with torch.cuda.device(dev):
-        if bounds is not None and art:
-            check(lib.aon_art_render_fwd_train_bounds(_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f), *common, C.byref(bounds)),
-                  "aon_art_render_fwd_train_bounds")
-        elif bounds is not None:
-            check(lib.aon_render_fwd_train_bounds(_pk(packed_c), _pk(packed_f), *common, C.byref(bounds)), "aon_render_fwd_train_bounds")
-        elif art:
-            check(lib.aon_art_render_fwd_train_ex(_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f), *common), "aon_art_render_fwd_train")
-        else:
-            check(lib.aon_render_fwd_train_ex(_pk(packed_c), _pk(packed_f), *common), "aon_render_fwd_train")
-    return outs, ws, (st, keep)
+    # per-ray near / far: non-differentiable data (DESIGN.md section 4.11)
+    pc = _PathCall(rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, opts, noise, per_ray=True)
+    ws = train_workspace(pc.dev, pc.n, art, num_levels, pc.st)
+    packs = (_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f)) if art else (_pk(packed_c), _pk(packed_f))
+    stem = "aon_art_render_fwd_train" if art else "aon_render_fwd_train"
+    name, extra = (stem + "_ex", ()) if pc.bounds is None else (stem + "_bounds", (C.byref(pc.bounds),))
+    with torch.cuda.device(pc.dev):
+        check(getattr(lib, name)(*packs, *pc.args(ws), *extra), stem if pc.bounds is None else name)
+    return pc.outs, ws, (pc.st, pc.noise_keep)
 
 
 def _grad_dicts(order, shapes, num_levels, dev, grads_out):
@@ -1367,51 +1346,36 @@ def _grender_chunk_rays(gst, st, n: int) -> tuple[int, int]:
         rays = max(128, min(rays // 2, int(rays * G_WS_BUDGET_BYTES / need)))
 
 
-def grender_fwd(geom: MlpGeometry, params_c: dict, params_f, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels=2, t_rand=None, u=None,
-                opts=None, noise=None):
-    """NeRF.forward with a NeRFMLP of any geometry (aon_grender_fwd)."""
-    o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
-    n, dev = o.shape[0], o.device
-    op = _opts(opts)
-    tr = None if t_rand is None else _f32(t_rand, "t_rand")
-    if tr is not None and tuple(tr.shape) != (n, op.Sc):
-        raise ValueError(f"t_rand must be ({n},{op.Sc})")
-    uu, us = _u_args(u, n, dev, op.num_fine_samples) if num_levels == 2 else (None, 0)
-    outs, fine = _level_outs(n, dev, num_levels)
-    st, keep = op.c_struct(near, far, _check_noise(noise, n, op, num_levels))
+def _grender_call(geom: MlpGeometry, params_c: dict, params_f, num_levels):
+    """-> (aon_mlp_geometry struct, the C prefix of the aon_grender_* forwards, the parameter tensors to keep alive)."""
     gst = geom.c_struct()
     tc, arr_c = _gmlp_param_array(geom, params_c)
     tf, arr_f = _gmlp_param_array(geom, params_f) if num_levels == 2 else (None, None)
-    _, need = _grender_chunk_rays(gst, st, n)
-    ws = _scratch(_GWS_CACHE, dev, need)
-    with torch.cuda.device(dev):
-        check(lib.aon_grender_fwd(C.byref(gst), arr_c, arr_f, _ptr(o), _ptr(d), _ptr(v), n, float(near), float(far), int(bool(white_bkgd)), num_levels,
-                                  _ptr(tr), _ptr(uu), us, _ptr(outs[0][0]), _ptr(outs[0][1]), _ptr(outs[0][2]), _ptr(fine[0]), _ptr(fine[1]),
-                                  _ptr(fine[2]), _ptr(ws), ws.numel(), _stream(), C.byref(st)), "aon_grender_fwd")
-    return outs
+    return gst, (C.byref(gst), arr_c, arr_f), (tc, tf)
+
+
+def grender_fwd(geom: MlpGeometry, params_c: dict, params_f, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels=2, t_rand=None, u=None,
+                opts=None, noise=None):
+    """NeRF.forward with a NeRFMLP of any geometry (aon_grender_fwd)."""
+    pc = _PathCall(rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, opts, noise)
+    gst, packs, keep = _grender_call(geom, params_c, params_f, num_levels)
+    _, need = _grender_chunk_rays(gst, pc.st, pc.n)
+    ws = _scratch(_GWS_CACHE, pc.dev, need)
+    with torch.cuda.device(pc.dev):
+        check(lib.aon_grender_fwd(*packs, *pc.args(ws)), "aon_grender_fwd")
+    return pc.outs
 
 
 def grender_fwd_train(geom: MlpGeometry, params_c: dict, params_f, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u,
                       opts=None, noise=None):
     """-> (outs, workspace, geometry): the forward of a training step; the workspace carries every layer's output to the backward."""
-    o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
-    n, dev = o.shape[0], o.device
-    op = _opts(opts)
-    tr = None if t_rand is None else _f32(t_rand, "t_rand")
-    if tr is not None and tuple(tr.shape) != (n, op.Sc):
-        raise ValueError(f"t_rand must be ({n},{op.Sc})")
-    uu, us = _u_args(u, n, dev, op.num_fine_samples) if num_levels == 2 else (None, 0)
-    outs, fine = _level_outs(n, dev, num_levels)
-    st, keep = op.c_struct(near, far, _check_noise(noise, n, op, num_levels))
-    gst = geom.c_struct()
-    tc, arr_c = _gmlp_param_array(geom, params_c)
-    tf, arr_f = _gmlp_param_array(geom, params_f) if num_levels == 2 else (None, None)
-    ws = _pool_take(int(lib.aon_grender_train_workspace_bytes(C.byref(gst), n, num_levels, C.byref(st))), "aon_grender_train_workspace_bytes", dev)   # (pooled: see _TRAIN_POOL)
-    with torch.cuda.device(dev):
-        check(lib.aon_grender_fwd_train(C.byref(gst), arr_c, arr_f, _ptr(o), _ptr(d), _ptr(v), n, float(near), float(far), int(bool(white_bkgd)),
-                                        num_levels, _ptr(tr), _ptr(uu), us, _ptr(outs[0][0]), _ptr(outs[0][1]), _ptr(outs[0][2]), _ptr(fine[0]),
-                                        _ptr(fine[1]), _ptr(fine[2]), _ptr(ws), ws.numel(), _stream(), C.byref(st)), "aon_grender_fwd_train")
-    return outs, ws, (st, keep, uu)
+    pc = _PathCall(rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, opts, noise)
+    gst, packs, keep = _grender_call(geom, params_c, params_f, num_levels)
+    ws = _pool_take(int(lib.aon_grender_train_workspace_bytes(C.byref(gst), pc.n, num_levels, C.byref(pc.st))), "aon_grender_train_workspace_bytes",
+                    pc.dev)   # (pooled: see _TRAIN_POOL)
+    with torch.cuda.device(pc.dev):
+        check(lib.aon_grender_fwd_train(*packs, *pc.args(ws)), "aon_grender_fwd_train")
+    return pc.outs, ws, (pc.st, pc.noise_keep, pc.uu)
 
 
 def grender_bwd(geom: MlpGeometry, ws, params_per_level, rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, geometry):
@@ -1738,42 +1702,14 @@ def occupancy_grid(density, lo, hi, threshold: float = 0.01, dilate: int = 1) ->
 _OCC_WS_CACHE = StreamCache()
 
 
-def _occ_workspace(device, n_rays: int, st, workspace_bytes):
+def _occ_workspace(device, n_rays: int, st, workspace_bytes, query="aon_render_occ_workspace_bytes"):
+    """Workspace of the _occ (`query` as given) / _stop / _bounds forms (query aon_render_stop_workspace_bytes)."""
     if workspace_bytes is not None:   # (tests: a workspace small enough to force chunking)
         return torch.empty(int(workspace_bytes), dtype=torch.uint8, device=device)
-    need = int(lib.aon_render_occ_workspace_bytes(min(n_rays, MAX_CHUNK_RAYS), C.byref(st)))
+    need = int(getattr(lib, query)(min(n_rays, MAX_CHUNK_RAYS), C.byref(st)))
     if need < 0:
-        check(need, "aon_render_occ_workspace_bytes")
+        check(need, query)
     return _scratch(_OCC_WS_CACHE, device, need)
-
-
-def _occ_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, num_levels, u, opts, workspace_bytes, ray_live=None):
-    if not isinstance(grid, OccupancyGrid):
-        raise TypeError(f"{name}: grid must be an ops.OccupancyGrid (ops.occupancy_grid), got {type(grid)}")
-    if isinstance(near, torch.Tensor) or isinstance(far, torch.Tensor) or ray_live is not None:
-        return _stop_call(name.replace("_occ", "_stop"), packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, 0.0, None, num_levels, u, opts,
-                          workspace_bytes, ray_live=ray_live)[:2]
-    if num_levels not in (1, 2):
-        raise ValueError(f"{name}: num_levels must be 1 or 2")
-    o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
-    n, dev = o.shape[0], o.device
-    if grid.device != dev:
-        raise ValueError(f"{name}: the grid is on {grid.device}, the rays on {dev}")
-    op = _opts(opts)
-    if op.noise_std > 0:
-        raise ValueError(f"{name}: inference only, density noise (noise_std > 0) is refused")
-    uu, us = _u_args(u, n, dev, op.num_fine_samples) if num_levels == 2 else (None, 0)
-    outs = [tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in ((n, 3), (n,), (n,))) for _ in range(num_levels)]
-    fine = outs[1] if num_levels == 2 else (None, None, None)
-    st, keep = op.c_struct(near, far)
-    occ = grid.c_struct()
-    occupied = torch.zeros(2, dtype=torch.int64, device=dev)
-    ws = _occ_workspace(dev, n, st, workspace_bytes)
-    with torch.cuda.device(dev):
-        check(getattr(lib, name)(*packs, _ptr(o), _ptr(d), _ptr(v), n, float(near), float(far), int(bool(white_bkgd)), num_levels, None, _ptr(uu), us,
-                                 _ptr(outs[0][0]), _ptr(outs[0][1]), _ptr(outs[0][2]), _ptr(fine[0]), _ptr(fine[1]), _ptr(fine[2]),
-                                 _ptr(ws), ws.numel(), _stream(), C.byref(st), C.byref(occ), _ptr(occupied)), name)
-    return [tuple(x) for x in outs], occupied
 
 
 def render_fwd_occ(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid: OccupancyGrid, num_levels=2, u=None,
@@ -1781,37 +1717,30 @@ def render_fwd_occ(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, near, f
     """render_fwd (inference: no t_rand, no noise) with every sample in an empty cell of `grid` skipped: zero density, no MLP evaluation.
     Returns (levels, occupied): the level tuples of render_fwd, and an int64 (2,) cuda tensor with the samples each level ran through the MLP.
     Per-ray ``near`` / ``far`` / ``ray_live``: as render_fwd."""
-    return _occ_call("aon_render_fwd_occ", (_pk(packed_coarse), _pk(packed_fine)), rays_o, rays_d, viewdirs, near, far, white_bkgd, grid,
-                     num_levels, u, opts, workspace_bytes, ray_live)
+    return _stop_call("aon_render_fwd_occ", (_pk(packed_coarse), _pk(packed_fine)), rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, 0.0, None,
+                      num_levels, u, opts, workspace_bytes, ray_live=ray_live)
 
 
 def art_render_fwd_occ(packed_c, small_c, packed_f, small_f, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid: OccupancyGrid, num_levels=2,
                        u=None, opts=None, workspace_bytes=None, ray_live=None):
     """art_render_fwd with the occupancy skip of render_fwd_occ -> (levels, occupied)."""
-    return _occ_call("aon_art_render_fwd_occ", (_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f)), rays_o, rays_d, viewdirs, near, far,
-                     white_bkgd, grid, num_levels, u, opts, workspace_bytes, ray_live)
+    return _stop_call("aon_art_render_fwd_occ", (_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f)), rays_o, rays_d, viewdirs, near, far,
+                      white_bkgd, grid, 0.0, None, num_levels, u, opts, workspace_bytes, ray_live=ray_live)
 
 
 # ------------------------------------------------------------------ early ray termination (DESIGN.md section 4.10)
 DEFAULT_ROUND_SAMPLES = 48   # measured: DESIGN.md section 4.10
 
 
-def _stop_workspace(device, n_rays: int, st, workspace_bytes):
-    if workspace_bytes is not None:
-        return torch.empty(int(workspace_bytes), dtype=torch.uint8, device=device)
-    need = int(lib.aon_render_stop_workspace_bytes(min(n_rays, MAX_CHUNK_RAYS), C.byref(st)))
-    if need < 0:
-        check(need, "aon_render_stop_workspace_bytes")
-    return _scratch(_OCC_WS_CACHE, device, need)
-
-
 def _stop_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, eps, round_samples, num_levels, u, opts, workspace_bytes,
                t_rand=None, noise=None, ray_live=None, want_stats=True):
-    """``want_stats=False`` (render_fwd / art_render_fwd with per-ray planes): no tally, no stop map -- NULL for both, nothing launched for them.
-    The _stop C calls; with per-ray near / far tensors or a `ray_live` mask, their _bounds forms (which also serve render_fwd /
-    render_fwd_occ with bounds: no grid and eps == 0 without a mask is aon_render_fwd_ex with per-ray planes, t_rand / noise allowed)."""
-    if grid is not None and not isinstance(grid, OccupancyGrid):
-        raise TypeError(f"{name}: grid must be an ops.OccupancyGrid (ops.occupancy_grid) or None, got {type(grid)}")
+    """The _occ / _stop C calls (`name`: which; the _occ form needs a grid, has no eps / round_samples and returns (levels, occupied)); with
+    per-ray near / far tensors or a `ray_live` mask, their common _bounds form (which also serves render_fwd with bounds: no grid and
+    eps == 0 without a mask is aon_render_fwd_ex with per-ray planes, t_rand / noise allowed).
+    ``want_stats=False`` (render_fwd / art_render_fwd with per-ray planes): no tally, no stop map -- NULL for both, nothing launched for them."""
+    occ_form = name.endswith("_occ")
+    if not isinstance(grid, OccupancyGrid) and (occ_form or grid is not None):
+        raise TypeError(f"{name}: grid must be an ops.OccupancyGrid (ops.occupancy_grid){'' if occ_form else ' or None'}, got {type(grid)}")
     if num_levels not in (1, 2):
         raise ValueError(f"{name}: num_levels must be 1 or 2")
     eps = float(eps)
@@ -1820,39 +1749,32 @@ def _stop_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, gri
     R = DEFAULT_ROUND_SAMPLES if round_samples is None else int(round_samples)
     if R < 1:
         raise ValueError(f"{name}: round_samples must be >= 1, got {R}")
-    o, d, v = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs")
-    n, dev = o.shape[0], o.device
+    per_ray = isinstance(near, torch.Tensor) or isinstance(far, torch.Tensor) or ray_live is not None
+    plain = per_ray and grid is None and eps == 0.0 and ray_live is None     # aon_render_fwd_ex with per-ray planes
+    pc = _PathCall(rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, opts, noise if plain else None, per_ray=True,
+                   ray_live=ray_live)
+    n, dev = pc.n, pc.dev
     if grid is not None and grid.device != dev:
         raise ValueError(f"{name}: the grid is on {grid.device}, the rays on {dev}")
-    op = _opts(opts)
-    near, far, bounds, bkeep = _ray_bounds(near, far, n, dev, ray_live)
-    plain = bounds is not None and grid is None and eps == 0.0 and ray_live is None     # aon_render_fwd_ex with per-ray planes
-    if not plain and (op.noise_std > 0 or t_rand is not None):
+    if not plain and (pc.op.noise_std > 0 or t_rand is not None):
         raise ValueError(f"{name}: inference only, density noise (noise_std > 0) and t_rand are refused")
-    tr = None if t_rand is None else _f32(t_rand, "t_rand")
-    if tr is not None and tuple(tr.shape) != (n, op.Sc):
-        raise ValueError(f"t_rand must be ({n},{op.Sc})")
-    uu, us = _u_args(u, n, dev, op.num_fine_samples) if num_levels == 2 else (None, 0)
-    outs = [tuple(torch.empty(s, dtype=torch.float32, device=dev) for s in ((n, 3), (n,), (n,))) for _ in range(num_levels)]
-    fine = outs[1] if num_levels == 2 else (None, None, None)
-    st, keep = op.c_struct(near, far, _check_noise(noise, n, op, num_levels) if plain else None)
     occ = grid.c_struct() if grid is not None else None
     occupied = torch.zeros(2, dtype=torch.int64, device=dev) if want_stats else None
-    stop = torch.zeros((n, 2), dtype=torch.int32, device=dev) if want_stats else None
-    if plain:
-        ws = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=dev) if workspace_bytes is not None else _workspace(dev, n, st)
+    extra = (C.byref(occ) if occ is not None else None, _ptr(occupied))
+    if occ_form and pc.bounds is None:
+        stop, ws = None, _occ_workspace(dev, n, pc.st, workspace_bytes)
     else:
-        ws = _stop_workspace(dev, n, st, workspace_bytes)
-    extra = ()
-    if bounds is not None:
-        name, extra = name.replace("_stop", "_bounds"), (C.byref(bounds),)
+        stop = torch.zeros((n, 2), dtype=torch.int32, device=dev) if want_stats else None
+        extra += (C.c_float(eps), R, _ptr(stop))
+        if pc.bounds is not None:
+            name, extra = name.rsplit("_", 1)[0] + "_bounds", extra + (C.byref(pc.bounds),)
+        if plain:
+            ws = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=dev) if workspace_bytes is not None else _workspace(dev, n, pc.st)
+        else:
+            ws = _occ_workspace(dev, n, pc.st, workspace_bytes, "aon_render_stop_workspace_bytes")
     with torch.cuda.device(dev):
-        check(getattr(lib, name)(*packs, _ptr(o), _ptr(d), _ptr(v), n, float(near), float(far), int(bool(white_bkgd)), num_levels, _ptr(tr) if tr is not None else None,
-                                 _ptr(uu), us,
-                                 _ptr(outs[0][0]), _ptr(outs[0][1]), _ptr(outs[0][2]), _ptr(fine[0]), _ptr(fine[1]), _ptr(fine[2]),
-                                 _ptr(ws), ws.numel(), _stream(), C.byref(st), C.byref(occ) if occ is not None else None, _ptr(occupied),
-                                 C.c_float(eps), R, _ptr(stop), *extra), name)
-    return [tuple(x) for x in outs], occupied, stop
+        check(getattr(lib, name)(*packs, *pc.args(ws), *extra), name)
+    return (pc.outs, occupied) if occ_form else (pc.outs, occupied, stop)
 
 
 def render_fwd_stop(packed_coarse, packed_fine, rays_o, rays_d, viewdirs, near, far, white_bkgd, grid, eps, round_samples=None, num_levels=2,

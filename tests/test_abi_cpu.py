@@ -354,3 +354,42 @@ def test_param_arena_mechanics_on_cpu():
     opt.arena.params[0].grad = torch.ones(2, 3)
     with pytest.raises(RuntimeError, match="cuda"):
         opt.step()                                                             # the product path has no CPU form
+
+
+# The argtypes of every whole-path forward as the binding listed them by hand before they were assembled from pieces (_lib._PATH and
+# friends): p = c_void_p, i = c_int, l = c_int64, f = c_float.
+WHOLE_PATH_ARGTYPES = {
+    "aon_render_fwd": "p p p p p l f f i i p p l p p p p p p p l p",
+    "aon_render_fwd_ex": "p p p p p l f f i i p p l p p p p p p p l p p",
+    "aon_render_fwd_occ": "p p p p p l f f i i p p l p p p p p p p l p p p p",
+    "aon_render_fwd_stop": "p p p p p l f f i i p p l p p p p p p p l p p p p f i p",
+    "aon_render_fwd_bounds": "p p p p p l f f i i p p l p p p p p p p l p p p p f i p p",
+    "aon_render_fwd_train": "p p p p p l f f i i p p l p p p p p p p l p",
+    "aon_render_fwd_train_ex": "p p p p p l f f i i p p l p p p p p p p l p p",
+    "aon_render_fwd_train_bounds": "p p p p p l f f i i p p l p p p p p p p l p p p",
+    "aon_art_render_fwd": "p p p p p p p l f f i i p p l p p p p p p p l p",
+    "aon_art_render_fwd_ex": "p p p p p p p l f f i i p p l p p p p p p p l p p",
+    "aon_art_render_fwd_occ": "p p p p p p p l f f i i p p l p p p p p p p l p p p p",
+    "aon_art_render_fwd_stop": "p p p p p p p l f f i i p p l p p p p p p p l p p p p f i p",
+    "aon_art_render_fwd_bounds": "p p p p p p p l f f i i p p l p p p p p p p l p p p p f i p p",
+    "aon_art_render_fwd_train": "p p p p p p p l f f i i p p l p p p p p p p l p",
+    "aon_art_render_fwd_train_ex": "p p p p p p p l f f i i p p l p p p p p p p l p p",
+    "aon_art_render_fwd_train_bounds": "p p p p p p p l f f i i p p l p p p p p p p l p p p",
+    "aon_grender_fwd": "p p p p p p l f f i i p p l p p p p p p p l p p",
+    "aon_grender_fwd_train": "p p p p p p l f f i i p p l p p p p p p p l p p",
+}
+
+
+def test_whole_path_argtypes_equal_the_handwritten_lists():
+    from aon_amd import _lib
+
+    kinds = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_int64, "f": ctypes.c_float}
+    # every whole-path forward is in the table: the names the header declares with a `u_stride` parameter
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "aon_hip.h")).read(), flags=re.S)
+    whole_path = sorted(re.findall(r"\b(aon_\w+)\s*\([^;]*?\bint64_t u_stride\b[^;]*?\bvoid\* workspace\b[^;]*;", text))
+    assert whole_path == sorted(WHOLE_PATH_ARGTYPES), set(whole_path) ^ set(WHOLE_PATH_ARGTYPES)
+    for name, letters in WHOLE_PATH_ARGTYPES.items():
+        fn = getattr(_lib.lib, name)
+        assert fn.restype is ctypes.c_int, name
+        assert list(fn.argtypes) == [kinds[k] for k in letters.split()], name
+        assert list(_lib._SIGS[name][1]) == list(fn.argtypes), name

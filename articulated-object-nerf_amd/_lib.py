@@ -149,6 +149,9 @@ _SIGS = {
     "aon_train_scratch_bytes_ex": (_l, [_l, _i, _i, _p]),
     "aon_render_bwd_ex": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p]),
     "aon_art_render_bwd_ex": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p]),
+    # latent-only backward of a frozen articulated network
+    "aon_train_scratch_bytes_latents": (_l, [_l, _i, _p]),
+    "aon_art_render_bwd_latents": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p]),
     # NeRFMLP of any constructor geometry (aon_mlp_geometry first)
     "aon_mlp_geometry_init": (None, [_p]),
     "aon_gmlp_param_count": (_i, [_p]),

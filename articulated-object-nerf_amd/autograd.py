@@ -210,3 +210,43 @@ class RenderArticulated(torch.autograd.Function):
         _arena_done(ctx)
         lat = tuple(g_lat[k].reshape(shp) for k, shp in zip(("density", "color", "articulation"), ctx.lat_shapes))
         return (None,) * 12 + lat + tuple(g[name] for g in per_level for name in ops.ART_PARAM_ORDER)
+
+
+class RenderArticulatedLatents(torch.autograd.Function):
+    """NeRF_AE_Art.forward of a FROZEN network with gradients to the three latents only (fitting codes to observed views, DESIGN.md section
+    4.13): RenderArticulated's forward, and a backward without the weight-gradient stage (aon_art_render_bwd_latents).  The latent
+    gradients are bit-equal to RenderArticulated's; the parameters get none."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, packs, opts, noise, lat_density, lat_color,
+                lat_articulation, *params):
+        ctx.rays_d, ctx.white_bkgd, ctx.num_levels = rays_d, white_bkgd, num_levels
+        ctx.set_materialize_grads(False)
+        ctx.lat_shapes = (lat_density.shape, lat_color.shape, lat_articulation.shape)
+        # the backward reads the weights a latent enters (d latent = W^T db): saved the autograd way, as RenderArticulated, so an in-place
+        # update of a parameter or a latent between forward and backward raises
+        ctx.save_for_backward(lat_density, lat_color, lat_articulation, *params)
+        levels, ws, ctx.geometry = ops.render_fwd_train(packs[0][0], packs[1][0] if num_levels == 2 else None, rays_o, rays_d, viewdirs, near, far,
+                                                        white_bkgd, num_levels, t_rand, u, small_c=packs[0][1],
+                                                        small_f=packs[1][1] if num_levels == 2 else None, opts=opts, noise=noise)
+        ctx.fused = (ws, [pk[2] for pk in packs], [pk[1] for pk in packs])   # ONE C call (aon_art_render_fwd_train)
+        return tuple(x for lvl in levels for x in lvl)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        n_per = len(ops.ART_PARAM_ORDER)
+        _check_not_released(ctx)
+        ws, packs_bwd, smalls = ctx.fused
+        _wait_packed(packs_bwd, ctx.rays_d.device)
+        n = ctx.rays_d.shape[0]
+        g_rgb = [gouts[3 * l] if gouts[3 * l] is not None else torch.zeros((n, 3), dtype=torch.float32, device=ctx.rays_d.device)
+                 for l in range(ctx.num_levels)]
+        saved = ctx.saved_tensors   # (raises if a parameter or latent was modified in place since the forward)
+        params = [dict(zip(ops.ART_PARAM_ORDER, saved[3 + l * n_per: 3 + (l + 1) * n_per])) for l in range(ctx.num_levels)]
+        g_lat = ops.art_render_bwd_latents(ws, packs_bwd, smalls, ctx.rays_d, ctx.white_bkgd, ctx.num_levels, g_rgb,
+                                           [gouts[3 * l + 1] for l in range(ctx.num_levels)], [gouts[3 * l + 2] for l in range(ctx.num_levels)],
+                                           params, geometry=ctx.geometry)
+        ctx.fused, ctx.released, ctx.geometry = None, True, None
+        ops.pool_give(ws)      # (the backward's launches are enqueued: whoever takes the workspace next is ordered behind them)
+        lat = tuple(g_lat[k].reshape(shp) for k, shp in zip(("density", "color", "articulation"), ctx.lat_shapes))
+        return (None,) * 12 + lat + (None,) * (n_per * ctx.num_levels)

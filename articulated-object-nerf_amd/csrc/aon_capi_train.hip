@@ -570,6 +570,82 @@ static int train_bwd_impl(const char* who, bool art, const TrainNet* nets, const
   return AON_OK;
 }
 
+// ---- the latent-only backward of a frozen articulated network ----
+// TrainScratch without its weight-gradient workspaces (96 MiB a level) and temporaries: what the compositing backward and the chain write, and
+// the partial sums of the four bias gradients a latent enters through.
+struct LatentScratch {
+  float* d_raw[2]; float* dplanes[2]; float* dxp[2]; float* ws[2];
+  int64_t bytes;
+};
+LatentScratch carve_scratch_latents(char* base, int64_t n, int num_levels, const Geo& g) {
+  LatentScratch sc{};
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { char* p = base + off; off += align_up(bytes, 256); return p; };
+  for (int l = 0; l < num_levels; ++l) {
+    const int64_t Np = level_np(n, l, g);
+    sc.d_raw[l] = reinterpret_cast<float*>(take(Np * 16));
+    sc.dplanes[l] = reinterpret_cast<float*>(take((int64_t)aon::kAPlRows * Np * 4));
+    sc.dxp[l] = reinterpret_cast<float*>(take(Np * 16));
+    sc.ws[l] = reinterpret_cast<float*>(take(aon::art_latent_ws_bytes()));
+  }
+  sc.bytes = off;
+  return sc;
+}
+
+// composite backward -> backward chain as train_bwd_impl launches them (same kernels, same arguments: same gradient planes), then the two
+// launches of aon_train_latent.hip.  Everything on the caller's stream.
+int latent_bwd_impl(const char* who, const TrainNet* nets, const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels,
+                    const float* const* g_rgb_host, const float* const* g_acc_host, const float* const* g_depth_host, const float* const* const* params,
+                    float* const* g_latents, void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, hipStream_t caller,
+                    const aon_render_opts* opts) {
+  auto bad = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
+  Geo g;
+  if (const char* b = make_geo(opts, g)) return fail(AON_E_INVALID, b);
+  g.other_degrees = false;   // (the articulated kernels carry their degrees themselves)
+  if (n_rays <= 0 || (num_levels != 1 && num_levels != 2)) return bad(AON_E_INVALID, "bad size / num_levels");
+  if (!rays_d || !g_rgb_host || !workspace || !scratch || !g_latents[0] || !g_latents[1] || !g_latents[2]) return bad(AON_E_INVALID, "null pointer");
+  if (reinterpret_cast<uintptr_t>(scratch) & 255) return bad(AON_E_INVALID, "scratch must be 256-byte aligned");
+  const TrainWs w = carve_train(static_cast<char*>(workspace), n_rays, true, num_levels, g);
+  if (w.bytes > workspace_bytes) return bad(AON_E_WORKSPACE, "workspace smaller than aon_train_workspace_bytes()");
+  const LatentScratch sc = carve_scratch_latents(static_cast<char*>(scratch), n_rays, num_levels, g);
+  if (sc.bytes > scratch_bytes) return bad(AON_E_WORKSPACE, "scratch smaller than aon_train_scratch_bytes_latents()");
+  for (int l = 0; l < num_levels; ++l) {
+    const void* pb = nets[l].packed_bwd;
+    if (!pb || !nets[l].small || !params[l] || !g_rgb_host[l]) return bad(AON_E_INVALID, "null level pointer");
+    if (aon::stream_form(pb) != aon::stream_form(nets[l].small) || aon::stream_form(pb) != aon::stream_form(nets[0].packed_bwd))
+      return bad(AON_E_INVALID, "transposed stream and per-call block were made in different forms (aon_set_bottleneck_fold changed in between)");
+    for (int i : {0, 10, 20, 26})   // the weights a latent enters: all the W^T db products read
+      if (!params[l][i]) return bad(AON_E_INVALID, "null parameter pointer");
+  }
+  for (int l = 0; l < num_levels; ++l) {
+    const TrainLevel& L = w.lvl[l];
+    const int64_t valid = n_rays * L.S;
+    if (int rc = check(hipMemsetAsync(sc.d_raw[l] + valid * 4, 0, (size_t)(L.Np - valid) * 16, caller), who)) return rc;
+    KTimer timer(kCompositeBwd, caller, n_rays);
+    if (int rc = check(aon::launch_composite_bwd(L.raw, L.t, rays_d, g_rgb_host[l], g_acc_host ? g_acc_host[l] : nullptr, g_depth_host ? g_depth_host[l] : nullptr,
+                                                 n_rays, L.S, white_bkgd, g.act(true, l, 0), sc.d_raw[l], caller), who)) return rc;
+  }
+  auto chain_seg = [&](int l) {
+    const TrainLevel& L = w.lvl[l];
+    return aon::ChainSeg{static_cast<const char*>(nets[l].packed_bwd), nets[l].small, sc.d_raw[l], L.masks, L.planes, sc.dplanes[l], sc.dxp[l], L.Np};
+  };
+  if (num_levels == 2 && g_bwd_merge.load(std::memory_order_relaxed) != 0) {
+    const aon::ChainSeg segs[2] = {chain_seg(1), chain_seg(0)};
+    KTimer timer(kBwdChain, caller, w.lvl[0].Np + w.lvl[1].Np);
+    if (int rc = check(aon::launch_art_bwd_chain2(segs, 2, caller), who)) return rc;
+  } else {
+    for (int l = 0; l < num_levels; ++l) {
+      const aon::ChainSeg seg = chain_seg(l);
+      KTimer timer(kBwdChain, caller, w.lvl[l].Np);
+      if (int rc = check(aon::launch_art_bwd_chain2(&seg, 1, caller), who)) return rc;
+    }
+  }
+  aon::ArtLatentLevel lv[2];
+  for (int l = 0; l < num_levels; ++l) lv[l] = aon::ArtLatentLevel{sc.dplanes[l], w.lvl[l].Np, nets[l].packed_bwd, params[l], sc.ws[l]};
+  KTimer timer(kWgrad, caller, w.lvl[0].Np + (num_levels == 2 ? w.lvl[1].Np : 0));   // (the class of the stage it replaces)
+  return check(aon::launch_art_latent_grads(lv, num_levels, g.max_deg - g.min_deg, g.deg_view, g_latents[0], g_latents[1], g_latents[2], caller), who);
+}
+
 }  // namespace
 
 int aon_set_bwd_overlap(int on) {
@@ -717,6 +793,24 @@ int aon_art_render_bwd_ex(const void* packed_bwd_coarse, const void* small_coars
   float* g_latents[3] = {g_shape, g_appearance, g_articulation};
   return train_bwd_impl("aon_art_render_bwd", true, nets, rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, params, latents, grads,
                         g_latents, workspace, workspace_bytes, scratch, scratch_bytes, (hipStream_t)stream_, opts);
+}
+
+int64_t aon_train_scratch_bytes_latents(int64_t n_rays, int num_levels, const aon_render_opts* opts) {
+  Geo g;
+  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
+  return carve_scratch_latents(nullptr, n_rays < 1 ? 1 : n_rays, num_levels == 1 ? 1 : 2, g).bytes;
+}
+int aon_art_render_bwd_latents(const void* packed_bwd_coarse, const void* small_coarse, const void* packed_bwd_fine, const void* small_fine,
+                               const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels, const float* const* g_rgb_host,
+                               const float* const* g_acc_host, const float* const* g_depth_host, const float* const* params_coarse_host,
+                               const float* const* params_fine_host, float* g_shape, float* g_appearance, float* g_articulation,
+                               void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, void* stream_,
+                               const aon_render_opts* opts) {
+  const TrainNet nets[2] = {{nullptr, static_cast<const float*>(small_coarse), packed_bwd_coarse}, {nullptr, static_cast<const float*>(small_fine), packed_bwd_fine}};
+  const float* const* params[2] = {params_coarse_host, params_fine_host};
+  float* g_latents[3] = {g_shape, g_appearance, g_articulation};
+  return latent_bwd_impl("aon_art_render_bwd_latents", nets, rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, params,
+                         g_latents, workspace, workspace_bytes, scratch, scratch_bytes, (hipStream_t)stream_, opts);
 }
 
 }  // extern "C"

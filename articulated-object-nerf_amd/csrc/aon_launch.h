@@ -122,6 +122,18 @@ hipError_t launch_art_wgrad(const float* planes, const float* dplanes, const flo
 hipError_t launch_art_wgrad_post2(const ArtWgDeferred* d0, const ArtWgDeferred* d1, hipStream_t stream);
 int art_wgrad_deferred_bytes();
 
+// ---- aon_train_latent.hip: the latent gradients of a frozen articulated network from the chain's gradient planes (no weight gradient) ----
+struct ArtLatentLevel {
+  const float* dplanes;          // the level's gradient planes, written by the backward chain
+  int64_t Np;
+  const void* packed_bwd;        // the transposed stream that chain ran with (its form decides the level's layer list)
+  const float* const* params;    // the level's 40 parameters; read: [0], [10], [20], [26] (the weights a latent enters)
+  float* ws;                     // art_latent_ws_bytes() of partial sums
+};
+int64_t art_latent_ws_bytes();
+hipError_t launch_art_latent_grads(const ArtLatentLevel* levels, int nlevels, int pos_levels, int view_levels, float* g_shape, float* g_app, float* g_art,
+                                   hipStream_t stream);
+
 // ---- aon_render.hip: rays, sampling, encodings, compositing, the training loss ----
 hipError_t launch_raygen(const float* c2w, int H, int W, float focal, const float* directions, int64_t pix_begin,
                          int64_t pix_end, float* rays_o, float* viewdirs, float* rays_d, hipStream_t stream);

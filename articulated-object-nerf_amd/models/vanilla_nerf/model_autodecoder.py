@@ -12,7 +12,7 @@ import torch.nn as nn
 import torch.nn.init as init
 
 from ... import ops
-from ...autograd import RenderArticulated
+from ...autograd import RenderArticulated, RenderArticulatedLatents
 
 
 class NeRFMLP(nn.Module):
@@ -214,8 +214,11 @@ class NeRF_AE_Art(nn.Module):
                 # no side-stream kernel may be in flight when the forward's persistent launches are dispatched (see pack_aside_mode)
                 torch.cuda.current_stream(rays_o.device).wait_event(bwd_ready)
             params = [p for mlp in mlps for p in mlp.ordered_params()]
+            # a frozen network (only latents require grad: fitting codes, LitNeRF_AutoDecoder.fit_latents): the same forward and the same latent
+            # gradients, bit for bit, from a backward without the weight-gradient stage
+            render = RenderArticulated if any(p.requires_grad for p in params) else RenderArticulatedLatents
             try:
-                flat = RenderArticulated.apply(rays_o, rays["rays_d"], rays["viewdirs"], *[x.detach() if isinstance(x, torch.Tensor) else float(x) for x in (near, far)], bool(white_bkgd),
+                flat = render.apply(rays_o, rays["rays_d"], rays["viewdirs"], *[x.detach() if isinstance(x, torch.Tensor) else float(x) for x in (near, far)], bool(white_bkgd),
                                                self.num_levels, t_rand, u, packs, self._opts, noise, latents["density"], latents["color"],
                                                latents["articulation"], *params)
             finally:
@@ -302,6 +305,101 @@ class LitNeRF_AutoDecoder(Harness):
         self.log("train/loss", stats[3])
         self.log("train/loss/reg", stats[2])
         return loss
+
+    def _initial_latents(self, init, dev) -> dict:
+        """`init` of fit_latents -> {"density": (1,128), "color": (1,128), "articulation": (1,32)} fp32 copies on `dev`."""
+        lib3 = self.code_library
+        tables = {"density": lib3.embedding_instance_shape.weight, "color": lib3.embedding_instance_appearance.weight,
+                  "articulation": lib3.embedding_instance_articulation.weight}
+        if isinstance(init, str):
+            if init != "mean":
+                raise ValueError(f"fit_latents: init must be a dict of three tensors, 'mean' or (instance_id, articulation_id), got {init!r}")
+            out = {k: w.detach().mean(dim=0, keepdim=True) for k, w in tables.items()}   # column means of the library's tables
+        elif isinstance(init, dict):
+            if set(init) != set(tables):
+                raise ValueError(f"fit_latents: init dict needs exactly the keys {sorted(tables)}, got {sorted(init)}")
+            out = {}
+            for k, w in tables.items():
+                t = torch.as_tensor(init[k])
+                if t.numel() != w.shape[1]:
+                    raise ValueError(f"fit_latents: init[{k!r}] must hold {w.shape[1]} values, got {tuple(t.shape)}")
+                out[k] = t.detach().reshape(1, -1)
+        elif isinstance(init, (tuple, list)) and len(init) == 2 and all(isinstance(i, int) and not isinstance(i, bool) for i in init):
+            iid, aid = init
+            if not (0 <= iid < tables["density"].shape[0] and 0 <= aid < tables["articulation"].shape[0]):
+                raise ValueError(f"fit_latents: init ids {tuple(init)} outside the library ({tables['density'].shape[0]} instances, "
+                                 f"{tables['articulation'].shape[0]} articulation states)")
+            out = {"density": tables["density"].detach()[iid: iid + 1], "color": tables["color"].detach()[iid: iid + 1],
+                   "articulation": tables["articulation"].detach()[aid: aid + 1]}
+        else:
+            raise ValueError(f"fit_latents: init must be a dict of three tensors, 'mean' or (instance_id, articulation_id), got {init!r}")
+        return {k: v.to(device=dev, dtype=torch.float32).clone() for k, v in out.items()}
+
+    def fit_latents(self, batches, steps: int, lr: float = 5.0e-3, init="mean", seed: int = 0, full_backward: bool = False):
+        """Fit the three codes of ONE object / joint state to observed rays with the network FROZEN (what an auto-decoder does with an
+        instance that is not in its library): `steps` Adam steps on the 288 latent floats against the reference's training_step loss
+        (helper.train_loss: mse(fine) + mse(coarse) + 1e-4 * latent norms, model_autodecoder.py:428-466), batch `i % len(batches)` at step i.
+
+        batches: training batches of that one object (the dicts training_step takes; instance / articulation ids are ignored).
+        init: a dict {"density", "color", "articulation"} of tensors, "mean" (column means of the library's tables), or
+        (instance_id, articulation_id) (those rows of the library).  seed: of the stratified / inverse-CDF draws when the harness samples
+        randomly.  -> (latents dict of (1, dim) tensors, per-step losses as one (steps,) device tensor); no host synchronisation per step.
+
+        The network's requires_grad flags are cleared for the duration and restored; with them cleared NeRF_AE_Art.forward runs the
+        latent-only backward.  The codes, their gradients and the Adam moments are one flat (4, 288) buffer
+        stepped by ONE launch (aon_adam_step).  full_backward=True (the A/B partner, tools/latent_fit_bench.py): the network keeps its flags,
+        so every step pays the full training backward -- same losses and codes, bit for bit."""
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise ValueError(f"fit_latents: steps must be a positive int, got {steps!r}")
+        batches = list(batches)
+        if not batches:
+            raise ValueError("fit_latents: no batches")
+        if not (isinstance(lr, (int, float)) and lr > 0):
+            raise ValueError(f"fit_latents: lr must be positive, got {lr!r}")
+        dev = next(self.model.parameters()).device
+        lat0 = self._initial_latents(init, dev)
+        keys, dims = ("density", "color", "articulation"), (128, 128, 32)
+        arena = torch.zeros((4, sum(dims)), dtype=torch.float32, device=dev)   # rows: codes, gradients, exp_avg, exp_avg_sq
+        leaves, off = {}, 0
+        for k, d in zip(keys, dims):
+            view = arena[0, off: off + d].view(1, d)
+            view.copy_(lat0[k])
+            leaves[k] = view.detach().requires_grad_(True)   # a leaf on the arena's storage
+            off += d
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        net_params = list(self.model.parameters())
+        flags = [p.requires_grad for p in net_params]
+        losses = torch.zeros(steps, dtype=torch.float32, device=dev)
+        try:
+            if not full_backward:
+                for p in net_params:
+                    p.requires_grad_(False)
+            with torch.enable_grad():
+                for i in range(steps):
+                    batch = self._unbatch(batches[i % len(batches)])
+                    near, far = self.near, self.far
+                    if self.ray_box is not None:
+                        near, far, _ = _ray_box_limits(self.ray_box, batch)
+                    t_rand = u = None
+                    if self.randomized:
+                        n = batch["rays_o"].shape[0]
+                        t_rand = torch.rand((n, self.model.num_coarse_samples + 1), device=dev, generator=gen)
+                        u = torch.rand((n, self.model.num_fine_samples), device=dev, generator=gen) if self.model.num_levels == 2 else None
+                    rendered = self.model(batch, self.randomized, self.white_bkgd, near, far, leaves, t_rand=t_rand, u=u)
+                    loss, _ = helper.train_loss(rendered, batch["target"], tuple(leaves[k] for k in keys), 1e-4)
+                    grads = torch.autograd.grad(loss, [leaves[k] for k in keys])
+                    torch.cat([g.reshape(-1) for g in grads], out=arena[1])
+                    losses[i] = loss.detach()
+                    ops.adam_step(arena[0], arena[1], arena[2], arena[3], 0, arena.shape[1], float(lr), 0.9, 0.999, 1e-8, i + 1)
+        finally:
+            for p, f in zip(net_params, flags):
+                p.requires_grad_(f)
+        off, out = 0, {}
+        for k, d in zip(keys, dims):
+            out[k] = arena[0, off: off + d].view(1, d).clone()
+            off += d
+        return out, losses
 
     def _render_chunks(self, batch, latents, skip=()):
         B = batch["rays_o"].shape[0]

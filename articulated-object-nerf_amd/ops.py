@@ -1230,6 +1230,42 @@ def art_render_bwd(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels, g_rgb,
     return grads, g_lat
 
 
+def train_scratch_latents(device, n_rays: int, num_levels: int = 2, st=None) -> torch.Tensor:
+    """The latent-only backward's temporaries (gradient planes, d_raw, a few MB of partial sums; no weight-gradient workspace), pooled as
+    `train_scratch`."""
+    return _pool_take(int(lib.aon_train_scratch_bytes_latents(n_rays, num_levels, None if st is None else C.byref(st))),
+                      "aon_train_scratch_bytes_latents", device)
+
+
+def art_render_bwd_latents(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, params_per_level, geometry=None) -> dict:
+    """loss.backward() through render_fwd_train of a FROZEN articulated network -> dict of the three latent gradients summed over the
+    levels, bit-equal to `art_render_bwd`'s second result for the same workspace and g_*; no parameter gradient is computed or written
+    (aon_art_render_bwd_latents)."""
+    d = _f32(rays_d, "rays_d")
+    n, dev = d.shape[0], d.device
+    st = None if geometry is None else geometry[0]
+    degrees = (0, 10, 4) if st is None else (int(st.min_deg_point), int(st.max_deg_point), int(st.deg_view))
+    tens, parr = [], []
+    for params in params_per_level:
+        t, arr = _art_param_array(params, degrees)
+        tens.append(t)
+        parr.append(arr)
+    parr += [None] * (2 - num_levels)
+    pb, sm = list(packs_bwd) + [None] * (2 - num_levels), list(smalls) + [None] * (2 - num_levels)
+    g_lat = {"density": torch.empty(128, device=dev), "color": torch.empty(128, device=dev), "articulation": torch.empty(32, device=dev)}
+    keep = [None if t is None else _f32(t, "grad") for t in list(g_rgb) + list(g_acc) + list(g_depth)]
+    k = num_levels
+    scratch = train_scratch_latents(dev, n, num_levels, st)
+    with torch.cuda.device(dev):
+        check(lib.aon_art_render_bwd_latents(_pk(pb[0]), _pk(sm[0]), _pk(pb[1]), _pk(sm[1]), _ptr(d), n, int(bool(white_bkgd)), num_levels,
+                                             _ptr_array(keep[:k]), _ptr_array(keep[k:2 * k]), _ptr_array(keep[2 * k:3 * k]), parr[0], parr[1],
+                                             _ptr(g_lat["density"]), _ptr(g_lat["color"]), _ptr(g_lat["articulation"]), _ptr(ws), ws.numel(),
+                                             _ptr(scratch), scratch.numel(), _stream(), None if st is None else C.byref(st)),
+              "aon_art_render_bwd_latents")
+    pool_give(scratch)
+    return g_lat
+
+
 # ------------------------------------------------------------------ NeRFMLP of any constructor geometry (csrc/aon_gmlp.hip)
 class MlpGeometry:
     """The arguments of ``NeRFMLP.__init__`` (model.py:40-54) -> ``aon_mlp_geometry``; parameter names / shapes / order of the

@@ -608,6 +608,22 @@ int aon_art_render_bwd_ex(const void* packed_bwd_coarse, const void* small_coars
                           float* const* grads_fine_host, float* g_shape, float* g_appearance, float* g_articulation,
                           void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, void* stream,
                           const aon_render_opts* opts);
+/* Latent-only backward of a FROZEN articulated network (fitting the three codes of an auto-decoder to observed views; DESIGN.md section
+ * 4.13): aon_art_render_bwd_ex without its weight-gradient stage.  Same workspace (the forward's), same g_* arrays, same opts (NULL =
+ * defaults); it writes g_shape (128), g_appearance (128) and g_articulation (32) -- summed over the levels, overwritten -- and nothing
+ * else: no parameter gradient is computed or stored.  The three vectors are BIT-EQUAL to what aon_art_render_bwd_ex writes for the same
+ * workspace and g_* (both stream forms, one or two levels, the _deg degree sets, per-ray bounds).  params_*_host: the forward's 40 device
+ * pointers per level, of which the four weights a latent enters are read (deformations_linear.0, pts_linears.0 and .5, views_linear.0:
+ * entries 0, 10, 20, 26; the others may be NULL).  The latents themselves are not needed.  scratch >= aon_train_scratch_bytes_latents(),
+ * 256-byte aligned: the full backward's scratch minus its weight-gradient workspaces.  Ordinary stream-ordered launches on `stream` only;
+ * deterministic (no atomics). */
+int64_t aon_train_scratch_bytes_latents(int64_t n_rays, int num_levels, const aon_render_opts* opts);
+int aon_art_render_bwd_latents(const void* packed_bwd_coarse, const void* small_coarse, const void* packed_bwd_fine,
+                               const void* small_fine, const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels,
+                               const float* const* g_rgb_host, const float* const* g_acc_host, const float* const* g_depth_host,
+                               const float* const* params_coarse_host, const float* const* params_fine_host, float* g_shape,
+                               float* g_appearance, float* g_articulation, void* workspace, int64_t workspace_bytes,
+                               void* scratch, int64_t scratch_bytes, void* stream, const aon_render_opts* opts);
 
 /* ---- NeRFMLP of ANY constructor geometry (models/vanilla_nerf/model.py:40-120), round 3 ----
  * The entry points above run the reference's default NeRFMLP (8 x 256, skip 4, 1 x 128, degrees 10 / 4) on fused kernels compiled

@@ -51,17 +51,6 @@ def _arena_done(ctx):
         ctx.arena_plan = None
 
 
-def _wait_packed(packs_bwd, device):
-    """The transposed streams may have been packed on a side stream (models.vanilla_nerf.model.packed_bwd_aside): the stream this backward
-    runs on -- not necessarily the forward's -- waits for that pack."""
-    seen = set()
-    for b in packs_bwd:
-        ev = getattr(b, "_aon_ready", None)
-        if ev is not None and id(ev) not in seen:
-            seen.add(id(ev))
-            torch.cuda.current_stream(device).wait_event(ev)
-
-
 def _check_not_released(ctx):
     """The activation planes (10-14 KB per sample) are handed back after the first backward, like autograd's own saved
     tensors without retain_graph: a second backward through the same forward gets the error autograd would give."""
@@ -91,7 +80,6 @@ class RenderVanilla(torch.autograd.Function):
     def backward(ctx, *gouts):
         _check_not_released(ctx)
         ws, packs_bwd, packs_fwd = ctx.fused    # the whole backward is ONE C call too (aon_render_bwd)
-        _wait_packed(packs_bwd, ctx.rays_d.device)
         n_per = len(ops.VANILLA_PARAM_ORDER)
         slots = _arena_grads(ctx, [ctx.param_shapes[l * n_per: (l + 1) * n_per] for l in range(ctx.num_levels)])
         n = ctx.rays_d.shape[0]
@@ -194,7 +182,6 @@ class RenderArticulated(torch.autograd.Function):
         n_per = len(ops.ART_PARAM_ORDER)
         _check_not_released(ctx)
         ws, packs_bwd, smalls = ctx.fused       # the whole backward in ONE C call (aon_art_render_bwd)
-        _wait_packed(packs_bwd, ctx.rays_d.device)
         n = ctx.rays_d.shape[0]
         g_rgb = [gouts[3 * l] if gouts[3 * l] is not None else torch.zeros((n, 3), dtype=torch.float32, device=ctx.rays_d.device)
                  for l in range(ctx.num_levels)]
@@ -237,7 +224,6 @@ class RenderArticulatedLatents(torch.autograd.Function):
         n_per = len(ops.ART_PARAM_ORDER)
         _check_not_released(ctx)
         ws, packs_bwd, smalls = ctx.fused
-        _wait_packed(packs_bwd, ctx.rays_d.device)
         n = ctx.rays_d.shape[0]
         g_rgb = [gouts[3 * l] if gouts[3 * l] is not None else torch.zeros((n, 3), dtype=torch.float32, device=ctx.rays_d.device)
                  for l in range(ctx.num_levels)]

@@ -21,17 +21,8 @@ SOURCES = ["aon_mlp.hip", "aon_mlp_art.hip", "aon_train.hip", "aon_train_art.hip
 HEADERS = [os.path.join(CSRC, "aon_common.h"), os.path.join(CSRC, "aon_launch.h"), os.path.join(CSRC, "aon_capi_util.h"), os.path.join(CSRC, "aon_mlp_core.h"), os.path.join(CSRC, "aon_wgrad.h"), os.path.join(CSRC, "aon_art_common.h"), os.path.join(CSRC, "aon_ray_core.h"), os.path.join(CSRC, "aon_gmlp.h"), os.path.join(CSRC, "aon_fold.h"),
            os.path.join(os.path.dirname(PKG), "include", "aon_hip.h")]
 # -ffp-contract=off: the stage kernels reproduce the reference's un-fused mul/add sequences; FMAs are explicit.
-# Per-file code-generation choices, A/B-measured on MI355X (round 1, tools/ab_train.sh, 4096-ray vanilla training step):
-# pinning the A-fragment read of step i+1 above the MFMAs of step i (AON_PIN_PREFETCH, aon_mlp_core.h) helps the vanilla
-# backward chain (5.62 -> 4.95 ms per level pair) but costs the forward kernels 2.7 % (144.0 -> 140.2 TFLOP/s) and does
-# nothing for the articulated chains, so it is applied to aon_train.hip only.  (-mllvm -amdgpu-mfma-vgpr-form on the same
-# file: backward chain 5.26 ms but the weight-gradient kernel 0.525 -> 0.643 ms -- a net loss.)
-# Round 4: with two segments per chain launch the pinned form of the vanilla chain spills 3.5 KB per lane (the sched_barrier per step
-# leaves the allocator no room for the segment bookkeeping); unpinned it is at 0 scratch, so the flag is off for every file.
-PER_FILE_FLAGS = {}
-if "AON_PER_FILE_FLAGS" in os.environ:   # experiments: JSON {"file.hip": ["flag", ...]} replaces the table
-    import json as _json
-    PER_FILE_FLAGS = _json.loads(os.environ["AON_PER_FILE_FLAGS"])
+# Every file takes the same flags: the one per-file choice ever kept (rounds 1-3: a sched_barrier per MFMA step pinning the A-fragment
+# prefetch in aon_train.hip) spilled 3.5 KB per lane once the chain took two segments (round 4) and is gone (profiles/LAB_NOTEBOOK.md).
 FLAGS = (os.environ.get("AON_EXTRA_FLAGS", "").split()) + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-lambda-capture"]
 
 
@@ -56,7 +47,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ, src.replace(".hip", ".o"))
-        cmd = [cc, *FLAGS, *PER_FILE_FLAGS.get(src, []), "-c", s, "-o", o]
+        cmd = [cc, *FLAGS, "-c", s, "-o", o]
         # an object is also stale when it was built with other flags (AON_EXTRA_FLAGS experiments must not reuse objects)
         stamp = o + ".cmd"
         same_cmd = os.path.exists(stamp) and open(stamp).read() == " ".join(cmd)

@@ -761,19 +761,10 @@ int aon_art_pack_step(const float* const* params_coarse_host, const float* const
       if (bwd[l]) jobs[n++] = aon::art_fold_job_bwd(P[l], bwd[l], Lv);
     if (int rc = check(aon::launch_fold_gemms(jobs, n, stream), "aon_art_pack_step")) return rc;
   }
-  // (AON_PACK_MERGE=0 in the environment: one launch per network and buffer as before, for A/B)
-  static const bool merge = [] { const char* e = std::getenv("AON_PACK_MERGE"); return !(e && e[0] == '0'); }();
-  if (merge) {
-    if (int rc = check(aon::launch_pack_prepare_art2(P, shape, appearance, articulation, fwd, sm, stream, min_deg_point, Lp, Lv, form), "aon_art_pack_step")) return rc;
-    if (bwd[0] && bwd[1]) return check(aon::launch_pack_art_bwd2(P, bwd, stream, Lp, Lv, form), "aon_art_pack_step");
-  } else {
-    for (int l = 0; l < 2; ++l) {
-      if (int rc = check(aon::launch_prepare_art(P[l], shape, appearance, articulation, sm[l], stream, min_deg_point, Lp, Lv), "aon_art_pack_step")) return rc;
-      if (int rc = check(aon::launch_pack_art(P[l], fwd[l], stream, Lp, Lv, folded), "aon_art_pack_step")) return rc;
-    }
-  }
-  for (int l = 0; l < 2; ++l)
-    if (bwd[l] && !(merge && bwd[0] && bwd[1]))
+  if (int rc = check(aon::launch_pack_prepare_art2(P, shape, appearance, articulation, fwd, sm, stream, min_deg_point, Lp, Lv, form), "aon_art_pack_step")) return rc;
+  if (bwd[0] && bwd[1]) return check(aon::launch_pack_art_bwd2(P, bwd, stream, Lp, Lv, form), "aon_art_pack_step");
+  for (int l = 0; l < 2; ++l)   // only one transposed buffer given: its own pack launch
+    if (bwd[l])
       if (int rc = check(aon::launch_pack_art_bwd(P[l], bwd[l], stream, Lp, Lv, folded), "aon_art_pack_step")) return rc;
   return AON_OK;
 }

@@ -441,15 +441,12 @@ static int train_bwd_impl(const char* who, bool art, const TrainNet* nets, const
   // Round 4: the two levels' chains are independent -> ONE persistent launch of two segments on the caller's stream (33 rounds of
   // workgroups instead of 9 + 25 at 4096 x (65 + 193) samples), then the weight gradients of the two levels on the two streams.
   const bool merged = num_levels == 2 && g_bwd_merge.load(std::memory_order_relaxed) != 0;
-  // 0: none; 1: round-3 level streams when not merged; 2: + head reductions on side streams when merged.  [articulated], round 6: mode 1
-  // means mode 2 -- each level's remaining head reductions (six jobs, 70 + 185 us, HBM-bound ordinary blocks) go onto the level's aux
-  // stream just BEFORE its grouped kernel and run beside it instead of in front of it: 30.418 -> 30.309 ms per 4096-ray step over eight
-  // alternating runs each (all eight below all eight), same bits (tools/grad_hash.py).  Round 4 had measured this form slower (34.5 vs 34.1 ms,
-  // profiles/r04_backward_schedules.txt; the kernels have changed since); the vanilla network's three head jobs gain nothing (24.446 vs
-  // 24.423 ms) and keep mode 1.  AON_ART_AUX_HEADS=0 in the environment: mode 1 as before (A/B).
-  static const bool art_aux_heads = [] { const char* e = std::getenv("AON_ART_AUX_HEADS"); return !(e && e[0] == '0'); }();
+  // 0: none; 1: round-3 level streams when not merged; 2: + head reductions on side streams when merged.  [articulated] mode 1 means
+  // mode 2 -- each level's remaining head reductions (six jobs, 70 + 185 us, HBM-bound ordinary blocks) go onto the level's aux stream
+  // just BEFORE its grouped kernel and run beside it instead of in front of it (30.418 -> 30.309 ms per 4096-ray step, same bits); the
+  // vanilla network's three head jobs gain nothing (24.446 vs 24.423 ms) and keep mode 1.
   const int overlap_raw = g_bwd_overlap.load(std::memory_order_relaxed);
-  const int overlap_mode = (art && overlap_raw == 1 && art_aux_heads) ? 2 : overlap_raw;
+  const int overlap_mode = (art && overlap_raw == 1) ? 2 : overlap_raw;
   // Round 5: the head / bias reductions that need nothing from the chain run on a side stream beside the merged chain launch (g_bwd_early_heads)
   const bool early_heads = merged && g_bwd_early_heads.load(std::memory_order_relaxed) != 0;
   // fork: with two levels each runs on its own library stream, ordered after everything already enqueued on the caller's
@@ -463,9 +460,8 @@ static int train_bwd_impl(const char* who, bool art, const TrainNet* nets, const
   // event gap either side) used to sit between the two grouped kernels with the chip all but idle; deferred, the grouped kernels follow
   // each other and the levels' reduce blocks, un-folding products and [articulated] finishing kernels go out as 1 + 1 (+ 2) launches behind
   // level 1's (launch_*_wgrad_post2; every block does what it did: same bits, tools/grad_hash.py).  Default degrees only (other degrees put
-  // remap launches between the stages).  AON_POST_MERGE=0 in the environment: per level as before (A/B).
-  static const bool post_merge_env = [] { const char* e = std::getenv("AON_POST_MERGE"); return !(e && e[0] == '0'); }();
-  const bool post_merged = merged && post_merge_env &&
+  // remap launches between the stages).
+  const bool post_merged = merged &&
                            (art ? g.max_deg - g.min_deg == 10 && g.deg_view == 4 && aon::art_wgrad_deferred_bytes() <= aon::kArtWgDeferredBytes
                                 : !g.other_degrees && aon::vanilla_wgrad_deferred_bytes() <= aon::kVanillaWgDeferredBytes);
   constexpr int kDeferBytes = aon::kArtWgDeferredBytes > aon::kVanillaWgDeferredBytes ? aon::kArtWgDeferredBytes : aon::kVanillaWgDeferredBytes;
@@ -509,9 +505,7 @@ static int train_bwd_impl(const char* who, bool art, const TrainNet* nets, const
       //   [articulated] in overlap mode 2 only: level 0's remaining reductions are queued on this very stream (aux(0) == side), behind the
       //   early ones, and run_wgrad_plan joins it in front of the second stage.  Mode 1 (remaining reductions on the caller's stream, no later
       //   join): the caller's stream waits here.
-      // AON_EARLY_JOIN=1 in the environment: wait here in any case (A/B).
-      static const bool join_here = [] { const char* e = std::getenv("AON_EARLY_JOIN"); return e && e[0] == '1'; }();
-      early_unjoined = (!art || overlap_mode == 2) && !join_here && !rc && !rj;
+      early_unjoined = (!art || overlap_mode == 2) && !rc && !rj;
       const int rw = early_unjoined ? AON_OK : check(hipStreamWaitEvent(caller, side->join, 0), who);
       if (rc || rj || rw) return rc ? rc : (rj ? rj : rw);
     }

@@ -112,13 +112,7 @@ __device__ __forceinline__ unsigned acquire(Pipe& p) {
   // second base selected per chunk kept two 64-bit per-lane addresses alive and tipped the vanilla chain into 3.5 KB of scratch)
   if constexpr (C == first_wrapping_chunk<Net>()) p.stream = p.next_stream;
   if constexpr ((C & 1) == 0) {
-#if defined(AON_EXP_NOVMWAIT)    // timing experiment only (WRONG results): the barrier without waiting for this wave's DMA
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#elif defined(AON_EXP_NOBARRIER) // timing experiment only (WRONG results): the DMA wait without the workgroup barrier
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#else
     __syncthreads();  // drains this wave's LDS-DMA (vmcnt(0)) + workgroup barrier
-#endif
     p.slot ^= 1;
   }
   unsigned off = p.issue_off;
@@ -182,7 +176,7 @@ __device__ __forceinline__ void chunk_mma(Pipe& p, const f32x16& in, f32x16 (&ou
   constexpr int NSTEP = NQ * NT_OUT;
   // (round-1 experiments on the forward kernels, all slower than the compiler's own interleave of this distance-1 form at
   // 0.915 of peak: a distance-2 prefetch pinned by sched_barrier(0) per step 0.900; this distance-1 read pinned above its
-  // four MFMAs 0.891 -- which does pay in the vanilla backward chain, see AON_PIN_PREFETCH; ReLU applied lazily here on
+  // four MFMAs 0.891 -- which paid in the vanilla backward chain only until round 4, see build.py; ReLU applied lazily here on
   // the input tile instead of as a block between layers 0.869 -- 16 more live registers.)
   // (Round 3: hipcc sinks the read of step i+1 from here to just in front of its own use -- `ds_read_b128; s_waitcnt lgkmcnt(0);
   // 4 x v_mfma` -- in 32 % of the steps of the inference kernel and 71 % of the articulated chain's, and after any LDS-DMA
@@ -208,9 +202,6 @@ __device__ __forceinline__ void chunk_mma(Pipe& p, const f32x16& in, f32x16 (&ou
     // (Round 3 experiment: a sched_barrier here that keeps this step's vector-memory instructions -- DMA round, plane store --
     // inside the step while letting MFMA / VALU / LDS cross.  hipcc does sink a chunk's stores to its end, in front of the next
     // pair's barrier, but pinning them changed nothing: forward 8.66 vs 8.61 ms, chains within 0.1 %.  Not kept.)
-#ifdef AON_PIN_PREFETCH   // per translation unit (build.py): keeps the read of step i+1 above the four MFMAs of step i
-    __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
     for (int cc = 0; cc < 4; ++cc) {
       if (4 * q + cc < NREG) {
@@ -228,13 +219,6 @@ __device__ __forceinline__ void chunk_mma(Pipe& p, const f32x16& in, f32x16 (&ou
 
 template <int NT_OUT>
 __device__ __forceinline__ void init_bias(f32x16 (&acc)[NT_OUT], const float* sm_bias, int h) {
-#ifdef AON_EXP_NOBIAS    // timing experiment only (WRONG results): what the per-layer bias reads cost
-#pragma unroll
-  for (int tp = 0; tp < NT_OUT; ++tp)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[tp][r] = 0.f;
-  return;
-#endif
 #pragma unroll
   for (int tp = 0; tp < NT_OUT; ++tp) {
 #pragma unroll
@@ -265,9 +249,6 @@ __device__ __forceinline__ float relu1(float x) {
 // "a" constraints, which frees ~75 arch VGPRs -- was measured in round 1: 0.875 of peak against 0.908 for this form.)
 template <int NT>
 __device__ __forceinline__ void relu_tiles(f32x16 (&x)[NT]) {
-#ifdef AON_EXP_NORELU    // timing experiment only (WRONG results): what the per-layer ReLU bursts cost
-  return;
-#endif
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
 #pragma unroll
@@ -352,7 +333,6 @@ __device__ __forceinline__ float* row_ptr(const PlaneIO& io, int row) {
 }
 template <bool STAGE = true>
 __device__ __forceinline__ void store_quad(const PlaneIO& io, int row, int g, const f32x16& t) {
-#ifndef AON_EXP_NOSTORE   // experiment builds only (tools/exp_train.sh): what the plane stores cost
   f32x4 v; v[0] = t[4 * g]; v[1] = t[4 * g + 1]; v[2] = t[4 * g + 2]; v[3] = t[4 * g + 3];
   // (STAGE = false, round 4: the forward's tiles are post-ReLU values that already live in architectural VGPRs; the staging asm, which
   // "modifies" its operand, forced a copy of every quad there -- 770 v_mov_b64 per pass of the articulated training forward)
@@ -360,18 +340,13 @@ __device__ __forceinline__ void store_quad(const PlaneIO& io, int row, int g, co
   // The store's data is staged in architectural VGPRs (four v_accvgpr_read where the tile sits in AGPRs, as the gradient
   // tiles of the backward chains do): a global_store whose data operand is an AGPR range reads it while MFMAs are streaming
   // their accumulators through the same register banks and holds the wave's issue port meanwhile.  Measured round 3
-  // (tools/exp_train.sh): articulated backward chain 9.60 -> 9.03 ms (4096 x 193 samples), 3.42 -> 3.25 (x 65).
+  // (experiment build): articulated backward chain 9.60 -> 9.03 ms (4096 x 193 samples), 3.42 -> 3.25 (x 65).
   asm volatile("" : "+v"(v));
   // ... and it is a streaming (`nt`) store: the 10.9 GB of planes a level writes are read back once, much later, by the
   // weight-gradient kernel; written with the default policy they push the 2.8-3.3 MB weight stream, which every workgroup
   // re-reads every pass, out of the 4 MB L2 of its XCD.  (Round 2 measured `nt` as a loss on the feature-major layout, 4-byte
   // stores to 3,456 scattered rows; on 1 KiB contiguous units: forward 9.04 -> 8.67 ms, chain 9.01 -> 8.68 ms.)
-#ifdef AON_EXP_NO_NT
-  *quad_ptr(io, row, g) = v;
-#else
   __builtin_nontemporal_store(v, quad_ptr(io, row, g));
-#endif
-#endif
 }
 
 // ReLU masks of one layer as bits (bit (t&1)*16 + r of word t>>1 <-> tile t, register r): 16 bytes per lane per layer,
@@ -405,12 +380,8 @@ __device__ __forceinline__ T* mask_ptr(T* masks, int64_t Np, int slot, unsigned 
 //             bit-reversed once (mask_word_finish) into the stored layout: bit (t&1)*16 + r of word t>>1 <-> tile t, register r.
 //   backward  m = sign-extended one-bit field of w at pos (0 or 0xffffffff);  dz = dh & m
 __device__ __forceinline__ unsigned mask_push_post(unsigned w, float y_post_relu) {
-#ifdef AON_EXP_NOMASK     // experiment builds only: what the decision-bit arithmetic costs
-  return w;
-#else
   const unsigned nb = 0u - __builtin_bit_cast(unsigned, y_post_relu);
   return __builtin_amdgcn_alignbit(w, nb, 31);
-#endif
 }
 __device__ __forceinline__ unsigned mask_word_finish(unsigned w) { return __builtin_bitreverse32(w); }
 
@@ -488,11 +459,7 @@ struct BwdSideOf {
         }
         if constexpr (MASKED) {
           if (j + 1 < NT) {
-            float z = mask_apply(m[(j + 1) >> 1], t[j + 1][i], ((j + 1) & 1) * 16 + i);
-#ifdef AON_EXP_MASK_VGPR   // experiment: the masked gradient lives in an architectural VGPR from here on (B operand + store source)
-            asm volatile("" : "+v"(z));
-#endif
-            t[j + 1][i] = z;
+            t[j + 1][i] = mask_apply(m[(j + 1) >> 1], t[j + 1][i], ((j + 1) & 1) * 16 + i);
           }
         }
       }

@@ -10,8 +10,6 @@ interface, forward and backward.  Sample counts, ``lindisp`` and ``noise_std`` a
 """
 from __future__ import annotations
 
-import os as _os
-
 import torch
 import torch.nn as nn
 import torch.nn.init as init
@@ -110,83 +108,6 @@ class NeRFMLP(nn.Module):
             return ops.gmlp_fwd(self.geometry, dict(self.named_parameters()), x, condition)
         raw = ops.mlp_fwd_enc(self.packed(), x, condition)
         return raw[..., :3], raw[..., 3:4]
-
-
-_SIDE_STREAMS: dict = {}
-
-
-def pack_aside_mode() -> int:
-    """AON_PACK_ASIDE: 0 (default since round 6) = every pack launch in line on the current stream; 1 = round 5: the transposed streams (and,
-    round 6, the fine level's forward pack) on side streams, the transposed ones waited for AFTER the forward's launches; 2 = the same side
-    streams, all of them waited for BEFORE the forward is launched.
-    Why 0: measured with the workspace pool in place (ops._TRAIN_POOL), six alternating runs each on one box, the four variants are the same to
-    0.02 ms per 30.4 ms step (30.401 / 30.403 / 30.404 / 30.421 ms: in line / mode 1 / mode 1 + the level-0 second stage aside / mode 2) --
-    the 0.03-0.05 ms that rounds 5 and 6 first read off shorter A/Bs do not survive more repetitions -- and side streams around persistent
-    launches are exactly where this code base has been burnt before (profiles/r04_backward_schedules.txt).  The modes stay for experiments."""
-    import os
-
-    v = os.environ.get("AON_PACK_ASIDE", "0")
-    return int(v) if v in ("0", "1", "2") else 0
-
-
-def packed_bwd_aside(mlps):
-    """The levels' transposed weight streams (read by the BACKWARD only), packed on a side stream so that the two small launches per level
-    (38 us each in a 31 ms step, profiles/r05_step_timeline.txt) run beside the forward's own pack kernels and launches instead of in front
-    of them.  Returns (buffers, event): the buffers are allocated on the current stream; the caller makes the current stream wait for
-    `event` once the forward is enqueued -- long before the backward reads them.  AON_PACK_ASIDE=0: packed in line, event None."""
-    import os
-
-    dev = next(mlps[0].parameters()).device
-    if pack_aside_mode() == 0 or dev.type != "cuda":
-        return [m.packed_bwd(True) for m in mlps], None
-    cur = torch.cuda.current_stream(dev)
-    outs = [m.new_bwd_buffer() for m in mlps]
-    # one side stream per level (round 6: the two levels' fold -> pack chains beside each other; the last stream waits for the others,
-    # so ONE event covers them all)
-    sides = []
-    for lvl in range(len(mlps)):
-        side = _SIDE_STREAMS.get((dev, "bwd", lvl))
-        if side is None:
-            side = _SIDE_STREAMS[(dev, "bwd", lvl)] = torch.cuda.Stream(device=dev)
-        sides.append(side)
-    for side, m, o in zip(sides, mlps, outs):
-        side.wait_stream(cur)        # the parameters as the optimiser step left them
-        with torch.cuda.stream(side):
-            m.packed_bwd(True, out=o)
-    for side in sides[:-1]:
-        sides[-1].wait_stream(side)
-    side = sides[-1]
-    ev = side.record_event()
-    for o in outs:
-        # ADVICE r5: (1) the buffers were allocated on the current stream but are written on the side stream: the caching allocator must not
-        # hand their memory to current-stream work before the pack kernels are done, even if the caller drops them early (an exception
-        # inside the forward); (2) the event travels WITH the buffer, so that a backward run on another stream than the forward waits too
-        for sd in sides:
-            o.record_stream(sd)
-        o._aon_ready = ev
-    return outs, ev
-
-
-def run_aside(dev, key: str, fn):
-    """`fn()` -> tuple of tensors, enqueued on a side stream of its own (one per device and `key`) behind everything the current stream
-    holds; -> (tensors, event or None).  Round 6: the FINE level's pack / prepare launches (fold -> pack, ~48 us in a row) run beside the
-    coarse level's instead of behind them; the caller makes the current stream wait for the event before the forward's C call.  The tensors
-    are allocated on the side stream and used on the current one: recorded for it, so the caching allocator keeps them until both are done."""
-    import os
-
-    if pack_aside_mode() == 0 or dev.type != "cuda":
-        return fn(), None
-    cur = torch.cuda.current_stream(dev)
-    side = _SIDE_STREAMS.get((dev, key))
-    if side is None:
-        side = _SIDE_STREAMS[(dev, key)] = torch.cuda.Stream(device=dev)
-    side.wait_stream(cur)
-    with torch.cuda.stream(side):
-        outs = fn()
-    ev = side.record_event()
-    for o in outs:
-        o.record_stream(cur)
-    return outs, ev
 
 
 class NeRF(nn.Module):
@@ -333,28 +254,17 @@ class NeRF(nn.Module):
             if n == 0:
                 raise ValueError("empty ray batch in training mode")
             mlps = [self.coarse_mlp, self.fine_mlp][: self.num_levels]
-            bwd_ready = fine_ready = None
             degs = [(m.min_deg_point, m.max_deg_point, m.deg_view) for m in mlps]
-            if len(mlps) == 2 and pack_aside_mode() == 0 and degs[0] == degs[1] and _os.environ.get("AON_PACK_STEP", "1") != "0":
-                # round 6: both networks' forward and transposed streams in ONE C call -- the eight fp64 fold products as one launch in front
+            if len(mlps) == 2 and degs[0] == degs[1]:
+                # both networks' forward and transposed streams in ONE C call -- the eight fp64 fold products as one launch in front
                 # instead of four in a row with their pack kernels (aon_vanilla_pack_step; the same bytes in every buffer)
                 packs = ops.vanilla_pack_step(dict(mlps[0].named_parameters()), dict(mlps[1].named_parameters()), degrees=degs[0])
             else:
-                bwd, bwd_ready = packed_bwd_aside(mlps)
-                fine_pk, fine_ready = run_aside(rays_o.device, "fine", lambda: (mlps[1].packed(True),)) if len(mlps) == 2 else (None, None)
-                packs = [(mlps[0].packed(True), bwd[0])] + ([(fine_pk[0], bwd[1])] if len(mlps) == 2 else [])
-            if fine_ready is not None:
-                torch.cuda.current_stream(rays_o.device).wait_event(fine_ready)
-            if bwd_ready is not None and pack_aside_mode() == 2:
-                # no side-stream kernel may be in flight when the forward's persistent launches are dispatched (see pack_aside_mode)
-                torch.cuda.current_stream(rays_o.device).wait_event(bwd_ready)
+                bwd = [m.packed_bwd(True) for m in mlps]
+                packs = [(m.packed(True), b) for m, b in zip(mlps, bwd)]
             params = [p for m in mlps for p in m.ordered_params()]
-            try:
-                flat = RenderVanilla.apply(rays_o, rays["rays_d"], rays["viewdirs"], *[x.detach() if isinstance(x, torch.Tensor) else float(x) for x in (near, far)], bool(white_bkgd),
-                                           self.num_levels, t_rand, u, packs, self._opts, noise, *params)
-            finally:
-                if bwd_ready is not None:   # (behind the forward's launches: free by then; also when the forward raised)
-                    torch.cuda.current_stream(rays_o.device).wait_event(bwd_ready)
+            flat = RenderVanilla.apply(rays_o, rays["rays_d"], rays["viewdirs"], *[x.detach() if isinstance(x, torch.Tensor) else float(x) for x in (near, far)], bool(white_bkgd),
+                                       self.num_levels, t_rand, u, packs, self._opts, noise, *params)
             return [tuple(flat[3 * i: 3 * i + 3]) for i in range(self.num_levels)]
         coarse = self.coarse_mlp.packed()
         fine = self.fine_mlp.packed() if self.num_levels == 2 else None

@@ -5,8 +5,6 @@ same constructor defaults, parameter names (``deformations_linear.*``, ``deforma
 (deformation_mlp=True, enc_after=True, embed_deg=False, 4x128 deformation and view branches) has kernels."""
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.init as init
@@ -192,38 +190,22 @@ class NeRF_AE_Art(nn.Module):
             # training: HIP forward that keeps the activation planes + HIP backward (autograd.RenderArticulated);
             # the per-call block must not alias the cached inference buffer (it is saved for backward)
             mlps = [self.coarse_mlp, self.fine_mlp][: self.num_levels]
-            bwd_ready = fine_ready = None
-            if (len(mlps) == 2 and pack_aside_mode() == 0 and mlps[0].degrees == mlps[1].degrees
-                    and os.environ.get("AON_PACK_STEP", "1") != "0"):
-                # round 6: both networks' streams, per-call blocks and transposed streams in ONE C call -- the four fp64 fold products as one
+            if len(mlps) == 2 and mlps[0].degrees == mlps[1].degrees:
+                # both networks' streams, per-call blocks and transposed streams in ONE C call -- the four fp64 fold products as one
                 # launch in front instead of four in a row with their pack kernels (aon_art_pack_step; the same bytes in every buffer)
                 packs = ops.art_pack_step(dict(mlps[0].named_parameters()), dict(mlps[1].named_parameters()), latents, degrees=mlps[0].degrees)
             else:
-                bwd, bwd_ready = packed_bwd_aside(mlps)
-
-                def level_pack(mlp):     # the per-call latent-folded block + the forward weight stream of one level (prepare | fold -> pack)
-                    return ops.art_prepare(dict(mlp.named_parameters()), latents, degrees=mlp.degrees), mlp.packed(True)
-
-                # (AON_PACK_ASIDE=1/2: the fine level's three launches on a side stream of their own, beside the coarse level's)
-                fine, fine_ready = run_aside(rays_o.device, "fine", lambda: level_pack(mlps[1])) if len(mlps) == 2 else (None, None)
-                small_c, pk_c = level_pack(mlps[0])
-                packs = [(pk_c, small_c, bwd[0])] + ([(fine[1], fine[0], bwd[1])] if len(mlps) == 2 else [])
-            if fine_ready is not None:
-                torch.cuda.current_stream(rays_o.device).wait_event(fine_ready)
-            if bwd_ready is not None and pack_aside_mode() == 2:
-                # no side-stream kernel may be in flight when the forward's persistent launches are dispatched (see pack_aside_mode)
-                torch.cuda.current_stream(rays_o.device).wait_event(bwd_ready)
+                bwd = [m.packed_bwd(True) for m in mlps]
+                # per level: the per-call latent-folded block + the forward weight stream (prepare | fold -> pack)
+                small = [ops.art_prepare(dict(m.named_parameters()), latents, degrees=m.degrees) for m in mlps]
+                packs = [(m.packed(True), sm, b) for m, sm, b in zip(mlps, small, bwd)]
             params = [p for mlp in mlps for p in mlp.ordered_params()]
             # a frozen network (only latents require grad: fitting codes, LitNeRF_AutoDecoder.fit_latents): the same forward and the same latent
             # gradients, bit for bit, from a backward without the weight-gradient stage
             render = RenderArticulated if any(p.requires_grad for p in params) else RenderArticulatedLatents
-            try:
-                flat = render.apply(rays_o, rays["rays_d"], rays["viewdirs"], *[x.detach() if isinstance(x, torch.Tensor) else float(x) for x in (near, far)], bool(white_bkgd),
-                                               self.num_levels, t_rand, u, packs, self._opts, noise, latents["density"], latents["color"],
-                                               latents["articulation"], *params)
-            finally:
-                if bwd_ready is not None:   # (behind the forward's launches: free by then; also when the forward raised)
-                    torch.cuda.current_stream(rays_o.device).wait_event(bwd_ready)
+            flat = render.apply(rays_o, rays["rays_d"], rays["viewdirs"], *[x.detach() if isinstance(x, torch.Tensor) else float(x) for x in (near, far)], bool(white_bkgd),
+                                self.num_levels, t_rand, u, packs, self._opts, noise, latents["density"], latents["color"],
+                                latents["articulation"], *params)
             return [tuple(flat[3 * i: 3 * i + 3]) for i in range(self.num_levels)]
         two = self.num_levels == 2
         pc = self.coarse_mlp.packed()
@@ -258,7 +240,7 @@ from collections import defaultdict  # noqa: E402
 from . import helper  # noqa: E402
 from ..code_library import CodeLibraryArticulated  # noqa: E402
 from ..interface import Harness  # noqa: E402
-from .model import _ray_box_limits, build_adam, pack_aside_mode, packed_bwd_aside, run_aside  # noqa: E402
+from .model import _ray_box_limits, build_adam  # noqa: E402
 
 _SCALAR_KEYS = ("deg", "instance_id", "articulation_id")
 

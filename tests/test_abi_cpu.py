@@ -393,3 +393,28 @@ def test_whole_path_argtypes_equal_the_handwritten_lists():
         assert fn.restype is ctypes.c_int, name
         assert list(fn.argtypes) == [kinds[k] for k in letters.split()], name
         assert list(_lib._SIGS[name][1]) == list(fn.argtypes), name
+
+
+def test_no_experiment_switches_in_the_product_tree():
+    """The product sources carry no timing-experiment switch, and the environment is read for the documented names only: the library
+    path, the three user opt-outs and the two whole-build A/B settings of build.py."""
+    import glob
+
+    import aon_amd
+
+    pkg = os.path.dirname(os.path.abspath(aon_amd.__file__))
+    product = (glob.glob(os.path.join(pkg, "csrc", "*")) + glob.glob(os.path.join(pkg, "models", "**", "*.py"), recursive=True)
+               + [os.path.join(pkg, "autograd.py"), os.path.join(pkg, "build.py")])
+    assert len(product) > 30
+    for path in product:
+        text = open(path).read()
+        for word in ("AON_EXP_", "AON_EXPERIMENT_BUILD", "AON_PIN_PREFETCH", "AON_PER_FILE_FLAGS"):
+            assert word not in text, f"{word} in {os.path.relpath(path, pkg)}"
+    read = set()
+    sources = glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True) + glob.glob(os.path.join(pkg, "csrc", "*"))
+    for path in sources:
+        text = open(path).read()
+        read |= set(re.findall(r"getenv\(\s*\"(AON_[A-Z_]+)\"", text))
+        read |= set(re.findall(r"environ(?:\.get\(|\.pop\(|\.setdefault\(|\[)\s*\"(AON_[A-Z_]+)\"", text))
+        read |= set(re.findall(r"\"(AON_[A-Z_]+)\"\s+(?:not\s+)?in\s+os\.environ", text))
+    assert read == {"AON_HIP_LIB", "AON_BOTTLENECK_FOLD", "AON_ARENA", "AON_FUSED_ADAM", "AON_BUILD_TAG", "AON_EXTRA_FLAGS"}, sorted(read)

@@ -16,9 +16,6 @@ inputs (test_gradient_bits_are_pinned, the chunking / fusion equalities), so the
 
 The two-stream cases are only meaningful with the per-stream caches: the evidence that they discriminate is the CPU mutation check
 (tests/test_stream_cache_cpu.py::test_parent_rule_aliases) plus the data_ptr() assertions of (d); a shared workspace is never raced here."""
-import os
-import subprocess
-import sys
 import threading
 import types
 
@@ -530,30 +527,6 @@ def test_ordering_probe_training_schedules(ops, dev, delay, net, schedule):
         _restore_schedule(ops)
 
 
-@pytest.mark.parametrize("mode", ["1", "2"])
-def test_ordering_probe_pack_aside_child(dev, mode):
-    """AON_PACK_ASIDE is read per call but the side streams are cached: each mode in a fresh child process (this file's __main__)."""
-    env = dict(os.environ, AON_PACK_ASIDE=mode)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True, text=True, timeout=600)
-    print(r.stdout[-2000:], r.stderr[-2000:])
-    assert r.returncode == 0, f"AON_PACK_ASIDE={mode}: child exited {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
-    assert f"child ok AON_PACK_ASIDE={mode} vanilla articulated" in r.stdout
-
-
-def _child():
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    from aon_amd import ops
-    from aon_amd.models.vanilla_nerf.model import pack_aside_mode
-
-    assert pack_aside_mode() in (1, 2)
-    dev = torch.device("cuda:0")
-    enqueue, _ = _make_delay(dev)
-    for fn, n, name in ((_case_vanilla_train, 1024, "vanilla"), (_case_art_train, 768, "articulated")):
-        st, call = fn(ops, dev, n)
-        _probe(dev, enqueue, st, call, f"{name} training step, AON_PACK_ASIDE={pack_aside_mode()}")
-    print(f"child ok AON_PACK_ASIDE={pack_aside_mode()} vanilla articulated")
-
-
 # ------------------------------------------------------------------ (b) two streams, two different jobs
 def _concurrent_pair(dev, delay):
     """Two torch streams whose work demonstrably runs side by side (streams may share a hardware queue, which serialises them: the overlap
@@ -831,7 +804,3 @@ def test_workspaces_are_per_stream_and_released(ops, dev):
     ops.release_workspaces()
     assert all(len(c) == 0 for c in caches.values()) and not ops._TRAIN_POOL
 
-
-if __name__ == "__main__":
-    if "--child" in sys.argv:
-        _child()

@@ -1,7 +1,7 @@
 """Per-kernel timing of the training / render kernels with HIP events on the launch stream (no profiler needed):
 
     python tools/kernel_bench.py [--rays 4096] [--reps 5] [--only fwd_train,art_fwd_train,...]
-    AON_HIP_LIB=articulated-object-nerf_amd/libaon_hip_x.so python tools/kernel_bench.py     # an experiment build
+    AON_HIP_LIB=articulated-object-nerf_amd/libaon_hip_x.so python tools/kernel_bench.py     # another build (AON_BUILD_TAG=x)
 
 One JSON line per kernel: ms per launch, executed and reference-literal TFLOP/s.  Sizes default to one level pair of a
 4096-ray training step (65 and 193 samples per ray)."""

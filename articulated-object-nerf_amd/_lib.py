@@ -36,6 +36,10 @@ _PATH = ([_p, _p, _p, _l]          # rays_o, rays_d, viewdirs, n_rays
          + [_p, _l, _p])           # workspace, workspace_bytes, stream
 _VANILLA, _ART, _GENERAL = [_p] * 2, [_p] * 4, [_p] * 3   # packed c/f | packed, small c/f | aon_mlp_geometry, parameter arrays c/f
 _OPTS, _OCC, _STOP, _BOUNDS = [_p], [_p, _p], [_f, _i, _p], [_p]   # opts | grid, tally | eps, round_samples, stop map | aon_ray_bounds
+# the latent-only backward: streams and per-call blocks | rays_d, n, white_bkgd, num_levels | g_rgb, g_acc, g_depth | parameter arrays |
+# three latent gradients | workspace, scratch, stream | opts
+_LATENTS_BWD = _ART + [_p, _l, _i, _i] + [_p] * 3 + [_p] * 2 + [_p] * 3 + [_p, _l, _p, _l, _p] + _OPTS
+_RAY_GRADS = [_p]   # aon_ray_grads
 
 
 def _path_sigs():
@@ -151,7 +155,10 @@ _SIGS = {
     "aon_art_render_bwd_ex": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p]),
     # latent-only backward of a frozen articulated network
     "aon_train_scratch_bytes_latents": (_l, [_l, _i, _p]),
-    "aon_art_render_bwd_latents": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p]),
+    "aon_art_render_bwd_latents": (_i, _LATENTS_BWD),
+    # ... plus the gradients of rays_o, rays_d, viewdirs: the same list and an aon_ray_grads
+    "aon_train_scratch_bytes_inputs": (_l, [_l, _i, _p]),
+    "aon_art_render_bwd_inputs": (_i, _LATENTS_BWD + _RAY_GRADS),
     # NeRFMLP of any constructor geometry (aon_mlp_geometry first)
     "aon_mlp_geometry_init": (None, [_p]),
     "aon_gmlp_param_count": (_i, [_p]),
@@ -188,6 +195,11 @@ class RenderOptsC(C.Structure):
 class OccupancyC(C.Structure):
     """aon_occupancy (include/aon_hip.h)."""
     _fields_ = [("bits", C.c_void_p), ("cells", C.c_int64 * 3), ("lo", C.c_float * 3), ("step", C.c_float * 3)]
+
+
+class RayGradsC(C.Structure):
+    """aon_ray_grads (include/aon_hip.h)."""
+    _fields_ = [("rays_o", C.c_void_p), ("viewdirs", C.c_void_p), ("g_rays_o", C.c_void_p), ("g_rays_d", C.c_void_p), ("g_viewdirs", C.c_void_p)]
 
 
 class RayBoundsC(C.Structure):

@@ -236,3 +236,51 @@ class RenderArticulatedLatents(torch.autograd.Function):
         ops.pool_give(ws)      # (the backward's launches are enqueued: whoever takes the workspace next is ordered behind them)
         lat = tuple(g_lat[k].reshape(shp) for k, shp in zip(("density", "color", "articulation"), ctx.lat_shapes))
         return (None,) * 12 + lat + (None,) * (n_per * ctx.num_levels)
+
+
+class RenderArticulatedInputs(torch.autograd.Function):
+    """NeRF_AE_Art.forward of a FROZEN network with gradients to its INPUTS: rays_o, rays_d, viewdirs -- whichever
+    of them requires grad -- and the three latents.  RenderArticulatedLatents' forward, saved tensors and released-workspace rules; the
+    backward is aon_art_render_bwd_inputs: the latent gradients are RenderArticulatedLatents' bits, and with no latent requiring grad its
+    latent launches are skipped.  t is data: nothing flows through the sampler, near / far or the inverse-CDF draws.  A tensor passed both
+    as rays_d and as viewdirs (the datasets' convention) receives the sum of the two slots from autograd."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, packs, opts, noise, lat_density, lat_color,
+                lat_articulation, *params):
+        ctx.white_bkgd, ctx.num_levels = white_bkgd, num_levels
+        ctx.set_materialize_grads(False)
+        ctx.lat_shapes = (lat_density.shape, lat_color.shape, lat_articulation.shape)
+        # the backward reads the rays, the latents' weights and views_linear.0 / deformations_linear.0 again: saved the autograd way
+        ctx.save_for_backward(rays_o, rays_d, viewdirs, lat_density, lat_color, lat_articulation, *params)
+        levels, ws, ctx.geometry = ops.render_fwd_train(packs[0][0], packs[1][0] if num_levels == 2 else None, rays_o, rays_d, viewdirs, near, far,
+                                                        white_bkgd, num_levels, t_rand, u, small_c=packs[0][1],
+                                                        small_f=packs[1][1] if num_levels == 2 else None, opts=opts, noise=noise)
+        ctx.fused = (ws, [pk[2] for pk in packs], [pk[1] for pk in packs])   # ONE C call (aon_art_render_fwd_train)
+        return tuple(x for lvl in levels for x in lvl)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        n_per = len(ops.ART_PARAM_ORDER)
+        _check_not_released(ctx)
+        ws, packs_bwd, smalls = ctx.fused
+        saved = ctx.saved_tensors   # (raises if a ray tensor, a latent or a parameter was modified in place since the forward)
+        rays_o, rays_d, viewdirs = saved[:3]
+        n = rays_d.shape[0]
+        g_rgb = [gouts[3 * l] if gouts[3 * l] is not None else torch.zeros((n, 3), dtype=torch.float32, device=rays_d.device)
+                 for l in range(ctx.num_levels)]
+        params = [dict(zip(ops.ART_PARAM_ORDER, saved[6 + l * n_per: 6 + (l + 1) * n_per])) for l in range(ctx.num_levels)]
+        want_lat = any(ctx.needs_input_grad[12:15])
+        g_lat, g_o, g_d, g_v = ops.art_render_bwd_inputs(ws, packs_bwd, smalls, rays_o, rays_d, viewdirs, ctx.white_bkgd, ctx.num_levels, g_rgb,
+                                                         [gouts[3 * l + 1] for l in range(ctx.num_levels)],
+                                                         [gouts[3 * l + 2] for l in range(ctx.num_levels)], params, geometry=ctx.geometry,
+                                                         want_latents=want_lat)
+        ctx.fused, ctx.released, ctx.geometry = None, True, None
+        ops.pool_give(ws)      # (the backward's launches are enqueued: whoever takes the workspace next is ordered behind them)
+        need = ctx.needs_input_grad
+        ray = tuple(g.reshape(t.shape) if need[i] else None for i, (g, t) in enumerate(zip((g_o, g_d, g_v), (rays_o, rays_d, viewdirs))))
+        lat = (None, None, None)
+        if want_lat:
+            lat = tuple(g_lat[k].reshape(shp) if need[12 + i] else None
+                        for i, (k, shp) in enumerate(zip(("density", "color", "articulation"), ctx.lat_shapes)))
+        return ray + (None,) * 9 + lat + (None,) * (n_per * ctx.num_levels)

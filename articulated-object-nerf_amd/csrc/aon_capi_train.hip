@@ -569,9 +569,10 @@ static int train_bwd_impl(const char* who, bool art, const TrainNet* nets, const
 // the partial sums of the four bias gradients a latent enters through.
 struct LatentScratch {
   float* d_raw[2]; float* dplanes[2]; float* dxp[2]; float* ws[2];
+  float* rec[2];   // the ray gradients' per-sample records, behind everything the latent-only call carves
   int64_t bytes;
 };
-LatentScratch carve_scratch_latents(char* base, int64_t n, int num_levels, const Geo& g) {
+LatentScratch carve_scratch_latents(char* base, int64_t n, int num_levels, const Geo& g, bool ray_records = false) {
   LatentScratch sc{};
   int64_t off = 0;
   auto take = [&](int64_t bytes) { char* p = base + off; off += align_up(bytes, 256); return p; };
@@ -582,6 +583,8 @@ LatentScratch carve_scratch_latents(char* base, int64_t n, int num_levels, const
     sc.dxp[l] = reinterpret_cast<float*>(take(Np * 16));
     sc.ws[l] = reinterpret_cast<float*>(take(aon::art_latent_ws_bytes()));
   }
+  if (ray_records)
+    for (int l = 0; l < num_levels; ++l) sc.rec[l] = reinterpret_cast<float*>(take(aon::ray_grad_record_bytes(level_np(n, l, g))));
   sc.bytes = off;
   return sc;
 }
@@ -591,24 +594,28 @@ LatentScratch carve_scratch_latents(char* base, int64_t n, int num_levels, const
 int latent_bwd_impl(const char* who, const TrainNet* nets, const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels,
                     const float* const* g_rgb_host, const float* const* g_acc_host, const float* const* g_depth_host, const float* const* const* params,
                     float* const* g_latents, void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, hipStream_t caller,
-                    const aon_render_opts* opts) {
+                    const aon_render_opts* opts, const aon_ray_grads* rg = nullptr) {
   auto bad = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
   Geo g;
   if (const char* b = make_geo(opts, g)) return fail(AON_E_INVALID, b);
   g.other_degrees = false;   // (the articulated kernels carry their degrees themselves)
   if (n_rays <= 0 || (num_levels != 1 && num_levels != 2)) return bad(AON_E_INVALID, "bad size / num_levels");
-  if (!rays_d || !g_rgb_host || !workspace || !scratch || !g_latents[0] || !g_latents[1] || !g_latents[2]) return bad(AON_E_INVALID, "null pointer");
+  // [ray gradients, DESIGN.md section 4.14] rg: the three latent outputs may all be null (a pose fitted under fixed codes)
+  const bool want_latents = g_latents[0] || g_latents[1] || g_latents[2] || !rg;
+  if (rg && (!rg->rays_o || !rg->viewdirs || !rg->g_rays_o || !rg->g_rays_d || !rg->g_viewdirs)) return bad(AON_E_INVALID, "null member of aon_ray_grads");
+  if (!rays_d || !g_rgb_host || !workspace || !scratch || (want_latents && (!g_latents[0] || !g_latents[1] || !g_latents[2]))) return bad(AON_E_INVALID, "null pointer");
   if (reinterpret_cast<uintptr_t>(scratch) & 255) return bad(AON_E_INVALID, "scratch must be 256-byte aligned");
   const TrainWs w = carve_train(static_cast<char*>(workspace), n_rays, true, num_levels, g);
   if (w.bytes > workspace_bytes) return bad(AON_E_WORKSPACE, "workspace smaller than aon_train_workspace_bytes()");
-  const LatentScratch sc = carve_scratch_latents(static_cast<char*>(scratch), n_rays, num_levels, g);
-  if (sc.bytes > scratch_bytes) return bad(AON_E_WORKSPACE, "scratch smaller than aon_train_scratch_bytes_latents()");
+  const LatentScratch sc = carve_scratch_latents(static_cast<char*>(scratch), n_rays, num_levels, g, rg != nullptr);
+  if (sc.bytes > scratch_bytes)
+    return bad(AON_E_WORKSPACE, rg ? "scratch smaller than aon_train_scratch_bytes_inputs()" : "scratch smaller than aon_train_scratch_bytes_latents()");
   for (int l = 0; l < num_levels; ++l) {
     const void* pb = nets[l].packed_bwd;
     if (!pb || !nets[l].small || !params[l] || !g_rgb_host[l]) return bad(AON_E_INVALID, "null level pointer");
     if (aon::stream_form(pb) != aon::stream_form(nets[l].small) || aon::stream_form(pb) != aon::stream_form(nets[0].packed_bwd))
       return bad(AON_E_INVALID, "transposed stream and per-call block were made in different forms (aon_set_bottleneck_fold changed in between)");
-    for (int i : {0, 10, 20, 26})   // the weights a latent enters: all the W^T db products read
+    for (int i : {0, 10, 20, 26})   // the weights a latent enters: all the W^T db products read (the ray gradients read 0 and 26)
       if (!params[l][i]) return bad(AON_E_INVALID, "null parameter pointer");
   }
   for (int l = 0; l < num_levels; ++l) {
@@ -637,7 +644,18 @@ int latent_bwd_impl(const char* who, const TrainNet* nets, const float* rays_d, 
   aon::ArtLatentLevel lv[2];
   for (int l = 0; l < num_levels; ++l) lv[l] = aon::ArtLatentLevel{sc.dplanes[l], w.lvl[l].Np, nets[l].packed_bwd, params[l], sc.ws[l]};
   KTimer timer(kWgrad, caller, w.lvl[0].Np + (num_levels == 2 ? w.lvl[1].Np : 0));   // (the class of the stage it replaces)
-  return check(aon::launch_art_latent_grads(lv, num_levels, g.max_deg - g.min_deg, g.deg_view, g_latents[0], g_latents[1], g_latents[2], caller), who);
+  if (want_latents)
+    if (int rc = check(aon::launch_art_latent_grads(lv, num_levels, g.max_deg - g.min_deg, g.deg_view, g_latents[0], g_latents[1], g_latents[2], caller), who))
+      return rc;
+  if (!rg) return AON_OK;
+  // the ray gradients read what the chain left (gradient planes, dxp) and the forward's t / raw: two launches behind the latent ones
+  aon::RayGradLevel rl[2];
+  for (int l = 0; l < num_levels; ++l) {
+    const TrainLevel& L = w.lvl[l];
+    rl[l] = aon::RayGradLevel{sc.dplanes[l], sc.dxp[l], L.Np, params[l], sc.rec[l], L.t, L.raw, g_rgb_host[l], g_acc_host ? g_acc_host[l] : nullptr,
+                              g_depth_host ? g_depth_host[l] : nullptr, g.act(true, l, 0), L.S};
+  }
+  return check(aon::launch_ray_grads(rl, num_levels, n_rays, g.deg_view, white_bkgd, rays_d, rg->viewdirs, rg->g_rays_o, rg->g_rays_d, rg->g_viewdirs, caller), who);
 }
 
 }  // namespace
@@ -805,6 +823,30 @@ int aon_art_render_bwd_latents(const void* packed_bwd_coarse, const void* small_
   float* g_latents[3] = {g_shape, g_appearance, g_articulation};
   return latent_bwd_impl("aon_art_render_bwd_latents", nets, rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, params,
                          g_latents, workspace, workspace_bytes, scratch, scratch_bytes, (hipStream_t)stream_, opts);
+}
+
+
+// ---- ray gradients of a frozen articulated network ----
+int64_t aon_train_scratch_bytes_inputs(int64_t n_rays, int num_levels, const aon_render_opts* opts) {
+  Geo g;
+  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
+  return carve_scratch_latents(nullptr, n_rays < 1 ? 1 : n_rays, num_levels == 1 ? 1 : 2, g, true).bytes;
+}
+int aon_art_render_bwd_inputs(const void* packed_bwd_coarse, const void* small_coarse, const void* packed_bwd_fine, const void* small_fine,
+                              const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels, const float* const* g_rgb_host,
+                              const float* const* g_acc_host, const float* const* g_depth_host, const float* const* params_coarse_host,
+                              const float* const* params_fine_host, float* g_shape, float* g_appearance, float* g_articulation,
+                              void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, void* stream_,
+                              const aon_render_opts* opts, const aon_ray_grads* rg) {
+  if (!rg)
+    return aon_art_render_bwd_latents(packed_bwd_coarse, small_coarse, packed_bwd_fine, small_fine, rays_d, n_rays, white_bkgd, num_levels, g_rgb_host,
+                                      g_acc_host, g_depth_host, params_coarse_host, params_fine_host, g_shape, g_appearance, g_articulation, workspace,
+                                      workspace_bytes, scratch, scratch_bytes, stream_, opts);
+  const TrainNet nets[2] = {{nullptr, static_cast<const float*>(small_coarse), packed_bwd_coarse}, {nullptr, static_cast<const float*>(small_fine), packed_bwd_fine}};
+  const float* const* params[2] = {params_coarse_host, params_fine_host};
+  float* g_latents[3] = {g_shape, g_appearance, g_articulation};
+  return latent_bwd_impl("aon_art_render_bwd_inputs", nets, rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, params,
+                         g_latents, workspace, workspace_bytes, scratch, scratch_bytes, (hipStream_t)stream_, opts, rg);
 }
 
 }  // extern "C"

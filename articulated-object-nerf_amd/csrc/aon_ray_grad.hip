@@ -1,0 +1,298 @@
+// Ray gradients of a FROZEN articulated network: dL/d rays_o, dL/d rays_d and dL/d viewdirs from what the backward
+// chain (aon_train_art.hip) already leaves behind -- d x' per sample (ChainSeg::dxp) and the pre-activation gradients of
+// deformations_linear.0 and views_linear.0 in the gradient planes.  Two ordinary launches on the caller's stream, both levels in each; no
+// MFMA, no atomics, nothing that depends on the launch geometry.
+//
+//   x_i = o + t_i d (t is data: the coarse t depends on near / far only, the fine t is detached, helper.py:249):
+//     g_x_i = dxp_i + W_d0[:, 0:3]^T dZ_d0,i          g_o = sum_i g_x_i          g_d = sum_i t_i g_x_i + g_n d / |d|
+//   viewdirs enters through pos_enc(viewdirs, 0, deg_view), a constant of the ray:
+//     g_ve = sum_i W_v0[:, 256 : 256 + V]^T dZ_v0,i   g_viewdirs = g_ve pulled back through the encoding at the forward's rounded arguments
+//   |d| scales the interval lengths of the compositing (helper.py:167):
+//     g_n = sum_i dL/dalpha_i (1 - alpha_i) sigma_i delta_i     (fp64 from raw, t, dirs and the upstream gradients, as composite_bwd_kernel)
+//
+//   ray_grad_sample_kernel   lane = sample.  A sample's 128 values of a layer are 32 units of 16 B, 512 B apart inside its step; the 32
+//                            samples of a step sit side by side, so a wave's load is two whole 512-byte runs.  3 + 27 fused multiply-add
+//                            chains over the 128 features in ascending order against weight columns held in LDS; one 128-byte record
+//                            {g_x (3), view-encoding partials (27), 0, 0} per sample.
+//   ray_grad_reduce_kernel   one wavefront per ray.  Lane c < 32 sums component c of the ray's records in fp64, sample after sample in
+//                            ascending order; lane 32 + c the same values times t_i.  Then the norm term (composite_bwd_kernel's two scans)
+//                            and the view encoding's backward; every output is rounded to fp32 once.
+#include "aon_art_common.h"
+#include "aon_launch.h"
+
+namespace aon {
+
+namespace {
+
+constexpr int kRecFloats = 32;    // g_x at 0..2, the view-encoding partials at 3..29
+constexpr int kRecView = 3;
+constexpr int kWvCols = 28;       // 27 view-encoding columns padded to whole float4s
+
+struct RgSampleSeg {
+  const float* dplanes;   // the level's gradient planes (chain output)
+  const float* dxp;       // (Np,4)
+  const float* Wd0;       // deformations_linear.0.weight (128, 163)
+  const float* Wv0;       // views_linear.0.weight (128, 256 + V + 128)
+  float* rec;             // (n * S, 32)
+  int64_t nvalid;         // n * S: padding samples are neither read nor written
+  int blk_begin;
+};
+struct RgSampleArgs {
+  RgSampleSeg seg[2];
+  int nsegs, V;
+};
+
+__global__ void __launch_bounds__(256) ray_grad_sample_kernel(RgSampleArgs a) {
+  __shared__ __attribute__((aligned(16))) float wd[128 * 4];
+  __shared__ __attribute__((aligned(16))) float wv[128 * kWvCols];
+  const int tid = (int)threadIdx.x;
+  const int si = (a.nsegs > 1 && (int)blockIdx.x >= a.seg[1].blk_begin) ? 1 : 0;
+  const RgSampleSeg& S = a.seg[si];
+  const int ldv = 256 + a.V + 128;
+  for (int i = tid; i < 128 * 4; i += 256) wd[i] = (i & 3) < 3 ? S.Wd0[(i >> 2) * 163 + (i & 3)] : 0.f;
+  for (int i = tid; i < 128 * kWvCols; i += 256) {
+    const int f = i / kWvCols, c = i % kWvCols;
+    wv[i] = c < a.V ? S.Wv0[(int64_t)f * ldv + 256 + c] : 0.f;
+  }
+  __syncthreads();
+  const int64_t n = (int64_t)((int)blockIdx.x - S.blk_begin) * 256 + tid;
+  if (n >= S.nvalid) return;
+  // feature row f of sample n: ((n >> 5) * (rows / 4) + (f >> 2)) * 128 + (n & 31) * 4 + (f & 3)   (aon_mlp_core.h)
+  const float* base = S.dplanes + (n >> 5) * ((int64_t)kAPlRows * 32) + (int)(n & 31) * 4;
+  const float* pd = base + (aplane_d(0) / 4) * 128;
+  const float* pv = base + (aplane_v(0) / 4) * 128;
+  float out[kRecFloats];
+#pragma unroll
+  for (int k = 0; k < kRecFloats; ++k) out[k] = 0.f;
+#pragma unroll 4
+  for (int u = 0; u < 32; ++u) {
+    const f32x4 z = *reinterpret_cast<const f32x4*>(pd + u * 128);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const f32x4 w = *reinterpret_cast<const f32x4*>(wd + (4 * u + j) * 4);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) out[k] = __builtin_fmaf(w[k], z[j], out[k]);
+    }
+  }
+#pragma unroll 2
+  for (int u = 0; u < 32; ++u) {
+    const f32x4 z = *reinterpret_cast<const f32x4*>(pv + u * 128);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int q = 0; q < kWvCols / 4; ++q) {
+        const f32x4 w = *reinterpret_cast<const f32x4*>(wv + (4 * u + j) * kWvCols + 4 * q);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (4 * q + k < 27) out[kRecView + 4 * q + k] = __builtin_fmaf(w[k], z[j], out[kRecView + 4 * q + k]);
+      }
+    }
+  }
+  const f32x4 dx = *reinterpret_cast<const f32x4*>(S.dxp + n * 4);   // x' = deformation_layer(..) + x: the identity path
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[k] = __fadd_rn(dx[k], out[k]);
+  f32x4* dst = reinterpret_cast<f32x4*>(S.rec + n * kRecFloats);
+#pragma unroll
+  for (int q = 0; q < kRecFloats / 4; ++q) {
+    f32x4 v; v[0] = out[4 * q]; v[1] = out[4 * q + 1]; v[2] = out[4 * q + 2]; v[3] = out[4 * q + 3];
+    dst[q] = v;
+  }
+}
+
+struct RgReduceLevel {
+  const float* rec; const float* t; const float* raw;
+  const float* g_rgb; const float* g_acc; const float* g_depth;
+  ActParams ap;
+  int S;
+};
+struct RgReduceArgs {
+  RgReduceLevel lvl[2];
+  int nlevels, white_bkgd, Lv;
+  int64_t n_rays;
+  const float* rays_d; const float* viewdirs;
+  float* g_o; float* g_d; float* g_v;
+};
+
+__device__ __forceinline__ double rg_sigmoidd(double x) { return 1.0 / (1.0 + exp(-x)); }
+__device__ __forceinline__ double rg_wsum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// g_n of one ray at one level: composite_bwd_kernel's two scans (aon_train.hip) with dalpha_i / d|d| = (1 - alpha_i) sigma_i delta_i in the
+// place of dalpha_i / d raw_sigma_i.  fp64 on the forward's fp32 inputs; the same value in every lane.
+template <int NB>
+__device__ __forceinline__ double rg_norm_term(const RgReduceLevel& L, const int64_t ray, const int lane, const float dn, const int white_bkgd) {
+  const int S = L.S;
+  const ActParams ap = L.ap;
+  const int nblk = (S + 63) >> 6;
+  const float* tv = L.t + ray * S;
+  const double gC0 = L.g_rgb[ray * 3], gC1 = L.g_rgb[ray * 3 + 1], gC2 = L.g_rgb[ray * 3 + 2];
+  const double gA = L.g_acc ? (double)L.g_acc[ray] : 0.0, gD = L.g_depth ? (double)L.g_depth[ray] : 0.0;
+  const double gw_const = gA - (white_bkgd ? (gC0 + gC1 + gC2) : 0.0);
+  double tgw[NB], f[NB], kn[NB], wgw[NB];   // T_i gw_i;  1 - alpha_i + 1e-10;  d alpha_i / d |d|;  w_i gw_i
+  double carry = 1.0;
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    tgw[b] = 0.0; f[b] = 1.0; kn[b] = 0.0; wgw[b] = 0.0;
+    if (b < nblk) {
+      const int s = b * 64 + lane;
+      const bool in = s < S;
+      double alpha = 0.0, gw = 0.0;
+      if (in) {
+        const int64_t g = ray * S + s;
+        const float t = tv[s];
+        const float delta = s == S - 1 ? 1e10f : __fsub_rn(tv[s + 1], t);
+        const double dist = (double)__fmul_rn(delta, dn);
+        float4 r = reinterpret_cast<const float4*>(L.raw)[g];
+        if (ap.noise) r.w = __fadd_rn(r.w, __fmul_rn(ap.noise[g], ap.noise_std));
+        double sg, c0, c1, c2;
+        if (ap.act == 1) {
+          sg = r.w > 0.f ? (double)r.w : 0.0;
+          c0 = rg_sigmoidd(r.x); c1 = rg_sigmoidd(r.y); c2 = rg_sigmoidd(r.z);
+        } else if (ap.act == 2) {
+          const float xs = __fadd_rn(r.w, ap.sigma_bias);
+          sg = xs > 20.0f ? (double)xs : log1p(exp((double)xs));
+          const double sc = ap.rgb_scale, sh = ap.rgb_shift;
+          c0 = rg_sigmoidd(r.x) * sc - sh; c1 = rg_sigmoidd(r.y) * sc - sh; c2 = rg_sigmoidd(r.z) * sc - sh;
+        } else {
+          sg = r.w; c0 = r.x; c1 = r.y; c2 = r.z;
+        }
+        const double ex = exp(-sg * dist);
+        alpha = 1.0 - ex;
+        f[b] = (1.0 - alpha) + 1e-10;
+        kn[b] = ex * sg * (double)delta;
+        gw = gC0 * c0 + gC1 * c1 + gC2 * c2 + gw_const + (double)t * gD;
+      }
+      double incl = f[b];
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const double o = __shfl_up(incl, off);
+        if (lane >= off) incl = incl * o;
+      }
+      double excl = __shfl_up(incl, 1);
+      if (lane == 0) excl = 1.0;
+      const double T = carry * excl;
+      carry = carry * __shfl(incl, 63);
+      tgw[b] = T * gw;
+      wgw[b] = in ? alpha * T * gw : 0.0;
+    }
+  }
+  double part = 0.0, sfx_carry = 0.0;
+#pragma unroll
+  for (int b = NB - 1; b >= 0; --b) {
+    if (b < nblk) {
+      double incl = wgw[b];
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const double o = __shfl_down(incl, off);
+        if (lane + off < 64) incl = incl + o;
+      }
+      double excl = __shfl_down(incl, 1);
+      if (lane == 63) excl = 0.0;
+      const double sfx = excl + sfx_carry;
+      sfx_carry = sfx_carry + __shfl(incl, 0);
+      if (b * 64 + lane < S) part += (tgw[b] - sfx / f[b]) * kn[b];   // dL/dalpha_i * dalpha_i/d|d|
+    }
+  }
+  return rg_wsum(part);
+}
+
+template <int NB>
+__global__ void __launch_bounds__(256) ray_grad_reduce_kernel(RgReduceArgs a) {
+  const int lane = (int)threadIdx.x & 63;
+  const int64_t ray = (int64_t)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  if (ray >= a.n_rays) return;
+  const float d0 = a.rays_d[ray * 3], d1 = a.rays_d[ray * 3 + 1], d2 = a.rays_d[ray * 3 + 2];
+  // |d| as the forward takes it (fp32, helper.py:167)
+  const float dn = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+  const int c = lane & 31;
+  const bool weighted = lane >= 32;
+  double acc = 0.0, gn = 0.0;
+  for (int l = 0; l < a.nlevels; ++l) {
+    const RgReduceLevel& L = a.lvl[l];
+    const int S = L.S;
+    const float* rec = L.rec + ray * S * kRecFloats + c;   // a record is one 128-byte line: lanes 0..31 read it whole
+    const float* tv = L.t + ray * S;
+    int i = 0;
+    for (; i + 8 <= S; i += 8) {
+      float r[8], t[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { r[k] = rec[(i + k) * kRecFloats]; t[k] = tv[i + k]; }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc += weighted ? (double)t[k] * (double)r[k] : (double)r[k];
+    }
+    for (; i < S; ++i) {
+      const float r = rec[i * kRecFloats], t = tv[i];
+      acc += weighted ? (double)t * (double)r : (double)r;
+    }
+    gn += rg_norm_term<NB>(L, ray, lane, dn, a.white_bkgd);
+  }
+  // view encoding, backwards: columns [v ; sin(2^l v) (level-major, xyz-minor) ; sin(2^l v + fp32(pi/2))] in ascending order
+  const float vd[3] = {a.viewdirs[ray * 3], a.viewdirs[ray * 3 + 1], a.viewdirs[ray * 3 + 2]};
+  double gv[3] = {0.0, 0.0, 0.0};
+  const int V = 3 + 6 * a.Lv;
+  for (int ci = 0; ci < V; ++ci) {
+    const double g = __shfl(acc, kRecView + ci);
+    int ax = ci;
+    double coef = 1.0;
+    if (ci >= 3) {
+      const int e = ci - 3, second = e >= 3 * a.Lv ? 1 : 0;
+      const int e2 = second ? e - 3 * a.Lv : e;
+      ax = e2 % 3;
+      const float scale = (float)(1 << (e2 / 3));
+      const float v = ax == 0 ? vd[0] : (ax == 1 ? vd[1] : vd[2]);
+      const float arg = __fadd_rn(__fmul_rn(v, scale), second ? AON_HALF_PI_F32 : 0.f);
+      coef = (double)scale * (double)cos_f32(arg);
+    }
+    const double term = coef * g;
+    gv[0] += ax == 0 ? term : 0.0;
+    gv[1] += ax == 1 ? term : 0.0;
+    gv[2] += ax == 2 ? term : 0.0;
+  }
+  const double tsum = __shfl(acc, (lane + 32) & 63);   // lanes 0..2: sum_i t_i g_x_i
+  if (lane < 3) {
+    const double dd = lane == 0 ? (double)d0 : (lane == 1 ? (double)d1 : (double)d2);
+    const double n64 = sqrt((double)d0 * d0 + (double)d1 * d1 + (double)d2 * d2);
+    a.g_o[ray * 3 + lane] = (float)acc;
+    a.g_d[ray * 3 + lane] = (float)(tsum + (n64 > 0.0 ? gn * dd / n64 : 0.0));
+    a.g_v[ray * 3 + lane] = (float)(lane == 0 ? gv[0] : (lane == 1 ? gv[1] : gv[2]));
+  }
+}
+
+}  // namespace
+
+int64_t ray_grad_record_bytes(int64_t n_samples) { return n_samples * kRecFloats * 4; }
+
+hipError_t launch_ray_grads(const RayGradLevel* lv, int nlevels, int64_t n_rays, int view_levels, int white_bkgd, const float* rays_d,
+                            const float* viewdirs, float* g_rays_o, float* g_rays_d, float* g_viewdirs, hipStream_t stream) {
+  if (nlevels < 1 || nlevels > 2 || n_rays <= 0 || view_levels < 0 || view_levels > 4) return hipErrorInvalidValue;
+  if (!rays_d || !viewdirs || !g_rays_o || !g_rays_d || !g_viewdirs) return hipErrorInvalidValue;
+  RgSampleArgs A{};
+  RgReduceArgs R{};
+  A.nsegs = nlevels; A.V = 3 + 6 * view_levels;
+  R.nlevels = nlevels; R.white_bkgd = white_bkgd; R.Lv = view_levels; R.n_rays = n_rays;
+  R.rays_d = rays_d; R.viewdirs = viewdirs; R.g_o = g_rays_o; R.g_d = g_rays_d; R.g_v = g_viewdirs;
+  int64_t blk = 0;
+  int smax = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    const RayGradLevel& L = lv[l];
+    if (!L.dplanes || !L.dxp || !L.params || !L.params[0] || !L.params[26] || !L.rec || !L.t || !L.raw || !L.g_rgb) return hipErrorInvalidValue;
+    const int64_t nvalid = n_rays * L.S;
+    if (L.S < 1 || L.S > 512 || nvalid > L.Np) return hipErrorInvalidValue;
+    A.seg[l] = RgSampleSeg{L.dplanes, L.dxp, L.params[0], L.params[26], L.rec, nvalid, (int)blk};
+    blk += (nvalid + 255) / 256;
+    if (blk > 0x7fffffff) return hipErrorInvalidValue;
+    R.lvl[l] = RgReduceLevel{L.rec, L.t, L.raw, L.g_rgb, L.g_acc, L.g_depth, L.ap, L.S};
+    smax = L.S > smax ? L.S : smax;
+  }
+  ray_grad_sample_kernel<<<dim3((unsigned)blk), dim3(256), 0, stream>>>(A);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  const dim3 grid((unsigned)((n_rays + 3) / 4));
+  if (smax <= 256) ray_grad_reduce_kernel<4><<<grid, dim3(256), 0, stream>>>(R);
+  else ray_grad_reduce_kernel<8><<<grid, dim3(256), 0, stream>>>(R);
+  return hipGetLastError();
+}
+
+}  // namespace aon

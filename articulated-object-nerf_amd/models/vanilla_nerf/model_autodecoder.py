@@ -10,7 +10,7 @@ import torch.nn as nn
 import torch.nn.init as init
 
 from ... import ops
-from ...autograd import RenderArticulated, RenderArticulatedLatents
+from ...autograd import RenderArticulated, RenderArticulatedInputs, RenderArticulatedLatents
 
 
 class NeRFMLP(nn.Module):
@@ -185,8 +185,9 @@ class NeRF_AE_Art(nn.Module):
                      for lvl in range(self.num_levels)]
         else:
             noise = None
+        ray_grad = any(getattr(rays[k], "requires_grad", False) for k in ("rays_o", "rays_d", "viewdirs"))
         if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
-                                        or any(getattr(v, "requires_grad", False) for v in latents.values())):
+                                        or any(getattr(v, "requires_grad", False) for v in latents.values()) or ray_grad):
             # training: HIP forward that keeps the activation planes + HIP backward (autograd.RenderArticulated);
             # the per-call block must not alias the cached inference buffer (it is saved for backward)
             mlps = [self.coarse_mlp, self.fine_mlp][: self.num_levels]
@@ -202,7 +203,9 @@ class NeRF_AE_Art(nn.Module):
             params = [p for mlp in mlps for p in mlp.ordered_params()]
             # a frozen network (only latents require grad: fitting codes, LitNeRF_AutoDecoder.fit_latents): the same forward and the same latent
             # gradients, bit for bit, from a backward without the weight-gradient stage
-            render = RenderArticulated if any(p.requires_grad for p in params) else RenderArticulatedLatents
+            # ... and when, on a frozen network, a ray tensor requires grad (refining a camera pose, LitNeRF_AutoDecoder.fit_pose): that backward
+            # plus the gradients of rays_o, rays_d and viewdirs.  A network that trains gives the rays none, as ever.
+            render = RenderArticulated if any(p.requires_grad for p in params) else (RenderArticulatedInputs if ray_grad else RenderArticulatedLatents)
             flat = render.apply(rays_o, rays["rays_d"], rays["viewdirs"], *[x.detach() if isinstance(x, torch.Tensor) else float(x) for x in (near, far)], bool(white_bkgd),
                                 self.num_levels, t_rand, u, packs, self._opts, noise, latents["density"], latents["color"],
                                 latents["articulation"], *params)
@@ -382,6 +385,95 @@ class LitNeRF_AutoDecoder(Harness):
             out[k] = arena[0, off: off + d].view(1, d).clone()
             off += d
         return out, losses
+
+    def fit_pose(self, batches, steps: int, lr=5.0e-3, codes="mean", poses=None, fit_codes: bool = False, seed: int = 0):
+        """Refine the camera pose of observed views of ONE object with the network FROZEN (iNeRF-style), alone or
+        together with its three codes: `steps` Adam steps against the reference's training_step loss (helper.train_loss), view
+        `i % len(batches)` at step i.
+
+        batches: one dict per VIEW with "directions" (camera-space ray directions, (N, 3) or (H, W, 3): ops.ray_directions, or a subset of
+        its pixels) and "target" (N, 3).  poses: the initial (3, 4) camera-to-world matrix of every view.  One 6-vector (omega, tau) is
+        kept per view and applied as R = exp([omega]x) R0, t = t0 + tau (ops.rays_from_pose).  codes: as fit_latents' `init`.  fit_codes:
+        step the (4, 288) code buffer too.  lr: one rate, or (pose rate, code rate).  seed: as fit_latents.
+        -> (list of corrected (3, 4) poses, codes dict of (1, dim) tensors, per-step losses as one (steps,) device tensor); no host
+        synchronisation per step.
+
+        The network's requires_grad flags are cleared for the duration and restored; with them cleared and the rays requiring grad,
+        NeRF_AE_Art.forward takes autograd.RenderArticulatedInputs.  Every buffer is stepped by aon_adam_step; a view's 6-vector keeps its
+        own step count.  Scalar near / far only (a ray box's per-ray limits would move with the pose and carry no gradient)."""
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise ValueError(f"fit_pose: steps must be a positive int, got {steps!r}")
+        batches = list(batches)
+        if not batches:
+            raise ValueError("fit_pose: no batches")
+        poses = [] if poses is None else list(poses)
+        if len(poses) != len(batches):
+            raise ValueError(f"fit_pose: one (3, 4) pose per view: {len(batches)} views, {len(poses)} poses")
+        lrs = tuple(lr) if isinstance(lr, (tuple, list)) else (lr, lr)
+        if len(lrs) != 2 or not all(isinstance(x, (int, float)) and x > 0 for x in lrs):
+            raise ValueError(f"fit_pose: lr must be positive (one rate, or a pair for poses and codes), got {lr!r}")
+        if self.ray_box is not None:
+            raise NotImplementedError("fit_pose: per-ray near / far from a ray box are not differentiated; use the scalar near / far")
+        for b in batches:
+            if "directions" not in b or "target" not in b:
+                raise ValueError("fit_pose: every batch needs 'directions' (camera-space) and 'target'")
+        dev = next(self.model.parameters()).device
+        lat0 = self._initial_latents(codes, dev)
+        pose0 = []
+        for c2w in poses:
+            c = torch.as_tensor(c2w, dtype=torch.float32).detach().to(dev)
+            if c.dim() != 2 or c.shape[0] < 3 or c.shape[1] != 4:
+                raise ValueError(f"fit_pose: a pose must be a (3, 4) matrix, got {tuple(c.shape)}")
+            pose0.append(c[:3].contiguous())
+        keys, dims = ("density", "color", "articulation"), (128, 128, 32)
+        arena = torch.zeros((4, sum(dims)), dtype=torch.float32, device=dev)          # rows: codes, gradients, exp_avg, exp_avg_sq
+        parena = torch.zeros((4, 6 * len(batches)), dtype=torch.float32, device=dev)  # the same rows for the views' 6-vectors
+        leaves, off = {}, 0
+        for k, d in zip(keys, dims):
+            view = arena[0, off: off + d].view(1, d)
+            view.copy_(lat0[k])
+            leaves[k] = view.detach().requires_grad_(bool(fit_codes))
+            off += d
+        corr = [parena[0, 6 * v: 6 * v + 6].detach().requires_grad_(True) for v in range(len(batches))]
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        net_params = list(self.model.parameters())
+        flags = [p.requires_grad for p in net_params]
+        losses = torch.zeros(steps, dtype=torch.float32, device=dev)
+        try:
+            for p in net_params:
+                p.requires_grad_(False)
+            with torch.enable_grad():
+                for i in range(steps):
+                    v = i % len(batches)
+                    directions = batches[v]["directions"].to(device=dev, dtype=torch.float32)
+                    target = batches[v]["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
+                    rays_o, rays_d = ops.rays_from_pose(directions, pose0[v], corr[v])
+                    rays = {"rays_o": rays_o, "rays_d": rays_d, "viewdirs": rays_d}
+                    t_rand = u = None
+                    if self.randomized:
+                        n = rays_d.shape[0]
+                        t_rand = torch.rand((n, self.model.num_coarse_samples + 1), device=dev, generator=gen)
+                        u = torch.rand((n, self.model.num_fine_samples), device=dev, generator=gen) if self.model.num_levels == 2 else None
+                    rendered = self.model(rays, self.randomized, self.white_bkgd, self.near, self.far, leaves, t_rand=t_rand, u=u)
+                    loss, _ = helper.train_loss(rendered, target, tuple(leaves[k] for k in keys), 1e-4)
+                    grads = torch.autograd.grad(loss, [corr[v]] + ([leaves[k] for k in keys] if fit_codes else []))
+                    parena[1, 6 * v: 6 * v + 6].copy_(grads[0])
+                    losses[i] = loss.detach()
+                    ops.adam_step(parena[0], parena[1], parena[2], parena[3], 6 * v, 6, float(lrs[0]), 0.9, 0.999, 1e-8, i // len(batches) + 1)
+                    if fit_codes:
+                        torch.cat([g.reshape(-1) for g in grads[1:]], out=arena[1])
+                        ops.adam_step(arena[0], arena[1], arena[2], arena[3], 0, arena.shape[1], float(lrs[1]), 0.9, 0.999, 1e-8, i + 1)
+        finally:
+            for p, f in zip(net_params, flags):
+                p.requires_grad_(f)
+        with torch.no_grad():
+            fitted = [ops.apply_pose_correction(pose0[v], parena[0, 6 * v: 6 * v + 6]) for v in range(len(batches))]
+        off, out = 0, {}
+        for k, d in zip(keys, dims):
+            out[k] = arena[0, off: off + d].view(1, d).clone()
+            off += d
+        return fitted, out, losses
 
     def _render_chunks(self, batch, latents, skip=()):
         B = batch["rays_o"].shape[0]

@@ -1266,6 +1266,80 @@ def art_render_bwd_latents(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels
     return g_lat
 
 
+def train_scratch_inputs(device, n_rays: int, num_levels: int = 2, st=None) -> torch.Tensor:
+    """`train_scratch_latents` plus the ray gradients' per-sample records (128 B a sample), pooled alike."""
+    return _pool_take(int(lib.aon_train_scratch_bytes_inputs(n_rays, num_levels, None if st is None else C.byref(st))),
+                      "aon_train_scratch_bytes_inputs", device)
+
+
+def art_render_bwd_inputs(ws, packs_bwd, smalls, rays_o, rays_d, viewdirs, white_bkgd, num_levels, g_rgb, g_acc, g_depth, params_per_level,
+                          geometry=None, want_latents: bool = True):
+    """loss.backward() through render_fwd_train of a FROZEN articulated network, down to its inputs -> (dict of the three latent gradients,
+    bit-equal to `art_render_bwd_latents`' -- or None when `want_latents` is false: the latent launches are skipped --, g_rays_o, g_rays_d,
+    g_viewdirs), each (n, 3), summed over the levels.  t is data: no gradient through the sampler or near / far."""
+    d, o, v = _f32(rays_d, "rays_d"), _f32(rays_o, "rays_o"), _f32(viewdirs, "viewdirs")
+    n, dev = d.shape[0], d.device
+    st = None if geometry is None else geometry[0]
+    degrees = (0, 10, 4) if st is None else (int(st.min_deg_point), int(st.max_deg_point), int(st.deg_view))
+    tens, parr = [], []
+    for params in params_per_level:
+        t, arr = _art_param_array(params, degrees)
+        tens.append(t)
+        parr.append(arr)
+    parr += [None] * (2 - num_levels)
+    pb, sm = list(packs_bwd) + [None] * (2 - num_levels), list(smalls) + [None] * (2 - num_levels)
+    g_lat = None
+    if want_latents:
+        g_lat = {"density": torch.empty(128, device=dev), "color": torch.empty(128, device=dev), "articulation": torch.empty(32, device=dev)}
+    lat_ptrs = [None if g_lat is None else _ptr(g_lat[k]) for k in ("density", "color", "articulation")]
+    g_o, g_d, g_v = (torch.empty((n, 3), dtype=torch.float32, device=dev) for _ in range(3))
+    rg = _lib.RayGradsC(o.data_ptr(), v.data_ptr(), g_o.data_ptr(), g_d.data_ptr(), g_v.data_ptr())
+    keep = [None if t is None else _f32(t, "grad") for t in list(g_rgb) + list(g_acc) + list(g_depth)]
+    k = num_levels
+    scratch = train_scratch_inputs(dev, n, num_levels, st)
+    with torch.cuda.device(dev):
+        check(lib.aon_art_render_bwd_inputs(_pk(pb[0]), _pk(sm[0]), _pk(pb[1]), _pk(sm[1]), _ptr(d), n, int(bool(white_bkgd)), num_levels,
+                                            _ptr_array(keep[:k]), _ptr_array(keep[k:2 * k]), _ptr_array(keep[2 * k:3 * k]), parr[0], parr[1],
+                                            *lat_ptrs, _ptr(ws), ws.numel(), _ptr(scratch), scratch.numel(), _stream(),
+                                            None if st is None else C.byref(st), C.byref(rg)),
+              "aon_art_render_bwd_inputs")
+    pool_give(scratch)
+    return g_lat, g_o, g_d, g_v
+
+
+# ------------------------------------------------------------------ differentiable rays from a camera pose (torch ops on (N, 3): no kernel)
+def so3_exp(omega: torch.Tensor) -> torch.Tensor:
+    """exp([omega]x), (3,) -> (3, 3), by Rodrigues' formula; differentiable at omega = 0 (the coefficients switch to their Taylor series
+    below |omega|^2 = 1e-4, where the closed forms lose their digits and the norm its gradient).  exp(0) is the identity exactly."""
+    w = omega.reshape(3)
+    z = torch.zeros((), dtype=w.dtype, device=w.device)
+    K = torch.stack([torch.stack([z, -w[2], w[1]]), torch.stack([w[2], z, -w[0]]), torch.stack([-w[1], w[0], z])])
+    t2 = (w * w).sum()
+    small = t2 < 1e-4
+    th = torch.sqrt(torch.where(small, torch.ones_like(t2), t2))   # (a safe argument where the series is taken: no 0 * inf in the backward)
+    a = torch.where(small, 1.0 - t2 / 6.0 + t2 * t2 / 120.0, torch.sin(th) / th)
+    b = torch.where(small, 0.5 - t2 / 24.0 + t2 * t2 / 720.0, (1.0 - torch.cos(th)) / (th * th))
+    return torch.eye(3, dtype=w.dtype, device=w.device) + a * K + b * (K @ K)
+
+
+def apply_pose_correction(c2w: torch.Tensor, correction: torch.Tensor) -> torch.Tensor:
+    """(3, 4) camera-to-world pose with the 6-vector correction (omega, tau) applied: R = exp([omega]x) R0, t = t0 + tau."""
+    c2w = c2w[:3, :4]
+    R = so3_exp(correction[:3]) @ c2w[:, :3]
+    return torch.cat([R, (c2w[:, 3] + correction[3:6])[:, None]], dim=1)
+
+
+def rays_from_pose(directions: torch.Tensor, c2w: torch.Tensor, correction: torch.Tensor | None = None):
+    """Differentiable `get_rays` (datasets/ray_utils.py:118-159): camera-space directions (..., 3) and a (3, 4) pose -> (rays_o, rays_d),
+    both (N, 3); rays_d is normalised and is also the view direction, as the datasets deliver it (pass the SAME tensor as rays_d and as
+    viewdirs: autograd then sums the two gradients).  `correction`: see apply_pose_correction.  Plain torch ops on whatever device and
+    dtype the inputs have; gradients reach `c2w` and `correction`."""
+    pose = c2w[:3, :4] if correction is None else apply_pose_correction(c2w, correction)
+    d = directions.reshape(-1, 3) @ pose[:, :3].T
+    d = d / torch.norm(d, dim=-1, keepdim=True)
+    return pose[:, 3].expand(d.shape), d
+
+
 # ------------------------------------------------------------------ NeRFMLP of any constructor geometry (csrc/aon_gmlp.hip)
 class MlpGeometry:
     """The arguments of ``NeRFMLP.__init__`` (model.py:40-54) -> ``aon_mlp_geometry``; parameter names / shapes / order of the

@@ -624,6 +624,29 @@ int aon_art_render_bwd_latents(const void* packed_bwd_coarse, const void* small_
                                const float* const* params_coarse_host, const float* const* params_fine_host, float* g_shape,
                                float* g_appearance, float* g_articulation, void* workspace, int64_t workspace_bytes,
                                void* scratch, int64_t scratch_bytes, void* stream, const aon_render_opts* opts);
+/* Ray gradients of a FROZEN articulated network (refining a camera pose together with the codes):
+ * aon_art_render_bwd_latents plus dL/d rays_o, dL/d rays_d and dL/d viewdirs, (n_rays, 3) fp32 each, overwritten, summed over the levels.
+ * The sample positions are x_i = rays_o + t_i rays_d with t as DATA (coarse t depends on near / far only, the fine t is detached by the
+ * reference); per-ray near / far get no gradient.  g_rays_d also carries the term through |rays_d| in the compositing's interval lengths.
+ * rg == NULL: the call IS aon_art_render_bwd_latents (same bits, same messages).  With rg the three latent vectors are bit-equal to that
+ * call's; g_shape / g_appearance / g_articulation may then be NULL, all three together (a pose fitted under fixed codes: the latent launches
+ * are skipped).  Every member of rg must be non-NULL (AON_E_INVALID before any launch, like everything aon_art_render_bwd_latents refuses);
+ * rg->viewdirs is the forward's viewdirs; rg->rays_o is the forward's rays_o (not read: no gradient depends on the origin's value).
+ * scratch >= aon_train_scratch_bytes_inputs(): the latents scratch plus one 128-byte record per sample.  Two more ordinary launches on
+ * `stream`; every sum over a ray's samples is fp64 in a fixed order (no atomics): a ray's gradients are the same bits on every run and do
+ * not depend on which other rays share the call.  ABI version unchanged (additive). */
+typedef struct aon_ray_grads {
+  const float* rays_o; const float* viewdirs;
+  float* g_rays_o; float* g_rays_d; float* g_viewdirs;
+} aon_ray_grads;
+int64_t aon_train_scratch_bytes_inputs(int64_t n_rays, int num_levels, const aon_render_opts* opts);
+int aon_art_render_bwd_inputs(const void* packed_bwd_coarse, const void* small_coarse, const void* packed_bwd_fine,
+                              const void* small_fine, const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels,
+                              const float* const* g_rgb_host, const float* const* g_acc_host, const float* const* g_depth_host,
+                              const float* const* params_coarse_host, const float* const* params_fine_host, float* g_shape,
+                              float* g_appearance, float* g_articulation, void* workspace, int64_t workspace_bytes,
+                              void* scratch, int64_t scratch_bytes, void* stream, const aon_render_opts* opts,
+                              const aon_ray_grads* rg);
 
 /* ---- NeRFMLP of ANY constructor geometry (models/vanilla_nerf/model.py:40-120), round 3 ----
  * The entry points above run the reference's default NeRFMLP (8 x 256, skip 4, 1 x 128, degrees 10 / 4) on fused kernels compiled

@@ -36,10 +36,10 @@ _PATH = ([_p, _p, _p, _l]          # rays_o, rays_d, viewdirs, n_rays
          + [_p, _l, _p])           # workspace, workspace_bytes, stream
 _VANILLA, _ART, _GENERAL = [_p] * 2, [_p] * 4, [_p] * 3   # packed c/f | packed, small c/f | aon_mlp_geometry, parameter arrays c/f
 _OPTS, _OCC, _STOP, _BOUNDS = [_p], [_p, _p], [_f, _i, _p], [_p]   # opts | grid, tally | eps, round_samples, stop map | aon_ray_bounds
-# the latent-only backward: streams and per-call blocks | rays_d, n, white_bkgd, num_levels | g_rgb, g_acc, g_depth | parameter arrays |
-# three latent gradients | workspace, scratch, stream | opts
-_LATENTS_BWD = _ART + [_p, _l, _i, _i] + [_p] * 3 + [_p] * 2 + [_p] * 3 + [_p, _l, _p, _l, _p] + _OPTS
-_RAY_GRADS = [_p]   # aon_ray_grads
+# The whole-path backwards share csrc/aon_capi_util.h's BwdCall: its two runs stand either side of the network's own arrays
+_BWD = ([_p, _l, _i, _i] + [_p] * 3,     # rays_d, n_rays, white_bkgd, num_levels | g_rgb, g_acc, g_depth (host arrays of device pointers)
+        [_p, _l, _p, _l, _p])            # workspace, workspace_bytes, scratch, scratch_bytes, stream
+_PER_LEVEL, _LATENTS, _RAY_GRADS = [_p] * 2, [_p] * 3, [_p]   # parameter / gradient arrays c/f | three codes or their gradients | aon_ray_grads
 
 
 def _path_sigs():
@@ -53,8 +53,20 @@ def _path_sigs():
     return {name: (_i, args) for name, args in sigs.items()}
 
 
+def _bwd_sigs():
+    head, tail = _BWD
+    vanilla = _VANILLA * 2 + head + _PER_LEVEL + tail                                 # transposed and forward stream c/f ... gradients
+    art = _ART + head + _PER_LEVEL + _LATENTS + _PER_LEVEL + _LATENTS + tail           # ... parameters, codes, gradients, code gradients
+    frozen = _ART + head + _PER_LEVEL + _LATENTS + tail + _OPTS                        # ... parameters, code gradients
+    sigs = {"aon_render_bwd": vanilla, "aon_render_bwd_ex": vanilla + _OPTS, "aon_art_render_bwd": art, "aon_art_render_bwd_ex": art + _OPTS,
+            "aon_art_render_bwd_latents": frozen, "aon_art_render_bwd_inputs": frozen + _RAY_GRADS,
+            "aon_grender_bwd": _GENERAL + head + _PER_LEVEL + tail + _OPTS}
+    return {name: (_i, args) for name, args in sigs.items()}
+
+
 _SIGS = {
     **_path_sigs(),
+    **_bwd_sigs(),
     "aon_abi_version": (_i, []),
     "aon_last_error": (C.c_char_p, []),
     "aon_raygen": (_i, [_p, _i, _i, _f, _l, _l, _p, _p, _p, _p]),
@@ -133,8 +145,6 @@ _SIGS = {
     "aon_set_wgrad_probe": (_i, [_p]),
     "aon_train_workspace_bytes": (_l, [_l, _i, _i]),
     "aon_train_scratch_bytes": (_l, [_l, _i, _i]),
-    "aon_render_bwd": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p]),
-    "aon_art_render_bwd": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p]),
     "aon_profile_begin": (_i, []),
     "aon_profile_end": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "aon_profile_class": (_i, [_i, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -151,14 +161,9 @@ _SIGS = {
     "aon_render_workspace_bytes_ex": (_l, [_l, _p]),
     "aon_train_workspace_bytes_ex": (_l, [_l, _i, _i, _p]),
     "aon_train_scratch_bytes_ex": (_l, [_l, _i, _i, _p]),
-    "aon_render_bwd_ex": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p]),
-    "aon_art_render_bwd_ex": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p]),
-    # latent-only backward of a frozen articulated network
+    # scratch of the latent-only backward, and with the ray gradients' records (section 4.14)
     "aon_train_scratch_bytes_latents": (_l, [_l, _i, _p]),
-    "aon_art_render_bwd_latents": (_i, _LATENTS_BWD),
-    # ... plus the gradients of rays_o, rays_d, viewdirs: the same list and an aon_ray_grads
     "aon_train_scratch_bytes_inputs": (_l, [_l, _i, _p]),
-    "aon_art_render_bwd_inputs": (_i, _LATENTS_BWD + _RAY_GRADS),
     # NeRFMLP of any constructor geometry (aon_mlp_geometry first)
     "aon_mlp_geometry_init": (None, [_p]),
     "aon_gmlp_param_count": (_i, [_p]),
@@ -167,7 +172,6 @@ _SIGS = {
     "aon_grender_workspace_bytes": (_l, [_p, _l, _p]),
     "aon_grender_train_workspace_bytes": (_l, [_p, _l, _i, _p]),
     "aon_grender_train_scratch_bytes": (_l, [_p, _l, _i, _p]),
-    "aon_grender_bwd": (_i, [_p, _p, _p, _p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _l, _p, _p]),
     # per-ray near / far from a ray-box intersection
     "aon_ray_limits_box": (_i, [_p, _p, _l, _p, _p, _p, _p, _p]),
     "aon_ray_limits_workspace_bytes": (_l, [_l]),

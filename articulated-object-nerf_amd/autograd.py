@@ -59,6 +59,21 @@ def _check_not_released(ctx):
                            "(a second backward / retain_graph=True is not supported; run the forward again)")
 
 
+def _level_grads(gouts, num_levels, rays_d):
+    """The output gradients of a whole-path forward -> per-level lists (g_rgb, g_acc, g_depth); an rgb that got none reads zeros, acc and depth
+    stay None (the C calls take NULL for them)."""
+    n = rays_d.shape[0]
+    g_rgb = [gouts[3 * l] if gouts[3 * l] is not None else torch.zeros((n, 3), dtype=torch.float32, device=rays_d.device) for l in range(num_levels)]
+    return g_rgb, [gouts[3 * l + 1] for l in range(num_levels)], [gouts[3 * l + 2] for l in range(num_levels)]
+
+
+def _release(ctx, ws):
+    """After the backward's one C call: the context lets go of the forward's workspace, which goes back to the pool (the backward's launches
+    are enqueued: whoever takes the workspace next is ordered behind them)."""
+    ctx.fused, ctx.released, ctx.geometry = None, True, None
+    ops.pool_give(ws)
+
+
 class RenderVanilla(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, packs, opts, noise, *params):
@@ -82,14 +97,9 @@ class RenderVanilla(torch.autograd.Function):
         ws, packs_bwd, packs_fwd = ctx.fused    # the whole backward is ONE C call too (aon_render_bwd)
         n_per = len(ops.VANILLA_PARAM_ORDER)
         slots = _arena_grads(ctx, [ctx.param_shapes[l * n_per: (l + 1) * n_per] for l in range(ctx.num_levels)])
-        n = ctx.rays_d.shape[0]
-        g_rgb = [gouts[3 * l] if gouts[3 * l] is not None else torch.zeros((n, 3), dtype=torch.float32, device=ctx.rays_d.device)
-                 for l in range(ctx.num_levels)]
-        per_level = ops.render_bwd(ws, packs_bwd, packs_fwd, ctx.rays_d, ctx.white_bkgd, ctx.num_levels, g_rgb,
-                                   [gouts[3 * l + 1] for l in range(ctx.num_levels)], [gouts[3 * l + 2] for l in range(ctx.num_levels)],
+        per_level = ops.render_bwd(ws, packs_bwd, packs_fwd, ctx.rays_d, ctx.white_bkgd, ctx.num_levels, *_level_grads(gouts, ctx.num_levels, ctx.rays_d),
                                    geometry=ctx.geometry, grads_out=slots)
-        ctx.fused, ctx.released, ctx.geometry = None, True, None
-        ops.pool_give(ws)      # (the backward's launches are enqueued: whoever takes the workspace next is ordered behind them)
+        _release(ctx, ws)
         _arena_done(ctx)
         return (None,) * 12 + tuple(g[name] for g in per_level for name in ops.VANILLA_PARAM_ORDER)
 
@@ -136,66 +146,74 @@ class RenderGeneral(torch.autograd.Function):
         # sets of weights (round 3 kept p.detach() aliases, which bypass the check).
         ctx.save_for_backward(*params)
         pd = [dict(zip(geom.param_order, [p.detach() for p in params[l * n_per: (l + 1) * n_per]])) for l in range(num_levels)]
-        levels, ctx.ws, ctx.geometry = ops.grender_fwd_train(geom, pd[0], pd[1] if num_levels == 2 else None, rays_o, rays_d,
-                                                             viewdirs, near, far, white_bkgd, num_levels, t_rand, u, opts=opts, noise=noise)
+        levels, ws, ctx.geometry = ops.grender_fwd_train(geom, pd[0], pd[1] if num_levels == 2 else None, rays_o, rays_d,
+                                                         viewdirs, near, far, white_bkgd, num_levels, t_rand, u, opts=opts, noise=noise)
+        ctx.fused = (ws,)
         return tuple(x for lvl in levels for x in lvl)
 
     @staticmethod
     def backward(ctx, *gouts):
         _check_not_released(ctx)
-        n = ctx.rays_d.shape[0]
-        g_rgb = [gouts[3 * l] if gouts[3 * l] is not None else torch.zeros((n, 3), dtype=torch.float32, device=ctx.rays_d.device)
-                 for l in range(ctx.num_levels)]
+        ws, = ctx.fused
         n_per = len(ctx.geom.param_order)
         saved = ctx.saved_tensors   # (raises if a parameter was modified in place since the forward)
         params = [dict(zip(ctx.geom.param_order, saved[l * n_per: (l + 1) * n_per])) for l in range(ctx.num_levels)]
-        per_level = ops.grender_bwd(ctx.geom, ctx.ws, params, ctx.rays_d, ctx.white_bkgd, ctx.num_levels, g_rgb,
-                                    [gouts[3 * l + 1] for l in range(ctx.num_levels)], [gouts[3 * l + 2] for l in range(ctx.num_levels)],
+        per_level = ops.grender_bwd(ctx.geom, ws, params, ctx.rays_d, ctx.white_bkgd, ctx.num_levels, *_level_grads(gouts, ctx.num_levels, ctx.rays_d),
                                     ctx.geometry)
-        ops.pool_give(ctx.ws)
-        ctx.ws, ctx.released, ctx.geometry = None, True, None
+        _release(ctx, ws)
         return (None,) * 12 + tuple(g[name] for g in per_level for name in ctx.geom.param_order)
+
+
+def _art_forward(ctx, save_rays, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, packs, opts, noise, lat_density, lat_color,
+                 lat_articulation, *params):
+    """The forward of the three articulated Functions, whose `forward(ctx, *args)` takes the arguments from rays_o on: ONE C call
+    (aon_art_render_fwd_train).  packs: per level (packed_fwd, small, packed_bwd); params: 40 tensors per level in ops.ART_PARAM_ORDER.
+    Parameters and latents (and, `save_rays`, the rays) are read again by the backward: saved the autograd way, so an in-place update in
+    between raises instead of mixing two sets of weights (as RenderGeneral)."""
+    rays, latents = (rays_o, rays_d, viewdirs), (lat_density, lat_color, lat_articulation)
+    ctx.white_bkgd, ctx.num_levels = white_bkgd, num_levels
+    if not save_rays:
+        ctx.rays_d = rays_d
+    ctx.set_materialize_grads(False)   # acc / depth carry no gradient in training: None, not four zero-filled tensors per step
+    ctx.lat_shapes = tuple(t.shape for t in latents)
+    ctx.save_for_backward(*(rays if save_rays else ()), *latents, *params)
+    levels, ws, ctx.geometry = ops.render_fwd_train(packs[0][0], packs[1][0] if num_levels == 2 else None, rays_o, rays_d, viewdirs, near, far,
+                                                    white_bkgd, num_levels, t_rand, u, small_c=packs[0][1],
+                                                    small_f=packs[1][1] if num_levels == 2 else None, opts=opts, noise=noise)
+    ctx.fused = (ws, [pk[2] for pk in packs], [pk[1] for pk in packs])
+    return tuple(x for lvl in levels for x in lvl)
+
+
+def _art_saved(ctx, first):
+    """-> (saved tensors, per-level dicts of the saved parameters, which start at `first`); raises if one was modified in place since the forward"""
+    n_per = len(ops.ART_PARAM_ORDER)
+    saved = ctx.saved_tensors
+    return saved, [dict(zip(ops.ART_PARAM_ORDER, saved[first + l * n_per: first + (l + 1) * n_per])) for l in range(ctx.num_levels)]
+
+
+_LATENT_KEYS = ("density", "color", "articulation")
 
 
 class RenderArticulated(torch.autograd.Function):
     """NeRF_AE_Art.forward with gradients to the 2 x 40 MLP parameters and the three latents."""
 
     @staticmethod
-    def forward(ctx, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, packs, opts, noise, lat_density, lat_color,
-                lat_articulation, *params):
-        # packs: per level (packed_fwd, small, packed_bwd); params: 40 tensors per level in ops.ART_PARAM_ORDER
-        ctx.rays_d, ctx.white_bkgd, ctx.num_levels = rays_d, white_bkgd, num_levels
-        ctx.set_materialize_grads(False)   # acc / depth carry no gradient in training: None, not four zero-filled tensors per step
-        ctx.lat_shapes = (lat_density.shape, lat_color.shape, lat_articulation.shape)
-        # parameters and latents are read again by the backward (latent columns: dW = db (x) latent, d latent = W^T db): saved the
-        # autograd way, so an in-place update in between raises instead of mixing two sets of weights (as RenderGeneral)
-        ctx.save_for_backward(lat_density, lat_color, lat_articulation, *params)
-        levels, ws, ctx.geometry = ops.render_fwd_train(packs[0][0], packs[1][0] if num_levels == 2 else None, rays_o, rays_d, viewdirs, near, far,
-                                                        white_bkgd, num_levels, t_rand, u, small_c=packs[0][1],
-                                                        small_f=packs[1][1] if num_levels == 2 else None, opts=opts, noise=noise)
-        ctx.fused = (ws, [pk[2] for pk in packs], [pk[1] for pk in packs])   # ONE C call (aon_art_render_fwd_train)
-        _arena_plan(ctx, params)
-        return tuple(x for lvl in levels for x in lvl)
+    def forward(ctx, *args):
+        out = _art_forward(ctx, False, *args)
+        _arena_plan(ctx, args[15:])
+        return out
 
     @staticmethod
     def backward(ctx, *gouts):
-        n_per = len(ops.ART_PARAM_ORDER)
         _check_not_released(ctx)
         ws, packs_bwd, smalls = ctx.fused       # the whole backward in ONE C call (aon_art_render_bwd)
-        n = ctx.rays_d.shape[0]
-        g_rgb = [gouts[3 * l] if gouts[3 * l] is not None else torch.zeros((n, 3), dtype=torch.float32, device=ctx.rays_d.device)
-                 for l in range(ctx.num_levels)]
-        saved = ctx.saved_tensors   # (raises if a parameter or latent was modified in place since the forward)
-        latents = {"density": saved[0], "color": saved[1], "articulation": saved[2]}
-        params = [dict(zip(ops.ART_PARAM_ORDER, saved[3 + l * n_per: 3 + (l + 1) * n_per])) for l in range(ctx.num_levels)]
-        slots = _arena_grads(ctx, [[tuple(t.shape) for t in saved[3 + l * n_per: 3 + (l + 1) * n_per]] for l in range(ctx.num_levels)])
-        per_level, g_lat = ops.art_render_bwd(ws, packs_bwd, smalls, ctx.rays_d, ctx.white_bkgd, ctx.num_levels, g_rgb,
-                                              [gouts[3 * l + 1] for l in range(ctx.num_levels)], [gouts[3 * l + 2] for l in range(ctx.num_levels)],
-                                              params, latents, geometry=ctx.geometry, grads_out=slots)
-        ctx.fused, ctx.released, ctx.geometry = None, True, None
-        ops.pool_give(ws)      # (the backward's launches are enqueued: whoever takes the workspace next is ordered behind them)
+        saved, params = _art_saved(ctx, 3)
+        slots = _arena_grads(ctx, [[tuple(t.shape) for t in p.values()] for p in params])
+        per_level, g_lat = ops.art_render_bwd(ws, packs_bwd, smalls, ctx.rays_d, ctx.white_bkgd, ctx.num_levels, *_level_grads(gouts, ctx.num_levels, ctx.rays_d),
+                                              params, dict(zip(_LATENT_KEYS, saved[:3])), geometry=ctx.geometry, grads_out=slots)
+        _release(ctx, ws)
         _arena_done(ctx)
-        lat = tuple(g_lat[k].reshape(shp) for k, shp in zip(("density", "color", "articulation"), ctx.lat_shapes))
+        lat = tuple(g_lat[k].reshape(shp) for k, shp in zip(_LATENT_KEYS, ctx.lat_shapes))
         return (None,) * 12 + lat + tuple(g[name] for g in per_level for name in ops.ART_PARAM_ORDER)
 
 
@@ -205,82 +223,47 @@ class RenderArticulatedLatents(torch.autograd.Function):
     gradients are bit-equal to RenderArticulated's; the parameters get none."""
 
     @staticmethod
-    def forward(ctx, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, packs, opts, noise, lat_density, lat_color,
-                lat_articulation, *params):
-        ctx.rays_d, ctx.white_bkgd, ctx.num_levels = rays_d, white_bkgd, num_levels
-        ctx.set_materialize_grads(False)
-        ctx.lat_shapes = (lat_density.shape, lat_color.shape, lat_articulation.shape)
-        # the backward reads the weights a latent enters (d latent = W^T db): saved the autograd way, as RenderArticulated, so an in-place
-        # update of a parameter or a latent between forward and backward raises
-        ctx.save_for_backward(lat_density, lat_color, lat_articulation, *params)
-        levels, ws, ctx.geometry = ops.render_fwd_train(packs[0][0], packs[1][0] if num_levels == 2 else None, rays_o, rays_d, viewdirs, near, far,
-                                                        white_bkgd, num_levels, t_rand, u, small_c=packs[0][1],
-                                                        small_f=packs[1][1] if num_levels == 2 else None, opts=opts, noise=noise)
-        ctx.fused = (ws, [pk[2] for pk in packs], [pk[1] for pk in packs])   # ONE C call (aon_art_render_fwd_train)
-        return tuple(x for lvl in levels for x in lvl)
+    def forward(ctx, *args):
+        return _art_forward(ctx, False, *args)
 
     @staticmethod
     def backward(ctx, *gouts):
-        n_per = len(ops.ART_PARAM_ORDER)
         _check_not_released(ctx)
         ws, packs_bwd, smalls = ctx.fused
-        n = ctx.rays_d.shape[0]
-        g_rgb = [gouts[3 * l] if gouts[3 * l] is not None else torch.zeros((n, 3), dtype=torch.float32, device=ctx.rays_d.device)
-                 for l in range(ctx.num_levels)]
-        saved = ctx.saved_tensors   # (raises if a parameter or latent was modified in place since the forward)
-        params = [dict(zip(ops.ART_PARAM_ORDER, saved[3 + l * n_per: 3 + (l + 1) * n_per])) for l in range(ctx.num_levels)]
-        g_lat = ops.art_render_bwd_latents(ws, packs_bwd, smalls, ctx.rays_d, ctx.white_bkgd, ctx.num_levels, g_rgb,
-                                           [gouts[3 * l + 1] for l in range(ctx.num_levels)], [gouts[3 * l + 2] for l in range(ctx.num_levels)],
+        _, params = _art_saved(ctx, 3)
+        g_lat = ops.art_render_bwd_latents(ws, packs_bwd, smalls, ctx.rays_d, ctx.white_bkgd, ctx.num_levels, *_level_grads(gouts, ctx.num_levels, ctx.rays_d),
                                            params, geometry=ctx.geometry)
-        ctx.fused, ctx.released, ctx.geometry = None, True, None
-        ops.pool_give(ws)      # (the backward's launches are enqueued: whoever takes the workspace next is ordered behind them)
-        lat = tuple(g_lat[k].reshape(shp) for k, shp in zip(("density", "color", "articulation"), ctx.lat_shapes))
-        return (None,) * 12 + lat + (None,) * (n_per * ctx.num_levels)
+        _release(ctx, ws)
+        lat = tuple(g_lat[k].reshape(shp) for k, shp in zip(_LATENT_KEYS, ctx.lat_shapes))
+        return (None,) * 12 + lat + (None,) * (len(ops.ART_PARAM_ORDER) * ctx.num_levels)
 
 
 class RenderArticulatedInputs(torch.autograd.Function):
     """NeRF_AE_Art.forward of a FROZEN network with gradients to its INPUTS: rays_o, rays_d, viewdirs -- whichever
-    of them requires grad -- and the three latents.  RenderArticulatedLatents' forward, saved tensors and released-workspace rules; the
+    of them requires grad -- and the three latents.  RenderArticulatedLatents' forward, saved tensors (plus the rays, which the backward
+    reads again) and released-workspace rules; the
     backward is aon_art_render_bwd_inputs: the latent gradients are RenderArticulatedLatents' bits, and with no latent requiring grad its
     latent launches are skipped.  t is data: nothing flows through the sampler, near / far or the inverse-CDF draws.  A tensor passed both
     as rays_d and as viewdirs (the datasets' convention) receives the sum of the two slots from autograd."""
 
     @staticmethod
-    def forward(ctx, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, packs, opts, noise, lat_density, lat_color,
-                lat_articulation, *params):
-        ctx.white_bkgd, ctx.num_levels = white_bkgd, num_levels
-        ctx.set_materialize_grads(False)
-        ctx.lat_shapes = (lat_density.shape, lat_color.shape, lat_articulation.shape)
-        # the backward reads the rays, the latents' weights and views_linear.0 / deformations_linear.0 again: saved the autograd way
-        ctx.save_for_backward(rays_o, rays_d, viewdirs, lat_density, lat_color, lat_articulation, *params)
-        levels, ws, ctx.geometry = ops.render_fwd_train(packs[0][0], packs[1][0] if num_levels == 2 else None, rays_o, rays_d, viewdirs, near, far,
-                                                        white_bkgd, num_levels, t_rand, u, small_c=packs[0][1],
-                                                        small_f=packs[1][1] if num_levels == 2 else None, opts=opts, noise=noise)
-        ctx.fused = (ws, [pk[2] for pk in packs], [pk[1] for pk in packs])   # ONE C call (aon_art_render_fwd_train)
-        return tuple(x for lvl in levels for x in lvl)
+    def forward(ctx, *args):
+        return _art_forward(ctx, True, *args)
 
     @staticmethod
     def backward(ctx, *gouts):
-        n_per = len(ops.ART_PARAM_ORDER)
         _check_not_released(ctx)
         ws, packs_bwd, smalls = ctx.fused
-        saved = ctx.saved_tensors   # (raises if a ray tensor, a latent or a parameter was modified in place since the forward)
+        saved, params = _art_saved(ctx, 6)
         rays_o, rays_d, viewdirs = saved[:3]
-        n = rays_d.shape[0]
-        g_rgb = [gouts[3 * l] if gouts[3 * l] is not None else torch.zeros((n, 3), dtype=torch.float32, device=rays_d.device)
-                 for l in range(ctx.num_levels)]
-        params = [dict(zip(ops.ART_PARAM_ORDER, saved[6 + l * n_per: 6 + (l + 1) * n_per])) for l in range(ctx.num_levels)]
-        want_lat = any(ctx.needs_input_grad[12:15])
-        g_lat, g_o, g_d, g_v = ops.art_render_bwd_inputs(ws, packs_bwd, smalls, rays_o, rays_d, viewdirs, ctx.white_bkgd, ctx.num_levels, g_rgb,
-                                                         [gouts[3 * l + 1] for l in range(ctx.num_levels)],
-                                                         [gouts[3 * l + 2] for l in range(ctx.num_levels)], params, geometry=ctx.geometry,
-                                                         want_latents=want_lat)
-        ctx.fused, ctx.released, ctx.geometry = None, True, None
-        ops.pool_give(ws)      # (the backward's launches are enqueued: whoever takes the workspace next is ordered behind them)
         need = ctx.needs_input_grad
+        want_lat = any(need[12:15])
+        g_lat, g_o, g_d, g_v = ops.art_render_bwd_inputs(ws, packs_bwd, smalls, rays_o, rays_d, viewdirs, ctx.white_bkgd, ctx.num_levels,
+                                                         *_level_grads(gouts, ctx.num_levels, rays_d), params, geometry=ctx.geometry,
+                                                         want_latents=want_lat)
+        _release(ctx, ws)
         ray = tuple(g.reshape(t.shape) if need[i] else None for i, (g, t) in enumerate(zip((g_o, g_d, g_v), (rays_o, rays_d, viewdirs))))
         lat = (None, None, None)
         if want_lat:
-            lat = tuple(g_lat[k].reshape(shp) if need[12 + i] else None
-                        for i, (k, shp) in enumerate(zip(("density", "color", "articulation"), ctx.lat_shapes)))
-        return ray + (None,) * 9 + lat + (None,) * (n_per * ctx.num_levels)
+            lat = tuple(g_lat[k].reshape(shp) if need[12 + i] else None for i, (k, shp) in enumerate(zip(_LATENT_KEYS, ctx.lat_shapes)))
+        return ray + (None,) * 9 + lat + (None,) * (len(ops.ART_PARAM_ORDER) * ctx.num_levels)

@@ -434,15 +434,14 @@ int aon_grender_bwd(const aon_mlp_geometry* geom, const float* const* params_coa
                     float* const* grads_fine_host, void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
                     void* stream_, const aon_render_opts* opts) {
   const char* who = "aon_grender_bwd";
-  hipStream_t stream = (hipStream_t)stream_;
+  const BwdCall c = bwd_call(rays_d, n, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, workspace, workspace_bytes, scratch, scratch_bytes,
+                             stream_, opts);
+  const hipStream_t stream = c.stream;
   GG g; Geo geo;
   if (const char* bad = make_gg(geom, g)) return fail(AON_E_INVALID, bad);
   if (const char* bad = whole_path_ok(g)) return fail(AON_E_INVALID, bad);
   if (const char* bad = make_geo(opts, geo, true)) return fail(AON_E_INVALID, bad);
-  if (n <= 0 || (num_levels != 1 && num_levels != 2)) return fail(AON_E_INVALID, "aon_grender_bwd: bad size / num_levels");
-  if (!rays_d || !g_rgb_host || !workspace || !scratch) return fail(AON_E_INVALID, "aon_grender_bwd: null pointer");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) || (reinterpret_cast<uintptr_t>(scratch) & 255))
-    return fail(AON_E_INVALID, "aon_grender_bwd: workspace / scratch must be 256-byte aligned");
+  if (int rc = bwd_call_check(who, c)) return rc;
   const GTrainWs w = carve_gtrain(workspace, g, geo, n, num_levels);
   if (w.bytes > workspace_bytes) return fail(AON_E_WORKSPACE, "aon_grender_bwd: workspace smaller than aon_grender_train_workspace_bytes()");
   const GScratch sc = carve_gscratch(scratch, g, geo, n, num_levels);
@@ -458,8 +457,7 @@ int aon_grender_bwd(const aon_mlp_geometry* geom, const float* const* params_coa
     int rc;
     {
       KTimer timer(kCompositeBwd, stream, n);
-      rc = check(aon::launch_composite_bwd(L.raw, L.t, rays_d, g_rgb_host[l], g_acc_host ? g_acc_host[l] : nullptr, g_depth_host ? g_depth_host[l] : nullptr,
-                                           n, L.S, white_bkgd, geo.act(false, l, 0), sc.d_raw, stream), who);
+      rc = check(aon::launch_composite_bwd(L.raw, L.t, rays_d, g_rgb_host[l], c.acc(l), c.depth(l), n, L.S, white_bkgd, geo.act(false, l, 0), sc.d_raw, stream), who);
     }
     if (rc) return rc;
     if ((rc = gmlp_backward(g, params[l], grads[l], L.acts, sc, n, L.S, stream, who))) return rc;

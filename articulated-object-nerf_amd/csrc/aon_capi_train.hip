@@ -385,54 +385,69 @@ int train_fwd_impl(const char* who, bool art, const TrainNet* nets, const PathCa
   return run_range(0, n, stream);
 }
 
+// What a backward entry point brings beside its call record (BwdCall, aon_capi_util.h) and its TrainNet[2]; pointers it does not have are null.
+struct BwdIo {
+  const float* const* params[2];   // [articulated] the forward's parameters, 40 device pointers per level
+  const float* latents[3];         // [articulated, full backward] shape, appearance, articulation
+  float* const* grads[2];          // [full backward] the parameter gradients per level
+  float* g_latents[3];             // [articulated]
+  const aon_ray_grads* rg;         // [aon_art_render_bwd_inputs]
+};
+
+// One level's compositing backward on `st`, the first stage of every backward here: d_raw (Np, 4) with its padded tail zeroed.
+// (static, as train_bwd_impl: under this file's extern "C" a function of the unnamed namespace would still be exported by name)
+static int composite_bwd_stage(const char* who, bool art, int l, const TrainLevel& L, float* d_raw, const Geo& g, const BwdCall& c, hipStream_t st) {
+  const int64_t valid = c.n_rays * L.S;
+  if (int rc = check(hipMemsetAsync(d_raw + valid * 4, 0, (size_t)(L.Np - valid) * 16, st), who)) return rc;
+  KTimer timer(kCompositeBwd, st, c.n_rays);
+  return check(aon::launch_composite_bwd(L.raw, L.t, c.rays_d, c.g_rgb[l], c.acc(l), c.depth(l), c.n_rays, L.S, c.white_bkgd, g.act(art, l, 0), d_raw, st), who);
+}
+// [articulated] one level's segment of the backward chain: the per-call block, planes and dxp
+static aon::ChainSeg art_chain_seg(const TrainNet& net, const TrainLevel& L, float* d_raw, float* dplanes, float* dxp) {
+  return aon::ChainSeg{static_cast<const char*>(net.packed_bwd), net.small, d_raw, L.masks, L.planes, dplanes, dxp, L.Np};
+}
+
 // The whole backward of a training step, shared by the vanilla and the articulated network (as train_fwd_impl is for the forward): composite
 // backward -> backward chain -> weight gradients per level, in the schedule the switches select.  What differs between the networks is
 // marked [vanilla] / [articulated] where it happens:
 //   the chain segment, the null / form checks, the overlap mode, who waits for the early head reductions, the conditions of the merged second
 //   stage, the remap of the encoding-fed gradients at other degrees [vanilla], the latent gradients [articulated].
-// params / latents / g_latents: [articulated] the forward's parameters (2 x 40), its three latent codes and their gradients; null for [vanilla].
-static int train_bwd_impl(const char* who, bool art, const TrainNet* nets, const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels,
-                   const float* const* g_rgb_host, const float* const* g_acc_host, const float* const* g_depth_host, const float* const* const* params,
-                   const float* const* latents, float* const* const* grads, float* const* g_latents, void* workspace, int64_t workspace_bytes,
-                   void* scratch, int64_t scratch_bytes, hipStream_t caller, const aon_render_opts* opts) {
+static int train_bwd_impl(const char* who, bool art, const TrainNet* nets, const BwdCall& c, const BwdIo& io) {
   auto bad = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
   Geo g;
-  if (const char* b = make_geo(opts, g)) return fail(AON_E_INVALID, b);
+  if (const char* b = make_geo(c.opts, g)) return fail(AON_E_INVALID, b);
   if (art) g.other_degrees = false;   // (as in train_fwd_impl: the articulated kernels carry their degrees themselves)
-  if (n_rays <= 0 || (num_levels != 1 && num_levels != 2)) return bad(AON_E_INVALID, "bad size / num_levels");
-  if (!rays_d || !g_rgb_host || !workspace || !scratch || !grads[0]) return bad(AON_E_INVALID, "null pointer");
-  if (art && (!params[0] || !latents[0] || !latents[1] || !latents[2] || !g_latents[0] || !g_latents[1] || !g_latents[2])) return bad(AON_E_INVALID, "null pointer");
-  if (reinterpret_cast<uintptr_t>(scratch) & 255) return bad(AON_E_INVALID, "scratch must be 256-byte aligned");
-  const TrainWs w = carve_train(static_cast<char*>(workspace), n_rays, art, num_levels, g);
-  if (w.bytes > workspace_bytes) return bad(AON_E_WORKSPACE, "workspace smaller than aon_train_workspace_bytes()");
-  const TrainScratch sc = carve_scratch(static_cast<char*>(scratch), n_rays, art, num_levels, g);
-  if (sc.bytes > scratch_bytes) return bad(AON_E_WORKSPACE, "scratch smaller than aon_train_scratch_bytes()");
+  const bool lat_null = !io.params[0] || !io.latents[0] || !io.latents[1] || !io.latents[2] || !io.g_latents[0] || !io.g_latents[1] || !io.g_latents[2];
+  if (int rc = bwd_call_check(who, c, !io.grads[0] || (art && lat_null))) return rc;
+  // (the record's fields under the names the schedule below uses)
+  const int64_t n_rays = c.n_rays;
+  const int num_levels = c.num_levels;
+  const hipStream_t caller = c.stream;
+  const float* const* const* params = io.params; const float* const* latents = io.latents;
+  float* const* const* grads = io.grads; float* const* g_latents = io.g_latents;
+  const TrainWs w = carve_train(static_cast<char*>(c.workspace), n_rays, art, num_levels, g);
+  if (w.bytes > c.workspace_bytes) return bad(AON_E_WORKSPACE, "workspace smaller than aon_train_workspace_bytes()");
+  const TrainScratch sc = carve_scratch(static_cast<char*>(c.scratch), n_rays, art, num_levels, g);
+  if (sc.bytes > c.scratch_bytes) return bad(AON_E_WORKSPACE, "scratch smaller than aon_train_scratch_bytes()");
   const int nparams = art ? 40 : aon::kNumVanillaParams;
   for (int l = 0; l < num_levels; ++l) {
     // the transposed stream's form is checked against its mate's: [vanilla] the forward stream, [articulated] the per-call block
     const void* pb = nets[l].packed_bwd;
     const void* mate = art ? static_cast<const void*>(nets[l].small) : nets[l].packed_fwd;
-    if (!pb || !mate || !grads[l] || (art && !params[l]) || !g_rgb_host[l]) return bad(AON_E_INVALID, "null level pointer");
+    if (!pb || !mate || !grads[l] || (art && !params[l]) || !c.g_rgb[l]) return bad(AON_E_INVALID, "null level pointer");
     if (aon::stream_form(pb) != aon::stream_form(mate) || aon::stream_form(pb) != aon::stream_form(nets[0].packed_bwd))
       return bad(AON_E_INVALID, art ? "transposed stream and per-call block were made in different forms (aon_set_bottleneck_fold changed in between)"
                                     : "forward and transposed streams were packed in different forms (aon_set_bottleneck_fold changed in between)");
     for (int i = 0; i < nparams; ++i)
       if (!grads[l][i] || (art && !params[l][i])) return bad(AON_E_INVALID, art ? "null parameter / gradient pointer" : "null gradient pointer");
   }
-  auto composite_bwd = [&](int l, hipStream_t st) -> int {
-    const TrainLevel& L = w.lvl[l];
-    const int64_t valid = n_rays * L.S;
-    if (int rc = check(hipMemsetAsync(sc.d_raw[l] + valid * 4, 0, (size_t)(L.Np - valid) * 16, st), who)) return rc;
-    KTimer timer(kCompositeBwd, st, n_rays);
-    return check(aon::launch_composite_bwd(L.raw, L.t, rays_d, g_rgb_host[l], g_acc_host ? g_acc_host[l] : nullptr, g_depth_host ? g_depth_host[l] : nullptr,
-                                           n_rays, L.S, white_bkgd, g.act(art, l, 0), sc.d_raw[l], st), who);
-  };
-  // [vanilla] the small block sits behind the forward stream, no planes / dxp; [articulated] the per-call block, planes and dxp
+  auto composite_bwd = [&](int l, hipStream_t st) { return composite_bwd_stage(who, art, l, w.lvl[l], sc.d_raw[l], g, c, st); };
+  // [vanilla] the small block sits behind the forward stream, no planes / dxp
   auto chain_seg = [&](int l) -> aon::ChainSeg {
     const TrainLevel& L = w.lvl[l];
-    const char* pb = static_cast<const char*>(nets[l].packed_bwd);
-    if (art) return aon::ChainSeg{pb, nets[l].small, sc.d_raw[l], L.masks, L.planes, sc.dplanes[l], sc.dxp[l], L.Np};
-    return aon::ChainSeg{pb, reinterpret_cast<const float*>(static_cast<const char*>(nets[l].packed_fwd) + aon::kStreamBytes), sc.d_raw[l], L.masks, nullptr,
+    if (art) return art_chain_seg(nets[l], L, sc.d_raw[l], sc.dplanes[l], sc.dxp[l]);
+    return aon::ChainSeg{static_cast<const char*>(nets[l].packed_bwd),
+                         reinterpret_cast<const float*>(static_cast<const char*>(nets[l].packed_fwd) + aon::kStreamBytes), sc.d_raw[l], L.masks, nullptr,
                          sc.dplanes[l], nullptr, L.Np};
   };
   auto chain = [&](const aon::ChainSeg* segs, int ns, hipStream_t st) {
@@ -589,47 +604,40 @@ LatentScratch carve_scratch_latents(char* base, int64_t n, int num_levels, const
   return sc;
 }
 
-// composite backward -> backward chain as train_bwd_impl launches them (same kernels, same arguments: same gradient planes), then the two
-// launches of aon_train_latent.hip.  Everything on the caller's stream.
-int latent_bwd_impl(const char* who, const TrainNet* nets, const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels,
-                    const float* const* g_rgb_host, const float* const* g_acc_host, const float* const* g_depth_host, const float* const* const* params,
-                    float* const* g_latents, void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, hipStream_t caller,
-                    const aon_render_opts* opts, const aon_ray_grads* rg = nullptr) {
+// composite backward -> backward chain by the functions train_bwd_impl launches them with (same gradient planes), then the two launches of
+// aon_train_latent.hip.  Everything on the caller's stream.  io.rg: the ray gradients as well, or null.
+int latent_bwd_impl(const char* who, const TrainNet* nets, const BwdCall& c, const BwdIo& io) {
   auto bad = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
   Geo g;
-  if (const char* b = make_geo(opts, g)) return fail(AON_E_INVALID, b);
+  if (const char* b = make_geo(c.opts, g)) return fail(AON_E_INVALID, b);
   g.other_degrees = false;   // (the articulated kernels carry their degrees themselves)
-  if (n_rays <= 0 || (num_levels != 1 && num_levels != 2)) return bad(AON_E_INVALID, "bad size / num_levels");
+  const aon_ray_grads* rg = io.rg;
+  float* const* g_latents = io.g_latents;
   // [ray gradients, DESIGN.md section 4.14] rg: the three latent outputs may all be null (a pose fitted under fixed codes)
   const bool want_latents = g_latents[0] || g_latents[1] || g_latents[2] || !rg;
-  if (rg && (!rg->rays_o || !rg->viewdirs || !rg->g_rays_o || !rg->g_rays_d || !rg->g_viewdirs)) return bad(AON_E_INVALID, "null member of aon_ray_grads");
-  if (!rays_d || !g_rgb_host || !workspace || !scratch || (want_latents && (!g_latents[0] || !g_latents[1] || !g_latents[2]))) return bad(AON_E_INVALID, "null pointer");
-  if (reinterpret_cast<uintptr_t>(scratch) & 255) return bad(AON_E_INVALID, "scratch must be 256-byte aligned");
-  const TrainWs w = carve_train(static_cast<char*>(workspace), n_rays, true, num_levels, g);
-  if (w.bytes > workspace_bytes) return bad(AON_E_WORKSPACE, "workspace smaller than aon_train_workspace_bytes()");
-  const LatentScratch sc = carve_scratch_latents(static_cast<char*>(scratch), n_rays, num_levels, g, rg != nullptr);
-  if (sc.bytes > scratch_bytes)
+  const bool rg_null = rg && (!rg->rays_o || !rg->viewdirs || !rg->g_rays_o || !rg->g_rays_d || !rg->g_viewdirs);
+  if (int rc = bwd_call_check(who, c, want_latents && (!g_latents[0] || !g_latents[1] || !g_latents[2]), rg_null ? "null member of aon_ray_grads" : nullptr))
+    return rc;
+  const int64_t n_rays = c.n_rays;
+  const int num_levels = c.num_levels;
+  const hipStream_t caller = c.stream;
+  const float* const* const* params = io.params;
+  const TrainWs w = carve_train(static_cast<char*>(c.workspace), n_rays, true, num_levels, g);
+  if (w.bytes > c.workspace_bytes) return bad(AON_E_WORKSPACE, "workspace smaller than aon_train_workspace_bytes()");
+  const LatentScratch sc = carve_scratch_latents(static_cast<char*>(c.scratch), n_rays, num_levels, g, rg != nullptr);
+  if (sc.bytes > c.scratch_bytes)
     return bad(AON_E_WORKSPACE, rg ? "scratch smaller than aon_train_scratch_bytes_inputs()" : "scratch smaller than aon_train_scratch_bytes_latents()");
   for (int l = 0; l < num_levels; ++l) {
     const void* pb = nets[l].packed_bwd;
-    if (!pb || !nets[l].small || !params[l] || !g_rgb_host[l]) return bad(AON_E_INVALID, "null level pointer");
+    if (!pb || !nets[l].small || !params[l] || !c.g_rgb[l]) return bad(AON_E_INVALID, "null level pointer");
     if (aon::stream_form(pb) != aon::stream_form(nets[l].small) || aon::stream_form(pb) != aon::stream_form(nets[0].packed_bwd))
       return bad(AON_E_INVALID, "transposed stream and per-call block were made in different forms (aon_set_bottleneck_fold changed in between)");
     for (int i : {0, 10, 20, 26})   // the weights a latent enters: all the W^T db products read (the ray gradients read 0 and 26)
       if (!params[l][i]) return bad(AON_E_INVALID, "null parameter pointer");
   }
-  for (int l = 0; l < num_levels; ++l) {
-    const TrainLevel& L = w.lvl[l];
-    const int64_t valid = n_rays * L.S;
-    if (int rc = check(hipMemsetAsync(sc.d_raw[l] + valid * 4, 0, (size_t)(L.Np - valid) * 16, caller), who)) return rc;
-    KTimer timer(kCompositeBwd, caller, n_rays);
-    if (int rc = check(aon::launch_composite_bwd(L.raw, L.t, rays_d, g_rgb_host[l], g_acc_host ? g_acc_host[l] : nullptr, g_depth_host ? g_depth_host[l] : nullptr,
-                                                 n_rays, L.S, white_bkgd, g.act(true, l, 0), sc.d_raw[l], caller), who)) return rc;
-  }
-  auto chain_seg = [&](int l) {
-    const TrainLevel& L = w.lvl[l];
-    return aon::ChainSeg{static_cast<const char*>(nets[l].packed_bwd), nets[l].small, sc.d_raw[l], L.masks, L.planes, sc.dplanes[l], sc.dxp[l], L.Np};
-  };
+  for (int l = 0; l < num_levels; ++l)
+    if (int rc = composite_bwd_stage(who, true, l, w.lvl[l], sc.d_raw[l], g, c, caller)) return rc;
+  auto chain_seg = [&](int l) { return art_chain_seg(nets[l], w.lvl[l], sc.d_raw[l], sc.dplanes[l], sc.dxp[l]); };
   if (num_levels == 2 && g_bwd_merge.load(std::memory_order_relaxed) != 0) {
     const aon::ChainSeg segs[2] = {chain_seg(1), chain_seg(0)};
     KTimer timer(kBwdChain, caller, w.lvl[0].Np + w.lvl[1].Np);
@@ -652,10 +660,9 @@ int latent_bwd_impl(const char* who, const TrainNet* nets, const float* rays_d, 
   aon::RayGradLevel rl[2];
   for (int l = 0; l < num_levels; ++l) {
     const TrainLevel& L = w.lvl[l];
-    rl[l] = aon::RayGradLevel{sc.dplanes[l], sc.dxp[l], L.Np, params[l], sc.rec[l], L.t, L.raw, g_rgb_host[l], g_acc_host ? g_acc_host[l] : nullptr,
-                              g_depth_host ? g_depth_host[l] : nullptr, g.act(true, l, 0), L.S};
+    rl[l] = aon::RayGradLevel{sc.dplanes[l], sc.dxp[l], L.Np, params[l], sc.rec[l], L.t, L.raw, c.g_rgb[l], c.acc(l), c.depth(l), g.act(true, l, 0), L.S};
   }
-  return check(aon::launch_ray_grads(rl, num_levels, n_rays, g.deg_view, white_bkgd, rays_d, rg->viewdirs, rg->g_rays_o, rg->g_rays_d, rg->g_viewdirs, caller), who);
+  return check(aon::launch_ray_grads(rl, num_levels, n_rays, g.deg_view, c.white_bkgd, c.rays_d, rg->viewdirs, rg->g_rays_o, rg->g_rays_d, rg->g_viewdirs, caller), who);
 }
 
 }  // namespace
@@ -685,25 +692,36 @@ int aon_set_fwd_overlap(int on) {
   return AON_OK;
 }
 
-// the workspace-size queries: the forward's workspace or the backward's scratch for n_rays (at least one) of the levels in use
-static int64_t train_bytes_query(int64_t n_rays, int articulated, int num_levels, const aon_render_opts* opts, bool scratch) {
+// the size queries: the forward's workspace or one of the backwards' scratch for n_rays (at least one) of the levels in use
+enum TrainBytes { kWorkspaceBytes, kScratchBytes, kLatentScratchBytes, kInputScratchBytes };
+static int64_t train_bytes_query(TrainBytes what, int64_t n_rays, int articulated, int num_levels, const aon_render_opts* opts) {
   Geo g;
   if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
   if (n_rays < 1) n_rays = 1;
   const int levels = num_levels == 1 ? 1 : 2;
-  return scratch ? carve_scratch(nullptr, n_rays, articulated != 0, levels, g).bytes : carve_train(nullptr, n_rays, articulated != 0, levels, g).bytes;
+  switch (what) {
+    case kWorkspaceBytes: return carve_train(nullptr, n_rays, articulated != 0, levels, g).bytes;
+    case kScratchBytes: return carve_scratch(nullptr, n_rays, articulated != 0, levels, g).bytes;
+    default: return carve_scratch_latents(nullptr, n_rays, levels, g, what == kInputScratchBytes).bytes;
+  }
 }
 int64_t aon_train_workspace_bytes_ex(int64_t n_rays, int articulated, int num_levels, const aon_render_opts* opts) {
-  return train_bytes_query(n_rays, articulated, num_levels, opts, false);
+  return train_bytes_query(kWorkspaceBytes, n_rays, articulated, num_levels, opts);
 }
 int64_t aon_train_workspace_bytes(int64_t n_rays, int articulated, int num_levels) {
   return aon_train_workspace_bytes_ex(n_rays, articulated, num_levels, nullptr);
 }
 int64_t aon_train_scratch_bytes_ex(int64_t n_rays, int articulated, int num_levels, const aon_render_opts* opts) {
-  return train_bytes_query(n_rays, articulated, num_levels, opts, true);
+  return train_bytes_query(kScratchBytes, n_rays, articulated, num_levels, opts);
 }
 int64_t aon_train_scratch_bytes(int64_t n_rays, int articulated, int num_levels) {
   return aon_train_scratch_bytes_ex(n_rays, articulated, num_levels, nullptr);
+}
+int64_t aon_train_scratch_bytes_latents(int64_t n_rays, int num_levels, const aon_render_opts* opts) {
+  return train_bytes_query(kLatentScratchBytes, n_rays, 1, num_levels, opts);
+}
+int64_t aon_train_scratch_bytes_inputs(int64_t n_rays, int num_levels, const aon_render_opts* opts) {
+  return train_bytes_query(kInputScratchBytes, n_rays, 1, num_levels, opts);
 }
 
 // ---- the exported training forwards: each lists its parameters once (the ABI) and builds the call record; _ex is _bounds without bounds ----
@@ -761,6 +779,7 @@ int aon_art_render_fwd_train(const void* packed_coarse, const void* small_coarse
                                      stream, nullptr);
 }
 
+// ---- the exported backwards: each lists its parameters once (the ABI), builds the call record and says what its network brings ----
 int aon_render_bwd(const void* packed_bwd_coarse, const void* packed_fwd_coarse, const void* packed_bwd_fine, const void* packed_fwd_fine,
                    const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels, const float* const* g_rgb_host,
                    const float* const* g_acc_host, const float* const* g_depth_host, float* const* grads_coarse_host,
@@ -776,9 +795,21 @@ int aon_render_bwd_ex(const void* packed_bwd_coarse, const void* packed_fwd_coar
                       float* const* grads_fine_host, void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
                       void* stream_, const aon_render_opts* opts) {
   const TrainNet nets[2] = {{packed_fwd_coarse, nullptr, packed_bwd_coarse}, {packed_fwd_fine, nullptr, packed_bwd_fine}};
-  float* const* grads[2] = {grads_coarse_host, grads_fine_host};
-  return train_bwd_impl("aon_render_bwd", false, nets, rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, nullptr, nullptr, grads,
-                        nullptr, workspace, workspace_bytes, scratch, scratch_bytes, (hipStream_t)stream_, opts);
+  BwdIo io{};
+  io.grads[0] = grads_coarse_host; io.grads[1] = grads_fine_host;
+  return train_bwd_impl("aon_render_bwd", false, nets,
+                        bwd_call(rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, workspace, workspace_bytes, scratch,
+                                 scratch_bytes, stream_, opts), io);
+}
+
+// [articulated] what the three backwards of the articulated network share: the levels' handles, the parameter arrays, the latent gradients
+struct ArtBwd { TrainNet nets[2]; BwdIo io; };
+static ArtBwd art_bwd(const void* packed_bwd_coarse, const void* small_coarse, const void* packed_bwd_fine, const void* small_fine,
+               const float* const* params_coarse_host, const float* const* params_fine_host, float* g_shape, float* g_appearance, float* g_articulation) {
+  ArtBwd a{{{nullptr, static_cast<const float*>(small_coarse), packed_bwd_coarse}, {nullptr, static_cast<const float*>(small_fine), packed_bwd_fine}}, {}};
+  a.io.params[0] = params_coarse_host; a.io.params[1] = params_fine_host;
+  a.io.g_latents[0] = g_shape; a.io.g_latents[1] = g_appearance; a.io.g_latents[2] = g_articulation;
+  return a;
 }
 
 int aon_art_render_bwd(const void* packed_bwd_coarse, const void* small_coarse, const void* packed_bwd_fine, const void* small_fine,
@@ -798,19 +829,26 @@ int aon_art_render_bwd_ex(const void* packed_bwd_coarse, const void* small_coars
                           float* const* grads_coarse_host, float* const* grads_fine_host, float* g_shape, float* g_appearance,
                           float* g_articulation, void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, void* stream_,
                           const aon_render_opts* opts) {
-  const TrainNet nets[2] = {{nullptr, static_cast<const float*>(small_coarse), packed_bwd_coarse}, {nullptr, static_cast<const float*>(small_fine), packed_bwd_fine}};
-  const float* const* params[2] = {params_coarse_host, params_fine_host};
-  float* const* grads[2] = {grads_coarse_host, grads_fine_host};
-  const float* latents[3] = {shape, appearance, articulation};
-  float* g_latents[3] = {g_shape, g_appearance, g_articulation};
-  return train_bwd_impl("aon_art_render_bwd", true, nets, rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, params, latents, grads,
-                        g_latents, workspace, workspace_bytes, scratch, scratch_bytes, (hipStream_t)stream_, opts);
+  ArtBwd a = art_bwd(packed_bwd_coarse, small_coarse, packed_bwd_fine, small_fine, params_coarse_host, params_fine_host, g_shape, g_appearance, g_articulation);
+  a.io.latents[0] = shape; a.io.latents[1] = appearance; a.io.latents[2] = articulation;
+  a.io.grads[0] = grads_coarse_host; a.io.grads[1] = grads_fine_host;
+  return train_bwd_impl("aon_art_render_bwd", true, a.nets,
+                        bwd_call(rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, workspace, workspace_bytes, scratch,
+                                 scratch_bytes, stream_, opts), a.io);
 }
 
-int64_t aon_train_scratch_bytes_latents(int64_t n_rays, int num_levels, const aon_render_opts* opts) {
-  Geo g;
-  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
-  return carve_scratch_latents(nullptr, n_rays < 1 ? 1 : n_rays, num_levels == 1 ? 1 : 2, g).bytes;
+// the latent-only backward and, with `rg`, the ray gradients (section 4.14); rg == NULL IS the latent-only call, name included
+int aon_art_render_bwd_inputs(const void* packed_bwd_coarse, const void* small_coarse, const void* packed_bwd_fine, const void* small_fine,
+                              const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels, const float* const* g_rgb_host,
+                              const float* const* g_acc_host, const float* const* g_depth_host, const float* const* params_coarse_host,
+                              const float* const* params_fine_host, float* g_shape, float* g_appearance, float* g_articulation,
+                              void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, void* stream_,
+                              const aon_render_opts* opts, const aon_ray_grads* rg) {
+  ArtBwd a = art_bwd(packed_bwd_coarse, small_coarse, packed_bwd_fine, small_fine, params_coarse_host, params_fine_host, g_shape, g_appearance, g_articulation);
+  a.io.rg = rg;
+  return latent_bwd_impl(rg ? "aon_art_render_bwd_inputs" : "aon_art_render_bwd_latents", a.nets,
+                         bwd_call(rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, workspace, workspace_bytes, scratch,
+                                  scratch_bytes, stream_, opts), a.io);
 }
 int aon_art_render_bwd_latents(const void* packed_bwd_coarse, const void* small_coarse, const void* packed_bwd_fine, const void* small_fine,
                                const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels, const float* const* g_rgb_host,
@@ -818,35 +856,9 @@ int aon_art_render_bwd_latents(const void* packed_bwd_coarse, const void* small_
                                const float* const* params_fine_host, float* g_shape, float* g_appearance, float* g_articulation,
                                void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, void* stream_,
                                const aon_render_opts* opts) {
-  const TrainNet nets[2] = {{nullptr, static_cast<const float*>(small_coarse), packed_bwd_coarse}, {nullptr, static_cast<const float*>(small_fine), packed_bwd_fine}};
-  const float* const* params[2] = {params_coarse_host, params_fine_host};
-  float* g_latents[3] = {g_shape, g_appearance, g_articulation};
-  return latent_bwd_impl("aon_art_render_bwd_latents", nets, rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, params,
-                         g_latents, workspace, workspace_bytes, scratch, scratch_bytes, (hipStream_t)stream_, opts);
-}
-
-
-// ---- ray gradients of a frozen articulated network ----
-int64_t aon_train_scratch_bytes_inputs(int64_t n_rays, int num_levels, const aon_render_opts* opts) {
-  Geo g;
-  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
-  return carve_scratch_latents(nullptr, n_rays < 1 ? 1 : n_rays, num_levels == 1 ? 1 : 2, g, true).bytes;
-}
-int aon_art_render_bwd_inputs(const void* packed_bwd_coarse, const void* small_coarse, const void* packed_bwd_fine, const void* small_fine,
-                              const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels, const float* const* g_rgb_host,
-                              const float* const* g_acc_host, const float* const* g_depth_host, const float* const* params_coarse_host,
-                              const float* const* params_fine_host, float* g_shape, float* g_appearance, float* g_articulation,
-                              void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, void* stream_,
-                              const aon_render_opts* opts, const aon_ray_grads* rg) {
-  if (!rg)
-    return aon_art_render_bwd_latents(packed_bwd_coarse, small_coarse, packed_bwd_fine, small_fine, rays_d, n_rays, white_bkgd, num_levels, g_rgb_host,
-                                      g_acc_host, g_depth_host, params_coarse_host, params_fine_host, g_shape, g_appearance, g_articulation, workspace,
-                                      workspace_bytes, scratch, scratch_bytes, stream_, opts);
-  const TrainNet nets[2] = {{nullptr, static_cast<const float*>(small_coarse), packed_bwd_coarse}, {nullptr, static_cast<const float*>(small_fine), packed_bwd_fine}};
-  const float* const* params[2] = {params_coarse_host, params_fine_host};
-  float* g_latents[3] = {g_shape, g_appearance, g_articulation};
-  return latent_bwd_impl("aon_art_render_bwd_inputs", nets, rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, params,
-                         g_latents, workspace, workspace_bytes, scratch, scratch_bytes, (hipStream_t)stream_, opts, rg);
+  return aon_art_render_bwd_inputs(packed_bwd_coarse, small_coarse, packed_bwd_fine, small_fine, rays_d, n_rays, white_bkgd, num_levels, g_rgb_host,
+                                   g_acc_host, g_depth_host, params_coarse_host, params_fine_host, g_shape, g_appearance, g_articulation, workspace,
+                                   workspace_bytes, scratch, scratch_bytes, stream_, opts, nullptr);
 }
 
 }  // extern "C"

@@ -144,5 +144,37 @@ inline int path_call_check(const char* who, const PathCall& c, const Geo& g, boo
   return AON_OK;
 }
 
+// The call record of the whole-path backward entry points (aon_render_bwd* / aon_art_render_bwd* / aon_grender_bwd), as PathCall is the
+// forwards': what the ABI's lists have in common around the network's own pointers.  g_rgb / g_acc / g_depth: the host arrays of per-level
+// device pointers as passed (g_acc / g_depth may be null, and so may their entries).
+struct BwdCall {
+  const float* rays_d; int64_t n_rays; int white_bkgd, num_levels;
+  const float* const* g_rgb; const float* const* g_acc; const float* const* g_depth;
+  void* workspace; int64_t workspace_bytes; void* scratch; int64_t scratch_bytes; hipStream_t stream;
+  const aon_render_opts* opts;
+  const float* acc(int l) const { return g_acc ? g_acc[l] : nullptr; }
+  const float* depth(int l) const { return g_depth ? g_depth[l] : nullptr; }
+};
+// (in the exported functions' order, without the network's pointers between g_depth_host and workspace)
+inline BwdCall bwd_call(const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels, const float* const* g_rgb_host, const float* const* g_acc_host,
+                        const float* const* g_depth_host, void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes, void* stream,
+                        const aon_render_opts* opts) {
+  return BwdCall{rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, workspace, workspace_bytes, scratch, scratch_bytes,
+                 static_cast<hipStream_t>(stream), opts};
+}
+
+// The checks every whole-path backward makes before any launch, in their order: size / num_levels, null pointers, alignment.  Two of
+// an entry point's own refusals rank among these and are handed in already judged: `site_first` (its message, or null) is reported right
+// behind the size check, `site_null` (a pointer of the network's that the call needs is null) with the common null pointers.  Everything else the
+// network brings (level pointers, forms, parameter and gradient arrays) and the two size refusals, which follow a carve, stay at the site.
+inline int bwd_call_check(const char* who, const BwdCall& c, bool site_null = false, const char* site_first = nullptr) {
+  auto bad = [&](const char* what) { return fail(AON_E_INVALID, (std::string(who) + ": " + what).c_str()); };
+  if (c.n_rays <= 0 || (c.num_levels != 1 && c.num_levels != 2)) return bad("bad size / num_levels");
+  if (site_first) return bad(site_first);
+  if (!c.rays_d || !c.g_rgb || !c.workspace || !c.scratch || site_null) return bad("null pointer");
+  if ((reinterpret_cast<uintptr_t>(c.workspace) | reinterpret_cast<uintptr_t>(c.scratch)) & 255) return bad("workspace / scratch must be 256-byte aligned");
+  return AON_OK;
+}
+
 }  // namespace capi
 }  // namespace aon

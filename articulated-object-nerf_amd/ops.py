@@ -1173,61 +1173,88 @@ def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[0 if t is None else t.data_ptr() for t in tensors])
 
 
+class _BwdCall:
+    """The prologue of every whole-path backward, and the Python side of csrc/aon_capi_util.h's BwdCall: rays_d,
+    the per-level g_* pointer arrays, the encoding degrees and aon_render_opts struct of the forward's `geometry`, and the per-level
+    parameter arrays (`param_array(params, degrees)` -> (tensors, C array)).  `call` is the C call itself: the network's `packs`, the
+    common head, what the network adds (`net`), the common tail for `ws` and `scratch`, `extra`.  The object holds every tensor those
+    pointers refer to: keep it until the call has returned."""
+
+    def __init__(self, rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, geometry, param_array=None, params_per_level=()):
+        self.d = d = _f32(rays_d, "rays_d")
+        self.n, self.dev, self.k = d.shape[0], d.device, num_levels
+        self.st = st = None if geometry is None else geometry[0]
+        self.degrees = (0, 10, 4) if st is None else (int(st.min_deg_point), int(st.max_deg_point), int(st.deg_view))
+        made = [param_array(params, self.degrees) for params in params_per_level]
+        self._keep = ([m[0] for m in made], [[None if t is None else _f32(t, "grad") for t in g] for g in (g_rgb, g_acc, g_depth)])
+        self.parr = self.pad(m[1] for m in made)
+        self._head = (_ptr(d), self.n, int(bool(white_bkgd)), num_levels, *(_ptr_array(g) for g in self._keep[1]))
+
+    def pad(self, per_level):
+        """per-level entries as the C lists take them: always two, None for a level not in use"""
+        return list(per_level) + [None] * (2 - self.k)
+
+    def grad_arrays(self, order, shapes, grads_out=None):
+        """-> (per-level dicts the C call writes the parameter gradients into, their two pointer arrays)"""
+        grads = _grad_dicts(order, shapes, self.k, self.dev, grads_out)
+        return grads, self.pad(_ptr_array([g[nm] for nm in order]) for g in grads)
+
+    def call(self, name, packs, net, ws, scratch, *extra):
+        """`scratch` comes from the pool and goes back to it once the call has succeeded (an _ex form reports under the plain name)."""
+        with torch.cuda.device(self.dev):
+            check(getattr(lib, name)(*packs, *self._head, *net, _ptr(ws), ws.numel(), _ptr(scratch), scratch.numel(), _stream(),
+                                     None if self.st is None else C.byref(self.st), *extra), name.removesuffix("_ex"))
+        pool_give(scratch)
+
+
 def render_bwd(ws, packs_bwd, packs_fwd, rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, geometry=None, grads_out=None):
     """loss.backward() through render_fwd_train (vanilla): g_* = per-level lists (entries may be None except g_rgb)
     -> per-level dicts of the 24 parameter gradients (shapes of the network's own encoding degrees, read from `geometry`).
     `grads_out`: per level, the 24 tensors to write them into (views of a gradient arena, aon_amd/arena.py) instead of fresh ones."""
-    d = _f32(rays_d, "rays_d")
-    n, dev = d.shape[0], d.device
-    st0 = None if geometry is None else geometry[0]
-    shapes = vanilla_param_shapes((0, 10, 4) if st0 is None else (st0.min_deg_point, st0.max_deg_point, st0.deg_view))
-    grads = _grad_dicts(VANILLA_PARAM_ORDER, shapes, num_levels, dev, grads_out)
-    garr = [_ptr_array([g[nm] for nm in VANILLA_PARAM_ORDER]) for g in grads] + [None] * (2 - num_levels)
-    pb, pf = list(packs_bwd) + [None] * (2 - num_levels), list(packs_fwd) + [None] * (2 - num_levels)
-    keep = [None if t is None else _f32(t, "grad") for t in list(g_rgb) + list(g_acc) + list(g_depth)]
-    k = num_levels
-    st = None if geometry is None else geometry[0]
-    scratch = train_scratch(dev, n, False, num_levels, st)
-    with torch.cuda.device(dev):
-        check(lib.aon_render_bwd_ex(_pk(pb[0]), _pk(pf[0]), _pk(pb[1]), _pk(pf[1]), _ptr(d), n, int(bool(white_bkgd)), num_levels,
-                                    _ptr_array(keep[:k]), _ptr_array(keep[k:2 * k]), _ptr_array(keep[2 * k:3 * k]), garr[0], garr[1], _ptr(ws), ws.numel(),
-                                    _ptr(scratch), scratch.numel(), _stream(), None if st is None else C.byref(st)), "aon_render_bwd")
-    pool_give(scratch)
+    bc = _BwdCall(rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, geometry)
+    grads, garr = bc.grad_arrays(VANILLA_PARAM_ORDER, vanilla_param_shapes(bc.degrees), grads_out)
+    pb, pf = bc.pad(packs_bwd), bc.pad(packs_fwd)
+    bc.call("aon_render_bwd_ex", (_pk(pb[0]), _pk(pf[0]), _pk(pb[1]), _pk(pf[1])), garr, ws,
+            train_scratch(bc.dev, bc.n, False, num_levels, bc.st))
     return grads
+
+
+_LATENT_KEYS = (("density", 128), ("color", 128), ("articulation", 32))
+
+
+def _art_render_bwd(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, params_per_level, geometry, latents=None,
+                    grads_out=None, rays=None, want_latents=True):
+    """The three backwards of the articulated network, one body.  `latents` given: the full backward (aon_art_render_bwd_ex) -> (parameter
+    gradients, latent gradients); else the frozen network's: latent gradients alone, or with `rays` = (rays_o, viewdirs) -> (latent
+    gradients or None, g_rays_o, g_rays_d, g_viewdirs)."""
+    rays = None if rays is None else (_f32(rays[0], "rays_o"), _f32(rays[1], "viewdirs"))
+    bc = _BwdCall(rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, geometry, _art_param_array, params_per_level)
+    n, dev, st = bc.n, bc.dev, bc.st
+    pb, sm = bc.pad(packs_bwd), bc.pad(smalls)
+    packs = (_pk(pb[0]), _pk(sm[0]), _pk(pb[1]), _pk(sm[1]))
+    g_lat = {k: torch.empty(w, device=dev) for k, w in _LATENT_KEYS} if want_latents else None
+    lat_ptrs = [None if g_lat is None else _ptr(g_lat[k]) for k, _ in _LATENT_KEYS]
+    if latents is not None:
+        grads, garr = bc.grad_arrays(ART_PARAM_ORDER, art_param_shapes(bc.degrees), grads_out)
+        codes = [_latent(latents, k, w) for k, w in _LATENT_KEYS]
+        bc.call("aon_art_render_bwd_ex", packs, (*bc.parr, *(_ptr(t) for t in codes), *garr, *lat_ptrs), ws,
+                train_scratch(dev, n, True, num_levels, st))
+        return grads, g_lat
+    if rays is None:
+        bc.call("aon_art_render_bwd_latents", packs, (*bc.parr, *lat_ptrs), ws, train_scratch_latents(dev, n, num_levels, st))
+        return g_lat
+    g_rays = tuple(torch.empty((n, 3), dtype=torch.float32, device=dev) for _ in range(3))
+    rg = _lib.RayGradsC(rays[0].data_ptr(), rays[1].data_ptr(), *(g.data_ptr() for g in g_rays))
+    bc.call("aon_art_render_bwd_inputs", packs, (*bc.parr, *lat_ptrs), ws, train_scratch_inputs(dev, n, num_levels, st), C.byref(rg))
+    return (g_lat, *g_rays)
 
 
 def art_render_bwd(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, params_per_level, latents: dict, geometry=None,
                    grads_out=None):
     """Articulated twin -> (per-level dicts of the 40 parameter gradients, dict of latent gradients summed over the levels).
     `grads_out`: as render_bwd."""
-    d = _f32(rays_d, "rays_d")
-    n, dev = d.shape[0], d.device
-    st0 = None if geometry is None else geometry[0]
-    degrees = (0, 10, 4) if st0 is None else (int(st0.min_deg_point), int(st0.max_deg_point), int(st0.deg_view))
-    shapes = art_param_shapes(degrees)
-    grads = _grad_dicts(ART_PARAM_ORDER, shapes, num_levels, dev, grads_out)
-    garr = [_ptr_array([g[nm] for nm in ART_PARAM_ORDER]) for g in grads] + [None] * (2 - num_levels)
-    tens, parr = [], []
-    for params in params_per_level:
-        t, arr = _art_param_array(params, degrees)
-        tens.append(t)
-        parr.append(arr)
-    parr += [None] * (2 - num_levels)
-    pb, sm = list(packs_bwd) + [None] * (2 - num_levels), list(smalls) + [None] * (2 - num_levels)
-    shape, app, art = _latent(latents, "density", 128), _latent(latents, "color", 128), _latent(latents, "articulation", 32)
-    g_lat = {"density": torch.empty(128, device=dev), "color": torch.empty(128, device=dev), "articulation": torch.empty(32, device=dev)}
-    keep = [None if t is None else _f32(t, "grad") for t in list(g_rgb) + list(g_acc) + list(g_depth)]
-    k = num_levels
-    st = None if geometry is None else geometry[0]
-    scratch = train_scratch(dev, n, True, num_levels, st)
-    with torch.cuda.device(dev):
-        check(lib.aon_art_render_bwd_ex(_pk(pb[0]), _pk(sm[0]), _pk(pb[1]), _pk(sm[1]), _ptr(d), n, int(bool(white_bkgd)), num_levels,
-                                        _ptr_array(keep[:k]), _ptr_array(keep[k:2 * k]), _ptr_array(keep[2 * k:3 * k]), parr[0], parr[1],
-                                        _ptr(shape), _ptr(app), _ptr(art), garr[0], garr[1], _ptr(g_lat["density"]), _ptr(g_lat["color"]),
-                                        _ptr(g_lat["articulation"]), _ptr(ws), ws.numel(), _ptr(scratch), scratch.numel(), _stream(),
-                                        None if st is None else C.byref(st)), "aon_art_render_bwd")
-    pool_give(scratch)
-    return grads, g_lat
+    return _art_render_bwd(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, params_per_level, geometry, latents=latents,
+                           grads_out=grads_out)
 
 
 def train_scratch_latents(device, n_rays: int, num_levels: int = 2, st=None) -> torch.Tensor:
@@ -1241,29 +1268,7 @@ def art_render_bwd_latents(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels
     """loss.backward() through render_fwd_train of a FROZEN articulated network -> dict of the three latent gradients summed over the
     levels, bit-equal to `art_render_bwd`'s second result for the same workspace and g_*; no parameter gradient is computed or written
     (aon_art_render_bwd_latents)."""
-    d = _f32(rays_d, "rays_d")
-    n, dev = d.shape[0], d.device
-    st = None if geometry is None else geometry[0]
-    degrees = (0, 10, 4) if st is None else (int(st.min_deg_point), int(st.max_deg_point), int(st.deg_view))
-    tens, parr = [], []
-    for params in params_per_level:
-        t, arr = _art_param_array(params, degrees)
-        tens.append(t)
-        parr.append(arr)
-    parr += [None] * (2 - num_levels)
-    pb, sm = list(packs_bwd) + [None] * (2 - num_levels), list(smalls) + [None] * (2 - num_levels)
-    g_lat = {"density": torch.empty(128, device=dev), "color": torch.empty(128, device=dev), "articulation": torch.empty(32, device=dev)}
-    keep = [None if t is None else _f32(t, "grad") for t in list(g_rgb) + list(g_acc) + list(g_depth)]
-    k = num_levels
-    scratch = train_scratch_latents(dev, n, num_levels, st)
-    with torch.cuda.device(dev):
-        check(lib.aon_art_render_bwd_latents(_pk(pb[0]), _pk(sm[0]), _pk(pb[1]), _pk(sm[1]), _ptr(d), n, int(bool(white_bkgd)), num_levels,
-                                             _ptr_array(keep[:k]), _ptr_array(keep[k:2 * k]), _ptr_array(keep[2 * k:3 * k]), parr[0], parr[1],
-                                             _ptr(g_lat["density"]), _ptr(g_lat["color"]), _ptr(g_lat["articulation"]), _ptr(ws), ws.numel(),
-                                             _ptr(scratch), scratch.numel(), _stream(), None if st is None else C.byref(st)),
-              "aon_art_render_bwd_latents")
-    pool_give(scratch)
-    return g_lat
+    return _art_render_bwd(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, params_per_level, geometry)
 
 
 def train_scratch_inputs(device, n_rays: int, num_levels: int = 2, st=None) -> torch.Tensor:
@@ -1277,34 +1282,8 @@ def art_render_bwd_inputs(ws, packs_bwd, smalls, rays_o, rays_d, viewdirs, white
     """loss.backward() through render_fwd_train of a FROZEN articulated network, down to its inputs -> (dict of the three latent gradients,
     bit-equal to `art_render_bwd_latents`' -- or None when `want_latents` is false: the latent launches are skipped --, g_rays_o, g_rays_d,
     g_viewdirs), each (n, 3), summed over the levels.  t is data: no gradient through the sampler or near / far."""
-    d, o, v = _f32(rays_d, "rays_d"), _f32(rays_o, "rays_o"), _f32(viewdirs, "viewdirs")
-    n, dev = d.shape[0], d.device
-    st = None if geometry is None else geometry[0]
-    degrees = (0, 10, 4) if st is None else (int(st.min_deg_point), int(st.max_deg_point), int(st.deg_view))
-    tens, parr = [], []
-    for params in params_per_level:
-        t, arr = _art_param_array(params, degrees)
-        tens.append(t)
-        parr.append(arr)
-    parr += [None] * (2 - num_levels)
-    pb, sm = list(packs_bwd) + [None] * (2 - num_levels), list(smalls) + [None] * (2 - num_levels)
-    g_lat = None
-    if want_latents:
-        g_lat = {"density": torch.empty(128, device=dev), "color": torch.empty(128, device=dev), "articulation": torch.empty(32, device=dev)}
-    lat_ptrs = [None if g_lat is None else _ptr(g_lat[k]) for k in ("density", "color", "articulation")]
-    g_o, g_d, g_v = (torch.empty((n, 3), dtype=torch.float32, device=dev) for _ in range(3))
-    rg = _lib.RayGradsC(o.data_ptr(), v.data_ptr(), g_o.data_ptr(), g_d.data_ptr(), g_v.data_ptr())
-    keep = [None if t is None else _f32(t, "grad") for t in list(g_rgb) + list(g_acc) + list(g_depth)]
-    k = num_levels
-    scratch = train_scratch_inputs(dev, n, num_levels, st)
-    with torch.cuda.device(dev):
-        check(lib.aon_art_render_bwd_inputs(_pk(pb[0]), _pk(sm[0]), _pk(pb[1]), _pk(sm[1]), _ptr(d), n, int(bool(white_bkgd)), num_levels,
-                                            _ptr_array(keep[:k]), _ptr_array(keep[k:2 * k]), _ptr_array(keep[2 * k:3 * k]), parr[0], parr[1],
-                                            *lat_ptrs, _ptr(ws), ws.numel(), _ptr(scratch), scratch.numel(), _stream(),
-                                            None if st is None else C.byref(st), C.byref(rg)),
-              "aon_art_render_bwd_inputs")
-    pool_give(scratch)
-    return g_lat, g_o, g_d, g_v
+    return _art_render_bwd(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, params_per_level, geometry,
+                           rays=(rays_o, viewdirs), want_latents=want_latents)
 
 
 # ------------------------------------------------------------------ differentiable rays from a camera pose (torch ops on (N, 3): no kernel)
@@ -1490,27 +1469,11 @@ def grender_fwd_train(geom: MlpGeometry, params_c: dict, params_f, rays_o, rays_
 
 def grender_bwd(geom: MlpGeometry, ws, params_per_level, rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, geometry):
     """loss.backward() through grender_fwd_train -> per-level dicts of parameter gradients."""
-    d = _f32(rays_d, "rays_d")
-    n, dev = d.shape[0], d.device
+    bc = _BwdCall(rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, geometry, lambda params, _: _gmlp_param_array(geom, params), params_per_level)
     gst = geom.c_struct()
-    shapes, order = geom.param_shapes, geom.param_order
-    grads = [{name: torch.empty(shapes[name], dtype=torch.float32, device=dev) for name in order} for _ in range(num_levels)]
-    garr = [_ptr_array([g[nm] for nm in order]) for g in grads] + [None] * (2 - num_levels)
-    tens, parr = [], []
-    for params in params_per_level:
-        t, arr = _gmlp_param_array(geom, params)
-        tens.append(t)
-        parr.append(arr)
-    parr += [None] * (2 - num_levels)
-    keep = [None if t is None else _f32(t, "grad") for t in list(g_rgb) + list(g_acc) + list(g_depth)]
-    k = num_levels
-    st = geometry[0]
-    scratch = _pool_take(int(lib.aon_grender_train_scratch_bytes(C.byref(gst), n, num_levels, C.byref(st))), "aon_grender_train_scratch_bytes", dev)
-    with torch.cuda.device(dev):
-        check(lib.aon_grender_bwd(C.byref(gst), parr[0], parr[1], _ptr(d), n, int(bool(white_bkgd)), num_levels, _ptr_array(keep[:k]),
-                                  _ptr_array(keep[k:2 * k]), _ptr_array(keep[2 * k:3 * k]), garr[0], garr[1], _ptr(ws), ws.numel(), _ptr(scratch),
-                                  scratch.numel(), _stream(), C.byref(st)), "aon_grender_bwd")
-    pool_give(scratch)
+    grads, garr = bc.grad_arrays(geom.param_order, geom.param_shapes)
+    scratch = _pool_take(int(lib.aon_grender_train_scratch_bytes(C.byref(gst), bc.n, num_levels, C.byref(bc.st))), "aon_grender_train_scratch_bytes", bc.dev)
+    bc.call("aon_grender_bwd", (C.byref(gst), *bc.parr), garr, ws, scratch)
     return grads
 
 

@@ -1,7 +1,8 @@
 """GPU: the ladder of exported whole-path forwards (plain, _ex, _occ, _stop, _bounds; _train, _train_ex, _train_bounds) called through
 ctypes directly, both networks.  Every rung with its extras switched off must give the bits of the rung below it: all of them hand one
 call record to the same driver, and an argument transposed on the way compiles and type-checks.  ops.py never
-calls the plain forms nor the _bounds forms with a null `bounds`, so only this file reaches them."""
+calls the plain forms nor the _bounds forms with a null `bounds`, so only this file reaches them.  The training ladder ends in the
+backwards: plain and _ex, and for the articulated network the latent-only one and aon_art_render_bwd_inputs with and without ray gradients."""
 import ctypes as C
 
 import pytest
@@ -205,3 +206,28 @@ def test_training_ladder(dev, art):
     want = backward(bwd, wss[0].clone())
     _same(backward(bwd + "_ex", wss[0].clone(), None), want, "render_bwd_ex(NULL) vs render_bwd")
     assert sum(bool((t != 0).any()) for t in want) > len(want) // 2      # not vacuous: gradients arrived
+    if not art:
+        return
+
+    # the frozen network's backwards on the same workspace contents: the latent gradients are aon_art_render_bwd_ex's bits
+    def frozen(name, query, ws, rg=()):
+        need = int(getattr(lib, query)(n, 2, None))
+        assert 0 < need < scratch_bytes
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        g_lat = [torch.full((w,), float("nan"), device=dev) for w in (128, 128, 32)]
+        params = [arr([p[k] for k in net.order]) for p in net.params]
+        with torch.cuda.device(dev):
+            rc = getattr(lib, name)(_p(net.bwd[0]), _p(net.small[0]), _p(net.bwd[1]), _p(net.small[1]), _p(rays[1]), n, 1, 2, arr(g_rgb), None, None, *params,
+                                    *(_p(t) for t in g_lat), _p(ws), ws.numel(), _p(scratch), scratch.numel(), None, None, *rg)
+        _lib.check(rc, name)
+        torch.cuda.synchronize(dev)
+        return g_lat
+
+    _same(frozen("aon_art_render_bwd_latents", "aon_train_scratch_bytes_latents", wss[0].clone()), want[-3:], "render_bwd_latents vs render_bwd_ex")
+    _same(frozen("aon_art_render_bwd_inputs", "aon_train_scratch_bytes_latents", wss[0].clone(), (None,)), want[-3:],
+          "render_bwd_inputs(rg=NULL) vs render_bwd_ex")
+    g_rays = [torch.full((n, 3), float("nan"), device=dev) for _ in range(3)]
+    rg = _lib.RayGradsC(rays[0].data_ptr(), rays[2].data_ptr(), *(t.data_ptr() for t in g_rays))
+    _same(frozen("aon_art_render_bwd_inputs", "aon_train_scratch_bytes_inputs", wss[0].clone(), (C.byref(rg),)), want[-3:],
+          "render_bwd_inputs(rg) vs render_bwd_ex")
+    assert all(torch.isfinite(t).all() for t in g_rays) and any(bool((t != 0).any()) for t in g_rays)

@@ -55,7 +55,7 @@ struct PackArgs {
 
 // (pos_col_in / view_col_in: aon_mlp_core.h)
 // FOLD: the folded form (aon_common.h).  W' / b' were written to packed + kFoldTmpOff by launch_fold_view on the same stream; the pack
-// kernel's own writes stay below kStreamBytesF or at / above kStreamBytes, so it never overwrites what it reads.
+// kernel's own writes stay below kStreamBytesF, behind W' / b', or at / above kStreamBytes, so it never overwrites what it reads.
 template <bool FOLD>
 __global__ void pack_vanilla_kernel(PackArgs a, float* __restrict__ packed, int L, int Lv) {
   const int P = 3 + 6 * L, V = 3 + 6 * Lv;
@@ -64,7 +64,10 @@ __global__ void pack_vanilla_kernel(PackArgs a, float* __restrict__ packed, int 
   constexpr int64_t used_floats = FOLD ? kStreamBytesF / 4 : stream_floats;
   const float* Wf = packed + kFoldTmpOff / 4;      // [FOLD] (128, 256), then b' (128)
   if (idx >= stream_floats + kSmallFloats) return;
-  if (idx >= used_floats && idx < stream_floats) return;   // [FOLD] the fold temporaries / unused tail of the literal-size buffer
+  if (idx >= used_floats && idx < stream_floats) {   // [FOLD] the fold temporaries, then the unused tail of the literal-size buffer:
+    if (idx >= used_floats + 128 * 256 + 128) packed[idx] = 0.f;   // zeroed, so that every byte of the buffer the caller handed in is defined
+    return;
+  }
   if (idx >= stream_floats) {  // resident small vectors
     const int s = (int)(idx - stream_floats);
     float v = 0.f;

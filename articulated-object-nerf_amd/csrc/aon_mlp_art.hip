@@ -59,7 +59,10 @@ __device__ __forceinline__ void pack_art_element(const Args& a, float* __restric
   const int P = 3 + 6 * L, V = 3 + 6 * Lv;
   auto pcol = [&](int c63) { return c63 < 0 ? -1 : pos_col_in(c63, L); };
   auto vcol = [&](int c27) { return c27 < 0 ? -1 : view_col_in(c27, Lv); };
-  if (idx >= (FOLD ? kAStreamBytesF : kAStreamBytes) / 4) return;
+  if (idx >= (FOLD ? kAStreamBytesF : kAStreamBytes) / 4) {   // [FOLD] W' (read below), then the unused tail of the literal-size buffer:
+    if (FOLD && idx >= kAFoldTmpOff / 4 + 128 * 256 && idx < kAStreamBytes / 4) packed[idx] = 0.f;   // zeroed: every byte of the buffer is defined
+    return;
+  }
   // locate the chunk
   int c, r, nt;
   constexpr int first_small_tail = FOLD ? kAChFV0 : kAChV0;
@@ -478,7 +481,7 @@ hipError_t launch_pack_art(const float* const* params, float* packed, hipStream_
       const FoldGemm job = art_fold_job_fwd(params, packed, view_levels);
       if (hipError_t e = launch_fold_gemms(&job, 1, stream); e != hipSuccess) return e;
     }
-    const int64_t n = kAStreamBytesF / 4;
+    const int64_t n = kAStreamBytes / 4;   // (the whole buffer: the kernel zeroes what lies behind W')
     pack_art_kernel<true><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(a, packed, pos_levels, view_levels);
   } else {
     const int64_t n = kAStreamBytes / 4;
@@ -510,7 +513,7 @@ hipError_t launch_pack_prepare_art2(const float* const* const params[2], const f
     set_stream_form(packed[l], form);
     set_stream_form(small[l], form);
   }
-  const int64_t n = (form == kFormFolded ? kAStreamBytesF : kAStreamBytes) / 4;
+  const int64_t n = kAStreamBytes / 4;   // (either form: the whole buffer, see pack_art_element)
   const dim3 grid((unsigned)(kPrepBlocks + (n + 255) / 256), 2);
   if (form == kFormFolded) pack_prepare_art2_kernel<true><<<grid, dim3(256), 0, stream>>>(a, min_deg, pos_levels, view_levels);
   else pack_prepare_art2_kernel<false><<<grid, dim3(256), 0, stream>>>(a, min_deg, pos_levels, view_levels);

@@ -216,7 +216,10 @@ __global__ void pack_vanilla_bwd_kernel(PackArgs24 a, float* __restrict__ packed
       return;
     }
   }
-  if (idx >= (FOLD ? kBwFStreamBytes : kBwStreamBytes) / 4) return;
+  if (idx >= (FOLD ? kBwFStreamBytes : kBwStreamBytes) / 4) {   // [literal] the buffer has the folded form's size: its tail is zeroed, so that
+    if (!FOLD && idx < kBwBufferBytes / 4) packed[idx] = 0.f;      // every byte of the buffer the caller handed in is defined
+    return;
+  }
   int c = (int)(idx / (kBigChunkBytes / 4));
   const int r = (int)(idx % (kBigChunkBytes / 4));
   const int cc = r & 3, lane = (r >> 2) & 63, rest = r >> 8;
@@ -406,7 +409,7 @@ hipError_t launch_pack_vanilla_bwd(const float* const* params, float* packed, hi
     const int64_t n = kBwFOffWf / 4;   // the stream and the raw copies behind it
     pack_vanilla_bwd_kernel<true><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(a, packed, pos_size, view_size);
   } else {
-    const int64_t n = kBwStreamBytes / 4;
+    const int64_t n = kBwBufferBytes / 4;   // (the whole buffer: the kernel zeroes what lies behind the stream)
     pack_vanilla_bwd_kernel<false><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(a, packed, pos_size, view_size);
   }
   return hipGetLastError();

@@ -76,7 +76,10 @@ template <bool FOLD>
 __device__ __forceinline__ void pack_art_bwd_element(const ArtParams& a, float* __restrict__ packed, int L, int Lv, const int64_t idx0, const int64_t idx) {
   using N = std::conditional_t<FOLD, ArtBwdFoldNet, ArtBwdNet>;
   const int P = 3 + 6 * L, V = 3 + 6 * Lv;   // (row strides of the three concatenating layers; the view-encoding columns are never read)
-  if (idx >= (FOLD ? kABwFStreamBytes : kABwStreamBytes) / 4) return;
+  if (idx >= (FOLD ? kABwFStreamBytes : kABwStreamBytes) / 4) {   // [FOLD] W' (read below), then the unused tail of the literal-size buffer:
+    if (FOLD && idx >= kABwFOffWf / 4 + 128 * 256 && idx < kABwStreamBytes / 4) packed[idx] = 0.f;   // zeroed: every byte of the buffer is defined
+    return;
+  }
   // locate the chunk.  The stream is a handful of RUNS of equal-sized chunks (16 / 32 / 8 / 32 / 8 / 16 KiB): find the run of the BLOCK's
   // first index `idx0` (chunks are multiples of 4 KiB, a block is 1 KiB of the stream: one chunk per block, scalar instructions), then the
   // chunk inside it by a shift.  Rounds 2-5 scanned the ~100 chunks one by one on the thread's own index -- a few thousand vector
@@ -478,7 +481,7 @@ hipError_t launch_pack_art_bwd2(const float* const* const params[2], float* cons
     a.packed[l] = packed[l];
     set_stream_form(packed[l], form);
   }
-  const int64_t n = (form == kFormFolded ? kABwFStreamBytes : kABwStreamBytes) / 4;
+  const int64_t n = kABwStreamBytes / 4;   // (either form: the whole buffer, see pack_art_bwd_element)
   const dim3 grid((unsigned)((n + 255) / 256), 2);
   if (form == kFormFolded) pack_art_bwd2_kernel<true><<<grid, dim3(256), 0, stream>>>(a, pos_levels, view_levels);
   else pack_art_bwd2_kernel<false><<<grid, dim3(256), 0, stream>>>(a, pos_levels, view_levels);
@@ -495,7 +498,7 @@ hipError_t launch_pack_art_bwd(const float* const* params, float* packed, hipStr
       const FoldGemm job = art_fold_job_bwd(params, packed, view_levels);
       if (hipError_t e = launch_fold_gemms(&job, 1, stream); e != hipSuccess) return e;
     }
-    const int64_t n = kABwFStreamBytes / 4;
+    const int64_t n = kABwStreamBytes / 4;   // (the whole buffer: the kernel zeroes what lies behind W')
     pack_art_bwd_kernel<true><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(a, packed, pos_levels, view_levels);
   } else {
     const int64_t n = kABwStreamBytes / 4;

@@ -10,7 +10,9 @@
  *   - every pointer is a DEVICE pointer to contiguous row-major fp32 unless the parameter is marked `host`;
  *   - nothing is allocated, freed or synchronised inside: outputs and workspace are caller-owned, launches are
  *     enqueued on `stream` (a hipStream_t passed as void*; NULL = the default stream) and return immediately;
- *   - inputs are never written;
+ *   - inputs are never written; outputs are written inside their stated extents and nowhere else; a workspace, scratch or packed
+ *     buffer of exactly the byte count its aon_*_bytes query returns is enough, and a pack call defines every byte of that buffer
+ *     (tests/test_hip_extents.py holds every entry point that takes a stream to this, with guard bands);
  *   - return value: 0 = success, negative = failure (AON_E_* below, or -(hipError_t) - 1000 for a HIP error);
  *     aon_last_error() returns a thread-local human-readable message for the last failure.
  */

@@ -211,7 +211,18 @@ class RayBoundsC(C.Structure):
     _fields_ = [("near_ray", C.c_void_p), ("far_ray", C.c_void_p), ("live", C.c_void_p)]
 
 
-for _name, (_res, _args) in _SIGS.items():
+def _ext_sigs():
+    """include/aon_hip_inputs.h: the extension header's entry points, composed like the others.  Bound like _SIGS, but kept out of
+    `exported_symbols()`, which lists include/aon_hip.h's names."""
+    head, tail = _BWD
+    return {"aon_render_bwd_inputs": (_i, _VANILLA * 2 + head + _PER_LEVEL + tail + _OPTS + _RAY_GRADS),   # ... parameters (DESIGN.md section 4.15)
+            "aon_train_scratch_bytes_inputs_vanilla": (_l, [_l, _i] + _OPTS)}
+
+
+_EXT_SIGS = _ext_sigs()
+
+
+for _name, (_res, _args) in {**_SIGS, **_EXT_SIGS}.items():
     _fn = getattr(lib, _name)  # AttributeError here = the .so does not export what the header declares
     _fn.restype = _res
     _fn.argtypes = _args
@@ -239,3 +250,8 @@ def check(rc: int, what: str = "") -> None:
 
 def exported_symbols():
     return sorted(_SIGS)
+
+
+def extension_symbols():
+    """the names include/aon_hip_inputs.h declares"""
+    return sorted(_EXT_SIGS)

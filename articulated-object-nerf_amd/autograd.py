@@ -3,7 +3,8 @@
 ``training_step`` (``loss.backward()``, model.py:264-282) works unchanged.  Forward and backward are both HIP kernels
 (no eager-PyTorch math): fused forward with activation planes -> composite backward -> fused data-gradient chain ->
 grouped split-N weight-gradient GEMMs, each direction ONE C call (aon_render_fwd_train / aon_render_bwd).  Gradients reach only the MLP parameters: the inverse-CDF draws are detached
-(helper.py:249) and rays are data."""
+(helper.py:249) and rays are data -- but for a FROZEN network whose ray tensors require grad: RenderVanillaInputs / RenderArticulatedInputs
+return the gradients of rays_o, rays_d and viewdirs (DESIGN.md sections 4.14, 4.15)."""
 from __future__ import annotations
 
 import torch
@@ -102,6 +103,39 @@ class RenderVanilla(torch.autograd.Function):
         _release(ctx, ws)
         _arena_done(ctx)
         return (None,) * 12 + tuple(g[name] for g in per_level for name in ops.VANILLA_PARAM_ORDER)
+
+
+class RenderVanillaInputs(torch.autograd.Function):
+    """NeRF.forward of a FROZEN network with gradients to its rays: rays_o, rays_d, viewdirs -- whichever of them
+    requires grad.  RenderVanilla's forward (arguments included) and released-workspace rule; the rays and the parameters, which the
+    backward reads again, are saved the autograd way (an in-place update in between raises).  The backward is aon_render_bwd_inputs: no
+    weight-gradient stage, the parameters get none.  t is data: nothing flows through the sampler, near / far or the inverse-CDF draws.  A
+    tensor passed both as rays_d and as viewdirs (the datasets' convention) receives the sum of the two slots from autograd."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, packs, opts, noise, *params):
+        ctx.white_bkgd, ctx.num_levels = white_bkgd, num_levels
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(rays_o, rays_d, viewdirs, *params)
+        levels, ws, ctx.geometry = ops.render_fwd_train(packs[0][0], packs[1][0] if num_levels == 2 else None, rays_o, rays_d, viewdirs, near, far,
+                                                        white_bkgd, num_levels, t_rand, u, opts=opts, noise=noise)
+        ctx.fused = (ws, [pk[1] for pk in packs], [pk[0] for pk in packs])
+        return tuple(x for lvl in levels for x in lvl)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        _check_not_released(ctx)
+        ws, packs_bwd, packs_fwd = ctx.fused
+        saved = ctx.saved_tensors   # (raises if a ray tensor or a parameter was modified in place since the forward)
+        rays_o, rays_d, viewdirs = saved[:3]
+        n_per = len(ops.VANILLA_PARAM_ORDER)
+        params = [saved[3 + l * n_per: 3 + (l + 1) * n_per] for l in range(ctx.num_levels)]
+        g_rays = ops.render_bwd_inputs(ws, packs_bwd, packs_fwd, rays_o, rays_d, viewdirs, ctx.white_bkgd, ctx.num_levels,
+                                       *_level_grads(gouts, ctx.num_levels, rays_d), params, geometry=ctx.geometry)
+        _release(ctx, ws)
+        need = ctx.needs_input_grad
+        ray = tuple(g.reshape(t.shape) if need[i] else None for i, (g, t) in enumerate(zip(g_rays, (rays_o, rays_d, viewdirs))))
+        return ray + (None,) * (9 + n_per * ctx.num_levels)
 
 
 class RenderLevelVanilla(torch.autograd.Function):

@@ -1,6 +1,7 @@
 // extern "C" surface, the training step in two calls: workspace carvers, the library's side streams, train_fwd_impl / train_bwd_impl for both
 // networks and the schedule switches.
 #include "aon_capi_util.h"
+#include "../../include/aon_hip_inputs.h"
 
 using namespace aon::capi;
 
@@ -665,6 +666,82 @@ int latent_bwd_impl(const char* who, const TrainNet* nets, const BwdCall& c, con
   return check(aon::launch_ray_grads(rl, num_levels, n_rays, g.deg_view, c.white_bkgd, c.rays_d, rg->viewdirs, rg->g_rays_o, rg->g_rays_d, rg->g_viewdirs, caller), who);
 }
 
+// ---- the ray gradients of a frozen vanilla network ----
+// What the compositing backward and the chain write, and the per-sample records: TrainScratch without its weight-gradient workspaces and
+// temporaries (no parameter gradient is computed, so none is remapped at other encoding degrees either).
+struct VanillaInputScratch {
+  float* d_raw[2]; float* dplanes[2]; float* rec[2];
+  int64_t bytes;
+};
+VanillaInputScratch carve_scratch_inputs_vanilla(char* base, int64_t n, int num_levels, const Geo& g) {
+  VanillaInputScratch sc{};
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { char* p = base + off; off += align_up(bytes, 256); return p; };
+  for (int l = 0; l < num_levels; ++l) {
+    const int64_t Np = level_np(n, l, g);
+    sc.d_raw[l] = reinterpret_cast<float*>(take(Np * 16));
+    sc.dplanes[l] = reinterpret_cast<float*>(take((int64_t)aon::kPlRows * Np * 4));
+  }
+  for (int l = 0; l < num_levels; ++l) sc.rec[l] = reinterpret_cast<float*>(take(aon::ray_grad_record_bytes(level_np(n, l, g))));
+  sc.bytes = off;
+  return sc;
+}
+
+// composite backward -> backward chain by the functions train_bwd_impl launches them with (same gradient planes), then the two launches of
+// launch_vanilla_ray_grads.  Everything on the caller's stream; no weight-gradient stage, no head reductions, no un-folding.
+int vanilla_inputs_bwd_impl(const char* who, const TrainNet* nets, const BwdCall& c, const BwdIo& io) {
+  auto bad = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
+  Geo g;
+  if (const char* b = make_geo(c.opts, g)) return fail(AON_E_INVALID, b);
+  const aon_ray_grads* rg = io.rg;
+  const char* rg_bad = !rg ? "null aon_ray_grads"
+                           : ((!rg->rays_o || !rg->viewdirs || !rg->g_rays_o || !rg->g_rays_d || !rg->g_viewdirs) ? "null member of aon_ray_grads" : nullptr);
+  if (int rc = bwd_call_check(who, c, false, rg_bad)) return rc;
+  const int64_t n_rays = c.n_rays;
+  const int num_levels = c.num_levels;
+  const hipStream_t caller = c.stream;
+  const float* const* const* params = io.params;
+  const TrainWs w = carve_train(static_cast<char*>(c.workspace), n_rays, false, num_levels, g);
+  if (w.bytes > c.workspace_bytes) return bad(AON_E_WORKSPACE, "workspace smaller than aon_train_workspace_bytes()");
+  const VanillaInputScratch sc = carve_scratch_inputs_vanilla(static_cast<char*>(c.scratch), n_rays, num_levels, g);
+  if (sc.bytes > c.scratch_bytes) return bad(AON_E_WORKSPACE, "scratch smaller than aon_train_scratch_bytes_inputs_vanilla()");
+  for (int l = 0; l < num_levels; ++l) {
+    const void* pb = nets[l].packed_bwd;
+    const void* pf = nets[l].packed_fwd;
+    if (!pb || !pf || !params[l] || !c.g_rgb[l]) return bad(AON_E_INVALID, "null level pointer");
+    if (aon::stream_form(pb) != aon::stream_form(pf) || aon::stream_form(pb) != aon::stream_form(nets[0].packed_bwd))
+      return bad(AON_E_INVALID, "forward and transposed streams were packed in different forms (aon_set_bottleneck_fold changed in between)");
+    for (int i : {0, 10, 16})   // the weights the encodings enter through
+      if (!params[l][i]) return bad(AON_E_INVALID, "null parameter pointer");
+  }
+  for (int l = 0; l < num_levels; ++l)
+    if (int rc = composite_bwd_stage(who, false, l, w.lvl[l], sc.d_raw[l], g, c, caller)) return rc;
+  auto chain_seg = [&](int l) {
+    return aon::ChainSeg{static_cast<const char*>(nets[l].packed_bwd),
+                         reinterpret_cast<const float*>(static_cast<const char*>(nets[l].packed_fwd) + aon::kStreamBytes), sc.d_raw[l], w.lvl[l].masks,
+                         nullptr, sc.dplanes[l], nullptr, w.lvl[l].Np};
+  };
+  if (num_levels == 2 && g_bwd_merge.load(std::memory_order_relaxed) != 0) {
+    const aon::ChainSeg segs[2] = {chain_seg(1), chain_seg(0)};
+    KTimer timer(kBwdChain, caller, w.lvl[0].Np + w.lvl[1].Np);
+    if (int rc = check(aon::launch_mlp_bwd_chain2(segs, 2, caller), who)) return rc;
+  } else {
+    for (int l = 0; l < num_levels; ++l) {
+      const aon::ChainSeg seg = chain_seg(l);
+      KTimer timer(kBwdChain, caller, w.lvl[l].Np);
+      if (int rc = check(aon::launch_mlp_bwd_chain2(&seg, 1, caller), who)) return rc;
+    }
+  }
+  aon::VanillaRayGradLevel rl[2];
+  for (int l = 0; l < num_levels; ++l) {
+    const TrainLevel& L = w.lvl[l];
+    rl[l] = aon::VanillaRayGradLevel{sc.dplanes[l], L.Np, params[l], sc.rec[l], L.t, L.raw, c.g_rgb[l], c.acc(l), c.depth(l), g.act(false, l, 0), L.S};
+  }
+  KTimer timer(kWgrad, caller, w.lvl[0].Np + (num_levels == 2 ? w.lvl[1].Np : 0));   // (the class of the stage it replaces)
+  return check(aon::launch_vanilla_ray_grads(rl, num_levels, n_rays, g.min_deg, g.max_deg - g.min_deg, g.deg_view, c.white_bkgd, rg->rays_o, c.rays_d,
+                                             rg->viewdirs, rg->g_rays_o, rg->g_rays_d, rg->g_viewdirs, caller), who);
+}
+
 }  // namespace
 
 int aon_set_bwd_overlap(int on) {
@@ -859,6 +936,26 @@ int aon_art_render_bwd_latents(const void* packed_bwd_coarse, const void* small_
   return aon_art_render_bwd_inputs(packed_bwd_coarse, small_coarse, packed_bwd_fine, small_fine, rays_d, n_rays, white_bkgd, num_levels, g_rgb_host,
                                    g_acc_host, g_depth_host, params_coarse_host, params_fine_host, g_shape, g_appearance, g_articulation, workspace,
                                    workspace_bytes, scratch, scratch_bytes, stream_, opts, nullptr);
+}
+
+// the ray gradients of a frozen vanilla network (declared in include/aon_hip_inputs.h)
+int64_t aon_train_scratch_bytes_inputs_vanilla(int64_t n_rays, int num_levels, const aon_render_opts* opts) {
+  Geo g;
+  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
+  return carve_scratch_inputs_vanilla(nullptr, n_rays < 1 ? 1 : n_rays, num_levels == 1 ? 1 : 2, g).bytes;
+}
+int aon_render_bwd_inputs(const void* packed_bwd_coarse, const void* packed_fwd_coarse, const void* packed_bwd_fine, const void* packed_fwd_fine,
+                          const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels, const float* const* g_rgb_host,
+                          const float* const* g_acc_host, const float* const* g_depth_host, const float* const* params_coarse_host,
+                          const float* const* params_fine_host, void* workspace, int64_t workspace_bytes, void* scratch, int64_t scratch_bytes,
+                          void* stream_, const aon_render_opts* opts, const aon_ray_grads* rg) {
+  const TrainNet nets[2] = {{packed_fwd_coarse, nullptr, packed_bwd_coarse}, {packed_fwd_fine, nullptr, packed_bwd_fine}};
+  BwdIo io{};
+  io.params[0] = params_coarse_host; io.params[1] = params_fine_host;
+  io.rg = rg;
+  return vanilla_inputs_bwd_impl("aon_render_bwd_inputs", nets,
+                                 bwd_call(rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, workspace, workspace_bytes, scratch,
+                                          scratch_bytes, stream_, opts), io);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 //   ray_grad_reduce_kernel   one wavefront per ray.  Lane c < 32 sums component c of the ray's records in fp64, sample after sample in
 //                            ascending order; lane 32 + c the same values times t_i.  Then the norm term (composite_bwd_kernel's two scans)
 //                            and the view encoding's backward; every output is rounded to fp32 once.
+//   vanilla_ray_grad_sample_kernel   the frozen VANILLA network's records for the same reduce kernel (described at the kernel).
 #include "aon_art_common.h"
 #include "aon_launch.h"
 
@@ -261,6 +262,163 @@ __global__ void __launch_bounds__(256) ray_grad_reduce_kernel(RgReduceArgs a) {
   }
 }
 
+// ---- the vanilla network ----
+// Position enters NeRFMLP twice -- the encoding is the input of pts_linears.0 and rides behind h into pts_linears.5 (model.py:95-103) --
+// and the chain leaves dZ0, dZ5 and dZ_v0 in the gradient planes for the weight-gradient stage.  Per sample, in row-vector notation:
+//   g_enc = dZ0 . W0 + dZ5 . W5[:, 256 : 256 + P]     (P = 3 + 6 (max_deg - min_deg) columns, each ONE fmaf chain from 0 over dZ0's 256
+//                                                      features in ascending order, then dZ5's 256 on the same accumulator)
+//   view partial = dZ_v0 . W_v0[:, 256 : 256 + V]     (one chain over 128 features, as ray_grad_sample_kernel's)
+//   g_x[a] = g_enc[a] + sum_l 2^l cos(arg) g_enc[..]  at the forward's rounded arguments, x = o + t d in cast_rays' bits; fp64 in ascending
+//                                                      column order, rounded once.
+// The weights are uniform across a wave: W0, then W5's slice, then W_v0's slice are staged through ONE 64 KiB LDS buffer from the network's
+// own nn.Linear storages (their own leading dimensions; columns beyond P / V are zero weights, so a chain there stays 0).  A lane carries
+// kVrgSpl samples, 256 apart: every 16-byte LDS read feeds 4 * kVrgSpl multiply-adds.
+constexpr int kVrgCols = 64;      // 63 position-encoding columns padded to whole float4s
+constexpr int kVrgSpl = 2;        // samples per lane (measured against 1: DESIGN.md section 4.15)
+constexpr int kVrgBlock = 256 * kVrgSpl;
+
+struct VrgSeg {
+  const float* dplanes;   // the level's gradient planes (chain output)
+  const float* W0;        // pts_linears.0.weight (256, P)
+  const float* W5;        // pts_linears.5.weight (256, 256 + P)
+  const float* Wv0;       // views_linear.0.weight (128, 256 + V)
+  const float* t;         // (n, S)
+  float* rec;             // (n * S, 32)
+  int64_t nvalid;         // n * S: padding samples are neither read nor written
+  int S, blk_begin;
+};
+struct VrgArgs {
+  VrgSeg seg[2];
+  const float* rays_o; const float* rays_d;
+  int nsegs, min_deg, Lp, V;
+};
+
+// w[f * LD + c] <- W[f * ld + col0 + c] for c < ncols, 0 beyond: `rows` features
+template <int LD>
+__device__ __forceinline__ void vrg_stage(float* w, const float* W, int rows, int ld, int col0, int ncols, int tid) {
+  for (int i = tid; i < rows * LD; i += 256) {
+    const int f = i / LD, c = i % LD;
+    w[i] = c < ncols ? W[(int64_t)f * ld + col0 + c] : 0.f;
+  }
+}
+
+// acc[s][c] <- fmaf(w[f][c], z_s[f], acc[s][c]) over the `units` * 4 features of a layer, ascending
+template <int NQ, int LD>
+__device__ __forceinline__ void vrg_accum(const float* w, const float* const (&pz)[kVrgSpl], int units, float (&acc)[kVrgSpl][kVrgCols]) {
+#pragma unroll 2
+  for (int u = 0; u < units; ++u) {
+    f32x4 z[kVrgSpl];
+#pragma unroll
+    for (int s = 0; s < kVrgSpl; ++s) z[s] = *reinterpret_cast<const f32x4*>(pz[s] + u * 128);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        const f32x4 wq = *reinterpret_cast<const f32x4*>(w + (4 * u + j) * LD + 4 * q);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+#pragma unroll
+          for (int s = 0; s < kVrgSpl; ++s) acc[s][4 * q + k] = __builtin_fmaf(wq[k], z[s][j], acc[s][4 * q + k]);
+        }
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) vanilla_ray_grad_sample_kernel(VrgArgs a) {
+  __shared__ __attribute__((aligned(16))) float w[256 * kVrgCols];
+  const int tid = (int)threadIdx.x;
+  const int si = (a.nsegs > 1 && (int)blockIdx.x >= a.seg[1].blk_begin) ? 1 : 0;
+  const VrgSeg& S = a.seg[si];
+  const int P = 3 + 6 * a.Lp;
+  int64_t n[kVrgSpl];
+  bool valid[kVrgSpl];
+  const float* base[kVrgSpl];
+#pragma unroll
+  for (int s = 0; s < kVrgSpl; ++s) {
+    n[s] = (int64_t)((int)blockIdx.x - S.blk_begin) * kVrgBlock + s * 256 + tid;
+    valid[s] = n[s] < S.nvalid;
+    const int64_t m = valid[s] ? n[s] : S.nvalid - 1;   // a lane without a sample follows the level's last one and stores nothing
+    // feature row f of sample m: ((m >> 5) * (rows / 4) + (f >> 2)) * 128 + (m & 31) * 4 + (f & 3)   (aon_mlp_core.h)
+    base[s] = S.dplanes + (m >> 5) * ((int64_t)kPlRows * 32) + (int)(m & 31) * 4;
+    n[s] = m;
+  }
+  float acc[kVrgSpl][kVrgCols];
+#pragma unroll
+  for (int s = 0; s < kVrgSpl; ++s) {
+#pragma unroll
+    for (int c = 0; c < kVrgCols; ++c) acc[s][c] = 0.f;
+  }
+  const float* pz[kVrgSpl];
+  vrg_stage<kVrgCols>(w, S.W0, 256, P, 0, P, tid);
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < kVrgSpl; ++s) pz[s] = base[s] + (plane_h(0) / 4) * 128;
+  vrg_accum<kVrgCols / 4, kVrgCols>(w, pz, 64, acc);
+  __syncthreads();
+  vrg_stage<kVrgCols>(w, S.W5, 256, 256 + P, 256, P, tid);
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < kVrgSpl; ++s) pz[s] = base[s] + (plane_h(5) / 4) * 128;
+  vrg_accum<kVrgCols / 4, kVrgCols>(w, pz, 64, acc);
+  __syncthreads();
+  vrg_stage<kWvCols>(w, S.Wv0, 128, 256 + a.V, 256, a.V, tid);
+  // the encoding, backwards: columns [x ; sin(2^l x) (level-major, xyz-minor) ; sin(2^l x + fp32(pi/2))] in ascending order
+  float gx[kVrgSpl][3];
+#pragma unroll
+  for (int s = 0; s < kVrgSpl; ++s) {
+    const int64_t ray = n[s] / S.S;
+    const float t = S.t[n[s]];
+    float x[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) x[k] = __fadd_rn(a.rays_o[ray * 3 + k], __fmul_rn(t, a.rays_d[ray * 3 + k]));
+    double g[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int ci = 0; ci < kPosEnc; ++ci) {
+      if (ci < P) {
+        int ax = ci;
+        double coef = 1.0;
+        if (ci >= 3) {
+          const int e = ci - 3, second = e >= 3 * a.Lp ? 1 : 0;
+          const int e2 = second ? e - 3 * a.Lp : e;
+          ax = e2 % 3;
+          const float scale = __builtin_ldexpf(1.0f, a.min_deg + e2 / 3);
+          const float xa = ax == 0 ? x[0] : (ax == 1 ? x[1] : x[2]);
+          const float arg = __fadd_rn(__fmul_rn(xa, scale), second ? AON_HALF_PI_F32 : 0.f);
+          coef = (double)scale * (double)cos_f32(arg);
+        }
+        const double term = coef * (double)acc[s][ci];
+        g[0] += ax == 0 ? term : 0.0;
+        g[1] += ax == 1 ? term : 0.0;
+        g[2] += ax == 2 ? term : 0.0;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gx[s][k] = (float)g[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < kVrgSpl; ++s) {
+#pragma unroll
+    for (int c = 0; c < kWvCols; ++c) acc[s][c] = 0.f;
+    pz[s] = base[s] + (kPlHV / 4) * 128;
+  }
+  vrg_accum<kWvCols / 4, kWvCols>(w, pz, 32, acc);
+#pragma unroll
+  for (int s = 0; s < kVrgSpl; ++s) {
+    if (!valid[s]) continue;
+    f32x4* dst = reinterpret_cast<f32x4*>(S.rec + n[s] * kRecFloats);
+    f32x4 v; v[0] = gx[s][0]; v[1] = gx[s][1]; v[2] = gx[s][2]; v[3] = acc[s][0];
+    dst[0] = v;
+#pragma unroll
+    for (int q = 1; q < kRecFloats / 4; ++q) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) v[k] = 4 * q + k - kRecView < 27 ? acc[s][4 * q + k - kRecView] : 0.f;
+      dst[q] = v;
+    }
+  }
+}
+
 }  // namespace
 
 int64_t ray_grad_record_bytes(int64_t n_samples) { return n_samples * kRecFloats * 4; }
@@ -288,6 +446,39 @@ hipError_t launch_ray_grads(const RayGradLevel* lv, int nlevels, int64_t n_rays,
     smax = L.S > smax ? L.S : smax;
   }
   ray_grad_sample_kernel<<<dim3((unsigned)blk), dim3(256), 0, stream>>>(A);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  const dim3 grid((unsigned)((n_rays + 3) / 4));
+  if (smax <= 256) ray_grad_reduce_kernel<4><<<grid, dim3(256), 0, stream>>>(R);
+  else ray_grad_reduce_kernel<8><<<grid, dim3(256), 0, stream>>>(R);
+  return hipGetLastError();
+}
+
+hipError_t launch_vanilla_ray_grads(const VanillaRayGradLevel* lv, int nlevels, int64_t n_rays, int min_deg, int pos_levels, int view_levels,
+                                    int white_bkgd, const float* rays_o, const float* rays_d, const float* viewdirs, float* g_rays_o,
+                                    float* g_rays_d, float* g_viewdirs, hipStream_t stream) {
+  if (nlevels < 1 || nlevels > 2 || n_rays <= 0 || view_levels < 0 || view_levels > 4 || pos_levels < 0 || pos_levels > 10 || min_deg < 0)
+    return hipErrorInvalidValue;
+  if (!rays_o || !rays_d || !viewdirs || !g_rays_o || !g_rays_d || !g_viewdirs) return hipErrorInvalidValue;
+  VrgArgs A{};
+  RgReduceArgs R{};
+  A.nsegs = nlevels; A.min_deg = min_deg; A.Lp = pos_levels; A.V = 3 + 6 * view_levels;
+  A.rays_o = rays_o; A.rays_d = rays_d;
+  R.nlevels = nlevels; R.white_bkgd = white_bkgd; R.Lv = view_levels; R.n_rays = n_rays;
+  R.rays_d = rays_d; R.viewdirs = viewdirs; R.g_o = g_rays_o; R.g_d = g_rays_d; R.g_v = g_viewdirs;
+  int64_t blk = 0;
+  int smax = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    const VanillaRayGradLevel& L = lv[l];
+    if (!L.dplanes || !L.params || !L.params[0] || !L.params[10] || !L.params[16] || !L.rec || !L.t || !L.raw || !L.g_rgb) return hipErrorInvalidValue;
+    const int64_t nvalid = n_rays * L.S;
+    if (L.S < 1 || L.S > 512 || nvalid > L.Np) return hipErrorInvalidValue;
+    A.seg[l] = VrgSeg{L.dplanes, L.params[0], L.params[10], L.params[16], L.t, L.rec, nvalid, L.S, (int)blk};
+    blk += (nvalid + kVrgBlock - 1) / kVrgBlock;
+    if (blk > 0x7fffffff) return hipErrorInvalidValue;
+    R.lvl[l] = RgReduceLevel{L.rec, L.t, L.raw, L.g_rgb, L.g_acc, L.g_depth, L.ap, L.S};
+    smax = L.S > smax ? L.S : smax;
+  }
+  vanilla_ray_grad_sample_kernel<<<dim3((unsigned)blk), dim3(256), 0, stream>>>(A);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   const dim3 grid((unsigned)((n_rays + 3) / 4));
   if (smax <= 256) ray_grad_reduce_kernel<4><<<grid, dim3(256), 0, stream>>>(R);

@@ -15,7 +15,7 @@ import torch.nn as nn
 import torch.nn.init as init
 
 from ... import ops
-from ...autograd import RenderGeneral, RenderLevelVanilla, RenderVanilla
+from ...autograd import RenderGeneral, RenderLevelVanilla, RenderVanilla, RenderVanillaInputs
 
 
 class NeRFMLP(nn.Module):
@@ -227,6 +227,16 @@ class NeRF(nn.Module):
             t_rand, u = None, None
         noise = self._draw_noise(noise, randomized, n, rays_o.device) if self.num_levels <= 2 else noise
         training = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        # a FROZEN network whose rays require grad (refining a camera pose, LitNeRF.fit_pose): the training forward and a backward that ends at
+        # rays_o, rays_d and viewdirs.  A parameter that trains, anywhere, keeps the path it took: its rays get none.
+        if torch.is_grad_enabled() and not training and any(getattr(rays[k], "requires_grad", False) for k in ("rays_o", "rays_d", "viewdirs")):
+            if self.num_levels > 2:
+                raise ValueError("ray gradients (a ray tensor requires grad on a frozen network) are served for one or two levels, not for "
+                                 f"num_levels={self.num_levels}")
+            if self._general or not self._fused_inference:
+                raise ValueError("ray gradients (a ray tensor requires grad on a frozen network) are served by the fused kernels only: this "
+                                 "network's geometry runs on the layer-wise engine")
+            return self._forward_ray_grads(rays, white_bkgd, near, far, t_rand, u, noise)
         if self.num_levels > 2:
             if self._general or not self.coarse_mlp.geometry.is_default:
                 raise NotImplementedError("num_levels > 2 is served for the default network geometry / encoding degrees only")
@@ -254,14 +264,7 @@ class NeRF(nn.Module):
             if n == 0:
                 raise ValueError("empty ray batch in training mode")
             mlps = [self.coarse_mlp, self.fine_mlp][: self.num_levels]
-            degs = [(m.min_deg_point, m.max_deg_point, m.deg_view) for m in mlps]
-            if len(mlps) == 2 and degs[0] == degs[1]:
-                # both networks' forward and transposed streams in ONE C call -- the eight fp64 fold products as one launch in front
-                # instead of four in a row with their pack kernels (aon_vanilla_pack_step; the same bytes in every buffer)
-                packs = ops.vanilla_pack_step(dict(mlps[0].named_parameters()), dict(mlps[1].named_parameters()), degrees=degs[0])
-            else:
-                bwd = [m.packed_bwd(True) for m in mlps]
-                packs = [(m.packed(True), b) for m, b in zip(mlps, bwd)]
+            packs = self._vanilla_packs(mlps)
             params = [p for m in mlps for p in m.ordered_params()]
             flat = RenderVanilla.apply(rays_o, rays["rays_d"], rays["viewdirs"], *[x.detach() if isinstance(x, torch.Tensor) else float(x) for x in (near, far)], bool(white_bkgd),
                                        self.num_levels, t_rand, u, packs, self._opts, noise, *params)
@@ -271,6 +274,26 @@ class NeRF(nn.Module):
         outs = ops.render_fwd(coarse, fine, rays_o, rays["rays_d"], rays["viewdirs"], near, far,
                               white_bkgd, self.num_levels, t_rand, u, opts=self._opts, noise=noise, ray_live=ray_live)
         return [tuple(o) for o in outs]
+
+    def _vanilla_packs(self, mlps):
+        """Per level (forward stream, transposed stream), freshly packed from the live parameters for one autograd graph."""
+        degs = [(m.min_deg_point, m.max_deg_point, m.deg_view) for m in mlps]
+        if len(mlps) == 2 and degs[0] == degs[1]:
+            # both networks' forward and transposed streams in ONE C call -- the eight fp64 fold products as one launch in front
+            # instead of four in a row with their pack kernels (aon_vanilla_pack_step; the same bytes in every buffer)
+            return ops.vanilla_pack_step(dict(mlps[0].named_parameters()), dict(mlps[1].named_parameters()), degrees=degs[0])
+        bwd = [m.packed_bwd(True) for m in mlps]
+        return [(m.packed(True), b) for m, b in zip(mlps, bwd)]
+
+    def _forward_ray_grads(self, rays, white_bkgd, near, far, t_rand, u, noise):
+        if rays["rays_o"].shape[0] == 0:
+            raise ValueError("empty ray batch under grad mode")
+        mlps = [self.coarse_mlp, self.fine_mlp][: self.num_levels]
+        params = [p for m in mlps for p in m.ordered_params()]
+        flat = RenderVanillaInputs.apply(rays["rays_o"], rays["rays_d"], rays["viewdirs"],
+                                         *[x.detach() if isinstance(x, torch.Tensor) else float(x) for x in (near, far)], bool(white_bkgd),
+                                         self.num_levels, t_rand, u, self._vanilla_packs(mlps), self._opts, noise, *params)
+        return [tuple(flat[3 * i: 3 * i + 3]) for i in range(self.num_levels)]
 
     def _forward_occupancy(self, rays, randomized, white_bkgd, near, far, u, occupancy, early_stop=None, ray_live=None):
         if randomized:
@@ -395,6 +418,77 @@ class LitNeRF(Harness):
         self.log("train/psnr0", stats[4])
         self.log("train/loss", stats[3])
         return loss
+
+    def fit_pose(self, batches, steps: int, lr: float = 5.0e-3, poses=None, seed: int = 0):
+        """Refine the camera pose of observed views of the scene with the network FROZEN (iNeRF): `steps` Adam steps
+        against training_step's loss (helper.train_loss), view `i % len(batches)` at step i.  LitNeRF_AutoDecoder.fit_pose without codes.
+
+        batches: one dict per VIEW with "directions" (camera-space ray directions, (N, 3) or (H, W, 3): ops.ray_directions, or a subset of
+        its pixels) and "target" (N, 3).  poses: the initial (3, 4) camera-to-world matrix of every view.  One 6-vector (omega, tau) is
+        kept per view and applied as R = exp([omega]x) R0, t = t0 + tau (ops.rays_from_pose).  seed: of the stratified / inverse-CDF draws
+        when the harness samples randomly.  -> (list of corrected (3, 4) poses, per-step losses as one (steps,) device tensor); no host
+        synchronisation per step.
+
+        The network's requires_grad flags are cleared for the duration and restored; with them cleared and the rays requiring grad,
+        NeRF.forward takes autograd.RenderVanillaInputs.  The views' 6-vectors, their gradients and Adam moments are one flat
+        (4, 6 * views) buffer stepped by aon_adam_step; a view's 6-vector keeps its own step count.  Scalar near / far only (a ray box's
+        per-ray limits would move with the pose and carry no gradient)."""
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise ValueError(f"fit_pose: steps must be a positive int, got {steps!r}")
+        batches = list(batches)
+        if not batches:
+            raise ValueError("fit_pose: no batches")
+        poses = [] if poses is None else list(poses)
+        if len(poses) != len(batches):
+            raise ValueError(f"fit_pose: one (3, 4) pose per view: {len(batches)} views, {len(poses)} poses")
+        if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not lr > 0:
+            raise ValueError(f"fit_pose: lr must be positive, got {lr!r}")
+        if self.ray_box is not None:
+            raise NotImplementedError("fit_pose: per-ray near / far from a ray box are not differentiated; use the scalar near / far")
+        for b in batches:
+            if "directions" not in b or "target" not in b:
+                raise ValueError("fit_pose: every batch needs 'directions' (camera-space) and 'target'")
+        dev = next(self.model.parameters()).device
+        pose0 = []
+        for c2w in poses:
+            c = torch.as_tensor(c2w, dtype=torch.float32).detach().to(dev)
+            if c.dim() != 2 or c.shape[0] < 3 or c.shape[1] != 4:
+                raise ValueError(f"fit_pose: a pose must be a (3, 4) matrix, got {tuple(c.shape)}")
+            pose0.append(c[:3].contiguous())
+        parena = torch.zeros((4, 6 * len(batches)), dtype=torch.float32, device=dev)   # rows: 6-vectors, gradients, exp_avg, exp_avg_sq
+        corr = [parena[0, 6 * v: 6 * v + 6].detach().requires_grad_(True) for v in range(len(batches))]
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        net_params = list(self.model.parameters())
+        flags = [p.requires_grad for p in net_params]
+        losses = torch.zeros(steps, dtype=torch.float32, device=dev)
+        try:
+            for p in net_params:
+                p.requires_grad_(False)
+            with torch.enable_grad():
+                for i in range(steps):
+                    v = i % len(batches)
+                    directions = batches[v]["directions"].to(device=dev, dtype=torch.float32)
+                    target = batches[v]["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
+                    rays_o, rays_d = ops.rays_from_pose(directions, pose0[v], corr[v])
+                    rays = {"rays_o": rays_o, "rays_d": rays_d, "viewdirs": rays_d}
+                    t_rand = u = None
+                    if self.randomized:
+                        n = rays_d.shape[0]
+                        t_rand = torch.rand((n, self.model.num_coarse_samples + 1), device=dev, generator=gen)
+                        u = torch.rand((n, self.model.num_fine_samples), device=dev, generator=gen) if self.model.num_levels == 2 else None
+                    rendered = self.model(rays, self.randomized, self.white_bkgd, self.near, self.far, t_rand=t_rand, u=u)
+                    loss, _ = helper.train_loss(rendered, target)
+                    grad, = torch.autograd.grad(loss, [corr[v]])
+                    parena[1, 6 * v: 6 * v + 6].copy_(grad)
+                    losses[i] = loss.detach()
+                    ops.adam_step(parena[0], parena[1], parena[2], parena[3], 6 * v, 6, float(lr), 0.9, 0.999, 1e-8, i // len(batches) + 1)
+        finally:
+            for p, f in zip(net_params, flags):
+                p.requires_grad_(f)
+        with torch.no_grad():
+            fitted = [ops.apply_pose_correction(pose0[v], parena[0, 6 * v: 6 * v + 6]) for v in range(len(batches))]
+        return fitted, losses
 
     @torch.no_grad()
     def render_rays(self, batch, batch_idx):

@@ -1219,6 +1219,38 @@ def render_bwd(ws, packs_bwd, packs_fwd, rays_d, white_bkgd, num_levels, g_rgb, 
     return grads
 
 
+def train_scratch_inputs_vanilla(device, n_rays: int, num_levels: int = 2, st=None) -> torch.Tensor:
+    """The temporaries of the frozen vanilla network's ray-gradient backward (d_raw, gradient planes, one 128-byte record per sample; no
+    weight-gradient workspace), pooled as `train_scratch`."""
+    return _pool_take(int(lib.aon_train_scratch_bytes_inputs_vanilla(n_rays, num_levels, None if st is None else C.byref(st))),
+                      "aon_train_scratch_bytes_inputs_vanilla", device)
+
+
+def _vanilla_input_param_array(params, _degrees):
+    """The 24-entry parameter array of aon_render_bwd_inputs from a dict (or an ordered sequence) of the level's parameters: the three
+    weights an encoding enters through, in their own nn.Linear layouts; the other entries stay NULL."""
+    if isinstance(params, dict):
+        params = [params.get(name) for name in VANILLA_PARAM_ORDER]
+    params = list(params)
+    keep = [_f32(params[i], VANILLA_PARAM_ORDER[i]) if i in (0, 10, 16) else None for i in range(len(VANILLA_PARAM_ORDER))]
+    return keep, _ptr_array(keep)
+
+
+def render_bwd_inputs(ws, packs_bwd, packs_fwd, rays_o, rays_d, viewdirs, white_bkgd, num_levels, g_rgb, g_acc, g_depth, params, geometry=None):
+    """loss.backward() through render_fwd_train of a FROZEN vanilla network, down to its rays -> (g_rays_o, g_rays_d, g_viewdirs), each
+    (n, 3), summed over the levels (aon_render_bwd_inputs).  `params`: per level, the network's parameters (a dict
+    by name, or the 24 tensors in VANILLA_PARAM_ORDER; only pts_linears.0.weight, pts_linears.5.weight and views_linear.0.weight are read).
+    t is data: no gradient through the sampler or near / far.  No parameter gradient is computed or written."""
+    ro, vd = _f32(rays_o, "rays_o"), _f32(viewdirs, "viewdirs")
+    bc = _BwdCall(rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, geometry, _vanilla_input_param_array, params)
+    pb, pf = bc.pad(packs_bwd), bc.pad(packs_fwd)
+    g_rays = tuple(torch.empty((bc.n, 3), dtype=torch.float32, device=bc.dev) for _ in range(3))
+    rg = _lib.RayGradsC(ro.data_ptr(), vd.data_ptr(), *(g.data_ptr() for g in g_rays))
+    bc.call("aon_render_bwd_inputs", (_pk(pb[0]), _pk(pf[0]), _pk(pb[1]), _pk(pf[1])), bc.parr, ws,
+            train_scratch_inputs_vanilla(bc.dev, bc.n, num_levels, bc.st), C.byref(rg))
+    return g_rays
+
+
 _LATENT_KEYS = (("density", 128), ("color", 128), ("articulation", 32))
 
 

@@ -75,22 +75,32 @@ def _release(ctx, ws):
     ops.pool_give(ws)
 
 
+def _ray_grads_out(ctx, g_rays, rays):
+    """The three ray gradients in their inputs' shapes, None for a ray tensor (the Function's first three inputs) that needs none"""
+    return tuple(g.reshape(t.shape) if ctx.needs_input_grad[i] else None for i, (g, t) in enumerate(zip(g_rays, rays)))
+
+
+def _vanilla_forward(ctx, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, packs, opts, noise):
+    """The forward of the two vanilla Functions: ONE C call (aon_render_fwd_train).  near / far: numbers, or per-ray tensors (DESIGN.md
+    section 4.11) -- data like the rays: non-differentiable inputs, no gradient returned.  packs: [(packed_fwd, packed_bwd)] per level;
+    the backward chain reads the forward stream for its head weights."""
+    ctx.white_bkgd, ctx.num_levels = white_bkgd, num_levels
+    ctx.set_materialize_grads(False)   # acc / depth carry no gradient in training: None, not four zero-filled tensors per step
+    levels, ws, ctx.geometry = ops.render_fwd_train(packs[0][0], packs[1][0] if num_levels == 2 else None, rays_o, rays_d, viewdirs, near, far,
+                                                    white_bkgd, num_levels, t_rand, u, opts=opts, noise=noise)
+    ctx.fused = (ws, [pk[1] for pk in packs], [pk[0] for pk in packs])
+    return tuple(x for lvl in levels for x in lvl)
+
+
 class RenderVanilla(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, packs, opts, noise, *params):
-        # near / far: numbers, or per-ray tensors -- data like the rays: non-differentiable inputs, no gradient returned.
-        # packs: [(packed_fwd, packed_bwd)] per level; params: 24 tensors per level in ops.VANILLA_PARAM_ORDER.  The whole
-        # forward is ONE C call (aon_render_fwd_train); the backward chain reads the forward stream for its head weights.
-        ctx.rays_d = rays_d
-        ctx.white_bkgd = white_bkgd
-        ctx.num_levels = num_levels
-        ctx.set_materialize_grads(False)   # acc / depth carry no gradient in training: None, not four zero-filled tensors per step
-        levels, ws, ctx.geometry = ops.render_fwd_train(packs[0][0], packs[1][0] if num_levels == 2 else None, rays_o, rays_d, viewdirs, near, far,
-                                                        white_bkgd, num_levels, t_rand, u, opts=opts, noise=noise)
-        ctx.fused = (ws, [pk[1] for pk in packs], [pk[0] for pk in packs])
+    def forward(ctx, *args):   # rays_o .. noise as _vanilla_forward, then params: 24 tensors per level in ops.VANILLA_PARAM_ORDER
+        params = args[12:]
+        ctx.rays_d = args[1]
+        out = _vanilla_forward(ctx, *args[:12])
         _arena_plan(ctx, params)
         ctx.param_shapes = [tuple(p.shape) for p in params]
-        return tuple(x for lvl in levels for x in lvl)
+        return out
 
     @staticmethod
     def backward(ctx, *gouts):
@@ -113,14 +123,9 @@ class RenderVanillaInputs(torch.autograd.Function):
     tensor passed both as rays_d and as viewdirs (the datasets' convention) receives the sum of the two slots from autograd."""
 
     @staticmethod
-    def forward(ctx, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, packs, opts, noise, *params):
-        ctx.white_bkgd, ctx.num_levels = white_bkgd, num_levels
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(rays_o, rays_d, viewdirs, *params)
-        levels, ws, ctx.geometry = ops.render_fwd_train(packs[0][0], packs[1][0] if num_levels == 2 else None, rays_o, rays_d, viewdirs, near, far,
-                                                        white_bkgd, num_levels, t_rand, u, opts=opts, noise=noise)
-        ctx.fused = (ws, [pk[1] for pk in packs], [pk[0] for pk in packs])
-        return tuple(x for lvl in levels for x in lvl)
+    def forward(ctx, *args):
+        ctx.save_for_backward(*args[:3], *args[12:])
+        return _vanilla_forward(ctx, *args[:12])
 
     @staticmethod
     def backward(ctx, *gouts):
@@ -133,9 +138,7 @@ class RenderVanillaInputs(torch.autograd.Function):
         g_rays = ops.render_bwd_inputs(ws, packs_bwd, packs_fwd, rays_o, rays_d, viewdirs, ctx.white_bkgd, ctx.num_levels,
                                        *_level_grads(gouts, ctx.num_levels, rays_d), params, geometry=ctx.geometry)
         _release(ctx, ws)
-        need = ctx.needs_input_grad
-        ray = tuple(g.reshape(t.shape) if need[i] else None for i, (g, t) in enumerate(zip(g_rays, (rays_o, rays_d, viewdirs))))
-        return ray + (None,) * (9 + n_per * ctx.num_levels)
+        return _ray_grads_out(ctx, g_rays, saved[:3]) + (None,) * (9 + n_per * ctx.num_levels)
 
 
 class RenderLevelVanilla(torch.autograd.Function):
@@ -225,7 +228,7 @@ def _art_saved(ctx, first):
     return saved, [dict(zip(ops.ART_PARAM_ORDER, saved[first + l * n_per: first + (l + 1) * n_per])) for l in range(ctx.num_levels)]
 
 
-_LATENT_KEYS = ("density", "color", "articulation")
+_LATENT_KEYS = tuple(k for k, _ in ops._LATENT_KEYS)
 
 
 class RenderArticulated(torch.autograd.Function):
@@ -296,7 +299,7 @@ class RenderArticulatedInputs(torch.autograd.Function):
                                                          *_level_grads(gouts, ctx.num_levels, rays_d), params, geometry=ctx.geometry,
                                                          want_latents=want_lat)
         _release(ctx, ws)
-        ray = tuple(g.reshape(t.shape) if need[i] else None for i, (g, t) in enumerate(zip((g_o, g_d, g_v), (rays_o, rays_d, viewdirs))))
+        ray = _ray_grads_out(ctx, (g_o, g_d, g_v), saved[:3])
         lat = (None, None, None)
         if want_lat:
             lat = tuple(g_lat[k].reshape(shp) if need[12 + i] else None for i, (k, shp) in enumerate(zip(_LATENT_KEYS, ctx.lat_shapes)))

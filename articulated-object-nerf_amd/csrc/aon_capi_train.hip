@@ -580,166 +580,114 @@ static int train_bwd_impl(const char* who, bool art, const TrainNet* nets, const
   return AON_OK;
 }
 
-// ---- the latent-only backward of a frozen articulated network ----
-// TrainScratch without its weight-gradient workspaces (96 MiB a level) and temporaries: what the compositing backward and the chain write, and
-// the partial sums of the four bias gradients a latent enters through.
-struct LatentScratch {
-  float* d_raw[2]; float* dplanes[2]; float* dxp[2]; float* ws[2];
-  float* rec[2];   // the ray gradients' per-sample records, behind everything the latent-only call carves
+// ---- the backwards of a frozen network: latent gradients [articulated] and ray gradients (DESIGN.md sections 4.13 - 4.15) ----
+// TrainScratch without its weight-gradient workspaces (96 MiB a level) and temporaries: what the compositing backward and the chain write,
+// [articulated] the partial sums of the four bias gradients a latent enters through, and behind all of that the ray gradients' per-sample records.
+struct FrozenScratch {
+  float* d_raw[2]; float* dplanes[2];
+  float* dxp[2]; float* ws[2];   // [articulated]
+  float* rec[2];                 // with ray_records
   int64_t bytes;
 };
-LatentScratch carve_scratch_latents(char* base, int64_t n, int num_levels, const Geo& g, bool ray_records = false) {
-  LatentScratch sc{};
+static FrozenScratch carve_scratch_frozen(char* base, int64_t n, bool art, int num_levels, const Geo& g, bool ray_records) {
+  FrozenScratch sc{};
   int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base + off; off += align_up(bytes, 256); return p; };
+  auto take = [&](int64_t bytes) { char* p = base + off; off += align_up(bytes, 256); return reinterpret_cast<float*>(p); };
   for (int l = 0; l < num_levels; ++l) {
     const int64_t Np = level_np(n, l, g);
-    sc.d_raw[l] = reinterpret_cast<float*>(take(Np * 16));
-    sc.dplanes[l] = reinterpret_cast<float*>(take((int64_t)aon::kAPlRows * Np * 4));
-    sc.dxp[l] = reinterpret_cast<float*>(take(Np * 16));
-    sc.ws[l] = reinterpret_cast<float*>(take(aon::art_latent_ws_bytes()));
+    sc.d_raw[l] = take(Np * 16);
+    sc.dplanes[l] = take((int64_t)(art ? aon::kAPlRows : aon::kPlRows) * Np * 4);
+    if (!art) continue;
+    sc.dxp[l] = take(Np * 16);
+    sc.ws[l] = take(aon::art_latent_ws_bytes());
   }
   if (ray_records)
-    for (int l = 0; l < num_levels; ++l) sc.rec[l] = reinterpret_cast<float*>(take(aon::ray_grad_record_bytes(level_np(n, l, g))));
+    for (int l = 0; l < num_levels; ++l) sc.rec[l] = take(aon::ray_grad_record_bytes(level_np(n, l, g)));
   sc.bytes = off;
   return sc;
 }
 
-// composite backward -> backward chain by the functions train_bwd_impl launches them with (same gradient planes), then the two launches of
-// aon_train_latent.hip.  Everything on the caller's stream.  io.rg: the ray gradients as well, or null.
-int latent_bwd_impl(const char* who, const TrainNet* nets, const BwdCall& c, const BwdIo& io) {
+// Shared by the two networks as train_bwd_impl is: composite backward -> backward chain by the functions train_bwd_impl launches them with
+// (same gradient planes), then [articulated] the two launches of aon_train_latent.hip and, with io.rg, the two of the ray gradients.
+// Everything on the caller's stream; no weight-gradient stage, no head reductions, no un-folding.
+//   io.rg: [articulated] optional -- without it the call IS the latent-only call; [vanilla] required
+static int frozen_bwd_impl(const char* who, bool art, const TrainNet* nets, const BwdCall& c, const BwdIo& io) {
   auto bad = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
   Geo g;
   if (const char* b = make_geo(c.opts, g)) return fail(AON_E_INVALID, b);
-  g.other_degrees = false;   // (the articulated kernels carry their degrees themselves)
+  if (art) g.other_degrees = false;   // (the articulated kernels carry their degrees themselves)
   const aon_ray_grads* rg = io.rg;
   float* const* g_latents = io.g_latents;
-  // [ray gradients, DESIGN.md section 4.14] rg: the three latent outputs may all be null (a pose fitted under fixed codes)
-  const bool want_latents = g_latents[0] || g_latents[1] || g_latents[2] || !rg;
-  const bool rg_null = rg && (!rg->rays_o || !rg->viewdirs || !rg->g_rays_o || !rg->g_rays_d || !rg->g_viewdirs);
-  if (int rc = bwd_call_check(who, c, want_latents && (!g_latents[0] || !g_latents[1] || !g_latents[2]), rg_null ? "null member of aon_ray_grads" : nullptr))
-    return rc;
+  // [articulated; ray gradients, DESIGN.md section 4.14] with rg the three latent outputs may all be null (a pose fitted under fixed codes)
+  const bool want_latents = art && (g_latents[0] || g_latents[1] || g_latents[2] || !rg);
+  const char* rg_bad = (!rg && !art) ? "null aon_ray_grads"
+                       : (rg && (!rg->rays_o || !rg->viewdirs || !rg->g_rays_o || !rg->g_rays_d || !rg->g_viewdirs)) ? "null member of aon_ray_grads" : nullptr;
+  if (int rc = bwd_call_check(who, c, want_latents && (!g_latents[0] || !g_latents[1] || !g_latents[2]), rg_bad)) return rc;
   const int64_t n_rays = c.n_rays;
   const int num_levels = c.num_levels;
   const hipStream_t caller = c.stream;
   const float* const* const* params = io.params;
-  const TrainWs w = carve_train(static_cast<char*>(c.workspace), n_rays, true, num_levels, g);
+  const TrainWs w = carve_train(static_cast<char*>(c.workspace), n_rays, art, num_levels, g);
   if (w.bytes > c.workspace_bytes) return bad(AON_E_WORKSPACE, "workspace smaller than aon_train_workspace_bytes()");
-  const LatentScratch sc = carve_scratch_latents(static_cast<char*>(c.scratch), n_rays, num_levels, g, rg != nullptr);
+  const FrozenScratch sc = carve_scratch_frozen(static_cast<char*>(c.scratch), n_rays, art, num_levels, g, rg != nullptr);
   if (sc.bytes > c.scratch_bytes)
-    return bad(AON_E_WORKSPACE, rg ? "scratch smaller than aon_train_scratch_bytes_inputs()" : "scratch smaller than aon_train_scratch_bytes_latents()");
+    return bad(AON_E_WORKSPACE, !art ? "scratch smaller than aon_train_scratch_bytes_inputs_vanilla()"
+                                : rg ? "scratch smaller than aon_train_scratch_bytes_inputs()" : "scratch smaller than aon_train_scratch_bytes_latents()");
   for (int l = 0; l < num_levels; ++l) {
+    // the transposed stream's form is checked against its mate's: [vanilla] the forward stream, [articulated] the per-call block
     const void* pb = nets[l].packed_bwd;
-    if (!pb || !nets[l].small || !params[l] || !c.g_rgb[l]) return bad(AON_E_INVALID, "null level pointer");
-    if (aon::stream_form(pb) != aon::stream_form(nets[l].small) || aon::stream_form(pb) != aon::stream_form(nets[0].packed_bwd))
-      return bad(AON_E_INVALID, "transposed stream and per-call block were made in different forms (aon_set_bottleneck_fold changed in between)");
-    for (int i : {0, 10, 20, 26})   // the weights a latent enters: all the W^T db products read (the ray gradients read 0 and 26)
-      if (!params[l][i]) return bad(AON_E_INVALID, "null parameter pointer");
+    const void* mate = art ? static_cast<const void*>(nets[l].small) : nets[l].packed_fwd;
+    if (!pb || !mate || !params[l] || !c.g_rgb[l]) return bad(AON_E_INVALID, "null level pointer");
+    if (aon::stream_form(pb) != aon::stream_form(mate) || aon::stream_form(pb) != aon::stream_form(nets[0].packed_bwd))
+      return bad(AON_E_INVALID, art ? "transposed stream and per-call block were made in different forms (aon_set_bottleneck_fold changed in between)"
+                                    : "forward and transposed streams were packed in different forms (aon_set_bottleneck_fold changed in between)");
+    // [articulated] the weights a latent enters: all the W^T db products read (the ray gradients read 0 and 26); [vanilla] the weights the
+    // encodings enter through
+    const int read[4] = {0, 10, art ? 20 : 16, 26};
+    for (int k = 0; k < (art ? 4 : 3); ++k)
+      if (!params[l][read[k]]) return bad(AON_E_INVALID, "null parameter pointer");
   }
   for (int l = 0; l < num_levels; ++l)
-    if (int rc = composite_bwd_stage(who, true, l, w.lvl[l], sc.d_raw[l], g, c, caller)) return rc;
-  auto chain_seg = [&](int l) { return art_chain_seg(nets[l], w.lvl[l], sc.d_raw[l], sc.dplanes[l], sc.dxp[l]); };
+    if (int rc = composite_bwd_stage(who, art, l, w.lvl[l], sc.d_raw[l], g, c, caller)) return rc;
+  // [vanilla] the small block sits behind the forward stream, no planes / dxp
+  auto chain_seg = [&](int l) {
+    const TrainLevel& L = w.lvl[l];
+    if (art) return art_chain_seg(nets[l], L, sc.d_raw[l], sc.dplanes[l], sc.dxp[l]);
+    return aon::ChainSeg{static_cast<const char*>(nets[l].packed_bwd),
+                         reinterpret_cast<const float*>(static_cast<const char*>(nets[l].packed_fwd) + aon::kStreamBytes), sc.d_raw[l], L.masks, nullptr,
+                         sc.dplanes[l], nullptr, L.Np};
+  };
+  auto chain = [&](const aon::ChainSeg* segs, int ns, int64_t units) {
+    KTimer timer(kBwdChain, caller, units);
+    return check(art ? aon::launch_art_bwd_chain2(segs, ns, caller) : aon::launch_mlp_bwd_chain2(segs, ns, caller), who);
+  };
+  // two levels merged into one chain launch of two segments (aon_set_bwd_merge, as train_bwd_impl), else one launch per level
   if (num_levels == 2 && g_bwd_merge.load(std::memory_order_relaxed) != 0) {
     const aon::ChainSeg segs[2] = {chain_seg(1), chain_seg(0)};
-    KTimer timer(kBwdChain, caller, w.lvl[0].Np + w.lvl[1].Np);
-    if (int rc = check(aon::launch_art_bwd_chain2(segs, 2, caller), who)) return rc;
+    if (int rc = chain(segs, 2, w.lvl[0].Np + w.lvl[1].Np)) return rc;
   } else {
     for (int l = 0; l < num_levels; ++l) {
       const aon::ChainSeg seg = chain_seg(l);
-      KTimer timer(kBwdChain, caller, w.lvl[l].Np);
-      if (int rc = check(aon::launch_art_bwd_chain2(&seg, 1, caller), who)) return rc;
+      if (int rc = chain(&seg, 1, w.lvl[l].Np)) return rc;
     }
   }
-  aon::ArtLatentLevel lv[2];
-  for (int l = 0; l < num_levels; ++l) lv[l] = aon::ArtLatentLevel{sc.dplanes[l], w.lvl[l].Np, nets[l].packed_bwd, params[l], sc.ws[l]};
-  KTimer timer(kWgrad, caller, w.lvl[0].Np + (num_levels == 2 ? w.lvl[1].Np : 0));   // (the class of the stage it replaces)
-  if (want_latents)
+  KTimer timer(kWgrad, caller, w.lvl[0].Np + (num_levels == 2 ? w.lvl[1].Np : 0));   // (the class of the stage these launches replace)
+  if (want_latents) {
+    aon::ArtLatentLevel lv[2];
+    for (int l = 0; l < num_levels; ++l) lv[l] = aon::ArtLatentLevel{sc.dplanes[l], w.lvl[l].Np, nets[l].packed_bwd, params[l], sc.ws[l]};
     if (int rc = check(aon::launch_art_latent_grads(lv, num_levels, g.max_deg - g.min_deg, g.deg_view, g_latents[0], g_latents[1], g_latents[2], caller), who))
       return rc;
+  }
   if (!rg) return AON_OK;
-  // the ray gradients read what the chain left (gradient planes, dxp) and the forward's t / raw: two launches behind the latent ones
+  // the ray gradients read what the chain left (gradient planes, [articulated] dxp) and the forward's t / raw: two launches, both levels in each
   aon::RayGradLevel rl[2];
   for (int l = 0; l < num_levels; ++l) {
     const TrainLevel& L = w.lvl[l];
-    rl[l] = aon::RayGradLevel{sc.dplanes[l], sc.dxp[l], L.Np, params[l], sc.rec[l], L.t, L.raw, c.g_rgb[l], c.acc(l), c.depth(l), g.act(true, l, 0), L.S};
+    rl[l] = aon::RayGradLevel{sc.dplanes[l], sc.dxp[l], L.Np, params[l], sc.rec[l], L.t, L.raw, c.g_rgb[l], c.acc(l), c.depth(l), g.act(art, l, 0), L.S};
   }
-  return check(aon::launch_ray_grads(rl, num_levels, n_rays, g.deg_view, c.white_bkgd, c.rays_d, rg->viewdirs, rg->g_rays_o, rg->g_rays_d, rg->g_viewdirs, caller), who);
-}
-
-// ---- the ray gradients of a frozen vanilla network ----
-// What the compositing backward and the chain write, and the per-sample records: TrainScratch without its weight-gradient workspaces and
-// temporaries (no parameter gradient is computed, so none is remapped at other encoding degrees either).
-struct VanillaInputScratch {
-  float* d_raw[2]; float* dplanes[2]; float* rec[2];
-  int64_t bytes;
-};
-VanillaInputScratch carve_scratch_inputs_vanilla(char* base, int64_t n, int num_levels, const Geo& g) {
-  VanillaInputScratch sc{};
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { char* p = base + off; off += align_up(bytes, 256); return p; };
-  for (int l = 0; l < num_levels; ++l) {
-    const int64_t Np = level_np(n, l, g);
-    sc.d_raw[l] = reinterpret_cast<float*>(take(Np * 16));
-    sc.dplanes[l] = reinterpret_cast<float*>(take((int64_t)aon::kPlRows * Np * 4));
-  }
-  for (int l = 0; l < num_levels; ++l) sc.rec[l] = reinterpret_cast<float*>(take(aon::ray_grad_record_bytes(level_np(n, l, g))));
-  sc.bytes = off;
-  return sc;
-}
-
-// composite backward -> backward chain by the functions train_bwd_impl launches them with (same gradient planes), then the two launches of
-// launch_vanilla_ray_grads.  Everything on the caller's stream; no weight-gradient stage, no head reductions, no un-folding.
-int vanilla_inputs_bwd_impl(const char* who, const TrainNet* nets, const BwdCall& c, const BwdIo& io) {
-  auto bad = [&](int code, const char* what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
-  Geo g;
-  if (const char* b = make_geo(c.opts, g)) return fail(AON_E_INVALID, b);
-  const aon_ray_grads* rg = io.rg;
-  const char* rg_bad = !rg ? "null aon_ray_grads"
-                           : ((!rg->rays_o || !rg->viewdirs || !rg->g_rays_o || !rg->g_rays_d || !rg->g_viewdirs) ? "null member of aon_ray_grads" : nullptr);
-  if (int rc = bwd_call_check(who, c, false, rg_bad)) return rc;
-  const int64_t n_rays = c.n_rays;
-  const int num_levels = c.num_levels;
-  const hipStream_t caller = c.stream;
-  const float* const* const* params = io.params;
-  const TrainWs w = carve_train(static_cast<char*>(c.workspace), n_rays, false, num_levels, g);
-  if (w.bytes > c.workspace_bytes) return bad(AON_E_WORKSPACE, "workspace smaller than aon_train_workspace_bytes()");
-  const VanillaInputScratch sc = carve_scratch_inputs_vanilla(static_cast<char*>(c.scratch), n_rays, num_levels, g);
-  if (sc.bytes > c.scratch_bytes) return bad(AON_E_WORKSPACE, "scratch smaller than aon_train_scratch_bytes_inputs_vanilla()");
-  for (int l = 0; l < num_levels; ++l) {
-    const void* pb = nets[l].packed_bwd;
-    const void* pf = nets[l].packed_fwd;
-    if (!pb || !pf || !params[l] || !c.g_rgb[l]) return bad(AON_E_INVALID, "null level pointer");
-    if (aon::stream_form(pb) != aon::stream_form(pf) || aon::stream_form(pb) != aon::stream_form(nets[0].packed_bwd))
-      return bad(AON_E_INVALID, "forward and transposed streams were packed in different forms (aon_set_bottleneck_fold changed in between)");
-    for (int i : {0, 10, 16})   // the weights the encodings enter through
-      if (!params[l][i]) return bad(AON_E_INVALID, "null parameter pointer");
-  }
-  for (int l = 0; l < num_levels; ++l)
-    if (int rc = composite_bwd_stage(who, false, l, w.lvl[l], sc.d_raw[l], g, c, caller)) return rc;
-  auto chain_seg = [&](int l) {
-    return aon::ChainSeg{static_cast<const char*>(nets[l].packed_bwd),
-                         reinterpret_cast<const float*>(static_cast<const char*>(nets[l].packed_fwd) + aon::kStreamBytes), sc.d_raw[l], w.lvl[l].masks,
-                         nullptr, sc.dplanes[l], nullptr, w.lvl[l].Np};
-  };
-  if (num_levels == 2 && g_bwd_merge.load(std::memory_order_relaxed) != 0) {
-    const aon::ChainSeg segs[2] = {chain_seg(1), chain_seg(0)};
-    KTimer timer(kBwdChain, caller, w.lvl[0].Np + w.lvl[1].Np);
-    if (int rc = check(aon::launch_mlp_bwd_chain2(segs, 2, caller), who)) return rc;
-  } else {
-    for (int l = 0; l < num_levels; ++l) {
-      const aon::ChainSeg seg = chain_seg(l);
-      KTimer timer(kBwdChain, caller, w.lvl[l].Np);
-      if (int rc = check(aon::launch_mlp_bwd_chain2(&seg, 1, caller), who)) return rc;
-    }
-  }
-  aon::VanillaRayGradLevel rl[2];
-  for (int l = 0; l < num_levels; ++l) {
-    const TrainLevel& L = w.lvl[l];
-    rl[l] = aon::VanillaRayGradLevel{sc.dplanes[l], L.Np, params[l], sc.rec[l], L.t, L.raw, c.g_rgb[l], c.acc(l), c.depth(l), g.act(false, l, 0), L.S};
-  }
-  KTimer timer(kWgrad, caller, w.lvl[0].Np + (num_levels == 2 ? w.lvl[1].Np : 0));   // (the class of the stage it replaces)
-  return check(aon::launch_vanilla_ray_grads(rl, num_levels, n_rays, g.min_deg, g.max_deg - g.min_deg, g.deg_view, c.white_bkgd, rg->rays_o, c.rays_d,
-                                             rg->viewdirs, rg->g_rays_o, rg->g_rays_d, rg->g_viewdirs, caller), who);
+  return check(art ? aon::launch_ray_grads(rl, num_levels, n_rays, g.deg_view, c.white_bkgd, c.rays_d, rg->viewdirs, rg->g_rays_o, rg->g_rays_d, rg->g_viewdirs, caller)
+                   : aon::launch_vanilla_ray_grads(rl, num_levels, n_rays, g.min_deg, g.max_deg - g.min_deg, g.deg_view, c.white_bkgd, rg->rays_o, c.rays_d,
+                                                   rg->viewdirs, rg->g_rays_o, rg->g_rays_d, rg->g_viewdirs, caller), who);
 }
 
 }  // namespace
@@ -779,7 +727,7 @@ static int64_t train_bytes_query(TrainBytes what, int64_t n_rays, int articulate
   switch (what) {
     case kWorkspaceBytes: return carve_train(nullptr, n_rays, articulated != 0, levels, g).bytes;
     case kScratchBytes: return carve_scratch(nullptr, n_rays, articulated != 0, levels, g).bytes;
-    default: return carve_scratch_latents(nullptr, n_rays, levels, g, what == kInputScratchBytes).bytes;
+    default: return carve_scratch_frozen(nullptr, n_rays, articulated != 0, levels, g, what == kInputScratchBytes).bytes;
   }
 }
 int64_t aon_train_workspace_bytes_ex(int64_t n_rays, int articulated, int num_levels, const aon_render_opts* opts) {
@@ -923,7 +871,7 @@ int aon_art_render_bwd_inputs(const void* packed_bwd_coarse, const void* small_c
                               const aon_render_opts* opts, const aon_ray_grads* rg) {
   ArtBwd a = art_bwd(packed_bwd_coarse, small_coarse, packed_bwd_fine, small_fine, params_coarse_host, params_fine_host, g_shape, g_appearance, g_articulation);
   a.io.rg = rg;
-  return latent_bwd_impl(rg ? "aon_art_render_bwd_inputs" : "aon_art_render_bwd_latents", a.nets,
+  return frozen_bwd_impl(rg ? "aon_art_render_bwd_inputs" : "aon_art_render_bwd_latents", true, a.nets,
                          bwd_call(rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, workspace, workspace_bytes, scratch,
                                   scratch_bytes, stream_, opts), a.io);
 }
@@ -940,9 +888,7 @@ int aon_art_render_bwd_latents(const void* packed_bwd_coarse, const void* small_
 
 // the ray gradients of a frozen vanilla network (declared in include/aon_hip_inputs.h)
 int64_t aon_train_scratch_bytes_inputs_vanilla(int64_t n_rays, int num_levels, const aon_render_opts* opts) {
-  Geo g;
-  if (const char* bad = make_geo(opts, g)) return fail(AON_E_INVALID, bad);
-  return carve_scratch_inputs_vanilla(nullptr, n_rays < 1 ? 1 : n_rays, num_levels == 1 ? 1 : 2, g).bytes;
+  return train_bytes_query(kInputScratchBytes, n_rays, 0, num_levels, opts);
 }
 int aon_render_bwd_inputs(const void* packed_bwd_coarse, const void* packed_fwd_coarse, const void* packed_bwd_fine, const void* packed_fwd_fine,
                           const float* rays_d, int64_t n_rays, int white_bkgd, int num_levels, const float* const* g_rgb_host,
@@ -953,8 +899,8 @@ int aon_render_bwd_inputs(const void* packed_bwd_coarse, const void* packed_fwd_
   BwdIo io{};
   io.params[0] = params_coarse_host; io.params[1] = params_fine_host;
   io.rg = rg;
-  return vanilla_inputs_bwd_impl("aon_render_bwd_inputs", nets,
-                                 bwd_call(rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, workspace, workspace_bytes, scratch,
+  return frozen_bwd_impl("aon_render_bwd_inputs", false, nets,
+                         bwd_call(rays_d, n_rays, white_bkgd, num_levels, g_rgb_host, g_acc_host, g_depth_host, workspace, workspace_bytes, scratch,
                                           scratch_bytes, stream_, opts), io);
 }
 

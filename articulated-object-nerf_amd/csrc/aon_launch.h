@@ -134,12 +134,14 @@ int64_t art_latent_ws_bytes();
 hipError_t launch_art_latent_grads(const ArtLatentLevel* levels, int nlevels, int pos_levels, int view_levels, float* g_shape, float* g_app, float* g_art,
                                    hipStream_t stream);
 
-// ---- aon_ray_grad.hip: dL/d rays_o, rays_d, viewdirs of a frozen articulated network from the chain's outputs ----
+// ---- aon_ray_grad.hip: dL/d rays_o, rays_d, viewdirs of a frozen network from the chain's outputs (DESIGN.md sections 4.14, 4.15) ----
 struct RayGradLevel {
   const float* dplanes;          // the level's gradient planes, written by the backward chain
-  const float* dxp;              // (Np,4): d x' per sample, written by the same launch
+  const float* dxp;              // [articulated] (Np,4): d x' per sample, written by the same launch; [vanilla] null: x is rebuilt from rays_o, rays_d and t
   int64_t Np;
-  const float* const* params;    // the level's 40 parameters; read: [0] deformations_linear.0.weight, [26] views_linear.0.weight
+  // the level's parameters; read: [articulated, 40] [0] deformations_linear.0.weight, [26] views_linear.0.weight;
+  // [vanilla, 24] [0] pts_linears.0.weight, [10] pts_linears.5.weight, [16] views_linear.0.weight
+  const float* const* params;
   float* rec;                    // ray_grad_record_bytes(n_rays * S) of per-sample records
   const float* t;                // (n_rays, S)
   const float* raw;              // (n_rays * S, 4), as the forward wrote it
@@ -150,20 +152,7 @@ struct RayGradLevel {
 int64_t ray_grad_record_bytes(int64_t n_samples);
 hipError_t launch_ray_grads(const RayGradLevel* levels, int nlevels, int64_t n_rays, int view_levels, int white_bkgd, const float* rays_d,
                             const float* viewdirs, float* g_rays_o, float* g_rays_d, float* g_viewdirs, hipStream_t stream);
-
-// the vanilla network's: from the gradient planes alone -- x is rebuilt from rays_o, rays_d and t
-struct VanillaRayGradLevel {
-  const float* dplanes;          // the level's gradient planes, written by the backward chain
-  int64_t Np;
-  const float* const* params;    // the level's 24 parameters; read: [0] pts_linears.0.weight, [10] pts_linears.5.weight, [16] views_linear.0.weight
-  float* rec;                    // ray_grad_record_bytes(n_rays * S) of per-sample records
-  const float* t;                // (n_rays, S)
-  const float* raw;              // (n_rays * S, 4), as the forward wrote it
-  const float* g_rgb; const float* g_acc; const float* g_depth;   // upstream gradients of the level (g_acc / g_depth: or null)
-  ActParams ap;
-  int S;
-};
-hipError_t launch_vanilla_ray_grads(const VanillaRayGradLevel* levels, int nlevels, int64_t n_rays, int min_deg, int pos_levels, int view_levels,
+hipError_t launch_vanilla_ray_grads(const RayGradLevel* levels, int nlevels, int64_t n_rays, int min_deg, int pos_levels, int view_levels,
                                     int white_bkgd, const float* rays_o, const float* rays_d, const float* viewdirs, float* g_rays_o,
                                     float* g_rays_d, float* g_viewdirs, hipStream_t stream);
 

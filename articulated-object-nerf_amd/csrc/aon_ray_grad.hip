@@ -423,17 +423,31 @@ __global__ void __launch_bounds__(256) vanilla_ray_grad_sample_kernel(VrgArgs a)
 
 int64_t ray_grad_record_bytes(int64_t n_samples) { return n_samples * kRecFloats * 4; }
 
+// the reduce launch both networks share: the levels' records, one wavefront per ray (4 or 8 samples a lane by the longer level)
+static hipError_t launch_reduce(const RayGradLevel* lv, int nlevels, int64_t n_rays, int view_levels, int white_bkgd, const float* rays_d,
+                                const float* viewdirs, float* g_rays_o, float* g_rays_d, float* g_viewdirs, hipStream_t stream) {
+  RgReduceArgs R{};
+  R.nlevels = nlevels; R.white_bkgd = white_bkgd; R.Lv = view_levels; R.n_rays = n_rays;
+  R.rays_d = rays_d; R.viewdirs = viewdirs; R.g_o = g_rays_o; R.g_d = g_rays_d; R.g_v = g_viewdirs;
+  int smax = 0;
+  for (int l = 0; l < nlevels; ++l) {
+    const RayGradLevel& L = lv[l];
+    R.lvl[l] = RgReduceLevel{L.rec, L.t, L.raw, L.g_rgb, L.g_acc, L.g_depth, L.ap, L.S};
+    smax = L.S > smax ? L.S : smax;
+  }
+  const dim3 grid((unsigned)((n_rays + 3) / 4));
+  if (smax <= 256) ray_grad_reduce_kernel<4><<<grid, dim3(256), 0, stream>>>(R);
+  else ray_grad_reduce_kernel<8><<<grid, dim3(256), 0, stream>>>(R);
+  return hipGetLastError();
+}
+
 hipError_t launch_ray_grads(const RayGradLevel* lv, int nlevels, int64_t n_rays, int view_levels, int white_bkgd, const float* rays_d,
                             const float* viewdirs, float* g_rays_o, float* g_rays_d, float* g_viewdirs, hipStream_t stream) {
   if (nlevels < 1 || nlevels > 2 || n_rays <= 0 || view_levels < 0 || view_levels > 4) return hipErrorInvalidValue;
   if (!rays_d || !viewdirs || !g_rays_o || !g_rays_d || !g_viewdirs) return hipErrorInvalidValue;
   RgSampleArgs A{};
-  RgReduceArgs R{};
   A.nsegs = nlevels; A.V = 3 + 6 * view_levels;
-  R.nlevels = nlevels; R.white_bkgd = white_bkgd; R.Lv = view_levels; R.n_rays = n_rays;
-  R.rays_d = rays_d; R.viewdirs = viewdirs; R.g_o = g_rays_o; R.g_d = g_rays_d; R.g_v = g_viewdirs;
   int64_t blk = 0;
-  int smax = 0;
   for (int l = 0; l < nlevels; ++l) {
     const RayGradLevel& L = lv[l];
     if (!L.dplanes || !L.dxp || !L.params || !L.params[0] || !L.params[26] || !L.rec || !L.t || !L.raw || !L.g_rgb) return hipErrorInvalidValue;
@@ -442,48 +456,34 @@ hipError_t launch_ray_grads(const RayGradLevel* lv, int nlevels, int64_t n_rays,
     A.seg[l] = RgSampleSeg{L.dplanes, L.dxp, L.params[0], L.params[26], L.rec, nvalid, (int)blk};
     blk += (nvalid + 255) / 256;
     if (blk > 0x7fffffff) return hipErrorInvalidValue;
-    R.lvl[l] = RgReduceLevel{L.rec, L.t, L.raw, L.g_rgb, L.g_acc, L.g_depth, L.ap, L.S};
-    smax = L.S > smax ? L.S : smax;
   }
   ray_grad_sample_kernel<<<dim3((unsigned)blk), dim3(256), 0, stream>>>(A);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  const dim3 grid((unsigned)((n_rays + 3) / 4));
-  if (smax <= 256) ray_grad_reduce_kernel<4><<<grid, dim3(256), 0, stream>>>(R);
-  else ray_grad_reduce_kernel<8><<<grid, dim3(256), 0, stream>>>(R);
-  return hipGetLastError();
+  return launch_reduce(lv, nlevels, n_rays, view_levels, white_bkgd, rays_d, viewdirs, g_rays_o, g_rays_d, g_viewdirs, stream);
 }
 
-hipError_t launch_vanilla_ray_grads(const VanillaRayGradLevel* lv, int nlevels, int64_t n_rays, int min_deg, int pos_levels, int view_levels,
+hipError_t launch_vanilla_ray_grads(const RayGradLevel* lv, int nlevels, int64_t n_rays, int min_deg, int pos_levels, int view_levels,
                                     int white_bkgd, const float* rays_o, const float* rays_d, const float* viewdirs, float* g_rays_o,
                                     float* g_rays_d, float* g_viewdirs, hipStream_t stream) {
   if (nlevels < 1 || nlevels > 2 || n_rays <= 0 || view_levels < 0 || view_levels > 4 || pos_levels < 0 || pos_levels > 10 || min_deg < 0)
     return hipErrorInvalidValue;
   if (!rays_o || !rays_d || !viewdirs || !g_rays_o || !g_rays_d || !g_viewdirs) return hipErrorInvalidValue;
   VrgArgs A{};
-  RgReduceArgs R{};
   A.nsegs = nlevels; A.min_deg = min_deg; A.Lp = pos_levels; A.V = 3 + 6 * view_levels;
   A.rays_o = rays_o; A.rays_d = rays_d;
-  R.nlevels = nlevels; R.white_bkgd = white_bkgd; R.Lv = view_levels; R.n_rays = n_rays;
-  R.rays_d = rays_d; R.viewdirs = viewdirs; R.g_o = g_rays_o; R.g_d = g_rays_d; R.g_v = g_viewdirs;
   int64_t blk = 0;
-  int smax = 0;
   for (int l = 0; l < nlevels; ++l) {
-    const VanillaRayGradLevel& L = lv[l];
+    const RayGradLevel& L = lv[l];
     if (!L.dplanes || !L.params || !L.params[0] || !L.params[10] || !L.params[16] || !L.rec || !L.t || !L.raw || !L.g_rgb) return hipErrorInvalidValue;
     const int64_t nvalid = n_rays * L.S;
     if (L.S < 1 || L.S > 512 || nvalid > L.Np) return hipErrorInvalidValue;
     A.seg[l] = VrgSeg{L.dplanes, L.params[0], L.params[10], L.params[16], L.t, L.rec, nvalid, L.S, (int)blk};
     blk += (nvalid + kVrgBlock - 1) / kVrgBlock;
     if (blk > 0x7fffffff) return hipErrorInvalidValue;
-    R.lvl[l] = RgReduceLevel{L.rec, L.t, L.raw, L.g_rgb, L.g_acc, L.g_depth, L.ap, L.S};
-    smax = L.S > smax ? L.S : smax;
   }
   vanilla_ray_grad_sample_kernel<<<dim3((unsigned)blk), dim3(256), 0, stream>>>(A);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  const dim3 grid((unsigned)((n_rays + 3) / 4));
-  if (smax <= 256) ray_grad_reduce_kernel<4><<<grid, dim3(256), 0, stream>>>(R);
-  else ray_grad_reduce_kernel<8><<<grid, dim3(256), 0, stream>>>(R);
-  return hipGetLastError();
+  return launch_reduce(lv, nlevels, n_rays, view_levels, white_bkgd, rays_d, viewdirs, g_rays_o, g_rays_d, g_viewdirs, stream);
 }
 
 }  // namespace aon

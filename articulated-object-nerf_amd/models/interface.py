@@ -8,6 +8,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .. import ops
+
 
 class LitModel(torch.nn.Module):
     def mse(self, image_pred, image_gt, valid_mask=None, reduction="mean"):
@@ -136,6 +138,27 @@ for _name in ("__getitem__", "__iter__", "__len__", "__repr__", "__eq__", "__ne_
     setattr(_LogSeries, _name, _settled(_name))
 
 
+def _code_arena(codes: dict, dev, requires_grad: bool):
+    """The three codes in one flat (4, 288) buffer -- rows: codes, gradients, exp_avg, exp_avg_sq -- and one (1, dim) leaf per code on
+    row 0's storage."""
+    arena = torch.zeros((4, sum(d for _, d in ops._LATENT_KEYS)), dtype=torch.float32, device=dev)
+    leaves, off = {}, 0
+    for k, d in ops._LATENT_KEYS:
+        view = arena[0, off: off + d].view(1, d)
+        view.copy_(codes[k])
+        leaves[k] = view.detach().requires_grad_(bool(requires_grad))
+        off += d
+    return arena, leaves
+
+
+def _arena_codes(arena) -> dict:
+    out, off = {}, 0
+    for k, d in ops._LATENT_KEYS:
+        out[k] = arena[0, off: off + d].view(1, d).clone()
+        off += d
+    return out
+
+
 class Harness(LitModel):
     """What the two LightningModules of the reference share once Lightning is removed: the ``self.log`` sink, the
     learning-rate rule of ``optimizer_step`` (model.py:391-419 == model_autodecoder.py:607-636) and the PSNR / SSIM part
@@ -144,7 +167,7 @@ class Harness(LitModel):
 
     lr_init, lr_final, lr_delay_steps, lr_delay_mult = 5.0e-4, 5.0e-6, 2500, 0.01
 
-    def _init_harness(self, hparams, defaults):
+    def _init_harness(self, hparams, defaults, lr_init, lr_final, lr_delay_steps, lr_delay_mult, randomized, near, far, white_bkgd, ray_box):
         from collections import defaultdict
         from types import SimpleNamespace
 
@@ -153,6 +176,11 @@ class Harness(LitModel):
         self.hparams = SimpleNamespace(**hp)
         self.logged = defaultdict(_LogSeries)
         self.global_step = 0
+        self.lr_init, self.lr_final, self.lr_delay_steps, self.lr_delay_mult = lr_init, lr_final, lr_delay_steps, lr_delay_mult
+        self.randomized, self.near, self.far, self.white_bkgd = randomized, near, far, white_bkgd
+        # ray_box (a side length, or (lo, hi)): per-ray near / far from the rays' intersection with that box (helper.get_ray_limits, the
+        # reference's near_obj / far_obj) instead of the scalars; None: the scalars, as before
+        self.ray_box = ray_box
 
     def log(self, name, value, **_):
         self.logged[name].append(value)
@@ -187,6 +215,110 @@ class Harness(LitModel):
         allreduce_gradients(self, find_unused_parameters=find_unused_parameters)
         self.optimizer_step(optimizer)
         return loss.detach()
+
+    _CHUNK_SKIP = ()   # batch keys that are never rays (a harness's scalar keys)
+
+    def _render_chunks(self, batch, *model_args, skip=(), whole=()):
+        """The model on `batch`, hparams.chunk rays at a time, without randomness -> the fine level's comp_rgb, acc, depth over all rays.
+        model_args: behind near / far (the latents); skip: batch keys left out; whole: keys handed to every chunk unsliced.  A ray box's
+        limits are those of the whole image -- the fallback for rays that miss the box is a property of the ray set -- sliced per chunk."""
+        step = self.hparams.chunk
+        limits = ops.ray_limits(batch["rays_o"], batch["rays_d"], self.ray_box) if self.ray_box is not None else None
+        outs = []
+        for i in range(0, batch["rays_o"].shape[0], step):
+            chunk = {k: (v if k in whole else v[i: i + step]) for k, v in batch.items() if k not in skip and k not in self._CHUNK_SKIP}
+            if limits is not None:
+                near, far, live = (x[i: i + step] for x in limits)
+                outs.append(self.model(chunk, False, self.white_bkgd, near, far, *model_args, ray_live=live)[1])
+            else:
+                outs.append(self.model(chunk, False, self.white_bkgd, self.near, self.far, *model_args)[1])
+        return {k: torch.cat([o[j] for o in outs], 0) for j, k in enumerate(("comp_rgb", "acc", "depth"))}
+
+    # ---- fitting poses and codes on the FROZEN network: what fit_latents and the two fit_pose share (DESIGN.md sections 4.13 - 4.15) ----
+    def _fit_args(self, name, steps, batches, poses=False):
+        """The checks of `steps` and `batches` and, for poses other than False (fit_pose), of one pose per view -> (batches, poses) as lists."""
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise ValueError(f"{name}: steps must be a positive int, got {steps!r}")
+        batches = list(batches)
+        if not batches:
+            raise ValueError(f"{name}: no batches")
+        if poses is not False:
+            poses = [] if poses is None else list(poses)
+            if len(poses) != len(batches):
+                raise ValueError(f"{name}: one (3, 4) pose per view: {len(batches)} views, {len(poses)} poses")
+        return batches, poses
+
+    def _fit_pose_batches(self, batches):
+        if self.ray_box is not None:
+            raise NotImplementedError("fit_pose: per-ray near / far from a ray box are not differentiated; use the scalar near / far")
+        for b in batches:
+            if "directions" not in b or "target" not in b:
+                raise ValueError("fit_pose: every batch needs 'directions' (camera-space) and 'target'")
+
+    def _fit_frozen(self, batches, steps, seed, poses=None, lr_pose=None, codes=None, lr_codes=None, fit_codes=False, freeze=True):
+        """`steps` Adam steps on the frozen network, batch `i % len(batches)` at step i -> (corrected poses or None, codes or None, losses).
+        poses: the views' initial (3, 4) matrices -- every batch is then a view ("directions", "target") whose 6-vector is fitted at rate
+        lr_pose -- or None: the batches are un-batched training batches, the ray box applies.  codes: the initial codes of an articulated
+        network (handed to self._frozen_loss; stepped at rate lr_codes when fit_codes) or None.  freeze=False: the network keeps its flags."""
+        dev = next(self.model.parameters()).device
+        views = len(batches)
+        if poses is not None:
+            pose0 = []
+            for c2w in poses:
+                c = torch.as_tensor(c2w, dtype=torch.float32).detach().to(dev)
+                if c.dim() != 2 or c.shape[0] < 3 or c.shape[1] != 4:
+                    raise ValueError(f"fit_pose: a pose must be a (3, 4) matrix, got {tuple(c.shape)}")
+                pose0.append(c[:3].contiguous())
+            parena = torch.zeros((4, 6 * views), dtype=torch.float32, device=dev)   # rows: 6-vectors, gradients, exp_avg, exp_avg_sq
+            corr = [parena[0, 6 * v: 6 * v + 6].detach().requires_grad_(True) for v in range(views)]
+        leaves = None
+        if codes is not None:
+            arena, leaves = _code_arena(codes, dev, fit_codes)   # the same rows for the 288 code floats; leaves on row 0
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+        net_params = list(self.model.parameters())
+        flags = [p.requires_grad for p in net_params]
+        losses = torch.zeros(steps, dtype=torch.float32, device=dev)
+        try:
+            if freeze:
+                for p in net_params:
+                    p.requires_grad_(False)
+            with torch.enable_grad():
+                for i in range(steps):
+                    v = i % views
+                    near, far = self.near, self.far
+                    if poses is not None:
+                        directions = batches[v]["directions"].to(device=dev, dtype=torch.float32)
+                        target = batches[v]["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
+                        rays_o, rays_d = ops.rays_from_pose(directions, pose0[v], corr[v])
+                        rays = {"rays_o": rays_o, "rays_d": rays_d, "viewdirs": rays_d}
+                    else:
+                        rays, target = batches[v], batches[v]["target"]
+                        if self.ray_box is not None:
+                            near, far, _ = ops.ray_limits(rays["rays_o"], rays["rays_d"], self.ray_box)
+                    t_rand = u = None
+                    if self.randomized:
+                        n = rays["rays_d"].shape[0]
+                        t_rand = torch.rand((n, self.model.num_coarse_samples + 1), device=dev, generator=gen)
+                        u = torch.rand((n, self.model.num_fine_samples), device=dev, generator=gen) if self.model.num_levels == 2 else None
+                    loss = self._frozen_loss(rays, target, near, far, leaves, t_rand, u)
+                    wrt = ([corr[v]] if poses is not None else []) + ([leaves[k] for k, _ in ops._LATENT_KEYS] if fit_codes else [])
+                    grads = list(torch.autograd.grad(loss, wrt))
+                    losses[i] = loss.detach()
+                    if poses is not None:   # a view's 6-vector keeps its own step count
+                        parena[1, 6 * v: 6 * v + 6].copy_(grads.pop(0))
+                        ops.adam_step(parena[0], parena[1], parena[2], parena[3], 6 * v, 6, float(lr_pose), 0.9, 0.999, 1e-8, i // views + 1)
+                    if fit_codes:
+                        torch.cat([g.reshape(-1) for g in grads], out=arena[1])
+                        ops.adam_step(arena[0], arena[1], arena[2], arena[3], 0, arena.shape[1], float(lr_codes), 0.9, 0.999, 1e-8, i + 1)
+        finally:
+            for p, f in zip(net_params, flags):
+                p.requires_grad_(f)
+        fitted = None
+        if poses is not None:
+            with torch.no_grad():
+                fitted = [ops.apply_pose_correction(pose0[v], parena[0, 6 * v: 6 * v + 6]) for v in range(views)]
+        return fitted, (_arena_codes(arena) if codes is not None else None), losses
 
     def finish_fit(self) -> None:
         """End of a training loop (Lightning's on_train_end): the deferred check of the LAST gradient exchange, which no later

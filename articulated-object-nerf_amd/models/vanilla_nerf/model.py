@@ -18,7 +18,74 @@ from ... import ops
 from ...autograd import RenderGeneral, RenderLevelVanilla, RenderVanilla, RenderVanillaInputs
 
 
-class NeRFMLP(nn.Module):
+class WeightStreams:
+    """The kernel-side weight streams of a NeRFMLP, vanilla or articulated (a mixin: it owns no parameter and no buffer).  The class names
+    its ops packers (_PACKERS) and the C byte queries (_BYTES) per stream kind and says in _pack_degrees() what the packers take beside
+    the parameters; its __init__ sets ``self._streams = {}``.
+
+    The streams are rebuilt from the LIVE parameters on every call (one ~6 us HIP pack kernel, 2.4 MB): no version/pointer key can go
+    stale, so `p.data.copy_()`, `dist.broadcast(p.data)`, EMA or clipping code that mutates parameters without bumping `p._version` is
+    seen exactly as nn.Linear would see it.  `fresh=True` (training) writes into a new buffer, because autograd saves the stream for
+    backward and a later forward must not overwrite what an earlier graph still needs; inference reuses one buffer per stream kind and
+    per (device, torch stream) the call is made on (stream-ordered; `_stream_buffer`)."""
+
+    def _pack(self, kind: str, fresh: bool, out: torch.Tensor | None = None) -> torch.Tensor:
+        params = dict(self.named_parameters())
+        dev = next(iter(params.values())).device
+        if out is None and not fresh:
+            out = self._stream_buffer(kind, dev)
+        return getattr(ops, self._PACKERS[kind])(params, out=out, **self._pack_degrees())
+
+    def _stream_buffer(self, kind: str, dev) -> torch.Tensor:
+        """The module's inference buffer of `kind` for `dev`'s current stream (ops.StreamCache: one per (device, stream), so renders of one
+        model on two streams never re-pack into a buffer the other stream's kernels still read)."""
+        cache = self._streams.get(kind)
+        if cache is None:
+            cache = self._streams[kind] = ops.StreamCache(register=False)
+        return ops._scratch(cache, dev, int(getattr(ops.lib, self._BYTES[kind])()))
+
+    def packed(self, fresh: bool = False) -> torch.Tensor:
+        """Forward weight stream of the fp32 kernels."""
+        return self._pack("fwd", fresh)
+
+    def packed_bwd(self, fresh: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Transposed weight stream for the backward data chain (training only)."""
+        return self._pack("bwd", fresh, out)
+
+    def new_bwd_buffer(self) -> torch.Tensor:
+        return torch.empty(int(getattr(ops.lib, self._BYTES["bwd"])()), dtype=torch.uint8, device=next(self.parameters()).device)
+
+
+def _draw_samples(model, rays, randomized, t_rand, u):
+    """The stratified / inverse-CDF draws of a forward -> (t_rand, u).  They may ride in the batch dict (keys "aon_t_rand", "aon_u": an
+    extension, namespaced so that a user batch carrying its own "u" / "t_rand" is never misread -- the reference's forward ignores extra
+    keys, model.py:299-306 -- that makes a harness run reproducible: tests/test_hip_long_training.py); what is still missing is drawn,
+    t_rand first, u with two levels only.  Not randomized: (None, None)."""
+    if not randomized:
+        return None, None
+    n, dev = rays["rays_o"].shape[0], rays["rays_o"].device
+    if t_rand is None:
+        t_rand = rays.get("aon_t_rand")
+    if u is None:
+        u = rays.get("aon_u")
+    if t_rand is None:
+        t_rand = torch.rand((n, model.num_coarse_samples + 1), device=dev)
+    if u is None and model.num_levels == 2:
+        u = torch.rand((n, model.num_fine_samples), device=dev)
+    return t_rand, u
+
+
+def _draw_noise(model, noise, randomized, n, device):
+    """The density noise of a forward (model.py:183-184), one (n, S) tensor per level: the caller's, else drawn level by level; or None."""
+    if not (model.noise_std > 0 and randomized):
+        return None
+    noise = list(noise) if noise is not None else []
+    noise += [None] * (model.num_levels - len(noise))
+    return [noise[lvl] if noise[lvl] is not None else torch.rand((n, model._opts.S(lvl)), device=device)
+            for lvl in range(model.num_levels)]
+
+
+class NeRFMLP(WeightStreams, nn.Module):
     """model.py:39-120.  ``forward(x, condition)``: x (N,S,63) encoded samples, condition (N,27) encoded view
     directions -> (raw_rgb (N,S,3), raw_density (N,S,1))."""
 
@@ -57,47 +124,13 @@ class NeRFMLP(nn.Module):
         init.xavier_uniform_(self.rgb_layer.weight)
         self._streams = {}
 
-    # Kernel-side weight streams.  They are rebuilt from the LIVE parameters on every call (one ~6 us HIP pack kernel,
-    # 2.4 MB): no version/pointer key can go stale, so `p.data.copy_()`, `dist.broadcast(p.data)`, EMA or clipping code
-    # that mutates parameters without bumping `p._version` is seen exactly as nn.Linear would see it.  `fresh=True`
-    # (training) writes into a new buffer, because autograd saves the stream for backward and a later forward must not
-    # overwrite what an earlier graph still needs; inference reuses one buffer per stream kind and per (device, torch stream) the call
-    # is made on (stream-ordered; `_stream_buffer`).
+    # the weight streams: WeightStreams
     _PACKERS = {"fwd": "pack_vanilla_mlp", "bwd": "pack_vanilla_mlp_bwd"}
-
-    def _pack(self, kind: str, fresh: bool, out: torch.Tensor | None = None) -> torch.Tensor:
-        params = dict(self.named_parameters())
-        dev = next(iter(params.values())).device
-        if out is None and not fresh:
-            out = self._stream_buffer(kind, dev)
-        if not self.geometry.is_default:   # other degrees on the fused kernels (fits_fused_inference): zero-weight slots
-            out = getattr(ops, self._PACKERS[kind])(params, out=out, degrees=(self.min_deg_point, self.max_deg_point, self.deg_view))
-        else:
-            out = getattr(ops, self._PACKERS[kind])(params, out=out)
-        return out
-
     _BYTES = {"fwd": "aon_mlp_packed_bytes", "bwd": "aon_bwd_packed_bytes"}
 
-    def _stream_buffer(self, kind: str, dev) -> torch.Tensor:
-        """The module's inference buffer of `kind` for `dev`'s current stream (ops.StreamCache: one per (device, stream), so renders of one
-        model on two streams never re-pack into a buffer the other stream's kernels still read)."""
-        cache = self._streams.get(kind)
-        if cache is None:
-            cache = self._streams[kind] = ops.StreamCache(register=False)
-        return ops._scratch(cache, dev, int(getattr(ops.lib, self._BYTES[kind])()))
-
-    def packed(self, fresh: bool = False) -> torch.Tensor:
-        """Forward weight stream of the fp32 kernels."""
-        return self._pack("fwd", fresh)
-
-    def packed_bwd(self, fresh: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
-        """Transposed weight stream for the backward data chain (training only)."""
-        return self._pack("bwd", fresh, out)
-
-    _BWD_BYTES = "aon_bwd_packed_bytes"
-
-    def new_bwd_buffer(self) -> torch.Tensor:
-        return torch.empty(int(getattr(ops.lib, self._BWD_BYTES)()), dtype=torch.uint8, device=next(self.parameters()).device)
+    def _pack_degrees(self):
+        # other degrees on the fused kernels (fits_fused_inference): zero-weight slots
+        return {} if self.geometry.is_default else {"degrees": (self.min_deg_point, self.max_deg_point, self.deg_view)}
 
     def ordered_params(self):
         params = dict(self.named_parameters())
@@ -144,14 +177,6 @@ class NeRF(nn.Module):
         self._fused_training = True      # (tests / measurements: False sends the training step of a padded-slot network to the layer-wise engine)
         if not geom.is_default and self._fused_inference:
             self._opts.degrees = (min_deg_point, max_deg_point, deg_view)
-
-    def _draw_noise(self, noise, randomized, n, device):
-        if not (self.noise_std > 0 and randomized):
-            return None
-        noise = list(noise) if noise is not None else []
-        noise += [None] * (self.num_levels - len(noise))
-        return [noise[lvl] if noise[lvl] is not None else torch.rand((n, self._opts.S(lvl)), device=device)
-                for lvl in range(self.num_levels)]
 
     def _forward_many_levels(self, rays, randomized, white_bkgd, near, far, t_rand, u, noise, training=False):
         """model.py:147-199 for num_levels > 2 (every level after the first resamples from the previous level's t and weights
@@ -212,20 +237,8 @@ class NeRF(nn.Module):
             raise ValueError("ray_live is inference only: randomized=False, under torch.no_grad(), one or two levels")
         if occupancy is not None or early_stop is not None:
             return self._forward_occupancy(rays, randomized, white_bkgd, near, far, u, occupancy, early_stop, ray_live)
-        # the stratified / inverse-CDF draws may ride in the batch dict (keys "aon_t_rand", "aon_u": an extension, namespaced so that a user batch carrying its own "u" / "t_rand" is never misread -- the reference's forward
-        # ignores extra keys, model.py:299-306 -- that makes a harness run reproducible: tests/test_hip_long_training.py)
-        if t_rand is None:
-            t_rand = rays.get("aon_t_rand")
-        if u is None:
-            u = rays.get("aon_u")
-        if randomized:
-            if t_rand is None:
-                t_rand = torch.rand((n, self.num_coarse_samples + 1), device=rays_o.device)
-            if u is None and self.num_levels == 2:
-                u = torch.rand((n, self.num_fine_samples), device=rays_o.device)
-        else:
-            t_rand, u = None, None
-        noise = self._draw_noise(noise, randomized, n, rays_o.device) if self.num_levels <= 2 else noise
+        t_rand, u = _draw_samples(self, rays, randomized, t_rand, u)
+        noise = _draw_noise(self, noise, randomized, n, rays_o.device) if self.num_levels <= 2 else noise
         training = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         # a FROZEN network whose rays require grad (refining a camera pose, LitNeRF.fit_pose): the training forward and a backward that ends at
         # rays_o, rays_d and viewdirs.  A parameter that trains, anywhere, keeps the path it took: its rays get none.
@@ -349,7 +362,6 @@ class NeRF(nn.Module):
 # Harness-level equivalents of the reference's LightningModule methods, without pytorch-lightning.
 # --------------------------------------------------------------------------------------------------------------------
 import math
-from collections import defaultdict
 from types import SimpleNamespace
 
 from . import helper
@@ -397,12 +409,8 @@ class LitNeRF(Harness):
                  lr_delay_mult: float = 0.01, randomized: bool = True, near: float = 2.0, far: float = 6.0, white_bkgd: bool = True,
                  model_kwargs: dict | None = None, ray_box=None):
         super().__init__()
-        self._init_harness(hparams, dict(chunk=3840, run_max_steps=100000, img_wh=(640, 480)))  # opt.py:103,112,17
-        self.lr_init, self.lr_final, self.lr_delay_steps, self.lr_delay_mult = lr_init, lr_final, lr_delay_steps, lr_delay_mult
-        self.randomized, self.near, self.far, self.white_bkgd = randomized, near, far, white_bkgd
-        # ray_box (a side length, or (lo, hi)): per-ray near / far from the rays' intersection with that box (helper.get_ray_limits, the
-        # reference's near_obj / far_obj) instead of the scalars; None: the scalars, as before
-        self.ray_box = ray_box
+        self._init_harness(hparams, dict(chunk=3840, run_max_steps=100000, img_wh=(640, 480)),  # opt.py:103,112,17
+                           lr_init, lr_final, lr_delay_steps, lr_delay_mult, randomized, near, far, white_bkgd, ray_box)
         # the reference builds NeRF() (model.py:218); `model_kwargs` hands its constructor arguments through (sample counts, degrees, ...)
         self.model = NeRF(**(model_kwargs or {}))
 
@@ -433,95 +441,26 @@ class LitNeRF(Harness):
         NeRF.forward takes autograd.RenderVanillaInputs.  The views' 6-vectors, their gradients and Adam moments are one flat
         (4, 6 * views) buffer stepped by aon_adam_step; a view's 6-vector keeps its own step count.  Scalar near / far only (a ray box's
         per-ray limits would move with the pose and carry no gradient)."""
-        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
-            raise ValueError(f"fit_pose: steps must be a positive int, got {steps!r}")
-        batches = list(batches)
-        if not batches:
-            raise ValueError("fit_pose: no batches")
-        poses = [] if poses is None else list(poses)
-        if len(poses) != len(batches):
-            raise ValueError(f"fit_pose: one (3, 4) pose per view: {len(batches)} views, {len(poses)} poses")
+        batches, poses = self._fit_args("fit_pose", steps, batches, poses)
         if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not lr > 0:
             raise ValueError(f"fit_pose: lr must be positive, got {lr!r}")
-        if self.ray_box is not None:
-            raise NotImplementedError("fit_pose: per-ray near / far from a ray box are not differentiated; use the scalar near / far")
-        for b in batches:
-            if "directions" not in b or "target" not in b:
-                raise ValueError("fit_pose: every batch needs 'directions' (camera-space) and 'target'")
-        dev = next(self.model.parameters()).device
-        pose0 = []
-        for c2w in poses:
-            c = torch.as_tensor(c2w, dtype=torch.float32).detach().to(dev)
-            if c.dim() != 2 or c.shape[0] < 3 or c.shape[1] != 4:
-                raise ValueError(f"fit_pose: a pose must be a (3, 4) matrix, got {tuple(c.shape)}")
-            pose0.append(c[:3].contiguous())
-        parena = torch.zeros((4, 6 * len(batches)), dtype=torch.float32, device=dev)   # rows: 6-vectors, gradients, exp_avg, exp_avg_sq
-        corr = [parena[0, 6 * v: 6 * v + 6].detach().requires_grad_(True) for v in range(len(batches))]
-        gen = torch.Generator(device=dev)
-        gen.manual_seed(int(seed))
-        net_params = list(self.model.parameters())
-        flags = [p.requires_grad for p in net_params]
-        losses = torch.zeros(steps, dtype=torch.float32, device=dev)
-        try:
-            for p in net_params:
-                p.requires_grad_(False)
-            with torch.enable_grad():
-                for i in range(steps):
-                    v = i % len(batches)
-                    directions = batches[v]["directions"].to(device=dev, dtype=torch.float32)
-                    target = batches[v]["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
-                    rays_o, rays_d = ops.rays_from_pose(directions, pose0[v], corr[v])
-                    rays = {"rays_o": rays_o, "rays_d": rays_d, "viewdirs": rays_d}
-                    t_rand = u = None
-                    if self.randomized:
-                        n = rays_d.shape[0]
-                        t_rand = torch.rand((n, self.model.num_coarse_samples + 1), device=dev, generator=gen)
-                        u = torch.rand((n, self.model.num_fine_samples), device=dev, generator=gen) if self.model.num_levels == 2 else None
-                    rendered = self.model(rays, self.randomized, self.white_bkgd, self.near, self.far, t_rand=t_rand, u=u)
-                    loss, _ = helper.train_loss(rendered, target)
-                    grad, = torch.autograd.grad(loss, [corr[v]])
-                    parena[1, 6 * v: 6 * v + 6].copy_(grad)
-                    losses[i] = loss.detach()
-                    ops.adam_step(parena[0], parena[1], parena[2], parena[3], 6 * v, 6, float(lr), 0.9, 0.999, 1e-8, i // len(batches) + 1)
-        finally:
-            for p, f in zip(net_params, flags):
-                p.requires_grad_(f)
-        with torch.no_grad():
-            fitted = [ops.apply_pose_correction(pose0[v], parena[0, 6 * v: 6 * v + 6]) for v in range(len(batches))]
+        self._fit_pose_batches(batches)
+        fitted, _, losses = self._fit_frozen(batches, steps, seed, poses=poses, lr_pose=lr)
         return fitted, losses
+
+    def _frozen_loss(self, rays, target, near, far, codes, t_rand, u):
+        rendered = self.model(rays, self.randomized, self.white_bkgd, near, far, t_rand=t_rand, u=u)
+        return helper.train_loss(rendered, target)[0]
 
     @torch.no_grad()
     def render_rays(self, batch, batch_idx):
-        B = batch["rays_o"].shape[0]
-        ret = defaultdict(list)
-        limits = _ray_box_limits(self.ray_box, batch) if self.ray_box is not None else None
-        for i in range(0, B, self.hparams.chunk):
-            chunk = {k: (v if k == "obj_idx" else v[i: i + self.hparams.chunk]) for k, v in batch.items()}
-            if limits is not None:
-                near, far, live = (x[i: i + self.hparams.chunk] for x in limits)
-                out = self.model(chunk, False, self.white_bkgd, near, far, ray_live=live)
-            else:
-                out = self.model(chunk, False, self.white_bkgd, self.near, self.far)
-            ret["comp_rgb"] += [out[1][0]]
-            ret["acc"] += [out[1][1]]
-            ret["depth"] += [out[1][2]]
-        ret = {k: torch.cat(v, 0) for k, v in ret.items()}
+        ret = self._render_chunks(batch, whole=("obj_idx",))
         self.log("val/psnr", self.psnr_legacy(ret["comp_rgb"], batch["target"]).mean().item())
         return ret
 
     @torch.no_grad()
     def render_rays_test(self, batch, batch_idx):
-        B = batch["rays_o"].shape[0]
-        rgb = []
-        limits = _ray_box_limits(self.ray_box, batch) if self.ray_box is not None else None
-        for i in range(0, B, self.hparams.chunk):
-            chunk = {k: v[i: i + self.hparams.chunk] for k, v in batch.items()}
-            if limits is not None:
-                near, far, live = (x[i: i + self.hparams.chunk] for x in limits)
-                rgb.append(self.model(chunk, False, self.white_bkgd, near, far, ray_live=live)[1][0])
-            else:
-                rgb.append(self.model(chunk, False, self.white_bkgd, self.near, self.far)[1][0])
-        return {"target": batch["target"], "instance_mask": batch["instance_mask"], "rgb": torch.cat(rgb, 0)}
+        return {"target": batch["target"], "instance_mask": batch["instance_mask"], "rgb": self._render_chunks(batch)["comp_rgb"]}
 
     def validation_step(self, batch, batch_idx):
         batch = {k: (v if k == "obj_idx" else v.squeeze(0)) for k, v in batch.items()}

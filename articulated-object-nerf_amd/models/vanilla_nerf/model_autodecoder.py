@@ -11,9 +11,10 @@ import torch.nn.init as init
 
 from ... import ops
 from ...autograd import RenderArticulated, RenderArticulatedInputs, RenderArticulatedLatents
+from .model import WeightStreams, _draw_noise, _draw_samples
 
 
-class NeRFMLP(nn.Module):
+class NeRFMLP(WeightStreams, nn.Module):
     """model_autodecoder.py:60-239.  ``forward(pos, condition, latents)``: pos (N,S,3) un-encoded sample positions,
     condition (N,27) encoded view dirs, latents {"density": (1,128), "color": (1,128), "articulation": (1,32)}
     -> (raw_rgb (N,S,3), raw_density (N,S,1))."""
@@ -59,33 +60,12 @@ class NeRFMLP(nn.Module):
             init.xavier_uniform_(m.weight)  # views_linear[0] keeps the default init, like the reference (:147-151)
         self._streams = {}
 
-    # weight streams are rebuilt from the live parameters on every call (see vanilla NeRFMLP._pack: nothing can go stale)
+    # the weight streams: model.WeightStreams
     _PACKERS = {"fwd": "pack_art_mlp", "bwd": "pack_art_mlp_bwd"}
-
-    def _pack(self, kind: str, fresh: bool, out: torch.Tensor | None = None) -> torch.Tensor:
-        params = dict(self.named_parameters())
-        dev = next(iter(params.values())).device
-        if out is None and not fresh:
-            out = self._stream_buffer(kind, dev)
-        return getattr(ops, self._PACKERS[kind])(params, out=out, degrees=self.degrees)
-
     _BYTES = {"fwd": "aon_art_packed_bytes", "bwd": "aon_art_bwd_packed_bytes", "small": "aon_art_small_bytes"}
 
-    def _stream_buffer(self, kind: str, dev) -> torch.Tensor:
-        """The module's inference buffer of `kind` for `dev`'s current stream (one per (device, stream): see vanilla NeRFMLP._stream_buffer)."""
-        cache = self._streams.get(kind)
-        if cache is None:
-            cache = self._streams[kind] = ops.StreamCache(register=False)
-        return ops._scratch(cache, dev, int(getattr(ops.lib, self._BYTES[kind])()))
-
-    def packed(self, fresh: bool = False) -> torch.Tensor:
-        return self._pack("fwd", fresh)
-
-    def packed_bwd(self, fresh: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
-        return self._pack("bwd", fresh, out)
-
-    def new_bwd_buffer(self) -> torch.Tensor:
-        return torch.empty(int(ops.lib.aon_art_bwd_packed_bytes()), dtype=torch.uint8, device=next(self.parameters()).device)
+    def _pack_degrees(self):
+        return {"degrees": self.degrees}
 
     def ordered_params(self):
         params = dict(self.named_parameters())
@@ -165,26 +145,8 @@ class NeRF_AE_Art(nn.Module):
                                              self.fine_mlp.prepared(latents) if two else None, rays_o, rays["rays_d"], rays["viewdirs"], near, far,
                                              white_bkgd, occupancy, self.num_levels, u, opts=self._opts, ray_live=ray_live)
             return [tuple(o) for o in outs]
-        # the stratified / inverse-CDF draws may ride in the batch dict (keys "aon_t_rand", "aon_u": an extension, namespaced so that a user batch carrying its own "u" / "t_rand" is never misread -- the reference's forward
-        # ignores extra keys, model.py:299-306 -- that makes a harness run reproducible: tests/test_hip_long_training.py)
-        if t_rand is None:
-            t_rand = rays.get("aon_t_rand")
-        if u is None:
-            u = rays.get("aon_u")
-        if randomized:
-            if t_rand is None:
-                t_rand = torch.rand((n, self.num_coarse_samples + 1), device=rays_o.device)
-            if u is None and self.num_levels == 2:
-                u = torch.rand((n, self.num_fine_samples), device=rays_o.device)
-        else:
-            t_rand, u = None, None
-        if self.noise_std > 0 and randomized:   # model_autodecoder.py:318-319
-            noise = list(noise) if noise is not None else []
-            noise += [None] * (self.num_levels - len(noise))
-            noise = [noise[lvl] if noise[lvl] is not None else torch.rand((n, self._opts.S(lvl)), device=rays_o.device)
-                     for lvl in range(self.num_levels)]
-        else:
-            noise = None
+        t_rand, u = _draw_samples(self, rays, randomized, t_rand, u)
+        noise = _draw_noise(self, noise, randomized, n, rays_o.device)   # model_autodecoder.py:318-319
         ray_grad = any(getattr(rays[k], "requires_grad", False) for k in ("rays_o", "rays_d", "viewdirs"))
         if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
                                         or any(getattr(v, "requires_grad", False) for v in latents.values()) or ray_grad):
@@ -238,8 +200,6 @@ class NeRF_AE_Art(nn.Module):
 
 
 # --------------------------------------------------------------------------------------------------------------------
-from collections import defaultdict  # noqa: E402
-
 from . import helper  # noqa: E402
 from ..code_library import CodeLibraryArticulated  # noqa: E402
 from ..interface import Harness  # noqa: E402
@@ -261,10 +221,8 @@ class LitNeRF_AutoDecoder(Harness):
                  lr_delay_mult: float = 0.01, randomized: bool = True, near: float = 2.0, far: float = 6.0, white_bkgd: bool = True,
                  model_kwargs: dict | None = None, ray_box=None):
         super().__init__()
-        self._init_harness(hparams, dict(chunk=3840, run_max_steps=100000, img_wh=(320, 240), N_max_objs=1, N_obj_code_length=128))
-        self.lr_init, self.lr_final, self.lr_delay_steps, self.lr_delay_mult = lr_init, lr_final, lr_delay_steps, lr_delay_mult
-        self.randomized, self.near, self.far, self.white_bkgd = randomized, near, far, white_bkgd
-        self.ray_box = ray_box   # per-ray near / far from this box (a side length, or (lo, hi)); None: the scalars (LitNeRF)
+        self._init_harness(hparams, dict(chunk=3840, run_max_steps=100000, img_wh=(320, 240), N_max_objs=1, N_obj_code_length=128),
+                           lr_init, lr_final, lr_delay_steps, lr_delay_mult, randomized, near, far, white_bkgd, ray_box)
         self.model = NeRF_AE_Art(**(model_kwargs or {}))   # the reference builds NeRF_AE_Art() (model_autodecoder.py:352)
         self.code_library = CodeLibraryArticulated(self.hparams)
 
@@ -334,57 +292,17 @@ class LitNeRF_AutoDecoder(Harness):
         latent-only backward.  The codes, their gradients and the Adam moments are one flat (4, 288) buffer
         stepped by ONE launch (aon_adam_step).  full_backward=True (the A/B partner, tools/latent_fit_bench.py): the network keeps its flags,
         so every step pays the full training backward -- same losses and codes, bit for bit."""
-        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
-            raise ValueError(f"fit_latents: steps must be a positive int, got {steps!r}")
-        batches = list(batches)
-        if not batches:
-            raise ValueError("fit_latents: no batches")
+        batches, _ = self._fit_args("fit_latents", steps, batches)
         if not (isinstance(lr, (int, float)) and lr > 0):
             raise ValueError(f"fit_latents: lr must be positive, got {lr!r}")
-        dev = next(self.model.parameters()).device
-        lat0 = self._initial_latents(init, dev)
-        keys, dims = ("density", "color", "articulation"), (128, 128, 32)
-        arena = torch.zeros((4, sum(dims)), dtype=torch.float32, device=dev)   # rows: codes, gradients, exp_avg, exp_avg_sq
-        leaves, off = {}, 0
-        for k, d in zip(keys, dims):
-            view = arena[0, off: off + d].view(1, d)
-            view.copy_(lat0[k])
-            leaves[k] = view.detach().requires_grad_(True)   # a leaf on the arena's storage
-            off += d
-        gen = torch.Generator(device=dev)
-        gen.manual_seed(int(seed))
-        net_params = list(self.model.parameters())
-        flags = [p.requires_grad for p in net_params]
-        losses = torch.zeros(steps, dtype=torch.float32, device=dev)
-        try:
-            if not full_backward:
-                for p in net_params:
-                    p.requires_grad_(False)
-            with torch.enable_grad():
-                for i in range(steps):
-                    batch = self._unbatch(batches[i % len(batches)])
-                    near, far = self.near, self.far
-                    if self.ray_box is not None:
-                        near, far, _ = _ray_box_limits(self.ray_box, batch)
-                    t_rand = u = None
-                    if self.randomized:
-                        n = batch["rays_o"].shape[0]
-                        t_rand = torch.rand((n, self.model.num_coarse_samples + 1), device=dev, generator=gen)
-                        u = torch.rand((n, self.model.num_fine_samples), device=dev, generator=gen) if self.model.num_levels == 2 else None
-                    rendered = self.model(batch, self.randomized, self.white_bkgd, near, far, leaves, t_rand=t_rand, u=u)
-                    loss, _ = helper.train_loss(rendered, batch["target"], tuple(leaves[k] for k in keys), 1e-4)
-                    grads = torch.autograd.grad(loss, [leaves[k] for k in keys])
-                    torch.cat([g.reshape(-1) for g in grads], out=arena[1])
-                    losses[i] = loss.detach()
-                    ops.adam_step(arena[0], arena[1], arena[2], arena[3], 0, arena.shape[1], float(lr), 0.9, 0.999, 1e-8, i + 1)
-        finally:
-            for p, f in zip(net_params, flags):
-                p.requires_grad_(f)
-        off, out = 0, {}
-        for k, d in zip(keys, dims):
-            out[k] = arena[0, off: off + d].view(1, d).clone()
-            off += d
-        return out, losses
+        lat0 = self._initial_latents(init, next(self.model.parameters()).device)
+        _, codes, losses = self._fit_frozen([self._unbatch(b) for b in batches], steps, seed, codes=lat0, lr_codes=lr, fit_codes=True,
+                                            freeze=not full_backward)
+        return codes, losses
+
+    def _frozen_loss(self, rays, target, near, far, codes, t_rand, u):
+        rendered = self.model(rays, self.randomized, self.white_bkgd, near, far, codes, t_rand=t_rand, u=u)
+        return helper.train_loss(rendered, target, tuple(codes[k] for k, _ in ops._LATENT_KEYS), 1e-4)[0]
 
     def fit_pose(self, batches, steps: int, lr=5.0e-3, codes="mean", poses=None, fit_codes: bool = False, seed: int = 0):
         """Refine the camera pose of observed views of ONE object with the network FROZEN (iNeRF-style), alone or
@@ -401,95 +319,15 @@ class LitNeRF_AutoDecoder(Harness):
         The network's requires_grad flags are cleared for the duration and restored; with them cleared and the rays requiring grad,
         NeRF_AE_Art.forward takes autograd.RenderArticulatedInputs.  Every buffer is stepped by aon_adam_step; a view's 6-vector keeps its
         own step count.  Scalar near / far only (a ray box's per-ray limits would move with the pose and carry no gradient)."""
-        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
-            raise ValueError(f"fit_pose: steps must be a positive int, got {steps!r}")
-        batches = list(batches)
-        if not batches:
-            raise ValueError("fit_pose: no batches")
-        poses = [] if poses is None else list(poses)
-        if len(poses) != len(batches):
-            raise ValueError(f"fit_pose: one (3, 4) pose per view: {len(batches)} views, {len(poses)} poses")
+        batches, poses = self._fit_args("fit_pose", steps, batches, poses)
         lrs = tuple(lr) if isinstance(lr, (tuple, list)) else (lr, lr)
         if len(lrs) != 2 or not all(isinstance(x, (int, float)) and x > 0 for x in lrs):
             raise ValueError(f"fit_pose: lr must be positive (one rate, or a pair for poses and codes), got {lr!r}")
-        if self.ray_box is not None:
-            raise NotImplementedError("fit_pose: per-ray near / far from a ray box are not differentiated; use the scalar near / far")
-        for b in batches:
-            if "directions" not in b or "target" not in b:
-                raise ValueError("fit_pose: every batch needs 'directions' (camera-space) and 'target'")
-        dev = next(self.model.parameters()).device
-        lat0 = self._initial_latents(codes, dev)
-        pose0 = []
-        for c2w in poses:
-            c = torch.as_tensor(c2w, dtype=torch.float32).detach().to(dev)
-            if c.dim() != 2 or c.shape[0] < 3 or c.shape[1] != 4:
-                raise ValueError(f"fit_pose: a pose must be a (3, 4) matrix, got {tuple(c.shape)}")
-            pose0.append(c[:3].contiguous())
-        keys, dims = ("density", "color", "articulation"), (128, 128, 32)
-        arena = torch.zeros((4, sum(dims)), dtype=torch.float32, device=dev)          # rows: codes, gradients, exp_avg, exp_avg_sq
-        parena = torch.zeros((4, 6 * len(batches)), dtype=torch.float32, device=dev)  # the same rows for the views' 6-vectors
-        leaves, off = {}, 0
-        for k, d in zip(keys, dims):
-            view = arena[0, off: off + d].view(1, d)
-            view.copy_(lat0[k])
-            leaves[k] = view.detach().requires_grad_(bool(fit_codes))
-            off += d
-        corr = [parena[0, 6 * v: 6 * v + 6].detach().requires_grad_(True) for v in range(len(batches))]
-        gen = torch.Generator(device=dev)
-        gen.manual_seed(int(seed))
-        net_params = list(self.model.parameters())
-        flags = [p.requires_grad for p in net_params]
-        losses = torch.zeros(steps, dtype=torch.float32, device=dev)
-        try:
-            for p in net_params:
-                p.requires_grad_(False)
-            with torch.enable_grad():
-                for i in range(steps):
-                    v = i % len(batches)
-                    directions = batches[v]["directions"].to(device=dev, dtype=torch.float32)
-                    target = batches[v]["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
-                    rays_o, rays_d = ops.rays_from_pose(directions, pose0[v], corr[v])
-                    rays = {"rays_o": rays_o, "rays_d": rays_d, "viewdirs": rays_d}
-                    t_rand = u = None
-                    if self.randomized:
-                        n = rays_d.shape[0]
-                        t_rand = torch.rand((n, self.model.num_coarse_samples + 1), device=dev, generator=gen)
-                        u = torch.rand((n, self.model.num_fine_samples), device=dev, generator=gen) if self.model.num_levels == 2 else None
-                    rendered = self.model(rays, self.randomized, self.white_bkgd, self.near, self.far, leaves, t_rand=t_rand, u=u)
-                    loss, _ = helper.train_loss(rendered, target, tuple(leaves[k] for k in keys), 1e-4)
-                    grads = torch.autograd.grad(loss, [corr[v]] + ([leaves[k] for k in keys] if fit_codes else []))
-                    parena[1, 6 * v: 6 * v + 6].copy_(grads[0])
-                    losses[i] = loss.detach()
-                    ops.adam_step(parena[0], parena[1], parena[2], parena[3], 6 * v, 6, float(lrs[0]), 0.9, 0.999, 1e-8, i // len(batches) + 1)
-                    if fit_codes:
-                        torch.cat([g.reshape(-1) for g in grads[1:]], out=arena[1])
-                        ops.adam_step(arena[0], arena[1], arena[2], arena[3], 0, arena.shape[1], float(lrs[1]), 0.9, 0.999, 1e-8, i + 1)
-        finally:
-            for p, f in zip(net_params, flags):
-                p.requires_grad_(f)
-        with torch.no_grad():
-            fitted = [ops.apply_pose_correction(pose0[v], parena[0, 6 * v: 6 * v + 6]) for v in range(len(batches))]
-        off, out = 0, {}
-        for k, d in zip(keys, dims):
-            out[k] = arena[0, off: off + d].view(1, d).clone()
-            off += d
-        return fitted, out, losses
+        self._fit_pose_batches(batches)
+        lat0 = self._initial_latents(codes, next(self.model.parameters()).device)
+        return self._fit_frozen(batches, steps, seed, poses=poses, lr_pose=lrs[0], codes=lat0, lr_codes=lrs[1], fit_codes=fit_codes)
 
-    def _render_chunks(self, batch, latents, skip=()):
-        B = batch["rays_o"].shape[0]
-        ret = defaultdict(list)
-        limits = _ray_box_limits(self.ray_box, batch) if self.ray_box is not None else None   # of the whole image, before the chunk loop
-        for i in range(0, B, self.hparams.chunk):
-            chunk = {k: v[i: i + self.hparams.chunk] for k, v in batch.items() if k not in skip and k not in _SCALAR_KEYS}
-            if limits is not None:
-                near, far, live = (x[i: i + self.hparams.chunk] for x in limits)
-                out = self.model(chunk, False, self.white_bkgd, near, far, latents, ray_live=live)
-            else:
-                out = self.model(chunk, False, self.white_bkgd, self.near, self.far, latents)
-            ret["comp_rgb"] += [out[1][0]]
-            ret["acc"] += [out[1][1]]
-            ret["depth"] += [out[1][2]]
-        return {k: torch.cat(v, 0) for k, v in ret.items()}
+    _CHUNK_SKIP = _SCALAR_KEYS
 
     @torch.no_grad()
     def render_rays(self, batch, latents):

@@ -1130,11 +1130,15 @@ def train_workspace(device, n_rays: int, articulated: bool, num_levels: int = 2,
                       "aon_train_workspace_bytes_ex", device)
 
 
+def _train_scratch(query: str, device, *query_args, st=None) -> torch.Tensor:
+    """A backward's temporaries, sized by the C query `query`: taken from the pool when the backward runs and given back right after."""
+    return _pool_take(int(getattr(lib, query)(*query_args, None if st is None else C.byref(st))), query, device)
+
+
 def train_scratch(device, n_rays: int, articulated: bool, num_levels: int = 2, st=None) -> torch.Tensor:
     """The backward's own temporaries (gradient planes, d_raw, weight-gradient partials): taken from the pool when the backward runs and
     given back right after, so a live graph pins the forward's workspace only."""
-    return _pool_take(int(lib.aon_train_scratch_bytes_ex(n_rays, int(articulated), num_levels, None if st is None else C.byref(st))),
-                      "aon_train_scratch_bytes_ex", device)
+    return _train_scratch("aon_train_scratch_bytes_ex", device, n_rays, int(articulated), num_levels, st=st)
 
 
 def render_fwd_train(packed_c, packed_f, rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, small_c=None, small_f=None,
@@ -1222,8 +1226,7 @@ def render_bwd(ws, packs_bwd, packs_fwd, rays_d, white_bkgd, num_levels, g_rgb, 
 def train_scratch_inputs_vanilla(device, n_rays: int, num_levels: int = 2, st=None) -> torch.Tensor:
     """The temporaries of the frozen vanilla network's ray-gradient backward (d_raw, gradient planes, one 128-byte record per sample; no
     weight-gradient workspace), pooled as `train_scratch`."""
-    return _pool_take(int(lib.aon_train_scratch_bytes_inputs_vanilla(n_rays, num_levels, None if st is None else C.byref(st))),
-                      "aon_train_scratch_bytes_inputs_vanilla", device)
+    return _train_scratch("aon_train_scratch_bytes_inputs_vanilla", device, n_rays, num_levels, st=st)
 
 
 def _vanilla_input_param_array(params, _degrees):
@@ -1236,6 +1239,12 @@ def _vanilla_input_param_array(params, _degrees):
     return keep, _ptr_array(keep)
 
 
+def _ray_grads_call(rays_o, viewdirs, n, dev):
+    """-> (g_rays_o, g_rays_d, g_viewdirs) to be written, each (n, 3), and the aon_ray_grads record that points at them and at the rays"""
+    g_rays = tuple(torch.empty((n, 3), dtype=torch.float32, device=dev) for _ in range(3))
+    return g_rays, _lib.RayGradsC(rays_o.data_ptr(), viewdirs.data_ptr(), *(g.data_ptr() for g in g_rays))
+
+
 def render_bwd_inputs(ws, packs_bwd, packs_fwd, rays_o, rays_d, viewdirs, white_bkgd, num_levels, g_rgb, g_acc, g_depth, params, geometry=None):
     """loss.backward() through render_fwd_train of a FROZEN vanilla network, down to its rays -> (g_rays_o, g_rays_d, g_viewdirs), each
     (n, 3), summed over the levels (aon_render_bwd_inputs).  `params`: per level, the network's parameters (a dict
@@ -1244,8 +1253,7 @@ def render_bwd_inputs(ws, packs_bwd, packs_fwd, rays_o, rays_d, viewdirs, white_
     ro, vd = _f32(rays_o, "rays_o"), _f32(viewdirs, "viewdirs")
     bc = _BwdCall(rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, geometry, _vanilla_input_param_array, params)
     pb, pf = bc.pad(packs_bwd), bc.pad(packs_fwd)
-    g_rays = tuple(torch.empty((bc.n, 3), dtype=torch.float32, device=bc.dev) for _ in range(3))
-    rg = _lib.RayGradsC(ro.data_ptr(), vd.data_ptr(), *(g.data_ptr() for g in g_rays))
+    g_rays, rg = _ray_grads_call(ro, vd, bc.n, bc.dev)
     bc.call("aon_render_bwd_inputs", (_pk(pb[0]), _pk(pf[0]), _pk(pb[1]), _pk(pf[1])), bc.parr, ws,
             train_scratch_inputs_vanilla(bc.dev, bc.n, num_levels, bc.st), C.byref(rg))
     return g_rays
@@ -1275,8 +1283,7 @@ def _art_render_bwd(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels, g_rgb
     if rays is None:
         bc.call("aon_art_render_bwd_latents", packs, (*bc.parr, *lat_ptrs), ws, train_scratch_latents(dev, n, num_levels, st))
         return g_lat
-    g_rays = tuple(torch.empty((n, 3), dtype=torch.float32, device=dev) for _ in range(3))
-    rg = _lib.RayGradsC(rays[0].data_ptr(), rays[1].data_ptr(), *(g.data_ptr() for g in g_rays))
+    g_rays, rg = _ray_grads_call(*rays, n, dev)
     bc.call("aon_art_render_bwd_inputs", packs, (*bc.parr, *lat_ptrs), ws, train_scratch_inputs(dev, n, num_levels, st), C.byref(rg))
     return (g_lat, *g_rays)
 
@@ -1292,8 +1299,7 @@ def art_render_bwd(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels, g_rgb,
 def train_scratch_latents(device, n_rays: int, num_levels: int = 2, st=None) -> torch.Tensor:
     """The latent-only backward's temporaries (gradient planes, d_raw, a few MB of partial sums; no weight-gradient workspace), pooled as
     `train_scratch`."""
-    return _pool_take(int(lib.aon_train_scratch_bytes_latents(n_rays, num_levels, None if st is None else C.byref(st))),
-                      "aon_train_scratch_bytes_latents", device)
+    return _train_scratch("aon_train_scratch_bytes_latents", device, n_rays, num_levels, st=st)
 
 
 def art_render_bwd_latents(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels, g_rgb, g_acc, g_depth, params_per_level, geometry=None) -> dict:
@@ -1305,8 +1311,7 @@ def art_render_bwd_latents(ws, packs_bwd, smalls, rays_d, white_bkgd, num_levels
 
 def train_scratch_inputs(device, n_rays: int, num_levels: int = 2, st=None) -> torch.Tensor:
     """`train_scratch_latents` plus the ray gradients' per-sample records (128 B a sample), pooled alike."""
-    return _pool_take(int(lib.aon_train_scratch_bytes_inputs(n_rays, num_levels, None if st is None else C.byref(st))),
-                      "aon_train_scratch_bytes_inputs", device)
+    return _train_scratch("aon_train_scratch_bytes_inputs", device, n_rays, num_levels, st=st)
 
 
 def art_render_bwd_inputs(ws, packs_bwd, smalls, rays_o, rays_d, viewdirs, white_bkgd, num_levels, g_rgb, g_acc, g_depth, params_per_level,

@@ -9,6 +9,9 @@ import sys
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_hip_vanilla_ray_grads import pose_errors  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -375,13 +378,6 @@ FIT = dict(H=8, W=12, steps=60, lr=5e-3, correction=(0.02, -0.025, 0.015, 0.03, 
            degrees=dict(min_deg_point=0, max_deg_point=3, deg_view=2), seed=2, density_scale=30.0, bias_shift=2.0)
 
 
-def _pose_errors(p, q):
-    import math
-
-    R = p[:3, :3].double().cpu() @ q[:3, :3].double().cpu().T
-    return math.degrees(math.acos(max(-1.0, min(1.0, (R.trace().item() - 1.0) / 2.0)))), (p[:3, 3].double().cpu() - q[:3, 3].double().cpu()).norm().item()
-
-
 def test_fit_pose_recovers_a_perturbed_pose(dev):
     """One level, 8 x 12 rays, 33 coarse samples, one view, from a pose perturbed by 2.03 degrees and 0.0498.  The field: the seeded weights at
     encoding degrees (0, 3, 2) with the density bias lowered by 2 -- three position frequencies make the photometric loss smooth over the
@@ -419,7 +415,7 @@ def test_fit_pose_recovers_a_perturbed_pose(dev):
     assert all(torch.equal(a, p.detach()) for a, p in zip(before, lit.model.parameters())) and all(p.grad is None for p in lit.model.parameters())
     assert all(torch.equal(out_codes[k], codes[k]) for k in KEYS)   # fit_codes=False: the codes come back as given
     assert losses.shape == (FIT["steps"],) and losses.device.type == "cuda" and torch.isfinite(losses).all()
-    e0, e1 = _pose_errors(start, true), _pose_errors(poses[0], true)
+    e0, e1 = pose_errors(start, true), pose_errors(poses[0], true)
     print(f"fit_pose: rotation {e0[0]:.4f} -> {e1[0]:.4f} degrees, translation {e0[1]:.5f} -> {e1[1]:.5f}; losses {[f'{x:.4e}' for x in losses[:8].tolist()]}")
     assert 1.9 < e0[0] < 2.2 and 0.045 < e0[1] < 0.055
 
@@ -454,3 +450,35 @@ def test_fit_pose_recovers_a_perturbed_pose(dev):
     poses2, codes2, losses2 = lit.fit_pose([{"directions": dirs, "target": target}], 12, lr=(5e-3, 5e-3), codes=noisy, poses=[start], fit_codes=True)
     assert all(not torch.equal(codes2[k], noisy[k]) for k in KEYS) and not torch.equal(poses2[0].cpu(), start)
     assert torch.isfinite(losses2).all() and losses2[-1].item() < losses2[0].item()
+
+
+def test_views_are_independent_fits(dev):
+    """Two views fitted in one call (fit_codes=False) are the two views fitted alone, bit for bit: the network and the codes are frozen,
+    nothing is drawn, a view's 6-vector and moments (columns 6v .. 6v + 5 of the (4, 6 * views) buffer, step count i // views + 1) are
+    touched at its own steps only, and the kernels are deterministic.  One level, 32 coarse samples, degrees (0, 3, 2), 7 x 11 rays a view
+    (77 x 33 samples: a padded tail), views at azimuths 40 and 75 degrees, each started from FIT's perturbation."""
+    import aon_amd.synthetic as syn
+    from aon_amd import ops
+    from aon_amd.models.vanilla_nerf.model_autodecoder import LitNeRF_AutoDecoder
+
+    lit = LitNeRF_AutoDecoder(hparams={"N_max_objs": 2}, randomized=False, near=2.0, far=6.0, white_bkgd=True,
+                              model_kwargs=dict(num_levels=1, num_coarse_samples=32, **FIT["degrees"])).to(dev)
+    sd = syn.make_art_state_dict(seed=FIT["seed"], density_scale=FIT["density_scale"], **FIT["degrees"])
+    sd["coarse_mlp.density_layer.bias"] = sd["coarse_mlp.density_layer.bias"] - FIT["bias_shift"]
+    lit.model.load_state_dict(sd)
+    lit.code_library.load_state_dict(syn.make_code_library_state(seed=0, n_max_objs=2))
+    codes = _codes(dev, inst=1, art=3)
+    dirs = ops.ray_directions(7, 11, syn.focal_from_fovy(7), device=dev).reshape(-1, 3)
+    views, starts = [], []
+    for azimuth in (40.0, 75.0):
+        true = syn.look_at_pose(4.0, azimuth, 25.0)
+        starts.append(ops.apply_pose_correction(true.double(), torch.tensor(FIT["correction"], dtype=torch.float64)).float())
+        with torch.no_grad():
+            o, d = ops.rays_from_pose(dirs, true.to(dev))
+            views.append({"directions": dirs,
+                          "target": lit.model({"rays_o": o.contiguous(), "rays_d": d, "viewdirs": d}, False, True, 2.0, 6.0, codes)[0][0].clone()})
+    both, _, losses = lit.fit_pose(views, 6, codes=codes, poses=starts, fit_codes=False)
+    for v in range(2):
+        alone, _, l = lit.fit_pose([views[v]], 3, codes=codes, poses=[starts[v]], fit_codes=False)
+        assert torch.equal(both[v], alone[0]) and not torch.equal(alone[0].cpu(), starts[v]), v
+        assert torch.equal(losses[v::2], l), v

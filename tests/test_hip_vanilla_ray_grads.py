@@ -460,3 +460,29 @@ def test_fit_pose_recovers_a_perturbed_pose(dev):
     for i in range(8):
         assert abs(hip8[i] - l64[i]) <= max(2.0 * abs(l32[i] - l64[i]), 0.02 * l64[i]), (i, hip8[i], l64[i])
     assert e1[0] < 0.5 * e0[0] and e1[1] < 0.5 * e0[1], (e0, e1)
+
+
+def test_views_are_independent_fits(dev):
+    """Two views fitted in one call are the two views fitted alone, bit for bit: the network is frozen, nothing is drawn, a view's 6-vector
+    and moments (columns 6v .. 6v + 5 of the (4, 6 * views) buffer, step count i // views + 1) are touched at its own steps only, and the
+    kernels are deterministic.  One level, 32 coarse samples, degrees (0, 3, 2), 7 x 11 rays a view (77 x 33 samples: a padded tail), views
+    at azimuths 40 and 75 degrees, each started from FIT's perturbation."""
+    import aon_amd.synthetic as syn
+    from aon_amd import ops
+    from aon_amd.models.vanilla_nerf.model import LitNeRF
+
+    lit = LitNeRF(randomized=False, near=2.0, far=6.0, white_bkgd=True, model_kwargs=dict(num_levels=1, num_coarse_samples=32, **FIT["degrees"])).to(dev)
+    lit.model.load_state_dict(fit_pose_field())
+    dirs = ops.ray_directions(7, 11, syn.focal_from_fovy(7), device=dev).reshape(-1, 3)
+    views, starts = [], []
+    for azimuth in (40.0, 75.0):
+        true = syn.look_at_pose(4.0, azimuth, 25.0)
+        starts.append(ops.apply_pose_correction(true.double(), torch.tensor(FIT["correction"], dtype=torch.float64)).float())
+        with torch.no_grad():
+            o, d = ops.rays_from_pose(dirs, true.to(dev))
+            views.append({"directions": dirs, "target": lit.model({"rays_o": o.contiguous(), "rays_d": d, "viewdirs": d}, False, True, 2.0, 6.0)[0][0].clone()})
+    both, losses = lit.fit_pose(views, 6, poses=starts)
+    for v in range(2):
+        alone, l = lit.fit_pose([views[v]], 3, poses=[starts[v]])
+        assert torch.equal(both[v], alone[0]) and not torch.equal(alone[0].cpu(), starts[v]), v
+        assert torch.equal(losses[v::2], l), v

@@ -211,6 +211,11 @@ class RayBoundsC(C.Structure):
     _fields_ = [("near_ray", C.c_void_p), ("far_ray", C.c_void_p), ("live", C.c_void_p)]
 
 
+class SceneObjectC(C.Structure):
+    """aon_scene_object (include/aon_hip_scene.h)."""
+    _fields_ = [("rot", C.c_float * 9), ("centre", C.c_float * 3), ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
 def _ext_sigs():
     """include/aon_hip_inputs.h: the extension header's entry points, composed like the others.  Bound like _SIGS, but kept out of
     `exported_symbols()`, which lists include/aon_hip.h's names."""
@@ -221,8 +226,17 @@ def _ext_sigs():
 
 _EXT_SIGS = _ext_sigs()
 
+# include/aon_hip_scene.h: a third table, kept out of `exported_symbols()` and `extension_symbols()`
+_SCENE_SIGS = {
+    "aon_scene_pairs_workspace_bytes": (_l, [_l, _i]),
+    # rays_o, rays_d, viewdirs, n | objects_host, k | workspace, bytes | offsets, slot, pair_ray, pair_o, pair_d, pair_v, pair_near, pair_far | stream
+    "aon_scene_pairs": (_i, [_p, _p, _p, _l] + [_p, _i] + [_p, _l] + [_p] * 8 + [_p]),
+    # raw, t_vals, slot, rays_d | n, k, pairs, s, white_bkgd, act | opts | rgb, acc, depth, obj_acc, weights | stream
+    "aon_scene_composite": (_i, [_p] * 4 + [_l, _i, _l, _i, _i, _i] + [_p] + [_p] * 5 + [_p]),
+}
 
-for _name, (_res, _args) in {**_SIGS, **_EXT_SIGS}.items():
+
+for _name, (_res, _args) in {**_SIGS, **_EXT_SIGS, **_SCENE_SIGS}.items():
     _fn = getattr(lib, _name)  # AttributeError here = the .so does not export what the header declares
     _fn.restype = _res
     _fn.argtypes = _args
@@ -255,3 +269,8 @@ def exported_symbols():
 def extension_symbols():
     """the names include/aon_hip_inputs.h declares"""
     return sorted(_EXT_SIGS)
+
+
+def scene_symbols():
+    """the names include/aon_hip_scene.h declares"""
+    return sorted(_SCENE_SIGS)

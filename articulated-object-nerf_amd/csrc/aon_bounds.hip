@@ -20,14 +20,7 @@ namespace aon {
 
 constexpr int kBoxThreads = 256;
 
-__device__ __forceinline__ float torch_max(float a, float b) {
-  if (a != a || b != b) return __builtin_nanf("");
-  return a < b ? b : a;
-}
-__device__ __forceinline__ float torch_min(float a, float b) {
-  if (a != a || b != b) return __builtin_nanf("");
-  return b < a ? b : a;
-}
+// (torch_max / torch_min: aon_common.h, shared with the scene pairs)
 
 struct Box {
   float lo[3], hi[3];

@@ -398,22 +398,7 @@ struct CompositeArgs {
   float* t_fine;                      // (n,193)
 };
 
-// 1 / (1 + exp(-x)).  The compositing kernels are bound by VALU issue (SQ_INSTS_VALU: 437 wave instructions per 193-sample ray,
-// three sigmoids per sample among them), so this is the short form: e = 2^(-x log2 e) straight on the transcendental unit --
-// the rounding of the product costs |x| 4e-8 relative on e, which reaches the RESULT as at most 1e-8 absolute (e / (1 + e)^2
-// is 0.25 at x = 0, where the product is exact, and 0.0066 at |x| = 5) -- then v_rcp_f32 (1 ulp) refined by one Newton step;
-// 8 instructions against 18 with the library expf and its range fix-ups.  x < -87: e overflows, the true value is below
-// 1.7e-38 -> 0 (a NaN input fails the comparison and stays NaN).  The density's alpha = 1 - exp(-sigma delta) keeps the
-// library expf: its error goes into the transmittance product and the inverse CDF's weights.
-__device__ __forceinline__ float sigmoid_f32(float x) {
-  const float e = __builtin_amdgcn_exp2f(__fmul_rn(x, -1.44269502162933349609375f));
-  const float d = __fadd_rn(1.0f, e);
-  const float r = __builtin_amdgcn_rcpf(d);
-  const float s = __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
-  return x < -87.0f ? 0.f : s;
-}
-
-// (softplus_f32: aon_common.h, shared with the density-grid kernels)
+// (sigmoid_f32, softplus_f32: aon_common.h, shared with the density-grid kernels and the scene composite)
 
 // output activations of the two networks on one (rgb, sigma) record of sample g; everything in `ap` is wave-uniform
 __device__ __forceinline__ void activate_record(const ActParams& ap, int64_t g, float& c0, float& c1, float& c2, float& sg) {

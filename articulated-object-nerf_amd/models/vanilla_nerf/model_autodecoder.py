@@ -352,6 +352,41 @@ class LitNeRF_AutoDecoder(Harness):
         batch = self._unbatch(batch)
         return self.render_rays_test(batch, self.code_library(batch, is_test=True))
 
+    @torch.no_grad()
+    def render_scene(self, batch, placements):
+        """Several instances of the library in ONE frame (scene.render_scene): ``placements`` is a list of up to 16
+        ``(instance_id, articulation, pose, box)`` -- ``articulation`` a row index into get_interpolated_articulations (the 19 rows of the
+        test epoch) or an explicit (32,) code, ``pose`` the (3, 4) rigid object-to-world matrix, ``box`` the object's box in its own
+        frame -- and ``batch`` holds the WORLD rays ("rays_o", "rays_d", "viewdirs"; "target" / "instance_mask" are passed through when
+        present).  -> {"rgb" (N, 3), "acc" (N,), "depth" (N,), "obj_acc" (N, K)} of the last level, rendered hparams.chunk rays at a time."""
+        from ...scene import SceneObject, render_scene
+
+        dev = next(self.model.parameters()).device
+        table = self.code_library.get_interpolated_articulations(max_interpolations=2, device=dev)
+        n_inst = self.code_library.embedding_instance_shape.weight.shape[0]
+        objects = []
+        for j, placement in enumerate(placements):
+            if len(placement) != 4:
+                raise ValueError(f"render_scene: placement {j} must be (instance_id, articulation, pose, box)")
+            iid, art, pose, box = placement
+            if isinstance(iid, bool) or not isinstance(iid, int) or not 0 <= iid < n_inst:
+                raise ValueError(f"render_scene: placement {j}: instance_id {iid!r} outside the library ({n_inst} instances)")
+            if isinstance(art, int) and not isinstance(art, bool):
+                if not 0 <= art < table.shape[0]:
+                    raise ValueError(f"render_scene: placement {j}: articulation row {art} outside the {table.shape[0]} interpolated states")
+                code = table[art: art + 1]
+            else:
+                code = torch.as_tensor(art, dtype=torch.float32, device=dev).reshape(1, -1)
+            ids = torch.tensor([iid], dtype=torch.int64, device=dev)
+            latents = {"density": self.code_library.embedding_instance_shape(ids), "color": self.code_library.embedding_instance_appearance(ids),
+                       "articulation": code}
+            objects.append(SceneObject(latents, pose, box))
+        rays = {k: batch[k].reshape(-1, 3) for k in ("rays_o", "rays_d", "viewdirs")}
+        rgb, acc, depth, obj_acc = render_scene(self.model, objects, rays, self.white_bkgd, chunk=self.hparams.chunk)[-1]
+        ret = {"rgb": rgb, "acc": acc, "depth": depth, "obj_acc": obj_acc}
+        ret.update({k: batch[k] for k in ("target", "instance_mask") if k in batch})
+        return ret
+
     def configure_optimizers(self):
         return build_adam([self.model, self.code_library], self.lr_init)   # (model_autodecoder.py:604-606; one arena, one launch: LitNeRF)
 

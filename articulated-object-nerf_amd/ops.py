@@ -824,10 +824,17 @@ def vanilla_pack_step(params_c: dict, params_f: dict, degrees=(0, 10, 4), with_b
     return [(_tag(pk[l]), None if bw[l] is None else _tag(bw[l])) for l in range(2)]
 
 
-def art_mlp_fwd(packed, small, rays_o, rays_d, viewdirs, t_vals):
+def art_mlp_fwd(packed, small, rays_o, rays_d, viewdirs, t_vals, out=None):
+    """``out``: a contiguous fp32 (n, S, 4) tensor to write instead of a fresh one (a slice of a larger buffer: ops.scene_pairs' segments)."""
     o, d, v, t = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs"), _f32(t_vals, "t_vals")
     n, S = t.shape
-    raw = torch.empty((n, S, 4), dtype=torch.float32, device=t.device)
+    if out is None:
+        raw = torch.empty((n, S, 4), dtype=torch.float32, device=t.device)
+    else:
+        raw = out
+        if not (isinstance(raw, torch.Tensor) and raw.dtype == torch.float32 and tuple(raw.shape) == (n, S, 4) and raw.device == t.device
+                and raw.is_contiguous()):
+            raise ValueError(f"art_mlp_fwd: out must be a contiguous float32 ({n}, {S}, 4) tensor on {t.device}")
     with torch.cuda.device(t.device):
         check(lib.aon_art_mlp_fwd(_pk(packed), _pk(small), _ptr(o), _ptr(d), _ptr(v), _ptr(t), n, S, _ptr(raw), _stream()),
               "aon_art_mlp_fwd")
@@ -1903,3 +1910,120 @@ def art_render_fwd_stop(packed_c, small_c, packed_f, small_f, rays_o, rays_d, vi
     """art_render_fwd with the occupancy skip and early termination of render_fwd_stop -> (levels, occupied, stop)."""
     return _stop_call("aon_art_render_fwd_stop", (_pk(packed_c), _pk(small_c), _pk(packed_f), _pk(small_f)), rays_o, rays_d, viewdirs, near, far,
                       white_bkgd, grid, eps, round_samples, num_levels, u, opts, workspace_bytes, ray_live=ray_live)
+
+
+# ------------------------------------------------------------------ scenes of several posed objects (DESIGN.md section 4.16)
+SCENE_MAX_OBJECTS, SCENE_MAX_MERGED = 16, 4096
+_SCENE_WS = StreamCache()
+
+
+def check_pose(pose, what: str = "pose") -> torch.Tensor:
+    """A rigid object-to-world pose -> its (3, 4) fp32 host tensor [R | c].  R must be orthonormal (max |R^T R - I| <= 1e-5) with
+    det > 0: there is no scale, so a ray's parameter t means the same distance in every frame."""
+    m = torch.as_tensor(pose).detach().to(device="cpu", dtype=torch.float32)
+    if tuple(m.shape) != (3, 4):
+        raise ValueError(f"{what}: expected a (3, 4) object-to-world matrix, got shape {tuple(m.shape)}")
+    R = m[:, :3].double()
+    err = float((R.T @ R - torch.eye(3, dtype=torch.float64)).abs().max())
+    if not err <= 1e-5:
+        raise ValueError(f"{what}: the rotation is not orthonormal (max |R^T R - I| = {err:.3g} > 1e-5; scaled or sheared placements are not supported)")
+    if not float(torch.linalg.det(R)) > 0:
+        raise ValueError(f"{what}: the rotation has a negative determinant (a reflection)")
+    return m.contiguous()
+
+
+def _scene_objects(objects):
+    """[(pose, box) or anything with .pose / .box] -> (aon_scene_object array, K)"""
+    objects = list(objects)
+    if not 1 <= len(objects) <= SCENE_MAX_OBJECTS:
+        raise ValueError(f"a scene holds 1 to {SCENE_MAX_OBJECTS} objects, got {len(objects)}")
+    arr = (_lib.SceneObjectC * len(objects))()
+    for k, ob in enumerate(objects):
+        pose, box = (ob.pose, ob.box) if hasattr(ob, "pose") else ob
+        m = check_pose(pose, f"object {k}: pose")
+        lo, hi = _box3(box)
+        arr[k].rot[:] = m[:, :3].reshape(-1).tolist()
+        arr[k].centre[:] = m[:, 3].tolist()
+        arr[k].lo[:] = list(lo)
+        arr[k].hi[:] = list(hi)
+    return arr, len(objects)
+
+
+class ScenePairs:
+    """What aon_scene_pairs wrote for n rays and K objects, the per-pair arrays cut to the P live pairs: `offsets` (K + 1,) int64 on the
+    device, `counts` the K segment lengths on the host (read back once: the single synchronisation of a chunk), `slot` (n, K) int32,
+    `ray` (P,) int32, `rays_o` / `rays_d` / `viewdirs` (P, 3) in the objects' frames, `near` / `far` (P,).  Object k's rows are
+    `segment(k)`.  `capacity`: the same six arrays at the n * K rows they were allocated with (rows from P on are not written)."""
+
+    def __init__(self, n, K, offsets, counts, slot, ray, rays_o, rays_d, viewdirs, near, far):
+        self.n, self.K, self.offsets, self.counts, self.slot = n, K, offsets, counts, slot
+        self.starts = [sum(counts[:k]) for k in range(K + 1)]
+        self.P = P = self.starts[K]
+        self.capacity = {"ray": ray, "rays_o": rays_o, "rays_d": rays_d, "viewdirs": viewdirs, "near": near, "far": far}
+        self.ray, self.rays_o, self.rays_d, self.viewdirs, self.near, self.far = ray[:P], rays_o[:P], rays_d[:P], viewdirs[:P], near[:P], far[:P]
+
+    def segment(self, k: int) -> slice:
+        return slice(self.starts[k], self.starts[k + 1])
+
+
+def scene_pairs(rays_o, rays_d, viewdirs, objects) -> ScenePairs:
+    """Pair every world ray with the objects ([(pose (3, 4) object-to-world, box as ops._box3 takes it)], or scene.SceneObject) whose box
+    it crosses, compacted object-major (include/aon_hip_scene.h)."""
+    o, d, v = (_f32(x.detach(), nm).reshape(-1, 3) for x, nm in ((rays_o, "rays_o"), (rays_d, "rays_d"), (viewdirs, "viewdirs")))
+    n, dev = o.shape[0], o.device
+    if d.shape[0] != n or v.shape[0] != n:
+        raise ValueError("rays_o, rays_d and viewdirs must hold the same number of rays")
+    arr, K = _scene_objects(objects)
+    cap = n * K
+    if n == 0:      # nothing to launch (and no pointer to hand over)
+        e = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)   # noqa: E731
+        return ScenePairs(0, K, torch.zeros((K + 1,), dtype=torch.int64, device=dev), [0] * K, e(0, K, dtype=torch.int32), e(0, dtype=torch.int32),
+                          e(0, 3), e(0, 3), e(0, 3), e(0), e(0))
+    offsets = torch.empty((K + 1,), dtype=torch.int64, device=dev)
+    slot = torch.empty((n, K), dtype=torch.int32, device=dev)
+    ray = torch.empty((cap,), dtype=torch.int32, device=dev)
+    po, pd, pv = (torch.empty((cap, 3), dtype=torch.float32, device=dev) for _ in range(3))
+    near, far = (torch.empty((cap,), dtype=torch.float32, device=dev) for _ in range(2))
+    ws = _scratch(_SCENE_WS, dev, int(lib.aon_scene_pairs_workspace_bytes(n, K)))
+    with torch.cuda.device(dev):
+        check(lib.aon_scene_pairs(_ptr(o), _ptr(d), _ptr(v), n, arr, K, _ptr(ws), ws.numel(), _ptr(offsets), _ptr(slot), _ptr(ray), _ptr(po), _ptr(pd),
+                                  _ptr(pv), _ptr(near), _ptr(far), _stream()), "aon_scene_pairs")
+    starts = offsets.tolist()
+    return ScenePairs(n, K, offsets, [starts[k + 1] - starts[k] for k in range(K)], slot, ray, po, pd, pv, near, far)
+
+
+def scene_composite(raw, t_vals, pairs: ScenePairs, rays_d, white_bkgd, opts=None, want_weights=True, act=ACT_ARTICULATED):
+    """Merge the live sample lists of every ray by distance and composite them (include/aon_hip_scene.h): raw (P, S, 4) and t_vals (P, S)
+    in `pairs`' row layout, rays_d the WORLD directions (n, 3) -> (rgb (n, 3), acc (n,), depth (n,), obj_acc (n, K), weights (P, S) or None)."""
+    d = _f32(rays_d.detach(), "rays_d").reshape(-1, 3)
+    n, K, P, dev = pairs.n, pairs.K, pairs.P, d.device
+    t = _f32(t_vals, "t_vals")
+    r = _f32(raw, "raw")
+    S = t.shape[-1]
+    if d.shape[0] != n or tuple(t.shape) != (P, S) or tuple(r.shape) != (P, S, 4):
+        raise ValueError(f"scene_composite: expected rays_d ({n}, 3), t_vals ({P}, S) and raw ({P}, S, 4), got {tuple(d.shape)}, {tuple(t.shape)}, {tuple(r.shape)}")
+    st, _keep = _opts(opts).c_struct(1.0, 1.0)
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    acc, depth = (torch.empty((n,), dtype=torch.float32, device=dev) for _ in range(2))
+    obj_acc = torch.empty((n, K), dtype=torch.float32, device=dev)
+    weights = torch.empty((P, S), dtype=torch.float32, device=dev) if want_weights else None
+    if n == 0:      # nothing to launch (and no pointer to hand over)
+        return rgb, acc, depth, obj_acc, weights
+    with torch.cuda.device(dev):
+        check(lib.aon_scene_composite(_ptr(r) if P else None, _ptr(t) if P else None, _ptr(pairs.slot), _ptr(d), n, K, P, S, int(bool(white_bkgd)), act,
+                                      C.byref(st), _ptr(rgb), _ptr(acc), _ptr(depth), _ptr(obj_acc), _ptr(weights), _stream()), "aon_scene_composite")
+    return rgb, acc, depth, obj_acc, weights
+
+
+def scene_art_mlp_fwd(packed, smalls, pairs: ScenePairs, t_vals) -> torch.Tensor:
+    """aon_art_mlp_fwd on every object's segment of `pairs` with that object's per-call block (`smalls[k]`, ops.art_prepare) -> one
+    (P, S, 4) buffer in the pairs' row layout.  An object without a pair costs no launch."""
+    t = _f32(t_vals, "t_vals")
+    if len(smalls) != pairs.K or t.shape[0] != pairs.P:
+        raise ValueError(f"scene_art_mlp_fwd: expected {pairs.K} per-call blocks and t_vals of {pairs.P} rows")
+    raw = torch.empty((pairs.P, t.shape[1], 4), dtype=torch.float32, device=t.device)
+    for k in range(pairs.K):
+        seg = pairs.segment(k)
+        if seg.stop > seg.start:
+            art_mlp_fwd(packed, smalls[k], pairs.rays_o[seg], pairs.rays_d[seg], pairs.viewdirs[seg], t[seg], out=raw[seg])
+    return raw

@@ -19,8 +19,7 @@
 //     read their A operands with conflict-free ds_read_b128 (4 MFMA steps per read).
 //   * per 128-sample pass a wave issues ~9.3k MFMAs (64 cycles each) against ~2.4k ds_read_b128 and a few
 //     hundred VALU ops (bias init, ReLU, heads), so the kernel is bound by the fp32 matrix pipe.
-#include "aon_launch.h"
-#include "aon_mlp_core.h"
+#include "aon_pass.h"
 
 namespace aon {
 
@@ -141,13 +140,22 @@ struct MlpSeg {
   };
   int64_t Np;                // npass * 128
   const float* view_bias;    // [VB] (n_rays,128): b' + W_v0[:, 256:] ve of the ray (view_bias_kernel)
+  static constexpr bool kPerCallBlock = false;   // the small block follows the stream
 };
 struct MlpArgs {
   MlpSeg seg[2];
   int npass_total;           // seg[0].npass + seg[1].npass (seg[1].npass == 0: a one-segment launch)
 };
+__host__ __device__ __forceinline__ const char* seg_stream(const MlpSeg& s) { return s.packed; }
+__device__ __forceinline__ const float* seg_small(const MlpSeg& s) { return reinterpret_cast<const float*>(s.packed + kStreamBytes); }
 
 constexpr int kLdsBytes = kRingBytes + (int)kSmallBytes;
+
+struct VanillaTrunk {   // trunk_fwd's view of the vanilla stream, small block, planes and decision bits
+  static constexpr int kL0 = kChL0, kL1 = kChL1, kL5 = kChL5, kL6 = kChL6, kL7 = kChL7;
+  static constexpr int kBias = kSmBias, kWSigma = kSmWSigma, kBSigma = kSmBSigma, kMask0 = 0;
+  static constexpr int plane(int l) { return plane_h(l); }
+};
 
 // TRAIN additionally stores every layer's input/output activations as step-major planes (aon_mlp_core.h) for the backward pass.
 // FOLD: the stream is the folded form -- the view layer reads the post-ReLU layer-7 output through W' (aon_common.h), there is no
@@ -163,43 +171,12 @@ __global__ void __launch_bounds__(256) mlp_fwd_kernel(MlpArgs args) {
   using Net = std::conditional_t<VB, VanillaFoldVbNet, std::conditional_t<FOLD, VanillaFoldNet, VanillaNet>>;
   // <false, true>: training on caller-encoded inputs (other encoding degrees in the padded 63 / 27-slot layout): where the
   // in-kernel form re-encodes from x[] / vd[], this one re-reads the encodings.
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* sm = reinterpret_cast<float*>(smem + kRingBytes);
-
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int m = lane & 31, h = lane >> 5;
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);   // the step base of the training planes is wave-uniform: keep it scalar
 
-  // [GATHER] one segment; its pass count is the occupancy list's
-  const int64_t listed = GATHER ? *args.seg[0].gather_count : 0;
-  const int npass0 = GATHER ? (int)((listed + 127) / 128) : args.seg[0].npass;
-  int cur = (int)blockIdx.x >= npass0 ? 1 : 0;               // segment of this workgroup's first pass
-  auto load_small = [&](const char* packed) {  // resident small vectors -> LDS (visible after the next workgroup barrier)
-    const f32x4* src = reinterpret_cast<const f32x4*>(packed + kStreamBytes);
-    f32x4* dst = reinterpret_cast<f32x4*>(sm);
-    for (int i = tid; i < kSmallFloats / 4; i += 256) dst[i] = src[i];
-  };
-  load_small(args.seg[cur].packed);
-
-  Pipe p;
-  pipe_init<Net>(p, args.seg[cur].packed, smem, wave, lane);  // also publishes the small block just written to LDS
-
-  for (int gpass = blockIdx.x; gpass < (GATHER ? npass0 : args.npass_total); gpass += gridDim.x) {
-    const int si = gpass >= npass0 ? 1 : 0;
-    if (si != cur) {   // (workgroup-uniform, at most once per launch) the other network's biases / head weights replace the resident block
-      __syncthreads();
-      load_small(args.seg[si].packed);
-      __syncthreads();
-      cur = si;
-    }
-    const MlpSeg& sg = args.seg[si];
-    const int pass = gpass - (si ? npass0 : 0);
-    {   // weight stream of this pass, and of this workgroup's next one (its first chunk pair is fetched during this pass's last chunk)
-      const int nxt = gpass + (int)gridDim.x;
-      p.stream = sg.packed;
-      p.next_stream = args.seg[(nxt >= npass0 && nxt < (GATHER ? npass0 : args.npass_total)) ? 1 : si].packed;
-    }
+  run_passes<Net, kSmallFloats, GATHER>(args, [&](const MlpSeg& sg, int pass, Pipe& p, const float* sm, int64_t listed = 0) __attribute__((always_inline)) {
     int64_t g = (int64_t)pass * 128 + wave * 32 + m;
     bool valid;
     int64_t gc;
@@ -239,84 +216,26 @@ __global__ void __launch_bounds__(256) mlp_fwd_kernel(MlpArgs args) {
       store_pos_enc_plane(E, io, kPlE, h);
       store_view_enc_plane(V, io, kPlVE, h);
     }
-    // [TRAIN] Every hidden activation tile is stored, and its ReLU decision bits are collected, by the chunk that CONSUMES
-    // it (side job of chunk_mma: one value per MFMA group, one 16-byte store per four), so neither a store burst nor a block of
-    // mask arithmetic sits at a layer boundary.  `in_row` = plane row of input tile 0; `with_mask` false: the bottleneck output
-    // has no activation.
-    auto consume = [&](const f32x16 (&in)[8], int in_row, u32x4& mw, bool with_mask) {
-      return [&, in_row, with_mask](int j) {
-        return [&, in_row, with_mask, j](int i) {
-          if constexpr (TRAIN) {
-            if (i < 16) {
-              if ((i & 3) == 0) store_quad<false>(io, in_row + 32 * j, i >> 2, in[j]);
-              if (with_mask) mw[j >> 1] = mask_push_post(mw[j >> 1], in[j][i]);
-            }
-          }
-        };
-      };
+    FwdTaps<TRAIN, MlpSeg> taps{sg, io, moff};   // [TRAIN] planes and decision bits, as side jobs of the consuming chunks
+    f32x16 X[8], Y[8], Z[4];
+    // (the in-kernel encoding stays live across layers 1-4, 32 registers, as in the inference kernel: with the view encoding gone from the
+    // trunk every form builds with 0 scratch, and re-encoding at layer 5 -- 30 sines -- was the slower way: see art_mlp_fwd_kernel)
+    auto reread_enc = [&]() {
+      if constexpr (TRAIN && !ENC_IN_KERNEL) {
+        int64_t gq = gc;
+        asm volatile("" : "+v"(gq));   // opaque: a second read, not the first one kept live
+        load_pos_enc(sg.samples_enc + gq * kPosEnc, h, E);
+      }
     };
-    auto put_mask = [&](const u32x4& mw, int mask_layer) {   // all 8 tiles (32 pushes per word) of the layer have been consumed
-      if constexpr (TRAIN)
-        *mask_ptr(sg.masks, sg.Np, mask_layer, moff) = u32x4{mask_word_finish(mw[0]), mask_word_finish(mw[1]), mask_word_finish(mw[2]), mask_word_finish(mw[3])};
+    auto l7_side = [&](auto plain) {
+      if constexpr (VB) {
+        asm volatile("" : "+v"(ray32));
+        return view_bias_side(plain, sg.view_bias + (int64_t)ray32 * kCondWidth + 4 * h, Z);
+      } else {
+        return plain;
+      }
     };
-    f32x16 X[8], Y[8];
-    u32x4 mw;
-    // L0: enc(63) -> 256
-    init_bias(X, sm + kSmBias + 0 * 256, h);
-    chunk_mma<Net, kChL0 + 0, 8, 16>(p, E[0], X);
-    chunk_mma<Net, kChL0 + 1, 8, 16>(p, E[1], X);
-    relu_tiles(X);
-    // L1..L4
-    mw = u32x4{0u, 0u, 0u, 0u}; init_bias(Y, sm + kSmBias + 1 * 256, h); dense_layer<Net, kChL1 + 0, 8, 8>(p, X, Y, consume(X, plane_h(0), mw, true)); put_mask(mw, 0); relu_tiles(Y);
-    mw = u32x4{0u, 0u, 0u, 0u}; init_bias(X, sm + kSmBias + 2 * 256, h); dense_layer<Net, kChL1 + 8, 8, 8>(p, Y, X, consume(Y, plane_h(1), mw, true)); put_mask(mw, 1); relu_tiles(X);
-    mw = u32x4{0u, 0u, 0u, 0u}; init_bias(Y, sm + kSmBias + 3 * 256, h); dense_layer<Net, kChL1 + 16, 8, 8>(p, X, Y, consume(X, plane_h(2), mw, true)); put_mask(mw, 2); relu_tiles(Y);
-    mw = u32x4{0u, 0u, 0u, 0u}; init_bias(X, sm + kSmBias + 4 * 256, h); dense_layer<Net, kChL1 + 24, 8, 8>(p, Y, X, consume(Y, plane_h(3), mw, true)); put_mask(mw, 3); relu_tiles(X);
-    // L5: cat[h(256), enc(63)] -> 256     (model.py:102-103: concat after layer 4's ReLU)
-    mw = u32x4{0u, 0u, 0u, 0u}; init_bias(Y, sm + kSmBias + 5 * 256, h);
-    dense_layer<Net, kChL5, 8, 8>(p, X, Y, consume(X, plane_h(4), mw, true)); put_mask(mw, 4);
-    // (the in-kernel encoding stays live across layers 1-4, 32 registers, as in the inference kernel; rounds 2-4 re-encoded it here:
-    // see art_mlp_fwd_kernel)
-#ifdef AON_TRAIN_REENCODE
-    if constexpr (TRAIN && ENC_IN_KERNEL) {  // (x made opaque: otherwise the two identical encodings are merged and the first stays live)
-      asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]));
-      encode_pos(x, h, E);
-    }
-#endif
-    if constexpr (TRAIN && !ENC_IN_KERNEL) {
-      int64_t gq = gc;
-      asm volatile("" : "+v"(gq));   // opaque: a second read, not the first one kept live
-      load_pos_enc(sg.samples_enc + gq * kPosEnc, h, E);
-    }
-    chunk_mma<Net, kChL5 + 8, 8, 16>(p, E[0], Y);
-    chunk_mma<Net, kChL5 + 9, 8, 16>(p, E[1], Y);
-    relu_tiles(Y);
-    // L6, L7
-    mw = u32x4{0u, 0u, 0u, 0u}; init_bias(X, sm + kSmBias + 6 * 256, h); dense_layer<Net, kChL6, 8, 8>(p, Y, X, consume(Y, plane_h(5), mw, true)); put_mask(mw, 5); relu_tiles(X);
-    f32x16 Z[4];
-    mw = u32x4{0u, 0u, 0u, 0u}; init_bias(Y, sm + kSmBias + 7 * 256, h);
-    if constexpr (VB) {
-      // the ray's view bias straight into the view layer's accumulators, one 16-byte load per side slot of layer 7's LAST chunk (tiles 0 .. 6
-      // of X are dead by then): a chunk of MFMAs (3.4 us) between the loads and their first use
-      asm volatile("" : "+v"(ray32));
-      const float* vb = sg.view_bias + (int64_t)ray32 * kCondWidth + 4 * h;
-      auto l7_side = [&](int j) {
-        auto base = consume(X, plane_h(6), mw, true)(j);
-        return [&, base, j, vb](int i) {
-          base(i);
-          if (j == 7 && i < 16) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(vb + 32 * (i >> 2) + 8 * (i & 3));
-            Z[i >> 2][4 * (i & 3)] = v[0]; Z[i >> 2][4 * (i & 3) + 1] = v[1]; Z[i >> 2][4 * (i & 3) + 2] = v[2]; Z[i >> 2][4 * (i & 3) + 3] = v[3];
-          }
-        };
-      };
-      dense_layer<Net, kChL7, 8, 8>(p, X, Y, l7_side);
-    } else {
-      dense_layer<Net, kChL7, 8, 8>(p, X, Y, consume(X, plane_h(6), mw, true));
-    }
-    put_mask(mw, 6); relu_tiles(Y);
-    // density head (model.py:105) on the post-ReLU layer-7 output
-    float sigma = head_partial<8>(Y, sm + kSmWSigma, h);
-    sigma = sigma + __shfl_xor(sigma, 32) + sm[kSmBSigma];
+    const float sigma = trunk_fwd<Net, VanillaTrunk>(p, E, X, Y, sm, h, taps, reread_enc, l7_side);
     constexpr int kChV = FOLD ? kChFView : kChView;
     auto reencode_view = [&]() {   // [TRAIN] the view encoding again (same function, same bits): 16 registers not held across the trunk
       if constexpr (TRAIN && ENC_IN_KERNEL) {
@@ -332,27 +251,23 @@ __global__ void __launch_bounds__(256) mlp_fwd_kernel(MlpArgs args) {
     if constexpr (FOLD) {
       // bottleneck (no activation, model.py:109) and the view layer's hidden columns (model.py:110-116) as ONE layer W' = W_v0[:, :256] W_b,
       // b' = W_v0[:, :256] b_b + b_v0 on the post-ReLU layer-7 output; the view-encoding columns FIRST (chunk form) or already in Z (VB)
-      mw = u32x4{0u, 0u, 0u, 0u};
       if constexpr (!VB) {
         init_bias(Z, sm + kSmBiasView, h);
         reencode_view();
         chunk_mma<Net, kChV, 4, 14>(p, V, Z);
       }
-      dense_layer<Net, kChV + (VB ? 0 : 1), 8, 4>(p, Y, Z, consume(Y, plane_h(7), mw, true)); put_mask(mw, 7);
+      dense_layer<Net, kChV + (VB ? 0 : 1), 8, 4>(p, Y, Z, taps.consume(Y, plane_h(7), true)); taps.put_mask(7);
     } else {
       // bottleneck, no activation (model.py:109)
-      mw = u32x4{0u, 0u, 0u, 0u}; init_bias(X, sm + kSmBiasBott, h); dense_layer<Net, kChBott, 8, 8>(p, Y, X, consume(Y, plane_h(7), mw, true)); put_mask(mw, 7);
+      init_bias(X, sm + kSmBiasBott, h); dense_layer<Net, kChBott, 8, 8>(p, Y, X, taps.consume(Y, plane_h(7), true)); taps.put_mask(7);
       // view branch: cat[bottleneck(256), viewenc(27)] -> 128, ReLU (model.py:110-116)
       init_bias(Z, sm + kSmBiasView, h);
-      dense_layer<Net, kChV, 8, 4>(p, X, Z, consume(X, kPlBot, mw, false));
+      dense_layer<Net, kChV, 8, 4>(p, X, Z, taps.consume(X, kPlBot, false));
       reencode_view();
       chunk_mma<Net, kChV + 8, 4, 14>(p, V, Z);
     }
     relu_tiles(Z);
-    if constexpr (TRAIN) {  // the view layer's output feeds the rgb head on the VALU: no consuming chunk, 64 values stored here
-      *mask_ptr(sg.masks, sg.Np, 8, moff) = relu_mask_bits(Z);   // burst form: already in the stored bit layout
-      store_plane(Z, io, kPlHV);
-    }
+    taps.burst(Z, kPlHV, 8);   // the view layer's output feeds the rgb head on the VALU
     // rgb head (model.py:118)
     float rgb[3];
 #pragma unroll
@@ -364,8 +279,7 @@ __global__ void __launch_bounds__(256) mlp_fwd_kernel(MlpArgs args) {
       f32x4 o; o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2]; o[3] = sigma;
       reinterpret_cast<f32x4*>(sg.raw)[g] = o;
     }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last prefetched chunk must land before the LDS is released
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -415,29 +329,18 @@ int num_cus() {  // CUs of the CURRENT device, cached per device ordinal (ops.py
 template <bool ENC, bool TRAIN, bool FOLD, bool VB = false, bool GATHER = false>
 static hipError_t launch_mlp_tf(const MlpArgs& args, hipStream_t stream) {
   static DeviceOnce lds_once;  // one per template instance
-  if (hipError_t e = set_max_lds(&mlp_fwd_kernel<ENC, TRAIN, FOLD, VB, GATHER>, kLdsBytes, lds_once); e != hipSuccess) return e;
-  const int g_num_cus = num_cus();
-  if (g_num_cus <= 0) return hipErrorInvalidDevice;
-  const int grid = args.npass_total < g_num_cus ? args.npass_total : g_num_cus;   // [GATHER] npass_total: the passes of a full list
-  if (grid <= 0) return hipSuccess;
-  mlp_fwd_kernel<ENC, TRAIN, FOLD, VB, GATHER><<<dim3(grid), dim3(256), kLdsBytes, stream>>>(args);
-  return hipGetLastError();
+  return launch_persistent(&mlp_fwd_kernel<ENC, TRAIN, FOLD, VB, GATHER>, kLdsBytes, args.npass_total, lds_once, stream, args);   // [GATHER] npass_total: the passes of a full list
 }
 
-// the kernel of the form the launch's streams were packed in; the segments of one launch must agree
+// the kernel of the form the launch's streams were packed in (agreed_form); the per-ray view bias serves the whole-path calls on the
+// in-kernel encodings
 template <bool ENC, bool TRAIN, bool GATHER = false>
 static hipError_t launch_mlp_t(const MlpArgs& args, hipStream_t stream) {
-  const int form = stream_form(args.seg[0].packed);
-  if (form == kFormUnknown) return hipErrorInvalidValue;   // never packed / declared (a copy): refuse instead of guessing
-  if (args.seg[1].npass > 0 && stream_form(args.seg[1].packed) != form) return hipErrorInvalidValue;
-  // the per-ray view bias: every segment of the launch or none (whole-path calls on the in-kernel encodings; folded form only)
-  const bool vb = args.seg[0].view_bias != nullptr;
-  if (args.seg[1].npass > 0 && (args.seg[1].view_bias != nullptr) != vb) return hipErrorInvalidValue;
-  if (vb && form != kFormFolded) return hipErrorInvalidValue;
-  if constexpr (ENC) {
-    if (vb) return launch_mlp_tf<ENC, TRAIN, true, true, GATHER>(args, stream);
-  } else {
-    if (vb) return hipErrorInvalidValue;
+  const int form = agreed_form(args);
+  if (form == kFormUnknown) return hipErrorInvalidValue;
+  if (args.seg[0].view_bias != nullptr) {
+    if constexpr (ENC) return launch_mlp_tf<ENC, TRAIN, true, true, GATHER>(args, stream);
+    else return hipErrorInvalidValue;
   }
   return form == kFormFolded ? launch_mlp_tf<ENC, TRAIN, true, false, GATHER>(args, stream)
                              : launch_mlp_tf<ENC, TRAIN, false, false, GATHER>(args, stream);
@@ -497,10 +400,8 @@ hipError_t launch_view_bias(const char* packed, const float* viewdirs, int64_t n
 hipError_t launch_mlp_fwd(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs,
                           const float* t_vals, int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias) {
   MlpArgs args{};
-  MlpSeg& a = args.seg[0];
-  a.packed = packed; a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.t_vals = t_vals; a.view_bias = view_bias;
-  a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)((a.total + 127) / 128);
-  args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
+  fill_seg(args.seg[0], TrainSeg{packed, nullptr, rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, nullptr, nullptr, 0, view_bias});
+  finish_segs(args, 1);
   return launch_mlp_t<true, false>(args, stream);
 }
 
@@ -511,10 +412,10 @@ hipError_t launch_mlp_fwd_gather(const char* packed, const float* rays_o, const 
                                  int64_t max_listed) {
   MlpArgs args{};
   MlpSeg& a = args.seg[0];
-  a.packed = packed; a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.t_vals = t_vals; a.view_bias = view_bias;
-  a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)(((max_listed > 0 ? max_listed : a.total) + 127) / 128);
+  fill_seg(a, TrainSeg{packed, nullptr, rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, nullptr, nullptr, 0, view_bias});
+  if (max_listed > 0) a.npass = (int)((max_listed + 127) / 128);
   a.gather_idx = idx; a.gather_count = count;
-  args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
+  finish_segs(args, 1);
   return launch_mlp_t<true, false, true>(args, stream);
 }
 
@@ -532,17 +433,8 @@ hipError_t launch_mlp_fwd_train(const char* packed, const float* rays_o, const f
 hipError_t launch_mlp_fwd_train2(const TrainSeg* segs, int nsegs, hipStream_t stream) {
   if (nsegs < 1 || nsegs > 2) return hipErrorInvalidValue;
   MlpArgs args{};
-  for (int i = 0; i < nsegs; ++i) {
-    const TrainSeg& t = segs[i];
-    MlpSeg& a = args.seg[i];
-    a.packed = t.packed; a.rays_o = t.rays_o; a.rays_d = t.rays_d; a.viewdirs = t.viewdirs; a.t_vals = t.t_vals;
-    a.raw = t.raw; a.total = t.n_rays * t.S; a.S = t.S; a.npass = (int)((a.total + 127) / 128);
-    a.planes = t.planes; a.masks = static_cast<u32x4*>(t.masks); a.Np = t.np_total > 0 ? t.np_total : (int64_t)a.npass * 128;
-    a.view_bias = t.view_bias;
-    args.npass_total += a.npass;
-  }
-  if (nsegs == 1) { args.seg[1] = args.seg[0]; args.seg[1].npass = 0; }
-  else if (args.seg[0].npass == 0) { args.seg[0] = args.seg[1]; args.seg[1].npass = 0; }   // (an empty first segment: the second one alone)
+  for (int i = 0; i < nsegs; ++i) fill_seg(args.seg[i], segs[i]);
+  finish_segs(args, nsegs);
   return launch_mlp_t<true, true>(args, stream);
 }
 
@@ -550,21 +442,18 @@ hipError_t launch_mlp_fwd_train2(const TrainSeg* segs, int nsegs, hipStream_t st
 hipError_t launch_mlp_fwd_train_enc(const char* packed, const float* samples_enc, const float* viewdirs_enc, int64_t n_rays, int S, float* raw,
                                     float* planes, void* masks, hipStream_t stream, int64_t np_total) {
   MlpArgs args{};
-  MlpSeg& a = args.seg[0];
-  a.packed = packed; a.samples_enc = samples_enc; a.viewdirs_enc = viewdirs_enc;
-  a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)((a.total + 127) / 128);
-  a.planes = planes; a.masks = static_cast<u32x4*>(masks); a.Np = np_total > 0 ? np_total : (int64_t)a.npass * 128;
-  args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
+  fill_seg(args.seg[0], TrainSeg{packed, nullptr, nullptr, nullptr, nullptr, nullptr, n_rays, S, raw, planes, masks, np_total});
+  args.seg[0].samples_enc = samples_enc; args.seg[0].viewdirs_enc = viewdirs_enc;
+  finish_segs(args, 1);
   return launch_mlp_t<false, true>(args, stream);
 }
 
 hipError_t launch_mlp_fwd_enc(const char* packed, const float* samples_enc, const float* viewdirs_enc,
                               int64_t n_rays, int S, float* raw, hipStream_t stream) {
   MlpArgs args{};
-  MlpSeg& a = args.seg[0];
-  a.packed = packed; a.samples_enc = samples_enc; a.viewdirs_enc = viewdirs_enc;
-  a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)((a.total + 127) / 128);
-  args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
+  fill_seg(args.seg[0], TrainSeg{packed, nullptr, nullptr, nullptr, nullptr, nullptr, n_rays, S, raw, nullptr, nullptr, 0});
+  args.seg[0].samples_enc = samples_enc; args.seg[0].viewdirs_enc = viewdirs_enc;
+  finish_segs(args, 1);
   return launch_mlp_t<false, false>(args, stream);
 }
 
@@ -582,67 +471,31 @@ struct VanillaTrunkNet {
 
 // (GridArgs, grid_point, grid_activation, grid_store: aon_mlp_core.h)
 
-// encode -> trunk -> density head of mlp_fwd_kernel, the same operations in the same order (the same bits as its raw sigma), on points
-// generated from the grid; no view encoding, view branch or rgb head.  One wave = 32 grid points, as there.
+// encode -> trunk -> density head of mlp_fwd_kernel -- the same trunk_fwd, so the same operations in the same order and the same bits as
+// its raw sigma -- on points generated from the grid; no view encoding, view branch or rgb head.  One wave = 32 grid points, as there.
 __global__ void __launch_bounds__(256) density_grid_kernel(GridArgs args) {
-  using Net = VanillaTrunkNet;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* sm = reinterpret_cast<float*>(smem + kRingBytes);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int m = lane & 31, h = lane >> 5;
-  {
-    const f32x4* src = reinterpret_cast<const f32x4*>(args.packed + kStreamBytes);
-    f32x4* dst = reinterpret_cast<f32x4*>(sm);
-    for (int i = tid; i < kSmallFloats / 4; i += 256) dst[i] = src[i];
-  }
-  Pipe p;
-  pipe_init<Net>(p, args.packed, smem, wave, lane);  // also publishes the small block
-  for (int pass = blockIdx.x; pass < args.npass; pass += gridDim.x) {
+  run_passes_one<VanillaTrunkNet, kSmallFloats>(args.packed, reinterpret_cast<const float*>(args.packed + kStreamBytes), args.npass,
+                                                [&](int pass, Pipe& p, const float* sm) __attribute__((always_inline)) {
     const int64_t l0 = (int64_t)pass * 128 + wave * 32;
     const int64_t l = l0 + m;
     float x[3];
     grid_point(args, l < args.total ? l : args.total - 1, x);
-    f32x16 E[2];
+    f32x16 E[2], X[8], Y[8];
     encode_pos(x, h, E);
-    f32x16 X[8], Y[8];
-    init_bias(X, sm + kSmBias + 0 * 256, h);
-    chunk_mma<Net, kChL0 + 0, 8, 16>(p, E[0], X);
-    chunk_mma<Net, kChL0 + 1, 8, 16>(p, E[1], X);
-    relu_tiles(X);
-    init_bias(Y, sm + kSmBias + 1 * 256, h); dense_layer<Net, kChL1 + 0, 8, 8>(p, X, Y); relu_tiles(Y);
-    init_bias(X, sm + kSmBias + 2 * 256, h); dense_layer<Net, kChL1 + 8, 8, 8>(p, Y, X); relu_tiles(X);
-    init_bias(Y, sm + kSmBias + 3 * 256, h); dense_layer<Net, kChL1 + 16, 8, 8>(p, X, Y); relu_tiles(Y);
-    init_bias(X, sm + kSmBias + 4 * 256, h); dense_layer<Net, kChL1 + 24, 8, 8>(p, Y, X); relu_tiles(X);
-    init_bias(Y, sm + kSmBias + 5 * 256, h);
-    dense_layer<Net, kChL5, 8, 8>(p, X, Y);
-    chunk_mma<Net, kChL5 + 8, 8, 16>(p, E[0], Y);
-    chunk_mma<Net, kChL5 + 9, 8, 16>(p, E[1], Y);
-    relu_tiles(Y);
-    init_bias(X, sm + kSmBias + 6 * 256, h); dense_layer<Net, kChL6, 8, 8>(p, Y, X); relu_tiles(X);
-    init_bias(Y, sm + kSmBias + 7 * 256, h); dense_layer<Net, kChL7, 8, 8>(p, X, Y); relu_tiles(Y);
-    float sigma = head_partial<8>(Y, sm + kSmWSigma, h);
-    sigma = sigma + __shfl_xor(sigma, 32) + sm[kSmBSigma];
+    NoTaps taps;
+    const float sigma = trunk_fwd<VanillaTrunkNet, VanillaTrunk>(p, E, X, Y, sm, h, taps);
     grid_store(args.out, l0, args.total, lane, grid_activation(sigma, args.act));
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last prefetched chunk must land before the LDS is released
+  });
 }
 
 hipError_t launch_density_grid(const char* packed, const int64_t* dims, const float* lo, const float* step, int64_t g_begin, int64_t g_end,
                                int act, float* out, hipStream_t stream) {
   if (stream_form(packed) == kFormUnknown) return hipErrorInvalidValue;   // never packed / declared (mlp_fwd refuses it too)
-  GridArgs a{};
-  a.packed = packed; a.ny = dims[1]; a.nz = dims[2]; a.g_begin = g_begin; a.total = g_end - g_begin;
-  for (int i = 0; i < 3; ++i) { a.lo[i] = lo[i]; a.step[i] = step[i]; }
-  a.act = act; a.out = out; a.npass = (int)((a.total + 127) / 128);
   static DeviceOnce lds_once;
-  if (hipError_t e = set_max_lds(&density_grid_kernel, kLdsBytes, lds_once); e != hipSuccess) return e;
-  const int cus = num_cus();
-  if (cus <= 0) return hipErrorInvalidDevice;
-  const int grid = a.npass < cus ? a.npass : cus;
-  if (grid <= 0) return hipSuccess;
-  density_grid_kernel<<<dim3(grid), dim3(256), kLdsBytes, stream>>>(a);
-  return hipGetLastError();
+  const GridArgs a = make_grid_args(packed, nullptr, dims, lo, step, g_begin, g_end, act, out);
+  return launch_persistent(&density_grid_kernel, kLdsBytes, a.npass, lds_once, stream, a);
 }
 
 }  // namespace aon

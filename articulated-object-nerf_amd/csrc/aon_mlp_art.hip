@@ -12,7 +12,7 @@
 //   * the 3->128 first deformation layer and the 128->3 deformation head are VALU work on register tiles;
 //     the deformed point is encoded in registers exactly like the vanilla path.
 #include "aon_art_common.h"
-#include "aon_launch.h"
+#include "aon_pass.h"
 
 namespace aon {
 
@@ -215,11 +215,51 @@ struct ArtSeg {
   };
   int64_t Np;
   const float* view_bias; // [VB] (n_rays,128): views_linear.0's effective bias + W_v0[:, 256:283] ve of the ray (launch_art_view_bias)
+  static constexpr bool kPerCallBlock = true;
 };
 struct ArtMlpArgs {
   ArtSeg seg[2];
   int npass_total;        // seg[0].npass + seg[1].npass (seg[1].npass == 0: a one-segment launch)
 };
+__host__ __device__ __forceinline__ const char* seg_stream(const ArtSeg& s) { return s.packed; }
+__device__ __forceinline__ const float* seg_small(const ArtSeg& s) { return s.small; }
+
+struct ArtTrunk {   // trunk_fwd's view of the articulated stream, per-call block, planes and decision bits
+  static constexpr int kL0 = kAChT0, kL1 = kAChT1, kL5 = kAChT5, kL6 = kAChT6, kL7 = kAChT7;
+  static constexpr int kBias = kA_BT, kWSigma = kA_WSIG, kBSigma = kA_BSIG, kMask0 = 4;
+  static constexpr int plane(int l) { return aplane_h(l); }
+};
+
+// Deformation MLP (model_autodecoder.py:196-205): the first layer's three xyz columns on the VALU (the latent columns are in its effective
+// bias), three 128 x 128 layers, the deformation head on the VALU -> xd = x + deformation.  taps: FwdTaps of the pass, or NoTaps.
+template <class Net, class Taps>
+__device__ __forceinline__ void deform_fwd(Pipe& p, const float (&x)[3], const float* sm, int h, Taps& taps, float (&xd)[3]) {
+  f32x16 H0[4], H1[4];
+  init_bias(H0, sm + kA_BD0, h);  // effective bias, then the three xyz columns on the VALU
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+#pragma unroll
+      for (int gq = 0; gq < 4; ++gq) {
+        const f32x4 w = *reinterpret_cast<const f32x4*>(sm + kA_WD0 + a * 128 + 32 * t + 8 * gq + 4 * h);
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) H0[t][4 * gq + cc] = __builtin_fmaf(w[cc], x[a], H0[t][4 * gq + cc]);
+      }
+    }
+  }
+  relu_tiles(H0);
+  init_bias(H1, sm + kA_BD + 0 * 128, h); dense_layer<Net, kAChD1 + 0, 4, 4>(p, H0, H1, taps.consume(H0, aplane_d(0), true)); taps.put_mask(0); relu_tiles(H1);
+  init_bias(H0, sm + kA_BD + 1 * 128, h); dense_layer<Net, kAChD1 + 4, 4, 4>(p, H1, H0, taps.consume(H1, aplane_d(1), true)); taps.put_mask(1); relu_tiles(H0);
+  init_bias(H1, sm + kA_BD + 2 * 128, h); dense_layer<Net, kAChD1 + 8, 4, 4>(p, H0, H1, taps.consume(H0, aplane_d(2), true)); taps.put_mask(2); relu_tiles(H1);
+  taps.burst(H1, aplane_d(3), 3);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {  // x' = deformation_layer(h) + pos   (:205)
+    float v = head_partial<4>(H1, sm + kA_WDL + a * 128, h);
+    v = v + __shfl_xor(v, 32) + sm[kA_BDL + a];
+    xd[a] = __fadd_rn(v, x[a]);
+  }
+}
 
 // FOLD: stream and per-call block are the folded form's (aon_art_common.h): views_linear.0 reads the post-ReLU layer-7 output through W';
 // no bottleneck layer and, [TRAIN], no bottleneck rows in the planes (rows kAPlBot .. kAPlBot + 255 stay unwritten).
@@ -232,40 +272,12 @@ __global__ void __launch_bounds__(256) art_mlp_fwd_kernel(ArtMlpArgs args) {
   using Net = std::conditional_t<VB, ArtFoldVbNet, std::conditional_t<FOLD, ArtFoldNet, ArtNet>>;
   constexpr int kV0 = FOLD ? kAChFV0 : kAChV0, kV1 = (FOLD ? kAChFV1 : kAChV1) - (VB ? 1 : 0);
   static_assert(!TRAIN || POS_IN_KERNEL, "the training path encodes the view direction from vd[], which only the in-kernel ray cast fills");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* sm = reinterpret_cast<float*>(smem + kRingBytes);
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int m = lane & 31, h = lane >> 5;
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);   // the step base of the training planes is wave-uniform: keep it scalar
-  // [GATHER] one segment; its pass count is the occupancy list's
-  const int64_t listed = GATHER ? *args.seg[0].gather_count : 0;
-  const int npass0 = GATHER ? (int)((listed + 127) / 128) : args.seg[0].npass;
-  int cur = (int)blockIdx.x >= npass0 ? 1 : 0;               // segment of this workgroup's first pass
-  auto load_small = [&](const float* small) {
-    const f32x4* src = reinterpret_cast<const f32x4*>(small);
-    f32x4* dst = reinterpret_cast<f32x4*>(sm);
-    for (int i = tid; i < kASmallFloats / 4; i += 256) dst[i] = src[i];
-  };
-  load_small(args.seg[cur].small);
-  Pipe p;
-  pipe_init<Net>(p, args.seg[cur].packed, smem, wave, lane);  // also publishes the small block just written to LDS
 
-  for (int gpass = blockIdx.x; gpass < (GATHER ? npass0 : args.npass_total); gpass += gridDim.x) {
-    const int si = gpass >= npass0 ? 1 : 0;
-    if (si != cur) {   // (workgroup-uniform, at most once per launch) the other network's biases / head weights replace the resident block
-      __syncthreads();
-      load_small(args.seg[si].small);
-      __syncthreads();
-      cur = si;
-    }
-    const ArtSeg& sg = args.seg[si];
-    const int pass = gpass - (si ? npass0 : 0);
-    {   // weight stream of this pass, and of this workgroup's next one (its first chunk pair is fetched during this pass's last chunk)
-      const int nxt = gpass + (int)gridDim.x;
-      p.stream = sg.packed;
-      p.next_stream = args.seg[(nxt >= npass0 && nxt < (GATHER ? npass0 : args.npass_total)) ? 1 : si].packed;
-    }
+  run_passes<Net, kASmallFloats, GATHER>(args, [&](const ArtSeg& sg, int pass, Pipe& p, const float* sm, int64_t listed = 0) __attribute__((always_inline)) {
     int64_t g = (int64_t)pass * 128 + wave * 32 + m;
     bool valid;
     int64_t gc;
@@ -296,37 +308,9 @@ __global__ void __launch_bounds__(256) art_mlp_fwd_kernel(ArtMlpArgs args) {
     PlaneIO io{};
     unsigned moff = 0;
     if constexpr (TRAIN) { io = make_plane_io(sg.planes, kAPlRows, (int64_t)pass * 4 + wave_s, m, h); moff = mask_lane_off(pass, tid); }
-    // [TRAIN] activation tiles are stored, and their ReLU decision bits collected, by the chunk that CONSUMES them (side job
-    // of chunk_mma, one value per MFMA group, one 16-byte store per four); only the tiles consumed on the VALU (deformation head,
-    // rgb head) and the VALU-computed first deformation layer's output go out in a burst of 64 values.
-    auto side = [&](const f32x16& tile, int row, unsigned& word, bool with_mask) {
-      return [&, row, with_mask](int i) {
-        if constexpr (TRAIN) {
-          if (i < 16) {
-            if ((i & 3) == 0) store_quad<false>(io, row, i >> 2, tile);
-            if (with_mask) word = mask_push_post(word, tile[i]);
-          }
-        }
-      };
-    };
-    unsigned mw[4] = {0u, 0u, 0u, 0u};
-    auto consume4 = [&](const f32x16 (&in)[4], int in_row, bool with_mask) {
-      return [&, in_row, with_mask](int j) { return side(in[j], in_row + 32 * j, mw[j >> 1], with_mask); };
-    };
-    auto consume8 = [&](const f32x16 (&in)[8], int in_row, bool with_mask) {
-      return [&, in_row, with_mask](int j) { return side(in[j], in_row + 32 * j, mw[j >> 1], with_mask); };
-    };
-    auto put_mask = [&](int slot) {
-      if constexpr (TRAIN)   // every word took 0 or 32 pushes (4- and 8-tile layers)
-        *mask_ptr(sg.masks, sg.Np, slot, moff) = u32x4{mask_word_finish(mw[0]), mask_word_finish(mw[1]), mask_word_finish(mw[2]), mask_word_finish(mw[3])};
-      mw[0] = mw[1] = mw[2] = mw[3] = 0u;
-    };
-    auto burst = [&](auto& tiles, int row, int mask_slot) {   // VALU-consumed tiles
-      if constexpr (TRAIN) {
-        store_plane(tiles, io, row);
-        *mask_ptr(sg.masks, sg.Np, mask_slot, moff) = relu_mask_bits(tiles);
-      }
-    };
+    // [TRAIN] planes and decision bits as side jobs of the consuming chunks; the VALU-computed first deformation layer's output and the
+    // tiles consumed on the VALU (deformation head, rgb head) go out in bursts
+    FwdTaps<TRAIN, ArtSeg> taps{sg, io, moff};
     auto save_row = [&](int row, float v) {  // one scalar per sample (lanes 0..31)
       if constexpr (TRAIN) { if (h == 0) *row_ptr(io, row) = v; }
     };
@@ -335,33 +319,8 @@ __global__ void __launch_bounds__(256) art_mlp_fwd_kernel(ArtMlpArgs args) {
       for (int a = 0; a < 3; ++a) save_row(kAPlPos + a, x[a]);
     }
 
-    // ---- deformation MLP (:196-205) ----
-    f32x16 H0[4], H1[4];
-    init_bias(H0, sm + kA_BD0, h);  // effective bias, then the three xyz columns on the VALU
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-          const f32x4 w = *reinterpret_cast<const f32x4*>(sm + kA_WD0 + a * 128 + 32 * t + 8 * gq + 4 * h);
-#pragma unroll
-          for (int cc = 0; cc < 4; ++cc) H0[t][4 * gq + cc] = __builtin_fmaf(w[cc], x[a], H0[t][4 * gq + cc]);
-        }
-      }
-    }
-    relu_tiles(H0);
-    init_bias(H1, sm + kA_BD + 0 * 128, h); dense_layer<Net, kAChD1 + 0, 4, 4>(p, H0, H1, consume4(H0, aplane_d(0), true)); put_mask(0); relu_tiles(H1);
-    init_bias(H0, sm + kA_BD + 1 * 128, h); dense_layer<Net, kAChD1 + 4, 4, 4>(p, H1, H0, consume4(H1, aplane_d(1), true)); put_mask(1); relu_tiles(H0);
-    init_bias(H1, sm + kA_BD + 2 * 128, h); dense_layer<Net, kAChD1 + 8, 4, 4>(p, H0, H1, consume4(H0, aplane_d(2), true)); put_mask(2); relu_tiles(H1);
-    burst(H1, aplane_d(3), 3);
     float xd[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {  // x' = deformation_layer(h) + pos   (:205)
-      float v = head_partial<4>(H1, sm + kA_WDL + a * 128, h);
-      v = v + __shfl_xor(v, 32) + sm[kA_BDL + a];
-      xd[a] = __fadd_rn(v, x[a]);
-    }
+    deform_fwd<Net>(p, x, sm, h, taps, xd);
     f32x16 E[2];
     encode_pos_scaled(xd, h, sm + kA_ESC, E);  // pos_enc after the deformation (enc_after=True, :207-208); scales: the network's degrees
     if constexpr (TRAIN) {
@@ -370,55 +329,21 @@ __global__ void __launch_bounds__(256) art_mlp_fwd_kernel(ArtMlpArgs args) {
       store_pos_enc_plane(E, io, kAPlE, h);
     }
 
-    // ---- trunk (:212-217), shape latent folded into the biases of layers 0 and 5 ----
-    f32x16 X[8], Y[8];
-    init_bias(X, sm + kA_BT + 0 * 256, h);
-    chunk_mma<Net, kAChT0 + 0, 8, 16>(p, E[0], X);
-    chunk_mma<Net, kAChT0 + 1, 8, 16>(p, E[1], X);
-    relu_tiles(X);
-    init_bias(Y, sm + kA_BT + 1 * 256, h); dense_layer<Net, kAChT1 + 0, 8, 8>(p, X, Y, consume8(X, aplane_h(0), true)); put_mask(4); relu_tiles(Y);
-    init_bias(X, sm + kA_BT + 2 * 256, h); dense_layer<Net, kAChT1 + 8, 8, 8>(p, Y, X, consume8(Y, aplane_h(1), true)); put_mask(5); relu_tiles(X);
-    init_bias(Y, sm + kA_BT + 3 * 256, h); dense_layer<Net, kAChT1 + 16, 8, 8>(p, X, Y, consume8(X, aplane_h(2), true)); put_mask(6); relu_tiles(Y);
-    init_bias(X, sm + kA_BT + 4 * 256, h); dense_layer<Net, kAChT1 + 24, 8, 8>(p, Y, X, consume8(Y, aplane_h(3), true)); put_mask(7); relu_tiles(X);
-    init_bias(Y, sm + kA_BT + 5 * 256, h);
-    dense_layer<Net, kAChT5, 8, 8>(p, X, Y, consume8(X, aplane_h(4), true)); put_mask(8);
-    // (the encoding stays live across layers 1-4, 32 registers, as in the inference kernel.  Rounds 2-4 re-encoded it here -- 30 sines --
-    // to stay clear of spills; with the view encoding gone from the trunk (per-ray view bias) both forms build with 0 scratch and this one
-    // is 0.04 ms per step faster: profiles/r05_view_bias_ab.txt)
-#ifdef AON_TRAIN_REENCODE
-    if constexpr (TRAIN) {
-      asm volatile("" : "+v"(xd[0]), "+v"(xd[1]), "+v"(xd[2]));
-      encode_pos_scaled(xd, h, sm + kA_ESC, E);
-    }
-#endif
-    chunk_mma<Net, kAChT5 + 8, 8, 16>(p, E[0], Y);
-    chunk_mma<Net, kAChT5 + 9, 8, 16>(p, E[1], Y);
-    relu_tiles(Y);
-    init_bias(X, sm + kA_BT + 6 * 256, h); dense_layer<Net, kAChT6, 8, 8>(p, Y, X, consume8(Y, aplane_h(5), true)); put_mask(9); relu_tiles(X);
-    f32x16 Z0[4], Z1[4];
-    init_bias(Y, sm + kA_BT + 7 * 256, h);
-    if constexpr (VB) {
-      // the ray's view bias straight into views_linear.0's accumulators, one 16-byte load per side slot of layer 7's LAST chunk
-      int ray32 = (int)ray;
-      asm volatile("" : "+v"(ray32));
-      const float* vb = sg.view_bias + (int64_t)ray32 * kCondWidth + 4 * h;
-      auto l7_side = [&](int j) {
-        auto base = consume8(X, aplane_h(6), true)(j);
-        return [&, base, j, vb](int i) {
-          base(i);
-          if (j == 7 && i < 16) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(vb + 32 * (i >> 2) + 8 * (i & 3));
-            Z0[i >> 2][4 * (i & 3)] = v[0]; Z0[i >> 2][4 * (i & 3) + 1] = v[1]; Z0[i >> 2][4 * (i & 3) + 2] = v[2]; Z0[i >> 2][4 * (i & 3) + 3] = v[3];
-          }
-        };
-      };
-      dense_layer<Net, kAChT7, 8, 8>(p, X, Y, l7_side);
-    } else {
-      dense_layer<Net, kAChT7, 8, 8>(p, X, Y, consume8(X, aplane_h(6), true));
-    }
-    put_mask(10); relu_tiles(Y);
-    float sigma = head_partial<8>(Y, sm + kA_WSIG, h);  // density_layer (:219)
-    sigma = sigma + __shfl_xor(sigma, 32) + sm[kA_BSIG];
+    // ---- trunk (:212-217), shape latent folded into the biases of layers 0 and 5; density_layer (:219) ----
+    // (the encoding stays live across layers 1-4, 32 registers, as in the inference kernel.  Rounds 2-4 re-encoded it at layer 5 -- 30
+    // sines -- to stay clear of spills; with the view encoding gone from the trunk (per-ray view bias) both forms build with 0 scratch and
+    // this one is 0.04 ms per step faster: profiles/r05_view_bias_ab.txt)
+    f32x16 X[8], Y[8], Z0[4], Z1[4];
+    auto l7_side = [&](auto plain) {
+      if constexpr (VB) {
+        int ray32 = (int)ray;
+        asm volatile("" : "+v"(ray32));
+        return view_bias_side(plain, sg.view_bias + (int64_t)ray32 * kCondWidth + 4 * h, Z0);
+      } else {
+        return plain;
+      }
+    };
+    const float sigma = trunk_fwd<Net, ArtTrunk>(p, E, X, Y, sm, h, taps, NoHook{}, l7_side);
     // ---- view branch (:227-234): cat[bottleneck, viewenc, appearance] -> 4 x (128, ReLU) ----
     auto view_enc_here = [&]() {   // [TRAIN] the view encoding where the branch needs it (and its plane rows)
       if constexpr (TRAIN) {
@@ -434,19 +359,19 @@ __global__ void __launch_bounds__(256) art_mlp_fwd_kernel(ArtMlpArgs args) {
         init_bias(Z0, sm + kA_BV + 0 * 128, h);
         chunk_mma<Net, kV0, 4, 14>(p, V, Z0);
       }
-      dense_layer<Net, kV0 + (VB ? 0 : 1), 8, 4>(p, Y, Z0, consume8(Y, aplane_h(7), true)); put_mask(11);
+      dense_layer<Net, kV0 + (VB ? 0 : 1), 8, 4>(p, Y, Z0, taps.consume(Y, aplane_h(7), true)); taps.put_mask(11);
     } else {
-      init_bias(X, sm + kA_BBOT, h); dense_layer<Net, kAChBott, 8, 8>(p, Y, X, consume8(Y, aplane_h(7), true)); put_mask(11);  // bottleneck (:223)
+      init_bias(X, sm + kA_BBOT, h); dense_layer<Net, kAChBott, 8, 8>(p, Y, X, taps.consume(Y, aplane_h(7), true)); taps.put_mask(11);  // bottleneck (:223)
       init_bias(Z0, sm + kA_BV + 0 * 128, h);
-      dense_layer<Net, kV0, 8, 4>(p, X, Z0, consume8(X, kAPlBot, false));
+      dense_layer<Net, kV0, 8, 4>(p, X, Z0, taps.consume(X, kAPlBot, false));
       view_enc_here();
       chunk_mma<Net, kV0 + 8, 4, 14>(p, V, Z0);
     }
     relu_tiles(Z0);
-    init_bias(Z1, sm + kA_BV + 1 * 128, h); dense_layer<Net, kV1 + 0, 4, 4>(p, Z0, Z1, consume4(Z0, aplane_v(0), true)); put_mask(12); relu_tiles(Z1);
-    init_bias(Z0, sm + kA_BV + 2 * 128, h); dense_layer<Net, kV1 + 4, 4, 4>(p, Z1, Z0, consume4(Z1, aplane_v(1), true)); put_mask(13); relu_tiles(Z0);
-    init_bias(Z1, sm + kA_BV + 3 * 128, h); dense_layer<Net, kV1 + 8, 4, 4>(p, Z0, Z1, consume4(Z0, aplane_v(2), true)); put_mask(14); relu_tiles(Z1);
-    burst(Z1, aplane_v(3), 15);
+    init_bias(Z1, sm + kA_BV + 1 * 128, h); dense_layer<Net, kV1 + 0, 4, 4>(p, Z0, Z1, taps.consume(Z0, aplane_v(0), true)); taps.put_mask(12); relu_tiles(Z1);
+    init_bias(Z0, sm + kA_BV + 2 * 128, h); dense_layer<Net, kV1 + 4, 4, 4>(p, Z1, Z0, taps.consume(Z1, aplane_v(1), true)); taps.put_mask(13); relu_tiles(Z0);
+    init_bias(Z1, sm + kA_BV + 3 * 128, h); dense_layer<Net, kV1 + 8, 4, 4>(p, Z0, Z1, taps.consume(Z0, aplane_v(2), true)); taps.put_mask(14); relu_tiles(Z1);
+    taps.burst(Z1, aplane_v(3), 15);
     float rgb[3];
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {  // rgb_layer (:236)
@@ -457,8 +382,7 @@ __global__ void __launch_bounds__(256) art_mlp_fwd_kernel(ArtMlpArgs args) {
       f32x4 o; o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2]; o[3] = sigma;
       reinterpret_cast<f32x4*>(sg.raw)[g] = o;
     }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -523,29 +447,17 @@ hipError_t launch_pack_prepare_art2(const float* const* const params[2], const f
 template <bool POS, bool TRAIN, bool FOLD, bool VB = false, bool GATHER = false>
 static hipError_t launch_art_tf(const ArtMlpArgs& args, hipStream_t stream) {
   static DeviceOnce lds_once;
-  if (hipError_t e = set_max_lds(&art_mlp_fwd_kernel<POS, TRAIN, FOLD, VB, GATHER>, kALdsBytes, lds_once); e != hipSuccess) return e;
-  const int cus = num_cus();
-  if (cus <= 0) return hipErrorInvalidDevice;
-  const int grid = args.npass_total < cus ? args.npass_total : cus;
-  if (grid <= 0) return hipSuccess;
-  art_mlp_fwd_kernel<POS, TRAIN, FOLD, VB, GATHER><<<dim3(grid), dim3(256), kALdsBytes, stream>>>(args);
-  return hipGetLastError();
+  return launch_persistent(&art_mlp_fwd_kernel<POS, TRAIN, FOLD, VB, GATHER>, kALdsBytes, args.npass_total, lds_once, stream, args);
 }
 
-// the kernel of the form the launch's streams AND per-call blocks were made in; everything in one launch must agree
+// the kernel of the form the launch's streams AND per-call blocks were made in (agreed_form); the per-ray view bias serves the in-kernel ray cast
 template <bool POS, bool TRAIN, bool GATHER = false>
 static hipError_t launch_art_t(const ArtMlpArgs& args, hipStream_t stream) {
-  const int form = stream_form(args.seg[0].packed);
-  if (form == kFormUnknown) return hipErrorInvalidValue;   // never packed / declared (a copy): refuse instead of guessing
-  if (stream_form(args.seg[0].small) != form) return hipErrorInvalidValue;
-  if (args.seg[1].npass > 0 && (stream_form(args.seg[1].packed) != form || stream_form(args.seg[1].small) != form)) return hipErrorInvalidValue;
-  const bool vb = args.seg[0].view_bias != nullptr;   // every segment of the launch or none; folded form, in-kernel ray cast only
-  if (args.seg[1].npass > 0 && (args.seg[1].view_bias != nullptr) != vb) return hipErrorInvalidValue;
-  if (vb && form != kFormFolded) return hipErrorInvalidValue;
-  if constexpr (POS) {
-    if (vb) return launch_art_tf<POS, TRAIN, true, true, GATHER>(args, stream);
-  } else {
-    if (vb) return hipErrorInvalidValue;
+  const int form = agreed_form(args);
+  if (form == kFormUnknown) return hipErrorInvalidValue;
+  if (args.seg[0].view_bias != nullptr) {
+    if constexpr (POS) return launch_art_tf<POS, TRAIN, true, true, GATHER>(args, stream);
+    else return hipErrorInvalidValue;
   }
   return form == kFormFolded ? launch_art_tf<POS, TRAIN, true, false, GATHER>(args, stream)
                              : launch_art_tf<POS, TRAIN, false, false, GATHER>(args, stream);
@@ -562,10 +474,8 @@ hipError_t launch_art_mlp_fwd(const char* packed, const float* small, const floa
                               const float* viewdirs, const float* t_vals, int64_t n_rays, int S, float* raw,
                               hipStream_t stream, const float* view_bias) {
   ArtMlpArgs args{};
-  ArtSeg& a = args.seg[0];
-  a.packed = packed; a.small = small; a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.t_vals = t_vals; a.view_bias = view_bias;
-  a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)((a.total + 127) / 128);
-  args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
+  fill_seg(args.seg[0], TrainSeg{packed, small, rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, nullptr, nullptr, 0, view_bias});
+  finish_segs(args, 1);
   return launch_art_t<true, false>(args, stream);
 }
 
@@ -576,10 +486,10 @@ hipError_t launch_art_mlp_fwd_gather(const char* packed, const float* small, con
                                      const int* idx, const int64_t* count, int64_t max_listed) {
   ArtMlpArgs args{};
   ArtSeg& a = args.seg[0];
-  a.packed = packed; a.small = small; a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.t_vals = t_vals; a.view_bias = view_bias;
-  a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)(((max_listed > 0 ? max_listed : a.total) + 127) / 128);
+  fill_seg(a, TrainSeg{packed, small, rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, nullptr, nullptr, 0, view_bias});
+  if (max_listed > 0) a.npass = (int)((max_listed + 127) / 128);
   a.gather_idx = idx; a.gather_count = count;
-  args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
+  finish_segs(args, 1);
   return launch_art_t<true, false, true>(args, stream);
 }
 
@@ -594,27 +504,17 @@ hipError_t launch_art_mlp_fwd_train(const char* packed, const float* small, cons
 hipError_t launch_art_mlp_fwd_train2(const TrainSeg* segs, int nsegs, hipStream_t stream) {
   if (nsegs < 1 || nsegs > 2) return hipErrorInvalidValue;
   ArtMlpArgs args{};
-  for (int i = 0; i < nsegs; ++i) {
-    const TrainSeg& t = segs[i];
-    ArtSeg& a = args.seg[i];
-    a.packed = t.packed; a.small = t.small; a.rays_o = t.rays_o; a.rays_d = t.rays_d; a.viewdirs = t.viewdirs; a.t_vals = t.t_vals;
-    a.raw = t.raw; a.total = t.n_rays * t.S; a.S = t.S; a.npass = (int)((a.total + 127) / 128);
-    a.planes = t.planes; a.masks = static_cast<u32x4*>(t.masks); a.Np = t.np_total > 0 ? t.np_total : (int64_t)a.npass * 128;   // (launch_mlp_fwd_train)
-    a.view_bias = t.view_bias;
-    args.npass_total += a.npass;
-  }
-  if (nsegs == 1) { args.seg[1] = args.seg[0]; args.seg[1].npass = 0; }
-  else if (args.seg[0].npass == 0) { args.seg[0] = args.seg[1]; args.seg[1].npass = 0; }   // (an empty first segment: the second one alone)
+  for (int i = 0; i < nsegs; ++i) fill_seg(args.seg[i], segs[i]);
+  finish_segs(args, nsegs);
   return launch_art_t<true, true>(args, stream);
 }
 
 hipError_t launch_art_mlp_fwd_pos(const char* packed, const float* small, const float* pos, const float* viewdirs_enc,
                                   int64_t n_rays, int S, float* raw, hipStream_t stream) {
   ArtMlpArgs args{};
-  ArtSeg& a = args.seg[0];
-  a.packed = packed; a.small = small; a.pos = pos; a.viewdirs_enc = viewdirs_enc;
-  a.raw = raw; a.total = n_rays * S; a.S = S; a.npass = (int)((a.total + 127) / 128);
-  args.seg[1] = a; args.seg[1].npass = 0; args.npass_total = a.npass;
+  fill_seg(args.seg[0], TrainSeg{packed, small, nullptr, nullptr, nullptr, nullptr, n_rays, S, raw, nullptr, nullptr, 0});
+  args.seg[0].pos = pos; args.seg[0].viewdirs_enc = viewdirs_enc;
+  finish_segs(args, 1);
   return launch_art_t<false, false>(args, stream);
 }
 
@@ -628,94 +528,32 @@ struct ArtTrunkNet {
   static constexpr int chunk_bytes(int c) { return c < kAChT0 ? kSmallChunkBytes : kBigChunkBytes; }
 };
 
-// art_mlp_fwd_kernel's operations up to its raw sigma, in the same order (the same bits), on points generated from the grid (grid_point)
+// art_mlp_fwd_kernel up to its raw sigma -- the same deform_fwd and trunk_fwd, so the same operations in the same order and the same
+// bits -- on points generated from the grid (grid_point)
 __global__ void __launch_bounds__(256) art_density_grid_kernel(GridArgs args) {
-  using Net = ArtTrunkNet;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* sm = reinterpret_cast<float*>(smem + kRingBytes);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int m = lane & 31, h = lane >> 5;
-  {
-    const f32x4* src = reinterpret_cast<const f32x4*>(args.small);
-    f32x4* dst = reinterpret_cast<f32x4*>(sm);
-    for (int i = tid; i < kASmallFloats / 4; i += 256) dst[i] = src[i];
-  }
-  Pipe p;
-  pipe_init<Net>(p, args.packed, smem, wave, lane);  // also publishes the small block
-  for (int pass = blockIdx.x; pass < args.npass; pass += gridDim.x) {
+  run_passes_one<ArtTrunkNet, kASmallFloats>(args.packed, args.small, args.npass, [&](int pass, Pipe& p, const float* sm) __attribute__((always_inline)) {
     const int64_t l0 = (int64_t)pass * 128 + wave * 32;
     const int64_t l = l0 + m;
-    float x[3];
+    float x[3], xd[3];
     grid_point(args, l < args.total ? l : args.total - 1, x);
-    // deformation MLP (model_autodecoder.py:196-205)
-    f32x16 H0[4], H1[4];
-    init_bias(H0, sm + kA_BD0, h);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-          const f32x4 w = *reinterpret_cast<const f32x4*>(sm + kA_WD0 + a * 128 + 32 * t + 8 * gq + 4 * h);
-#pragma unroll
-          for (int cc = 0; cc < 4; ++cc) H0[t][4 * gq + cc] = __builtin_fmaf(w[cc], x[a], H0[t][4 * gq + cc]);
-        }
-      }
-    }
-    relu_tiles(H0);
-    init_bias(H1, sm + kA_BD + 0 * 128, h); dense_layer<Net, kAChD1 + 0, 4, 4>(p, H0, H1); relu_tiles(H1);
-    init_bias(H0, sm + kA_BD + 1 * 128, h); dense_layer<Net, kAChD1 + 4, 4, 4>(p, H1, H0); relu_tiles(H0);
-    init_bias(H1, sm + kA_BD + 2 * 128, h); dense_layer<Net, kAChD1 + 8, 4, 4>(p, H0, H1); relu_tiles(H1);
-    float xd[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {  // x' = deformation_layer(h) + pos   (:205)
-      float v = head_partial<4>(H1, sm + kA_WDL + a * 128, h);
-      v = v + __shfl_xor(v, 32) + sm[kA_BDL + a];
-      xd[a] = __fadd_rn(v, x[a]);
-    }
-    f32x16 E[2];
+    NoTaps taps;
+    deform_fwd<ArtTrunkNet>(p, x, sm, h, taps, xd);
+    f32x16 E[2], X[8], Y[8];
     encode_pos_scaled(xd, h, sm + kA_ESC, E);
-    // trunk (:212-217) and density_layer (:219)
-    f32x16 X[8], Y[8];
-    init_bias(X, sm + kA_BT + 0 * 256, h);
-    chunk_mma<Net, kAChT0 + 0, 8, 16>(p, E[0], X);
-    chunk_mma<Net, kAChT0 + 1, 8, 16>(p, E[1], X);
-    relu_tiles(X);
-    init_bias(Y, sm + kA_BT + 1 * 256, h); dense_layer<Net, kAChT1 + 0, 8, 8>(p, X, Y); relu_tiles(Y);
-    init_bias(X, sm + kA_BT + 2 * 256, h); dense_layer<Net, kAChT1 + 8, 8, 8>(p, Y, X); relu_tiles(X);
-    init_bias(Y, sm + kA_BT + 3 * 256, h); dense_layer<Net, kAChT1 + 16, 8, 8>(p, X, Y); relu_tiles(Y);
-    init_bias(X, sm + kA_BT + 4 * 256, h); dense_layer<Net, kAChT1 + 24, 8, 8>(p, Y, X); relu_tiles(X);
-    init_bias(Y, sm + kA_BT + 5 * 256, h);
-    dense_layer<Net, kAChT5, 8, 8>(p, X, Y);
-    chunk_mma<Net, kAChT5 + 8, 8, 16>(p, E[0], Y);
-    chunk_mma<Net, kAChT5 + 9, 8, 16>(p, E[1], Y);
-    relu_tiles(Y);
-    init_bias(X, sm + kA_BT + 6 * 256, h); dense_layer<Net, kAChT6, 8, 8>(p, Y, X); relu_tiles(X);
-    init_bias(Y, sm + kA_BT + 7 * 256, h); dense_layer<Net, kAChT7, 8, 8>(p, X, Y); relu_tiles(Y);
-    float sigma = head_partial<8>(Y, sm + kA_WSIG, h);
-    sigma = sigma + __shfl_xor(sigma, 32) + sm[kA_BSIG];
+    const float sigma = trunk_fwd<ArtTrunkNet, ArtTrunk>(p, E, X, Y, sm, h, taps);
     grid_store(args.out, l0, args.total, lane, grid_activation(sigma, args.act));
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last prefetched chunk must land before the LDS is released
+  });
 }
 
 hipError_t launch_art_density_grid(const char* packed, const float* small, const int64_t* dims, const float* lo, const float* step,
                                    int64_t g_begin, int64_t g_end, int act, float* out, hipStream_t stream) {
   const int form = stream_form(packed);
-  if (form == kFormUnknown || stream_form(small) != form) return hipErrorInvalidValue;   // as launch_art_t
-  GridArgs a{};
-  a.packed = packed; a.small = small; a.ny = dims[1]; a.nz = dims[2]; a.g_begin = g_begin; a.total = g_end - g_begin;
-  for (int i = 0; i < 3; ++i) { a.lo[i] = lo[i]; a.step[i] = step[i]; }
-  a.act = act; a.out = out; a.npass = (int)((a.total + 127) / 128);
+  if (form == kFormUnknown || stream_form(small) != form) return hipErrorInvalidValue;   // as agreed_form
   static DeviceOnce lds_once;
-  if (hipError_t e = set_max_lds(&art_density_grid_kernel, kALdsBytes, lds_once); e != hipSuccess) return e;
-  const int cus = num_cus();
-  if (cus <= 0) return hipErrorInvalidDevice;
-  const int grid = a.npass < cus ? a.npass : cus;
-  if (grid <= 0) return hipSuccess;
-  art_density_grid_kernel<<<dim3(grid), dim3(256), kALdsBytes, stream>>>(a);
-  return hipGetLastError();
+  const GridArgs a = make_grid_args(packed, small, dims, lo, step, g_begin, g_end, act, out);
+  return launch_persistent(&art_density_grid_kernel, kALdsBytes, a.npass, lds_once, stream, a);
 }
 
 int64_t art_stream_bytes() { return kAStreamBytes; }

@@ -504,6 +504,121 @@ __device__ __forceinline__ void load_plane(f32x16 (&x)[NT], const PlaneIO& io, i
   }
 }
 
+template <int NT>
+__device__ __forceinline__ void zero_tiles(f32x16 (&x)[NT]) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) x[t][r] = 0.f;
+}
+
+// What a forward kernel records of a pass for the backward pass (TRAIN; nothing otherwise).  Every hidden activation tile is stored, and
+// its ReLU decision bits are collected, by the chunk that CONSUMES it (side job of chunk_mma: one value per MFMA group, one 16-byte
+// store per four), so neither a store burst nor a block of mask arithmetic sits at a layer boundary.  Only tiles consumed on the VALU
+// (deformation head, rgb head) go out in a burst of 64 values.  Seg: the segment record (`masks`, `Np`).
+template <bool TRAIN, class Seg>
+struct FwdTaps {
+  const Seg& sg;
+  const PlaneIO& io;
+  const unsigned moff;                  // mask_lane_off of the pass
+  unsigned mw[4] = {0u, 0u, 0u, 0u};    // decision-bit words of the layer being consumed
+
+  // side jobs of the layer that consumes `in` (4 or 8 tiles); in_row: plane row of tile 0; with_mask false: `in` has no activation
+  template <int NT>
+  __device__ __forceinline__ auto consume(const f32x16 (&in)[NT], int in_row, bool with_mask) {
+    return [this, &in, in_row, with_mask](int j) {
+      return [this, &in, in_row, with_mask, j](int i) {
+        if constexpr (TRAIN) {
+          if (i < 16) {
+            if ((i & 3) == 0) store_quad<false>(io, in_row + 32 * j, i >> 2, in[j]);
+            if (with_mask) mw[j >> 1] = mask_push_post(mw[j >> 1], in[j][i]);
+          }
+        }
+      };
+    };
+  }
+  // all tiles of the layer have been consumed: every word took 0 or 32 pushes (4- and 8-tile layers)
+  __device__ __forceinline__ void put_mask(int slot) {
+    if constexpr (TRAIN)
+      *mask_ptr(sg.masks, sg.Np, slot, moff) = u32x4{mask_word_finish(mw[0]), mask_word_finish(mw[1]), mask_word_finish(mw[2]), mask_word_finish(mw[3])};
+    mw[0] = mw[1] = mw[2] = mw[3] = 0u;
+  }
+  // VALU-consumed tiles: no consuming chunk, 64 values stored here (the bits in burst form: already in the stored layout)
+  template <int NT>
+  __device__ __forceinline__ void burst(const f32x16 (&tiles)[NT], int row, int slot) {
+    if constexpr (TRAIN) {
+      store_plane(tiles, io, row);
+      *mask_ptr(sg.masks, sg.Np, slot, moff) = relu_mask_bits(tiles);
+    }
+  }
+};
+struct NoTaps {   // the density-grid kernels record nothing
+  template <int NT> __device__ __forceinline__ NoSideOf consume(const f32x16 (&)[NT], int, bool) const { return NoSideOf{}; }
+  __device__ __forceinline__ void put_mask(int) const {}
+  template <int NT> __device__ __forceinline__ void burst(const f32x16 (&)[NT], int, int) const {}
+};
+
+// [VB] side jobs of layer 7 = `base_of`'s, plus the ray's view bias straight into the view layer's accumulators Z: one 16-byte load per
+// side slot of layer 7's LAST chunk (tiles 0 .. 6 of its input are dead by then): a chunk of MFMAs (3.4 us) between the loads and their
+// first use.  vb: the ray's 128 floats + 4 h.
+template <class BaseOf>
+__device__ __forceinline__ auto view_bias_side(BaseOf base_of, const float* vb, f32x16 (&Z)[4]) {
+  return [base_of, vb, &Z](int j) {
+    auto base = base_of(j);
+    return [&Z, base, j, vb](int i) {
+      base(i);
+      if (j == 7 && i < 16) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(vb + 32 * (i >> 2) + 8 * (i & 3));
+        Z[i >> 2][4 * (i & 3)] = v[0]; Z[i >> 2][4 * (i & 3) + 1] = v[1]; Z[i >> 2][4 * (i & 3) + 2] = v[2]; Z[i >> 2][4 * (i & 3) + 3] = v[3];
+      }
+    };
+  };
+}
+
+// The 8 x 256 trunk both networks share: encoding E (63) -> layers 0 .. 7, the encoding again at layer 5 (concatenated after layer 4's
+// ReLU), then the density head on the post-ReLU layer-7 output.  Returns the raw sigma; on exit the post-ReLU layer-7 tiles are in Y and
+// dead tiles in X.  T, per network: chunk bases kL0 / kL1 / kL5 / kL6 / kL7, small-block offsets kBias (8 x 256) / kWSigma / kBSigma,
+// plane(l) = plane row of layer l's output, kMask0 = decision-bit slot of layer 0's output.
+//   taps      FwdTaps of the pass, or NoTaps
+//   at_skip   called between layer 5's hidden chunks and its two encoding chunks (a kernel that does not keep E live re-reads it there)
+//   l7_side   side jobs of layer 7 from the plain ones (view_bias_side, or the plain ones unchanged)
+struct NoHook {
+  __device__ __forceinline__ void operator()() const {}
+};
+struct PlainSide {
+  template <class SideOf> __device__ __forceinline__ SideOf operator()(SideOf s) const { return s; }
+};
+template <class Net, class T, class Taps, class AtSkip = NoHook, class L7Side = PlainSide>
+__device__ __forceinline__ float trunk_fwd(Pipe& p, const f32x16 (&E)[2], f32x16 (&X)[8], f32x16 (&Y)[8], const float* sm, int h, Taps& taps,
+                                           AtSkip at_skip = AtSkip{}, L7Side l7_side = L7Side{}) {
+  const float* bias = sm + T::kBias;
+  // L0: enc(63) -> 256
+  init_bias(X, bias + 0 * 256, h);
+  chunk_mma<Net, T::kL0 + 0, 8, 16>(p, E[0], X);
+  chunk_mma<Net, T::kL0 + 1, 8, 16>(p, E[1], X);
+  relu_tiles(X);
+  // L1..L4
+  init_bias(Y, bias + 1 * 256, h); dense_layer<Net, T::kL1 + 0, 8, 8>(p, X, Y, taps.consume(X, T::plane(0), true)); taps.put_mask(T::kMask0 + 0); relu_tiles(Y);
+  init_bias(X, bias + 2 * 256, h); dense_layer<Net, T::kL1 + 8, 8, 8>(p, Y, X, taps.consume(Y, T::plane(1), true)); taps.put_mask(T::kMask0 + 1); relu_tiles(X);
+  init_bias(Y, bias + 3 * 256, h); dense_layer<Net, T::kL1 + 16, 8, 8>(p, X, Y, taps.consume(X, T::plane(2), true)); taps.put_mask(T::kMask0 + 2); relu_tiles(Y);
+  init_bias(X, bias + 4 * 256, h); dense_layer<Net, T::kL1 + 24, 8, 8>(p, Y, X, taps.consume(Y, T::plane(3), true)); taps.put_mask(T::kMask0 + 3); relu_tiles(X);
+  // L5: cat[h(256), enc(63)] -> 256
+  init_bias(Y, bias + 5 * 256, h);
+  dense_layer<Net, T::kL5, 8, 8>(p, X, Y, taps.consume(X, T::plane(4), true)); taps.put_mask(T::kMask0 + 4);
+  at_skip();
+  chunk_mma<Net, T::kL5 + 8, 8, 16>(p, E[0], Y);
+  chunk_mma<Net, T::kL5 + 9, 8, 16>(p, E[1], Y);
+  relu_tiles(Y);
+  // L6, L7
+  init_bias(X, bias + 6 * 256, h); dense_layer<Net, T::kL6, 8, 8>(p, Y, X, taps.consume(Y, T::plane(5), true)); taps.put_mask(T::kMask0 + 5); relu_tiles(X);
+  init_bias(Y, bias + 7 * 256, h);
+  dense_layer<Net, T::kL7, 8, 8>(p, X, Y, l7_side(taps.consume(X, T::plane(6), true)));
+  taps.put_mask(T::kMask0 + 6); relu_tiles(Y);
+  // density head on the post-ReLU layer-7 output
+  const float sigma = head_partial<8>(Y, sm + T::kWSigma, h);
+  return sigma + __shfl_xor(sigma, 32) + sm[T::kBSigma];
+}
+
 // encodings are held in a permuted register order (posenc_col / viewenc_col); planes use the reference's columns, so these
 // rows are written one value at a time (62 + 26 four-byte stores per sample against 3,400 rows in 16-byte stores).  The row of
 // a register depends on the half-wave (sin rows for h = 0, sin(. + pi/2) rows for h = 1): both byte offsets are compile-time
@@ -646,6 +761,14 @@ struct GridArgs {
   float* out;
   int npass;               // ceil(total / 128)
 };
+inline GridArgs make_grid_args(const char* packed, const float* small, const int64_t* dims, const float* lo, const float* step, int64_t g_begin,
+                               int64_t g_end, int act, float* out) {
+  GridArgs a{};
+  a.packed = packed; a.small = small; a.ny = dims[1]; a.nz = dims[2]; a.g_begin = g_begin; a.total = g_end - g_begin;
+  for (int i = 0; i < 3; ++i) { a.lo[i] = lo[i]; a.step[i] = step[i]; }
+  a.act = act; a.out = out; a.npass = (int)((a.total + 127) / 128);
+  return a;
+}
 
 // Point l of a call (0 <= l < total) is grid point g = g_begin + l, C order over (nx, ny, nz) with k fastest; its coordinates are
 // lo_a + idx_a * step_a, multiply then add, each rounded (a torch expression gives the same bits).

@@ -16,7 +16,7 @@
 #include <atomic>
 #define AON_WGRAD_KERNELS
 #define AON_CHAIN_STAGE_MASKED   // see BwdSideOf (aon_mlp_core.h)
-#include "aon_launch.h"
+#include "aon_pass.h"
 #include "aon_wgrad.h"
 
 namespace aon {
@@ -255,14 +255,6 @@ struct BwdArgs {
   int npass_total;          // seg[1].npass == 0: a one-segment launch
 };
 
-template <int NT>
-__device__ __forceinline__ void zero_tiles(f32x16 (&x)[NT]) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) x[t][r] = 0.f;
-}
-
 // FOLD: the transposed stream is the folded form (BwdFoldNet): d H7 = W'^T dZ_view + W_sigma^T d_sigma in one layer, no bottleneck gradient.
 template <bool FOLD>
 __global__ void __launch_bounds__(256) mlp_bwd_chain_kernel(BwdArgs args) {
@@ -418,12 +410,9 @@ hipError_t launch_pack_vanilla_bwd(const float* const* params, float* packed, hi
 int64_t bwd_stream_bytes() { return kBwBufferBytes; }
 
 template <bool FOLD>
-static hipError_t launch_chain_f(const BwdArgs& a, int grid, hipStream_t stream) {
+static hipError_t launch_chain_f(const BwdArgs& a, hipStream_t stream) {
   static DeviceOnce lds_once;
-  constexpr int lds = kRingBytes + (int)kSmallBytes;
-  if (hipError_t e = set_max_lds(&mlp_bwd_chain_kernel<FOLD>, lds, lds_once); e != hipSuccess) return e;
-  mlp_bwd_chain_kernel<FOLD><<<dim3(grid), dim3(256), lds, stream>>>(a);
-  return hipGetLastError();
+  return launch_persistent(&mlp_bwd_chain_kernel<FOLD>, kRingBytes + (int)kSmallBytes, a.npass_total, lds_once, stream, a);
 }
 
 hipError_t launch_mlp_bwd_chain2(const ChainSeg* segs, int nsegs, hipStream_t stream) {
@@ -435,15 +424,9 @@ hipError_t launch_mlp_bwd_chain2(const ChainSeg* segs, int nsegs, hipStream_t st
   for (int i = 0; i < nsegs; ++i) {
     const ChainSeg& c = segs[i];
     a.seg[i] = BwdSeg{c.packed_bwd, c.small, c.d_raw, static_cast<const u32x4*>(c.masks), c.dplanes, c.Np, (int)(c.Np / 128)};
-    a.npass_total += a.seg[i].npass;
   }
-  if (nsegs == 1) { a.seg[1] = a.seg[0]; a.seg[1].npass = 0; }
-  else if (a.seg[0].npass == 0) { a.seg[0] = a.seg[1]; a.seg[1].npass = 0; }
-  const int cus = num_cus();
-  if (cus <= 0) return hipErrorInvalidDevice;
-  const int grid = a.npass_total < cus ? a.npass_total : cus;
-  if (grid <= 0) return hipSuccess;
-  return form == kFormFolded ? launch_chain_f<true>(a, grid, stream) : launch_chain_f<false>(a, grid, stream);
+  finish_segs(a, nsegs);
+  return form == kFormFolded ? launch_chain_f<true>(a, stream) : launch_chain_f<false>(a, stream);
 }
 
 hipError_t launch_mlp_bwd_chain(const char* packed_bwd, const char* packed_fwd, const float* d_raw, const void* masks,

@@ -10,7 +10,7 @@
 //   * every latent is broadcast to all samples, so  dW[:, latent cols] = db (x) latent  and  d latent = W[:, cols]^T db:
 //     both come from the bias gradients, no per-sample work.
 #include "aon_art_common.h"
-#include "aon_launch.h"
+#include "aon_pass.h"
 #include "aon_wgrad.h"
 
 namespace aon {
@@ -155,14 +155,6 @@ struct ArtBwdArgs {
   ArtBwdSeg seg[2];
   int npass_total;        // seg[1].npass == 0: a one-segment launch
 };
-
-template <int NT>
-__device__ __forceinline__ void zero_tiles_a(f32x16 (&x)[NT]) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) x[t][r] = 0.f;
-}
 
 // FOLD: transposed stream of the folded form: d H7 = W'^T dZ_V0 + W_sigma^T d_sigma in one layer, no bottleneck gradient.
 template <bool FOLD>
@@ -510,11 +502,9 @@ hipError_t launch_pack_art_bwd(const float* const* params, float* packed, hipStr
 int64_t art_bwd_stream_bytes() { return kABwStreamBytes; }
 
 template <bool FOLD>
-static hipError_t launch_art_chain_f(const ArtBwdArgs& a, int grid, hipStream_t stream) {
+static hipError_t launch_art_chain_f(const ArtBwdArgs& a, hipStream_t stream) {
   static DeviceOnce lds_once;
-  if (hipError_t e = set_max_lds(&art_bwd_chain_kernel<FOLD>, kALdsBytes, lds_once); e != hipSuccess) return e;
-  art_bwd_chain_kernel<FOLD><<<dim3(grid), dim3(256), kALdsBytes, stream>>>(a);
-  return hipGetLastError();
+  return launch_persistent(&art_bwd_chain_kernel<FOLD>, kALdsBytes, a.npass_total, lds_once, stream, a);
 }
 
 hipError_t launch_art_bwd_chain2(const ChainSeg* segs, int nsegs, hipStream_t stream) {
@@ -527,15 +517,9 @@ hipError_t launch_art_bwd_chain2(const ChainSeg* segs, int nsegs, hipStream_t st
   for (int i = 0; i < nsegs; ++i) {
     const ChainSeg& c = segs[i];
     a.seg[i] = ArtBwdSeg{c.packed_bwd, c.small, c.d_raw, static_cast<const u32x4*>(c.masks), c.planes, c.dplanes, c.dxp, c.Np, (int)(c.Np / 128)};
-    a.npass_total += a.seg[i].npass;
   }
-  if (nsegs == 1) { a.seg[1] = a.seg[0]; a.seg[1].npass = 0; }
-  else if (a.seg[0].npass == 0) { a.seg[0] = a.seg[1]; a.seg[1].npass = 0; }
-  const int cus = num_cus();
-  if (cus <= 0) return hipErrorInvalidDevice;
-  const int grid = a.npass_total < cus ? a.npass_total : cus;
-  if (grid <= 0) return hipSuccess;
-  return form == kFormFolded ? launch_art_chain_f<true>(a, grid, stream) : launch_art_chain_f<false>(a, grid, stream);
+  finish_segs(a, nsegs);
+  return form == kFormFolded ? launch_art_chain_f<true>(a, stream) : launch_art_chain_f<false>(a, stream);
 }
 
 hipError_t launch_art_bwd_chain(const char* packed_bwd, const float* small, const float* d_raw, const void* masks, const float* planes,

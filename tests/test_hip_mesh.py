@@ -115,6 +115,27 @@ def test_art_density_bits_equal_art_mlp_fwd_pos(dev, dims):
     assert torch.equal(model.density_grid((LO, HI), dims, lat), sp)
 
 
+@pytest.mark.parametrize("fold", [True, False])
+def test_art_density_bits_equal_art_mlp_fwd_pos_both_forms(dev, fold, fold_state):
+    """The grid kernel and art_mlp_fwd_pos run the same deformation MLP and trunk code on two chunk maps (the truncated stream; the
+    literal or the folded one): on a stream of either form the raw sigma is the same bits.  693 points: 6 passes, a ragged last one."""
+    from aon_amd import ops
+
+    ops.set_bottleneck_fold(fold)
+    model, _ = _art(dev)
+    lat = _latents(dev)
+    mlp = model.fine_mlp
+    packed, small = mlp.packed(True), ops.art_prepare(dict(mlp.named_parameters()), lat)
+    assert ops.bottleneck_fold() == fold
+    dims = (7, 9, 11)
+    raw = ops.density_grid(packed, dims, LO, HI, ops.ACT_NONE, small=small)
+    pts = ops.grid_points(dims, LO, HI, device=dev)
+    assert pts.shape[0] == 693
+    venc = ops.pos_enc(torch.zeros_like(pts) + torch.tensor([0.0, 0.0, 1.0], device=dev), 0, 4)
+    ref = ops.art_mlp_fwd_pos(packed, small, pts[:, None, :].contiguous(), venc.contiguous())[..., 3].reshape(-1)
+    assert torch.equal(raw.reshape(-1), ref)
+
+
 # ---------------------------------------------------------------- density against the fp64 oracle
 def _sample(dims, n, seed):
     P = dims[0] * dims[1] * dims[2]

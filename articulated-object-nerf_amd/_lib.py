@@ -235,8 +235,15 @@ _SCENE_SIGS = {
     "aon_scene_composite": (_i, [_p] * 4 + [_l, _i, _l, _i, _i, _i] + [_p] + [_p] * 5 + [_p]),
 }
 
+# include/aon_hip_scene_occ.h: a fourth table, kept out of the three lists above
+_SCENE_OCC_SIGS = {
+    "aon_scene_occ_workspace_bytes": (_l, [_l, _i, _i]),
+    # packed, smalls_host, grids_host, starts_host | pair_o, pair_d, pair_v, t_vals | k, s | raw, occupied_dev | workspace, bytes | stream
+    "aon_scene_art_mlp_fwd_occ": (_i, [_p] * 4 + [_p] * 4 + [_i, _i] + [_p, _p] + [_p, _l] + [_p]),
+}
 
-for _name, (_res, _args) in {**_SIGS, **_EXT_SIGS, **_SCENE_SIGS}.items():
+
+for _name, (_res, _args) in {**_SIGS, **_EXT_SIGS, **_SCENE_SIGS, **_SCENE_OCC_SIGS}.items():
     _fn = getattr(lib, _name)  # AttributeError here = the .so does not export what the header declares
     _fn.restype = _res
     _fn.argtypes = _args
@@ -274,3 +281,8 @@ def extension_symbols():
 def scene_symbols():
     """the names include/aon_hip_scene.h declares"""
     return sorted(_SCENE_SIGS)
+
+
+def scene_occ_symbols():
+    """the names include/aon_hip_scene_occ.h declares"""
+    return sorted(_SCENE_OCC_SIGS)

@@ -245,13 +245,6 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
 }
 
 // ---- occupancy-grid accelerated inference (aon_occ.hip) ----
-static const char* occ_cells_bad(const int64_t* cells3) {
-  if (!cells3) return "null cell counts";
-  for (int a = 0; a < 3; ++a)
-    if (cells3[a] < 1 || cells3[a] > (int64_t)1 << 24) return "every cell count must be in [1, 2^24]";
-  if (cells3[0] > ((int64_t)1 << 40) / cells3[1] / cells3[2]) return "grid too large (more than 2^40 cells)";
-  return nullptr;
-}
 int64_t aon_occupancy_bytes(const int64_t* cells3_host) {
   if (const char* msg = occ_cells_bad(cells3_host)) return fail(AON_E_INVALID, (std::string("aon_occupancy_bytes: ") + msg).c_str());
   return (cells3_host[0] * cells3_host[1] * cells3_host[2] + 31) / 32 * 4;
@@ -264,19 +257,6 @@ int aon_occupancy_build(const float* density, const int64_t* dims3_host, float t
   if (threshold != threshold) return fail(AON_E_INVALID, "aon_occupancy_build: threshold is NaN");
   if (!density || !bits) return fail(AON_E_INVALID, "aon_occupancy_build: null pointer");
   return check(aon::launch_occ_build(density, dims3_host, threshold, dilate, bits, (hipStream_t)stream), "aon_occupancy_build");
-}
-static const char* occ_grid_bad(const aon_occupancy* occ, aon::OccGrid& G) {
-  if (!occ || !occ->bits) return "null occupancy grid";
-  if (const char* msg = occ_cells_bad(occ->cells)) return msg;
-  G.bits = occ->bits;
-  for (int a = 0; a < 3; ++a) {
-    if (!std::isfinite(occ->lo[a]) || !std::isfinite(occ->step[a]) || !(occ->step[a] > 0.f)) return "occupancy lo must be finite and step finite and > 0";
-    G.cells[a] = occ->cells[a]; G.lo[a] = occ->lo[a]; G.step[a] = occ->step[a];
-    const float span = (float)occ->cells[a] * occ->step[a];   // the last grid point: multiply, then add (ops.grid_points)
-    G.hi[a] = occ->lo[a] + span;
-    if (!std::isfinite(G.hi[a])) return "occupancy box not finite";
-  }
-  return nullptr;
 }
 // the inference-only limits of the occupancy path, checked before any launch
 static const char* occ_opts_bad(const aon_render_opts* opts, bool art, const float* t_rand) {

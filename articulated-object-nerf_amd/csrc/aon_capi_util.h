@@ -107,6 +107,29 @@ struct Geo {
 // caller who fills them to match a (1, 12, 5) geometry used to get AON_E_INVALID from the general engine: ADVICE r3).
 const char* make_geo(const aon_render_opts* o, Geo& g, bool general_engine = false);
 
+// An aon_occupancy as handed to an entry point (DESIGN.md sections 4.9, 4.17): nullptr when fine, else what is wrong; occ_grid_bad also fills
+// the kernels' view of the grid (hi = lo + cells * step: multiply, then add -- the last grid point of ops.grid_points)
+inline const char* occ_cells_bad(const int64_t* cells3) {
+  if (!cells3) return "null cell counts";
+  for (int a = 0; a < 3; ++a)
+    if (cells3[a] < 1 || cells3[a] > (int64_t)1 << 24) return "every cell count must be in [1, 2^24]";
+  if (cells3[0] > ((int64_t)1 << 40) / cells3[1] / cells3[2]) return "grid too large (more than 2^40 cells)";
+  return nullptr;
+}
+inline const char* occ_grid_bad(const aon_occupancy* occ, aon::OccGrid& G) {
+  if (!occ || !occ->bits) return "null occupancy grid";
+  if (const char* msg = occ_cells_bad(occ->cells)) return msg;
+  G.bits = occ->bits;
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(occ->lo[a]) || !std::isfinite(occ->step[a]) || !(occ->step[a] > 0.f)) return "occupancy lo must be finite and step finite and > 0";
+    G.cells[a] = occ->cells[a]; G.lo[a] = occ->lo[a]; G.step[a] = occ->step[a];
+    const float span = (float)occ->cells[a] * occ->step[a];   // the last grid point: multiply, then add (ops.grid_points)
+    G.hi[a] = occ->lo[a] + span;
+    if (!std::isfinite(G.hi[a])) return "occupancy box not finite";
+  }
+  return nullptr;
+}
+
 // The call record of the whole-path forward entry points: what aon_render_fwd* / aon_art_render_fwd* /
 // aon_*render_fwd_train* / aon_grender_fwd* have in common.  An exported function lists its parameters once -- that list is the ABI --
 // builds the record with path_call() and passes the record on; nothing behind it takes those parameters by position again.

@@ -213,6 +213,14 @@ hipError_t launch_occ_compact_round(const OccGrid& G, const float* rays_o, const
 hipError_t launch_occ_depth(const float* raw, const float* t_vals, const float* dirs, int64_t n, int S, int s0, int s1, const ActParams& ap,
                             float tau_stop, char* state, hipStream_t stream);
 
+// ---- aon_scene_occ.hip: launch_occ_compact for the K object segments of a scene's pair rows at once ----
+// grids: K records, bits == nullptr: a dense object (no tile, not touched); starts: K + 1 segment starts in rows.  ws: scene_occ_list_bytes()
+// bytes, 256-byte aligned -> idx (object k's list of segment-local sample indices at idx + starts[k] * S) and counts (K int64: the lists'
+// lengths, starts-difference * S for a dense object), which are also added to tally[k] when tally is given
+int64_t scene_occ_list_bytes(int64_t pairs, int K, int S);
+hipError_t launch_scene_occ_compact(const OccGrid* grids, const int64_t* starts, int K, int S, const float* pair_o, const float* pair_d,
+                                    const float* t_vals, float* raw, char* ws, int64_t* tally, const int** idx_out, const int64_t** counts_out,
+                                    hipStream_t stream);
 
 // ---- aon_bounds.hip: per-ray near / far from a ray-box intersection ----
 int64_t ray_limits_workspace_bytes(int64_t n);

@@ -23,6 +23,7 @@
 //       MLP launch reads its pass count from (no host synchronisation) and adds to the caller's per-level tally;
 //   (c) emit: the lookup again, and the ascending list of occupied sample indices at the scanned offsets.
 #include "aon_launch.h"
+#include "aon_occ_lookup.h"
 
 namespace aon {
 
@@ -62,19 +63,7 @@ hipError_t launch_occ_build(const float* dens, const int64_t* dims, float thr, i
   return hipGetLastError();
 }
 
-// ---- per-level sample marking and compaction ----
-__device__ __forceinline__ bool occ_lookup(const OccGrid& G, const float (&x)[3]) {
-  int64_t c[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (!(x[a] >= G.lo[a] && x[a] <= G.hi[a])) return false;   // outside the box, or NaN
-    const int64_t q = (int64_t)__builtin_floorf(__fdiv_rn(__fsub_rn(x[a], G.lo[a]), G.step[a]));
-    c[a] = q < G.cells[a] - 1 ? q : G.cells[a] - 1;
-  }
-  const int64_t lin = (c[0] * G.cells[1] + c[1]) * G.cells[2] + c[2];
-  return (G.bits[lin >> 5] >> (lin & 31)) & 1u;
-}
-
+// ---- per-level sample marking and compaction (the lookup itself: occ_lookup, aon_occ_lookup.h) ----
 struct OccSamples {
   const float* rays_o; const float* rays_d; const float* t_vals;   // (n,3), (n,3), (n,S)
   int64_t total; int S;                                             // n * S <= INT32_MAX (the caller's chunking)

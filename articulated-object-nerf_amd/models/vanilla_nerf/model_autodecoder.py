@@ -226,6 +226,22 @@ class LitNeRF_AutoDecoder(Harness):
         self.model = NeRF_AE_Art(**(model_kwargs or {}))   # the reference builds NeRF_AE_Art() (model_autodecoder.py:352)
         self.code_library = CodeLibraryArticulated(self.hparams)
 
+    @property
+    def _scene_grids(self) -> dict:
+        """render_scene(occupancy=...)'s grids, keyed by (instance_id, articulation, arguments); not a module attribute torch would see.
+        The dict is emptied whenever a parameter of the network or of the code library has been replaced or written through autograd's
+        version counter since the grids were built: an optimiser step, `load_state_dict` on this module or on `model` / `code_library`,
+        `p.copy_()`, `p.mul_()` ...  A write that bypasses the counter (`p.data.copy_()`) is not seen: call clear_scene_grids()."""
+        stamp = tuple((p.data_ptr(), p._version) for m in (self.model, self.code_library) for p in m.parameters())
+        if self.__dict__.get("_scene_grid_stamp") != stamp:
+            self.__dict__["_scene_grid_stamp"] = stamp
+            self.__dict__["_scene_grid_cache"] = {}
+        return self.__dict__.setdefault("_scene_grid_cache", {})
+
+    def clear_scene_grids(self) -> None:
+        """Drop the occupancy grids render_scene(occupancy=...) keeps (after a change of the weights that torch's version counters miss)."""
+        self.__dict__["_scene_grid_cache"] = {}
+
     def setup(self, dataset):
         self.near, self.far, self.white_bkgd = dataset.near, dataset.far, dataset.white_back
 
@@ -353,13 +369,26 @@ class LitNeRF_AutoDecoder(Harness):
         return self.render_rays_test(batch, self.code_library(batch, is_test=True))
 
     @torch.no_grad()
-    def render_scene(self, batch, placements):
+    def render_scene(self, batch, placements, occupancy=None):
         """Several instances of the library in ONE frame (scene.render_scene): ``placements`` is a list of up to 16
         ``(instance_id, articulation, pose, box)`` -- ``articulation`` a row index into get_interpolated_articulations (the 19 rows of the
         test epoch) or an explicit (32,) code, ``pose`` the (3, 4) rigid object-to-world matrix, ``box`` the object's box in its own
         frame -- and ``batch`` holds the WORLD rays ("rays_o", "rays_d", "viewdirs"; "target" / "instance_mask" are passed through when
-        present).  -> {"rgb" (N, 3), "acc" (N,), "depth" (N,), "obj_acc" (N, K)} of the last level, rendered hparams.chunk rays at a time."""
+        present).  -> {"rgb" (N, 3), "acc" (N,), "depth" (N,), "obj_acc" (N, K)} of the last level, rendered hparams.chunk rays at a time.
+        ``occupancy``: None, or a dict of occupancy.build_occupancy's keyword arguments (``bounds``, ``resolution``,
+        ``threshold``, ``dilate``, ``level``; the bounds must enclose every box): one grid is built per distinct (instance_id, articulation)
+        among the placements and the objects' empty space is skipped.  In eval mode the grids are kept on the module, keyed by those and the
+        arguments, until train() / eval() or load_state_dict() is called or a parameter of the network or the code library changes (their
+        version counters are compared on every call; clear_scene_grids() drops them by hand): a stale grid is a wrong picture.  The dict gains "occupied", the
+        (K,) samples of the last level that ran through the MLP."""
+        from ... import occupancy as _occupancy
         from ...scene import SceneObject, render_scene
+
+        if occupancy is not None:
+            if not isinstance(occupancy, dict) or not set(occupancy) <= set(self._OCC_KEYS):
+                raise ValueError(f"render_scene: occupancy must be None or a dict with keys among {list(self._OCC_KEYS)}, got {occupancy!r}")
+            occ_args = {"bounds": (-1.2, 1.2), **occupancy}
+            occ_key = tuple(repr(occ_args.get(k)) for k in self._OCC_KEYS)
 
         dev = next(self.model.parameters()).device
         table = self.code_library.get_interpolated_articulations(max_interpolations=2, device=dev)
@@ -380,12 +409,37 @@ class LitNeRF_AutoDecoder(Harness):
             ids = torch.tensor([iid], dtype=torch.int64, device=dev)
             latents = {"density": self.code_library.embedding_instance_shape(ids), "color": self.code_library.embedding_instance_appearance(ids),
                        "articulation": code}
-            objects.append(SceneObject(latents, pose, box))
+            grid = None
+            if occupancy is not None:
+                key = (iid, art if isinstance(art, int) else tuple(code.reshape(-1).tolist()), occ_key)
+                grid = self._scene_grids.get(key)
+                if grid is None:
+                    grid = _occupancy.build_occupancy(self.model, latents=latents, **occ_args)
+                    self._scene_grids[key] = grid
+            objects.append(SceneObject(latents, pose, box, grid))
         rays = {k: batch[k].reshape(-1, 3) for k in ("rays_o", "rays_d", "viewdirs")}
-        rgb, acc, depth, obj_acc = render_scene(self.model, objects, rays, self.white_bkgd, chunk=self.hparams.chunk)[-1]
+        levels = render_scene(self.model, objects, rays, self.white_bkgd, chunk=self.hparams.chunk, want_occupied=occupancy is not None)
+        if occupancy is not None:
+            levels, occupied = levels
+        if self.training:      # the weights may move before the next frame
+            self._scene_grids.clear()
+        rgb, acc, depth, obj_acc = levels[-1]
         ret = {"rgb": rgb, "acc": acc, "depth": depth, "obj_acc": obj_acc}
+        if occupancy is not None:
+            ret["occupied"] = occupied[-1]
         ret.update({k: batch[k] for k in ("target", "instance_mask") if k in batch})
         return ret
+
+    _OCC_KEYS = ("bounds", "resolution", "threshold", "dilate", "level")
+
+    def train(self, mode: bool = True):
+        if "model" in self._modules:      # (nn.Module.__init__ does not call this, but a subclass may before the network exists)
+            self.clear_scene_grids()      # render_scene(occupancy=...)'s grids belong to the weights they were built from
+        return super().train(mode)
+
+    def load_state_dict(self, *args, **kwargs):
+        self.clear_scene_grids()
+        return super().load_state_dict(*args, **kwargs)
 
     def configure_optimizers(self):
         return build_adam([self.model, self.code_library], self.lr_init)   # (model_autodecoder.py:604-606; one arena, one launch: LitNeRF)

@@ -2027,3 +2027,42 @@ def scene_art_mlp_fwd(packed, smalls, pairs: ScenePairs, t_vals) -> torch.Tensor
         if seg.stop > seg.start:
             art_mlp_fwd(packed, smalls[k], pairs.rays_o[seg], pairs.rays_d[seg], pairs.viewdirs[seg], t[seg], out=raw[seg])
     return raw
+
+
+# ------------------------------------------------------------------ occupancy grids for scenes
+_SCENE_OCC_WS = StreamCache()
+
+
+def scene_art_mlp_fwd_occ(packed, smalls, grids, pairs: ScenePairs, t_vals):
+    """scene_art_mlp_fwd with an optional OccupancyGrid per object (`grids[k]`, in object k's own frame -- the frame of `pairs.rays_o` /
+    `pairs.rays_d`; None: dense): a sample in an empty cell of its object's grid gets the record (0, 0, 0, -inf) and never reaches the MLP
+    (include/aon_hip_scene_occ.h).  One C call.  -> (raw (P, S, 4), occupied (K,) int64 on the device: the samples of each object that ran
+    through the MLP, all of its segment's for a dense object).  With every grid None the bits are scene_art_mlp_fwd's."""
+    t = _f32(t_vals, "t_vals")
+    K, P, dev = pairs.K, pairs.P, t.device
+    grids = list(grids)
+    if len(smalls) != K or len(grids) != K or t.dim() != 2 or t.shape[0] != P:
+        raise ValueError(f"scene_art_mlp_fwd_occ: expected {K} per-call blocks, {K} grids (or None) and t_vals of {P} rows")
+    for k, g in enumerate(grids):
+        if g is not None and not isinstance(g, OccupancyGrid):
+            raise TypeError(f"scene_art_mlp_fwd_occ: grids[{k}] must be an ops.OccupancyGrid (ops.occupancy_grid) or None, got {type(g)}")
+        if g is not None and g.device != dev:
+            raise ValueError(f"scene_art_mlp_fwd_occ: grids[{k}] is on {g.device}, the pairs on {dev}")
+    S = t.shape[1]
+    raw = torch.empty((P, S, 4), dtype=torch.float32, device=dev)
+    occupied = torch.zeros((K,), dtype=torch.int64, device=dev)
+    if P == 0:      # nothing to launch (and no pointer to hand over)
+        return raw, occupied
+    need = int(lib.aon_scene_occ_workspace_bytes(P, K, S))
+    if need <= 0:
+        raise ValueError(f"scene_art_mlp_fwd_occ: {P} pairs of {S} samples are more than 2^31 - 1 samples: render fewer rays per chunk")
+    ws = _scratch(_SCENE_OCC_WS, dev, need)
+    structs = [None if g is None else g.c_struct() for g in grids]      # (kept alive until the call has returned)
+    grid_arr = (C.c_void_p * K)(*[None if st is None else C.addressof(st) for st in structs])
+    small_arr = (C.c_void_p * K)(*[_pk(s).value for s in smalls])
+    starts = (C.c_int64 * (K + 1))(*pairs.starts)
+    o, d, v = _f32(pairs.rays_o, "pairs.rays_o"), _f32(pairs.rays_d, "pairs.rays_d"), _f32(pairs.viewdirs, "pairs.viewdirs")
+    with torch.cuda.device(dev):
+        check(lib.aon_scene_art_mlp_fwd_occ(_pk(packed), small_arr, grid_arr, starts, _ptr(o), _ptr(d), _ptr(v), _ptr(t), K, S, _ptr(raw),
+                                            _ptr(occupied), _ptr(ws), ws.numel(), _stream()), "aon_scene_art_mlp_fwd_occ")
+    return raw, occupied

@@ -5,7 +5,9 @@ ray-box test per object, samples inside each box, one sorted merge along the ray
 Per chunk of rays: ``ops.scene_pairs`` pairs rays with the boxes they cross (one host read-back: the pair counts), the existing per-ray-bounds
 sampler, MLP kernel and inverse-CDF kernel run on the pairs -- the MLP once per object segment with that object's per-call block -- and
 ``ops.scene_composite`` merges a ray's lists by distance.  The second level's draws come from the MERGED weights, so parts hidden behind
-another object get few fine samples."""
+another object get few fine samples.
+
+An object may carry an occupancy grid in its own frame: its samples in empty cells get zero density and skip the MLP."""
 from __future__ import annotations
 
 import torch
@@ -18,9 +20,11 @@ _LATENT_WIDTHS = dict(ops._LATENT_KEYS)
 class SceneObject:
     """One placed object: ``latents`` {"density" (1, 128), "color" (1, 128), "articulation" (1, 32)} as ``NeRF_AE_Art.forward`` takes them,
     ``pose`` the (3, 4) rigid object-to-world matrix [R | c] (orthonormal R, det > 0: no scale), ``box`` the axis-aligned box in the
-    object's frame (a side length, or (lo, hi): ``ops._box3``)."""
+    object's frame (a side length, or (lo, hi): ``ops._box3``), ``grid`` an optional ``ops.OccupancyGrid`` built under the same latents in the
+    object's frame (``occupancy.build_occupancy``).  The grid's extent must contain the box: a sample outside the grid counts as empty, so
+    the part of a box that sticks out of it would be silently cut away."""
 
-    def __init__(self, latents: dict, pose, box):
+    def __init__(self, latents: dict, pose, box, grid=None):
         if not isinstance(latents, dict) or set(latents) != set(_LATENT_WIDTHS):
             raise ValueError(f"SceneObject: latents needs exactly the keys {sorted(_LATENT_WIDTHS)}")
         for key, width in _LATENT_WIDTHS.items():
@@ -28,8 +32,21 @@ class SceneObject:
                 raise ValueError(f"SceneObject: latents[{key!r}] must be a tensor of {width} values")
         self.latents = latents
         self.pose = ops.check_pose(pose, "SceneObject: pose")
-        ops._box3(box)      # raises for a malformed box
+        lo, hi = ops._box3(box)      # raises for a malformed box
         self.box = box
+        if grid is not None:
+            if not isinstance(grid, ops.OccupancyGrid):
+                raise TypeError(f"SceneObject: grid must be an ops.OccupancyGrid (occupancy.build_occupancy) or None, got {type(grid)}")
+            g_lo = grid.lo
+            g_hi = grid.lo + torch.tensor(grid.cells, dtype=torch.float32) * grid.step      # multiply, then add: the last grid point
+            b_lo, b_hi = torch.tensor(list(lo), dtype=torch.float32), torch.tensor(list(hi), dtype=torch.float32)
+            if not bool(((g_lo <= b_lo) & (b_hi <= g_hi)).all()):
+                raise ValueError(f"SceneObject: the grid spans {g_lo.tolist()} .. {g_hi.tolist()} and does not contain the box "
+                                 f"{b_lo.tolist()} .. {b_hi.tolist()}: samples outside the grid count as empty, so that part of the box would "
+                                 "be cut away; build the grid over bounds that enclose the box")
+            if not grid.bits.is_cuda:
+                raise ValueError(f"SceneObject: the grid is on {grid.bits.device}; it must be on a cuda (ROCm) device")
+        self.grid = grid
 
 
 def _check_objects(objects) -> list:
@@ -42,10 +59,13 @@ def _check_objects(objects) -> list:
     return objects
 
 
-def render_scene(model, objects, rays, white_bkgd, chunk: int = 65536, randomized: bool = False) -> list:
+def render_scene(model, objects, rays, white_bkgd, chunk: int = 65536, randomized: bool = False, want_occupied: bool = False):
     """``model``: a NeRF_AE_Art; ``objects``: 1 to 16 SceneObject; ``rays``: {"rays_o", "rays_d", "viewdirs"} (N, 3) in WORLD coordinates.
     -> ``[(rgb (N, 3), acc (N,), depth (N,), obj_acc (N, K))]`` per level, the shape ``forward`` returns with the per-object opacity appended.
-    A ray that meets no box returns the background (rgb 1 or 0, acc = depth = 0)."""
+    A ray that meets no box returns the background (rgb 1 or 0, acc = depth = 0).
+    When an object carries a grid, the levels' MLP stage is ``ops.scene_art_mlp_fwd_occ``; without grids it is ``ops.scene_art_mlp_fwd``, as
+    ever.  ``want_occupied``: -> ``(levels, occupied)`` with ``occupied[level]`` the (K,) int64 device tensor of the samples of each object
+    that ran through the MLP (all of an object's samples when it has no grid)."""
     if randomized:
         raise ValueError("scene rendering is inference only: randomized=True is refused")
     if torch.is_grad_enabled():
@@ -66,15 +86,30 @@ def render_scene(model, objects, rays, white_bkgd, chunk: int = 65536, randomize
     smalls = [[ops.art_prepare(dict(m.named_parameters()), ob.latents, out=None, degrees=m.degrees) for ob in objects] for m in mlps]
     opts = model._opts
     parts = [[] for _ in mlps]
+    grids = [ob.grid for ob in objects]
+    with_occ = any(g is not None for g in grids)
+    # per level: the device tallies of the occupancy call, or -- without grids -- the host's own counts, uploaded once at the end
+    occupied = [torch.zeros((len(objects),), dtype=torch.int64, device=o.device) for _ in mlps] if want_occupied and with_occ else None
+    host_counts = [[0] * len(objects) for _ in mlps] if want_occupied and not with_occ else None
     for c0 in range(0, max(n, 1), chunk):
         co, cd, cv = o[c0: c0 + chunk], d[c0: c0 + chunk], v[c0: c0 + chunk]
         pairs = ops.scene_pairs(co, cd, cv, objects)
         t, _ = ops.sample_along_rays(pairs.rays_o, pairs.rays_d, model.num_coarse_samples, pairs.near, pairs.far, want_coords=False, lindisp=model.lindisp)
         for level in range(len(mlps)):
             last = level == len(mlps) - 1
-            raw = ops.scene_art_mlp_fwd(packed[level], smalls[level], pairs, t)
+            if with_occ:
+                raw, occ = ops.scene_art_mlp_fwd_occ(packed[level], smalls[level], grids, pairs, t)
+                if want_occupied:
+                    occupied[level] += occ
+            else:
+                raw = ops.scene_art_mlp_fwd(packed[level], smalls[level], pairs, t)
+                if want_occupied:
+                    host_counts[level] = [a + c * t.shape[1] for a, c in zip(host_counts[level], pairs.counts)]
             rgb, acc, depth, obj_acc, weights = ops.scene_composite(raw, t, pairs, cd, white_bkgd, opts=opts, want_weights=not last)
             parts[level].append((rgb, acc, depth, obj_acc))
             if not last:
                 t = ops.sample_pdf_t_n(t, weights, model.num_fine_samples)
-    return [tuple(torch.cat([p[i] for p in lvl]) for i in range(4)) for lvl in parts]
+    levels = [tuple(torch.cat([p[i] for p in lvl]) for i in range(4)) for lvl in parts]
+    if host_counts is not None:
+        occupied = [torch.tensor(c, dtype=torch.int64).to(o.device) for c in host_counts]
+    return (levels, occupied) if want_occupied else levels

@@ -10,7 +10,13 @@ cover different shares of the frame; one JSON line per scene and everything agai
 The weights are the synthetic ones (timing does not depend on what the network has learnt).  For the kernels alone run it under
 `rocprofv3 --kernel-trace --stats -- python tools/scene_bench.py` and read scene_pair_*_kernel / scene_composite_kernel.
 
-    python tools/scene_bench.py [--reps 5] [--out profiles/scene_bench.json]
+--occupancy adds a leg per scene: the same frame with an occupancy grid on every object -- FULL grids (every cell
+set: the three compaction launches and the gather launches against the dense ones, nothing skipped), then grids built from the bench's own
+field at section 4.9's defaults (128^3 cells over [-1.2, 1.2]^3, threshold 0.01, dilate 1) -- with the frame without grids re-measured in
+the same run, the samples that reached the MLP per level, and the gather-to-dense per-sample rate of the MLP stage.  When the synthetic
+field is too hazy for a grid to empty anything, that is reported and the leg is repeated on synthetic.sparsify_nerf_(latents=)'s field.
+
+    python tools/scene_bench.py [--reps 5] [--occupancy] [--out profiles/scene_bench.json]
 """
 import argparse
 import json
@@ -80,22 +86,86 @@ class Stages:
 
 
 def staged_frame(model, objects, rays, st):
-    """scene.render_scene's flow for one chunk, every stage under its own pair of events"""
+    """scene.render_scene's flow for one chunk, every stage under its own pair of events (objects with grids: the occupancy stage call)"""
+    grids = [ob.grid for ob in objects]
+    occ = any(g is not None for g in grids)
     mlps = [model.coarse_mlp, model.fine_mlp]
     smalls = [[ops.art_prepare(dict(m.named_parameters()), ob.latents, degrees=m.degrees) for ob in objects] for m in mlps]
     pairs = st.run("pairs", lambda: ops.scene_pairs(rays["rays_o"], rays["rays_d"], rays["viewdirs"], objects))
     t = st.run("sample", lambda: ops.sample_along_rays(pairs.rays_o, pairs.rays_d, 64, pairs.near, pairs.far, want_coords=False)[0])
     for level, m in enumerate(mlps):
-        raw = st.run("mlp", lambda: ops.scene_art_mlp_fwd(m.packed(), smalls[level], pairs, t))
+        if occ:
+            raw = st.run("mlp", lambda: ops.scene_art_mlp_fwd_occ(m.packed(), smalls[level], grids, pairs, t)[0])
+        else:
+            raw = st.run("mlp", lambda: ops.scene_art_mlp_fwd(m.packed(), smalls[level], pairs, t))
         out = st.run("composite", lambda: ops.scene_composite(raw, t, pairs, rays["rays_d"], True, want_weights=level == 0))
         if level == 0:
             t = st.run("sample", lambda: ops.sample_pdf_t_n(t, out[4], 128))
     return pairs
 
 
+def staged_mlp_ms(model, objects, rays, reps):
+    """median over `reps` staged frames (after a warm-up) of the MLP stage's device time, both levels"""
+    staged_frame(model, objects, rays, Stages())
+    runs = []
+    for _ in range(reps):
+        st = Stages()
+        staged_frame(model, objects, rays, st)
+        runs.append(st.totals()["mlp"])
+    return statistics.median(runs)
+
+
+def with_grids(objects, grids):
+    return [scene.SceneObject(ob.latents, ob.pose, ob.box, g) for ob, g in zip(objects, grids)]
+
+
+OCC_BOUNDS = (-1.2, 1.2)        # section 4.9's defaults; every box of make_scene (side <= 1.3) lies inside
+
+
+def occupancy_leg(model, objects, rays, n, reps, ms_dense, mlp_dense, tag):
+    """one set of grids on `objects` -> the leg's record; ms_dense / mlp_dense: the frame and MLP stage without grids, same run, same model"""
+    _, occupied = scene.render_scene(model, objects, rays, True, chunk=n, want_occupied=True)
+    _, total = scene.render_scene(model, with_grids(objects, [None] * len(objects)), rays, True, chunk=n, want_occupied=True)
+    ms = frame_time(lambda: scene.render_scene(model, objects, rays, True, chunk=n), reps) * 1e3
+    mlp = staged_mlp_ms(model, objects, rays, reps)
+    run, tot = [int(o.sum()) for o in occupied], [int(o.sum()) for o in total]
+    return {"grids": tag, "ms_frame": round(ms, 3), "frame_vs_no_grids": round(ms / ms_dense, 4), "ms_mlp_stage": round(mlp, 3),
+            "samples_run": run, "samples_total": tot, "share_run": [round(r / max(t, 1), 4) for r, t in zip(run, tot)],
+            "share_run_per_object_fine": [round(int(r) / max(int(t), 1), 4) for r, t in zip(occupied[-1].tolist(), total[-1].tolist())],
+            "cells_occupied_per_object": [round(ob.grid.occupied_fraction(), 4) for ob in objects],
+            # samples per millisecond of the MLP stage (compaction launches included) over the dense stage's
+            "gather_to_dense_rate": round((sum(run) / mlp) / (sum(tot) / mlp_dense), 4)}
+
+
+def occupancy_record(model, objects, rays, n, reps, dev):
+    from aon_amd.models.vanilla_nerf.model_autodecoder import NeRF_AE_Art
+    from aon_amd.occupancy import build_occupancy
+
+    ms_dense = frame_time(lambda: scene.render_scene(model, objects, rays, True, chunk=n), reps) * 1e3
+    mlp_dense = staged_mlp_ms(model, objects, rays, reps)
+    full = ops.occupancy_grid(torch.ones(5, 5, 5, device=dev), OCC_BOUNDS[0], OCC_BOUNDS[1], 0.01, 0)
+    rec = {"ms_frame_no_grids": round(ms_dense, 3), "ms_mlp_stage_no_grids": round(mlp_dense, 3),
+           "legs": [occupancy_leg(model, with_grids(objects, [full] * len(objects)), rays, n, reps, ms_dense, mlp_dense, "full")]}
+    field = [build_occupancy(model, OCC_BOUNDS, latents=ob.latents) for ob in objects]
+    rec["legs"].append(occupancy_leg(model, with_grids(objects, field), rays, n, reps, ms_dense, mlp_dense, "field (128^3, threshold 0.01, dilate 1)"))
+    if min(g.occupied_fraction() for g in field) > 0.99:
+        rec["finding"] = "the synthetic articulated field is too hazy for a grid to empty anything; repeated on synthetic.sparsify_nerf_(latents=)'s field"
+        sparse = NeRF_AE_Art().to(dev)
+        sparse.load_state_dict(model.state_dict())
+        syn.sparsify_nerf_(sparse, 0.8, OCC_BOUNDS[1], latents=objects[0].latents)
+        ms_sparse = frame_time(lambda: scene.render_scene(sparse, objects, rays, True, chunk=n), reps) * 1e3
+        mlp_sparse = staged_mlp_ms(sparse, objects, rays, reps)
+        grids = [build_occupancy(sparse, OCC_BOUNDS, latents=ob.latents) for ob in objects]
+        leg = occupancy_leg(sparse, with_grids(objects, grids), rays, n, reps, ms_sparse, mlp_sparse, "sparsified field (128^3, threshold 0.01, dilate 1)")
+        leg["ms_frame_no_grids"] = round(ms_sparse, 3)
+        rec["legs"].append(leg)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--occupancy", action="store_true", help="add the occupancy-grid legs (DESIGN.md section 4.17)")
     ap.add_argument("--objects", type=int, nargs="+", default=[1, 3, 8])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_bench.json"))
     args = ap.parse_args()
@@ -131,6 +201,8 @@ def main():
                    "pairs": pairs.P, "pairs_per_ray": round(pairs.P / n, 4), "rays_with_a_pair": round(float((pairs.slot >= 0).any(1).float().mean()), 4),
                    "mlp_samples": pairs.P * (65 + 193), "mlp_samples_dense_one_object": n * (65 + 193),
                    "ms_one_whole_frame_art_render_fwd": round(ms_single, 3), "ms_k_whole_frame_renders": round(K * ms_single, 3)}
+            if args.occupancy:
+                rec["occupancy"] = occupancy_record(model, objects, rays, n, args.reps, dev)
             print(json.dumps(rec), flush=True)
             recs.append(rec)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)

@@ -105,6 +105,14 @@ static hipError_t launch_net(const NetRef& net, const float* o, const float* d, 
     if (e != hipSuccess) return e;
     vbias = w->vbias;
   }
+  const int* idx = nullptr;
+  const int64_t* count = nullptr;
+  // the compaction of the level's samples [s0, s1) of every ray (aon_occ.hip): one segment, the buffers laid out for the whole level
+  auto compact = [&](int s0, int s1, const int* stop) {
+    const int64_t starts[2] = {0, n};
+    const aon::OccCompact c{&occ->grid, starts, 1, S, s0, s1, o, d, t, live, stop};
+    return aon::launch_occ_compact(c, raw, w->occ, (n * S + 1023) / 1024, occ->tally ? occ->tally + level : nullptr, &idx, &count, stream);
+  };
   if (occ && occ->rounds) {
     // per round: mark -> scan -> emit -> the GATHER launch on the round's list -> the live rays' optical depth; all stream-ordered
     if (hipError_t e = aon::launch_occ_stop_init(w->stop, n, S, stream); e != hipSuccess) return e;
@@ -112,12 +120,7 @@ static hipError_t launch_net(const NetRef& net, const float* o, const float* d, 
     const aon::ActParams ap = g->act(net.articulated, level, 0);   // (no noise on this path)
     for (int s0 = 0; s0 < S; s0 += R) {
       const int s1 = s0 + R < S ? s0 + R : S;
-      const int* idx = nullptr;
-      const int64_t* count = nullptr;
-      if (hipError_t e = aon::launch_occ_compact_round(occ->grid, o, d, t, n, S, s0, s1, w->stop, raw, w->occ, occ->tally ? occ->tally + level : nullptr,
-                                                       &idx, &count, stream, live);
-          e != hipSuccess)
-        return e;
+      if (hipError_t e = compact(s0, s1, aon::occ_stop_state(w->stop, n).stop); e != hipSuccess) return e;
       {
         MlpTimer timer(stream, n * (s1 - s0));
         const hipError_t e = net.articulated ? aon::launch_art_mlp_fwd_gather(static_cast<const char*>(net.packed), net.small, o, d, v, t, n, S, raw, stream,
@@ -132,12 +135,7 @@ static hipError_t launch_net(const NetRef& net, const float* o, const float* d, 
     return hipSuccess;
   }
   if (occ) {
-    const int* idx = nullptr;
-    const int64_t* count = nullptr;
-    if (hipError_t e = aon::launch_occ_compact(occ->grid, o, d, t, n, S, raw, w->occ, occ->tally ? occ->tally + level : nullptr, &idx, &count, stream,
-                                                live);
-        e != hipSuccess)
-      return e;
+    if (hipError_t e = compact(0, S, nullptr); e != hipSuccess) return e;
     MlpTimer timer(stream, n * S);
     if (net.articulated)
       return aon::launch_art_mlp_fwd_gather(static_cast<const char*>(net.packed), net.small, o, d, v, t, n, S, raw, stream, vbias, idx, count);

@@ -274,6 +274,33 @@ __device__ __forceinline__ T block_excl_scan(T v, T& total, T* red) {
   return base + x - v;
 }
 
+// ONE 256-thread workgroup turns n tile counts into their exclusive offsets, in tile order, and returns their total: 2,048 counts a round
+// (8 per thread, block_excl_scan over the threads' sums, the total carried into the next round).  `red`: __shared__ int64_t[4].
+template <class C, class O>
+__device__ __forceinline__ int64_t block_scan_counts(const C* __restrict__ counts, int64_t n, O* __restrict__ offs, int64_t* red) {
+  constexpr int kThreads = 256, kPer = 8;
+  int64_t carry = 0;
+  for (int64_t base = 0; base < n; base += (int64_t)kThreads * kPer) {
+    const int64_t t0 = base + (int64_t)threadIdx.x * kPer;
+    C cv[kPer];
+    int64_t sv = 0;
+#pragma unroll
+    for (int r = 0; r < kPer; ++r) {
+      cv[r] = t0 + r < n ? counts[t0 + r] : 0;
+      sv += cv[r];
+    }
+    int64_t tv;
+    int64_t run = carry + block_excl_scan<int64_t>(sv, tv, red);
+#pragma unroll
+    for (int r = 0; r < kPer; ++r) {
+      if (t0 + r < n) offs[t0 + r] = (O)run;
+      run += cv[r];
+    }
+    carry += tv;
+  }
+  return carry;
+}
+
 // An occupancy grid as the kernels see it (aon_occupancy, include/aon_hip.h; aon_occ.hip): hi = lo + cells * step, multiply then add
 struct OccGrid {
   const uint32_t* bits;

@@ -198,29 +198,33 @@ hipError_t launch_mc(const float* grid, const int64_t* dims, float level, const 
 
 // ---- aon_occ.hip ----
 hipError_t launch_occ_build(const float* dens, const int64_t* dims, float thr, int dilate, uint32_t* bits, hipStream_t stream);
+// One compaction (mark / scan / emit) of K segments of rows, each against its own grid, over the sample window [s0, s1) of every row.
+struct OccCompact {
+  const OccGrid* grids;      // K records; bits == nullptr: no grid (every cell occupied)
+  const int64_t* starts;     // K + 1 segment starts in rows; starts[K] * S <= INT32_MAX
+  int K, S, s0, s1;          // [0, S): a whole level
+  const float* rays_o; const float* rays_d; const float* t_vals;   // (rows,3), (rows,3), (rows,S)
+  const uint8_t* ray_live;   // (rows,) or null: a dead ray's samples get the sentinel record and are not listed
+  const int* stop;           // (rows,) or null: so do the samples i >= stop[row] (occ_stop_state().stop)
+};
+// A segment without a grid, with ray_live and stop null, is DENSE: not touched, its count all of its samples.  ws: 256-byte aligned, as
+// occ_list_bytes / scene_occ_list_bytes size it, tile_cap the tile capacity that function used (ceil(total / 1024) / scene_occ_tile_cap)
+// -> idx (segment k's ascending list of segment-local sample indices row_local * S + i at idx + starts[k] * S) and counts (K int64: the
+// lists' lengths, the device counters of the gather launches), which are also added to tally[k] when tally is given
 int64_t occ_list_bytes(int64_t total);
-// ray_live (n bytes, or null: every ray is live): a dead ray's samples get the sentinel record and are not listed.  G.bits == nullptr: no grid
-hipError_t launch_occ_compact(const OccGrid& G, const float* rays_o, const float* rays_d, const float* t_vals, int64_t n, int S, float* raw,
-                              char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out, hipStream_t stream,
-                              const uint8_t* ray_live = nullptr);
+int64_t scene_occ_tile_cap(int64_t pairs, int K, int S);
+int64_t scene_occ_list_bytes(int64_t pairs, int K, int S);
+hipError_t launch_occ_compact(const OccCompact& c, float* raw, char* ws, int64_t tile_cap, int64_t* tally, const int** idx_out,
+                              const int64_t** counts_out, hipStream_t stream);
+// early termination: the per-ray state of a level, tau (fp32) then stop (int32), each padded to 256 bytes (state == nullptr: both null)
+struct OccStopState { float* tau; int* stop; };
 int64_t occ_stop_state_bytes(int64_t n);
+OccStopState occ_stop_state(char* state, int64_t n);
 hipError_t launch_occ_stop_init(char* state, int64_t n, int S, hipStream_t stream);
-hipError_t launch_occ_stop_store(const char* state, int value, int* dst, int64_t n, int stride, hipStream_t stream);
+hipError_t launch_occ_stop_store(char* state, int value, int* dst, int64_t n, int stride, hipStream_t stream);
 hipError_t launch_occ_tally_set(int64_t* tally, int64_t v0, int64_t v1, hipStream_t stream);
-hipError_t launch_occ_compact_round(const OccGrid& G, const float* rays_o, const float* rays_d, const float* t_vals, int64_t n, int S, int s0, int s1,
-                                    const char* state, float* raw, char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out,
-                                    hipStream_t stream, const uint8_t* ray_live = nullptr);
 hipError_t launch_occ_depth(const float* raw, const float* t_vals, const float* dirs, int64_t n, int S, int s0, int s1, const ActParams& ap,
                             float tau_stop, char* state, hipStream_t stream);
-
-// ---- aon_scene_occ.hip: launch_occ_compact for the K object segments of a scene's pair rows at once ----
-// grids: K records, bits == nullptr: a dense object (no tile, not touched); starts: K + 1 segment starts in rows.  ws: scene_occ_list_bytes()
-// bytes, 256-byte aligned -> idx (object k's list of segment-local sample indices at idx + starts[k] * S) and counts (K int64: the lists'
-// lengths, starts-difference * S for a dense object), which are also added to tally[k] when tally is given
-int64_t scene_occ_list_bytes(int64_t pairs, int K, int S);
-hipError_t launch_scene_occ_compact(const OccGrid* grids, const int64_t* starts, int K, int S, const float* pair_o, const float* pair_d,
-                                    const float* t_vals, float* raw, char* ws, int64_t* tally, const int** idx_out, const int64_t** counts_out,
-                                    hipStream_t stream);
 
 // ---- aon_bounds.hip: per-ray near / far from a ray-box intersection ----
 int64_t ray_limits_workspace_bytes(int64_t n);

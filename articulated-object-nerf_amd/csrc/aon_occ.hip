@@ -17,18 +17,21 @@
 //   * an empty sample's raw record is (0, 0, 0, -inf): relu(-inf) = 0 and softplus(-inf + sigma_bias) = 0 exactly (softplus_f32 takes
 //     exp2(-inf) = 0), so its density is exactly zero under both activations and its weight is exactly zero.
 //
-// Per level and render chunk, three launches over tiles of kOccTile = 1024 consecutive samples (256 threads x 4), as aon_mesh.hip:
+// Per level and render chunk (or round, section 4.10; or scene level, section 4.17), three launches over tiles of kOccTile = 1024 samples:
 //   (a) mark: look every sample up, write the sentinel record of the empty ones, count the occupied ones of the tile;
 //   (b) scan: ONE workgroup turns the tile counts into exclusive offsets and the total, which it writes to the device counter the gather
-//       MLP launch reads its pass count from (no host synchronisation) and adds to the caller's per-level tally;
+//       MLP launch reads its pass count from (no host synchronisation) and adds to the caller's tally;
 //   (c) emit: the lookup again, and the ascending list of occupied sample indices at the scanned offsets.
 #include "aon_launch.h"
+#include "../../include/aon_hip_scene.h"
 #include "aon_occ_lookup.h"
 
 namespace aon {
 
 constexpr int kOccTile = 1024;
 constexpr int kOccThreads = 256;
+constexpr int kOccPer = kOccTile / kOccThreads;
+constexpr int kOccWaves = kOccThreads / 64;
 
 // ---- build: density grid -> dilated bitfield, one launch, one thread per cell, a wave's 64 bits packed with one ballot ----
 __global__ __launch_bounds__(kOccThreads) void occ_build_kernel(const float* __restrict__ dens, int64_t nx, int64_t ny, int64_t nz, float thr, int r,
@@ -63,118 +66,185 @@ hipError_t launch_occ_build(const float* dens, const int64_t* dims, float thr, i
   return hipGetLastError();
 }
 
-// ---- per-level sample marking and compaction (the lookup itself: occ_lookup, aon_occ_lookup.h) ----
-struct OccSamples {
-  const float* rays_o; const float* rays_d; const float* t_vals;   // (n,3), (n,3), (n,S)
-  int64_t total; int S;                                             // n * S <= INT32_MAX (the caller's chunking)
-  const uint8_t* ray_live;                                          // (n,) or null: a dead ray's samples are EMPTY
+// ---- sample marking and compaction (the lookup itself: occ_lookup, aon_occ_lookup.h) ----
+// ONE mark / scan / emit for K segments of rows, each against its own grid, over the sample window [s0, s1) of every row: a render level is
+// one segment and the window [0, S) (section 4.9), a round of early termination a narrower window and the rays' stop map (section 4.10), a
+// scene level its K objects' pair rows (section 4.17).  A tile is kOccTile consecutive window slots of ONE segment and finds its segment
+// from the K + 1 first-tile numbers.  The record travels by value in the kernel arguments (no device copy to keep alive, nothing for the
+// host to wait for): KMAX = 1 keeps it at 152 bytes for the single-object renders, KMAX = AON_SCENE_MAX_OBJECTS takes 1.4 KB.
+// A segment without a grid to which neither a ray mask nor a stop map applies is DENSE: there is nothing to decide, so it has no tiles, its
+// rows of `raw` and of the list are not touched, and its count is all of its samples (the caller runs the ordinary MLP launch on it).
+template <int KMAX>
+struct OccArgs {
+  OccGrid g[KMAX];          // bits == nullptr: every cell occupied
+  int64_t row0[KMAX + 1];   // segment starts in rows; row0[K] = the number of rows
+  int tile0[KMAX + 1];      // first tile of each segment, ascending; tile0[K] = the number of tiles
+  int K, S, s0, s1;         // rows * S <= INT32_MAX (the entry points' checks): slots, records and list entries fit 32 bits
+  const float* o; const float* d; const float* t_vals;   // (rows,3), (rows,3), (rows,S)
+  const uint8_t* ray_live;  // (rows,) or null: a dead ray's samples are EMPTY
+  const int* stop;          // (rows,) or null: sample i >= stop[row] is DEAD (section 4.10)
 };
 
-__device__ __forceinline__ int occ_tile_flags(const OccGrid& G, const OccSamples& s, int64_t g0, bool (&occ)[4]) {
-  int n = 0;
+template <int KMAX>
+__host__ __device__ __forceinline__ bool occ_dense(const OccArgs<KMAX>& a, int k) { return !a.g[k].bits && !a.ray_live && !a.stop; }
+
+// Slot q of segment k's window -> row q / (s1 - s0), sample i = s0 + q % (s1 - s0).  rec: the sample's index in `raw` and `t_vals` (-1: the
+// slot lies past the segment's end); local: its listed, SEGMENT-LOCAL index row_local * S + i.  Returns whether the sample is occupied.
+template <int KMAX>
+__device__ __forceinline__ bool occ_flag(const OccArgs<KMAX>& a, int k, uint32_t q, int64_t& rec, int& local) {
+  const uint32_t w = a.s1 - a.s0;
+  rec = -1;
+  if (q >= (uint32_t)(a.row0[k + 1] - a.row0[k]) * w) return false;
+  const uint32_t row_local = q / w;
+  const int i = a.s0 + (int)(q - row_local * w);
+  const int64_t row = a.row0[k] + row_local;
+  local = (int)row_local * a.S + i;
+  rec = a.row0[k] * a.S + local;
+  if (a.stop && a.stop[row] <= i) return false;       // dead: behind the ray's stop
+  if (a.ray_live && !a.ray_live[row]) return false;   // dead ray
+  if (!a.g[k].bits) return true;
+  const float t = a.t_vals[rec];
+  float x[3];
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int64_t g = g0 + r;
-    occ[r] = false;
-    if (g >= s.total) continue;
-    const int64_t ray = g / s.S;
-    if (s.ray_live && !s.ray_live[ray]) continue;   // dead ray
-    if (G.bits) {
-      const float t = s.t_vals[g];
-      float x[3];
+  for (int c = 0; c < 3; ++c) x[c] = __fadd_rn(a.o[row * 3 + c], __fmul_rn(t, a.d[row * 3 + c]));   // helper.cast_rays
+  return occ_lookup(a.g[k], x);
+}
+
+// A workgroup's tile: thread t takes slots t, t + 256, t + 512, t + 768 (coalesced t_vals reads), so slot r * 256 + 64 * wave + lane
+// ascends with (r, wave, lane).  Counts by wave ballots: cnt[r][wave] = the occupied slots of quarter r in that wave, after a barrier.
+struct OccTile {
+  int k;                     // the tile's segment: the last k with tile0[k] <= tile (segments without tiles lose to their successor)
+  int64_t rec[kOccPer];
+  int local[kOccPer];
+  uint64_t bal[kOccPer];     // the wave's ballot of quarter r
+  bool occ[kOccPer];
+};
+
+template <int KMAX>
+__device__ __forceinline__ void occ_tile_flags(const OccArgs<KMAX>& a, OccTile& s, int (&cnt)[kOccPer][kOccWaves]) {
+  s.k = 0;
+  for (int j = 1; j < a.K; ++j)   // (uniform)
+    if ((int)blockIdx.x >= a.tile0[j]) s.k = j;
+  const uint32_t q0 = (uint32_t)((int)blockIdx.x - a.tile0[s.k]) * kOccTile + threadIdx.x;
 #pragma unroll
-      for (int a = 0; a < 3; ++a) x[a] = __fadd_rn(s.rays_o[ray * 3 + a], __fmul_rn(t, s.rays_d[ray * 3 + a]));   // helper.cast_rays
-      occ[r] = occ_lookup(G, x);
-    } else {
-      occ[r] = true;   // a null grid: every cell occupied
-    }
-    n += occ[r] ? 1 : 0;
+  for (int r = 0; r < kOccPer; ++r) {
+    s.occ[r] = occ_flag(a, s.k, q0 + r * kOccThreads, s.rec[r], s.local[r]);
+    s.bal[r] = __builtin_amdgcn_ballot_w64(s.occ[r]);
+    if ((threadIdx.x & 63) == 0) cnt[r][threadIdx.x >> 6] = __builtin_popcountll(s.bal[r]);
   }
-  return n;
+  __syncthreads();
 }
 
 // (a) the sentinel record of every empty sample; the tile's occupied count
-__global__ __launch_bounds__(kOccThreads) void occ_mark_kernel(OccGrid G, OccSamples s, f32x4* __restrict__ raw, int* __restrict__ tile_counts) {
-  __shared__ int red[kOccThreads / 64];
-  const int64_t g0 = (int64_t)blockIdx.x * kOccTile + 4 * threadIdx.x;
-  bool occ[4];
-  const int n = occ_tile_flags(G, s, g0, occ);
+template <int KMAX>
+__global__ __launch_bounds__(kOccThreads) void occ_mark_kernel(OccArgs<KMAX> a, f32x4* __restrict__ raw, int* __restrict__ tile_counts) {
+  __shared__ int cnt[kOccPer][kOccWaves];
+  OccTile s;
+  occ_tile_flags(a, s, cnt);
   f32x4 sentinel;
   sentinel[0] = 0.f; sentinel[1] = 0.f; sentinel[2] = 0.f; sentinel[3] = -__builtin_huge_valf();
 #pragma unroll
-  for (int r = 0; r < 4; ++r)
-    if (g0 + r < s.total && !occ[r]) raw[g0 + r] = sentinel;
-  int tot;
-  block_excl_scan<int>(n, tot, red);
-  if (threadIdx.x == 0) tile_counts[blockIdx.x] = tot;
-}
-
-// (b) one workgroup: exclusive offsets of the tile counts in tile order; *count = total; tally[0] += total when tally is given
-__global__ __launch_bounds__(kOccThreads) void occ_scan_kernel(const int* __restrict__ tile_counts, int64_t ntiles, int* __restrict__ offs,
-                                                               int64_t* __restrict__ count, int64_t* __restrict__ tally) {
-  __shared__ int64_t red[kOccThreads / 64];
-  constexpr int kPer = 8;
-  int64_t carry = 0;
-  for (int64_t base = 0; base < ntiles; base += (int64_t)kOccThreads * kPer) {
-    const int64_t t0 = base + (int64_t)threadIdx.x * kPer;
-    int cv[kPer];
-    int64_t sv = 0;
-#pragma unroll
-    for (int r = 0; r < kPer; ++r) {
-      cv[r] = t0 + r < ntiles ? tile_counts[t0 + r] : 0;
-      sv += cv[r];
-    }
-    int64_t tv;
-    int64_t run = carry + block_excl_scan<int64_t>(sv, tv, red);
-#pragma unroll
-    for (int r = 0; r < kPer; ++r) {
-      if (t0 + r < ntiles) offs[t0 + r] = (int)run;
-      run += cv[r];
-    }
-    carry += tv;
-  }
+  for (int r = 0; r < kOccPer; ++r)
+    if (s.rec[r] >= 0 && !s.occ[r]) raw[s.rec[r]] = sentinel;
   if (threadIdx.x == 0) {
-    *count = carry;
-    if (tally) *tally += carry;
+    int tot = 0;
+#pragma unroll
+    for (int r = 0; r < kOccPer; ++r)
+#pragma unroll
+      for (int w = 0; w < kOccWaves; ++w) tot += cnt[r][w];
+    tile_counts[blockIdx.x] = tot;
   }
 }
 
-// (c) the occupied sample indices of a tile at its scanned offset, ascending
-__global__ __launch_bounds__(kOccThreads) void occ_emit_kernel(OccGrid G, OccSamples s, const int* __restrict__ offs, int* __restrict__ idx) {
-  __shared__ int red[kOccThreads / 64];
-  const int64_t g0 = (int64_t)blockIdx.x * kOccTile + 4 * threadIdx.x;
-  bool occ[4];
-  const int n = occ_tile_flags(G, s, g0, occ);
-  int tot;
-  int run = offs[blockIdx.x] + block_excl_scan<int>(n, tot, red);
+// (b) one workgroup, per segment: offs[tile] = the occupied samples of the segment's earlier tiles; counts[k] = the segment's total (dense:
+// all of its samples); tally[k] += counts[k] when tally is given.  Integers: exact, the order of the sums does not matter.
+template <int KMAX>
+__global__ __launch_bounds__(kOccThreads) void occ_scan_kernel(OccArgs<KMAX> a, const int* __restrict__ tile_counts, int* __restrict__ offs,
+                                                               int64_t* __restrict__ counts, int64_t* __restrict__ tally) {
+  __shared__ int64_t red[kOccWaves];
+  for (int k = 0; k < a.K; ++k) {   // (uniform)
+    const int64_t total = (occ_dense(a, k) ? (a.row0[k + 1] - a.row0[k]) * (a.s1 - a.s0) : 0) +
+                          block_scan_counts(tile_counts + a.tile0[k], a.tile0[k + 1] - a.tile0[k], offs + a.tile0[k], red);
+    if (threadIdx.x == 0) {
+      counts[k] = total;
+      if (tally) tally[k] += total;
+    }
+  }
+}
+
+// (c) the occupied samples of a tile at its scanned offset in the segment's list (idx + row0[k] * S), ascending: the rank of a slot is the
+// tile's offset + the earlier quarters + the earlier waves of its quarter + the earlier lanes of its ballot
+template <int KMAX>
+__global__ __launch_bounds__(kOccThreads) void occ_emit_kernel(OccArgs<KMAX> a, const int* __restrict__ offs, int* __restrict__ idx) {
+  __shared__ int cnt[kOccPer][kOccWaves];
+  OccTile s;
+  occ_tile_flags(a, s, cnt);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  int* list = idx + a.row0[s.k] * a.S;
+  int run = offs[blockIdx.x];
 #pragma unroll
-  for (int r = 0; r < 4; ++r)
-    if (occ[r]) idx[run++] = (int)(g0 + r);
+  for (int r = 0; r < kOccPer; ++r) {
+    int before = run;
+#pragma unroll
+    for (int w = 0; w < kOccWaves; ++w) {
+      if (w < wave) before += cnt[r][w];
+      run += cnt[r][w];
+    }
+    if (s.occ[r]) list[before + __builtin_popcountll(s.bal[r] & below)] = s.local[r];
+  }
 }
 
-int64_t occ_list_bytes(int64_t total) {   // per chunk and level: sample list, tile counts, tile offsets, the device counter
-  const int64_t tiles = (total + kOccTile - 1) / kOccTile;
-  return ((total * 4 + 255) / 256 + (tiles * 4 + 255) / 256 * 2 + 1) * 256;
+// The workspace of a compaction, 256-byte aligned parts: the lists (`total` int32), tile counts and tile offsets (`tile_cap` int32 each)
+// and the K counters (int64).  ws == nullptr: the size alone.
+struct OccLists {
+  int* idx; int* tile_counts; int* offs; int64_t* counts;
+  int64_t bytes;
+};
+static OccLists occ_carve(char* ws, int64_t total, int64_t tile_cap, int K) {
+  auto up = [](int64_t b) { return (b + 255) / 256 * 256; };
+  const int64_t o1 = up(total * 4), o2 = o1 + up(tile_cap * 4), o3 = o2 + up(tile_cap * 4);
+  return {reinterpret_cast<int*>(ws), reinterpret_cast<int*>(ws + o1), reinterpret_cast<int*>(ws + o2), reinterpret_cast<int64_t*>(ws + o3),
+          o3 + up((int64_t)K * 8)};
+}
+static int64_t occ_tiles(int64_t samples) { return (samples + kOccTile - 1) / kOccTile; }
+int64_t occ_list_bytes(int64_t total) { return occ_carve(nullptr, total, occ_tiles(total), 1).bytes; }   // per chunk and level
+int64_t scene_occ_tile_cap(int64_t pairs, int K, int S) { return pairs * S / kOccTile + K; }              // >= sum_k ceil(P_k S / 1024)
+int64_t scene_occ_list_bytes(int64_t pairs, int K, int S) {
+  return occ_carve(nullptr, (pairs > 0 ? pairs : 1) * S, scene_occ_tile_cap(pairs, K, S), K).bytes;
 }
 
-// raw: (total, 4) records; ws: occ_list_bytes(total) bytes, 256-byte aligned -> idx (total int32) and the counter (int64) for the gather launch
-hipError_t launch_occ_compact(const OccGrid& G, const float* rays_o, const float* rays_d, const float* t_vals, int64_t n, int S, float* raw,
-                              char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out, hipStream_t stream,
-                              const uint8_t* ray_live) {
-  const OccSamples s{rays_o, rays_d, t_vals, n * S, S, ray_live};
-  const int64_t tiles = (s.total + kOccTile - 1) / kOccTile;
-  int* idx = reinterpret_cast<int*>(ws);
-  int* counts = reinterpret_cast<int*>(ws + (s.total * 4 + 255) / 256 * 256);
-  int* offs = counts + (tiles * 4 + 255) / 256 * 64;
-  int64_t* count = reinterpret_cast<int64_t*>(offs + (tiles * 4 + 255) / 256 * 64);
-  *idx_out = idx; *count_out = count;
-  if (tiles == 0) return hipMemsetAsync(count, 0, 8, stream);
-  occ_mark_kernel<<<dim3((unsigned)tiles), dim3(kOccThreads), 0, stream>>>(G, s, reinterpret_cast<f32x4*>(raw), counts);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  occ_scan_kernel<<<dim3(1), dim3(kOccThreads), 0, stream>>>(counts, tiles, offs, count, tally);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  occ_emit_kernel<<<dim3((unsigned)tiles), dim3(kOccThreads), 0, stream>>>(G, s, offs, idx);
+template <int KMAX>
+static hipError_t occ_compact(const OccCompact& c, float* raw, const OccLists& L, int64_t* tally, hipStream_t stream) {
+  OccArgs<KMAX> a{};
+  a.K = c.K; a.S = c.S; a.s0 = c.s0; a.s1 = c.s1;
+  a.o = c.rays_o; a.d = c.rays_d; a.t_vals = c.t_vals; a.ray_live = c.ray_live; a.stop = c.stop;
+  for (int k = 0; k < c.K; ++k) a.g[k] = c.grids[k];
+  int64_t tiles = 0;
+  for (int k = 0; k <= c.K; ++k) {
+    a.row0[k] = c.starts[k];
+    a.tile0[k] = (int)tiles;
+    if (k < c.K && !occ_dense(a, k)) tiles += occ_tiles((c.starts[k + 1] - c.starts[k]) * (c.s1 - c.s0));
+  }
+  const dim3 grid((unsigned)tiles), block(kOccThreads);
+  if (tiles > 0) {
+    occ_mark_kernel<KMAX><<<grid, block, 0, stream>>>(a, reinterpret_cast<f32x4*>(raw), L.tile_counts);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  if (tiles > 0 || tally) {   // (every segment dense or empty: the dense launches read no counter, the tally is all the scan writes)
+    occ_scan_kernel<KMAX><<<dim3(1), block, 0, stream>>>(a, L.tile_counts, L.offs, L.counts, tally);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  }
+  if (tiles > 0) occ_emit_kernel<KMAX><<<grid, block, 0, stream>>>(a, L.offs, L.idx);
   return hipGetLastError();
+}
+
+hipError_t launch_occ_compact(const OccCompact& c, float* raw, char* ws, int64_t tile_cap, int64_t* tally, const int** idx_out,
+                              const int64_t** counts_out, hipStream_t stream) {
+  const OccLists L = occ_carve(ws, c.starts[c.K] * c.S, tile_cap, c.K);
+  *idx_out = L.idx; *counts_out = L.counts;
+  if (c.starts[c.K] == 0) return hipMemsetAsync(L.counts, 0, (size_t)c.K * 8, stream);   // no rows: empty lists, nothing to launch
+  return c.K == 1 ? occ_compact<1>(c, raw, L, tally, stream) : occ_compact<AON_SCENE_MAX_OBJECTS>(c, raw, L, tally, stream);
 }
 
 // ---- early ray termination (tests/_stop_ref.py is an independent numpy copy) ----
@@ -182,74 +252,7 @@ hipError_t launch_occ_compact(const OccGrid& G, const float* rays_o, const float
 // tau (fp32, 0 at the start of the level) and stop (int32, S at the start).  After round k's MLP launch a ray with stop == S adds
 // sigma_i * delta_i of the round's samples to tau in ascending i -- one sequential fp32 chain, every multiply and add rounded -- with
 // sigma_i / delta_i as composite_kernel (aon_render.hip) forms them, and stops (stop = (k+1)R) when tau >= tau_stop = fp32(-ln eps).
-// In a later round a sample i >= stop[ray] is DEAD: the sentinel record, not listed.  The last round decides nothing (no depth launch).
-struct OccRound {
-  const int* stop;   // (n,)
-  int s0, s1;        // the round's sample indices [s0, s1) of every ray
-  int64_t count;     // n * (s1 - s0)
-};
-
-// tile slot q -> ray q / (s1 - s0), sample s0 + q % (s1 - s0); a null grid: every cell occupied
-__device__ __forceinline__ int occ_round_flags(const OccGrid& G, const OccSamples& s, const OccRound& rd, int64_t q0, bool (&occ)[4], int64_t (&gi)[4]) {
-  const int w = rd.s1 - rd.s0;
-  int n = 0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int64_t q = q0 + r;
-    occ[r] = false;
-    gi[r] = -1;
-    if (q >= rd.count) continue;
-    const int64_t ray = q / w;
-    const int i = rd.s0 + (int)(q - ray * w);
-    const int64_t g = ray * s.S + i;
-    gi[r] = g;
-    if (rd.stop[ray] <= i) continue;   // dead: behind the ray's stop
-    if (s.ray_live && !s.ray_live[ray]) continue;   // dead ray
-    if (G.bits) {
-      const float t = s.t_vals[g];
-      float x[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) x[a] = __fadd_rn(s.rays_o[ray * 3 + a], __fmul_rn(t, s.rays_d[ray * 3 + a]));
-      occ[r] = occ_lookup(G, x);
-    } else {
-      occ[r] = true;
-    }
-    n += occ[r] ? 1 : 0;
-  }
-  return n;
-}
-
-__global__ __launch_bounds__(kOccThreads) void occ_mark_round_kernel(OccGrid G, OccSamples s, OccRound rd, f32x4* __restrict__ raw,
-                                                                     int* __restrict__ tile_counts) {
-  __shared__ int red[kOccThreads / 64];
-  const int64_t q0 = (int64_t)blockIdx.x * kOccTile + 4 * threadIdx.x;
-  bool occ[4];
-  int64_t gi[4];
-  const int n = occ_round_flags(G, s, rd, q0, occ, gi);
-  f32x4 sentinel;
-  sentinel[0] = 0.f; sentinel[1] = 0.f; sentinel[2] = 0.f; sentinel[3] = -__builtin_huge_valf();
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    if (gi[r] >= 0 && !occ[r]) raw[gi[r]] = sentinel;
-  int tot;
-  block_excl_scan<int>(n, tot, red);
-  if (threadIdx.x == 0) tile_counts[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(kOccThreads) void occ_emit_round_kernel(OccGrid G, OccSamples s, OccRound rd, const int* __restrict__ offs,
-                                                                     int* __restrict__ idx) {
-  __shared__ int red[kOccThreads / 64];
-  const int64_t q0 = (int64_t)blockIdx.x * kOccTile + 4 * threadIdx.x;
-  bool occ[4];
-  int64_t gi[4];
-  const int n = occ_round_flags(G, s, rd, q0, occ, gi);
-  int tot;
-  int run = offs[blockIdx.x] + block_excl_scan<int>(n, tot, red);
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    if (occ[r]) idx[run++] = (int)gi[r];   // ascending: q ascends with (ray, i)
-}
-
+// In a later round a sample i >= stop[ray] is DEAD: the sentinel record, not listed (occ_flag).  The last round decides nothing (no depth launch).
 // tau[ray] = 0, stop[ray] = S
 __global__ __launch_bounds__(kOccThreads) void occ_stop_init_kernel(float* __restrict__ tau, int* __restrict__ stop, int64_t n, int S) {
   const int64_t ray = (int64_t)blockIdx.x * kOccThreads + threadIdx.x;
@@ -303,55 +306,34 @@ hipError_t launch_occ_tally_set(int64_t* tally, int64_t v0, int64_t v1, hipStrea
   occ_tally_set_kernel<<<dim3(1), dim3(64), 0, stream>>>(tally, v0, v1);
   return hipGetLastError();
 }
-
 int64_t occ_stop_state_bytes(int64_t n) { return (n * 4 + 255) / 256 * 256 * 2; }   // tau, stop
+OccStopState occ_stop_state(char* state, int64_t n) {
+  if (!state) return {nullptr, nullptr};
+  return {reinterpret_cast<float*>(state), reinterpret_cast<int*>(state + occ_stop_state_bytes(n) / 2)};
+}
 
 hipError_t launch_occ_stop_init(char* state, int64_t n, int S, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
-  float* tau = reinterpret_cast<float*>(state);
-  int* stop = reinterpret_cast<int*>(state + (n * 4 + 255) / 256 * 256);
-  occ_stop_init_kernel<<<dim3((unsigned)((n + kOccThreads - 1) / kOccThreads)), dim3(kOccThreads), 0, stream>>>(tau, stop, n, S);
+  const OccStopState st = occ_stop_state(state, n);
+  occ_stop_init_kernel<<<dim3((unsigned)((n + kOccThreads - 1) / kOccThreads)), dim3(kOccThreads), 0, stream>>>(st.tau, st.stop, n, S);
   return hipGetLastError();
 }
 
 // state == nullptr: fill with `value`
-hipError_t launch_occ_stop_store(const char* state, int value, int* dst, int64_t n, int stride, hipStream_t stream) {
+hipError_t launch_occ_stop_store(char* state, int value, int* dst, int64_t n, int stride, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
-  const int* stop = state ? reinterpret_cast<const int*>(state + (n * 4 + 255) / 256 * 256) : nullptr;
-  occ_stop_store_kernel<<<dim3((unsigned)((n + kOccThreads - 1) / kOccThreads)), dim3(kOccThreads), 0, stream>>>(stop, value, dst, n, stride);
-  return hipGetLastError();
-}
-
-// launch_occ_compact over the sub-range [s0, s1) of every ray, minus the dead samples.  G.bits == nullptr: no grid.
-hipError_t launch_occ_compact_round(const OccGrid& G, const float* rays_o, const float* rays_d, const float* t_vals, int64_t n, int S, int s0, int s1,
-                                    const char* state, float* raw, char* ws, int64_t* tally, const int** idx_out, const int64_t** count_out,
-                                    hipStream_t stream, const uint8_t* ray_live) {
-  const OccSamples s{rays_o, rays_d, t_vals, n * S, S, ray_live};
-  const OccRound rd{reinterpret_cast<const int*>(state + (n * 4 + 255) / 256 * 256), s0, s1, n * (s1 - s0)};
-  const int64_t tiles = (rd.count + kOccTile - 1) / kOccTile;
-  const int64_t full_tiles = (s.total + kOccTile - 1) / kOccTile;   // the buffers keep launch_occ_compact's layout
-  int* idx = reinterpret_cast<int*>(ws);
-  int* counts = reinterpret_cast<int*>(ws + (s.total * 4 + 255) / 256 * 256);
-  int* offs = counts + (full_tiles * 4 + 255) / 256 * 64;
-  int64_t* count = reinterpret_cast<int64_t*>(offs + (full_tiles * 4 + 255) / 256 * 64);
-  *idx_out = idx; *count_out = count;
-  if (tiles == 0) return hipMemsetAsync(count, 0, 8, stream);
-  occ_mark_round_kernel<<<dim3((unsigned)tiles), dim3(kOccThreads), 0, stream>>>(G, s, rd, reinterpret_cast<f32x4*>(raw), counts);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  occ_scan_kernel<<<dim3(1), dim3(kOccThreads), 0, stream>>>(counts, tiles, offs, count, tally);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  occ_emit_round_kernel<<<dim3((unsigned)tiles), dim3(kOccThreads), 0, stream>>>(G, s, rd, offs, idx);
+  occ_stop_store_kernel<<<dim3((unsigned)((n + kOccThreads - 1) / kOccThreads)), dim3(kOccThreads), 0, stream>>>(occ_stop_state(state, n).stop, value, dst,
+                                                                                                                n, stride);
   return hipGetLastError();
 }
 
 hipError_t launch_occ_depth(const float* raw, const float* t_vals, const float* dirs, int64_t n, int S, int s0, int s1, const ActParams& ap,
                             float tau_stop, char* state, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
-  float* tau = reinterpret_cast<float*>(state);
-  int* stop = reinterpret_cast<int*>(state + (n * 4 + 255) / 256 * 256);
+  const OccStopState st = occ_stop_state(state, n);
   constexpr int kRays = kOccThreads / 64;
   occ_depth_kernel<<<dim3((unsigned)((n + kRays - 1) / kRays)), dim3(kOccThreads), 0, stream>>>(reinterpret_cast<const f32x4*>(raw), t_vals, dirs, n, S,
-                                                                                               s0, s1, ap, tau_stop, tau, stop);
+                                                                                               s0, s1, ap, tau_stop, st.tau, st.stop);
   return hipGetLastError();
 }
 

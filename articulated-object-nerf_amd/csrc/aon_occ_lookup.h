@@ -1,6 +1,5 @@
-// The occupancy lookup of DESIGN.md section 4.9, shared by the translation units that mark samples against a grid: aon_occ.hip (one grid per
-// render, sections 4.9 - 4.11) and aon_scene_occ.hip (one grid per placed object, section 4.17).  ONE device function, so the two paths cannot
-// drift apart: sample x lies in cell floor((x_a - lo_a) / step_a) per axis (fp32 subtraction, IEEE division, floor), clamped to cells_a - 1
+// The occupancy lookup of DESIGN.md section 4.9, used by aon_occ.hip's one mark / emit pair for every path (one grid per render, sections 4.9 - 4.11;
+// one grid per placed object, section 4.17): sample x lies in cell floor((x_a - lo_a) / step_a) per axis (fp32 subtraction, IEEE division, floor), clamped to cells_a - 1
 // (x_a == hi_a); a coordinate outside [lo_a, hi_a], or NaN, is EMPTY.  tests/_occ_ref.py is an independent numpy copy.
 #pragma once
 #include "aon_common.h"

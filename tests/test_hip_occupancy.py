@@ -101,14 +101,18 @@ def _mask(grid, o, d, t):
     return torch.from_numpy(m).to(t.device)
 
 
-def _yardstick(net, o, d, v, grid):
-    """Stage entry points with the empty samples' sigma overwritten by the sentinel: sample_along_rays -> mlp -> mask -> composite_pdf ->
-    mlp on t_fine -> mask -> composite.  Returns the level tuples and the per-level counts of occupied samples."""
+def _yardstick(net, o, d, v, grid, nc=64, num_levels=2):
+    """Stage entry points with the empty samples' sigma overwritten by the sentinel: sample_along_rays (nc + 1 samples) -> mlp -> mask ->
+    composite_pdf -> mlp on t_fine -> mask -> composite; one level: sample_along_rays -> mlp -> mask -> composite.  Returns the level
+    tuples and the per-level counts of occupied samples (0 for a level that does not run)."""
     ops = net.ops
-    t_c, _ = ops.sample_along_rays(o, d, 64, NEAR, FAR, want_coords=False)
+    t_c, _ = ops.sample_along_rays(o, d, nc, NEAR, FAR, want_coords=False)
     raw = net.mlp(0, o, d, v, t_c)
     m0 = _mask(grid, o, d, t_c)
     raw[..., 3][~m0] = float("-inf")
+    if num_levels == 1:
+        comp_c, acc_c, _, depth_c = ops.composite_raw(raw, t_c, d, True, net.act, want_weights=False)
+        return [(comp_c, acc_c, depth_c)], [int(m0.sum()), 0]
     comp_c, acc_c, _, depth_c, t_f = ops.composite_pdf(raw, t_c, d, True, net.act)
     raw_f = net.mlp(1, o, d, v, t_f)
     m1 = _mask(grid, o, d, t_f)
@@ -196,29 +200,42 @@ def test_empty_grid_returns_background(ops, dev, articulated):
 
 
 # ---------------------------------------------------------------- 4. skipping == zeroing, bit for bit
-@pytest.mark.parametrize("articulated", [False, True])
-@pytest.mark.parametrize("fold", [True, False])
-@pytest.mark.parametrize("kind", ["random", "halfspace"])
-def test_skip_equals_zeroing(ops, dev, articulated, fold, kind):
+# shape: rays, levels, coarse / fine sample counts (None: the default 64 / 128, levels of 65 and 193 samples).  The compaction works on tiles
+# of 1,024 samples and scans 2,048 tile counts a round:
+#   tiles4 / tiles4_plus1  one level of 64 samples, 64 and 65 rays: exactly 4 tiles, and one sample past them
+#   many_tiles             11,000 rays: the fine level has ceil(11000 * 193 / 1024) = 2,074 tiles, so the scan carries a total into a second round
+SHAPES = {"default": (900, 2, None), "tiles4": (64, 1, (63, 64)), "tiles4_plus1": (65, 1, (63, 64)), "many_tiles": (11000, 2, None)}
+#             (the ids of the cases that were here before the shapes)
+SKIP_CASES = [pytest.param(kind, fold, art, "default", id=f"{kind}-{fold}-{art}") for art in (False, True) for fold in (True, False)
+              for kind in ("random", "halfspace")]
+SKIP_CASES += [pytest.param(kind, True, art, shape, id=f"{kind}-{shape}-{art}") for art in (False, True)
+               for kind, shape in (("random", "tiles4"), ("random", "tiles4_plus1"), ("halfspace", "many_tiles"))]
+
+
+@pytest.mark.parametrize("kind,fold,articulated,shape", SKIP_CASES)
+def test_skip_equals_zeroing(ops, dev, articulated, fold, kind, shape):
     ops.set_bottleneck_fold(fold)
     net = Net(ops, _art(dev), _latents(dev)) if articulated else Net(ops, _nerf(dev))
-    o, d, v = _rays(dev, 900, seed=4)
+    n, num_levels, sizes = SHAPES[shape]
+    opts = None if sizes is None else ops.RenderOpts(num_coarse_samples=sizes[0], num_fine_samples=sizes[1])
+    op = ops._opts(opts)
+    o, d, v = _rays(dev, n, seed=4)
     if kind == "random":
         g = torch.Generator().manual_seed(7)
         grid = ops.occupancy_grid(torch.rand(9, 10, 11, generator=g).to(dev), -1.5, 1.5, 0.917, 0)   # 1 - 0.917^8 ~ 50 % of the cells
     else:
         grid = _grid_from(ops, lambda p: (p[..., 0] + 0.5 * p[..., 1] > 0.1).float(), (12, 13, 14), (-1.4, -1.5, -1.3), (1.5, 1.2, 1.4), dev, 0.5, 0)
     assert 0.3 < grid.occupied_fraction() < 0.8
-    want, counts = _yardstick(net, o, d, v, grid)
-    got, occupied = net.occ(o, d, v, grid)
+    want, counts = _yardstick(net, o, d, v, grid, op.Sc - 1, num_levels)
+    got, occupied = net.occ(o, d, v, grid, num_levels, opts)
     _same(want, got)
     assert occupied.tolist() == counts
-    assert 0 < counts[1] < o.shape[0] * 193
+    assert 0 < counts[num_levels - 1] < n * (op.Sf if num_levels == 2 else op.Sc)
     # 5. determinism: a second call, and a chunked call, give the same bits
-    again, occ2 = net.occ(o, d, v, grid)
+    again, occ2 = net.occ(o, d, v, grid, num_levels, opts)
     _same(got, again)
-    small = int(ops.lib.aon_render_occ_workspace_bytes(101, None))
-    chunked, occ3 = net.occ(o, d, v, grid, workspace_bytes=small)
+    small = int(ops.lib.aon_render_occ_workspace_bytes(101, None if opts is None else ops.C.byref(op.c_struct(NEAR, FAR)[0])))
+    chunked, occ3 = net.occ(o, d, v, grid, num_levels, opts, workspace_bytes=small)
     _same(got, chunked)
     assert occ2.tolist() == occ3.tolist() == counts
 

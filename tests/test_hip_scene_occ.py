@@ -112,7 +112,8 @@ def same_levels(got, want):
 #              name            S    rows per object
 STAGE_CASES = [("tile_edges",   64,  (0, 1, 16, 17, 33)),                 # empty, a partial tile, exactly 1,024 samples, one past it, a boundary inside
                ("k16_s9",       9,   (40, 0, 7, 0, 0, 61, 1, 30, 0, 25, 44, 0, 19, 50, 0, 23)),      # P = 300, K = 16, six empty segments
-               ("s193",         193, (11, 20, 6))]                        # P = 37: tiles that end inside a row
+               ("s193",         193, (11, 20, 6)),                        # P = 37: tiles that end inside a row
+               ("many_tiles",   193, (11000, 3))]                         # 2,074 tiles, more than one round of the scan; then offsets restart at 0
 GUARD_REACHES = ["aon_scene_occ_workspace_bytes", "aon_scene_art_mlp_fwd_occ"]
 
 
@@ -338,7 +339,7 @@ def _guard_case(name, S, rows, shift):
     return Case("scene_occ", name, make, call, GUARD_REACHES)
 
 
-for _name, _S, _rows in STAGE_CASES:
+for _name, _S, _rows in STAGE_CASES[:3]:          # (many_tiles: the same code at a size the stage test covers)
     for _shift in (0, 3):
         GUARD_CASES.append(_guard_case(f"scene_occ_{_name}_shift{_shift}", _S, _rows, _shift))
 

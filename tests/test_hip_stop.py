@@ -137,24 +137,31 @@ def _zeroed(raw, keep):
     return r
 
 
-def _yardstick(net, o, d, v, grid, stop):
+def _yardstick(net, o, d, v, grid, stop, nc=64, nf=128, num_levels=2):
     """Stage entry points with the sigma of the empty samples (numpy grid lookup) and of the dead ones (i >= stop[ray], the product's own
-    stop map) overwritten by the sentinel: sample_along_rays -> mlp -> mask -> composite_pdf -> mlp on t_fine -> mask -> composite.
+    stop map) overwritten by the sentinel: sample_along_rays (nc + 1 samples) -> mlp -> mask -> composite_pdf -> mlp on t_fine -> mask ->
+    composite; one level: sample_along_rays -> mlp -> mask -> composite.
     Returns per level: the terminated tuple, the tuple with the grid mask alone on the same t values, t, the exact raw records, the grid
     mask and the count of samples that are neither empty nor dead."""
     ops = net.ops
     dev = o.device
     out = []
-    t_c, _ = ops.sample_along_rays(o, d, 64, NEAR, FAR, want_coords=False)
+    t_c, _ = ops.sample_along_rays(o, d, nc, NEAR, FAR, want_coords=False)
     raw = net.mlp(0, o, d, v, t_c)
     m0 = _mask(grid, o, d, t_c)
-    live0 = m0 & torch.from_numpy(ref.live_mask(stop[:, 0].cpu().numpy(), 65)).to(dev)
-    comp_c, acc_c, _, depth_c, t_f = ops.composite_pdf(_zeroed(raw, live0), t_c, d, True, net.act)
-    g_c, ga_c, _, gd_c, _ = ops.composite_pdf(_zeroed(raw, m0), t_c, d, True, net.act)
+    live0 = m0 & torch.from_numpy(ref.live_mask(stop[:, 0].cpu().numpy(), nc + 1)).to(dev)
+    if num_levels == 1:
+        comp_c, acc_c, _, depth_c = ops.composite_raw(_zeroed(raw, live0), t_c, d, True, net.act, want_weights=False)
+        g_c, ga_c, _, gd_c = ops.composite_raw(_zeroed(raw, m0), t_c, d, True, net.act, want_weights=False)
+    else:
+        comp_c, acc_c, _, depth_c, t_f = ops.composite_pdf(_zeroed(raw, live0), t_c, d, True, net.act)
+        g_c, ga_c, _, gd_c, _ = ops.composite_pdf(_zeroed(raw, m0), t_c, d, True, net.act)
     out.append({"got": (comp_c, acc_c, depth_c), "grid_only": (g_c, ga_c, gd_c), "t": t_c, "raw": raw, "mask": m0, "count": int(live0.sum())})
+    if num_levels == 1:
+        return out
     raw_f = net.mlp(1, o, d, v, t_f)
     m1 = _mask(grid, o, d, t_f)
-    live1 = m1 & torch.from_numpy(ref.live_mask(stop[:, 1].cpu().numpy(), 193)).to(dev)
+    live1 = m1 & torch.from_numpy(ref.live_mask(stop[:, 1].cpu().numpy(), nc + 1 + nf)).to(dev)
     comp_f, acc_f, _, depth_f = ops.composite_raw(_zeroed(raw_f, live1), t_f, d, True, net.act, want_weights=False)
     g_f, ga_f, _, gd_f = ops.composite_raw(_zeroed(raw_f, m1), t_f, d, True, net.act, want_weights=False)
     out.append({"got": (comp_f, acc_f, depth_f), "grid_only": (g_f, ga_f, gd_f), "t": t_f, "raw": raw_f, "mask": m1, "count": int(live1.sum())})
@@ -213,24 +220,38 @@ def test_eps_zero_is_bit_equal(ops, dev, articulated, fold):
 
 
 # ---------------------------------------------------------------- 2.-5. zeroing, the rule, not vacuous, the bound
-@pytest.mark.parametrize("articulated", [False, True])
-@pytest.mark.parametrize("kind", ["none", "random", "halfspace"])
-@pytest.mark.parametrize("R", [500, 16, 48])
-@pytest.mark.parametrize("eps", [1e-2, 1e-4])
-def test_stop_equals_zeroing_and_follows_the_rule(ops, dev, articulated, kind, R, eps):
+# shape: rays, levels, coarse / fine sample counts (None: the default 64 / 128, levels of 65 and 193 samples).  The compaction works on tiles
+# of 1,024 slots of a round and scans 2,048 tile counts a round:
+#   tiles / tiles_plus1  one level of 64 samples, R = 48 (rounds of 48 and 16: the width divides neither 64 nor 1,024), 64 and 65 rays:
+#                        exactly 3 tiles and exactly 1 tile, and one slot past each
+#   many_tiles           11,000 rays, R = 192: the fine level's first round has ceil(11000 * 192 / 1024) = 2,063 tiles, so the scan carries a
+#                        total into a second round
+SHAPES = {"default": (900, 2, None), "tiles": (64, 1, (63, 64)), "tiles_plus1": (65, 1, (63, 64)), "many_tiles": (11000, 2, None)}
+#             (the ids of the cases that were here before the shapes)
+STOP_CASES = [pytest.param(eps, R, kind, art, "default", id=f"{eps}-{R}-{kind}-{art}") for art in (False, True) for kind in ("none", "random", "halfspace")
+              for R in (500, 16, 48) for eps in (1e-2, 1e-4)]
+STOP_CASES += [pytest.param(1e-2, R, kind, art, shape, id=f"0.01-{R}-{kind}-{shape}-{art}") for art in (False, True)
+               for R, kind, shape in ((48, "random", "tiles"), (48, "none", "tiles"), (48, "random", "tiles_plus1"), (48, "none", "tiles_plus1"),
+                                      (192, "halfspace", "many_tiles"))]
+
+
+@pytest.mark.parametrize("eps,R,kind,articulated,shape", STOP_CASES)
+def test_stop_equals_zeroing_and_follows_the_rule(ops, dev, articulated, kind, R, eps, shape):
     ops.set_bottleneck_fold(True)
     net = Net(ops, _model(dev, articulated, eps), _latents(dev) if articulated else None)
-    o, d, v = _rays(dev, 900, seed=4)
-    n = o.shape[0]
+    n, num_levels, sizes = SHAPES[shape]
+    opts = None if sizes is None else ops.RenderOpts(num_coarse_samples=sizes[0], num_fine_samples=sizes[1])
+    op = ops._opts(opts)
+    o, d, v = _rays(dev, n, seed=4)
     grid = _grid(ops, dev, kind)
-    got, occupied, stop = net.stop(o, d, v, grid, eps, R)
-    yard = _yardstick(net, o, d, v, grid, stop)
+    got, occupied, stop = net.stop(o, d, v, grid, eps, R, num_levels, opts)
+    yard = _yardstick(net, o, d, v, grid, stop, op.num_coarse_samples, op.num_fine_samples, num_levels)
     # 2. the same bits as zeroing the empty and the dead samples; `occupied` counts the samples that ran
     _same([y["got"] for y in yard], got)
-    assert occupied.tolist() == [y["count"] for y in yard]
+    assert occupied.tolist() == [y["count"] for y in yard] + [0] * (2 - num_levels)
     # determinism and chunking: the same bits, the same stops
-    small = int(ops.lib.aon_render_stop_workspace_bytes(101, None))
-    again, occ2, stop2 = net.stop(o, d, v, grid, eps, R, workspace_bytes=small)
+    small = int(ops.lib.aon_render_stop_workspace_bytes(101, None if opts is None else ops.C.byref(op.c_struct(NEAR, FAR)[0])))
+    again, occ2, stop2 = net.stop(o, d, v, grid, eps, R, num_levels, opts, workspace_bytes=small)
     _same(got, again)
     assert torch.equal(stop, stop2) and occ2.tolist() == occupied.tolist()
 

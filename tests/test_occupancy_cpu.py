@@ -1,7 +1,9 @@
 """CPU: the occupancy-grid convention through its numpy reference on hand-computed cases, and the C ABI / Python
 wrappers' argument checks, which need no GPU."""
 import ctypes
+import json
 import math
+import os
 
 import numpy as np
 import pytest
@@ -198,3 +200,28 @@ def test_python_wrappers_raise_on_bad_arguments():
     g = ops.OccupancyGrid(torch.zeros(2, dtype=torch.int32), (4, 4, 4), (-1.0, -1.0, -1.0), (0.5, 0.5, 0.5), 0.01, 1)
     with pytest.raises(ValueError):
         ops.render_fwd_occ(None, None, x, x, x, 2.0, 6.0, True, g, num_levels=3)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the workspace queries
+def _workspace_table():
+    """The three occupancy workspace queries over the table of tests/golden/g29_occ_workspace_bytes.json, in that file's shape."""
+    from aon_amd import _lib, ops
+
+    lib = _lib.lib
+    render = {}
+    for name, opts in (("default", None), ("63_64", ops.RenderOpts(num_coarse_samples=63, num_fine_samples=64))):
+        st = None if opts is None else ctypes.byref(opts.c_struct(2.0, 6.0)[0])
+        render[name] = [[n, int(lib.aon_render_occ_workspace_bytes(n, st)), int(lib.aon_render_stop_workspace_bytes(n, st))]
+                        for n in (0, 1, 5, 16, 17, 340, 1024, 65536, 327680)]
+    scene = [[pairs, k, s, int(lib.aon_scene_occ_workspace_bytes(pairs, k, s))]
+             for pairs in (0, 1, 16, 17, 300, 65536) for k in (1, 3, 16) for s in (9, 64, 193)]
+    return {"render": render, "scene": scene}
+
+
+def test_workspace_queries_return_the_recorded_sizes():
+    """aon_render_occ_workspace_bytes, aon_render_stop_workspace_bytes (rows: n_rays, occ bytes, stop bytes; default and (63, 64) sample
+    counts) and aon_scene_occ_workspace_bytes (rows: pairs, k, s, bytes) against the answers recorded from the library before the three
+    compactions shared one workspace layout: callers size their buffers with these, so every answer stays what it was."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g29_occ_workspace_bytes.json")) as f:
+        want = json.load(f)
+    assert _workspace_table() == want

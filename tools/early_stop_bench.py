@@ -9,8 +9,8 @@
 Fields: the synthetic weights made sparse by synthetic.sparsify_nerf_ ("sparse", density scale 30, the field of section 4.9), the same with
 the density scale --opaque-scale ("opaque": surfaces a ray cannot see through), and the synthetic scene trained by
 examples/run_single_scene.py for --steps steps ("trained"; --no-trained skips it).  For the kernels alone run it under
-`rocprofv3 --kernel-trace --stats -- python tools/early_stop_bench.py` and read occ_mark_round_kernel / occ_scan_kernel /
-occ_emit_round_kernel / occ_depth_kernel and the mlp_fwd_kernel instances.
+`rocprofv3 --kernel-trace --stats -- python tools/early_stop_bench.py` and read occ_mark_kernel<1> / occ_scan_kernel<1> /
+occ_emit_kernel<1> / occ_depth_kernel and the mlp_fwd_kernel instances.
 
     python tools/early_stop_bench.py [--reps 5] [--eps 1e-3] [--rounds 16 32 48 64] [--chunk 3840] [--steps 300] [--no-trained]
 """

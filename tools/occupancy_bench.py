@@ -8,7 +8,7 @@
 
 Fields: the synthetic weights made sparse by synthetic.sparsify_nerf_ (80 % of [-4, 4]^3 empty, "sparse"), and the synthetic scene trained by
 examples/run_single_scene.py for --steps steps ("trained"; --no-trained skips it).  For the kernels alone run it under
-`rocprofv3 --kernel-trace --stats -- python tools/occupancy_bench.py` and read occ_mark_kernel / occ_scan_kernel / occ_emit_kernel and the
+`rocprofv3 --kernel-trace --stats -- python tools/occupancy_bench.py` and read occ_mark_kernel<1> / occ_scan_kernel<1> / occ_emit_kernel<1> and the
 mlp_fwd_kernel instances.
 
     python tools/occupancy_bench.py [--reps 5] [--steps 300] [--no-trained]

@@ -243,7 +243,14 @@ _SCENE_OCC_SIGS = {
 }
 
 
-for _name, (_res, _args) in {**_SIGS, **_EXT_SIGS, **_SCENE_SIGS, **_SCENE_OCC_SIGS}.items():
+# include/aon_hip_scene_grad.h: a fifth table, kept out of the four lists above
+_SCENE_GRAD_SIGS = {
+    # raw, t_vals, slot, rays_d | g_rgb, g_acc, g_depth, g_obj_acc | n, k, pairs, s, white_bkgd, act | opts | d_raw | stream
+    "aon_scene_composite_bwd": (_i, [_p] * 4 + [_p] * 4 + [_l, _i, _l, _i, _i, _i] + [_p] + [_p] + [_p]),
+}
+
+
+for _name, (_res, _args) in {**_SIGS, **_EXT_SIGS, **_SCENE_SIGS, **_SCENE_OCC_SIGS, **_SCENE_GRAD_SIGS}.items():
     _fn = getattr(lib, _name)  # AttributeError here = the .so does not export what the header declares
     _fn.restype = _res
     _fn.argtypes = _args
@@ -286,3 +293,8 @@ def scene_symbols():
 def scene_occ_symbols():
     """the names include/aon_hip_scene_occ.h declares"""
     return sorted(_SCENE_OCC_SIGS)
+
+
+def scene_grad_symbols():
+    """the names include/aon_hip_scene_grad.h declares"""
+    return sorted(_SCENE_GRAD_SIGS)

@@ -304,3 +304,75 @@ class RenderArticulatedInputs(torch.autograd.Function):
         if want_lat:
             lat = tuple(g_lat[k].reshape(shp) if need[12 + i] else None for i, (k, shp) in enumerate(zip(_LATENT_KEYS, ctx.lat_shapes)))
         return ray + (None,) * 9 + lat + (None,) * (len(ops.ART_PARAM_ORDER) * ctx.num_levels)
+
+
+class RenderLevelScene(torch.autograd.Function):
+    """ONE level of a scene on given sample positions t (P, S), from the stage-level entry points, as
+    RenderLevelVanilla is for the vanilla network: per object with pairs, in ascending k, aon_art_mlp_fwd_train on its segment with its own
+    per-call block -> aon_scene_composite | aon_scene_composite_bwd -> per object aon_art_bwd_chain -> aon_art_wgrad.  Gradients reach the 40
+    parameters (summed over the objects in ascending k) and each object's three codes; the pairs, t and the rays are data.  The merged
+    weights it returns feed the next level's inverse CDF and carry no gradient.
+
+    ``apply(pairs, t_vals, rays_d, white_bkgd, opts, packed_fwd, packed_bwd, degrees, *tensors)``: pairs an ops.ScenePairs, rays_d the WORLD
+    directions, tensors = (density, color, articulation) of object 0 .. K - 1, then the 40 parameters in ops.ART_PARAM_ORDER.
+    -> (rgb (n, 3), acc (n,), depth (n,), obj_acc (n, K), weights (P, S))."""
+
+    @staticmethod
+    def forward(ctx, pairs, t_vals, rays_d, white_bkgd, opts, packed_fwd, packed_bwd, degrees, *tensors):
+        K, n_par = pairs.K, len(ops.ART_PARAM_ORDER)
+        if len(tensors) != 3 * K + n_par:
+            raise ValueError(f"RenderLevelScene: expected {3 * K} codes and {n_par} parameters, got {len(tensors)} tensors")
+        # codes and parameters are read again by the backward: saved the autograd way (an in-place update in between raises)
+        ctx.save_for_backward(*tensors)
+        ctx.set_materialize_grads(False)
+        params = dict(zip(ops.ART_PARAM_ORDER, (p.detach() for p in tensors[3 * K:])))
+        t = t_vals.detach()
+        raw = torch.empty((pairs.P, t.shape[1], 4), dtype=torch.float32, device=t.device)
+        per_object = []
+        for k in range(K):
+            seg = pairs.segment(k)
+            if seg.stop == seg.start:      # an object without a pair costs no launch
+                per_object.append(None)
+                continue
+            small = ops.art_prepare(params, dict(zip(_LATENT_KEYS, tensors[3 * k: 3 * k + 3])), out=None, degrees=degrees)
+            _, planes, masks = ops.art_mlp_fwd_train(packed_fwd, small, pairs.rays_o[seg], pairs.rays_d[seg], pairs.viewdirs[seg], t[seg], out=raw[seg])
+            per_object.append((small, planes, masks))
+        rgb, acc, depth, obj_acc, weights = ops.scene_composite(raw, t, pairs, rays_d, white_bkgd, opts=opts)
+        ctx.keep = (pairs, t, rays_d.detach(), raw, per_object, packed_bwd, opts, tuple(degrees))
+        ctx.white_bkgd = white_bkgd
+        ctx.mark_non_differentiable(weights)
+        return rgb, acc, depth, obj_acc, weights
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, _g_weights):
+        _check_not_released(ctx)
+        pairs, t, rays_d, raw, per_object, packed_bwd, opts, degrees = ctx.keep
+        tensors = ctx.saved_tensors   # (raises if a code or a parameter was modified in place since the forward)
+        K, S, dev = pairs.K, t.shape[1], t.device
+        params = dict(zip(ops.ART_PARAM_ORDER, tensors[3 * K:]))
+        if g_rgb is None:
+            g_rgb = torch.zeros((pairs.n, 3), dtype=torch.float32, device=dev)
+        d_raw = ops.scene_composite_bwd(raw, t, pairs, rays_d, g_rgb, g_acc, g_depth, g_obj_acc, ctx.white_bkgd, opts=opts)
+        total, g_codes = None, []
+        for k in range(K):
+            codes = tensors[3 * k: 3 * k + 3]
+            if per_object[k] is None:
+                g_codes += [torch.zeros_like(c) for c in codes]
+                continue
+            small, planes, masks = per_object[k]
+            seg = pairs.segment(k)
+            rows = (seg.stop - seg.start) * S
+            d_seg = torch.zeros((ops.plane_samples(planes), 4), dtype=torch.float32, device=dev)   # the chain reads the zero tail
+            d_seg[:rows] = d_raw[seg].reshape(rows, 4)
+            dplanes, dxp = ops.art_bwd_chain(packed_bwd, small, d_seg, masks, planes)
+            grads, g_lat = ops.art_wgrad(planes, dplanes, d_seg, dxp, params, dict(zip(_LATENT_KEYS, codes)), degrees, packed_bwd=packed_bwd)
+            if total is None:
+                total = grads
+            else:      # plain adds in ascending k: a fixed order
+                for name in ops.ART_PARAM_ORDER:
+                    total[name] += grads[name]
+            g_codes += [g_lat[key].reshape(c.shape) for key, c in zip(_LATENT_KEYS, codes)]
+        if total is None:
+            total = {name: torch.zeros_like(p) for name, p in params.items()}
+        ctx.keep, ctx.released = None, True
+        return (None,) * 8 + tuple(g_codes) + tuple(total[name] for name in ops.ART_PARAM_ORDER)

@@ -231,4 +231,10 @@ int64_t ray_limits_workspace_bytes(int64_t n);
 hipError_t launch_ray_limits(const float* rays_o, const float* rays_d, int64_t n, const float* lo3, const float* hi3, float* near, float* far,
                              uint8_t* live, char* ws, hipStream_t stream);
 
+// ---- aon_scene_grad.hip: the backward of the merged scene composite ----
+int64_t scene_composite_bwd_wave_bytes(int K, int S);   // LDS of one wavefront (= one ray)
+hipError_t launch_scene_composite_bwd(const float* raw, const float* t_vals, const int32_t* slot, const float* dirs, const float* g_rgb,
+                                      const float* g_acc, const float* g_depth, const float* g_obj_acc, int64_t n, int K, int64_t pairs, int S,
+                                      int white_bkgd, const ActParams& ap, float* d_raw, hipStream_t stream);
+
 }  // namespace aon

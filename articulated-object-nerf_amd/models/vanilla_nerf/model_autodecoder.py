@@ -368,6 +368,108 @@ class LitNeRF_AutoDecoder(Harness):
         batch = self._unbatch(batch)
         return self.render_rays_test(batch, self.code_library(batch, is_test=True))
 
+    def _placement_codes(self, who, placements):
+        """``(instance_id, articulation, pose, box)`` placements -> [(instance_id, articulation, latents, pose, box)], the latents looked up in the
+        library: ``articulation`` a row index into get_interpolated_articulations or an explicit (32,) code."""
+        dev = next(self.model.parameters()).device
+        table = self.code_library.get_interpolated_articulations(max_interpolations=2, device=dev)
+        n_inst = self.code_library.embedding_instance_shape.weight.shape[0]
+        out = []
+        for j, placement in enumerate(placements):
+            if len(placement) != 4:
+                raise ValueError(f"{who}: placement {j} must be (instance_id, articulation, pose, box)")
+            iid, art, pose, box = placement
+            if isinstance(iid, bool) or not isinstance(iid, int) or not 0 <= iid < n_inst:
+                raise ValueError(f"{who}: placement {j}: instance_id {iid!r} outside the library ({n_inst} instances)")
+            if isinstance(art, int) and not isinstance(art, bool):
+                if not 0 <= art < table.shape[0]:
+                    raise ValueError(f"{who}: placement {j}: articulation row {art} outside the {table.shape[0]} interpolated states")
+                code = table[art: art + 1]
+            else:
+                code = torch.as_tensor(art, dtype=torch.float32, device=dev).reshape(1, -1)
+            ids = torch.tensor([iid], dtype=torch.int64, device=dev)
+            latents = {"density": self.code_library.embedding_instance_shape(ids), "color": self.code_library.embedding_instance_appearance(ids),
+                       "articulation": code}
+            out.append((iid, art, latents, pose, box))
+        return out
+
+    def fit_scene_codes(self, batches, placements, steps: int, lr: float = 5.0e-3, fit_keys=("density", "color", "articulation"), seed: int = 0):
+        """Fit the codes of the K objects of ONE frame layout to observed frames with the network FROZEN: `steps` Adam
+        steps against mse over the levels (helper.train_loss) + 1e-4 * sum over objects and codes of mean ||code||, batch `i % len(batches)`
+        at step i.
+
+        batches: dicts of WORLD rays ("rays_o", "rays_d", "viewdirs") plus "target".  placements: as render_scene takes them, at known poses;
+        each object's codes start from the library rows (or the explicit articulation code) of its placement.  fit_keys: the codes that
+        move; the others keep their starting values.  seed: accepted for symmetry with fit_latents; scenes sample without randomness.
+        -> (list of K code dicts of (1, dim) tensors, per-step losses as one (steps,) device tensor); the only host synchronisation of a
+        step is the read-back of the pair counts (ops.scene_pairs).
+
+        The network's requires_grad flags are cleared for the duration and restored.  The codes of all K objects, their gradients and the
+        Adam moments are one flat (4, 288 K) buffer stepped by ONE launch (aon_adam_step).  Every step pays the full weight-gradient stage
+        (scene.render_scene_grad has no latent-only shortcut)."""
+        from ...scene import SceneObject, render_scene_grad
+
+        batches, _ = self._fit_args("fit_scene_codes", steps, batches)
+        if not (isinstance(lr, (int, float)) and lr > 0):
+            raise ValueError(f"fit_scene_codes: lr must be positive, got {lr!r}")
+        keys = [k for k, _ in ops._LATENT_KEYS]
+        fit_keys = tuple(fit_keys)
+        if not fit_keys or not set(fit_keys) <= set(keys):
+            raise ValueError(f"fit_scene_codes: fit_keys must name some of {keys}, got {fit_keys!r}")
+        placed = self._placement_codes("fit_scene_codes", placements)
+        if not 1 <= len(placed) <= ops.SCENE_MAX_OBJECTS:
+            raise ValueError(f"fit_scene_codes: a scene holds 1 to {ops.SCENE_MAX_OBJECTS} objects, got {len(placed)}")
+        for b in batches:
+            if not all(k in b for k in ("rays_o", "rays_d", "viewdirs", "target")):
+                raise ValueError("fit_scene_codes: every batch needs 'rays_o', 'rays_d', 'viewdirs' (world) and 'target'")
+        dev = next(self.model.parameters()).device
+        width = sum(d for _, d in ops._LATENT_KEYS)
+        arena = torch.zeros((4, width * len(placed)), dtype=torch.float32, device=dev)   # rows: codes, gradients, exp_avg, exp_avg_sq
+        objects, leaves = [], []
+        for j, (_, _, latents, pose, box) in enumerate(placed):
+            SceneObject(latents, pose, box)      # raises for a malformed code, pose or box before anything is copied
+            off, codes = j * width, {}
+            for k, d in ops._LATENT_KEYS:
+                view = arena[0, off: off + d].view(1, d)
+                view.copy_(latents[k].detach().reshape(1, d))
+                codes[k] = view.detach().requires_grad_(k in fit_keys)
+                off += d
+            leaves.append(codes)
+            objects.append(SceneObject(codes, pose, box))
+        wrt = [codes[k] for codes in leaves for k in keys if k in fit_keys]
+        slots = [arena[1, j * width + off: j * width + off + d] for j in range(len(placed))
+                 for (k, d), off in zip(ops._LATENT_KEYS, (0, 128, 256)) if k in fit_keys]
+        net_params = list(self.model.parameters())
+        flags = [p.requires_grad for p in net_params]
+        losses = torch.zeros(steps, dtype=torch.float32, device=dev)
+        try:
+            for p in net_params:
+                p.requires_grad_(False)
+            with torch.enable_grad():
+                for i in range(steps):
+                    b = batches[i % len(batches)]
+                    rays = {k: b[k].to(device=dev, dtype=torch.float32).reshape(-1, 3) for k in ("rays_o", "rays_d", "viewdirs")}
+                    target = b["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
+                    levels = render_scene_grad(self.model, objects, rays, self.white_bkgd)
+                    loss = helper.train_loss([lvl[:3] for lvl in levels], target, (), 1e-4)[0]
+                    loss = loss + 1e-4 * sum(torch.mean(torch.norm(codes[k], dim=0)) for codes in leaves for k in keys)
+                    grads = torch.autograd.grad(loss, wrt)
+                    losses[i] = loss.detach()
+                    for slot, g in zip(slots, grads):
+                        slot.copy_(g.reshape(-1))
+                    ops.adam_step(arena[0], arena[1], arena[2], arena[3], 0, arena.shape[1], float(lr), 0.9, 0.999, 1e-8, i + 1)
+        finally:
+            for p, f in zip(net_params, flags):
+                p.requires_grad_(f)
+        fitted = []
+        for j in range(len(placed)):
+            off, codes = j * width, {}
+            for k, d in ops._LATENT_KEYS:
+                codes[k] = arena[0, off: off + d].view(1, d).clone()
+                off += d
+            fitted.append(codes)
+        return fitted, losses
+
     @torch.no_grad()
     def render_scene(self, batch, placements, occupancy=None):
         """Several instances of the library in ONE frame (scene.render_scene): ``placements`` is a list of up to 16
@@ -390,28 +492,11 @@ class LitNeRF_AutoDecoder(Harness):
             occ_args = {"bounds": (-1.2, 1.2), **occupancy}
             occ_key = tuple(repr(occ_args.get(k)) for k in self._OCC_KEYS)
 
-        dev = next(self.model.parameters()).device
-        table = self.code_library.get_interpolated_articulations(max_interpolations=2, device=dev)
-        n_inst = self.code_library.embedding_instance_shape.weight.shape[0]
         objects = []
-        for j, placement in enumerate(placements):
-            if len(placement) != 4:
-                raise ValueError(f"render_scene: placement {j} must be (instance_id, articulation, pose, box)")
-            iid, art, pose, box = placement
-            if isinstance(iid, bool) or not isinstance(iid, int) or not 0 <= iid < n_inst:
-                raise ValueError(f"render_scene: placement {j}: instance_id {iid!r} outside the library ({n_inst} instances)")
-            if isinstance(art, int) and not isinstance(art, bool):
-                if not 0 <= art < table.shape[0]:
-                    raise ValueError(f"render_scene: placement {j}: articulation row {art} outside the {table.shape[0]} interpolated states")
-                code = table[art: art + 1]
-            else:
-                code = torch.as_tensor(art, dtype=torch.float32, device=dev).reshape(1, -1)
-            ids = torch.tensor([iid], dtype=torch.int64, device=dev)
-            latents = {"density": self.code_library.embedding_instance_shape(ids), "color": self.code_library.embedding_instance_appearance(ids),
-                       "articulation": code}
+        for iid, art, latents, pose, box in self._placement_codes("render_scene", placements):
             grid = None
             if occupancy is not None:
-                key = (iid, art if isinstance(art, int) else tuple(code.reshape(-1).tolist()), occ_key)
+                key = (iid, art if isinstance(art, int) else tuple(latents["articulation"].reshape(-1).tolist()), occ_key)
                 grid = self._scene_grids.get(key)
                 if grid is None:
                     grid = _occupancy.build_occupancy(self.model, latents=latents, **occ_args)

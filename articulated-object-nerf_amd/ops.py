@@ -977,11 +977,18 @@ def pack_art_mlp_bwd(params: dict, out: torch.Tensor | None = None, degrees=(0, 
     return _tag(out)
 
 
-def art_mlp_fwd_train(packed, small, rays_o, rays_d, viewdirs, t_vals):
+def art_mlp_fwd_train(packed, small, rays_o, rays_d, viewdirs, t_vals, out=None):
+    """``out``: as ops.art_mlp_fwd's -- a contiguous fp32 (n, S, 4) tensor to write ``raw`` into instead of a fresh one (a scene's segments)."""
     o, d, v, t = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs"), _f32(t_vals, "t_vals")
     n, S = t.shape
     Np = padded_samples(n * S)
-    raw = torch.empty((n, S, 4), dtype=torch.float32, device=t.device)
+    if out is None:
+        raw = torch.empty((n, S, 4), dtype=torch.float32, device=t.device)
+    else:
+        raw = out
+        if not (isinstance(raw, torch.Tensor) and raw.dtype == torch.float32 and tuple(raw.shape) == (n, S, 4) and raw.device == t.device
+                and raw.is_contiguous()):
+            raise ValueError(f"art_mlp_fwd_train: out must be a contiguous float32 ({n}, {S}, 4) tensor on {t.device}")
     planes = _new_planes(int(lib.aon_art_train_plane_rows()), Np, t.device)
     masks = torch.empty(int(lib.aon_art_train_mask_bytes(Np)), dtype=torch.uint8, device=t.device)
     with torch.cuda.device(t.device):
@@ -2013,6 +2020,35 @@ def scene_composite(raw, t_vals, pairs: ScenePairs, rays_d, white_bkgd, opts=Non
         check(lib.aon_scene_composite(_ptr(r) if P else None, _ptr(t) if P else None, _ptr(pairs.slot), _ptr(d), n, K, P, S, int(bool(white_bkgd)), act,
                                       C.byref(st), _ptr(rgb), _ptr(acc), _ptr(depth), _ptr(obj_acc), _ptr(weights), _stream()), "aon_scene_composite")
     return rgb, acc, depth, obj_acc, weights
+
+
+def scene_composite_bwd(raw, t_vals, pairs: ScenePairs, rays_d, g_rgb, g_acc=None, g_depth=None, g_obj_acc=None, white_bkgd=True, opts=None,
+                        act=ACT_ARTICULATED) -> torch.Tensor:
+    """The backward of scene_composite on the same raw (P, S, 4), t_vals (P, S), pairs and WORLD rays_d (include/aon_hip_scene_grad.h,
+    DESIGN.md section 4.18): upstream gradients g_rgb (n, 3), g_acc / g_depth (n,), g_obj_acc (n, K) -- the last three None for zero --
+    -> d_raw (P, S, 4) = dL/d raw.  t, the pairs and rays_d are data: nothing flows to them."""
+    d = _f32(rays_d.detach(), "rays_d").reshape(-1, 3)
+    n, K, P, dev = pairs.n, pairs.K, pairs.P, d.device
+    t, r, g = _f32(t_vals, "t_vals"), _f32(raw, "raw"), _f32(g_rgb, "g_rgb")
+    S = t.shape[-1]
+    if d.shape[0] != n or tuple(t.shape) != (P, S) or tuple(r.shape) != (P, S, 4) or tuple(g.shape) != (n, 3):
+        raise ValueError(f"scene_composite_bwd: expected rays_d ({n}, 3), t_vals ({P}, S), raw ({P}, S, 4) and g_rgb ({n}, 3), got {tuple(d.shape)}, "
+                         f"{tuple(t.shape)}, {tuple(r.shape)}, {tuple(g.shape)}")
+    opt = []
+    for x, name, shape in ((g_acc, "g_acc", (n,)), (g_depth, "g_depth", (n,)), (g_obj_acc, "g_obj_acc", (n, K))):
+        if x is not None:
+            x = _f32(x, name)
+            if tuple(x.shape) != shape:
+                raise ValueError(f"scene_composite_bwd: expected {name} {shape} or None, got {tuple(x.shape)}")
+        opt.append(x)
+    st, _keep = _opts(opts).c_struct(1.0, 1.0)
+    d_raw = torch.zeros((P, S, 4), dtype=torch.float32, device=dev)
+    if n == 0 or P == 0:      # nothing to launch (and no pointer to hand over)
+        return d_raw
+    with torch.cuda.device(dev):
+        check(lib.aon_scene_composite_bwd(_ptr(r), _ptr(t), _ptr(pairs.slot), _ptr(d), _ptr(g), _ptr(opt[0]), _ptr(opt[1]), _ptr(opt[2]), n, K, P, S,
+                                          int(bool(white_bkgd)), act, C.byref(st), _ptr(d_raw), _stream()), "aon_scene_composite_bwd")
+    return d_raw
 
 
 def scene_art_mlp_fwd(packed, smalls, pairs: ScenePairs, t_vals) -> torch.Tensor:

@@ -1,6 +1,7 @@
 """Scenes of several posed articulated objects in one frame: one ``NeRF_AE_Art`` and K <= 16 objects, each with its
 own codes, rigid object-to-world pose and box, rendered with correct mutual occlusion -- the approach of Neural Scene Graphs (Ost et al.): a
-ray-box test per object, samples inside each box, one sorted merge along the ray.  Inference only.
+ray-box test per object, samples inside each box, one sorted merge along the ray.  ``render_scene`` is inference only; ``render_scene_grad``
+ is the same frame with gradients to the objects' codes and the network's weights.
 
 Per chunk of rays: ``ops.scene_pairs`` pairs rays with the boxes they cross (one host read-back: the pair counts), the existing per-ray-bounds
 sampler, MLP kernel and inverse-CDF kernel run on the pairs -- the MLP once per object segment with that object's per-call block -- and
@@ -113,3 +114,42 @@ def render_scene(model, objects, rays, white_bkgd, chunk: int = 65536, randomize
     if host_counts is not None:
         occupied = [torch.tensor(c, dtype=torch.int64).to(o.device) for c in host_counts]
     return (levels, occupied) if want_occupied else levels
+
+
+def render_scene_grad(model, objects, rays, white_bkgd, randomized: bool = False):
+    """``render_scene`` with autograd history: -> ``[(rgb (N, 3), acc (N,), depth (N,), obj_acc (N, K))]`` per level,
+    the bits ``render_scene`` returns, whose gradients reach every object's three codes (``SceneObject.latents`` may hold leaf tensors that
+    require grad) and the network's weights.  The pairs, the sample positions of both levels (the fine draws come from the merged coarse
+    weights, detached: helper.py:249) and the rays are data: no gradient reaches a pose or a ray.
+
+    One chunk: the activation planes of every pair (13.8 KB per sample) live until the backward, and are released by it -- a second backward
+    through the same forward raises.  Dense only: an object carrying a grid is refused (the training forward has no gather instance).  A
+    frozen network still pays the full weight-gradient stage."""
+    from .autograd import RenderLevelScene
+
+    if randomized:
+        raise ValueError("scene gradients sample without randomness: randomized=True is refused")
+    if model.noise_std > 0:
+        raise NotImplementedError("scene gradients take no density noise (noise_std > 0)")
+    if model.num_levels not in (1, 2):
+        raise NotImplementedError("scene gradients run one or two levels")
+    objects = _check_objects(objects)
+    for k, ob in enumerate(objects):
+        if ob.grid is not None:
+            raise NotImplementedError(f"scene gradients are dense only: object {k} carries an occupancy grid")
+    o, d, v = rays["rays_o"], rays["rays_d"], rays["viewdirs"]
+    mlps = [model.coarse_mlp, model.fine_mlp][: model.num_levels]
+    codes = [ob.latents[key] for ob in objects for key in _LATENT_WIDTHS]
+    with torch.no_grad():
+        pairs = ops.scene_pairs(o, d, v, objects)
+        t, _ = ops.sample_along_rays(pairs.rays_o, pairs.rays_d, model.num_coarse_samples, pairs.near, pairs.far, want_coords=False, lindisp=model.lindisp)
+    levels = []
+    for level, mlp in enumerate(mlps):
+        # fresh streams: the backward reads them again, and a later forward must not overwrite what this graph still needs
+        rgb, acc, depth, obj_acc, weights = RenderLevelScene.apply(pairs, t, d, bool(white_bkgd), model._opts, mlp.packed(True), mlp.packed_bwd(True),
+                                                                   mlp.degrees, *codes, *mlp.ordered_params())
+        levels.append((rgb, acc, depth, obj_acc))
+        if level + 1 < len(mlps):
+            with torch.no_grad():
+                t = ops.sample_pdf_t_n(t, weights, model.num_fine_samples)
+    return levels

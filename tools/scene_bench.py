@@ -16,7 +16,14 @@ field at section 4.9's defaults (128^3 cells over [-1.2, 1.2]^3, threshold 0.01,
 the same run, the samples that reached the MLP per level, and the gather-to-dense per-sample rate of the MLP stage.  When the synthetic
 field is too hazy for a grid to empty anything, that is reported and the leg is repeated on synthetic.sparsify_nerf_(latents=)'s field.
 
-    python tools/scene_bench.py [--reps 5] [--occupancy] [--out profiles/scene_bench.json]
+--grad measures gradients through scenes INSTEAD of the frames above and adds a "grad" list to the file, leaving its
+other records as they are: K = 1 and 3 on 4,096 rays of the frame at 65 + 193 samples -- one step of scene.render_scene_grad, a loss on all
+four outputs of both levels and its gradients to every code and weight (host clock around work that ends in a device synchronise, and
+device events around the whole step), the device time of ops.scene_composite_bwd and ops.scene_composite inside that step and their share
+of it, and for K = 1 the step of the same sample count through NeRF_AE_Art.forward + backward on the one object's pairs (its object-frame
+rays with their per-ray near / far), measured in the same run.
+
+    python tools/scene_bench.py [--reps 5] [--occupancy] [--grad] [--out profiles/scene_bench.json]
 """
 import argparse
 import json
@@ -162,10 +169,70 @@ def occupancy_record(model, objects, rays, n, reps, dev):
     return rec
 
 
+GRAD_RAYS = 4096
+
+
+def grad_records(model, ro, vd, reps, dev):
+    """the --grad legs -> one record per K"""
+    idx = (torch.arange(GRAD_RAYS, device=dev) * (ro.shape[0] // GRAD_RAYS)).long()
+    rays = {"rays_o": ro[idx].contiguous(), "rays_d": vd[idx].contiguous(), "viewdirs": vd[idx].contiguous()}
+    target = syn.seeded_uniform(5, GRAD_RAYS, 3).to(dev)
+    keys = ("density", "color", "articulation")
+    nets = [p for m in (model.coarse_mlp, model.fine_mlp) for p in m.ordered_params()]
+    recs = []
+    for K in (1, 3):
+        objects = [scene.SceneObject({k: v.clone().requires_grad_(True) for k, v in ob.latents.items()}, ob.pose, ob.box) for ob in make_scene(K, dev)]
+        wrt = [ob.latents[k] for ob in objects for k in keys] + nets
+
+        def step():
+            levels = scene.render_scene_grad(model, objects, rays, True)
+            loss = sum(torch.mean((lv[0] - target) ** 2) + 0.1 * lv[1].mean() + 0.05 * lv[2].mean() + 0.2 * (lv[3] ** 2).mean() for lv in levels)
+            return torch.autograd.grad(loss, wrt)
+
+        ms_host = frame_time(step, reps) * 1e3
+        # device events: around the whole step, and around the two composite stage calls inside it
+        real_bwd, real_fwd = ops.scene_composite_bwd, ops.scene_composite
+        runs = []
+        try:
+            for _ in range(reps):
+                st = Stages()
+                ops.scene_composite_bwd = lambda *a, **kw: st.run("composite_bwd", lambda: real_bwd(*a, **kw))
+                ops.scene_composite = lambda *a, **kw: st.run("composite", lambda: real_fwd(*a, **kw))
+                st.run("step", step)
+                runs.append(st.totals())
+        finally:
+            ops.scene_composite_bwd, ops.scene_composite = real_bwd, real_fwd
+        dev_ms = {k: statistics.median(r[k] for r in runs) for k in runs[0]}
+        with torch.no_grad():
+            pairs = ops.scene_pairs(rays["rays_o"], rays["rays_d"], rays["viewdirs"], objects)
+        rec = {"rays": GRAD_RAYS, "samples": "65 + 193", "objects": K, "reps": reps, "pairs": pairs.P, "mlp_samples": pairs.P * (65 + 193),
+               "ms_step_host": round(ms_host, 3), "ms_step_device": round(dev_ms["step"], 3), "ms_composite_bwd": round(dev_ms["composite_bwd"], 4),
+               "ms_composite_fwd": round(dev_ms["composite"], 4), "share_composite_bwd": round(dev_ms["composite_bwd"] / dev_ms["step"], 5),
+               "share_composite_fwd": round(dev_ms["composite"] / dev_ms["step"], 5),
+               "composite_bwd_bytes": pairs.P * (65 + 193) * 36}
+        if K == 1:      # the same samples through the one-object step: the object's pairs as a batch of rays with per-ray near / far
+            one = {"rays_o": pairs.rays_o.contiguous(), "rays_d": pairs.rays_d.contiguous(), "viewdirs": pairs.viewdirs.contiguous()}
+            near, far = pairs.near.reshape(-1, 1).contiguous(), pairs.far.reshape(-1, 1).contiguous()
+            lat = objects[0].latents
+            tg = target[pairs.ray.long()]
+
+            def single():
+                out = model(one, False, True, near, far, lat)
+                loss = sum(torch.mean((o[0] - tg) ** 2) + 0.1 * o[1].mean() + 0.05 * o[2].mean() for o in out)
+                return torch.autograd.grad(loss, [lat[k] for k in keys] + nets)
+
+            rec["ms_one_object_step_host"] = round(frame_time(single, reps) * 1e3, 3)
+            rec["scene_step_vs_one_object_step"] = round(ms_host / rec["ms_one_object_step_host"], 4)
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+    return recs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--occupancy", action="store_true", help="add the occupancy-grid legs (DESIGN.md section 4.17)")
+    ap.add_argument("--grad", action="store_true", help="measure gradients through scenes instead (DESIGN.md section 4.18)")
     ap.add_argument("--objects", type=int, nargs="+", default=[1, 3, 8])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_bench.json"))
     args = ap.parse_args()
@@ -179,6 +246,14 @@ def main():
     ro, vd = ops.raygen(syn.look_at_pose(), H, W, syn.focal_from_fovy(H), device=dev)
     rays = {"rays_o": ro, "rays_d": vd, "viewdirs": vd}
     n = ro.shape[0]
+    if args.grad:
+        doc = json.load(open(args.out)) if os.path.exists(args.out) else {"tool": "tools/scene_bench.py", "device": torch.cuda.get_device_name(0)}
+        doc["grad"] = grad_records(model, ro, vd, args.reps, dev)
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+        return
     recs = []
     with torch.no_grad():
         for K in args.objects:

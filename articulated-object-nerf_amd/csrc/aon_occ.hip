@@ -25,6 +25,7 @@
 #include "aon_launch.h"
 #include "../../include/aon_hip_scene.h"
 #include "aon_occ_lookup.h"
+#include "aon_ray_core.h"
 
 namespace aon {
 
@@ -275,8 +276,7 @@ __global__ __launch_bounds__(kOccThreads) void occ_depth_kernel(const f32x4* __r
   const int64_t ray = (int64_t)blockIdx.x * (kOccThreads / 64) + (threadIdx.x >> 6);
   if (ray >= n) return;              // wave-uniform
   if (stop[ray] != S) return;        // stopped in an earlier round
-  const float dn = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(dirs[ray * 3], dirs[ray * 3]), __fmul_rn(dirs[ray * 3 + 1], dirs[ray * 3 + 1])),
-                                        __fmul_rn(dirs[ray * 3 + 2], dirs[ray * 3 + 2])));
+  const float dn = ray_norm_f32(dirs, ray);
   const float* tv = t_vals + ray * S;
   float acc = tau[ray];
   for (int base = s0; base < s1; base += 64) {

@@ -5,6 +5,13 @@
 
 namespace aon {
 
+// ||dirs[ray]|| as the compositing takes it (helper.py:167): fp32, each operation rounded on its own, in this order.  The interval lengths
+// delta_i ||d|| are INPUTS of the function the backward kernels differentiate, so they take the norm from here too.
+__device__ __forceinline__ float ray_norm_f32(const float* dirs, int64_t ray) {
+  const float x = dirs[ray * 3], y = dirs[ray * 3 + 1], z = dirs[ray * 3 + 2];
+  return __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z)));
+}
+
 // ---------------------------------------------------------------------------------------------
 // wave64 helpers
 // ---------------------------------------------------------------------------------------------
@@ -72,6 +79,39 @@ __device__ __forceinline__ double wave_inclusive_sum_f64(double v) {
   v += dpp_f64<0x142, 0xa>(v);
   v += dpp_f64<0x143, 0xc>(v);
   return v;
+}
+
+// The two scans of the compositing backward (aon_composite_grad.h) over a list longer than a wave: 64 elements at a time, lane = element,
+// `carry` kept by the caller from one block of 64 to the next.  Both are Hillis-Steele shuffle scans with fixed operand orders (incl * o,
+// carry * excl;  incl + o, excl + carry): the gradient bits are pinned (tests/golden/g30_composite_hashes.json), and another tree rounds
+// differently.
+// -> carry * prod of v over the lanes below this one;  carry <- carry * prod over all 64   (front to back: carry starts at 1)
+__device__ __forceinline__ double wave_exclusive_product_f64(double v, int lane, double& carry) {
+  double incl = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const double o = __shfl_up(incl, off);
+    if (lane >= off) incl = incl * o;
+  }
+  double excl = __shfl_up(incl, 1);
+  if (lane == 0) excl = 1.0;
+  const double out = carry * excl;
+  carry = carry * __shfl(incl, 63);
+  return out;
+}
+// -> sum of v over the lanes above this one + carry;  carry <- carry + sum over all 64   (blocks taken from the far end: carry starts at 0)
+__device__ __forceinline__ double wave_exclusive_suffix_sum_f64(double v, int lane, double& carry) {
+  double incl = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const double o = __shfl_down(incl, off);
+    if (lane + off < 64) incl = incl + o;
+  }
+  double excl = __shfl_down(incl, 1);
+  if (lane == 63) excl = 0.0;
+  const double out = excl + carry;
+  carry = carry + __shfl(incl, 0);
+  return out;
 }
 
 // inclusive prefix minimum of ints over the 64 lanes

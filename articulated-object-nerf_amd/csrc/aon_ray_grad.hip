@@ -8,17 +8,18 @@
 //   viewdirs enters through pos_enc(viewdirs, 0, deg_view), a constant of the ray:
 //     g_ve = sum_i W_v0[:, 256 : 256 + V]^T dZ_v0,i   g_viewdirs = g_ve pulled back through the encoding at the forward's rounded arguments
 //   |d| scales the interval lengths of the compositing (helper.py:167):
-//     g_n = sum_i dL/dalpha_i (1 - alpha_i) sigma_i delta_i     (fp64 from raw, t, dirs and the upstream gradients, as composite_bwd_kernel)
+//     g_n = sum_i dL/dalpha_i (1 - alpha_i) sigma_i delta_i     (fp64 from raw, t, dirs and the upstream gradients: aon_composite_grad.h)
 //
 //   ray_grad_sample_kernel   lane = sample.  A sample's 128 values of a layer are 32 units of 16 B, 512 B apart inside its step; the 32
 //                            samples of a step sit side by side, so a wave's load is two whole 512-byte runs.  3 + 27 fused multiply-add
 //                            chains over the 128 features in ascending order against weight columns held in LDS; one 128-byte record
 //                            {g_x (3), view-encoding partials (27), 0, 0} per sample.
 //   ray_grad_reduce_kernel   one wavefront per ray.  Lane c < 32 sums component c of the ray's records in fp64, sample after sample in
-//                            ascending order; lane 32 + c the same values times t_i.  Then the norm term (composite_bwd_kernel's two scans)
+//                            ascending order; lane 32 + c the same values times t_i.  Then the norm term (aon_composite_grad.h with d alpha / d |d|)
 //                            and the view encoding's backward; every output is rounded to fp32 once.
 //   vanilla_ray_grad_sample_kernel   the frozen VANILLA network's records for the same reduce kernel (described at the kernel).
 #include "aon_art_common.h"
+#include "aon_composite_grad.h"
 #include "aon_launch.h"
 
 namespace aon {
@@ -114,14 +115,14 @@ struct RgReduceArgs {
   float* g_o; float* g_d; float* g_v;
 };
 
-__device__ __forceinline__ double rg_sigmoidd(double x) { return 1.0 / (1.0 + exp(-x)); }
+// (a butterfly: not the prefix tree of wave_inclusive_sum_f64, which associates differently)
 __device__ __forceinline__ double rg_wsum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;
 }
 
-// g_n of one ray at one level: composite_bwd_kernel's two scans (aon_train.hip) with dalpha_i / d|d| = (1 - alpha_i) sigma_i delta_i in the
+// g_n of one ray at one level: the compositing backward (aon_composite_grad.h) with dalpha_i / d|d| = (1 - alpha_i) sigma_i delta_i in the
 // place of dalpha_i / d raw_sigma_i.  fp64 on the forward's fp32 inputs; the same value in every lane.
 template <int NB>
 __device__ __forceinline__ double rg_norm_term(const RgReduceLevel& L, const int64_t ray, const int lane, const float dn, const int white_bkgd) {
@@ -129,9 +130,7 @@ __device__ __forceinline__ double rg_norm_term(const RgReduceLevel& L, const int
   const ActParams ap = L.ap;
   const int nblk = (S + 63) >> 6;
   const float* tv = L.t + ray * S;
-  const double gC0 = L.g_rgb[ray * 3], gC1 = L.g_rgb[ray * 3 + 1], gC2 = L.g_rgb[ray * 3 + 2];
-  const double gA = L.g_acc ? (double)L.g_acc[ray] : 0.0, gD = L.g_depth ? (double)L.g_depth[ray] : 0.0;
-  const double gw_const = gA - (white_bkgd ? (gC0 + gC1 + gC2) : 0.0);
+  const CompositeUpstream up(L.g_rgb, L.g_acc, L.g_depth, white_bkgd, ray);
   double tgw[NB], f[NB], kn[NB], wgw[NB];   // T_i gw_i;  1 - alpha_i + 1e-10;  d alpha_i / d |d|;  w_i gw_i
   double carry = 1.0;
 #pragma unroll
@@ -145,37 +144,15 @@ __device__ __forceinline__ double rg_norm_term(const RgReduceLevel& L, const int
         const int64_t g = ray * S + s;
         const float t = tv[s];
         const float delta = s == S - 1 ? 1e10f : __fsub_rn(tv[s + 1], t);
-        const double dist = (double)__fmul_rn(delta, dn);
         float4 r = reinterpret_cast<const float4*>(L.raw)[g];
         if (ap.noise) r.w = __fadd_rn(r.w, __fmul_rn(ap.noise[g], ap.noise_std));
-        double sg, c0, c1, c2;
-        if (ap.act == 1) {
-          sg = r.w > 0.f ? (double)r.w : 0.0;
-          c0 = rg_sigmoidd(r.x); c1 = rg_sigmoidd(r.y); c2 = rg_sigmoidd(r.z);
-        } else if (ap.act == 2) {
-          const float xs = __fadd_rn(r.w, ap.sigma_bias);
-          sg = xs > 20.0f ? (double)xs : log1p(exp((double)xs));
-          const double sc = ap.rgb_scale, sh = ap.rgb_shift;
-          c0 = rg_sigmoidd(r.x) * sc - sh; c1 = rg_sigmoidd(r.y) * sc - sh; c2 = rg_sigmoidd(r.z) * sc - sh;
-        } else {
-          sg = r.w; c0 = r.x; c1 = r.y; c2 = r.z;
-        }
-        const double ex = exp(-sg * dist);
-        alpha = 1.0 - ex;
-        f[b] = (1.0 - alpha) + 1e-10;
-        kn[b] = ex * sg * (double)delta;
-        gw = gC0 * c0 + gC1 * c1 + gC2 * c2 + gw_const + (double)t * gD;
+        CompositeSample m;
+        composite_sample(ap, r, __fmul_rn(delta, dn), m);
+        alpha = m.alpha; f[b] = m.f;
+        kn[b] = m.ex * m.sg * (double)delta;
+        gw = up.gw(m, t);
       }
-      double incl = f[b];
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const double o = __shfl_up(incl, off);
-        if (lane >= off) incl = incl * o;
-      }
-      double excl = __shfl_up(incl, 1);
-      if (lane == 0) excl = 1.0;
-      const double T = carry * excl;
-      carry = carry * __shfl(incl, 63);
+      const double T = wave_exclusive_product_f64(f[b], lane, carry);
       tgw[b] = T * gw;
       wgw[b] = in ? alpha * T * gw : 0.0;
     }
@@ -184,16 +161,7 @@ __device__ __forceinline__ double rg_norm_term(const RgReduceLevel& L, const int
 #pragma unroll
   for (int b = NB - 1; b >= 0; --b) {
     if (b < nblk) {
-      double incl = wgw[b];
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const double o = __shfl_down(incl, off);
-        if (lane + off < 64) incl = incl + o;
-      }
-      double excl = __shfl_down(incl, 1);
-      if (lane == 63) excl = 0.0;
-      const double sfx = excl + sfx_carry;
-      sfx_carry = sfx_carry + __shfl(incl, 0);
+      const double sfx = wave_exclusive_suffix_sum_f64(wgw[b], lane, sfx_carry);
       if (b * 64 + lane < S) part += (tgw[b] - sfx / f[b]) * kn[b];   // dL/dalpha_i * dalpha_i/d|d|
     }
   }
@@ -206,8 +174,7 @@ __global__ void __launch_bounds__(256) ray_grad_reduce_kernel(RgReduceArgs a) {
   const int64_t ray = (int64_t)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
   if (ray >= a.n_rays) return;
   const float d0 = a.rays_d[ray * 3], d1 = a.rays_d[ray * 3 + 1], d2 = a.rays_d[ray * 3 + 2];
-  // |d| as the forward takes it (fp32, helper.py:167)
-  const float dn = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+  const float dn = ray_norm_f32(a.rays_d, ray);
   const int c = lane & 31;
   const bool weighted = lane >= 32;
   double acc = 0.0, gn = 0.0;

@@ -7,8 +7,8 @@
 //                               row per object (in place) and the K + 1 segment starts;
 //   scene_pair_emit_kernel      one thread per ray again: row = block base + rank among the block's live rays of that object (ballot ranks),
 //                               so an object's rows ascend with the ray index; writes slot and the pair's ray, o', d', v', near, far.
-//   scene_composite_kernel      one wavefront per ray: the t of its live lists staged in LDS, every sample ranked by counting (own index +
-//                               a binary search in each other list: the lists are sorted already), 1 - alpha + 1e-10 placed in rank order,
+//   scene_composite_kernel      one wavefront per ray: the t of its live lists staged in LDS and every sample ranked by counting
+//                               (aon_scene_merge.h, shared with the backward), 1 - alpha + 1e-10 placed in rank order,
 //                               a multiplicative wave scan in rank order in blocks of 64 with a carry, then the sums in a fixed order.
 //
 // Arithmetic of the pairs, operation by operation: R^T x as ((R[0][a] x_0) + R[1][a] x_1) + R[2][a] x_2 with separately rounded operations,
@@ -16,7 +16,7 @@
 // clamp-and-live rule without the set-wide patching.
 #include "../../include/aon_hip_scene.h"
 #include "aon_capi_util.h"
-#include "aon_ray_core.h"
+#include "aon_scene_merge.h"
 
 using namespace aon::capi;
 
@@ -24,7 +24,6 @@ namespace aon {
 namespace {
 
 constexpr int kPairThreads = 256;
-constexpr int kMaxObj = AON_SCENE_MAX_OBJECTS;
 
 struct SceneObjects {   // by value in the kernel arguments (1152 B): no device copy to keep alive, nothing for the host to wait for
   aon_scene_object o[kMaxObj];
@@ -172,9 +171,8 @@ int64_t pair_count_bytes(int64_t n, int k) { return align_up((n > 0 ? pair_block
 // ---------------------------------------------------------------------------------------------
 // the merged composite
 // ---------------------------------------------------------------------------------------------
-// Per wave in LDS: a 256-byte head (the live lists' rows, objects, first and last t) and, per sample of the K * S the call admits, 14 bytes:
+// Per wave in LDS: the head of the live lists (aon_scene_merge.h) and, per sample of the K * S the call admits, 14 bytes:
 // t in list layout, 1 - alpha + 1e-10 -> T in RANK order, alpha and the rank (16 bits: K * S <= 4096) in list layout.
-constexpr int kHeadBytes = 256;
 constexpr int kSampleBytes = 14;
 constexpr int kLdsBudget = 64 * 1024;
 int64_t composite_wave_bytes(int K, int S) { return align_up(kHeadBytes + (int64_t)K * S * kSampleBytes, 16); }
@@ -204,21 +202,15 @@ __global__ __launch_bounds__(256) void scene_composite_kernel(SceneCompositeArgs
   if (ray >= a.n) return;   // wave-uniform; no block-level barrier below
   const int K = a.K, S = a.S, MS = K * S;
   char* base = scene_lds + (size_t)wv * a.wave_bytes;
-  int* lp = reinterpret_cast<int*>(base);        // row of live list j
-  int* lk = lp + kMaxObj;                         // its object
-  float* llo = reinterpret_cast<float*>(lk + kMaxObj);   // its first and last t
-  float* lhi = llo + kMaxObj;
+  const SceneLists h(base);
   float* tl = reinterpret_cast<float*>(base + kHeadBytes);
   float* fT = tl + MS;
   float* al = fT + MS;
   unsigned short* rk = reinterpret_cast<unsigned short*>(al + MS);
   const ActParams ap = a.ap;
 
-  int p = -1;
-  if (lane < K) p = a.slot[ray * K + lane];
-  const bool live = p >= 0 && p < a.pairs;   // (a row past `pairs` is nobody's: treated as dead, never dereferenced)
-  const uint64_t m = __builtin_amdgcn_ballot_w64(live);
-  const int L = __builtin_popcountll(m);
+  bool live;
+  const int L = scene_live_lists(h, a.slot, a.t_vals, ray, K, a.pairs, S, lane, live);
   if (a.obj_acc && lane < K && !live) a.obj_acc[ray * K + lane] = 0.f;
   if (L == 0) {
     if (lane == 0) {
@@ -229,47 +221,17 @@ __global__ __launch_bounds__(256) void scene_composite_kernel(SceneCompositeArgs
     }
     return;
   }
-  if (live) {
-    const int j = __builtin_popcountll(m & (lane == 0 ? 0ull : (~0ull >> (64 - lane))));
-    lp[j] = p;
-    lk[j] = lane;
-    llo[j] = a.t_vals[(int64_t)p * S];
-    lhi[j] = a.t_vals[(int64_t)p * S + S - 1];
-  }
-  wave_lds_sync();
-  for (int j = 0; j < L; ++j) {
-    const float* tv = a.t_vals + (int64_t)lp[j] * S;
-    for (int i = lane; i < S; i += 64) tl[j * S + i] = tv[i];
-  }
-  wave_lds_sync();
-  const float dn = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(a.dirs[ray * 3], a.dirs[ray * 3]), __fmul_rn(a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 1])),
-                                        __fmul_rn(a.dirs[ray * 3 + 2], a.dirs[ray * 3 + 2])));
+  scene_stage_t(h, tl, a.t_vals, L, S, lane);
+  const float dn = ray_norm_f32(a.dirs, ray);
   const int M = L * S;
-  // rank by counting: own index + in every other list the number of keys (t, object, i) below this one -- t <= mine in a list of a lower
-  // object, t < mine in a list of a higher one.  0 <= rank <= M - 1 whatever the t hold (each count is at most S).
   for (int j = 0; j < L; ++j) {
-    const int64_t row = (int64_t)lp[j] * S;
-    const int kj = lk[j];
+    const int64_t row = (int64_t)h.lp[j] * S;
     for (int i = lane; i < S; i += 64) {
       const float t = tl[j * S + i];
       const float dist = i < S - 1 ? __fmul_rn(__fsub_rn(tl[j * S + i + 1], t), dn) : 0.f;
       const float sg = scene_sigma(ap, a.raw[row + i].w);
       const float alpha = __fsub_rn(1.0f, expf(-__fmul_rn(sg, dist)));
-      int rank = i;
-      for (int b = 0; b < L; ++b) {
-        if (b == j) continue;
-        if (t < llo[b]) continue;                  // wholly behind this sample
-        if (t > lhi[b]) { rank += S; continue; }   // wholly in front of it
-        const bool le = lk[b] < kj;
-        const float* x = tl + b * S;
-        int lo = 0, hi = S;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          const float xm = x[mid];
-          if (le ? xm <= t : xm < t) lo = mid + 1; else hi = mid;
-        }
-        rank += lo;
-      }
+      const int rank = scene_rank(h, tl, t, i, j, L, S);
       fT[rank] = __fadd_rn(__fsub_rn(1.0f, alpha), 1e-10f);
       al[j * S + i] = alpha;
       rk[j * S + i] = (unsigned short)rank;
@@ -290,7 +252,7 @@ __global__ __launch_bounds__(256) void scene_composite_kernel(SceneCompositeArgs
   // the sums: per lane over (list, i) ascending, then one fixed tree over the lanes
   float s_r = 0.f, s_g = 0.f, s_b = 0.f, s_w = 0.f, s_d = 0.f;
   for (int j = 0; j < L; ++j) {
-    const int64_t row = (int64_t)lp[j] * S;
+    const int64_t row = (int64_t)h.lp[j] * S;
     float s_o = 0.f;
     for (int i = lane; i < S; i += 64) {
       const int e = j * S + i;
@@ -305,7 +267,7 @@ __global__ __launch_bounds__(256) void scene_composite_kernel(SceneCompositeArgs
       if (a.weights) a.weights[row + i] = w;
     }
     s_o = wave_sum(s_o);
-    if (a.obj_acc && lane == 0) a.obj_acc[ray * K + lk[j]] = s_o;
+    if (a.obj_acc && lane == 0) a.obj_acc[ray * K + h.lk[j]] = s_o;
   }
   s_r = wave_sum(s_r); s_g = wave_sum(s_g); s_b = wave_sum(s_b); s_w = wave_sum(s_w); s_d = wave_sum(s_d);
   if (lane == 0) {

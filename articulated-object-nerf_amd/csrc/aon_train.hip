@@ -16,6 +16,7 @@
 #include <atomic>
 #define AON_WGRAD_KERNELS
 #define AON_CHAIN_STAGE_MASKED   // see BwdSideOf (aon_mlp_core.h)
+#include "aon_composite_grad.h"
 #include "aon_pass.h"
 #include "aon_wgrad.h"
 
@@ -36,20 +37,9 @@ struct CompositeBwdArgs {
   float* d_raw;         // (n*S,4) dL/d raw
 };
 
-// Round 4: the whole backward of the compositing is evaluated in fp64 on the fp32 inputs and rounded to fp32 ONCE per output.
-// dL/dalpha_i = T_i gw_i - Sfx_i / f_i is a difference of nearly equal terms, and the density-head bias gradient is the plain sum of
-// dL/d raw_sigma over every sample of a level -- on a field where that sum cancels to 1e-4 of its terms (constructor-fuzz seed 112:
-// x6,368) the fp32 form's correlated rounding along each ray (both scans feed every sample in front of them) left the bias 3e-3 from
-// the fp64 truth where torch's fp32 autograd happened to land at 9e-5 (tests/diag/diag_density_bias.py: per-sample errors 1.2x
-// torch's, their per-ray sums 3-5x).  The kernel handles 20 B per sample and runs ~15 us per 4096-ray step: fp64 costs nothing
-// visible, and every d_raw value is now the correctly rounded derivative of the reference's formula at the forward's fp32 inputs.
-__device__ __forceinline__ double sigmoidd_(double x) { return 1.0 / (1.0 + exp(-x)); }
-
-__device__ __forceinline__ double shfl_up_d(double v, int off) { return __shfl_up(v, off); }
-__device__ __forceinline__ double shfl_down_d(double v, int off) { return __shfl_down(v, off); }
-
 // NB: blocks of 64 samples held in registers -- 4 for the reference geometry (S <= 256), 8 for anything up to S = 512 (the training
 // entry points stop at 512 samples per ray).  Per block and lane four doubles and three floats survive between the two scans.
+// The function and its fp64 arithmetic: aon_composite_grad.h.
 template <int NB>
 __global__ void __launch_bounds__(256) composite_bwd_kernel(CompositeBwdArgs a) {
   const int lane = threadIdx.x & 63;
@@ -59,14 +49,8 @@ __global__ void __launch_bounds__(256) composite_bwd_kernel(CompositeBwdArgs a) 
   const ActParams ap = a.ap;
   const int nblk = (S + 63) >> 6;  // <= NB
   const float* tv = a.t_vals + ray * S;
-  // ||d|| as the forward takes it (fp32, helper.py:167): the interval lengths are INPUTS of the function being differentiated
-  const float dn = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(a.dirs[ray * 3], a.dirs[ray * 3]),
-                                                  __fmul_rn(a.dirs[ray * 3 + 1], a.dirs[ray * 3 + 1])),
-                                        __fmul_rn(a.dirs[ray * 3 + 2], a.dirs[ray * 3 + 2])));
-  const double gC0 = a.g_rgb[ray * 3], gC1 = a.g_rgb[ray * 3 + 1], gC2 = a.g_rgb[ray * 3 + 2];
-  const double gA = a.g_acc ? (double)a.g_acc[ray] : 0.0, gD = a.g_depth ? (double)a.g_depth[ray] : 0.0;
-  // dL/dw_i = gC.c_i - [white] sum(gC) + g_acc + t_i g_depth     (comp_rgb += 1 - acc, helper.py:187-188)
-  const double gw_const = gA - (a.white_bkgd ? (gC0 + gC1 + gC2) : 0.0);
+  const float dn = ray_norm_f32(a.dirs, ray);
+  const CompositeUpstream up(a.g_rgb, a.g_acc, a.g_depth, a.white_bkgd, ray);
 
   double tgw[NB], f[NB], kf[NB], wgw[NB];   // T_i gw_i;  1 - alpha_i + 1e-10;  d alpha_i / d raw_sigma_i;  w_i gw_i
   float o0[NB], o1[NB], o2[NB];             // dL/d raw rgb, finished in the first sweep
@@ -81,65 +65,28 @@ __global__ void __launch_bounds__(256) composite_bwd_kernel(CompositeBwdArgs a) 
       if (in) {
         const int64_t g = ray * S + s;
         const float t = tv[s];
-        const double dist = (double)__fmul_rn(s == S - 1 ? 1e10f : __fsub_rn(tv[s + 1], t), dn);
+        const float dist = __fmul_rn(s == S - 1 ? 1e10f : __fsub_rn(tv[s + 1], t), dn);
         float4 r = reinterpret_cast<const float4*>(a.raw)[g];
         if (ap.noise) r.w = __fadd_rn(r.w, __fmul_rn(ap.noise[g], ap.noise_std));   // model.py:183-184 (d/d raw_sigma = 1)
-        double sg, dsg, c0, c1, c2;
-        if (ap.act == 1) {
-          sg = r.w > 0.f ? (double)r.w : 0.0; dsg = r.w > 0.f ? 1.0 : 0.0;
-          c0 = sigmoidd_(r.x); c1 = sigmoidd_(r.y); c2 = sigmoidd_(r.z);
-          d0 = c0 * (1.0 - c0); d1 = c1 * (1.0 - c1); d2 = c2 * (1.0 - c2);
-        } else if (ap.act == 2) {
-          const float xs = __fadd_rn(r.w, ap.sigma_bias);   // (an fp32 add in the forward: part of the function)
-          sg = xs > 20.0f ? (double)xs : log1p(exp((double)xs)); dsg = xs > 20.0f ? 1.0 : sigmoidd_(xs);   // torch Softplus, threshold 20
-          const double s0 = sigmoidd_(r.x), s1 = sigmoidd_(r.y), s2 = sigmoidd_(r.z);
-          const double sc = ap.rgb_scale, sh = ap.rgb_shift;
-          c0 = s0 * sc - sh; c1 = s1 * sc - sh; c2 = s2 * sc - sh;
-          d0 = sc * s0 * (1.0 - s0); d1 = sc * s1 * (1.0 - s1); d2 = sc * s2 * (1.0 - s2);
-        } else {
-          sg = r.w; dsg = 1.0; c0 = r.x; c1 = r.y; c2 = r.z; d0 = d1 = d2 = 1.0;
-        }
-        const double ex = exp(-sg * dist);
-        alpha = 1.0 - ex;
-        f[b] = (1.0 - alpha) + 1e-10;
-        kf[b] = dist * ex * dsg;   // d alpha / d sigma = dist exp(-sigma dist), times the density activation's derivative
-        gw = gC0 * c0 + gC1 * c1 + gC2 * c2 + gw_const + (double)t * gD;
+        CompositeSample m;
+        composite_sample(ap, r, dist, m);
+        alpha = m.alpha; f[b] = m.f; kf[b] = m.kf; d0 = m.d0; d1 = m.d1; d2 = m.d2;
+        gw = up.gw(m, t);
       }
-      // forward transmittance T_i = prod_{j<i} f_j
-      double incl = f[b];
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const double o = shfl_up_d(incl, off);
-        if (lane >= off) incl = incl * o;
-      }
-      double excl = shfl_up_d(incl, 1);
-      if (lane == 0) excl = 1.0;
-      const double T = carry * excl;
-      carry = carry * __shfl(incl, 63);
+      const double T = wave_exclusive_product_f64(f[b], lane, carry);   // T_i = prod_{j<i} f_j
       const double w = alpha * T;
       tgw[b] = T * gw;
       wgw[b] = in ? w * gw : 0.0;
-      o0[b] = (float)(w * gC0 * d0); o1[b] = (float)(w * gC1 * d1); o2[b] = (float)(w * gC2 * d2);
+      o0[b] = (float)(w * up.gC0 * d0); o1[b] = (float)(w * up.gC1 * d1); o2[b] = (float)(w * up.gC2 * d2);
     }
   }
-  // suffix sums  Sfx_i = sum_{k>i} w_k gw_k, scanned from the far end
   double sfx_carry = 0.0;
 #pragma unroll
   for (int b = NB - 1; b >= 0; --b) {
     if (b < nblk) {
-      double incl = wgw[b];
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const double o = shfl_down_d(incl, off);
-        if (lane + off < 64) incl = incl + o;
-      }
-      double excl = shfl_down_d(incl, 1);
-      if (lane == 63) excl = 0.0;
-      const double sfx = excl + sfx_carry;
-      sfx_carry = sfx_carry + __shfl(incl, 0);
+      const double sfx = wave_exclusive_suffix_sum_f64(wgw[b], lane, sfx_carry);   // Sfx_i = sum_{k>i} w_k gw_k
       const int s = b * 64 + lane;
       if (s < S) {
-        // dL/dalpha_i = T_i gw_i - Sfx_i / (1 - alpha_i + 1e-10)
         const double dalpha = tgw[b] - sfx / f[b];
         float4 o;
         o.x = o0[b]; o.y = o1[b]; o.z = o2[b];

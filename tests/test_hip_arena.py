@@ -451,3 +451,24 @@ def test_gradient_bits_are_pinned(dev):
     assert set(got) == set(want["hashes"])
     moved = [k for k in got if got[k] != want["hashes"][k]]
     assert not moved, f"{len(moved)} of {len(got)} tensors changed bits: {moved[:6]}"
+
+
+def test_composite_bits_are_pinned(dev):
+    """The outputs of every kernel that differentiates or orders the composite (csrc/aon_composite_grad.h, csrc/aon_scene_merge.h):
+    aon_composite_bwd, aon_scene_composite, aon_scene_composite_bwd and the frozen networks' backwards on the seeded inputs of
+    `tools/grad_hash.py --composite` (block edges 64 / 65 and 256 / 257, K * S = 4096, ties, sentinel records, dead slot entries), held to
+    tests/golden/g30_composite_hashes.json.  The file was written with the library of the commit it names, BEFORE the kernels shared their
+    code: a caller that uses a shared piece differently shows here, and the file is not rewritten from a build that fails it."""
+    import json
+    import os
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import grad_hash
+
+    want = json.load(open(os.path.join(root, "tests", "golden", "g30_composite_hashes.json")))["hashes"]
+    got = dict(grad_hash.composite_hashes())
+    assert set(got) == set(want)
+    moved = [k for k in got if got[k] != want[k]]
+    assert not moved, f"{len(moved)} of {len(got)} outputs changed bits: {moved[:6]}"

@@ -2,7 +2,13 @@
 changes that must not move a bit -- run it with two builds of the library (AON_HIP_LIB=... selects an alternative build) and diff.
     python tools/grad_hash.py > a.txt;  AON_HIP_LIB=articulated-object-nerf_amd/libaon_hip_prev.so python tools/grad_hash.py > b.txt;  diff a.txt b.txt
 --frozen: the outputs of the frozen networks' backwards instead (aon_art_render_bwd_latents, aon_art_render_bwd_inputs with and without the
-latents wanted, aon_render_bwd_inputs) on 37 rays: one and two levels, the default sample counts and (39, 32), both stream forms."""
+latents wanted, aon_render_bwd_inputs) on 37 rays: one and two levels, the default sample counts and (39, 32), both stream forms, and two
+levels at (64, 224): a fine level of 289 samples, the 8-block form of the reduce kernel.
+--composite: every kernel that differentiates or orders the composite (csrc/aon_composite_grad.h, csrc/aon_scene_merge.h) on seeded inputs made
+here -- aon_composite_bwd, aon_scene_composite and aon_scene_composite_bwd at the block edges (64 / 65, 256 / 257 samples, K * S = 4096), all
+three activations, both backgrounds, the optional gradients given and null, twins tied in t, sentinel records, dead slot entries -- and
+the --frozen set.  `--composite --write COMMIT` writes tests/golden/g30_composite_hashes.json
+(tests/test_hip_arena.py::test_composite_bits_are_pinned); COMMIT names the commit the library in use was built from."""
 import hashlib
 import os
 import sys
@@ -25,7 +31,32 @@ def hashes(n=4096):
     return out
 
 
+def composite_hashes():
+    """-> ordered list of (label, 16-hex-digit hash): the --composite set."""
+    out = []
+    emit = lambda *a: out.append((" ".join(a[:-1]), a[-1]))   # noqa: E731
+    _run_composite(emit)
+    _run_frozen(emit)
+    return out
+
+
 def main():
+    if "--composite" in sys.argv:
+        got = composite_hashes()
+        if "--write" in sys.argv:
+            import json
+
+            commit = sys.argv[sys.argv.index("--write") + 1]
+            path = os.path.join(ROOT, "tests", "golden", "g30_composite_hashes.json")
+            json.dump({"note": "sha256[:16] of the outputs of aon_composite_bwd, aon_scene_composite, aon_scene_composite_bwd and the frozen networks' "
+                               "backwards on seeded inputs on gfx950, written by `AON_HIP_LIB=<library built from library_commit> python "
+                               "tools/grad_hash.py --composite --write <library_commit>`", "library_commit": commit, "hashes": dict(got)},
+                      open(path, "w"), indent=0)
+            print("wrote", path, len(got))
+            return
+        for label, digest in got:
+            print(label, digest)
+        return
     if "--write" in sys.argv:     # tests/golden/g24_gradient_hashes.json (tests/test_hip_arena.py::test_gradient_bits_are_pinned)
         import json
 
@@ -94,7 +125,9 @@ def _run_frozen(emit, n=37):
                       "bwd": [ops.pack_art_mlp_bwd(p) for p in nets[True]]}
             van_pk = {"fwd": [ops.pack_vanilla_mlp(p) for p in nets[False]], "bwd": [ops.pack_vanilla_mlp_bwd(p) for p in nets[False]]}
             for k in (1, 2):
-                for counts in ({}, dict(num_coarse_samples=39, num_fine_samples=32)):
+                for counts in ({}, dict(num_coarse_samples=39, num_fine_samples=32), dict(num_fine_samples=224)):
+                    if k == 1 and counts.get("num_fine_samples") == 224:
+                        continue      # (the long fine level is the case)
                     nc, nf = counts.get("num_coarse_samples", 64), counts.get("num_fine_samples", 128)
                     t_rand, u = syn.seeded_uniform(140, n, nc + 1).to(dev), (syn.seeded_uniform(141, n, nf).to(dev) if k == 2 else None)
                     tag = f"{'folded' if fold else 'literal'} L{k} {nc}+{nf}"
@@ -124,6 +157,77 @@ def _run_frozen(emit, n=37):
                         emit("van", "inputs", tag, name, h(g))
     finally:
         ops.set_bottleneck_fold(before)
+
+
+def _unit(seed, *shape):
+    import aon_amd.synthetic as syn
+
+    return syn.seeded_uniform(seed, *shape)
+
+
+def _raw(seed, act, *shape):
+    """records (…, 4) in [-2, 2); a raw density that is used as it is (act 0) is not negative"""
+    raw = 4.0 * _unit(seed, *shape, 4) - 2.0
+    if act == 0:
+        raw[..., 3] = raw[..., 3].abs()
+    return raw
+
+
+def _scene_case(kind, n, K, S, seed):
+    """-> (slot (n, K), P, t (P, S) ascending in [2, 6], rays_d): about a third of the pairs dead, ray 0 without a pair, ray 1 with all K,
+    rows object-major and ascending with the ray as aon_scene_pairs lays them out"""
+    live = _unit(seed, n, K) < 0.67
+    live[0], live[1] = False, True
+    if kind == "twins":
+        live[:] = True
+    flat = live.T.reshape(-1)
+    rows = torch.cumsum(flat.to(torch.int64), 0) - 1
+    slot = torch.where(flat, rows, torch.full_like(rows, -1)).reshape(K, n).T.contiguous().to(torch.int32)
+    P = int(flat.sum())
+    t = 2.0 + 4.0 * torch.sort(_unit(seed + 1, P, S), dim=1).values
+    if kind == "twins":         # object 1's lists are object 0's, t for t
+        t[n:] = t[:n]
+    if kind == "dead_slot":     # entries that name no row: -1 already; a row past the pairs is dead too (ray 0 still has no pair)
+        slot[0, 0], slot[0, 1] = P + 5, P
+    return slot, P, t.contiguous(), (_unit(seed + 2, n, 3) - 0.5).contiguous()
+
+
+def _run_composite(emit):
+    from aon_amd import ops
+
+    dev = torch.device("cuda:0")
+    for n, S in ((5, 2), (5, 64), (5, 65), (37, 193), (3, 257), (3, 512)):
+        t = (2.0 + 4.0 * torch.sort(_unit(200 + S, n, S), dim=1).values).to(dev)
+        dirs = (_unit(201 + S, n, 3) - 0.5).to(dev)
+        g_rgb, g_acc, g_depth = ((_unit(202 + S + i, *sh) - 0.5).to(dev) for i, sh in enumerate(((n, 3), (n,), (n,))))
+        for act in (0, 1, 2):
+            raw = _raw(210 + S + act, act, n * S).to(dev)
+            for white in (True, False):
+                for given in (True, False):
+                    d_raw = ops.composite_bwd(raw, t, dirs, g_rgb, g_acc if given else None, g_depth if given else None, white, act, n * S)
+                    emit("composite_bwd", f"n{n} S{S} act{act}", "white" if white else "black", "all" if given else "rgb_only", "d_raw", h(d_raw))
+    sizes = [("plain", n, K, S) for n, K, S in ((5, 2, 2), (5, 2, 3), (37, 3, 65), (9, 5, 13), (20, 16, 193), (7, 16, 256))]
+    for kind, n, K, S in sizes + [("twins", 9, 2, 17), ("sentinel", 9, 5, 13), ("dead_slot", 37, 3, 65)]:
+        slot, P, t, dirs = _scene_case(kind, n, K, S, 300 + 7 * K + S)
+        pairs = types.SimpleNamespace(n=n, K=K, P=P, slot=slot.to(dev))
+        t, dirs = t.to(dev), dirs.to(dev)
+        g = [(_unit(310 + K + S + i, *sh) - 0.5).to(dev) for i, sh in enumerate(((n, 3), (n,), (n,), (n, K)))]
+        for act in (0, 1, 2):
+            raw = _raw(320 + K + S + act, act, P, S)
+            if kind == "sentinel":
+                mask = _unit(330 + act, P, S) < 0.3
+                mask[1] = True      # a whole list
+                raw[mask] = torch.tensor([0.0, 0.0, 0.0, float("-inf")])
+            raw = raw.to(dev)
+            for white in (True, False):
+                tag = (kind, f"n{n} K{K} S{S} act{act}", "white" if white else "black")
+                outs = ops.scene_composite(raw, t, pairs, dirs, white, act=act)
+                for name, x in zip(("rgb", "acc", "depth", "obj_acc", "weights"), outs):
+                    emit("scene_composite", *tag, name, h(x))
+                for given in (True, False):
+                    extra = dict(g_acc=g[1], g_depth=g[2], g_obj_acc=g[3]) if given else {}
+                    d_raw = ops.scene_composite_bwd(raw, t, pairs, dirs, g[0], white_bkgd=white, act=act, **extra)
+                    emit("scene_composite_bwd", *tag, "all" if given else "rgb_only", "d_raw", h(d_raw))
 
 
 if __name__ == "__main__":

@@ -137,6 +137,10 @@ _SIGS = {
     "aon_set_bwd_early_heads": (_i, [_i]),
     "aon_set_view_bias": (_i, [_i]),
     "aon_get_view_bias": (_i, []),
+    "aon_set_deferred_view": (_i, [_i]),
+    "aon_get_deferred_view": (_i, []),
+    "aon_render_deferred_workspace_bytes": (_l, [_l, _p]),
+    "aon_test_set_deferred_slab": (_i, [_i]),
     "aon_view_bias": (_i, [_p, _p, _l, _p, _p]),
     "aon_set_bwd_overlap": (_i, [_i]),
     "aon_set_fwd_overlap": (_i, [_i]),

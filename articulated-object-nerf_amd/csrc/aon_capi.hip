@@ -31,6 +31,10 @@ std::atomic<int> g_fuse_coarse{1};
 // Round 5: whole-path calls of the vanilla network in its folded form hand the view layer b' + W_v0[:, 256:] ve as a per-ray bias
 // (launch_view_bias) instead of running the view-encoding chunk per sample -- same bits (aon_common.h).  0: the chunk form.
 std::atomic<int> g_view_bias{1};
+// Whole-path dense renders of the vanilla network (folded form, per-ray view bias): the view branch runs only on the samples with raw
+// sigma > 0, behind a compaction -- same bits: the others' colours are multiplied by a weight of exactly 0.
+// 0: the single kernel.
+std::atomic<int> g_deferred_view{1};
 
 const char* make_geo(const aon_render_opts* o, Geo& g, bool general_engine) {
   aon_render_opts d;
@@ -697,6 +701,13 @@ int aon_set_view_bias(int on) {
 }
 
 int aon_get_view_bias(void) { return g_view_bias.load(std::memory_order_relaxed); }
+
+int aon_set_deferred_view(int on) {
+  g_deferred_view.store(on ? 1 : 0, std::memory_order_relaxed);
+  return AON_OK;
+}
+
+int aon_get_deferred_view(void) { return g_deferred_view.load(std::memory_order_relaxed); }
 
 // ---- articulated network (model_autodecoder.py) ----
 int64_t aon_art_packed_bytes(void) { return aon::art_stream_bytes(); }

@@ -15,10 +15,25 @@ struct Ws {
   float* vbias;   // n*128: the level's per-ray view bias (vanilla, folded form; launch_view_bias) -- both levels in turn
   char* occ;      // [occupancy] the level's sample list, tile counts and list length (aon::occ_list_bytes of n*Sf) -- both levels in turn
   char* stop;     // [early termination] the level's per-ray tau and stop index (aon::occ_stop_state_bytes of n) -- both levels in turn
+  // [deferred view branch, DESIGN.md section 4.19] of a slab of `slab` rays, both levels in turn: the samples' marks, their live list
+  // (aon::occ_list_bytes of slab*Sf) and the live samples' layer-7 rows (1 KiB per sample)
+  int64_t slab; uint8_t* live_mark; char* live_list; float* live_rows;
   int64_t bytes;
 };
 
-Ws carve(char* base, int64_t n, const Geo& g, bool occ = false, bool stop = false) {
+// deferred view branch: what a slab of s rays adds to the workspace, and the largest slab (the rows stay at or under 8 GiB with every sample live)
+int64_t defer_bytes(int64_t s, const Geo& g) {
+  return s <= 0 ? 0 : align_up(s * g.Sf, 256) + aon::occ_list_bytes(s * g.Sf) + align_up(s * g.Sf * 1024, 256);
+}
+std::atomic<int> g_defer_slab_test{0};   // aon_test_set_deferred_slab
+constexpr int64_t kDeferSlabRays = 32768, kDeferMinSlabRays = 4096;
+int64_t defer_slab_cap(const Geo& g) {
+  if (const int t = g_defer_slab_test.load(std::memory_order_relaxed); t > 0) return t;
+  const int64_t by_rows = ((int64_t)8 << 30) / ((int64_t)g.Sf * 1024);
+  return by_rows < kDeferSlabRays ? (by_rows < 1 ? 1 : by_rows) : kDeferSlabRays;
+}
+
+Ws carve(char* base, int64_t n, const Geo& g, bool occ = false, bool stop = false, int64_t slab = 0) {
   Ws w{};
   int64_t off = 0;
   w.t_c = reinterpret_cast<float*>(base + off); off += align_up(n * g.Sc * 4, 256);
@@ -34,6 +49,12 @@ Ws carve(char* base, int64_t n, const Geo& g, bool occ = false, bool stop = fals
   }
   if (occ) { w.occ = base + off; off += aon::occ_list_bytes(n * g.Sf); }
   if (stop) { w.stop = base + off; off += aon::occ_stop_state_bytes(n); }
+  if (slab > 0) {   // behind everything else: the plain layout does not move
+    w.slab = slab;
+    w.live_mark = reinterpret_cast<uint8_t*>(base + off); off += align_up(slab * g.Sf, 256);
+    w.live_list = base + off; off += aon::occ_list_bytes(slab * g.Sf);
+    w.live_rows = reinterpret_cast<float*>(base + off); off += align_up(slab * g.Sf * 1024, 256);
+  }
   w.bytes = off;
   return w;
 }
@@ -52,6 +73,22 @@ static int64_t workspace_query(int64_t n_rays, const aon_render_opts* opts, bool
 }
 int64_t aon_render_workspace_bytes_ex(int64_t n_rays, const aon_render_opts* opts) { return workspace_query(n_rays, opts, false, false); }
 int64_t aon_render_workspace_bytes(int64_t n_rays) { return aon_render_workspace_bytes_ex(n_rays, nullptr); }
+// ... plus what the deferred view branch of the vanilla network takes (a slab's marks, list and rows): with less, aon_render_fwd* runs the
+// single-kernel form
+int64_t aon_render_deferred_workspace_bytes(int64_t n_rays, const aon_render_opts* opts) {
+  const int64_t plain = workspace_query(n_rays, opts, false, false);
+  if (plain < 0) return plain;
+  Geo g;
+  (void)make_geo(opts, g);
+  if (g.other_degrees) return plain;
+  if (n_rays < 1) n_rays = 1;
+  const int64_t cap = defer_slab_cap(g);
+  return plain + defer_bytes(n_rays < cap ? n_rays : cap, g);
+}
+int aon_test_set_deferred_slab(int rays) {
+  g_defer_slab_test.store(rays > 0 ? rays : 0, std::memory_order_relaxed);
+  return AON_OK;
+}
 
 // Whole-path orchestration shared by the vanilla and the articulated network (NeRF.forward, model.py:147-199;
 // NeRF_AE_Art.forward, model_autodecoder.py:278-337): only the MLP launch and the output activation differ.
@@ -144,6 +181,27 @@ static hipError_t launch_net(const NetRef& net, const float* o, const float* d, 
   MlpTimer timer(stream, n * S);
   if (net.articulated)
     return aon::launch_art_mlp_fwd(static_cast<const char*>(net.packed), net.small, o, d, v, t, n, S, raw, stream, vbias);
+  // [deferred view branch] per slab of rays: the trunk, the compaction of its marks (one "row" per sample, the mark as its ray_live byte,
+  // no grid: the list holds the slab's live sample indices) and the view branch of the listed samples; all stream-ordered.  Density noise
+  // can lift a sample with raw sigma <= 0 above zero: such a level keeps the single kernel.
+  if (w && w->slab > 0 && vbias && !(g->noise[level] && g->noise_std > 0.f)) {
+    const char* packed = static_cast<const char*>(net.packed);
+    for (int64_t r = 0; r < n; r += w->slab) {
+      const int64_t ns = n - r < w->slab ? n - r : w->slab;
+      float* raw_s = raw + r * S * 4;
+      if (hipError_t e = aon::launch_mlp_trunk_defer(packed, o + r * 3, d + r * 3, v + r * 3, t + r * S, ns, S, raw_s, w->live_mark, w->live_rows, stream);
+          e != hipSuccess) return e;
+      const int64_t starts[2] = {0, ns * S};
+      const aon::OccGrid no_grid{};
+      const aon::OccCompact c{&no_grid, starts, 1, 1, 0, 1, nullptr, nullptr, nullptr, w->live_mark, nullptr};
+      const int* live_idx = nullptr;
+      const int64_t* live_count = nullptr;
+      if (hipError_t e = aon::launch_occ_compact(c, nullptr, w->live_list, (ns * S + 1023) / 1024, nullptr, &live_idx, &live_count, stream); e != hipSuccess) return e;
+      if (hipError_t e = aon::launch_view_deferred(packed, w->live_rows, live_idx, live_count, ns * S, vbias + r * aon::kCondWidth, S, raw_s, stream);
+          e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
   return aon::launch_mlp_fwd(static_cast<const char*>(net.packed), o, d, v, t, n, S, raw, stream, vbias);
 }
 
@@ -177,7 +235,20 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
                                                 : with_occ ? "render: workspace smaller than aon_render_occ_workspace_bytes(1)"
                                                          : "render: workspace smaller than aon_render_workspace_bytes(1)");
   }
-  const Ws w = carve(static_cast<char*>(c.workspace), chunk, g, with_occ, with_stop);
+  // [deferred view branch] the dense renders of the vanilla network on the fused encodings, when the switch is on and the workspace holds a
+  // slab's marks, list and rows behind the plain layout (aon_render_deferred_workspace_bytes): the largest slab that fits, up to the cap
+  int64_t slab = 0;
+  if (!art && !with_occ && !g.other_degrees && g_deferred_view.load(std::memory_order_relaxed) != 0) {
+    const int64_t left = c.workspace_bytes - carve(nullptr, chunk, g).bytes;
+    int64_t s = defer_slab_cap(g) < chunk ? defer_slab_cap(g) : chunk;
+    if (defer_bytes(s, g) > left) {
+      s = left / ((int64_t)g.Sf * 1030);
+      while (s > 0 && defer_bytes(s, g) > left) --s;
+    }
+    const bool hook = g_defer_slab_test.load(std::memory_order_relaxed) > 0;
+    if (s > 0 && (hook || s >= kDeferMinSlabRays || s >= chunk)) slab = s;
+  }
+  const Ws w = carve(static_cast<char*>(c.workspace), chunk, g, with_occ, with_stop, slab);
   if (with_occ && occ->tally) {
     if (int rc = check(hipMemsetAsync(occ->tally, 0, 2 * sizeof(int64_t), stream), who); rc != AON_OK) return rc;
   }

@@ -35,6 +35,7 @@ inline bool forms_differ(const void* a, const void* b) {
 // process-wide switches read by more than one file; every call reads them ONCE
 extern std::atomic<int> g_fuse_coarse;   // aon_set_coarse_fusion
 extern std::atomic<int> g_view_bias;     // aon_set_view_bias
+extern std::atomic<int> g_deferred_view;   // aon_set_deferred_view
 
 // Optional live timing of the path's kernels with HIP events on the LAUNCH stream (torch.cuda.Event would only see torch's
 // current stream), by kernel class; bench.py turns the totals into roofline figures.  Off unless aon_profile_begin() was

@@ -14,6 +14,11 @@ hipError_t launch_pack_vanilla(const float* const* params, float* packed, hipStr
 void vanilla_fold_jobs_fwd(const float* const* params, float* packed, int view_levels, FoldGemm jobs[2]);
 hipError_t launch_mlp_fwd(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs,
                           const float* t_vals, int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias = nullptr);
+// the deferred view branch: the trunk of launch_mlp_fwd's per-ray-bias form, and the view layer + rgb head of the listed samples
+hipError_t launch_mlp_trunk_defer(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_vals,
+                                  int64_t n_rays, int S, float* raw, uint8_t* live_mark, float* live_rows, hipStream_t stream);
+hipError_t launch_view_deferred(const char* packed, const float* live_rows, const int* idx, const int64_t* count, int64_t max_listed,
+                                const float* view_bias, int S, float* raw, hipStream_t stream);
 hipError_t launch_view_bias(const char* packed, const float* viewdirs, int64_t n_rays, float* out, hipStream_t stream);
 hipError_t launch_view_bias_raw(const float* chunk, const float* bias_vec, const float* viewdirs, int64_t n_rays, float* out, hipStream_t stream);
 hipError_t launch_mlp_fwd_enc(const char* packed, const float* samples_enc, const float* viewdirs_enc, int64_t n_rays,

@@ -45,6 +45,15 @@ struct VanillaFoldVbNet {
   static constexpr int skip_before(int c) { return c == kChFView ? kSmallChunkBytes : 0; }
 };
 
+// (density grid, deferred-view trunk) The stream truncated after layer 7: chunks 0 .. 59, which the literal and the folded forms share (aon_common.h).  The prefetch of the
+// next pass's first pair wraps at chunk 58 here (first_wrapping_chunk), not at the end of the view branch.
+struct VanillaTrunkNet {
+  static constexpr int kSlotBytes = kPairSlotBytes;
+  static constexpr bool kPair = true;
+  static constexpr int kNumChunks = kChBott;
+  static constexpr int chunk_bytes(int) { return kBigChunkBytes; }
+};
+
 // ---------------------------------------------------------------------------------------------
 // weight packing
 // ---------------------------------------------------------------------------------------------
@@ -133,10 +142,12 @@ struct MlpSeg {
   union {
     float* planes;             // [TRAIN] kPlRows x Np activation planes, step-major (aon_mlp_core.h)
     const int* gather_idx;     // [GATHER] ascending sample indices of the segment (< total)
+    float* live_rows;          // [DEFER] (total, 256): the post-ReLU layer-7 output of every live sample, one 1 KiB row at the sample's index
   };
   union {
     u32x4* masks;              // [TRAIN] kMaskLayers x (Np*2) ReLU bit masks
     const int64_t* gather_count;   // [GATHER] number of entries of gather_idx (device)
+    uint8_t* live_mark;        // [DEFER] (total,): 1 where raw sigma > 0, else 0 (the compaction's ray_live bytes, one "row" per sample)
   };
   int64_t Np;                // npass * 128
   const float* view_bias;    // [VB] (n_rays,128): b' + W_v0[:, 256:] ve of the ray (view_bias_kernel)
@@ -164,11 +175,17 @@ struct VanillaTrunk {   // trunk_fwd's view of the vanilla stream, small block, 
 // chunk of layer 7 runs, instead of from b' followed by the view-encoding chunk -- same bits (aon_common.h), 56 MFMAs, 12 sines and a
 // 16 KiB chunk fewer per pass; the inference kernel no longer carries the 16 registers of the view encoding through the trunk.
 // GATHER (inference on the in-kernel encodings only): the samples of a pass come from an occupancy list (aon_mlp_core.h).
-template <bool ENC_IN_KERNEL, bool TRAIN, bool FOLD, bool VB = false, bool GATHER = false>
+// DEFER (the VB inference form only): the TRUNK of that form.  The kernel ends behind layer 7 and the density head
+// -- the stream is the buffer's chunks 0 .. 59 (VanillaTrunkNet), no view-bias loads, no view layer, no rgb head -- and writes the record
+// (+0, +0, +0, raw sigma), the sample's mark (raw sigma > 0; NaN is not) and, for a marked sample only, its 256 post-ReLU layer-7 values
+// as a 1 KiB row in feature order: a quad of accumulator registers is four consecutive features, so the row goes out in 32 16-byte
+// stores straight from the registers.  view_kernel below finishes the marked samples from their rows.
+template <bool ENC_IN_KERNEL, bool TRAIN, bool FOLD, bool VB = false, bool GATHER = false, bool DEFER = false>
 __global__ void __launch_bounds__(256) mlp_fwd_kernel(MlpArgs args) {
   static_assert(FOLD || !VB, "the per-ray view bias belongs to the folded form");
   static_assert(!GATHER || (ENC_IN_KERNEL && !TRAIN), "the occupancy list serves the inference kernel on in-kernel encodings");
-  using Net = std::conditional_t<VB, VanillaFoldVbNet, std::conditional_t<FOLD, VanillaFoldNet, VanillaNet>>;
+  static_assert(!DEFER || (ENC_IN_KERNEL && !TRAIN && VB && !GATHER), "the deferred view branch serves the dense per-ray-bias inference form");
+  using Net = std::conditional_t<DEFER, VanillaTrunkNet, std::conditional_t<VB, VanillaFoldVbNet, std::conditional_t<FOLD, VanillaFoldNet, VanillaNet>>>;
   // <false, true>: training on caller-encoded inputs (other encoding degrees in the padded 63 / 27-slot layout): where the
   // in-kernel form re-encodes from x[] / vd[], this one re-reads the encodings.
   const int tid = threadIdx.x;
@@ -228,7 +245,7 @@ __global__ void __launch_bounds__(256) mlp_fwd_kernel(MlpArgs args) {
       }
     };
     auto l7_side = [&](auto plain) {
-      if constexpr (VB) {
+      if constexpr (VB && !DEFER) {
         asm volatile("" : "+v"(ray32));
         return view_bias_side(plain, sg.view_bias + (int64_t)ray32 * kCondWidth + 4 * h, Z);
       } else {
@@ -236,48 +253,72 @@ __global__ void __launch_bounds__(256) mlp_fwd_kernel(MlpArgs args) {
       }
     };
     const float sigma = trunk_fwd<Net, VanillaTrunk>(p, E, X, Y, sm, h, taps, reread_enc, l7_side);
-    constexpr int kChV = FOLD ? kChFView : kChView;
-    auto reencode_view = [&]() {   // [TRAIN] the view encoding again (same function, same bits): 16 registers not held across the trunk
-      if constexpr (TRAIN && ENC_IN_KERNEL) {
-        asm volatile("" : "+v"(vd[0]), "+v"(vd[1]), "+v"(vd[2]));
-        encode_view(vd, h, V);
-      }
-      if constexpr (TRAIN && !ENC_IN_KERNEL) {
-        int64_t rq = ray;
-        asm volatile("" : "+v"(rq));
-        load_view_enc(sg.viewdirs_enc + rq * kViewEnc, h, V);
-      }
-    };
-    if constexpr (FOLD) {
-      // bottleneck (no activation, model.py:109) and the view layer's hidden columns (model.py:110-116) as ONE layer W' = W_v0[:, :256] W_b,
-      // b' = W_v0[:, :256] b_b + b_v0 on the post-ReLU layer-7 output; the view-encoding columns FIRST (chunk form) or already in Z (VB)
-      if constexpr (!VB) {
-        init_bias(Z, sm + kSmBiasView, h);
-        reencode_view();
-        chunk_mma<Net, kChV, 4, 14>(p, V, Z);
-      }
-      dense_layer<Net, kChV + (VB ? 0 : 1), 8, 4>(p, Y, Z, taps.consume(Y, plane_h(7), true)); taps.put_mask(7);
-    } else {
-      // bottleneck, no activation (model.py:109)
-      init_bias(X, sm + kSmBiasBott, h); dense_layer<Net, kChBott, 8, 8>(p, Y, X, taps.consume(Y, plane_h(7), true)); taps.put_mask(7);
-      // view branch: cat[bottleneck(256), viewenc(27)] -> 128, ReLU (model.py:110-116)
-      init_bias(Z, sm + kSmBiasView, h);
-      dense_layer<Net, kChV, 8, 4>(p, X, Z, taps.consume(X, kPlBot, false));
-      reencode_view();
-      chunk_mma<Net, kChV + 8, 4, 14>(p, V, Z);
-    }
-    relu_tiles(Z);
-    taps.burst(Z, kPlHV, 8);   // the view layer's output feeds the rgb head on the VALU
-    // rgb head (model.py:118)
-    float rgb[3];
+    if constexpr (DEFER) {
+      const bool live = sigma > 0.f;   // both half-waves hold the same sum (a + b == b + a)
+      if (valid) {
+        if (h == 0) {
+          f32x4 o; o[0] = 0.f; o[1] = 0.f; o[2] = 0.f; o[3] = sigma;
+          reinterpret_cast<f32x4*>(sg.raw)[g] = o;
+          sg.live_mark[g] = live ? 1 : 0;
+        }
+        if (live) {
+          char* row = reinterpret_cast<char*>(sg.live_rows) + g * 1024 + h * 16;   // features 32 t + 8 q + 4 h + {0..3}
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      float v = head_partial<4>(Z, sm + kSmWRgb + ch * kCondWidth, h);
-      rgb[ch] = v + __shfl_xor(v, 32) + sm[kSmBRgb + ch];
-    }
-    if (valid && h == 0) {
-      f32x4 o; o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2]; o[3] = sigma;
-      reinterpret_cast<f32x4*>(sg.raw)[g] = o;
+          for (int t = 0; t < 8; ++t) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              f32x4 v; v[0] = Y[t][4 * q]; v[1] = Y[t][4 * q + 1]; v[2] = Y[t][4 * q + 2]; v[3] = Y[t][4 * q + 3];
+              // streaming (`nt`) stores, as the training planes' (store_quad): the rows are read back once, by view_kernel, and written with
+              // the default policy they push the weight stream out of the L2 (measured: 564.7 against 568.0 ms per 640x480 frame)
+              __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(row + (32 * t + 8 * q) * 4));
+            }
+          }
+        }
+      }
+    } else {
+      constexpr int kChV = FOLD ? kChFView : kChView;
+      auto reencode_view = [&]() {   // [TRAIN] the view encoding again (same function, same bits): 16 registers not held across the trunk
+        if constexpr (TRAIN && ENC_IN_KERNEL) {
+          asm volatile("" : "+v"(vd[0]), "+v"(vd[1]), "+v"(vd[2]));
+          encode_view(vd, h, V);
+        }
+        if constexpr (TRAIN && !ENC_IN_KERNEL) {
+          int64_t rq = ray;
+          asm volatile("" : "+v"(rq));
+          load_view_enc(sg.viewdirs_enc + rq * kViewEnc, h, V);
+        }
+      };
+      if constexpr (FOLD) {
+        // bottleneck (no activation, model.py:109) and the view layer's hidden columns (model.py:110-116) as ONE layer W' = W_v0[:, :256] W_b,
+        // b' = W_v0[:, :256] b_b + b_v0 on the post-ReLU layer-7 output; the view-encoding columns FIRST (chunk form) or already in Z (VB)
+        if constexpr (!VB) {
+          init_bias(Z, sm + kSmBiasView, h);
+          reencode_view();
+          chunk_mma<Net, kChV, 4, 14>(p, V, Z);
+        }
+        dense_layer<Net, kChV + (VB ? 0 : 1), 8, 4>(p, Y, Z, taps.consume(Y, plane_h(7), true)); taps.put_mask(7);
+      } else {
+        // bottleneck, no activation (model.py:109)
+        init_bias(X, sm + kSmBiasBott, h); dense_layer<Net, kChBott, 8, 8>(p, Y, X, taps.consume(Y, plane_h(7), true)); taps.put_mask(7);
+        // view branch: cat[bottleneck(256), viewenc(27)] -> 128, ReLU (model.py:110-116)
+        init_bias(Z, sm + kSmBiasView, h);
+        dense_layer<Net, kChV, 8, 4>(p, X, Z, taps.consume(X, kPlBot, false));
+        reencode_view();
+        chunk_mma<Net, kChV + 8, 4, 14>(p, V, Z);
+      }
+      relu_tiles(Z);
+      taps.burst(Z, kPlHV, 8);   // the view layer's output feeds the rgb head on the VALU
+      // rgb head (model.py:118)
+      float rgb[3];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        float v = head_partial<4>(Z, sm + kSmWRgb + ch * kCondWidth, h);
+        rgb[ch] = v + __shfl_xor(v, 32) + sm[kSmBRgb + ch];
+      }
+      if (valid && h == 0) {
+        f32x4 o; o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2]; o[3] = sigma;
+        reinterpret_cast<f32x4*>(sg.raw)[g] = o;
+      }
     }
   });
 }
@@ -326,10 +367,10 @@ int num_cus() {  // CUs of the CURRENT device, cached per device ordinal (ops.py
   return cus;
 }
 
-template <bool ENC, bool TRAIN, bool FOLD, bool VB = false, bool GATHER = false>
+template <bool ENC, bool TRAIN, bool FOLD, bool VB = false, bool GATHER = false, bool DEFER = false>
 static hipError_t launch_mlp_tf(const MlpArgs& args, hipStream_t stream) {
   static DeviceOnce lds_once;  // one per template instance
-  return launch_persistent(&mlp_fwd_kernel<ENC, TRAIN, FOLD, VB, GATHER>, kLdsBytes, args.npass_total, lds_once, stream, args);   // [GATHER] npass_total: the passes of a full list
+  return launch_persistent(&mlp_fwd_kernel<ENC, TRAIN, FOLD, VB, GATHER, DEFER>, kLdsBytes, args.npass_total, lds_once, stream, args);   // [GATHER] npass_total: the passes of a full list
 }
 
 // the kernel of the form the launch's streams were packed in (agreed_form); the per-ray view bias serves the whole-path calls on the
@@ -397,6 +438,150 @@ hipError_t launch_view_bias(const char* packed, const float* viewdirs, int64_t n
                               viewdirs, n_rays, out, stream);
 }
 
+// ---------------------------------------------------------------------------------------------
+// deferred view branch: the view layer and the rgb head of the LISTED samples of a trunk launch
+// ---------------------------------------------------------------------------------------------
+// The vanilla density is relu(raw sigma): a sample with raw sigma <= 0 composites with weight exactly 0 and its colour is never seen.  The
+// DEFER instance of mlp_fwd_kernel stops behind the density head; the live samples are compacted (aon_occ.hip) and this kernel runs the
+// folded view layer W' (256 -> 128), its ReLU and the rgb head on them alone -- the operations of mlp_fwd_kernel's VB form in its order, so
+// the same bits: accumulators from the ray's view bias, then input tile j = 0 .. 7, register quad q, output tile tp, four two-deep MFMA
+// steps each (chunk_mma with NT_OUT = 4).  One wave = 32 listed samples, one wave per SIMD; W' (the stream's chunks 61 .. 68, 128 KiB) and
+// the small block sit in LDS for the whole launch: no ring, no barrier after the first.  The rows of a wave's NEXT tile are fetched into a
+// second register set while the current tile's MFMAs run.
+struct ViewArgs {
+  const char* packed;        // the level's folded stream
+  const float* rows;         // (total, 256) post-ReLU layer-7 rows, written for the listed samples
+  const int* idx;            // ascending live sample indices
+  const int64_t* count;      // their number (device)
+  const float* view_bias;    // (n_rays, 128)
+  float* raw;                // (total, 4): rgb of the listed samples is written, sigma stays
+  int S;
+};
+constexpr int kViewWBytes = 8 * kSmallChunkBytes;
+constexpr int kViewLdsBytes = kViewWBytes + (int)kSmallBytes;
+
+__device__ __forceinline__ int view_listed(const ViewArgs& a, int64_t listed, int64_t tile, int m) {
+  const int64_t e = tile * 32 + m;
+  return a.idx[e < listed ? e : listed - 1];   // a partial last tile repeats the last entry; its lanes do not store
+}
+// rows of input tile t of sample g: features 32 t + 8 q + 4 h + {0..3}, the accumulator layout the trunk stored them from
+__device__ __forceinline__ void view_gather_tile(const ViewArgs& a, int g, int h, int t, f32x16& Y) {
+  const char* row = reinterpret_cast<const char*>(a.rows) + (int64_t)g * 1024 + h * 16;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(row + (32 * t + 8 * q) * 4);
+    Y[4 * q] = v[0]; Y[4 * q + 1] = v[1]; Y[4 * q + 2] = v[2]; Y[4 * q + 3] = v[3];
+  }
+}
+__device__ __forceinline__ void view_bias_init(const ViewArgs& a, int g, int h, f32x16 (&Z)[4]) {
+  const float* vb = a.view_bias + (int64_t)(g / a.S) * kCondWidth + 4 * h;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(vb + 32 * (i >> 2) + 8 * (i & 3));
+    Z[i >> 2][4 * (i & 3)] = v[0]; Z[i >> 2][4 * (i & 3) + 1] = v[1]; Z[i >> 2][4 * (i & 3) + 2] = v[2]; Z[i >> 2][4 * (i & 3) + 3] = v[3];
+  }
+}
+// Z[tp] += W'[tp][input tile j] Y: chunk_mma's steps for NT_OUT = 4, NREG = 16 (q = i / 4, tp = i % 4, four two-deep MFMA steps each)
+// Z0: the tile's view bias; chunk 0's first step into each output tile takes it as the C operand (the fused multiply-add a zero-cost copy
+// would feed), so the bias of the NEXT samples can land in its own registers while this tile's accumulators are busy
+__device__ __forceinline__ void view_chunk(const char* w, int j, int lane, const f32x16& Y, f32x16 (&Z)[4], const f32x16 (&Z0)[4]) {
+  const char* buf = w + j * kSmallChunkBytes + lane * 16;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int q = i / 4, tp = i % 4;
+    const f32x4 av = *reinterpret_cast<const f32x4*>(buf + i * 1024);
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc)
+      Z[tp] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cc], Y[4 * q + cc], (j == 0 && q == 0 && cc == 0) ? Z0[tp] : Z[tp], 0, 0, 0);
+  }
+}
+
+__global__ void __launch_bounds__(256) view_kernel(ViewArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int64_t listed = *a.count;
+  const int64_t ntiles = (listed + 31) / 32;
+  if ((int64_t)blockIdx.x * 4 >= ntiles) return;   // (workgroup-uniform; an empty list: every workgroup leaves here)
+  float* sm = reinterpret_cast<float*>(smem + kViewWBytes);
+  {
+    const f32x4* src = reinterpret_cast<const f32x4*>(a.packed + chunk_offset_f(kChFView + 1));
+    f32x4* dst = reinterpret_cast<f32x4*>(smem);
+    for (int i = threadIdx.x; i < kViewWBytes / 16; i += 256) dst[i] = src[i];
+  }
+  load_small_block<kSmallFloats>(sm, reinterpret_cast<const float*>(a.packed + kStreamBytes));
+  __syncthreads();
+  const int lane = threadIdx.x & 63, m = lane & 31, h = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  int64_t tile = (int64_t)blockIdx.x * 4 + wave;
+  if (tile >= ntiles) return;
+  // ONE set of 8 input tiles: tile j of the wave's NEXT 32 samples is fetched into the registers of tile j as soon as the current samples'
+  // chunk j has consumed them, so every row load has 7/8 of a tile's MFMAs (12 us) to arrive.  The next samples' view bias is fetched in
+  // the middle of the tile into a set of its own (Zb): vmcnt retires in order, and the bias is the first thing the next tile waits for.
+  f32x16 Y[8], Z[4], Zb[4];
+  int g = view_listed(a, listed, tile, m);
+  int gn = view_listed(a, listed, tile + stride, m);
+  __builtin_amdgcn_sched_barrier(0);   // the loop's order here too -- list entries, bias, rows: its waits are sized for the later of its two entries
+  view_bias_init(a, g, h, Zb);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int t = 0; t < 8; ++t) view_gather_tile(a, g, h, t, Y[t]);
+  __builtin_amdgcn_sched_barrier(0);
+  while (true) {
+    // (no branch around the fetches: the wave's last tiles re-read the list's last entry -- valid memory -- because a load that may or
+    // may not have been issued makes every later vmcnt wait for everything.  The list entry is fetched TWO tiles ahead: the row
+    // addresses of the next tile are formed early in this one, and a wait for an entry fetched here would be a wait for every row.)
+    const int64_t nxt = tile + stride;
+    const int gnn = view_listed(a, listed, nxt + stride, m);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      view_chunk(smem, j, lane, Y[j], Z, Zb);
+      __builtin_amdgcn_sched_barrier(0);
+      view_gather_tile(a, gn, h, j, Y[j]);
+      if (j == 3) view_bias_init(a, gn, h, Zb);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    relu_tiles(Z);
+    float rgb[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float v = head_partial<4>(Z, sm + kSmWRgb + ch * kCondWidth, h);
+      rgb[ch] = v + __shfl_xor(v, 32) + sm[kSmBRgb + ch];
+    }
+    if (tile * 32 + m < listed && h == 0) {
+      float* rec = a.raw + (int64_t)g * 4;
+      rec[0] = rgb[0]; rec[1] = rgb[1]; rec[2] = rgb[2];
+    }
+    if (nxt >= ntiles) break;
+    tile = nxt; g = gn; gn = gnn;
+  }
+}
+
+// the trunk of launch_mlp_fwd's per-ray-bias form: records (0, 0, 0, raw sigma), marks and the live samples' rows (mlp_fwd_kernel, DEFER)
+hipError_t launch_mlp_trunk_defer(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_vals,
+                                  int64_t n_rays, int S, float* raw, uint8_t* live_mark, float* live_rows, hipStream_t stream) {
+  if (stream_form(packed) != kFormFolded) return hipErrorInvalidValue;
+  MlpArgs args{};
+  fill_seg(args.seg[0], TrainSeg{packed, nullptr, rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, nullptr, nullptr, 0, nullptr});
+  args.seg[0].live_rows = live_rows; args.seg[0].live_mark = live_mark;
+  finish_segs(args, 1);
+  return launch_mlp_tf<true, false, true, true, false, true>(args, stream);
+}
+
+// ... and the view branch of the listed samples (view_kernel); max_listed: an upper bound of *count, which only sizes the grid
+hipError_t launch_view_deferred(const char* packed, const float* live_rows, const int* idx, const int64_t* count, int64_t max_listed,
+                                const float* view_bias, int S, float* raw, hipStream_t stream) {
+  if (stream_form(packed) != kFormFolded) return hipErrorInvalidValue;
+  if (max_listed <= 0) return hipSuccess;
+  static DeviceOnce lds_once;
+  if (hipError_t e = set_max_lds(&view_kernel, kViewLdsBytes, lds_once); e != hipSuccess) return e;
+  const int cus = num_cus();
+  if (cus <= 0) return hipErrorInvalidDevice;
+  const int64_t groups = (max_listed + 127) / 128;
+  const ViewArgs a{packed, live_rows, idx, count, view_bias, raw, S};
+  view_kernel<<<dim3((unsigned)(groups < cus ? groups : cus)), dim3(256), kViewLdsBytes, stream>>>(a);
+  return hipGetLastError();
+}
+
 hipError_t launch_mlp_fwd(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs,
                           const float* t_vals, int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias) {
   MlpArgs args{};
@@ -460,15 +645,6 @@ hipError_t launch_mlp_fwd_enc(const char* packed, const float* samples_enc, cons
 // ---------------------------------------------------------------------------------------------
 // density on a grid (aon_density_grid, mesh extraction)
 // ---------------------------------------------------------------------------------------------
-// The stream truncated after layer 7: chunks 0 .. 59, which the literal and the folded forms share (aon_common.h).  The prefetch of the
-// next pass's first pair wraps at chunk 58 here (first_wrapping_chunk), not at the end of the view branch.
-struct VanillaTrunkNet {
-  static constexpr int kSlotBytes = kPairSlotBytes;
-  static constexpr bool kPair = true;
-  static constexpr int kNumChunks = kChBott;
-  static constexpr int chunk_bytes(int) { return kBigChunkBytes; }
-};
-
 // (GridArgs, grid_point, grid_activation, grid_store: aon_mlp_core.h)
 
 // encode -> trunk -> density head of mlp_fwd_kernel -- the same trunk_fwd, so the same operations in the same order and the same bits as

@@ -146,7 +146,7 @@ __global__ __launch_bounds__(kOccThreads) void occ_mark_kernel(OccArgs<KMAX> a, 
   sentinel[0] = 0.f; sentinel[1] = 0.f; sentinel[2] = 0.f; sentinel[3] = -__builtin_huge_valf();
 #pragma unroll
   for (int r = 0; r < kOccPer; ++r)
-    if (s.rec[r] >= 0 && !s.occ[r]) raw[s.rec[r]] = sentinel;
+    if (raw && s.rec[r] >= 0 && !s.occ[r]) raw[s.rec[r]] = sentinel;   // (raw null: the records are the caller's, the deferred view branch)
   if (threadIdx.x == 0) {
     int tot = 0;
 #pragma unroll

@@ -606,13 +606,15 @@ _WS_CACHE = StreamCache()
 MAX_CHUNK_RAYS = 327680
 
 
-def _workspace(device, n_rays: int, st=None) -> torch.Tensor:
+def _workspace(device, n_rays: int, st=None, vanilla=False) -> torch.Tensor:
+    """``vanilla``: with room for the deferred view branch (set_deferred_view) while that switch is on."""
     chunk = MAX_CHUNK_RAYS
     if st is not None and (st.min_deg_point, st.max_deg_point, st.deg_view) != (0, 10, 4):
         chunk = 65536      # the encodings of a chunk are materialised (51 KB per ray) for other degrees
-    need = int(lib.aon_render_workspace_bytes_ex(min(n_rays, chunk), None if st is None else C.byref(st)))
+    query = "aon_render_deferred_workspace_bytes" if vanilla and lib.aon_get_deferred_view() else "aon_render_workspace_bytes_ex"
+    need = int(getattr(lib, query)(min(n_rays, chunk), None if st is None else C.byref(st)))
     if need < 0:
-        check(need, "aon_render_workspace_bytes_ex")
+        check(need, query)
     return _scratch(_WS_CACHE, device, need)
 
 
@@ -666,7 +668,7 @@ def _render_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, n
         return _stop_call(name + "_stop", packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, None, 0.0, None, num_levels, u, opts, workspace_bytes,
                           t_rand=t_rand, noise=noise, ray_live=ray_live, want_stats=False)[0]
     pc = _PathCall(rays_o, rays_d, viewdirs, near, far, white_bkgd, num_levels, t_rand, u, opts, noise)
-    ws = _workspace(pc.dev, pc.n, pc.st)
+    ws = _workspace(pc.dev, pc.n, pc.st, vanilla=name == "aon_render_fwd")
     with torch.cuda.device(pc.dev):
         check(getattr(lib, name + "_ex")(*packs, *pc.args(ws)), name)
     return pc.outs
@@ -1059,6 +1061,16 @@ def set_fwd_overlap(on: bool) -> None:
 def set_view_bias(on: bool) -> None:
     """Whole-path calls of the folded vanilla network: the view-encoding term as a per-ray bias (default on; same bits as the chunk form)."""
     check(lib.aon_set_view_bias(int(bool(on))), "aon_set_view_bias")
+
+
+def set_deferred_view(on: bool) -> None:
+    """Dense whole-path renders of the folded vanilla network: the view branch only on the samples with raw sigma > 0, behind a
+    compaction (default on; same bits as the single kernel, which ``False`` puts back)."""
+    check(lib.aon_set_deferred_view(int(bool(on))), "aon_set_deferred_view")
+
+
+def deferred_view_enabled() -> bool:
+    return bool(lib.aon_get_deferred_view())
 
 
 def view_bias_enabled() -> bool:
@@ -1893,7 +1905,8 @@ def _stop_call(name, packs, rays_o, rays_d, viewdirs, near, far, white_bkgd, gri
         if pc.bounds is not None:
             name, extra = name.rsplit("_", 1)[0] + "_bounds", extra + (C.byref(pc.bounds),)
         if plain:
-            ws = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=dev) if workspace_bytes is not None else _workspace(dev, n, pc.st)
+            ws = torch.empty(int(workspace_bytes), dtype=torch.uint8, device=dev) if workspace_bytes is not None else \
+                _workspace(dev, n, pc.st, vanilla=name.startswith("aon_render_fwd"))
         else:
             ws = _occ_workspace(dev, n, pc.st, workspace_bytes, "aon_render_stop_workspace_bytes")
     with torch.cuda.device(dev):

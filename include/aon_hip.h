@@ -517,6 +517,18 @@ int aon_sample_pdf_n(const float* bins, const float* weights, int64_t w_stride, 
                      int64_t u_stride, int64_t n_rays, int num_bins, int num_samples, int num_t, float* samples, float* t_fine,
                      void* stream);
 int64_t aon_render_workspace_bytes_ex(int64_t n_rays, const aon_render_opts* opts);
+/* Default 1: the dense whole-path renders of the vanilla network (aon_render_fwd*, folded form with the per-ray view bias, default
+ * encoding degrees, no density noise at the level) run the view branch only on the samples with raw sigma > 0.  The density is
+ * relu(raw sigma), so every other sample composites with weight exactly 0 and its colour is never seen: the MLP kernel stops behind the
+ * density head and stores the layer-7 output of the live samples, they are compacted on the device, and a second kernel runs the view
+ * layer and the rgb head on the list.  Same bits in every output.  The form needs workspace beyond
+ * aon_render_workspace_bytes_ex -- aon_render_deferred_workspace_bytes sizes it -- and a call whose workspace does not hold it runs the
+ * single kernel, as does every call after aon_set_deferred_view(0). */
+int aon_set_deferred_view(int on);
+int aon_get_deferred_view(void);
+int64_t aon_render_deferred_workspace_bytes(int64_t n_rays, const aon_render_opts* opts);
+/* Tests: rays per slab of the deferred view branch (0: the default, 32,768), so that a small render crosses slab borders. */
+int aon_test_set_deferred_slab(int rays);
 int aon_render_fwd_ex(const void* packed_coarse, const void* packed_fine, const float* rays_o, const float* rays_d,
                       const float* viewdirs, int64_t n_rays, float near_, float far_, int white_bkgd, int num_levels,
                       const float* t_rand, const float* u, int64_t u_stride, float* rgb_c, float* acc_c, float* depth_c,

@@ -178,8 +178,9 @@ int aon_mlp_fwd(const void* packed, const float* rays_o, const float* rays_d, co
   if (!packed || !rays_o || !rays_d || !viewdirs || !t_vals || !raw) return fail(AON_E_INVALID, "aon_mlp_fwd: null pointer");
   if (n_rays * (int64_t)S > (int64_t)INT32_MAX * 64) return fail(AON_E_INVALID, "aon_mlp_fwd: too many samples for one call");
   MlpTimer timer((hipStream_t)stream, n_rays * S);
-  return check(aon::launch_mlp_fwd(static_cast<const char*>(packed), rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw,
-                                   (hipStream_t)stream), "aon_mlp_fwd");
+  const aon::FwdSeg seg{.packed = static_cast<const char*>(packed), .rays_o = rays_o, .rays_d = rays_d, .viewdirs = viewdirs, .t_vals = t_vals,
+                        .n_rays = n_rays, .S = S, .raw = raw};
+  return check(aon::launch_net_fwd(false, &seg, 1, (hipStream_t)stream), "aon_mlp_fwd");
 }
 
 int aon_mlp_fwd_enc(const void* packed, const float* samples_enc, const float* viewdirs_enc, int64_t n_rays, int S,
@@ -187,8 +188,9 @@ int aon_mlp_fwd_enc(const void* packed, const float* samples_enc, const float* v
   if (n_rays < 0 || S < 1) return fail(AON_E_INVALID, "aon_mlp_fwd_enc: bad size");
   if (n_rays == 0) return AON_OK;
   if (!packed || !samples_enc || !viewdirs_enc || !raw) return fail(AON_E_INVALID, "aon_mlp_fwd_enc: null pointer");
-  return check(aon::launch_mlp_fwd_enc(static_cast<const char*>(packed), samples_enc, viewdirs_enc, n_rays, S, raw,
-                                       (hipStream_t)stream), "aon_mlp_fwd_enc");
+  const aon::FwdSeg seg{.packed = static_cast<const char*>(packed), .n_rays = n_rays, .S = S, .raw = raw, .samples_enc = samples_enc,
+                        .viewdirs_enc = viewdirs_enc};
+  return check(aon::launch_net_fwd(false, &seg, 1, (hipStream_t)stream), "aon_mlp_fwd_enc");
 }
 
 int aon_composite(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* t_vals,
@@ -416,8 +418,9 @@ int aon_mlp_fwd_train(const void* packed, const float* rays_o, const float* rays
     return fail(AON_E_INVALID, "aon_mlp_fwd_train: null pointer");
   if (reinterpret_cast<uintptr_t>(masks) & 15) return fail(AON_E_INVALID, "aon_mlp_fwd_train: masks must be 16-byte aligned");
   MlpTimer timer((hipStream_t)stream, n_rays * S);
-  return check(aon::launch_mlp_fwd_train(static_cast<const char*>(packed), rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, planes,
-                                         masks, (hipStream_t)stream), "aon_mlp_fwd_train");
+  const aon::FwdSeg seg{.packed = static_cast<const char*>(packed), .rays_o = rays_o, .rays_d = rays_d, .viewdirs = viewdirs, .t_vals = t_vals,
+                        .n_rays = n_rays, .S = S, .raw = raw, .planes = planes, .masks = masks};
+  return check(aon::launch_net_fwd(false, &seg, 1, (hipStream_t)stream), "aon_mlp_fwd_train");
 }
 
 int aon_composite_bwd(const float* raw, const float* t_vals, const float* dirs, const float* g_rgb, const float* g_acc,
@@ -488,8 +491,9 @@ int aon_art_mlp_fwd_train(const void* packed, const void* small, const float* ra
   if (forms_differ(packed, small)) return fail(AON_E_INVALID, kFormsMsg);
   if (reinterpret_cast<uintptr_t>(masks) & 15) return fail(AON_E_INVALID, "aon_art_mlp_fwd_train: masks must be 16-byte aligned");
   MlpTimer timer((hipStream_t)stream, n_rays * S);
-  return check(aon::launch_art_mlp_fwd_train(static_cast<const char*>(packed), static_cast<const float*>(small), rays_o, rays_d, viewdirs,
-                                             t_vals, n_rays, S, raw, planes, masks, (hipStream_t)stream), "aon_art_mlp_fwd_train");
+  const aon::FwdSeg seg{.packed = static_cast<const char*>(packed), .small = static_cast<const float*>(small), .rays_o = rays_o, .rays_d = rays_d,
+                        .viewdirs = viewdirs, .t_vals = t_vals, .n_rays = n_rays, .S = S, .raw = raw, .planes = planes, .masks = masks};
+  return check(aon::launch_net_fwd(true, &seg, 1, (hipStream_t)stream), "aon_art_mlp_fwd_train");
 }
 
 int aon_art_bwd_chain(const void* packed_bwd, const void* small, const float* d_raw, const void* masks, const float* planes,
@@ -787,8 +791,9 @@ int aon_art_mlp_fwd(const void* packed, const void* small, const float* rays_o, 
   if (!packed || !small || !rays_o || !rays_d || !viewdirs || !t_vals || !raw) return fail(AON_E_INVALID, "aon_art_mlp_fwd: null pointer");
   if (forms_differ(packed, small)) return fail(AON_E_INVALID, kFormsMsg);
   MlpTimer timer((hipStream_t)stream, n_rays * S);
-  return check(aon::launch_art_mlp_fwd(static_cast<const char*>(packed), static_cast<const float*>(small), rays_o, rays_d, viewdirs,
-                                       t_vals, n_rays, S, raw, (hipStream_t)stream), "aon_art_mlp_fwd");
+  const aon::FwdSeg seg{.packed = static_cast<const char*>(packed), .small = static_cast<const float*>(small), .rays_o = rays_o, .rays_d = rays_d,
+                        .viewdirs = viewdirs, .t_vals = t_vals, .n_rays = n_rays, .S = S, .raw = raw};
+  return check(aon::launch_net_fwd(true, &seg, 1, (hipStream_t)stream), "aon_art_mlp_fwd");
 }
 
 int aon_art_mlp_fwd_pos(const void* packed, const void* small, const float* pos, const float* viewdirs_enc, int64_t n_rays, int S,
@@ -797,8 +802,9 @@ int aon_art_mlp_fwd_pos(const void* packed, const void* small, const float* pos,
   if (n_rays == 0) return AON_OK;
   if (!packed || !small || !pos || !viewdirs_enc || !raw) return fail(AON_E_INVALID, "aon_art_mlp_fwd_pos: null pointer");
   if (forms_differ(packed, small)) return fail(AON_E_INVALID, kFormsMsg);
-  return check(aon::launch_art_mlp_fwd_pos(static_cast<const char*>(packed), static_cast<const float*>(small), pos, viewdirs_enc,
-                                           n_rays, S, raw, (hipStream_t)stream), "aon_art_mlp_fwd_pos");
+  const aon::FwdSeg seg{.packed = static_cast<const char*>(packed), .small = static_cast<const float*>(small), .n_rays = n_rays, .S = S, .raw = raw,
+                        .pos = pos, .viewdirs_enc = viewdirs_enc};
+  return check(aon::launch_net_fwd(true, &seg, 1, (hipStream_t)stream), "aon_art_mlp_fwd_pos");
 }
 
 }  // extern "C"

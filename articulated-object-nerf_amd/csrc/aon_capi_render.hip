@@ -59,6 +59,18 @@ Ws carve(char* base, int64_t n, const Geo& g, bool occ = false, bool stop = fals
   return w;
 }
 
+// the largest k in [lo, hi] with bytes_of(k) <= budget for a size function that does not decrease in k, or lo - 1 when not even lo fits
+template <class F>
+int64_t largest_fit(int64_t lo, int64_t hi, int64_t budget, F bytes_of) {
+  if (hi >= lo && bytes_of(hi) <= budget) return hi;
+  int64_t fit = lo - 1;   // invariant: fit fits (or is lo - 1), hi does not
+  while (hi - fit > 1) {
+    const int64_t mid = fit + (hi - fit) / 2;
+    if (bytes_of(mid) <= budget) fit = mid; else hi = mid;
+  }
+  return fit;
+}
+
 }  // namespace
 
 extern "C" {
@@ -119,90 +131,109 @@ struct OccCtx {
   int32_t* stop_dev;
 };
 
+// One level of a chunk of rays through the MLP: the network, the chunk's rays and the level's t, where the records go, and what the call
+// brings along (geometry, workspace, occupancy).
+struct LevelRun {
+  const NetRef& net;
+  const float* o; const float* d; const float* v; const float* t;
+  int64_t n; int S; float* raw; int level; const uint8_t* live; hipStream_t stream;
+  const Geo& g; const Ws& w; const OccCtx* occ;
+};
+// the whole level as one forward segment on the in-kernel encodings; the forms below add what is theirs
+static aon::FwdSeg level_seg(const LevelRun& r, const float* vbias) {
+  return aon::FwdSeg{.packed = static_cast<const char*>(r.net.packed), .small = r.net.small, .rays_o = r.o, .rays_d = r.d, .viewdirs = r.v, .t_vals = r.t,
+                     .n_rays = r.n, .S = r.S, .raw = r.raw, .view_bias = vbias};
+}
+
+// NeRF(min_deg_point, max_deg_point, deg_view) with at most 10 / 4 levels: the encodings are computed by the stage kernels in the fused
+// kernel's 63 / 27-slot layout (zeros in the missing levels' slots, matched by zero weights in the packed stream, aon_pack_vanilla_mlp_deg)
+// and the MLP runs as NeRFMLP.forward(x, condition) on them: 252 B/sample of extra HBM traffic against 1.19 MFLOP/sample
+static hipError_t run_other_degrees(const LevelRun& r) {
+  if (hipError_t e = aon::launch_cast_rays(r.t, r.o, r.d, r.n, r.S, r.w.coords, r.stream); e != hipSuccess) return e;
+  if (hipError_t e = aon::launch_pos_enc(r.w.coords, r.n * r.S, r.g.min_deg, r.g.max_deg, r.w.enc, r.stream, aon::kPosEnc, 10); e != hipSuccess) return e;
+  if (hipError_t e = aon::launch_pos_enc(r.v, r.n, 0, r.g.deg_view, r.w.venc, r.stream, aon::kViewEnc, 4); e != hipSuccess) return e;
+  MlpTimer timer(r.stream, r.n * r.S);
+  const aon::FwdSeg seg{.packed = static_cast<const char*>(r.net.packed), .n_rays = r.n, .S = r.S, .raw = r.raw, .samples_enc = r.w.enc, .viewdirs_enc = r.w.venc};
+  return aon::launch_net_fwd(false, &seg, 1, r.stream);
+}
+
 // occ: mark the level's samples, compact the occupied ones into a list (aon_occ.hip) and run the MLP on that list alone (the GATHER
 // instances); the empty samples' records hold the zero-density sentinel.  Same view bias, same kernel arithmetic per sample.
-static hipError_t launch_net(const NetRef& net, const float* o, const float* d, const float* v, const float* t, int64_t n, int S,
-                             float* raw, hipStream_t stream, const Geo* g = nullptr, const Ws* w = nullptr, const OccCtx* occ = nullptr,
-                             int level = 0, const uint8_t* live = nullptr) {
-  if (g && g->other_degrees) {
-    // NeRF(min_deg_point, max_deg_point, deg_view) with at most 10 / 4 levels: the encodings are computed by the stage kernels in
-    // the fused kernel's 63 / 27-slot layout (zeros in the missing levels' slots, matched by zero weights in the packed stream,
-    // aon_pack_vanilla_mlp_deg) and the MLP runs as NeRFMLP.forward(x, condition) on them: 252 B/sample of extra HBM traffic
-    // against 1.19 MFLOP/sample
-    if (hipError_t e = aon::launch_cast_rays(t, o, d, n, S, w->coords, stream); e != hipSuccess) return e;
-    if (hipError_t e = aon::launch_pos_enc(w->coords, n * S, g->min_deg, g->max_deg, w->enc, stream, aon::kPosEnc, 10); e != hipSuccess) return e;
-    if (hipError_t e = aon::launch_pos_enc(v, n, 0, g->deg_view, w->venc, stream, aon::kViewEnc, 4); e != hipSuccess) return e;
-    MlpTimer timer(stream, n * S);
-    return aon::launch_mlp_fwd_enc(static_cast<const char*>(net.packed), w->enc, w->venc, n, S, raw, stream);
+// The compaction of the level's samples [s0, s1) of every ray: one segment, the buffers laid out for the whole level -> the list in `seg`
+static hipError_t compact_level(const LevelRun& r, int s0, int s1, const int* stop, aon::FwdSeg& seg) {
+  const int64_t starts[2] = {0, r.n};
+  const aon::OccCompact c{&r.occ->grid, starts, 1, r.S, s0, s1, r.o, r.d, r.t, r.live, stop};
+  return aon::launch_occ_compact(c, r.raw, r.w.occ, (r.n * r.S + 1023) / 1024, r.occ->tally ? r.occ->tally + r.level : nullptr, &seg.gather_idx,
+                                 &seg.gather_count, r.stream);
+}
+// [early termination] per round: mark -> scan -> emit -> the GATHER launch on the round's list -> the live rays' optical depth; all stream-ordered
+static hipError_t run_rounds(const LevelRun& r, const float* vbias) {
+  if (hipError_t e = aon::launch_occ_stop_init(r.w.stop, r.n, r.S, r.stream); e != hipSuccess) return e;
+  const int R = r.occ->R < r.S ? r.occ->R : r.S;
+  const aon::ActParams ap = r.g.act(r.net.articulated, r.level, 0);   // (no noise on this path)
+  aon::FwdSeg seg = level_seg(r, vbias);
+  for (int s0 = 0; s0 < r.S; s0 += R) {
+    const int s1 = s0 + R < r.S ? s0 + R : r.S;
+    if (hipError_t e = compact_level(r, s0, s1, aon::occ_stop_state(r.w.stop, r.n).stop, seg); e != hipSuccess) return e;
+    {
+      MlpTimer timer(r.stream, r.n * (s1 - s0));
+      seg.max_listed = r.n * (s1 - s0);
+      if (hipError_t e = aon::launch_net_fwd(r.net.articulated, &seg, 1, r.stream); e != hipSuccess) return e;
+    }
+    if (s1 < r.S)   // the last round (sample S-1 and its 1e10 interval) decides nothing
+      if (hipError_t e = aon::launch_occ_depth(r.raw, r.t, r.d, r.n, r.S, s0, s1, ap, r.occ->tau_stop, r.w.stop, r.stream); e != hipSuccess) return e;
   }
+  return hipSuccess;
+}
+static hipError_t run_listed(const LevelRun& r, const float* vbias) {
+  aon::FwdSeg seg = level_seg(r, vbias);
+  if (hipError_t e = compact_level(r, 0, r.S, nullptr, seg); e != hipSuccess) return e;
+  MlpTimer timer(r.stream, r.n * r.S);
+  return aon::launch_net_fwd(r.net.articulated, &seg, 1, r.stream);
+}
+// [deferred view branch] per slab of rays: the trunk, the compaction of its marks (one "row" per sample, the mark as its ray_live byte,
+// no grid: the list holds the slab's live sample indices) and the view branch of the listed samples; all stream-ordered.
+static hipError_t run_deferred(const LevelRun& r, const float* vbias) {
+  MlpTimer timer(r.stream, r.n * r.S);
+  const char* packed = static_cast<const char*>(r.net.packed);
+  const int S = r.S;
+  for (int64_t r0 = 0; r0 < r.n; r0 += r.w.slab) {
+    const int64_t ns = r.n - r0 < r.w.slab ? r.n - r0 : r.w.slab;
+    float* raw_s = r.raw + r0 * S * 4;
+    const float* vb_s = vbias + r0 * aon::kCondWidth;
+    const aon::FwdSeg trunk{.packed = packed, .rays_o = r.o + r0 * 3, .rays_d = r.d + r0 * 3, .viewdirs = r.v + r0 * 3, .t_vals = r.t + r0 * S, .n_rays = ns,
+                            .S = S, .raw = raw_s, .view_bias = vb_s, .live_mark = r.w.live_mark, .live_rows = r.w.live_rows};
+    if (hipError_t e = aon::launch_net_fwd(false, &trunk, 1, r.stream); e != hipSuccess) return e;
+    const int64_t starts[2] = {0, ns * S};
+    const aon::OccGrid no_grid{};
+    const aon::OccCompact c{&no_grid, starts, 1, 1, 0, 1, nullptr, nullptr, nullptr, r.w.live_mark, nullptr};
+    const int* live_idx = nullptr;
+    const int64_t* live_count = nullptr;
+    if (hipError_t e = aon::launch_occ_compact(c, nullptr, r.w.live_list, (ns * S + 1023) / 1024, nullptr, &live_idx, &live_count, r.stream); e != hipSuccess) return e;
+    if (hipError_t e = aon::launch_view_deferred(packed, r.w.live_rows, live_idx, live_count, ns * S, vb_s, S, raw_s, r.stream); e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+static hipError_t run_dense(const LevelRun& r, const float* vbias) {
+  MlpTimer timer(r.stream, r.n * r.S);
+  const aon::FwdSeg seg = level_seg(r, vbias);
+  return aon::launch_net_fwd(r.net.articulated, &seg, 1, r.stream);
+}
+
+// The form of a level, in order of precedence: other degrees, rounds, listed, deferred, dense.  The per-ray view bias of the folded form is
+// computed once, here.  Density noise can lift a sample with raw sigma <= 0 above zero: such a level keeps the single kernel.
+static hipError_t launch_net(const LevelRun& r) {
+  if (r.g.other_degrees) return run_other_degrees(r);
   const float* vbias = nullptr;
-  if (w && w->vbias && g_view_bias.load(std::memory_order_relaxed) != 0 && aon::stream_form(net.packed) == aon::kFormFolded) {
-    const hipError_t e = net.articulated ? aon::launch_art_view_bias(static_cast<const char*>(net.packed), net.small, v, n, w->vbias, stream)
-                                         : aon::launch_view_bias(static_cast<const char*>(net.packed), v, n, w->vbias, stream);
-    if (e != hipSuccess) return e;
-    vbias = w->vbias;
+  if (r.w.vbias && g_view_bias.load(std::memory_order_relaxed) != 0 && aon::stream_form(r.net.packed) == aon::kFormFolded) {
+    if (hipError_t e = aon::launch_net_view_bias(r.net.articulated, static_cast<const char*>(r.net.packed), r.net.small, r.v, r.n, r.w.vbias, r.stream);
+        e != hipSuccess) return e;
+    vbias = r.w.vbias;
   }
-  const int* idx = nullptr;
-  const int64_t* count = nullptr;
-  // the compaction of the level's samples [s0, s1) of every ray (aon_occ.hip): one segment, the buffers laid out for the whole level
-  auto compact = [&](int s0, int s1, const int* stop) {
-    const int64_t starts[2] = {0, n};
-    const aon::OccCompact c{&occ->grid, starts, 1, S, s0, s1, o, d, t, live, stop};
-    return aon::launch_occ_compact(c, raw, w->occ, (n * S + 1023) / 1024, occ->tally ? occ->tally + level : nullptr, &idx, &count, stream);
-  };
-  if (occ && occ->rounds) {
-    // per round: mark -> scan -> emit -> the GATHER launch on the round's list -> the live rays' optical depth; all stream-ordered
-    if (hipError_t e = aon::launch_occ_stop_init(w->stop, n, S, stream); e != hipSuccess) return e;
-    const int R = occ->R < S ? occ->R : S;
-    const aon::ActParams ap = g->act(net.articulated, level, 0);   // (no noise on this path)
-    for (int s0 = 0; s0 < S; s0 += R) {
-      const int s1 = s0 + R < S ? s0 + R : S;
-      if (hipError_t e = compact(s0, s1, aon::occ_stop_state(w->stop, n).stop); e != hipSuccess) return e;
-      {
-        MlpTimer timer(stream, n * (s1 - s0));
-        const hipError_t e = net.articulated ? aon::launch_art_mlp_fwd_gather(static_cast<const char*>(net.packed), net.small, o, d, v, t, n, S, raw, stream,
-                                                                              vbias, idx, count, n * (s1 - s0))
-                                             : aon::launch_mlp_fwd_gather(static_cast<const char*>(net.packed), o, d, v, t, n, S, raw, stream, vbias, idx,
-                                                                          count, n * (s1 - s0));
-        if (e != hipSuccess) return e;
-      }
-      if (s1 < S)   // the last round (sample S-1 and its 1e10 interval) decides nothing
-        if (hipError_t e = aon::launch_occ_depth(raw, t, d, n, S, s0, s1, ap, occ->tau_stop, w->stop, stream); e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }
-  if (occ) {
-    if (hipError_t e = compact(0, S, nullptr); e != hipSuccess) return e;
-    MlpTimer timer(stream, n * S);
-    if (net.articulated)
-      return aon::launch_art_mlp_fwd_gather(static_cast<const char*>(net.packed), net.small, o, d, v, t, n, S, raw, stream, vbias, idx, count);
-    return aon::launch_mlp_fwd_gather(static_cast<const char*>(net.packed), o, d, v, t, n, S, raw, stream, vbias, idx, count);
-  }
-  MlpTimer timer(stream, n * S);
-  if (net.articulated)
-    return aon::launch_art_mlp_fwd(static_cast<const char*>(net.packed), net.small, o, d, v, t, n, S, raw, stream, vbias);
-  // [deferred view branch] per slab of rays: the trunk, the compaction of its marks (one "row" per sample, the mark as its ray_live byte,
-  // no grid: the list holds the slab's live sample indices) and the view branch of the listed samples; all stream-ordered.  Density noise
-  // can lift a sample with raw sigma <= 0 above zero: such a level keeps the single kernel.
-  if (w && w->slab > 0 && vbias && !(g->noise[level] && g->noise_std > 0.f)) {
-    const char* packed = static_cast<const char*>(net.packed);
-    for (int64_t r = 0; r < n; r += w->slab) {
-      const int64_t ns = n - r < w->slab ? n - r : w->slab;
-      float* raw_s = raw + r * S * 4;
-      if (hipError_t e = aon::launch_mlp_trunk_defer(packed, o + r * 3, d + r * 3, v + r * 3, t + r * S, ns, S, raw_s, w->live_mark, w->live_rows, stream);
-          e != hipSuccess) return e;
-      const int64_t starts[2] = {0, ns * S};
-      const aon::OccGrid no_grid{};
-      const aon::OccCompact c{&no_grid, starts, 1, 1, 0, 1, nullptr, nullptr, nullptr, w->live_mark, nullptr};
-      const int* live_idx = nullptr;
-      const int64_t* live_count = nullptr;
-      if (hipError_t e = aon::launch_occ_compact(c, nullptr, w->live_list, (ns * S + 1023) / 1024, nullptr, &live_idx, &live_count, stream); e != hipSuccess) return e;
-      if (hipError_t e = aon::launch_view_deferred(packed, w->live_rows, live_idx, live_count, ns * S, vbias + r * aon::kCondWidth, S, raw_s, stream);
-          e != hipSuccess) return e;
-    }
-    return hipSuccess;
-  }
-  return aon::launch_mlp_fwd(static_cast<const char*>(net.packed), o, d, v, t, n, S, raw, stream, vbias);
+  if (r.occ) return r.occ->rounds ? run_rounds(r, vbias) : run_listed(r, vbias);
+  const bool noisy = r.g.noise[r.level] && r.g.noise_std > 0.f;
+  if (!r.net.articulated && r.w.slab > 0 && vbias && !noisy) return run_deferred(r, vbias);
+  return run_dense(r, vbias);
 }
 
 static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine, const PathCall& c, const OccCtx* occ = nullptr) {
@@ -223,28 +254,17 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
   const bool with_stop = with_occ && occ->rounds;
 
   // largest chunk the workspace admits ([occupancy] and whose sample indices fit the int32 list)
-  int64_t chunk = n_rays;
-  if (with_occ && chunk > INT32_MAX / g.Sf) chunk = INT32_MAX / g.Sf;
-  if (carve(nullptr, chunk, g, with_occ, with_stop).bytes > c.workspace_bytes) {
-    const int64_t per_ray = (int64_t)(g.Sc + g.Sc + g.Sf + 4 * g.Sf + (g.other_degrees ? (3 + aon::kPosEnc) * g.Sf + aon::kViewEnc : aon::kCondWidth) +
-                                      (with_occ ? g.Sf + 2 * (g.Sf / 1024 + 1) : 0) + (with_stop ? 2 : 0)) * 4;
-    const int64_t slack = (g.other_degrees ? 7 * 256 : 5 * 256) + (with_occ ? 4 * 256 : 0) + (with_stop ? 2 * 256 : 0);
-    chunk = (c.workspace_bytes - slack) / per_ray;
-    while (chunk > 0 && carve(nullptr, chunk, g, with_occ, with_stop).bytes > c.workspace_bytes) --chunk;
-    if (chunk < 1) return fail(AON_E_WORKSPACE, with_stop ? "render: workspace smaller than aon_render_stop_workspace_bytes(1)"
-                                                : with_occ ? "render: workspace smaller than aon_render_occ_workspace_bytes(1)"
-                                                         : "render: workspace smaller than aon_render_workspace_bytes(1)");
-  }
+  const int64_t chunk = largest_fit(1, with_occ && n_rays > INT32_MAX / g.Sf ? INT32_MAX / g.Sf : n_rays, c.workspace_bytes,
+                                    [&](int64_t k) { return carve(nullptr, k, g, with_occ, with_stop).bytes; });
+  if (chunk < 1) return fail(AON_E_WORKSPACE, with_stop ? "render: workspace smaller than aon_render_stop_workspace_bytes(1)"
+                                              : with_occ ? "render: workspace smaller than aon_render_occ_workspace_bytes(1)"
+                                                       : "render: workspace smaller than aon_render_workspace_bytes(1)");
   // [deferred view branch] the dense renders of the vanilla network on the fused encodings, when the switch is on and the workspace holds a
   // slab's marks, list and rows behind the plain layout (aon_render_deferred_workspace_bytes): the largest slab that fits, up to the cap
   int64_t slab = 0;
   if (!art && !with_occ && !g.other_degrees && g_deferred_view.load(std::memory_order_relaxed) != 0) {
-    const int64_t left = c.workspace_bytes - carve(nullptr, chunk, g).bytes;
-    int64_t s = defer_slab_cap(g) < chunk ? defer_slab_cap(g) : chunk;
-    if (defer_bytes(s, g) > left) {
-      s = left / ((int64_t)g.Sf * 1030);
-      while (s > 0 && defer_bytes(s, g) > left) --s;
-    }
+    const int64_t s = largest_fit(1, defer_slab_cap(g) < chunk ? defer_slab_cap(g) : chunk, c.workspace_bytes - carve(nullptr, chunk, g).bytes,
+                                  [&](int64_t k) { return defer_bytes(k, g); });
     const bool hook = g_defer_slab_test.load(std::memory_order_relaxed) > 0;
     if (s > 0 && (hook || s >= kDeferMinSlabRays || s >= chunk)) slab = s;
   }
@@ -258,7 +278,6 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
     const float* o = c.rays_o + r0 * 3;
     const float* d = c.rays_d + r0 * 3;
     const float* v = c.viewdirs + r0 * 3;
-    const float* uu = c.u_stride ? c.u + r0 * c.u_stride : c.u;
     // [per-ray bounds, DESIGN.md section 4.11] the chunk's near / far / live
     const float* near_ray = c.bounds ? c.bounds->near_ray + r0 : nullptr;
     const float* far_ray = c.bounds ? c.bounds->far_ray + r0 : nullptr;
@@ -271,43 +290,26 @@ static int render_impl(const char* who, const NetRef& coarse, const NetRef& fine
                                                g.lindisp, g.inv_near, g.inv_far, near_ray, far_ray), who);
     }
     if (rc) return rc;
-    rc = check(launch_net(coarse, o, d, v, w.t_c, n, g.Sc, w.raw, stream, &g, &w, occ, 0, live), who);
+    rc = check(launch_net(LevelRun{coarse, o, d, v, w.t_c, n, g.Sc, w.raw, 0, live, stream, g, w, occ}), who);
     if (rc) return rc;
     if (with_stop && occ->stop_dev) {
       rc = check(aon::launch_occ_stop_store(w.stop, 0, occ->stop_dev + r0 * 2, n, 2, stream), who);
       if (rc) return rc;
     }
-    if (fuse_coarse) {
-      // compositing + the fine level's sampling (model.py:162-173) in one kernel: the coarse weights stay in registers
-      KTimer timer(kCompositePdf, stream, n);
-      rc = check(aon::launch_composite_pdf(w.raw, w.t_c, d, n, c.white_bkgd, g.act(art, 0, r0), uu, c.u_stride, c.rgb[0] + r0 * 3,
-                                           c.acc[0] + r0, c.depth[0] + r0, nullptr, w.t_f, stream), who);
-    } else {
-      KTimer timer(kComposite, stream, n);
-      rc = check(aon::launch_composite(w.raw, 4, w.raw + 3, 4, w.t_c, d, n, g.Sc, c.white_bkgd, g.act(art, 0, r0), c.rgb[0] + r0 * 3, c.acc[0] + r0,
-                                       c.depth[0] + r0, num_levels == 2 ? w.w_c : nullptr, stream), who);
-    }
+    const bool two = num_levels == 2;
+    rc = coarse_tail(LevelTail{w.raw, w.t_c, d, n, g.Sc, r0, c.white_bkgd, art, g, fuse_coarse, c.u, c.u_stride, c.rgb[0] + r0 * 3, c.acc[0] + r0,
+                               c.depth[0] + r0, two ? w.w_c : nullptr, two ? w.t_f : nullptr, stream, who});
     if (rc) return rc;
-    if (num_levels == 1) continue;
+    if (!two) continue;
     // level 1 (model.py:162-173, :175-197)
-    if (!fuse_coarse) {
-      KTimer timer(kSamplePdf, stream, n);
-      rc = check(g.default_sizes ? aon::launch_sample_pdf(nullptr, w.w_c + 1, kSc, w.t_c, uu, c.u_stride, n, nullptr, w.t_f, stream)
-                                 : aon::launch_sample_pdf_n(nullptr, w.w_c + 1, g.Sc, w.t_c, uu, c.u_stride, n, g.Sc - 1, g.nf, g.Sc, nullptr,
-                                                            w.t_f, stream), who);
-      if (rc) return rc;
-    }
-    rc = check(launch_net(fine, o, d, v, w.t_f, n, g.Sf, w.raw, stream, &g, &w, occ, 1, live), who);
+    rc = check(launch_net(LevelRun{fine, o, d, v, w.t_f, n, g.Sf, w.raw, 1, live, stream, g, w, occ}), who);
     if (rc) return rc;
     if (with_stop && occ->stop_dev) {
       rc = check(aon::launch_occ_stop_store(w.stop, 0, occ->stop_dev + r0 * 2 + 1, n, 2, stream), who);
       if (rc) return rc;
     }
-    {
-      KTimer timer(kComposite, stream, n);
-      rc = check(aon::launch_composite(w.raw, 4, w.raw + 3, 4, w.t_f, d, n, g.Sf, c.white_bkgd, g.act(art, 1, r0), c.rgb[1] + r0 * 3, c.acc[1] + r0,
-                                       c.depth[1] + r0, nullptr, stream), who);
-    }
+    rc = fine_tail(LevelTail{w.raw, w.t_f, d, n, g.Sf, r0, c.white_bkgd, art, g, false, nullptr, 0, c.rgb[1] + r0 * 3, c.acc[1] + r0, c.depth[1] + r0,
+                             nullptr, nullptr, stream, who});
     if (rc) return rc;
   }
   return AON_OK;

@@ -247,60 +247,56 @@ int train_fwd_impl(const char* who, bool art, const TrainNet* nets, const PathCa
   const bool use_vb = !g.other_degrees && g_view_bias.load(std::memory_order_relaxed) != 0 && aon::stream_form(nets[0].packed_fwd) == aon::kFormFolded;
   if (use_vb)
     for (int l = 0; l < num_levels; ++l)
-      if (int rc = check(art ? aon::launch_art_view_bias(static_cast<const char*>(nets[l].packed_fwd), nets[l].small, viewdirs, n, w.lvl[l].vbias, stream)
-                             : aon::launch_view_bias(static_cast<const char*>(nets[l].packed_fwd), viewdirs, n, w.lvl[l].vbias, stream), who)) return rc;
+      if (int rc = check(aon::launch_net_view_bias(art, static_cast<const char*>(nets[l].packed_fwd), nets[l].small, viewdirs, n, w.lvl[l].vbias, stream), who))
+        return rc;
 
-  // Both levels of the ray range [r0, r0 + nk) on stream `st`.  r0 is a multiple of 128, so the range's samples start on a pass
-  // boundary at both levels: its planes / decision bits / raw records are the whole batch's buffers at an offset, the slot stride of
-  // the decision bits stays the whole batch's Np.
+  // The forward segment of level l of the ray range [r0, r0 + nk), and what follows its launch (LevelTail).  r0 is a multiple of 128, so
+  // the range's samples start on a pass boundary at both levels: its planes / decision bits / raw records are the whole batch's buffers
+  // at an offset, the slot stride of the decision bits stays the whole batch's Np.
+  auto seg_of = [&](int64_t r0, int64_t nk, int l) {
+    const TrainLevel& L = w.lvl[l];
+    const int64_t s0 = r0 * L.S;
+    return aon::FwdSeg{.packed = static_cast<const char*>(nets[l].packed_fwd), .small = nets[l].small, .rays_o = rays_o + r0 * 3, .rays_d = rays_d + r0 * 3,
+                       .viewdirs = viewdirs + r0 * 3, .t_vals = L.t + s0, .n_rays = nk, .S = L.S, .raw = L.raw + s0 * 4, .planes = L.planes + s0 * rows,
+                       .masks = L.masks + s0 * 32, .np_total = L.Np, .view_bias = use_vb ? L.vbias + r0 * aon::kCondWidth : nullptr};
+  };
+  auto tail_of = [&](int64_t r0, int64_t nk, int l, hipStream_t st) {
+    const TrainLevel& L = w.lvl[l];
+    const bool next = l == 0 && num_levels == 2;
+    return LevelTail{L.raw + r0 * L.S * 4, L.t + r0 * L.S, rays_d + r0 * 3, nk, L.S, r0, white_bkgd, art, g, fuse && l == 0, u, u_stride,
+                     rgb[l] + r0 * 3, acc[l] + r0, depth[l] + r0, next ? w.w_c + r0 * g.Sc : nullptr, next ? w.lvl[1].t + r0 * w.lvl[1].S : nullptr, st, who};
+  };
+  auto mlp = [&](const aon::FwdSeg* segs, int ns, hipStream_t st) {
+    int64_t samples = 0;
+    for (int i = 0; i < ns; ++i) samples += segs[i].n_rays * segs[i].S;
+    MlpTimer timer(st, samples);
+    return check(aon::launch_net_fwd(art, segs, ns, st), who);
+  };
+
+  // Both levels of the ray range [r0, r0 + nk) on stream `st`.
   auto run_range = [&](int64_t r0, int64_t nk, hipStream_t st) -> int {
-    const float* o = rays_o + r0 * 3; const float* d = rays_d + r0 * 3; const float* v = viewdirs + r0 * 3;
-    const float* uu = (u && u_stride) ? u + r0 * u_stride : u;
+    {
+      KTimer timer(kSampleT, st, nk);
+      if (int rc = check(aon::launch_sample_along_rays(rays_o + r0 * 3, rays_d + r0 * 3, nk, g.Sc, near_, far_, t_rand ? t_rand + r0 * g.Sc : nullptr,
+                                                       w.lvl[0].t + r0 * g.Sc, nullptr, st, g.lindisp, g.inv_near, g.inv_far, near_ray ? near_ray + r0 : nullptr,
+                                                       far_ray ? far_ray + r0 : nullptr), who)) return rc;
+    }
     for (int l = 0; l < num_levels; ++l) {
-      const TrainLevel& L = w.lvl[l];
-      const int64_t s0 = r0 * L.S;
-      float* t = L.t + s0; float* raw = L.raw + s0 * 4;
-      float* planes = L.planes + s0 * rows; char* masks = L.masks + s0 * 32;
-      float* t_next = num_levels == 2 ? w.lvl[1].t + r0 * w.lvl[1].S : nullptr;
-      int rc = AON_OK;
-      if (l == 0) {
-        KTimer timer(kSampleT, st, nk);
-        rc = check(aon::launch_sample_along_rays(o, d, nk, g.Sc, near_, far_, t_rand ? t_rand + r0 * g.Sc : nullptr, t, nullptr, st, g.lindisp, g.inv_near,
-                                                 g.inv_far, near_ray ? near_ray + r0 : nullptr, far_ray ? far_ray + r0 : nullptr), who);
-      } else if (!fuse) {
-        KTimer timer(kSamplePdf, st, nk);
-        const float* wc = w.w_c + r0 * g.Sc; const float* tc = w.lvl[0].t + r0 * g.Sc;
-        rc = check(g.default_sizes ? aon::launch_sample_pdf(nullptr, wc + 1, kSc, tc, uu, u_stride, nk, nullptr, t, st)
-                                   : aon::launch_sample_pdf_n(nullptr, wc + 1, g.Sc, tc, uu, u_stride, nk, g.Sc - 1, g.nf, g.Sc, nullptr, t, st), who);
-      }
-      if (rc) return rc;
+      aon::FwdSeg seg = seg_of(r0, nk, l);
       if (g.other_degrees) {
         // other encoding degrees: encodings by the stage kernels in the padded 63 / 27-slot layout, then the training forward on
         // caller-encoded inputs (same planes, same decision bits)
+        const TrainLevel& L = w.lvl[l];
+        const int64_t s0 = r0 * L.S;
         float* coords = L.coords + s0 * 3; float* enc = L.enc + s0 * aon::kPosEnc; float* venc = L.venc + r0 * aon::kViewEnc;
-        if ((rc = check(aon::launch_cast_rays(t, o, d, nk, L.S, coords, st), who))) return rc;
-        if ((rc = check(aon::launch_pos_enc(coords, nk * L.S, g.min_deg, g.max_deg, enc, st, aon::kPosEnc, 10), who))) return rc;
-        if ((rc = check(aon::launch_pos_enc(v, nk, 0, g.deg_view, venc, st, aon::kViewEnc, 4), who))) return rc;
-        MlpTimer timer(st, nk * L.S);
-        rc = check(aon::launch_mlp_fwd_train_enc(static_cast<const char*>(nets[l].packed_fwd), enc, venc, nk, L.S, raw, planes, masks, st, L.Np), who);
-      } else {
-        MlpTimer timer(st, nk * L.S);
-        const float* vb = use_vb ? L.vbias + r0 * aon::kCondWidth : nullptr;
-        rc = check(art ? aon::launch_art_mlp_fwd_train(static_cast<const char*>(nets[l].packed_fwd), nets[l].small, o, d, v, t, nk, L.S, raw, planes, masks,
-                                                       st, L.Np, vb)
-                       : aon::launch_mlp_fwd_train(static_cast<const char*>(nets[l].packed_fwd), o, d, v, t, nk, L.S, raw, planes, masks, st, L.Np, vb), who);
+        if (int rc = check(aon::launch_cast_rays(seg.t_vals, seg.rays_o, seg.rays_d, nk, L.S, coords, st), who)) return rc;
+        if (int rc = check(aon::launch_pos_enc(coords, nk * L.S, g.min_deg, g.max_deg, enc, st, aon::kPosEnc, 10), who)) return rc;
+        if (int rc = check(aon::launch_pos_enc(seg.viewdirs, nk, 0, g.deg_view, venc, st, aon::kViewEnc, 4), who)) return rc;
+        seg.rays_o = seg.rays_d = seg.viewdirs = seg.t_vals = nullptr;
+        seg.samples_enc = enc; seg.viewdirs_enc = venc;
       }
-      if (rc) return rc;
-      if (l == 0 && fuse) {
-        KTimer timer(kCompositePdf, st, nk);
-        rc = check(aon::launch_composite_pdf(raw, t, d, nk, white_bkgd, g.act(art, 0, r0), uu, u_stride, rgb[0] + r0 * 3, acc[0] + r0, depth[0] + r0, nullptr,
-                                             t_next, st), who);
-      } else {
-        KTimer timer(kComposite, st, nk);
-        rc = check(aon::launch_composite(raw, 4, raw + 3, 4, t, d, nk, L.S, white_bkgd, g.act(art, l, r0), rgb[l] + r0 * 3, acc[l] + r0, depth[l] + r0,
-                                         (l == 0 && num_levels == 2) ? w.w_c + r0 * g.Sc : nullptr, st), who);
-      }
-      if (rc) return rc;
+      if (int rc = mlp(&seg, 1, st)) return rc;
+      if (int rc = l == 0 ? coarse_tail(tail_of(r0, nk, 0, st)) : fine_tail(tail_of(r0, nk, 1, st))) return rc;
     }
     return AON_OK;
   };
@@ -312,60 +308,22 @@ int train_fwd_impl(const char* who, bool art, const TrainNet* nets, const PathCa
     if (kA > 0) {
       struct Rng { int64_t r0, nk; };
       const Rng R[2] = {{0, kA}, {kA, n - kA}};
-      auto seg_of = [&](const Rng& r, int l) {
-        const TrainLevel& L = w.lvl[l];
-        const int64_t s0 = r.r0 * L.S;
-        return aon::TrainSeg{static_cast<const char*>(nets[l].packed_fwd), nets[l].small, rays_o + r.r0 * 3, rays_d + r.r0 * 3, viewdirs + r.r0 * 3,
-                             L.t + s0, r.nk, L.S, L.raw + s0 * 4, L.planes + s0 * rows, L.masks + s0 * 32, L.Np,
-                             use_vb ? L.vbias + r.r0 * aon::kCondWidth : nullptr};
-      };
-      auto mlp = [&](const aon::TrainSeg* segs, int ns) {
-        int64_t samples = 0;
-        for (int i = 0; i < ns; ++i) samples += segs[i].n_rays * segs[i].S;
-        MlpTimer timer(stream, samples);
-        return check(art ? aon::launch_art_mlp_fwd_train2(segs, ns, stream) : aon::launch_mlp_fwd_train2(segs, ns, stream), who);
-      };
-      auto coarse_tail = [&](const Rng& r) {   // compositing + inverse CDF + merge of the range's coarse level -> its fine t
-        const float* d = rays_d + r.r0 * 3;
-        const float* uu = (u && u_stride) ? u + r.r0 * u_stride : u;
-        const TrainLevel& L = w.lvl[0];
-        float* t = L.t + r.r0 * L.S; float* raw = L.raw + r.r0 * L.S * 4;
-        float* t_next = w.lvl[1].t + r.r0 * w.lvl[1].S;
-        if (fuse) {
-          KTimer timer(kCompositePdf, stream, r.nk);
-          return check(aon::launch_composite_pdf(raw, t, d, r.nk, white_bkgd, g.act(art, 0, r.r0), uu, u_stride, rgb[0] + r.r0 * 3, acc[0] + r.r0, depth[0] + r.r0,
-                                                 nullptr, t_next, stream), who);
-        }
-        {
-          KTimer timer(kComposite, stream, r.nk);
-          if (int rc = check(aon::launch_composite(raw, 4, raw + 3, 4, t, d, r.nk, L.S, white_bkgd, g.act(art, 0, r.r0), rgb[0] + r.r0 * 3, acc[0] + r.r0,
-                                                   depth[0] + r.r0, w.w_c + r.r0 * g.Sc, stream), who)) return rc;
-        }
-        KTimer timer(kSamplePdf, stream, r.nk);
-        const float* wc = w.w_c + r.r0 * g.Sc;
-        return check(g.default_sizes ? aon::launch_sample_pdf(nullptr, wc + 1, kSc, t, uu, u_stride, r.nk, nullptr, t_next, stream)
-                                     : aon::launch_sample_pdf_n(nullptr, wc + 1, g.Sc, t, uu, u_stride, r.nk, g.Sc - 1, g.nf, g.Sc, nullptr, t_next, stream), who);
-      };
-      auto fine_tail = [&](const Rng& r) {
-        const TrainLevel& L = w.lvl[1];
-        KTimer timer(kComposite, stream, r.nk);
-        return check(aon::launch_composite(L.raw + r.r0 * L.S * 4, 4, L.raw + r.r0 * L.S * 4 + 3, 4, L.t + r.r0 * L.S, rays_d + r.r0 * 3, r.nk, L.S, white_bkgd,
-                                           g.act(art, 1, r.r0), rgb[1] + r.r0 * 3, acc[1] + r.r0, depth[1] + r.r0, nullptr, stream), who);
-      };
+      auto coarse = [&](const Rng& r) { return coarse_tail(tail_of(r.r0, r.nk, 0, stream)); };   // compositing + inverse CDF -> the range's fine t
+      auto fine = [&](const Rng& r) { return fine_tail(tail_of(r.r0, r.nk, 1, stream)); };
       {   // stratified t of the whole batch
         KTimer timer(kSampleT, stream, n);
         if (int rc = check(aon::launch_sample_along_rays(rays_o, rays_d, n, g.Sc, near_, far_, t_rand, w.lvl[0].t, nullptr, stream, g.lindisp, g.inv_near,
                                                          g.inv_far, near_ray, far_ray), who)) return rc;
       }
-      const aon::TrainSeg cA = seg_of(R[0], 0), fA = seg_of(R[0], 1), cB = seg_of(R[1], 0), fB = seg_of(R[1], 1);
-      if (int rc = mlp(&cA, 1)) return rc;
-      if (int rc = coarse_tail(R[0])) return rc;
-      const aon::TrainSeg mid[2] = {fA, cB};
-      if (int rc = mlp(mid, 2)) return rc;
-      if (int rc = coarse_tail(R[1])) return rc;
-      if (int rc = fine_tail(R[0])) return rc;
-      if (int rc = mlp(&fB, 1)) return rc;
-      return fine_tail(R[1]);
+      const aon::FwdSeg cA = seg_of(R[0].r0, R[0].nk, 0), fB = seg_of(R[1].r0, R[1].nk, 1);
+      const aon::FwdSeg mid[2] = {seg_of(R[0].r0, R[0].nk, 1), seg_of(R[1].r0, R[1].nk, 0)};
+      if (int rc = mlp(&cA, 1, stream)) return rc;
+      if (int rc = coarse(R[0])) return rc;
+      if (int rc = mlp(mid, 2, stream)) return rc;
+      if (int rc = coarse(R[1])) return rc;
+      if (int rc = fine(R[0])) return rc;
+      if (int rc = mlp(&fB, 1, stream)) return rc;
+      return fine(R[1]);
     }
   }
 

@@ -168,6 +168,43 @@ inline int path_call_check(const char* who, const PathCall& c, const Geo& g, boo
   return AON_OK;
 }
 
+// What follows a level's MLP launch, for inference (render_impl) and training (train_fwd_impl) alike: the level of the n rays from r0 on,
+// every pointer already at r0 (u: the call's, offset here by its stride).
+struct LevelTail {
+  const float* raw; const float* t; const float* d; int64_t n; int S; int64_t r0;
+  int white_bkgd; bool art; const Geo& g; bool fuse;
+  const float* u; int64_t u_stride;
+  float* rgb; float* acc; float* depth;   // the level's outputs
+  float* w_c; float* t_next;              // [coarse] its weights and the fine level's t, both null when there is no fine level
+  hipStream_t stream; const char* who;
+};
+// level 0 (model.py:162-197): compositing, then the fine level's t by the inverse CDF -- in one kernel where `fuse` says so (the coarse
+// weights stay in registers)
+inline int coarse_tail(const LevelTail& a) {
+  const float* uu = (a.u && a.u_stride) ? a.u + a.r0 * a.u_stride : a.u;
+  if (a.fuse) {
+    KTimer timer(kCompositePdf, a.stream, a.n);
+    return check(aon::launch_composite_pdf(a.raw, a.t, a.d, a.n, a.white_bkgd, a.g.act(a.art, 0, a.r0), uu, a.u_stride, a.rgb, a.acc, a.depth, nullptr,
+                                           a.t_next, a.stream), a.who);
+  }
+  {
+    KTimer timer(kComposite, a.stream, a.n);
+    if (int rc = check(aon::launch_composite(a.raw, 4, a.raw + 3, 4, a.t, a.d, a.n, a.S, a.white_bkgd, a.g.act(a.art, 0, a.r0), a.rgb, a.acc, a.depth,
+                                             a.w_c, a.stream), a.who)) return rc;
+  }
+  if (!a.t_next) return AON_OK;
+  KTimer timer(kSamplePdf, a.stream, a.n);
+  return check(a.g.default_sizes ? aon::launch_sample_pdf(nullptr, a.w_c + 1, kSc, a.t, uu, a.u_stride, a.n, nullptr, a.t_next, a.stream)
+                                 : aon::launch_sample_pdf_n(nullptr, a.w_c + 1, a.g.Sc, a.t, uu, a.u_stride, a.n, a.g.Sc - 1, a.g.nf, a.g.Sc, nullptr,
+                                                            a.t_next, a.stream), a.who);
+}
+// level 1 (model.py:175-197): compositing
+inline int fine_tail(const LevelTail& a) {
+  KTimer timer(kComposite, a.stream, a.n);
+  return check(aon::launch_composite(a.raw, 4, a.raw + 3, 4, a.t, a.d, a.n, a.S, a.white_bkgd, a.g.act(a.art, 1, a.r0), a.rgb, a.acc, a.depth, nullptr,
+                                     a.stream), a.who);
+}
+
 // The call record of the whole-path backward entry points (aon_render_bwd* / aon_art_render_bwd* / aon_grender_bwd), as PathCall is the
 // forwards': what the ABI's lists have in common around the network's own pointers.  g_rgb / g_acc / g_depth: the host arrays of per-level
 // device pointers as passed (g_acc / g_depth may be null, and so may their entries).

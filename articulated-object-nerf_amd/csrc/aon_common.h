@@ -232,19 +232,28 @@ struct ChainSeg {
   int64_t Np;
 };
 
-// One segment of a training-forward launch (host side): a network's streams and one ray range's buffers at one level.  The fused
-// training forwards take one or two of these per launch (launch_*_fwd_train2): e.g. the fine level of ray range A together with
-// the coarse level of ray range B, so the partial last round of workgroups of one is filled with passes of the other.
-struct TrainSeg {
-  const char* packed;      // the level's packed forward stream
-  const float* small;      // articulated: the level's per-call small block; vanilla: null (it follows the stream)
-  const float* rays_o; const float* rays_d; const float* viewdirs;   // of the ray range
-  const float* t_vals;     // (n_rays, S)
-  int64_t n_rays; int S;
-  float* raw;              // (n_rays * S, 4)
-  float* planes; void* masks;   // the range's offsets into the level's planes / decision bits
-  int64_t np_total;        // padded samples of the WHOLE level (slot stride of the decision bits); 0: this range alone
-  const float* view_bias = nullptr;   // vanilla, folded form: (n_rays, 128) per-ray bias of the view layer (launch_view_bias), or null
+// One segment of a fused forward launch (host side), inference or training: a network's streams and one ray range's buffers at one level.
+// launch_mlp_fwd / launch_art_mlp_fwd take one or two of these per launch: e.g. the fine level of ray range A together with the coarse
+// level of ray range B, so the partial last round of workgroups of one is filled with passes of the other.  What a segment holds decides
+// the kernel instance (see those launchers); everything a form does not use stays null / 0.
+struct FwdSeg {
+  const char* packed = nullptr;      // the level's packed forward stream
+  const float* small = nullptr;      // articulated: the level's per-call small block; vanilla: null (it follows the stream)
+  const float* rays_o = nullptr; const float* rays_d = nullptr; const float* viewdirs = nullptr;   // of the ray range
+  const float* t_vals = nullptr;     // (n_rays, S)
+  int64_t n_rays = 0; int S = 0;
+  float* raw = nullptr;              // (n_rays * S, 4)
+  float* planes = nullptr; void* masks = nullptr;   // [training] the range's offsets into the level's planes / decision bits
+  int64_t np_total = 0;              // padded samples of the WHOLE level (slot stride of the decision bits); 0: this range alone
+  const float* view_bias = nullptr;  // folded form: (n_rays, 128) per-ray bias of the view layer (launch_net_view_bias), or null
+  // caller-made inputs instead of the in-kernel ray cast and encodings: [vanilla] samples_enc (n_rays*S, 63) and viewdirs_enc (n_rays, 27),
+  // [articulated] pos (n_rays*S, 3) and viewdirs_enc
+  const float* samples_enc = nullptr; const float* pos = nullptr; const float* viewdirs_enc = nullptr;
+  // an occupancy list (aon_mlp_core.h): idx / count stay on the device; max_listed > 0: an upper bound of *count below n_rays * S (a round
+  // of the early-termination loop lists a sub-range of every ray), which only sizes the grid
+  const int* gather_idx = nullptr; const int64_t* gather_count = nullptr; int64_t max_listed = 0;
+  // [vanilla] the trunk of the deferred view branch: the samples' marks and the live samples' layer-7 rows
+  uint8_t* live_mark = nullptr; float* live_rows = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------------

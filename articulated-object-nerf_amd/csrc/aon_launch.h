@@ -1,5 +1,6 @@
 // The library's internal launch interface: the ONE declaration, with its default arguments, of every aon:: host function that is called from
-// another translation unit, and the small structs and constants that cross translation units.  Declarations only -- no kernels.  Every file
+// another translation unit, and the small structs and constants that cross translation units.  Declarations (and the two one-line network
+// dispatchers) only -- no kernels.  Every file
 // that defines one of these functions includes this header, so a definition that disagrees with its declaration does not compile.
 // (The fold products and the layer-wise engine keep their own headers: aon_fold.h, aon_gmlp.h.)
 #pragma once
@@ -12,26 +13,13 @@ namespace aon {
 int num_cus();   // CUs of the CURRENT device, cached per device ordinal
 hipError_t launch_pack_vanilla(const float* const* params, float* packed, hipStream_t stream, int pos_levels = 10, int view_levels = 4, bool fold_done = false);
 void vanilla_fold_jobs_fwd(const float* const* params, float* packed, int view_levels, FoldGemm jobs[2]);
-hipError_t launch_mlp_fwd(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs,
-                          const float* t_vals, int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias = nullptr);
-// the deferred view branch: the trunk of launch_mlp_fwd's per-ray-bias form, and the view layer + rgb head of the listed samples
-hipError_t launch_mlp_trunk_defer(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_vals,
-                                  int64_t n_rays, int S, float* raw, uint8_t* live_mark, float* live_rows, hipStream_t stream);
+// the one fused forward launch, inference and training: one or two segments, the kernel instance read off what they hold (FwdSeg, aon_common.h)
+hipError_t launch_mlp_fwd(const FwdSeg* segs, int nsegs, hipStream_t stream);
+// the view layer + rgb head of the samples a deferred trunk (a segment with live_rows) listed
 hipError_t launch_view_deferred(const char* packed, const float* live_rows, const int* idx, const int64_t* count, int64_t max_listed,
                                 const float* view_bias, int S, float* raw, hipStream_t stream);
 hipError_t launch_view_bias(const char* packed, const float* viewdirs, int64_t n_rays, float* out, hipStream_t stream);
 hipError_t launch_view_bias_raw(const float* chunk, const float* bias_vec, const float* viewdirs, int64_t n_rays, float* out, hipStream_t stream);
-hipError_t launch_mlp_fwd_enc(const char* packed, const float* samples_enc, const float* viewdirs_enc, int64_t n_rays,
-                              int S, float* raw, hipStream_t stream);
-hipError_t launch_mlp_fwd_gather(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_vals,
-                                 int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias, const int* idx, const int64_t* count,
-                                 int64_t max_listed = 0);
-hipError_t launch_mlp_fwd_train(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs,
-                                const float* t_vals, int64_t n_rays, int S, float* raw, float* planes, void* masks,
-                                hipStream_t stream, int64_t np_total = 0, const float* view_bias = nullptr);
-hipError_t launch_mlp_fwd_train2(const TrainSeg* segs, int nsegs, hipStream_t stream);
-hipError_t launch_mlp_fwd_train_enc(const char* packed, const float* samples_enc, const float* viewdirs_enc, int64_t n_rays, int S, float* raw,
-                                    float* planes, void* masks, hipStream_t stream, int64_t np_total = 0);
 hipError_t launch_density_grid(const char* packed, const int64_t* dims, const float* lo, const float* step, int64_t g_begin, int64_t g_end,
                                int act, float* out, hipStream_t stream);
 
@@ -44,21 +32,18 @@ hipError_t launch_prepare_art(const float* const* params, const float* shape, co
                               float* small, hipStream_t stream, int min_deg = 0, int pos_levels = 10, int view_levels = 4);
 hipError_t launch_pack_prepare_art2(const float* const* const params[2], const float* shape, const float* app, const float* art, float* const packed[2],
                                     float* const small[2], hipStream_t stream, int min_deg, int pos_levels, int view_levels, int form);
-hipError_t launch_art_mlp_fwd(const char* packed, const float* small, const float* rays_o, const float* rays_d,
-                              const float* viewdirs, const float* t_vals, int64_t n_rays, int S, float* raw,
-                              hipStream_t stream, const float* view_bias = nullptr);
+hipError_t launch_art_mlp_fwd(const FwdSeg* segs, int nsegs, hipStream_t stream);
 hipError_t launch_art_view_bias(const char* packed, const float* small, const float* viewdirs, int64_t n_rays, float* out, hipStream_t stream);
-hipError_t launch_art_mlp_fwd_pos(const char* packed, const float* small, const float* pos, const float* viewdirs_enc,
-                                  int64_t n_rays, int S, float* raw, hipStream_t stream);
-hipError_t launch_art_mlp_fwd_gather(const char* packed, const float* small, const float* rays_o, const float* rays_d, const float* viewdirs,
-                                     const float* t_vals, int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias,
-                                     const int* idx, const int64_t* count, int64_t max_listed = 0);
-hipError_t launch_art_mlp_fwd_train(const char* packed, const float* small, const float* rays_o, const float* rays_d,
-                                    const float* viewdirs, const float* t_vals, int64_t n_rays, int S, float* raw, float* planes,
-                                    void* masks, hipStream_t stream, int64_t np_total = 0, const float* view_bias = nullptr);
-hipError_t launch_art_mlp_fwd_train2(const TrainSeg* segs, int nsegs, hipStream_t stream);
 hipError_t launch_art_density_grid(const char* packed, const float* small, const int64_t* dims, const float* lo, const float* step,
                                    int64_t g_begin, int64_t g_end, int act, float* out, hipStream_t stream);
+
+// ---- the single place where the network of a forward launch is chosen (small: the articulated per-call block, null for the vanilla network) ----
+inline hipError_t launch_net_fwd(bool art, const FwdSeg* segs, int nsegs, hipStream_t stream) {
+  return art ? launch_art_mlp_fwd(segs, nsegs, stream) : launch_mlp_fwd(segs, nsegs, stream);
+}
+inline hipError_t launch_net_view_bias(bool art, const char* packed, const float* small, const float* viewdirs, int64_t n_rays, float* out, hipStream_t stream) {
+  return art ? launch_art_view_bias(packed, small, viewdirs, n_rays, out, stream) : launch_view_bias(packed, viewdirs, n_rays, out, stream);
+}
 
 // ---- the weight-gradient stage shared by aon_train.hip and aon_train_art.hip (kernels and plan types: aon_wgrad.h) ----
 struct WgLayerDesc;

@@ -556,17 +556,6 @@ __global__ void __launch_bounds__(256) view_kernel(ViewArgs a) {
   }
 }
 
-// the trunk of launch_mlp_fwd's per-ray-bias form: records (0, 0, 0, raw sigma), marks and the live samples' rows (mlp_fwd_kernel, DEFER)
-hipError_t launch_mlp_trunk_defer(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_vals,
-                                  int64_t n_rays, int S, float* raw, uint8_t* live_mark, float* live_rows, hipStream_t stream) {
-  if (stream_form(packed) != kFormFolded) return hipErrorInvalidValue;
-  MlpArgs args{};
-  fill_seg(args.seg[0], TrainSeg{packed, nullptr, rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, nullptr, nullptr, 0, nullptr});
-  args.seg[0].live_rows = live_rows; args.seg[0].live_mark = live_mark;
-  finish_segs(args, 1);
-  return launch_mlp_tf<true, false, true, true, false, true>(args, stream);
-}
-
 // ... and the view branch of the listed samples (view_kernel); max_listed: an upper bound of *count, which only sizes the grid
 hipError_t launch_view_deferred(const char* packed, const float* live_rows, const int* idx, const int64_t* count, int64_t max_listed,
                                 const float* view_bias, int S, float* raw, hipStream_t stream) {
@@ -582,64 +571,32 @@ hipError_t launch_view_deferred(const char* packed, const float* live_rows, cons
   return hipGetLastError();
 }
 
-hipError_t launch_mlp_fwd(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs,
-                          const float* t_vals, int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias) {
+// The one forward launch of the vanilla network: one or two segments in ONE persistent launch (see MlpSeg), the kernel instance read off
+// what the segments hold (fwd_form) --
+//   planes: the training forward, which also stores the activation planes (kPlRows x Np floats, Np = 128*ceil(n*S/128)) and decision bits;
+//           np_total: the padded sample count of the WHOLE batch when the segment covers a ray range of it starting on a pass boundary
+//           (planes / masks / raw / t_vals already point at the range): the decision bits' slot stride is the whole batch's;
+//   gather_idx: the samples of an occupancy list (aon_mlp_core.h);
+//   samples_enc / viewdirs_enc: caller-encoded inputs (padded 63 / 27-column layout) instead of the in-kernel encodings;
+//   live_rows: the trunk of the per-ray-bias form (mlp_fwd_kernel, DEFER): records (0, 0, 0, raw sigma), marks and the live samples' rows
+//           -- folded streams only, and the segment carries the view bias launch_view_deferred will finish the samples with.
+// A combination no instance serves is hipErrorInvalidValue, as are an unknown form, mixed forms and a view bias on caller-made encodings.
+hipError_t launch_mlp_fwd(const FwdSeg* segs, int nsegs, hipStream_t stream) {
+  const FwdForm f = fwd_form(segs, nsegs);
+  if (!f.ok) return hipErrorInvalidValue;
   MlpArgs args{};
-  fill_seg(args.seg[0], TrainSeg{packed, nullptr, rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, nullptr, nullptr, 0, view_bias});
-  finish_segs(args, 1);
-  return launch_mlp_t<true, false>(args, stream);
-}
-
-// launch_mlp_fwd on the samples of an occupancy list (aon_mlp_core.h): idx / count stay on the device.  max_listed > 0: an upper bound of
-// *count below n_rays * S (a round of the early-termination loop lists a sub-range of every ray), which only sizes the grid.
-hipError_t launch_mlp_fwd_gather(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs, const float* t_vals,
-                                 int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias, const int* idx, const int64_t* count,
-                                 int64_t max_listed) {
-  MlpArgs args{};
-  MlpSeg& a = args.seg[0];
-  fill_seg(a, TrainSeg{packed, nullptr, rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, nullptr, nullptr, 0, view_bias});
-  if (max_listed > 0) a.npass = (int)((max_listed + 127) / 128);
-  a.gather_idx = idx; a.gather_count = count;
-  finish_segs(args, 1);
-  return launch_mlp_t<true, false, true>(args, stream);
-}
-
-// Training forward: as launch_mlp_fwd, plus the activation planes (kPlRows x Np floats, Np = 128*ceil(n*S/128)).
-// np_total: the padded sample count of the WHOLE batch when this launch covers a ray range of it starting on a pass boundary
-// (planes / masks / raw / t_vals already point at the range): the decision bits' slot stride is the whole batch's.
-hipError_t launch_mlp_fwd_train(const char* packed, const float* rays_o, const float* rays_d, const float* viewdirs,
-                                const float* t_vals, int64_t n_rays, int S, float* raw, float* planes, void* masks,
-                                hipStream_t stream, int64_t np_total, const float* view_bias) {
-  const TrainSeg one{packed, nullptr, rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, planes, masks, np_total, view_bias};
-  return launch_mlp_fwd_train2(&one, 1, stream);
-}
-
-// one or two segments in ONE persistent launch (see MlpSeg)
-hipError_t launch_mlp_fwd_train2(const TrainSeg* segs, int nsegs, hipStream_t stream) {
-  if (nsegs < 1 || nsegs > 2) return hipErrorInvalidValue;
-  MlpArgs args{};
-  for (int i = 0; i < nsegs; ++i) fill_seg(args.seg[i], segs[i]);
+  for (int i = 0; i < nsegs; ++i) {
+    if (segs[i].pos) return hipErrorInvalidValue;   // the articulated network's caller-made input
+    fill_seg(args.seg[i], segs[i]);
+  }
   finish_segs(args, nsegs);
-  return launch_mlp_t<true, true>(args, stream);
-}
-
-// training forward on caller-encoded inputs (padded 63 / 27-column layout): planes and decision bits as launch_mlp_fwd_train
-hipError_t launch_mlp_fwd_train_enc(const char* packed, const float* samples_enc, const float* viewdirs_enc, int64_t n_rays, int S, float* raw,
-                                    float* planes, void* masks, hipStream_t stream, int64_t np_total) {
-  MlpArgs args{};
-  fill_seg(args.seg[0], TrainSeg{packed, nullptr, nullptr, nullptr, nullptr, nullptr, n_rays, S, raw, planes, masks, np_total});
-  args.seg[0].samples_enc = samples_enc; args.seg[0].viewdirs_enc = viewdirs_enc;
-  finish_segs(args, 1);
-  return launch_mlp_t<false, true>(args, stream);
-}
-
-hipError_t launch_mlp_fwd_enc(const char* packed, const float* samples_enc, const float* viewdirs_enc,
-                              int64_t n_rays, int S, float* raw, hipStream_t stream) {
-  MlpArgs args{};
-  fill_seg(args.seg[0], TrainSeg{packed, nullptr, nullptr, nullptr, nullptr, nullptr, n_rays, S, raw, nullptr, nullptr, 0});
-  args.seg[0].samples_enc = samples_enc; args.seg[0].viewdirs_enc = viewdirs_enc;
-  finish_segs(args, 1);
-  return launch_mlp_t<false, false>(args, stream);
+  if (f.defer) {
+    if (!segs[0].view_bias || agreed_form(args) != kFormFolded) return hipErrorInvalidValue;
+    return launch_mlp_tf<true, false, true, true, false, true>(args, stream);
+  }
+  if (f.gather) return launch_mlp_t<true, false, true>(args, stream);
+  if (f.train) return f.own_inputs ? launch_mlp_t<false, true>(args, stream) : launch_mlp_t<true, true>(args, stream);
+  return f.own_inputs ? launch_mlp_t<false, false>(args, stream) : launch_mlp_t<true, false>(args, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

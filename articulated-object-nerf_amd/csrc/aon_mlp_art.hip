@@ -470,52 +470,23 @@ hipError_t launch_art_view_bias(const char* packed, const float* small, const fl
   return launch_view_bias_raw(reinterpret_cast<const float*>(packed + off), small + kA_BV, viewdirs, n_rays, out, stream);
 }
 
-hipError_t launch_art_mlp_fwd(const char* packed, const float* small, const float* rays_o, const float* rays_d,
-                              const float* viewdirs, const float* t_vals, int64_t n_rays, int S, float* raw,
-                              hipStream_t stream, const float* view_bias) {
+// The one forward launch of the articulated network: one or two segments in ONE persistent launch (see ArtSeg), the kernel instance read
+// off what the segments hold (fwd_form) -- planes: the training forward; gather_idx: the samples of an occupancy list (aon_mlp_core.h);
+// pos / viewdirs_enc: caller-made positions instead of the in-kernel ray cast.  A combination no instance serves (the training forward on
+// caller-made positions, the vanilla network's deferred trunk) is hipErrorInvalidValue, as are an unknown form, mixed forms and a view bias
+// on caller-made positions.
+hipError_t launch_art_mlp_fwd(const FwdSeg* segs, int nsegs, hipStream_t stream) {
+  const FwdForm f = fwd_form(segs, nsegs);
+  if (!f.ok || f.defer || (f.train && f.own_inputs)) return hipErrorInvalidValue;
   ArtMlpArgs args{};
-  fill_seg(args.seg[0], TrainSeg{packed, small, rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, nullptr, nullptr, 0, view_bias});
-  finish_segs(args, 1);
-  return launch_art_t<true, false>(args, stream);
-}
-
-// launch_art_mlp_fwd on the samples of an occupancy list (aon_mlp_core.h): idx / count stay on the device.  max_listed > 0: an upper bound
-// of *count below n_rays * S (a round of the early-termination loop), which only sizes the grid.
-hipError_t launch_art_mlp_fwd_gather(const char* packed, const float* small, const float* rays_o, const float* rays_d, const float* viewdirs,
-                                     const float* t_vals, int64_t n_rays, int S, float* raw, hipStream_t stream, const float* view_bias,
-                                     const int* idx, const int64_t* count, int64_t max_listed) {
-  ArtMlpArgs args{};
-  ArtSeg& a = args.seg[0];
-  fill_seg(a, TrainSeg{packed, small, rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, nullptr, nullptr, 0, view_bias});
-  if (max_listed > 0) a.npass = (int)((max_listed + 127) / 128);
-  a.gather_idx = idx; a.gather_count = count;
-  finish_segs(args, 1);
-  return launch_art_t<true, false, true>(args, stream);
-}
-
-hipError_t launch_art_mlp_fwd_train(const char* packed, const float* small, const float* rays_o, const float* rays_d,
-                                    const float* viewdirs, const float* t_vals, int64_t n_rays, int S, float* raw, float* planes,
-                                    void* masks, hipStream_t stream, int64_t np_total, const float* view_bias) {
-  const TrainSeg one{packed, small, rays_o, rays_d, viewdirs, t_vals, n_rays, S, raw, planes, masks, np_total, view_bias};
-  return launch_art_mlp_fwd_train2(&one, 1, stream);
-}
-
-// one or two segments in ONE persistent launch (see ArtSeg)
-hipError_t launch_art_mlp_fwd_train2(const TrainSeg* segs, int nsegs, hipStream_t stream) {
-  if (nsegs < 1 || nsegs > 2) return hipErrorInvalidValue;
-  ArtMlpArgs args{};
-  for (int i = 0; i < nsegs; ++i) fill_seg(args.seg[i], segs[i]);
+  for (int i = 0; i < nsegs; ++i) {
+    if (segs[i].samples_enc) return hipErrorInvalidValue;   // the vanilla network's caller-made input
+    fill_seg(args.seg[i], segs[i]);
+  }
   finish_segs(args, nsegs);
-  return launch_art_t<true, true>(args, stream);
-}
-
-hipError_t launch_art_mlp_fwd_pos(const char* packed, const float* small, const float* pos, const float* viewdirs_enc,
-                                  int64_t n_rays, int S, float* raw, hipStream_t stream) {
-  ArtMlpArgs args{};
-  fill_seg(args.seg[0], TrainSeg{packed, small, nullptr, nullptr, nullptr, nullptr, n_rays, S, raw, nullptr, nullptr, 0});
-  args.seg[0].pos = pos; args.seg[0].viewdirs_enc = viewdirs_enc;
-  finish_segs(args, 1);
-  return launch_art_t<false, false>(args, stream);
+  if (f.gather) return launch_art_t<true, false, true>(args, stream);
+  if (f.train) return launch_art_t<true, true>(args, stream);
+  return f.own_inputs ? launch_art_t<false, false>(args, stream) : launch_art_t<true, false>(args, stream);
 }
 
 // ---- density on a grid (aon_art_density_grid): deformation MLP -> encoding of x' -> trunk -> density head ----

@@ -1,6 +1,8 @@
 // The persistent pass loop of the fused MLP kernels (device) and the one launch path of those kernels (host).
 //
 // A launch carries one or two SEGMENTS: a run of 128-sample passes of one network over one range (MlpSeg, ArtSeg, BwdSeg, ArtBwdSeg).
+// The forward segments are filled from the host-side record FwdSeg (aon_common.h) by fill_seg, and fwd_form reads off the record which
+// kernel instance the launch names.
 // A segment record shows the driver two things through overloads next to its definition:
 //   seg_stream(sg)  the weight stream its passes run on,
 //   seg_small(sg)   the small block (biases, head weights) resident in LDS behind the ring while they run.
@@ -117,17 +119,40 @@ inline int agreed_form(const Args& a) {
   return vb && form != kFormFolded ? kFormUnknown : form;
 }
 
-// What every forward segment is made of, from the host-side record; the few fields particular to a launcher (caller-made encodings, the
-// occupancy list) are set behind it.
+// A forward segment from the host-side record, all of it: the ray range or the caller-made inputs, the buffers, and whichever of the
+// training planes, the occupancy list (with the pass count of max_listed) or the deferred trunk's marks and rows the record holds.
 template <class Seg>
-inline void fill_seg(Seg& a, const TrainSeg& t) {
+inline void fill_seg(Seg& a, const FwdSeg& t) {
   a.packed = t.packed;
-  if constexpr (Seg::kPerCallBlock) a.small = t.small;
+  if constexpr (Seg::kPerCallBlock) { a.small = t.small; a.pos = t.pos; }
+  else a.samples_enc = t.samples_enc;
+  a.viewdirs_enc = t.viewdirs_enc;
   a.rays_o = t.rays_o; a.rays_d = t.rays_d; a.viewdirs = t.viewdirs; a.t_vals = t.t_vals; a.view_bias = t.view_bias;
-  a.raw = t.raw; a.total = t.n_rays * t.S; a.S = t.S; a.npass = (int)((a.total + 127) / 128);
+  a.raw = t.raw; a.total = t.n_rays * t.S; a.S = t.S; a.npass = (int)(((t.max_listed > 0 ? t.max_listed : a.total) + 127) / 128);
   if (t.planes) {   // training: Np is the padded sample count of the WHOLE level where the segment is a ray range of it
     a.planes = t.planes; a.masks = static_cast<u32x4*>(t.masks); a.Np = t.np_total > 0 ? t.np_total : (int64_t)a.npass * 128;
+  } else if (t.gather_idx) {
+    a.gather_idx = t.gather_idx; a.gather_count = t.gather_count;
+  } else if constexpr (!Seg::kPerCallBlock) {
+    if (t.live_rows) { a.live_rows = t.live_rows; a.live_mark = t.live_mark; }
   }
+}
+
+// What the segments of a forward launch hold, which names the kernel instance (launch_mlp_fwd, launch_art_mlp_fwd).  `ok` is false where
+// no instance serves the launch whatever the network: nsegs outside 1..2, two segments that hold different things, more than one of
+// planes / list / deferred rows (the kernels' static_asserts), or an occupancy list on two segments (run_passes reads seg[0]'s count).
+struct FwdForm { bool ok, train, gather, own_inputs, defer; };
+inline FwdForm fwd_form(const FwdSeg* segs, int nsegs) {
+  auto of = [](const FwdSeg& s) { return FwdForm{true, s.planes != nullptr, s.gather_idx != nullptr, s.samples_enc || s.pos, s.live_rows != nullptr}; };
+  FwdForm f{};
+  if (nsegs < 1 || nsegs > 2) return f;
+  f = of(segs[0]);
+  if (nsegs == 2) {
+    const FwdForm g = of(segs[1]);
+    if (g.train != f.train || g.gather != f.gather || g.own_inputs != f.own_inputs || g.defer != f.defer || f.gather) f.ok = false;
+  }
+  if ((int)f.train + (int)f.gather + (int)f.defer > 1 || ((f.gather || f.defer) && f.own_inputs)) f.ok = false;
+  return f;
 }
 
 }  // namespace aon

@@ -6,7 +6,7 @@
 // A pair's ray is already in its object's frame, so a grid built in that frame applies verbatim: x = o' + t d' (multiply, then add: the MLP
 // kernel's own bits), looked up by occ_lookup (aon_occ_lookup.h).  Object k has ceil(P_k S / 1024) tiles when it has a grid and none
 // otherwise (a DENSE segment: not touched, its counter all of its samples); its list holds SEGMENT-LOCAL sample indices row_local * S + i at
-// idx + starts[k] S, so each segment feeds launch_art_mlp_fwd_gather unchanged with its own ray / t / raw pointers.
+// idx + starts[k] S, so each segment feeds the GATHER launch unchanged with its own ray / t / raw pointers.
 #include "../../include/aon_hip_scene_occ.h"
 #include "aon_capi_util.h"
 
@@ -56,13 +56,10 @@ int aon_scene_art_mlp_fwd_occ(const void* packed, const void* const* smalls_host
     const int64_t r0 = starts_host[j], rows = starts_host[j + 1] - r0;
     if (rows == 0) continue;
     MlpTimer timer(stream, rows * s);
-    const char* pk = static_cast<const char*>(packed);
-    const float* sm = static_cast<const float*>(smalls_host[j]);
-    const hipError_t e = grids[j].bits ? aon::launch_art_mlp_fwd_gather(pk, sm, pair_o + r0 * 3, pair_d + r0 * 3, pair_v + r0 * 3, t_vals + r0 * s, rows, s,
-                                                                        raw + r0 * s * 4, stream, nullptr, idx + r0 * s, counts + j, rows * s)
-                                       : aon::launch_art_mlp_fwd(pk, sm, pair_o + r0 * 3, pair_d + r0 * 3, pair_v + r0 * 3, t_vals + r0 * s, rows, s,
-                                                                 raw + r0 * s * 4, stream);
-    if (int rc = check(e, "aon_scene_art_mlp_fwd_occ")) return rc;
+    aon::FwdSeg seg{.packed = static_cast<const char*>(packed), .small = static_cast<const float*>(smalls_host[j]), .rays_o = pair_o + r0 * 3,
+                    .rays_d = pair_d + r0 * 3, .viewdirs = pair_v + r0 * 3, .t_vals = t_vals + r0 * s, .n_rays = rows, .S = s, .raw = raw + r0 * s * 4};
+    if (grids[j].bits) { seg.gather_idx = idx + r0 * s; seg.gather_count = counts + j; seg.max_listed = rows * s; }
+    if (int rc = check(aon::launch_net_fwd(true, &seg, 1, stream), "aon_scene_art_mlp_fwd_occ")) return rc;
   }
   return AON_OK;
 }

@@ -254,7 +254,17 @@ _SCENE_GRAD_SIGS = {
 }
 
 
-for _name, (_res, _args) in {**_SIGS, **_EXT_SIGS, **_SCENE_SIGS, **_SCENE_OCC_SIGS, **_SCENE_GRAD_SIGS}.items():
+# include/aon_hip_scene_pose.h: a sixth table, kept out of the five lists above
+_SCENE_POSE_SIGS = {
+    "aon_art_ray_grads_record_bytes": (_l, [_l, _i]),
+    # dplanes, dxp, params, t_vals, viewdirs | n_rays, s, np, deg_view | records, bytes | g_rays_o, g_rays_d, g_viewdirs | stream
+    "aon_art_ray_grads": (_i, [_p] * 5 + [_l, _i, _l, _i] + [_p, _l] + [_p] * 3 + [_p]),
+    # rays_o, rays_d, viewdirs, n | pair_ray, offsets | objects_host, k | pairs | g_o, g_d, g_v | g_pose | stream
+    "aon_scene_pose_grads": (_i, [_p, _p, _p, _l] + [_p, _p] + [_p, _i] + [_l] + [_p] * 3 + [_p] + [_p]),
+}
+
+
+for _name, (_res, _args) in {**_SIGS, **_EXT_SIGS, **_SCENE_SIGS, **_SCENE_OCC_SIGS, **_SCENE_GRAD_SIGS, **_SCENE_POSE_SIGS}.items():
     _fn = getattr(lib, _name)  # AttributeError here = the .so does not export what the header declares
     _fn.restype = _res
     _fn.argtypes = _args
@@ -302,3 +312,8 @@ def scene_occ_symbols():
 def scene_grad_symbols():
     """the names include/aon_hip_scene_grad.h declares"""
     return sorted(_SCENE_GRAD_SIGS)
+
+
+def scene_pose_symbols():
+    """the names include/aon_hip_scene_pose.h declares"""
+    return sorted(_SCENE_POSE_SIGS)

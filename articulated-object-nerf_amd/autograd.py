@@ -319,60 +319,125 @@ class RenderLevelScene(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pairs, t_vals, rays_d, white_bkgd, opts, packed_fwd, packed_bwd, degrees, *tensors):
-        K, n_par = pairs.K, len(ops.ART_PARAM_ORDER)
-        if len(tensors) != 3 * K + n_par:
-            raise ValueError(f"RenderLevelScene: expected {3 * K} codes and {n_par} parameters, got {len(tensors)} tensors")
-        # codes and parameters are read again by the backward: saved the autograd way (an in-place update in between raises)
-        ctx.save_for_backward(*tensors)
-        ctx.set_materialize_grads(False)
-        params = dict(zip(ops.ART_PARAM_ORDER, (p.detach() for p in tensors[3 * K:])))
-        t = t_vals.detach()
-        raw = torch.empty((pairs.P, t.shape[1], 4), dtype=torch.float32, device=t.device)
-        per_object = []
-        for k in range(K):
-            seg = pairs.segment(k)
-            if seg.stop == seg.start:      # an object without a pair costs no launch
-                per_object.append(None)
-                continue
-            small = ops.art_prepare(params, dict(zip(_LATENT_KEYS, tensors[3 * k: 3 * k + 3])), out=None, degrees=degrees)
-            _, planes, masks = ops.art_mlp_fwd_train(packed_fwd, small, pairs.rays_o[seg], pairs.rays_d[seg], pairs.viewdirs[seg], t[seg], out=raw[seg])
-            per_object.append((small, planes, masks))
-        rgb, acc, depth, obj_acc, weights = ops.scene_composite(raw, t, pairs, rays_d, white_bkgd, opts=opts)
-        ctx.keep = (pairs, t, rays_d.detach(), raw, per_object, packed_bwd, opts, tuple(degrees))
-        ctx.white_bkgd = white_bkgd
-        ctx.mark_non_differentiable(weights)
-        return rgb, acc, depth, obj_acc, weights
+        return _scene_level_forward(ctx, "RenderLevelScene", pairs, t_vals, rays_d, white_bkgd, opts, packed_fwd, packed_bwd, degrees, tensors)
 
     @staticmethod
     def backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, _g_weights):
-        _check_not_released(ctx)
-        pairs, t, rays_d, raw, per_object, packed_bwd, opts, degrees = ctx.keep
-        tensors = ctx.saved_tensors   # (raises if a code or a parameter was modified in place since the forward)
-        K, S, dev = pairs.K, t.shape[1], t.device
-        params = dict(zip(ops.ART_PARAM_ORDER, tensors[3 * K:]))
-        if g_rgb is None:
-            g_rgb = torch.zeros((pairs.n, 3), dtype=torch.float32, device=dev)
-        d_raw = ops.scene_composite_bwd(raw, t, pairs, rays_d, g_rgb, g_acc, g_depth, g_obj_acc, ctx.white_bkgd, opts=opts)
-        total, g_codes = None, []
-        for k in range(K):
-            codes = tensors[3 * k: 3 * k + 3]
-            if per_object[k] is None:
-                g_codes += [torch.zeros_like(c) for c in codes]
-                continue
-            small, planes, masks = per_object[k]
-            seg = pairs.segment(k)
-            rows = (seg.stop - seg.start) * S
-            d_seg = torch.zeros((ops.plane_samples(planes), 4), dtype=torch.float32, device=dev)   # the chain reads the zero tail
-            d_seg[:rows] = d_raw[seg].reshape(rows, 4)
-            dplanes, dxp = ops.art_bwd_chain(packed_bwd, small, d_seg, masks, planes)
-            grads, g_lat = ops.art_wgrad(planes, dplanes, d_seg, dxp, params, dict(zip(_LATENT_KEYS, codes)), degrees, packed_bwd=packed_bwd)
-            if total is None:
-                total = grads
-            else:      # plain adds in ascending k: a fixed order
-                for name in ops.ART_PARAM_ORDER:
-                    total[name] += grads[name]
-            g_codes += [g_lat[key].reshape(c.shape) for key, c in zip(_LATENT_KEYS, codes)]
-        if total is None:
-            total = {name: torch.zeros_like(p) for name, p in params.items()}
-        ctx.keep, ctx.released = None, True
+        g_codes, total, _ = _scene_level_backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, want_weights=True, rays=None)
         return (None,) * 8 + tuple(g_codes) + tuple(total[name] for name in ops.ART_PARAM_ORDER)
+
+
+def _scene_level_forward(ctx, who, pairs, t_vals, rays_d, white_bkgd, opts, packed_fwd, packed_bwd, degrees, tensors):
+    """The forward of the two scene-level Functions; tensors = 3 K codes, then the 40 parameters."""
+    K, n_par = pairs.K, len(ops.ART_PARAM_ORDER)
+    if len(tensors) != 3 * K + n_par:
+        raise ValueError(f"{who}: expected {3 * K} codes and {n_par} parameters, got {len(tensors)} tensors")
+    # codes and parameters are read again by the backward: saved the autograd way (an in-place update in between raises)
+    ctx.save_for_backward(*tensors)
+    ctx.set_materialize_grads(False)
+    params = dict(zip(ops.ART_PARAM_ORDER, (p.detach() for p in tensors[3 * K:])))
+    t = t_vals.detach()
+    raw = torch.empty((pairs.P, t.shape[1], 4), dtype=torch.float32, device=t.device)
+    per_object = []
+    for k in range(K):
+        seg = pairs.segment(k)
+        if seg.stop == seg.start:      # an object without a pair costs no launch
+            per_object.append(None)
+            continue
+        small = ops.art_prepare(params, dict(zip(_LATENT_KEYS, tensors[3 * k: 3 * k + 3])), out=None, degrees=degrees)
+        _, planes, masks = ops.art_mlp_fwd_train(packed_fwd, small, pairs.rays_o[seg], pairs.rays_d[seg], pairs.viewdirs[seg], t[seg], out=raw[seg])
+        per_object.append((small, planes, masks))
+    rgb, acc, depth, obj_acc, weights = ops.scene_composite(raw, t, pairs, rays_d, white_bkgd, opts=opts)
+    ctx.keep = (pairs, t, rays_d.detach(), raw, per_object, packed_bwd, opts, tuple(degrees))
+    ctx.white_bkgd = white_bkgd
+    ctx.mark_non_differentiable(weights)
+    return rgb, acc, depth, obj_acc, weights
+
+
+def _scene_level_backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, want_weights, rays):
+    """The backward of the two scene-level Functions -> (code gradients, parameter gradients, g_pose (K, 12)), the first two None without
+    `want_weights` (no aon_art_wgrad launch), the last None without `rays` = (world rays_o, viewdirs, objects): with them every segment's
+    chain is followed by ops.art_ray_grads into one (P, 3) x 3 buffer, and ops.scene_pose_grads reduces that once."""
+    _check_not_released(ctx)
+    pairs, t, rays_d, raw, per_object, packed_bwd, opts, degrees = ctx.keep
+    tensors = ctx.saved_tensors   # (raises if a code or a parameter was modified in place since the forward)
+    K, S, dev = pairs.K, t.shape[1], t.device
+    params = dict(zip(ops.ART_PARAM_ORDER, tensors[3 * K:]))
+    if g_rgb is None:
+        g_rgb = torch.zeros((pairs.n, 3), dtype=torch.float32, device=dev)
+    d_raw = ops.scene_composite_bwd(raw, t, pairs, rays_d, g_rgb, g_acc, g_depth, g_obj_acc, ctx.white_bkgd, opts=opts)
+    total, g_codes = None, []
+    g_pairs = torch.zeros((3, pairs.P, 3), dtype=torch.float32, device=dev) if rays is not None else None
+    for k in range(K):
+        codes = tensors[3 * k: 3 * k + 3]
+        if per_object[k] is None:
+            g_codes += [torch.zeros_like(c) for c in codes]
+            continue
+        small, planes, masks = per_object[k]
+        seg = pairs.segment(k)
+        rows = (seg.stop - seg.start) * S
+        d_seg = torch.zeros((ops.plane_samples(planes), 4), dtype=torch.float32, device=dev)   # the chain reads the zero tail
+        d_seg[:rows] = d_raw[seg].reshape(rows, 4)
+        dplanes, dxp = ops.art_bwd_chain(packed_bwd, small, d_seg, masks, planes)
+        if g_pairs is not None:
+            for dst, g in zip(g_pairs, ops.art_ray_grads(dplanes, dxp, params, t[seg], pairs.viewdirs[seg], degrees)):
+                dst[seg] = g
+        if not want_weights:
+            continue
+        grads, g_lat = ops.art_wgrad(planes, dplanes, d_seg, dxp, params, dict(zip(_LATENT_KEYS, codes)), degrees, packed_bwd=packed_bwd)
+        if total is None:
+            total = grads
+        else:      # plain adds in ascending k: a fixed order
+            for name in ops.ART_PARAM_ORDER:
+                total[name] += grads[name]
+        g_codes += [g_lat[key].reshape(c.shape) for key, c in zip(_LATENT_KEYS, codes)]
+    if not want_weights:
+        g_codes = None
+    elif total is None:
+        total = {name: torch.zeros_like(p) for name, p in params.items()}
+    g_pose = None
+    if rays is not None:
+        rays_o, viewdirs, objects = rays
+        g_pose = ops.scene_pose_grads(rays_o, rays_d, viewdirs, pairs, objects, g_pairs[0], g_pairs[1], g_pairs[2])
+    ctx.keep, ctx.released = None, True
+    return g_codes, total, g_pose
+
+
+class RenderLevelScenePoses(torch.autograd.Function):
+    """RenderLevelScene with gradients to the objects' poses too.  The forward is RenderLevelScene's, bit for bit:
+    it runs on the pair arrays aon_scene_pairs wrote, and the pose tensors are inputs for autograd's sake only -- their VALUES must be the
+    poses `pairs` was built from (`objects`, whose host copies the backward reads).  Backward: after each object's aon_art_bwd_chain,
+    aon_art_ray_grads on its segment; aon_scene_pose_grads once; each pose receives the plain derivative with respect to its (3, 4) entries
+    (no tangent-space projection), on its own device and dtype.  t, slot, the pairs' existence, near / far and the world direction's norm
+    are data.  The code and parameter gradients are RenderLevelScene's bits; when no code and no parameter needs a gradient,
+    aon_art_wgrad is not launched.
+
+    ``apply(pairs, t_vals, rays_o, rays_d, viewdirs, objects, white_bkgd, opts, packed_fwd, packed_bwd, degrees, *tensors)``: the WORLD rays,
+    objects as ops.scene_pairs took them, tensors = the K poses (3, 4), then as RenderLevelScene.  -> RenderLevelScene's five outputs."""
+
+    N_HEAD = 11
+
+    @staticmethod
+    def forward(ctx, pairs, t_vals, rays_o, rays_d, viewdirs, objects, white_bkgd, opts, packed_fwd, packed_bwd, degrees, *tensors):
+        K = pairs.K
+        poses = tensors[:K]
+        if len(list(objects)) != K or any(tuple(p.shape) != (3, 4) for p in poses):
+            raise ValueError(f"RenderLevelScenePoses: expected {K} objects and {K} poses of shape (3, 4)")
+        ctx.rays = (rays_o.detach(), viewdirs.detach(), list(objects))
+        ctx.pose_like = [(p.device, p.dtype) for p in poses]
+        return _scene_level_forward(ctx, "RenderLevelScenePoses", pairs, t_vals, rays_d, white_bkgd, opts, packed_fwd, packed_bwd, degrees, tensors[K:])
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, _g_weights):
+        K, need = len(ctx.pose_like), ctx.needs_input_grad
+        head = RenderLevelScenePoses.N_HEAD
+        want_poses, want_weights = any(need[head: head + K]), any(need[head + K:])
+        n_rest = len(need) - head - K
+        g_codes, total, g_pose = _scene_level_backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, want_weights, ctx.rays if want_poses else None)
+        ctx.rays = None
+        g_poses = (None,) * K
+        if want_poses:
+            g_poses = tuple(torch.cat([g_pose[k, :9].view(3, 3), g_pose[k, 9:].view(3, 1)], dim=1).to(device=dev, dtype=dt) if need[head + k] else None
+                            for k, (dev, dt) in enumerate(ctx.pose_like))
+        rest = tuple(g_codes) + tuple(total[name] for name in ops.ART_PARAM_ORDER) if want_weights else (None,) * n_rest
+        return (None,) * head + g_poses + rest

@@ -145,6 +145,11 @@ hipError_t launch_ray_grads(const RayGradLevel* levels, int nlevels, int64_t n_r
 hipError_t launch_vanilla_ray_grads(const RayGradLevel* levels, int nlevels, int64_t n_rays, int min_deg, int pos_levels, int view_levels,
                                     int white_bkgd, const float* rays_o, const float* rays_d, const float* viewdirs, float* g_rays_o,
                                     float* g_rays_d, float* g_viewdirs, hipStream_t stream);
+// one level of one block of rays, g_rays_d without the norm term: Wd0 / Wv0 the storages of
+// deformations_linear.0.weight / views_linear.0.weight, rec ray_grad_record_bytes(n_rays * S)
+hipError_t launch_art_ray_grads(const float* dplanes, const float* dxp, const float* Wd0, const float* Wv0, const float* t_vals,
+                                const float* viewdirs, int64_t n_rays, int S, int view_levels, float* rec, float* g_rays_o, float* g_rays_d,
+                                float* g_viewdirs, hipStream_t stream);
 
 // ---- aon_render.hip: rays, sampling, encodings, compositing, the training loss ----
 hipError_t launch_raygen(const float* c2w, int H, int W, float focal, const float* directions, int64_t pix_begin,

@@ -17,6 +17,8 @@
 //   ray_grad_reduce_kernel   one wavefront per ray.  Lane c < 32 sums component c of the ray's records in fp64, sample after sample in
 //                            ascending order; lane 32 + c the same values times t_i.  Then the norm term (aon_composite_grad.h with d alpha / d |d|)
 //                            and the view encoding's backward; every output is rounded to fp32 once.
+//   ray_grad_reduce_plain_kernel   the same reduce without the norm term, for ONE level of one block of rays from the stage calls (DESIGN.md
+//                            section 4.20: a scene's pair segments, whose interval lengths come from the WORLD direction).
 //   vanilla_ray_grad_sample_kernel   the frozen VANILLA network's records for the same reduce kernel (described at the kernel).
 #include "aon_art_common.h"
 #include "aon_composite_grad.h"
@@ -168,6 +170,49 @@ __device__ __forceinline__ double rg_norm_term(const RgReduceLevel& L, const int
   return rg_wsum(part);
 }
 
+// The record loop both reduce kernels share: `rec` the ray's first record at this lane's component (a record is one 128-byte line: lanes
+// 0..31 read it whole), `tv` its S sample positions; acc += r_i (weighted: t_i r_i) in fp64, sample after sample in ascending order.
+__device__ __forceinline__ void rg_sum_records(const float* rec, const float* tv, const int S, const bool weighted, double& acc) {
+  int i = 0;
+  for (; i + 8 <= S; i += 8) {
+    float r[8], t[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { r[k] = rec[(i + k) * kRecFloats]; t[k] = tv[i + k]; }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc += weighted ? (double)t[k] * (double)r[k] : (double)r[k];
+  }
+  for (; i < S; ++i) {
+    const float r = rec[i * kRecFloats], t = tv[i];
+    acc += weighted ? (double)t * (double)r : (double)r;
+  }
+}
+
+// The view encoding, backwards (both reduce kernels): lane kRecView + ci of `acc` holds the summed partial of column ci; columns
+// [v ; sin(2^l v) (level-major, xyz-minor) ; sin(2^l v + fp32(pi/2))] in ascending order, at the forward's rounded arguments.  Every lane
+// of the wave calls it and gets the same gv.
+__device__ __forceinline__ void rg_view_backward(const double acc, const float (&vd)[3], const int Lv, double (&gv)[3]) {
+  gv[0] = 0.0; gv[1] = 0.0; gv[2] = 0.0;
+  const int V = 3 + 6 * Lv;
+  for (int ci = 0; ci < V; ++ci) {
+    const double g = __shfl(acc, kRecView + ci);
+    int ax = ci;
+    double coef = 1.0;
+    if (ci >= 3) {
+      const int e = ci - 3, second = e >= 3 * Lv ? 1 : 0;
+      const int e2 = second ? e - 3 * Lv : e;
+      ax = e2 % 3;
+      const float scale = (float)(1 << (e2 / 3));
+      const float v = ax == 0 ? vd[0] : (ax == 1 ? vd[1] : vd[2]);
+      const float arg = __fadd_rn(__fmul_rn(v, scale), second ? AON_HALF_PI_F32 : 0.f);
+      coef = (double)scale * (double)cos_f32(arg);
+    }
+    const double term = coef * g;
+    gv[0] += ax == 0 ? term : 0.0;
+    gv[1] += ax == 1 ? term : 0.0;
+    gv[2] += ax == 2 ? term : 0.0;
+  }
+}
+
 template <int NB>
 __global__ void __launch_bounds__(256) ray_grad_reduce_kernel(RgReduceArgs a) {
   const int lane = (int)threadIdx.x & 63;
@@ -181,50 +226,44 @@ __global__ void __launch_bounds__(256) ray_grad_reduce_kernel(RgReduceArgs a) {
   for (int l = 0; l < a.nlevels; ++l) {
     const RgReduceLevel& L = a.lvl[l];
     const int S = L.S;
-    const float* rec = L.rec + ray * S * kRecFloats + c;   // a record is one 128-byte line: lanes 0..31 read it whole
-    const float* tv = L.t + ray * S;
-    int i = 0;
-    for (; i + 8 <= S; i += 8) {
-      float r[8], t[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { r[k] = rec[(i + k) * kRecFloats]; t[k] = tv[i + k]; }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) acc += weighted ? (double)t[k] * (double)r[k] : (double)r[k];
-    }
-    for (; i < S; ++i) {
-      const float r = rec[i * kRecFloats], t = tv[i];
-      acc += weighted ? (double)t * (double)r : (double)r;
-    }
+    rg_sum_records(L.rec + ray * S * kRecFloats + c, L.t + ray * S, S, weighted, acc);
     gn += rg_norm_term<NB>(L, ray, lane, dn, a.white_bkgd);
   }
-  // view encoding, backwards: columns [v ; sin(2^l v) (level-major, xyz-minor) ; sin(2^l v + fp32(pi/2))] in ascending order
   const float vd[3] = {a.viewdirs[ray * 3], a.viewdirs[ray * 3 + 1], a.viewdirs[ray * 3 + 2]};
-  double gv[3] = {0.0, 0.0, 0.0};
-  const int V = 3 + 6 * a.Lv;
-  for (int ci = 0; ci < V; ++ci) {
-    const double g = __shfl(acc, kRecView + ci);
-    int ax = ci;
-    double coef = 1.0;
-    if (ci >= 3) {
-      const int e = ci - 3, second = e >= 3 * a.Lv ? 1 : 0;
-      const int e2 = second ? e - 3 * a.Lv : e;
-      ax = e2 % 3;
-      const float scale = (float)(1 << (e2 / 3));
-      const float v = ax == 0 ? vd[0] : (ax == 1 ? vd[1] : vd[2]);
-      const float arg = __fadd_rn(__fmul_rn(v, scale), second ? AON_HALF_PI_F32 : 0.f);
-      coef = (double)scale * (double)cos_f32(arg);
-    }
-    const double term = coef * g;
-    gv[0] += ax == 0 ? term : 0.0;
-    gv[1] += ax == 1 ? term : 0.0;
-    gv[2] += ax == 2 ? term : 0.0;
-  }
+  double gv[3];
+  rg_view_backward(acc, vd, a.Lv, gv);
   const double tsum = __shfl(acc, (lane + 32) & 63);   // lanes 0..2: sum_i t_i g_x_i
   if (lane < 3) {
     const double dd = lane == 0 ? (double)d0 : (lane == 1 ? (double)d1 : (double)d2);
     const double n64 = sqrt((double)d0 * d0 + (double)d1 * d1 + (double)d2 * d2);
     a.g_o[ray * 3 + lane] = (float)acc;
     a.g_d[ray * 3 + lane] = (float)(tsum + (n64 > 0.0 ? gn * dd / n64 : 0.0));
+    a.g_v[ray * 3 + lane] = (float)(lane == 0 ? gv[0] : (lane == 1 ? gv[1] : gv[2]));
+  }
+}
+
+// The stage-level reduce of ONE level of one block of rays (include/aon_hip_scene_pose.h): ray_grad_reduce_kernel
+// without the norm term -- it reads no raw, no directions and no upstream gradients, and S has no limit of its own.
+struct RgPlainArgs {
+  const float* rec; const float* t; const float* viewdirs;
+  float* g_o; float* g_d; float* g_v;
+  int64_t n_rays;
+  int S, Lv;
+};
+
+__global__ void __launch_bounds__(256) ray_grad_reduce_plain_kernel(RgPlainArgs a) {
+  const int lane = (int)threadIdx.x & 63;
+  const int64_t ray = (int64_t)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  if (ray >= a.n_rays) return;
+  double acc = 0.0;
+  rg_sum_records(a.rec + ray * a.S * kRecFloats + (lane & 31), a.t + ray * a.S, a.S, lane >= 32, acc);
+  const float vd[3] = {a.viewdirs[ray * 3], a.viewdirs[ray * 3 + 1], a.viewdirs[ray * 3 + 2]};
+  double gv[3];
+  rg_view_backward(acc, vd, a.Lv, gv);
+  const double tsum = __shfl(acc, (lane + 32) & 63);   // lanes 0..2: sum_i t_i g_x_i
+  if (lane < 3) {
+    a.g_o[ray * 3 + lane] = (float)acc;
+    a.g_d[ray * 3 + lane] = (float)tsum;
     a.g_v[ray * 3 + lane] = (float)(lane == 0 ? gv[0] : (lane == 1 ? gv[1] : gv[2]));
   }
 }
@@ -427,6 +466,24 @@ hipError_t launch_ray_grads(const RayGradLevel* lv, int nlevels, int64_t n_rays,
   ray_grad_sample_kernel<<<dim3((unsigned)blk), dim3(256), 0, stream>>>(A);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   return launch_reduce(lv, nlevels, n_rays, view_levels, white_bkgd, rays_d, viewdirs, g_rays_o, g_rays_d, g_viewdirs, stream);
+}
+
+// One level of one block of rays from the stage calls' buffers: ray_grad_sample_kernel with ONE segment, then the
+// reduce without the norm term.  The caller (aon_art_ray_grads) has checked every argument.
+hipError_t launch_art_ray_grads(const float* dplanes, const float* dxp, const float* Wd0, const float* Wv0, const float* t_vals,
+                                const float* viewdirs, int64_t n_rays, int S, int view_levels, float* rec, float* g_rays_o, float* g_rays_d,
+                                float* g_viewdirs, hipStream_t stream) {
+  if (n_rays <= 0 || S < 1 || view_levels < 0 || view_levels > 4) return hipErrorInvalidValue;
+  const int64_t nvalid = n_rays * S, blk = (nvalid + 255) / 256;
+  if (blk > 0x7fffffff) return hipErrorInvalidValue;
+  RgSampleArgs A{};
+  A.nsegs = 1; A.V = 3 + 6 * view_levels;
+  A.seg[0] = RgSampleSeg{dplanes, dxp, Wd0, Wv0, rec, nvalid, 0};
+  ray_grad_sample_kernel<<<dim3((unsigned)blk), dim3(256), 0, stream>>>(A);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  const RgPlainArgs R{rec, t_vals, viewdirs, g_rays_o, g_rays_d, g_viewdirs, n_rays, S, view_levels};
+  ray_grad_reduce_plain_kernel<<<dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, stream>>>(R);
+  return hipGetLastError();
 }
 
 hipError_t launch_vanilla_ray_grads(const RayGradLevel* lv, int nlevels, int64_t n_rays, int min_deg, int pos_levels, int view_levels,

@@ -470,6 +470,95 @@ class LitNeRF_AutoDecoder(Harness):
             fitted.append(codes)
         return fitted, losses
 
+    def fit_scene_poses(self, batches, placements, steps: int, lr, fit_codes: bool = False, seed: int = 0):
+        """Recover where the K objects of ONE frame layout ARE from observed frames with the network FROZEN, alone or
+        together with their codes: `steps` Adam steps against mse over the levels (helper.train_loss), batch `i % len(batches)` at step i;
+        with fit_codes the loss also carries fit_scene_codes' 1e-4 * sum over objects and codes of mean ||code||.
+
+        batches, placements, seed: as fit_scene_codes; a placement's pose is the starting guess.  One 6-vector (omega, tau) is kept per
+        object and applied as R = exp([omega]x) R0, c = c0 + tau (ops.apply_pose_correction); the poses are rebuilt from it every step.
+        lr: one rate, or (pose rate, code rate).
+        -> (list of K fitted (3, 4) poses, list of K code dicts of (1, dim) tensors, per-step losses as one (steps,) device tensor); the host
+        synchronisations of a step are the read-backs of the poses (the pair kernel takes them from the host) and of the pair counts.
+
+        The network's requires_grad flags are cleared for the duration and restored.  The 6-vectors, their gradients and the Adam moments
+        are one flat (4, 6 K) buffer, the codes one flat (4, 288 K) buffer when fit_codes; each is stepped by ONE launch (aon_adam_step).
+        With fit_codes off no code and no weight requires grad, and a step launches no weight-gradient kernel
+        (autograd.RenderLevelScenePoses).  The pairs' existence, near / far and the sample positions are data: a pose moves only through the
+        samples a ray already has inside the object's box, so start close enough for the boxes to overlap the object."""
+        from ...scene import SceneObject, render_scene_grad
+
+        batches, _ = self._fit_args("fit_scene_poses", steps, batches)
+        lrs = tuple(lr) if isinstance(lr, (tuple, list)) else (lr, lr)
+        if len(lrs) != 2 or not all(isinstance(x, (int, float)) and not isinstance(x, bool) and x > 0 for x in lrs):
+            raise ValueError(f"fit_scene_poses: lr must be positive (one rate, or a pair for poses and codes), got {lr!r}")
+        keys = [k for k, _ in ops._LATENT_KEYS]
+        placed = self._placement_codes("fit_scene_poses", placements)
+        if not 1 <= len(placed) <= ops.SCENE_MAX_OBJECTS:
+            raise ValueError(f"fit_scene_poses: a scene holds 1 to {ops.SCENE_MAX_OBJECTS} objects, got {len(placed)}")
+        for b in batches:
+            if not all(k in b for k in ("rays_o", "rays_d", "viewdirs", "target")):
+                raise ValueError("fit_scene_poses: every batch needs 'rays_o', 'rays_d', 'viewdirs' (world) and 'target'")
+        dev = next(self.model.parameters()).device
+        K, width = len(placed), sum(d for _, d in ops._LATENT_KEYS)
+        pose_arena = torch.zeros((4, 6 * K), dtype=torch.float32, device=dev)      # rows: 6-vectors, gradients, exp_avg, exp_avg_sq
+        code_arena = torch.zeros((4, width * K), dtype=torch.float32, device=dev)   # (stepped only when fit_codes)
+        poses0, boxes, leaves = [], [], []
+        for j, (_, _, latents, pose, box) in enumerate(placed):
+            SceneObject(latents, pose, box)      # raises for a malformed code, pose or box before anything is copied
+            poses0.append(ops.check_pose(pose).to(dev))
+            boxes.append(box)
+            off, codes = j * width, {}
+            for k, d in ops._LATENT_KEYS:
+                view = code_arena[0, off: off + d].view(1, d)
+                view.copy_(latents[k].detach().reshape(1, d))
+                codes[k] = view.detach().requires_grad_(bool(fit_codes))
+                off += d
+            leaves.append(codes)
+        corrections = pose_arena[0].detach().requires_grad_(True)
+        wrt = [corrections] + ([codes[k] for codes in leaves for k in keys] if fit_codes else [])
+
+        def current_poses():
+            return [ops.apply_pose_correction(poses0[j], corrections[6 * j: 6 * j + 6]) for j in range(K)]
+
+        net_params = list(self.model.parameters())
+        flags = [p.requires_grad for p in net_params]
+        losses = torch.zeros(steps, dtype=torch.float32, device=dev)
+        try:
+            for p in net_params:
+                p.requires_grad_(False)
+            with torch.enable_grad():
+                for i in range(steps):
+                    b = batches[i % len(batches)]
+                    rays = {k: b[k].to(device=dev, dtype=torch.float32).reshape(-1, 3) for k in ("rays_o", "rays_d", "viewdirs")}
+                    target = b["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
+                    objects = [SceneObject(codes, pose, box) for codes, pose, box in zip(leaves, current_poses(), boxes)]
+                    levels = render_scene_grad(self.model, objects, rays, self.white_bkgd)
+                    loss = helper.train_loss([lvl[:3] for lvl in levels], target, (), 1e-4)[0]
+                    if fit_codes:
+                        loss = loss + 1e-4 * sum(torch.mean(torch.norm(codes[k], dim=0)) for codes in leaves for k in keys)
+                    grads = torch.autograd.grad(loss, wrt)
+                    losses[i] = loss.detach()
+                    pose_arena[1].copy_(grads[0])
+                    ops.adam_step(pose_arena[0], pose_arena[1], pose_arena[2], pose_arena[3], 0, pose_arena.shape[1], float(lrs[0]), 0.9, 0.999, 1e-8, i + 1)
+                    if fit_codes:
+                        code_arena[1].copy_(torch.cat([g.reshape(-1) for g in grads[1:]]))
+                        ops.adam_step(code_arena[0], code_arena[1], code_arena[2], code_arena[3], 0, code_arena.shape[1], float(lrs[1]), 0.9, 0.999,
+                                      1e-8, i + 1)
+        finally:
+            for p, f in zip(net_params, flags):
+                p.requires_grad_(f)
+        with torch.no_grad():
+            fitted_poses = [p.clone() for p in current_poses()]
+        fitted = []
+        for j in range(K):
+            off, codes = j * width, {}
+            for k, d in ops._LATENT_KEYS:
+                codes[k] = code_arena[0, off: off + d].view(1, d).clone()
+                off += d
+            fitted.append(codes)
+        return fitted_poses, fitted, losses
+
     @torch.no_grad()
     def render_scene(self, batch, placements, occupancy=None):
         """Several instances of the library in ONE frame (scene.render_scene): ``placements`` is a list of up to 16

@@ -2115,3 +2115,60 @@ def scene_art_mlp_fwd_occ(packed, smalls, grids, pairs: ScenePairs, t_vals):
         check(lib.aon_scene_art_mlp_fwd_occ(_pk(packed), small_arr, grid_arr, starts, _ptr(o), _ptr(d), _ptr(v), _ptr(t), K, S, _ptr(raw),
                                             _ptr(occupied), _ptr(ws), ws.numel(), _stream()), "aon_scene_art_mlp_fwd_occ")
     return raw, occupied
+
+
+# ------------------------------------------------------------------ pose gradients of scenes
+_RAY_REC = StreamCache()
+
+
+def art_ray_grads(dplanes, dxp, params: dict, t_vals, viewdirs, degrees=(0, 10, 4)):
+    """Stage-level ray gradients of ONE level of ONE block of rays on a frozen articulated network (include/aon_hip_scene_pose.h): dplanes
+    and dxp as art_bwd_chain returned them for the block, params the level's 40 parameters, t_vals (n, S) and viewdirs (n, 3) the block's
+    own -> (g_rays_o, g_rays_d, g_viewdirs), each (n, 3).  g_rays_d is sum_i t_i g_x_i alone: the norm term of a ray whose own |d| scales
+    the compositing is the caller's (a scene has none).  t is data."""
+    t, v = _f32(t_vals, "t_vals"), _f32(viewdirs.detach(), "viewdirs").reshape(-1, 3)
+    if t.dim() != 2 or v.shape[0] != t.shape[0]:
+        raise ValueError(f"art_ray_grads: expected t_vals (n, S) and viewdirs (n, 3), got {tuple(t.shape)} and {tuple(v.shape)}")
+    n, S = t.shape
+    dev = t.device
+    dp, dx = _f32(dplanes, "dplanes"), _f32(dxp, "dxp")
+    Np = plane_samples(dp)
+    if dp.dim() != 4 or tuple(dx.shape) != (Np, 4):
+        raise ValueError(f"art_ray_grads: expected the step-major gradient planes and dxp ({Np}, 4), got {tuple(dp.shape)} and {tuple(dx.shape)}")
+    outs = tuple(torch.empty((n, 3), dtype=torch.float32, device=dev) for _ in range(3))
+    if n == 0:      # nothing to launch (and no pointer to hand over)
+        return outs
+    if S < 1:
+        raise ValueError("art_ray_grads: t_vals needs at least one sample per ray")
+    tensors, parr = _art_param_array(params, degrees)
+    need = int(lib.aon_art_ray_grads_record_bytes(n, S))
+    if need < 0:
+        raise ValueError(f"art_ray_grads: {n} rays of {S} samples are more than 2^31 - 1 samples")
+    rec = _scratch(_RAY_REC, dev, need)
+    with torch.cuda.device(dev):
+        check(lib.aon_art_ray_grads(_ptr(dp), _ptr(dx), parr, _ptr(t), _ptr(v), n, S, Np, int(degrees[2]), _ptr(rec), rec.numel(), _ptr(outs[0]),
+                                    _ptr(outs[1]), _ptr(outs[2]), _stream()), "aon_art_ray_grads")
+    return outs
+
+
+def scene_pose_grads(rays_o, rays_d, viewdirs, pairs: ScenePairs, objects, g_o, g_d, g_v) -> torch.Tensor:
+    """The per-pair gradients g_o / g_d / g_v (P, 3) with respect to the pairs' object-frame origins, directions and view directions
+    (art_ray_grads on every segment of `pairs`) -> (K, 12): row k = [dL/dR (9, row-major) | dL/dc (3)] of object k's (3, 4) pose, the plain
+    derivative with respect to its 12 entries (include/aon_hip_scene_pose.h).  rays_o / rays_d / viewdirs: the WORLD rays `pairs` was built
+    from, objects: as scene_pairs took them.  An object without pairs gets zeros."""
+    o, d, v = (_f32(x.detach(), nm).reshape(-1, 3) for x, nm in ((rays_o, "rays_o"), (rays_d, "rays_d"), (viewdirs, "viewdirs")))
+    n, K, P, dev = pairs.n, pairs.K, pairs.P, o.device
+    gs = [_f32(x, nm) for x, nm in ((g_o, "g_o"), (g_d, "g_d"), (g_v, "g_v"))]
+    if any(x.shape[0] != n for x in (o, d, v)) or any(tuple(x.shape) != (P, 3) for x in gs):
+        raise ValueError(f"scene_pose_grads: expected world rays ({n}, 3) and per-pair gradients ({P}, 3), got "
+                         f"{[tuple(x.shape) for x in (o, d, v)]} and {[tuple(x.shape) for x in gs]}")
+    arr, k = _scene_objects(objects)
+    if k != K:
+        raise ValueError(f"scene_pose_grads: the pairs were built for {K} objects, got {k}")
+    g_pose = torch.empty((K, 12), dtype=torch.float32, device=dev)
+    some = P > 0
+    with torch.cuda.device(dev):
+        check(lib.aon_scene_pose_grads(_ptr(o) if some else None, _ptr(d) if some else None, _ptr(v) if some else None, n,
+                                       _ptr(pairs.ray) if some else None, _ptr(pairs.offsets), arr, K, P, *(_ptr(x) if some else None for x in gs),
+                                       _ptr(g_pose), _stream()), "aon_scene_pose_grads")
+    return g_pose

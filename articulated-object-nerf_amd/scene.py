@@ -1,7 +1,7 @@
 """Scenes of several posed articulated objects in one frame: one ``NeRF_AE_Art`` and K <= 16 objects, each with its
 own codes, rigid object-to-world pose and box, rendered with correct mutual occlusion -- the approach of Neural Scene Graphs (Ost et al.): a
 ray-box test per object, samples inside each box, one sorted merge along the ray.  ``render_scene`` is inference only; ``render_scene_grad``
- is the same frame with gradients to the objects' codes and the network's weights.
+(DESIGN.md sections 4.18, 4.20) is the same frame with gradients to the objects' codes, the network's weights and the objects' poses.
 
 Per chunk of rays: ``ops.scene_pairs`` pairs rays with the boxes they cross (one host read-back: the pair counts), the existing per-ray-bounds
 sampler, MLP kernel and inverse-CDF kernel run on the pairs -- the MLP once per object segment with that object's per-call block -- and
@@ -23,7 +23,12 @@ class SceneObject:
     ``pose`` the (3, 4) rigid object-to-world matrix [R | c] (orthonormal R, det > 0: no scale), ``box`` the axis-aligned box in the
     object's frame (a side length, or (lo, hi): ``ops._box3``), ``grid`` an optional ``ops.OccupancyGrid`` built under the same latents in the
     object's frame (``occupancy.build_occupancy``).  The grid's extent must contain the box: a sample outside the grid counts as empty, so
-    the part of a box that sticks out of it would be silently cut away."""
+    the part of a box that sticks out of it would be silently cut away.
+
+    ``pose`` is validated and kept as a detached fp32 host copy (``ob.pose``), which every kernel reads.  A pose TENSOR that carries autograd
+    history (a leaf that requires grad, or the result of ``ops.apply_pose_correction`` on one) is kept beside it as ``ob.pose_tensor``
+    (None otherwise): ``render_scene_grad`` hands the pose's gradient back to it.  The copy is taken here: build the
+    object again after changing the tensor's values."""
 
     def __init__(self, latents: dict, pose, box, grid=None):
         if not isinstance(latents, dict) or set(latents) != set(_LATENT_WIDTHS):
@@ -33,6 +38,7 @@ class SceneObject:
                 raise ValueError(f"SceneObject: latents[{key!r}] must be a tensor of {width} values")
         self.latents = latents
         self.pose = ops.check_pose(pose, "SceneObject: pose")
+        self.pose_tensor = pose if isinstance(pose, torch.Tensor) and pose.requires_grad else None
         lo, hi = ops._box3(box)      # raises for a malformed box
         self.box = box
         if grid is not None:
@@ -119,13 +125,17 @@ def render_scene(model, objects, rays, white_bkgd, chunk: int = 65536, randomize
 def render_scene_grad(model, objects, rays, white_bkgd, randomized: bool = False):
     """``render_scene`` with autograd history: -> ``[(rgb (N, 3), acc (N,), depth (N,), obj_acc (N, K))]`` per level,
     the bits ``render_scene`` returns, whose gradients reach every object's three codes (``SceneObject.latents`` may hold leaf tensors that
-    require grad) and the network's weights.  The pairs, the sample positions of both levels (the fine draws come from the merged coarse
-    weights, detached: helper.py:249) and the rays are data: no gradient reaches a pose or a ray.
+    require grad), the network's weights and -- for every object whose ``pose_tensor`` is set (``SceneObject``) -- the object's (3, 4) pose
+    (the plain derivative with respect to its 12 entries; differentiate ``ops.apply_pose_correction`` for a
+    tangent-space step; the levels' contributions add).  The pairs' existence, near / far, the sample positions of both levels (the fine
+    draws come from the merged coarse weights, detached: helper.py:249), the world direction's norm and the world rays are data: no
+    gradient reaches a ray or the camera.  Without a pose tensor the path and the bits are those of section 4.18.
 
     One chunk: the activation planes of every pair (13.8 KB per sample) live until the backward, and are released by it -- a second backward
     through the same forward raises.  Dense only: an object carrying a grid is refused (the training forward has no gather instance).  A
-    frozen network still pays the full weight-gradient stage."""
-    from .autograd import RenderLevelScene
+    frozen network still pays the full weight-gradient stage, unless a pose tensor is present and no code and no weight requires grad: a
+    pose-only backward launches no weight-gradient kernel."""
+    from .autograd import RenderLevelScene, RenderLevelScenePoses
 
     if randomized:
         raise ValueError("scene gradients sample without randomness: randomized=True is refused")
@@ -143,11 +153,17 @@ def render_scene_grad(model, objects, rays, white_bkgd, randomized: bool = False
     with torch.no_grad():
         pairs = ops.scene_pairs(o, d, v, objects)
         t, _ = ops.sample_along_rays(pairs.rays_o, pairs.rays_d, model.num_coarse_samples, pairs.near, pairs.far, want_coords=False, lindisp=model.lindisp)
+    with_poses = any(ob.pose_tensor is not None for ob in objects)
+    poses = [ob.pose_tensor if ob.pose_tensor is not None else ob.pose for ob in objects]
     levels = []
     for level, mlp in enumerate(mlps):
         # fresh streams: the backward reads them again, and a later forward must not overwrite what this graph still needs
-        rgb, acc, depth, obj_acc, weights = RenderLevelScene.apply(pairs, t, d, bool(white_bkgd), model._opts, mlp.packed(True), mlp.packed_bwd(True),
-                                                                   mlp.degrees, *codes, *mlp.ordered_params())
+        if with_poses:
+            rgb, acc, depth, obj_acc, weights = RenderLevelScenePoses.apply(pairs, t, o, d, v, objects, bool(white_bkgd), model._opts, mlp.packed(True),
+                                                                            mlp.packed_bwd(True), mlp.degrees, *poses, *codes, *mlp.ordered_params())
+        else:
+            rgb, acc, depth, obj_acc, weights = RenderLevelScene.apply(pairs, t, d, bool(white_bkgd), model._opts, mlp.packed(True), mlp.packed_bwd(True),
+                                                                       mlp.degrees, *codes, *mlp.ordered_params())
         levels.append((rgb, acc, depth, obj_acc))
         if level + 1 < len(mlps):
             with torch.no_grad():

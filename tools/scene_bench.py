@@ -23,7 +23,11 @@ device events around the whole step), the device time of ops.scene_composite_bwd
 of it, and for K = 1 the step of the same sample count through NeRF_AE_Art.forward + backward on the one object's pairs (its object-frame
 rays with their per-ray near / far), measured in the same run.
 
-    python tools/scene_bench.py [--reps 5] [--occupancy] [--grad] [--out profiles/scene_bench.json]
+--grad --poses adds a "grad_poses" list instead: the same rays and objects, a pose-only step on the frozen network
+(gradients to every object's (3, 4) pose, no weight-gradient stage) beside the code-and-weight step of --grad in the same run, device
+events, and the device time and share of ops.art_ray_grads and ops.scene_pose_grads inside the pose-only step.
+
+    python tools/scene_bench.py [--reps 5] [--occupancy] [--grad [--poses]] [--out profiles/scene_bench.json]
 """
 import argparse
 import json
@@ -228,11 +232,69 @@ def grad_records(model, ro, vd, reps, dev):
     return recs
 
 
+def pose_records(model, ro, vd, reps, dev):
+    """the --grad --poses legs -> one record per K: a pose-only step on a frozen network beside the code-and-weight
+    step of section 4.18, the same rays and objects in the same run; device events, median of `reps`"""
+    idx = (torch.arange(GRAD_RAYS, device=dev) * (ro.shape[0] // GRAD_RAYS)).long()
+    rays = {"rays_o": ro[idx].contiguous(), "rays_d": vd[idx].contiguous(), "viewdirs": vd[idx].contiguous()}
+    target = syn.seeded_uniform(5, GRAD_RAYS, 3).to(dev)
+    keys = ("density", "color", "articulation")
+    params = [p for p in model.parameters()]
+    nets = [p for m in (model.coarse_mlp, model.fine_mlp) for p in m.ordered_params()]
+    loss_of = lambda levels: sum(torch.mean((lv[0] - target) ** 2) + 0.1 * lv[1].mean() + 0.05 * lv[2].mean() + 0.2 * (lv[3] ** 2).mean() for lv in levels)  # noqa: E731
+    recs = []
+    for K in (1, 3):
+        base = make_scene(K, dev)
+        coded = [scene.SceneObject({k: v.clone().requires_grad_(True) for k, v in ob.latents.items()}, ob.pose, ob.box) for ob in base]
+        posed = [scene.SceneObject(ob.latents, ob.pose.clone().requires_grad_(True), ob.box) for ob in base]
+
+        def weight_step():
+            return torch.autograd.grad(loss_of(scene.render_scene_grad(model, coded, rays, True)), [ob.latents[k] for ob in coded for k in keys] + nets)
+
+        def pose_step():
+            return torch.autograd.grad(loss_of(scene.render_scene_grad(model, posed, rays, True)), [ob.pose_tensor for ob in posed])
+
+        def timed(step, frozen, spies=()):
+            flags = [p.requires_grad for p in params]
+            reals = {name: getattr(ops, name) for name in spies}
+            runs = []
+            try:
+                for p in params:
+                    p.requires_grad_(not frozen)
+                step()                                     # warm-up
+                for _ in range(reps):
+                    st = Stages()
+                    for name, real in reals.items():
+                        setattr(ops, name, (lambda real, name: lambda *a, **kw: st.run(name, lambda: real(*a, **kw)))(real, name))
+                    st.run("step", step)
+                    runs.append(st.totals())
+            finally:
+                for name, real in reals.items():
+                    setattr(ops, name, real)
+                for p, f in zip(params, flags):
+                    p.requires_grad_(f)
+            return {k: statistics.median(r[k] for r in runs) for k in runs[0]}
+
+        w = timed(weight_step, False)
+        p = timed(pose_step, True, ("art_ray_grads", "scene_pose_grads"))
+        with torch.no_grad():
+            pairs = ops.scene_pairs(rays["rays_o"], rays["rays_d"], rays["viewdirs"], base)
+        rec = {"rays": GRAD_RAYS, "samples": "65 + 193", "objects": K, "reps": reps, "pairs": pairs.P, "mlp_samples": pairs.P * (65 + 193),
+               "ms_code_and_weight_step_device": round(w["step"], 3), "ms_pose_only_step_device": round(p["step"], 3),
+               "pose_only_vs_code_and_weight": round(p["step"] / w["step"], 4),
+               "ms_art_ray_grads": round(p["art_ray_grads"], 4), "ms_scene_pose_grads": round(p["scene_pose_grads"], 4),
+               "share_art_ray_grads": round(p["art_ray_grads"] / p["step"], 5), "share_scene_pose_grads": round(p["scene_pose_grads"] / p["step"], 5)}
+        print(json.dumps(rec), flush=True)
+        recs.append(rec)
+    return recs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--occupancy", action="store_true", help="add the occupancy-grid legs (DESIGN.md section 4.17)")
     ap.add_argument("--grad", action="store_true", help="measure gradients through scenes instead (DESIGN.md section 4.18)")
+    ap.add_argument("--poses", action="store_true", help="with --grad: the pose-only step beside the code-and-weight step (DESIGN.md section 4.20), key grad_poses")
     ap.add_argument("--objects", type=int, nargs="+", default=[1, 3, 8])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_bench.json"))
     args = ap.parse_args()
@@ -248,7 +310,10 @@ def main():
     n = ro.shape[0]
     if args.grad:
         doc = json.load(open(args.out)) if os.path.exists(args.out) else {"tool": "tools/scene_bench.py", "device": torch.cuda.get_device_name(0)}
-        doc["grad"] = grad_records(model, ro, vd, args.reps, dev)
+        if args.poses:
+            doc["grad_poses"] = pose_records(model, ro, vd, args.reps, dev)
+        else:
+            doc["grad"] = grad_records(model, ro, vd, args.reps, dev)
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(doc, f, indent=1)

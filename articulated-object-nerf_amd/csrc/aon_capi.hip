@@ -49,7 +49,8 @@ const char* make_geo(const aon_render_opts* o, Geo& g, bool general_engine) {
   g.noise[0] = d.noise_c; g.noise[1] = d.noise_f; g.noise_std = d.noise_std;
   g.rgb_scale = d.rgb_scale; g.rgb_shift = d.rgb_shift; g.sigma_bias = d.sigma_bias;
   g.min_deg = d.min_deg_point; g.max_deg = d.max_deg_point; g.deg_view = d.deg_view;
-  if (general_engine) { g.min_deg = 0; g.max_deg = 10; g.deg_view = 4; g.other_degrees = false; return nullptr; }
+  if (general_engine) { g.min_deg = 0; g.max_deg = 10; g.deg_view = 4; g.other_degrees = false; return nullptr; }   // (its rule: make_gg)
+  if (g.min_deg < -32 || g.max_deg > 32) return "min_deg_point / max_deg_point must lie in [-32, 32]";
   if (g.max_deg < g.min_deg || g.max_deg - g.min_deg > 10 || g.deg_view < 0 || g.deg_view > 4)
     return "the fused kernels hold up to 10 position and 4 view frequency levels (other degrees: aon_grender_*)";
   g.other_degrees = !(g.min_deg == 0 && g.max_deg == 10 && g.deg_view == 4);
@@ -466,6 +467,8 @@ static const char* art_degrees_ok(int min_deg_point, int max_deg_point, int deg_
   const int L = max_deg_point - min_deg_point;
   if (L < 0 || L > 10 || deg_view < 0 || deg_view > 4) return "up to 10 position and 4 view frequency levels";
   if (min_deg_point < -32 || max_deg_point > 32) return "min_deg_point / max_deg_point must lie in [-32, 32]";
+  // the fused kernels encode the deformed point with the short sine (sin_f32<false>, aon_common.h): 2^(max_deg_point - 1) |x'| < 2^19
+  if (max_deg_point > 16) return "the articulated kernels' in-register encoding holds for max_deg_point <= 16";
   return nullptr;
 }
 

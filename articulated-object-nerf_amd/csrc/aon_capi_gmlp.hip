@@ -27,6 +27,7 @@ const char* make_gg(const aon_mlp_geometry* g, GG& o) {
   if (g->netdepth < 1 || g->netwidth < 1 || g->netdepth_condition < 1 || g->netwidth_condition < 1 || g->skip_layer < 1 || g->input_ch < 1 ||
       g->input_ch_view < 1 || g->num_rgb_channels < 1 || g->num_density_channels < 1 || g->max_deg_point < g->min_deg_point || g->deg_view < 0)
     return "bad NeRFMLP geometry";
+  if (g->min_deg_point < -32 || g->max_deg_point > 32) return "min_deg_point / max_deg_point must lie in [-32, 32]";
   if (g->netdepth > 64 || g->netdepth_condition > 64 || g->netwidth > 4096 || g->netwidth_condition > 4096) return "NeRFMLP geometry too large";
   o.min_deg = g->min_deg_point; o.max_deg = g->max_deg_point; o.deg_view = g->deg_view; o.in_ch = g->input_ch; o.in_ch_view = g->input_ch_view;
   o.P = ((g->max_deg_point - g->min_deg_point) * 2 + 1) * g->input_ch;

@@ -16,44 +16,89 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // (models/vanilla_nerf/helper.py:139).
 #define AON_HALF_PI_F32 1.57079637050628662109375f
 
-// sin(x) for |x| < ~1e5, max abs error 9.3e-8 against fp64 (|x| <= 3200): three-term Cody-Waite reduction by
-// multiples of pi/2 with FMA, then degree-7/8 minimax polynomials on [-pi/4, pi/4].  Branch-free (the library
-// sinf carries a Payne-Hanek slow path that costs registers and divergence and is never taken here: the
-// largest argument on this path is 2^9 * 6 + pi/2).
-__device__ __forceinline__ float sin_f32(float x) {
-  const float ax = __builtin_fabsf(x);
+// Argument reduction by multiples of pi/2, shared by sin_f32 and cos_f32: ax = |x| -> the quadrant q (only q mod 4 matters) and the
+// reduced argument r = ax - q pi/2, |r| <= pi/4 (+ a rounding).
+//   ax < 2^19: three-term Cody-Waite reduction with FMA; k = rint(ax 2/pi) < 2^19, and the three terms of pi/2 carry 22 / 21 / 20
+//     significant bits.  Beyond 2^19 the error of this r grows (on the device 2.9e-7 absolute on the sine in [2^20, 2^21)), and from
+//     k >= 2^23 on the fp32 k is off by whole quadrants.
+//   ax >= 2^19, every larger finite fp32: an exact quadrant reduction (Payne-Hanek).  ax = ia 2^(ex - 158) with the 32-bit integer
+//     ia = mantissa << 8; ia * (2/pi) is formed modulo 4 from the 96 bits of 2/pi that can reach the two quadrant bits and the 62
+//     fraction bits below them (higher bits of 2/pi give multiples of 4, lower ones less than 2^-62), rounded to the nearest
+//     quadrant, and the signed fraction times pi/2 is rounded once, through fp64: r is the correctly rounded reduced argument up to
+//     2^-31 relative, at any cancellation an fp32 argument can produce (the closest an fp32 comes to a multiple of pi/2 is ~2^-29
+//     relative).  +-inf -> NaN (ex == 255 below); a NaN fails the comparison and stays NaN through the fast path.
+// ACCURATE = false: the first form alone, for |x| < 2^19.  The fused MLP kernels (aon_mlp_core.h's in-register encodings, the
+// articulated training chain's derivative) take it: they run at the register limit (256 VGPRs, one wave per SIMD), where the second
+// form's branch changes the allocation of every instance, and what they encode stays inside the domain -- the default degrees' 2^9 |x| +
+// pi/2, and the articulated network's 2^(max_deg_point - 1) |x'| with max_deg_point <= 16 (art_degrees_ok), i.e. |x'| < 16 at the
+// limit.  pos_enc_kernel (the stage call, the layer-wise engine, the vanilla network at other degrees) and the ray-gradient kernels'
+// derivative of the encoding (aon_ray_grad.hip) take the accurate form.
+template <bool ACCURATE>
+__device__ __forceinline__ float reduce_pio2_f32(float ax, int& q) {
+  if (ACCURATE && ax >= 0x1p19f) {
+    const uint32_t bits = __builtin_bit_cast(uint32_t, ax);
+    const int ex = (int)(bits >> 23);                      // 146 .. 254 (255: inf)
+    const uint32_t ia = (bits << 8) | 0x80000000u;
+    // 2/pi = 0.A2F9836E 4E441529 FC2757D1 F534DDC0 DB629599 3C439041 ... (hex), with a zero word in front so that the window may
+    // start above the binary point: it starts at bit ex - 128 of this string (18 .. 126) and is 96 bits long
+    const int start = ex - 128, i = start >> 5, sh = start & 31;
+    const uint32_t t0 = i == 0 ? 0u : i == 1 ? 0xA2F9836Eu : i == 2 ? 0x4E441529u : 0xFC2757D1u;
+    const uint32_t t1 = i == 0 ? 0xA2F9836Eu : i == 1 ? 0x4E441529u : i == 2 ? 0xFC2757D1u : 0xF534DDC0u;
+    const uint32_t t2 = i == 0 ? 0x4E441529u : i == 1 ? 0xFC2757D1u : i == 2 ? 0xF534DDC0u : 0xDB629599u;
+    const uint32_t t3 = i == 0 ? 0xFC2757D1u : i == 1 ? 0xF534DDC0u : i == 2 ? 0xDB629599u : 0x3C439041u;
+    const uint32_t hi = (uint32_t)((((uint64_t)t0 << 32) | t1) >> (32 - sh));
+    const uint32_t mid = (uint32_t)((((uint64_t)t1 << 32) | t2) >> (32 - sh));
+    const uint32_t lo = (uint32_t)((((uint64_t)t2 << 32) | t3) >> (32 - sh));
+    // bits 32 .. 95 of the 128-bit product ia * (hi:mid:lo): two quadrant bits, then the fraction
+    const uint64_t p = (((uint64_t)ia * lo) >> 32) + (uint64_t)ia * mid + (((uint64_t)ia * hi) << 32);
+    q = (int)((p + 0x2000000000000000ull) >> 62);          // to the nearest quadrant
+    const double f = (double)(int64_t)(p << 2);             // the signed fraction, in units of 2^-64
+    const float r = (float)(f * 0x1.921fb54442d18p-64);    // * pi/2
+    return ex == 255 ? __builtin_nanf("") : r;
+  }
   const float k = __builtin_rintf(ax * 0.636619747f);
-  const int q = (int)k;
+  q = (int)k;
   float r = __builtin_fmaf(k, -0x1.921fb4p+0f, ax);   // pi/2 = 0x3fc90fda + 0x33a22168 + 0x27c234c4
   r = __builtin_fmaf(k, -0x1.4442d0p-24f, r);
   r = __builtin_fmaf(k, -0x1.846988p-48f, r);
+  return r;
+}
+
+// sin and cos of a reduced argument |r| <= pi/4: degree-7/8 minimax polynomials
+__device__ __forceinline__ void sincos_poly_f32(float r, float& s, float& c) {
   const float z = r * r;
   float ps = __builtin_fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f);
   ps = __builtin_fmaf(z, ps, -1.6666654611e-1f);
-  const float s = __builtin_fmaf(r * z, ps, r);
+  s = __builtin_fmaf(r * z, ps, r);
   float pc = __builtin_fmaf(z, 2.443315711809948e-5f, -1.388731625493765e-3f);
   pc = __builtin_fmaf(z, pc, 4.166664568298827e-2f);
-  const float c = __builtin_fmaf(z * z, pc, __builtin_fmaf(z, -0.5f, 1.0f));
+  c = __builtin_fmaf(z * z, pc, __builtin_fmaf(z, -0.5f, 1.0f));
+}
+
+// sin(x) for every fp32 x: reduce_pio2_f32, then the polynomials.  Against fp64 sin of the same fp32 argument the absolute error is
+// at most 9.3e-8 for |x| < 2^19 -- the bits of this range are those of the branch-free form the function had while the default
+// encodings were the only ones (their largest argument is 2^9 * 6 + pi/2) -- and below 4 * 2^-24, the bound OpenCL sets for sin, for
+// every larger finite x (measured: 9.30e-8); +-inf and NaN give NaN, as torch.sin does.  tests/test_hip_device_math.py sweeps every
+// binade on the device.  (The library sinf would serve the large arguments too; its small-argument path has other bits, and one
+// function with one reduction is what cos_f32 can share.)  sin_f32<false>: |x| < 2^19 only, see reduce_pio2_f32.
+template <bool ACCURATE = true>
+__device__ __forceinline__ float sin_f32(float x) {
+  int q;
+  const float r = reduce_pio2_f32<ACCURATE>(__builtin_fabsf(x), q);
+  float s, c;
+  sincos_poly_f32(r, s, c);
   float res = (q & 1) ? c : s;
   res = (q & 2) ? -res : res;
   return x < 0.f ? -res : res;
 }
 
 // cos(x) with the same reduction / polynomials (the derivative of the encoding in the backward pass).
+template <bool ACCURATE = true>
 __device__ __forceinline__ float cos_f32(float x) {
-  const float ax = __builtin_fabsf(x);
-  const float k = __builtin_rintf(ax * 0.636619747f);
-  const int q = (int)k;
-  float r = __builtin_fmaf(k, -0x1.921fb4p+0f, ax);
-  r = __builtin_fmaf(k, -0x1.4442d0p-24f, r);
-  r = __builtin_fmaf(k, -0x1.846988p-48f, r);
-  const float z = r * r;
-  float ps = __builtin_fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f);
-  ps = __builtin_fmaf(z, ps, -1.6666654611e-1f);
-  const float s = __builtin_fmaf(r * z, ps, r);
-  float pc = __builtin_fmaf(z, 2.443315711809948e-5f, -1.388731625493765e-3f);
-  pc = __builtin_fmaf(z, pc, 4.166664568298827e-2f);
-  const float c = __builtin_fmaf(z * z, pc, __builtin_fmaf(z, -0.5f, 1.0f));
+  int q;
+  const float r = reduce_pio2_f32<ACCURATE>(__builtin_fabsf(x), q);
+  float s, c;
+  sincos_poly_f32(r, s, c);
   // cos(|x|) = cos(r + q pi/2): q=0: c, 1: -s, 2: -c, 3: s
   float res = (q & 1) ? s : c;
   return ((q + 1) & 2) ? -res : res;
@@ -61,8 +106,8 @@ __device__ __forceinline__ float cos_f32(float x) {
 
 // torch Softplus(beta=1, threshold=20): x > 20 ? x : log1p(exp(x)), written as max(x, 0) + log1p(z), z = exp(-|x|) in (0, 1]
 // (above 20 the second term is below half an ulp of x: the threshold needs no branch).  log1p(z) = z * P(z) with P the degree-10
-// Chebyshev interpolant of log1p(z)/z on [0, 1] (1.1e-7 relative in fp32 Horner form, tests/diag/diag_sigmoid.py checks the
-// function on the device); z straight from the transcendental unit.  ~20 instructions against ~70 with the library expf and
+// Chebyshev interpolant of log1p(z)/z on [0, 1] (1.1e-7 relative in fp32 Horner form; tests/test_hip_device_math.py checks the
+// function on the device over [-100, 100]); z straight from the transcendental unit.  ~20 instructions against ~70 with the library expf and
 // log1pf, which had the articulated compositing at twice the vanilla kernel's instruction count.  NaN stays NaN (through z),
 // +inf -> +inf, -inf -> 0.
 __device__ __forceinline__ float softplus_f32(float x) {

@@ -682,7 +682,7 @@ __device__ __forceinline__ void encode_pos_scaled(const float (&x)[3], int h, co
 #pragma unroll
   for (int rho = 0; rho < 30; ++rho) {
     const float xb = __fmul_rn(x[rho % 3], sc[rho / 3]);
-    E[rho >> 4][rho & 15] = sin_f32(__fadd_rn(xb, phase));
+    E[rho >> 4][rho & 15] = sin_f32<false>(__fadd_rn(xb, phase));
   }
   E[1][14] = h ? x[2] : x[0];
   E[1][15] = h ? 0.f : x[1];
@@ -693,7 +693,7 @@ __device__ __forceinline__ void encode_pos(const float (&x)[3], int h, f32x16 (&
 #pragma unroll
   for (int rho = 0; rho < 30; ++rho) {
     const float xb = __fmul_rn(x[rho % 3], (float)(1 << (rho / 3)));
-    E[rho >> 4][rho & 15] = sin_f32(__fadd_rn(xb, phase));
+    E[rho >> 4][rho & 15] = sin_f32<false>(__fadd_rn(xb, phase));
   }
   E[1][14] = h ? x[2] : x[0];
   E[1][15] = h ? 0.f : x[1];
@@ -704,7 +704,7 @@ __device__ __forceinline__ void encode_view(const float (&vd)[3], int h, f32x16&
 #pragma unroll
   for (int rho = 0; rho < 12; ++rho) {
     const float xb = __fmul_rn(vd[rho % 3], (float)(1 << (rho / 3)));
-    V[rho] = sin_f32(__fadd_rn(xb, phase));
+    V[rho] = sin_f32<false>(__fadd_rn(xb, phase));
   }
   V[12] = h ? vd[2] : vd[0];
   V[13] = h ? 0.f : vd[1];

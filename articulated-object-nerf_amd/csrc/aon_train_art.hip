@@ -314,7 +314,7 @@ __global__ void __launch_bounds__(256) art_bwd_chain_kernel(ArtBwdArgs args) {
     for (int rho = 0; rho < 30; ++rho) {
       const float scale = sm[kA_ESC + rho / 3];   // 2^(min_deg_point + l), 0 for a level the network lacks (aon_art_prepare)
       const float arg = __fadd_rn(__fmul_rn(xd[rho % 3], scale), phase);
-      const float c = cos_f32(arg);  // d/d(arg) sin(arg), at the forward's own (rounded) argument
+      const float c = cos_f32<false>(arg);  // d/d(arg) sin(arg), at the forward's own (rounded) argument
       dx[rho % 3] = __builtin_fmaf(scale * c, dE[rho >> 4][rho & 15], dx[rho % 3]);
     }
     if (h) dx[2] += dE[1][14]; else { dx[0] += dE[1][14]; dx[1] += dE[1][15]; }

@@ -714,8 +714,9 @@ def art_param_shapes(degrees=(0, 10, 4)) -> dict:
     """Parameter shapes of the articulated NeRFMLP built with (min_deg_point, max_deg_point, deg_view) and default widths
     (model_autodecoder.py:60-170): the three concatenating layers follow P = 3 + 6 (max - min), V = 3 + 6 deg_view."""
     lo, hi, dv = (int(x) for x in degrees)
-    if not (0 <= hi - lo <= 10 and 0 <= dv <= 4 and -32 <= lo and hi <= 32):
-        raise NotImplementedError(f"articulated NeRFMLP with degrees {tuple(degrees)}: the kernels hold up to 10 position and 4 view frequency levels")
+    if not (0 <= hi - lo <= 10 and 0 <= dv <= 4 and -32 <= lo and hi <= 16):
+        raise NotImplementedError(f"articulated NeRFMLP with degrees {tuple(degrees)}: the kernels hold up to 10 position and 4 view frequency levels, "
+                                  "min_deg_point >= -32 and max_deg_point <= 16 (the in-register encoding's sine holds for arguments below 2^19)")
     P, V = 3 + 6 * (hi - lo), 3 + 6 * dv
     shapes = dict(ART_PARAM_SHAPES)
     shapes["pts_linears.0.weight"] = (256, P + 128)

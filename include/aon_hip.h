@@ -280,7 +280,8 @@ int64_t aon_art_packed_bytes(void);
 int64_t aon_art_small_bytes(void);
 int aon_pack_art_mlp(const float* const* params_host, void* packed, void* stream);
 /* Round 4: the articulated network at other encoding degrees (NeRFMLP(min_deg_point, max_deg_point, deg_view), model_autodecoder.py:60-170;
- * at most 10 position and 4 view frequency levels, default widths).  The streams keep the kernels' 63 / 27-wide slots with zero weight in
+ * at most 10 position and 4 view frequency levels, default widths; -32 <= min_deg_point, max_deg_point <= 16: the kernels encode the
+ * deformed point in registers with a sine that holds for 2^(max_deg_point - 1) |x'| < 2^19).  The streams keep the kernels' 63 / 27-wide slots with zero weight in
  * the levels the network lacks (row strides of pts_linears.0 / .5 and views_linear.0 follow P = 3 + 6 L, V = 3 + 6 Lv), and the small
  * block carries the ten encoding scales 2^(min_deg_point + l) the kernels multiply the DEFORMED point by (0 for a missing level), so
  * every aon_art_* call works unchanged on streams / blocks made by the _deg forms; aon_art_render_bwd_ex and aon_art_wgrad_deg take the

@@ -243,6 +243,41 @@ def test_constructor_option_entry_points_validate_without_gpu():
     assert b"input_ch" in lib.aon_last_error()
 
 
+def test_encoding_degrees_outside_the_fp32_scales_are_refused():
+    """min_deg_point / max_deg_point outside [-32, 32] are refused by every geometry check -- the layer-wise engine's, the fused vanilla
+    route's, the articulated pack calls' -- and the articulated kernels, whose in-register encoding uses the short sine (|arg| < 2^19,
+    csrc/aon_common.h), stop at max_deg_point = 16.  The degrees are checked before anything is read or launched."""
+    import ctypes as C
+
+    import pytest
+
+    from aon_amd import _lib, ops
+
+    lib = _lib.lib
+    g = _lib.MlpGeometryC()
+    for lo, hi, ok in ((-32, -22, True), (22, 32, True), (0, 32, True), (23, 33, False), (-33, -23, False), (-40, 40, False)):
+        lib.aon_mlp_geometry_init(C.byref(g))
+        g.min_deg_point, g.max_deg_point = lo, hi
+        if ok:
+            assert lib.aon_gmlp_param_count(C.byref(g)) == 24, (lo, hi)
+        else:
+            assert lib.aon_gmlp_param_count(C.byref(g)) == -1 and b"[-32, 32]" in lib.aon_last_error(), (lo, hi)
+            with pytest.raises(Exception):
+                ops.MlpGeometry(min_deg_point=lo, max_deg_point=hi)
+    st = _lib.RenderOptsC()
+    for lo, hi, ok in ((-32, -22, True), (22, 32, True), (23, 33, False), (-33, -23, False)):
+        lib.aon_render_opts_init(C.byref(st))
+        st.min_deg_point, st.max_deg_point = lo, hi
+        rc = lib.aon_render_workspace_bytes_ex(256, C.byref(st))
+        assert (rc > 0) if ok else (rc == -1 and b"[-32, 32]" in lib.aon_last_error()), (lo, hi)
+    fake = (C.c_void_p * 40)(*([16] * 40))     # never read: the degree rule comes before the first launch
+    for lo, hi, msg in ((23, 33, b"[-32, 32]"), (-33, -23, b"[-32, 32]"), (7, 17, b"max_deg_point <= 16"), (14, 24, b"max_deg_point <= 16")):
+        assert lib.aon_pack_art_mlp_bwd_deg(fake, lo, hi, 4, C.c_void_p(16), None) == -1 and msg in lib.aon_last_error(), (lo, hi)
+        with pytest.raises(NotImplementedError):
+            ops.art_param_shapes((lo, hi, 4))
+    assert ops.art_param_shapes((6, 16, 4))["pts_linears.0.weight"] == (256, 63 + 128)
+
+
 def test_bottleneck_fold_switch_without_gpu():
     """Round 5: the form switch of the pack calls (include/aon_hip.h, aon_set_bottleneck_fold) is host state: default folded.  Round 6
     (ADVICE r5): a pointer this process never packed or declared has NO form (-1) whatever the switch says -- the launchers refuse it --

@@ -109,9 +109,11 @@ def _fma(a, b, c):
 
 
 def cos_f32(x):
-    """csrc/aon_common.h's cos_f32, operation by operation"""
+    """csrc/aon_common.h's cos_f32, operation by operation, for |x| < 2^19 (beyond, the kernels' function takes the exact quadrant reduction;
+    the view encodings this copy is used on stay below 2^3 + pi/2)"""
     h = float.fromhex
     ax = F(abs(F(x)))
+    assert ax < F(2.0 ** 19)
     k = F(np.rint(F(ax * F(0.636619747))))
     q = int(k)
     r = _fma(k, F(-h("0x1.921fb4p+0")), ax)

@@ -8,7 +8,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from .. import ops
+from .. import fit, ops
 
 
 class LitModel(torch.nn.Module):
@@ -138,27 +138,6 @@ for _name in ("__getitem__", "__iter__", "__len__", "__repr__", "__eq__", "__ne_
     setattr(_LogSeries, _name, _settled(_name))
 
 
-def _code_arena(codes: dict, dev, requires_grad: bool):
-    """The three codes in one flat (4, 288) buffer -- rows: codes, gradients, exp_avg, exp_avg_sq -- and one (1, dim) leaf per code on
-    row 0's storage."""
-    arena = torch.zeros((4, sum(d for _, d in ops._LATENT_KEYS)), dtype=torch.float32, device=dev)
-    leaves, off = {}, 0
-    for k, d in ops._LATENT_KEYS:
-        view = arena[0, off: off + d].view(1, d)
-        view.copy_(codes[k])
-        leaves[k] = view.detach().requires_grad_(bool(requires_grad))
-        off += d
-    return arena, leaves
-
-
-def _arena_codes(arena) -> dict:
-    out, off = {}, 0
-    for k, d in ops._LATENT_KEYS:
-        out[k] = arena[0, off: off + d].view(1, d).clone()
-        off += d
-    return out
-
-
 class Harness(LitModel):
     """What the two LightningModules of the reference share once Lightning is removed: the ``self.log`` sink, the
     learning-rate rule of ``optimizer_step`` (model.py:391-419 == model_autodecoder.py:607-636) and the PSNR / SSIM part
@@ -234,7 +213,7 @@ class Harness(LitModel):
                 outs.append(self.model(chunk, False, self.white_bkgd, self.near, self.far, *model_args)[1])
         return {k: torch.cat([o[j] for o in outs], 0) for j, k in enumerate(("comp_rgb", "acc", "depth"))}
 
-    # ---- fitting poses and codes on the FROZEN network: what fit_latents and the two fit_pose share (DESIGN.md sections 4.13 - 4.15) ----
+    # ---- fitting poses and codes on the FROZEN network: what fit_latents and the two fit_pose hand fit.py's loop (DESIGN.md sections 4.13 - 4.15) ----
     def _fit_args(self, name, steps, batches, poses=False):
         """The checks of `steps` and `batches` and, for poses other than False (fit_pose), of one pose per view -> (batches, poses) as lists."""
         if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
@@ -269,56 +248,52 @@ class Harness(LitModel):
                 if c.dim() != 2 or c.shape[0] < 3 or c.shape[1] != 4:
                     raise ValueError(f"fit_pose: a pose must be a (3, 4) matrix, got {tuple(c.shape)}")
                 pose0.append(c[:3].contiguous())
-            parena = torch.zeros((4, 6 * views), dtype=torch.float32, device=dev)   # rows: 6-vectors, gradients, exp_avg, exp_avg_sq
-            corr = [parena[0, 6 * v: 6 * v + 6].detach().requires_grad_(True) for v in range(views)]
-        leaves = None
+            pose_buf = fit.AdamBuffer(6 * views, dev)
+            corr = [pose_buf.leaf(6 * v, 6) for v in range(views)]
+        code_buf = leaves = None
         if codes is not None:
-            arena, leaves = _code_arena(codes, dev, fit_codes)   # the same rows for the 288 code floats; leaves on row 0
+            code_buf = fit.CodeBuffer([codes], dev, [k for k, _ in ops._LATENT_KEYS] if fit_codes else ())
+            leaves = code_buf.leaves[0]
         gen = torch.Generator(device=dev)
         gen.manual_seed(int(seed))
-        net_params = list(self.model.parameters())
-        flags = [p.requires_grad for p in net_params]
-        losses = torch.zeros(steps, dtype=torch.float32, device=dev)
-        try:
-            if freeze:
-                for p in net_params:
-                    p.requires_grad_(False)
-            with torch.enable_grad():
-                for i in range(steps):
-                    v = i % views
-                    near, far = self.near, self.far
-                    if poses is not None:
-                        directions = batches[v]["directions"].to(device=dev, dtype=torch.float32)
-                        target = batches[v]["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
-                        rays_o, rays_d = ops.rays_from_pose(directions, pose0[v], corr[v])
-                        rays = {"rays_o": rays_o, "rays_d": rays_d, "viewdirs": rays_d}
-                    else:
-                        rays, target = batches[v], batches[v]["target"]
-                        if self.ray_box is not None:
-                            near, far, _ = ops.ray_limits(rays["rays_o"], rays["rays_d"], self.ray_box)
-                    t_rand = u = None
-                    if self.randomized:
-                        n = rays["rays_d"].shape[0]
-                        t_rand = torch.rand((n, self.model.num_coarse_samples + 1), device=dev, generator=gen)
-                        u = torch.rand((n, self.model.num_fine_samples), device=dev, generator=gen) if self.model.num_levels == 2 else None
-                    loss = self._frozen_loss(rays, target, near, far, leaves, t_rand, u)
-                    wrt = ([corr[v]] if poses is not None else []) + ([leaves[k] for k, _ in ops._LATENT_KEYS] if fit_codes else [])
-                    grads = list(torch.autograd.grad(loss, wrt))
-                    losses[i] = loss.detach()
-                    if poses is not None:   # a view's 6-vector keeps its own step count
-                        parena[1, 6 * v: 6 * v + 6].copy_(grads.pop(0))
-                        ops.adam_step(parena[0], parena[1], parena[2], parena[3], 6 * v, 6, float(lr_pose), 0.9, 0.999, 1e-8, i // views + 1)
-                    if fit_codes:
-                        torch.cat([g.reshape(-1) for g in grads], out=arena[1])
-                        ops.adam_step(arena[0], arena[1], arena[2], arena[3], 0, arena.shape[1], float(lr_codes), 0.9, 0.999, 1e-8, i + 1)
-        finally:
-            for p, f in zip(net_params, flags):
-                p.requires_grad_(f)
+
+        def forward(i):
+            v = i % views
+            near, far = self.near, self.far
+            if poses is not None:
+                directions = batches[v]["directions"].to(device=dev, dtype=torch.float32)
+                target = batches[v]["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
+                rays_o, rays_d = ops.rays_from_pose(directions, pose0[v], corr[v])
+                rays = {"rays_o": rays_o, "rays_d": rays_d, "viewdirs": rays_d}
+            else:
+                rays, target = batches[v], batches[v]["target"]
+                if self.ray_box is not None:
+                    near, far, _ = ops.ray_limits(rays["rays_o"], rays["rays_d"], self.ray_box)
+            t_rand = u = None
+            if self.randomized:
+                n = rays["rays_d"].shape[0]
+                t_rand = torch.rand((n, self.model.num_coarse_samples + 1), device=dev, generator=gen)
+                u = torch.rand((n, self.model.num_fine_samples), device=dev, generator=gen) if self.model.num_levels == 2 else None
+            loss = self._frozen_loss(rays, target, near, far, leaves, t_rand, u)
+            return loss, ([corr[v]] if poses is not None else []) + (code_buf.wrt if fit_codes else [])
+
+        def apply(i, grads):
+            if poses is not None:   # a view's 6-vector keeps its own step count
+                v = i % views
+                pose_buf.take(grads[:1], v)
+                pose_buf.step(lr_pose, i // views + 1, 6 * v, 6)
+                grads = grads[1:]
+            if fit_codes:
+                code_buf.take(grads)
+                code_buf.step(lr_codes, i + 1)
+
+        with fit.frozen(self.model, freeze):
+            losses = fit.run(steps, dev, forward, apply)
         fitted = None
         if poses is not None:
             with torch.no_grad():
-                fitted = [ops.apply_pose_correction(pose0[v], parena[0, 6 * v: 6 * v + 6]) for v in range(views)]
-        return fitted, (_arena_codes(arena) if codes is not None else None), losses
+                fitted = [ops.apply_pose_correction(pose0[v], pose_buf.rows[0, 6 * v: 6 * v + 6]) for v in range(views)]
+        return fitted, (code_buf.clones()[0] if codes is not None else None), losses
 
     def finish_fit(self) -> None:
         """End of a training loop (Lightning's on_train_end): the deferred check of the LAST gradient exchange, which no later

@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 import torch.nn.init as init
 
-from ... import ops
+from ... import fit, ops
 from ...autograd import RenderArticulated, RenderArticulatedInputs, RenderArticulatedLatents
 from .model import WeightStreams, _draw_noise, _draw_samples
 
@@ -336,9 +336,7 @@ class LitNeRF_AutoDecoder(Harness):
         NeRF_AE_Art.forward takes autograd.RenderArticulatedInputs.  Every buffer is stepped by aon_adam_step; a view's 6-vector keeps its
         own step count.  Scalar near / far only (a ray box's per-ray limits would move with the pose and carry no gradient)."""
         batches, poses = self._fit_args("fit_pose", steps, batches, poses)
-        lrs = tuple(lr) if isinstance(lr, (tuple, list)) else (lr, lr)
-        if len(lrs) != 2 or not all(isinstance(x, (int, float)) and x > 0 for x in lrs):
-            raise ValueError(f"fit_pose: lr must be positive (one rate, or a pair for poses and codes), got {lr!r}")
+        lrs = fit.lr_pair("fit_pose", lr)
         self._fit_pose_batches(batches)
         lat0 = self._initial_latents(codes, next(self.model.parameters()).device)
         return self._fit_frozen(batches, steps, seed, poses=poses, lr_pose=lrs[0], codes=lat0, lr_codes=lrs[1], fit_codes=fit_codes)
@@ -393,6 +391,31 @@ class LitNeRF_AutoDecoder(Harness):
             out.append((iid, art, latents, pose, box))
         return out
 
+    def _scene_fit_placed(self, who, placements, batches):
+        """What fit_scene_codes and fit_scene_poses check alike, in this order: the placements and their number, the batches' keys, every
+        object's code, pose and box (SceneObject raises) -> _placement_codes' list."""
+        from ...scene import SceneObject
+
+        placed = self._placement_codes(who, placements)
+        if not 1 <= len(placed) <= ops.SCENE_MAX_OBJECTS:
+            raise ValueError(f"{who}: a scene holds 1 to {ops.SCENE_MAX_OBJECTS} objects, got {len(placed)}")
+        for b in batches:
+            if not all(k in b for k in ("rays_o", "rays_d", "viewdirs", "target")):
+                raise ValueError(f"{who}: every batch needs 'rays_o', 'rays_d', 'viewdirs' (world) and 'target'")
+        for _, _, latents, pose, box in placed:
+            SceneObject(latents, pose, box)
+        return placed
+
+    def _scene_fit_loss(self, objects, batch, dev, reg_codes=None):
+        """mse over the levels of `objects` rendered on the batch's rays against its target, plus the code-norm penalty of reg_codes."""
+        from ...scene import render_scene_grad
+
+        rays = {k: batch[k].to(device=dev, dtype=torch.float32).reshape(-1, 3) for k in ("rays_o", "rays_d", "viewdirs")}
+        target = batch["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
+        levels = render_scene_grad(self.model, objects, rays, self.white_bkgd)
+        loss = helper.train_loss([lvl[:3] for lvl in levels], target, (), 1e-4)[0]
+        return loss if reg_codes is None else loss + fit.code_norm_penalty(reg_codes)
+
     def fit_scene_codes(self, batches, placements, steps: int, lr: float = 5.0e-3, fit_keys=("density", "color", "articulation"), seed: int = 0):
         """Fit the codes of the K objects of ONE frame layout to observed frames with the network FROZEN: `steps` Adam
         steps against mse over the levels (helper.train_loss) + 1e-4 * sum over objects and codes of mean ||code||, batch `i % len(batches)`
@@ -407,7 +430,7 @@ class LitNeRF_AutoDecoder(Harness):
         The network's requires_grad flags are cleared for the duration and restored.  The codes of all K objects, their gradients and the
         Adam moments are one flat (4, 288 K) buffer stepped by ONE launch (aon_adam_step).  Every step pays the full weight-gradient stage
         (scene.render_scene_grad has no latent-only shortcut)."""
-        from ...scene import SceneObject, render_scene_grad
+        from ...scene import SceneObject
 
         batches, _ = self._fit_args("fit_scene_codes", steps, batches)
         if not (isinstance(lr, (int, float)) and lr > 0):
@@ -416,59 +439,21 @@ class LitNeRF_AutoDecoder(Harness):
         fit_keys = tuple(fit_keys)
         if not fit_keys or not set(fit_keys) <= set(keys):
             raise ValueError(f"fit_scene_codes: fit_keys must name some of {keys}, got {fit_keys!r}")
-        placed = self._placement_codes("fit_scene_codes", placements)
-        if not 1 <= len(placed) <= ops.SCENE_MAX_OBJECTS:
-            raise ValueError(f"fit_scene_codes: a scene holds 1 to {ops.SCENE_MAX_OBJECTS} objects, got {len(placed)}")
-        for b in batches:
-            if not all(k in b for k in ("rays_o", "rays_d", "viewdirs", "target")):
-                raise ValueError("fit_scene_codes: every batch needs 'rays_o', 'rays_d', 'viewdirs' (world) and 'target'")
+        placed = self._scene_fit_placed("fit_scene_codes", placements, batches)
         dev = next(self.model.parameters()).device
-        width = sum(d for _, d in ops._LATENT_KEYS)
-        arena = torch.zeros((4, width * len(placed)), dtype=torch.float32, device=dev)   # rows: codes, gradients, exp_avg, exp_avg_sq
-        objects, leaves = [], []
-        for j, (_, _, latents, pose, box) in enumerate(placed):
-            SceneObject(latents, pose, box)      # raises for a malformed code, pose or box before anything is copied
-            off, codes = j * width, {}
-            for k, d in ops._LATENT_KEYS:
-                view = arena[0, off: off + d].view(1, d)
-                view.copy_(latents[k].detach().reshape(1, d))
-                codes[k] = view.detach().requires_grad_(k in fit_keys)
-                off += d
-            leaves.append(codes)
-            objects.append(SceneObject(codes, pose, box))
-        wrt = [codes[k] for codes in leaves for k in keys if k in fit_keys]
-        slots = [arena[1, j * width + off: j * width + off + d] for j in range(len(placed))
-                 for (k, d), off in zip(ops._LATENT_KEYS, (0, 128, 256)) if k in fit_keys]
-        net_params = list(self.model.parameters())
-        flags = [p.requires_grad for p in net_params]
-        losses = torch.zeros(steps, dtype=torch.float32, device=dev)
-        try:
-            for p in net_params:
-                p.requires_grad_(False)
-            with torch.enable_grad():
-                for i in range(steps):
-                    b = batches[i % len(batches)]
-                    rays = {k: b[k].to(device=dev, dtype=torch.float32).reshape(-1, 3) for k in ("rays_o", "rays_d", "viewdirs")}
-                    target = b["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
-                    levels = render_scene_grad(self.model, objects, rays, self.white_bkgd)
-                    loss = helper.train_loss([lvl[:3] for lvl in levels], target, (), 1e-4)[0]
-                    loss = loss + 1e-4 * sum(torch.mean(torch.norm(codes[k], dim=0)) for codes in leaves for k in keys)
-                    grads = torch.autograd.grad(loss, wrt)
-                    losses[i] = loss.detach()
-                    for slot, g in zip(slots, grads):
-                        slot.copy_(g.reshape(-1))
-                    ops.adam_step(arena[0], arena[1], arena[2], arena[3], 0, arena.shape[1], float(lr), 0.9, 0.999, 1e-8, i + 1)
-        finally:
-            for p, f in zip(net_params, flags):
-                p.requires_grad_(f)
-        fitted = []
-        for j in range(len(placed)):
-            off, codes = j * width, {}
-            for k, d in ops._LATENT_KEYS:
-                codes[k] = arena[0, off: off + d].view(1, d).clone()
-                off += d
-            fitted.append(codes)
-        return fitted, losses
+        codes = fit.CodeBuffer([latents for _, _, latents, _, _ in placed], dev, fit_keys)
+        objects = [SceneObject(leaves, pose, box) for leaves, (_, _, _, pose, box) in zip(codes.leaves, placed)]
+
+        def forward(i):
+            return self._scene_fit_loss(objects, batches[i % len(batches)], dev, codes.leaves), codes.wrt
+
+        def apply(i, grads):
+            codes.take(grads)
+            codes.step(lr, i + 1)
+
+        with fit.frozen(self.model):
+            losses = fit.run(steps, dev, forward, apply)
+        return codes.clones(), losses
 
     def fit_scene_poses(self, batches, placements, steps: int, lr, fit_codes: bool = False, seed: int = 0):
         """Recover where the K objects of ONE frame layout ARE from observed frames with the network FROZEN, alone or
@@ -486,78 +471,37 @@ class LitNeRF_AutoDecoder(Harness):
         With fit_codes off no code and no weight requires grad, and a step launches no weight-gradient kernel
         (autograd.RenderLevelScenePoses).  The pairs' existence, near / far and the sample positions are data: a pose moves only through the
         samples a ray already has inside the object's box, so start close enough for the boxes to overlap the object."""
-        from ...scene import SceneObject, render_scene_grad
+        from ...scene import SceneObject
 
         batches, _ = self._fit_args("fit_scene_poses", steps, batches)
-        lrs = tuple(lr) if isinstance(lr, (tuple, list)) else (lr, lr)
-        if len(lrs) != 2 or not all(isinstance(x, (int, float)) and not isinstance(x, bool) and x > 0 for x in lrs):
-            raise ValueError(f"fit_scene_poses: lr must be positive (one rate, or a pair for poses and codes), got {lr!r}")
-        keys = [k for k, _ in ops._LATENT_KEYS]
-        placed = self._placement_codes("fit_scene_poses", placements)
-        if not 1 <= len(placed) <= ops.SCENE_MAX_OBJECTS:
-            raise ValueError(f"fit_scene_poses: a scene holds 1 to {ops.SCENE_MAX_OBJECTS} objects, got {len(placed)}")
-        for b in batches:
-            if not all(k in b for k in ("rays_o", "rays_d", "viewdirs", "target")):
-                raise ValueError("fit_scene_poses: every batch needs 'rays_o', 'rays_d', 'viewdirs' (world) and 'target'")
+        lrs = fit.lr_pair("fit_scene_poses", lr)
+        placed = self._scene_fit_placed("fit_scene_poses", placements, batches)
         dev = next(self.model.parameters()).device
-        K, width = len(placed), sum(d for _, d in ops._LATENT_KEYS)
-        pose_arena = torch.zeros((4, 6 * K), dtype=torch.float32, device=dev)      # rows: 6-vectors, gradients, exp_avg, exp_avg_sq
-        code_arena = torch.zeros((4, width * K), dtype=torch.float32, device=dev)   # (stepped only when fit_codes)
-        poses0, boxes, leaves = [], [], []
-        for j, (_, _, latents, pose, box) in enumerate(placed):
-            SceneObject(latents, pose, box)      # raises for a malformed code, pose or box before anything is copied
-            poses0.append(ops.check_pose(pose).to(dev))
-            boxes.append(box)
-            off, codes = j * width, {}
-            for k, d in ops._LATENT_KEYS:
-                view = code_arena[0, off: off + d].view(1, d)
-                view.copy_(latents[k].detach().reshape(1, d))
-                codes[k] = view.detach().requires_grad_(bool(fit_codes))
-                off += d
-            leaves.append(codes)
-        corrections = pose_arena[0].detach().requires_grad_(True)
-        wrt = [corrections] + ([codes[k] for codes in leaves for k in keys] if fit_codes else [])
+        K = len(placed)
+        codes = fit.CodeBuffer([latents for _, _, latents, _, _ in placed], dev, [k for k, _ in ops._LATENT_KEYS] if fit_codes else ())
+        pose_buf = fit.AdamBuffer(6 * K, dev)
+        corrections = pose_buf.leaf(0, 6 * K)
+        poses0 = [ops.check_pose(pose).to(dev) for _, _, _, pose, _ in placed]
 
         def current_poses():
             return [ops.apply_pose_correction(poses0[j], corrections[6 * j: 6 * j + 6]) for j in range(K)]
 
-        net_params = list(self.model.parameters())
-        flags = [p.requires_grad for p in net_params]
-        losses = torch.zeros(steps, dtype=torch.float32, device=dev)
-        try:
-            for p in net_params:
-                p.requires_grad_(False)
-            with torch.enable_grad():
-                for i in range(steps):
-                    b = batches[i % len(batches)]
-                    rays = {k: b[k].to(device=dev, dtype=torch.float32).reshape(-1, 3) for k in ("rays_o", "rays_d", "viewdirs")}
-                    target = b["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
-                    objects = [SceneObject(codes, pose, box) for codes, pose, box in zip(leaves, current_poses(), boxes)]
-                    levels = render_scene_grad(self.model, objects, rays, self.white_bkgd)
-                    loss = helper.train_loss([lvl[:3] for lvl in levels], target, (), 1e-4)[0]
-                    if fit_codes:
-                        loss = loss + 1e-4 * sum(torch.mean(torch.norm(codes[k], dim=0)) for codes in leaves for k in keys)
-                    grads = torch.autograd.grad(loss, wrt)
-                    losses[i] = loss.detach()
-                    pose_arena[1].copy_(grads[0])
-                    ops.adam_step(pose_arena[0], pose_arena[1], pose_arena[2], pose_arena[3], 0, pose_arena.shape[1], float(lrs[0]), 0.9, 0.999, 1e-8, i + 1)
-                    if fit_codes:
-                        code_arena[1].copy_(torch.cat([g.reshape(-1) for g in grads[1:]]))
-                        ops.adam_step(code_arena[0], code_arena[1], code_arena[2], code_arena[3], 0, code_arena.shape[1], float(lrs[1]), 0.9, 0.999,
-                                      1e-8, i + 1)
-        finally:
-            for p, f in zip(net_params, flags):
-                p.requires_grad_(f)
+        def forward(i):
+            objects = [SceneObject(leaves, pose, p[4]) for leaves, pose, p in zip(codes.leaves, current_poses(), placed)]
+            return self._scene_fit_loss(objects, batches[i % len(batches)], dev, codes.leaves if fit_codes else None), [corrections] + codes.wrt
+
+        def apply(i, grads):
+            pose_buf.take(grads[:1])
+            pose_buf.step(lrs[0], i + 1)
+            if fit_codes:
+                codes.take(grads[1:])
+                codes.step(lrs[1], i + 1)
+
+        with fit.frozen(self.model):
+            losses = fit.run(steps, dev, forward, apply)
         with torch.no_grad():
             fitted_poses = [p.clone() for p in current_poses()]
-        fitted = []
-        for j in range(K):
-            off, codes = j * width, {}
-            for k, d in ops._LATENT_KEYS:
-                codes[k] = code_arena[0, off: off + d].view(1, d).clone()
-                off += d
-            fitted.append(codes)
-        return fitted_poses, fitted, losses
+        return fitted_poses, codes.clones(), losses
 
     @torch.no_grad()
     def render_scene(self, batch, placements, occupancy=None):

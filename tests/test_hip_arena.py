@@ -472,3 +472,24 @@ def test_composite_bits_are_pinned(dev):
     assert set(got) == set(want)
     moved = [k for k in got if got[k] != want[k]]
     assert not moved, f"{len(moved)} of {len(got)} outputs changed bits: {moved[:6]}"
+
+
+def test_fit_bits_are_pinned(dev):
+    """The trajectories of the five fits on a frozen network -- fit_latents (random draws; a ray box), both fit_pose (two views with different
+    step counts; codes at their own rate), fit_scene_codes (all keys; one key) and fit_scene_poses (alone; with codes) -- on the seeded cases of
+    `tools/grad_hash.py --fit`: the (steps,) losses, every returned code and every returned pose, held to tests/golden/g31_fit_hashes.json.
+    The file was written with the fit code of the commit it names, BEFORE the fits shared one loop (fit.py): a piece of that loop that orders
+    a draw, a sum or a step differently shows here, and the file is not rewritten from a tree that fails it."""
+    import json
+    import os
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import grad_hash
+
+    want = json.load(open(os.path.join(root, "tests", "golden", "g31_fit_hashes.json")))["hashes"]
+    got = dict(grad_hash.fit_hashes())
+    assert set(got) == set(want)
+    moved = [k for k in got if got[k] != want[k]]
+    assert not moved, f"{len(moved)} of {len(got)} tensors changed bits: {moved[:6]}"

@@ -183,6 +183,8 @@ def test_fit_pose_rejects_bad_arguments():
         lit.fit_pose([batch], 3, lr=0.0, poses=[pose])
     with pytest.raises(ValueError, match="lr"):
         lit.fit_pose([batch], 3, lr=(1e-3, 1e-3, 1e-3), poses=[pose])
+    with pytest.raises(ValueError, match="fit_pose: lr must be positive"):      # a bool is not a rate (it used to run at rate 1.0)
+        lit.fit_pose([batch], 3, lr=True, poses=[pose])
     with pytest.raises(ValueError, match="'directions'"):
         lit.fit_pose([{"rays_o": torch.zeros(4, 3), "target": torch.zeros(4, 3)}], 3, poses=[pose])
     with pytest.raises(ValueError, match=r"\(3, 4\) matrix"):

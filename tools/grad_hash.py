@@ -8,7 +8,10 @@ levels at (64, 224): a fine level of 289 samples, the 8-block form of the reduce
 here -- aon_composite_bwd, aon_scene_composite and aon_scene_composite_bwd at the block edges (64 / 65, 256 / 257 samples, K * S = 4096), all
 three activations, both backgrounds, the optional gradients given and null, twins tied in t, sentinel records, dead slot entries -- and
 the --frozen set.  `--composite --write COMMIT` writes tests/golden/g30_composite_hashes.json
-(tests/test_hip_arena.py::test_composite_bits_are_pinned); COMMIT names the commit the library in use was built from."""
+(tests/test_hip_arena.py::test_composite_bits_are_pinned); COMMIT names the commit the library in use was built from.
+--fit: the trajectories of the five fits on a frozen network (fit_latents, both fit_pose, fit_scene_codes, fit_scene_poses) on small seeded
+cases: per case the (steps,) losses, every returned code and every returned pose.  `--fit --write COMMIT` writes
+tests/golden/g31_fit_hashes.json (tests/test_hip_arena.py::test_fit_bits_are_pinned); COMMIT names the commit whose fit code ran."""
 import hashlib
 import os
 import sys
@@ -40,7 +43,29 @@ def composite_hashes():
     return out
 
 
+def fit_hashes():
+    """-> ordered list of (label, 16-hex-digit hash): the --fit set."""
+    out = []
+    _run_fit(lambda *a: out.append((" ".join(a[:-1]), a[-1])))
+    return out
+
+
 def main():
+    if "--fit" in sys.argv:
+        got = fit_hashes()
+        if "--write" in sys.argv:
+            import json
+
+            commit = sys.argv[sys.argv.index("--write") + 1]
+            path = os.path.join(ROOT, "tests", "golden", "g31_fit_hashes.json")
+            json.dump({"note": "sha256[:16] of the losses, codes and poses of fit_latents, both fit_pose, fit_scene_codes and fit_scene_poses on "
+                               "seeded cases on gfx950, written by `python tools/grad_hash.py --fit --write <library_commit>` with the fit "
+                               "code of library_commit", "library_commit": commit, "hashes": dict(got)}, open(path, "w"), indent=0)
+            print("wrote", path, len(got))
+            return
+        for label, digest in got:
+            print(label, digest)
+        return
     if "--composite" in sys.argv:
         got = composite_hashes()
         if "--write" in sys.argv:
@@ -228,6 +253,89 @@ def _run_composite(emit):
                     extra = dict(g_acc=g[1], g_depth=g[2], g_obj_acc=g[3]) if given else {}
                     d_raw = ops.scene_composite_bwd(raw, t, pairs, dirs, g[0], white_bkgd=white, act=act, **extra)
                     emit("scene_composite_bwd", *tag, "all" if given else "rgb_only", "d_raw", h(d_raw))
+
+
+def _run_fit(emit):
+    """Single object: the default networks at both levels (65 / 193 samples), two 6 x 8 views (48 rays).  Scenes: K = 2, an 8 x 12 frame, one
+    level of 33 samples, degrees (0, 3, 2), the density bias lowered by 2, two batches of the same rays with different targets.  The targets
+    are seeded noise: nothing is to be recovered, every step has a gradient."""
+    import numpy as np
+
+    import aon_amd.synthetic as syn
+    from aon_amd import ops
+    from aon_amd.models.vanilla_nerf.model import LitNeRF
+    from aon_amd.models.vanilla_nerf.model_autodecoder import LitNeRF_AutoDecoder
+
+    dev = torch.device("cuda:0")
+    keys = [k for k, _ in ops._LATENT_KEYS]
+
+    def emit_codes(tag, codes):
+        for k in keys:
+            emit(tag, k, h(codes[k]))
+
+    def art(**kw):
+        lit = LitNeRF_AutoDecoder(hparams={"N_max_objs": 2}, near=2.0, far=6.0, white_bkgd=True, **kw).to(dev)
+        lit.code_library.load_state_dict(syn.make_code_library_state(seed=0, n_max_objs=2))
+        return lit
+
+    # ---- one object
+    H, W = 6, 8
+    focal = syn.focal_from_fovy(H)
+    cams = [syn.look_at_pose(azim_deg=a) for a in (20.0, 75.0)]
+    targets = [syn.seeded_uniform(400 + v, H * W, 3).to(dev) for v in range(2)]
+    batches = []
+    for c2w, target in zip(cams, targets):
+        ro, vd = ops.raygen(c2w, H, W, focal, device=dev)
+        batches.append({"rays_o": ro, "rays_d": vd, "viewdirs": vd, "target": target})
+    views = [{"directions": ops.ray_directions(H, W, focal, device=dev).reshape(-1, 3), "target": target} for target in targets]
+    for tag, kw, steps in (("fit_latents randomized", dict(randomized=True), 4), ("fit_latents ray_box", dict(randomized=False, ray_box=2.0), 3)):
+        lit = art(**kw)
+        lit.model.load_state_dict(syn.make_art_state_dict(seed=2, density_scale=10.0))
+        codes, losses = lit.fit_latents(batches, steps, lr=5e-3, init=(1, 3), seed=3)
+        emit(tag, "losses", h(losses))
+        emit_codes(tag, codes)
+    lit = art(randomized=False)
+    lit.model.load_state_dict(syn.make_art_state_dict(seed=2, density_scale=10.0))
+    for tag, kw in (("art fit_pose", dict(lr=5e-3)), ("art fit_pose codes", dict(lr=(2e-3, 5e-3), fit_codes=True))):
+        poses, codes, losses = lit.fit_pose(views, 5, codes=(1, 3), poses=cams, seed=3, **kw)     # view 0 takes 3 steps, view 1 takes 2
+        emit(tag, "losses", h(losses))
+        for v, p in enumerate(poses):
+            emit(tag, f"pose{v}", h(p))
+        emit_codes(tag, codes)
+    van = LitNeRF(randomized=False, near=2.0, far=6.0, white_bkgd=True).to(dev)
+    van.model.load_state_dict(syn.make_nerf_state_dict(seed=0, density_scale=30.0))
+    poses, losses = van.fit_pose(views, 5, lr=5e-3, poses=cams, seed=3)
+    emit("van fit_pose", "losses", h(losses))
+    for v, p in enumerate(poses):
+        emit("van fit_pose", f"pose{v}", h(p))
+
+    # ---- scenes
+    degrees = dict(min_deg_point=0, max_deg_point=3, deg_view=2)
+    lit = art(randomized=False, model_kwargs=dict(num_levels=1, num_coarse_samples=32, **degrees))
+    sd = syn.make_art_state_dict(seed=2, density_scale=30.0, **degrees)
+    sd["coarse_mlp.density_layer.bias"] = sd["coarse_mlp.density_layer.bias"] - 2.0
+    lit.model.load_state_dict(sd)
+
+    def pose(seed, centre):      # tests/test_hip_scene.py::pose
+        w = np.random.default_rng(seed).normal(size=3)
+        R = ops.so3_exp(torch.tensor(w / np.linalg.norm(w) * (0.3 + 0.2 * seed % 2.5), dtype=torch.float64)).float()
+        return torch.cat([R, torch.tensor(centre, dtype=torch.float32)[:, None]], 1)
+
+    H, W = 8, 12
+    placements = [(0, 4, pose(1, (0.35, 0.0, 0.0)), 1.6), (1, 11, pose(2, (-0.45, 0.1, 0.1)), 1.4)]
+    rays = {k: v.to(dev) for k, v in syn.make_rays(H, W, syn.look_at_pose(4.0, 30.0, 30.0), syn.focal_from_fovy(H, 30.0)).items()}
+    frames = [{**rays, "target": syn.seeded_uniform(410 + b, H * W, 3).to(dev)} for b in range(2)]
+    for tag, kw in (("fit_scene_codes", {}), ("fit_scene_codes articulation", dict(fit_keys=("articulation",)))):
+        codes, losses = lit.fit_scene_codes(frames, placements, 4, lr=5e-3, **kw)
+        emit(tag, "losses", h(losses))
+        for j, c in enumerate(codes):
+            emit_codes(f"{tag} obj{j}", c)
+    for tag, lr, fit_codes in (("fit_scene_poses", 2e-3, False), ("fit_scene_poses codes", (2e-3, 5e-3), True)):
+        poses, codes, losses = lit.fit_scene_poses(frames, placements, 4, lr, fit_codes=fit_codes)
+        emit(tag, "losses", h(losses))
+        for j, (p, c) in enumerate(zip(poses, codes)):
+            emit(f"{tag} obj{j}", "pose", h(p))
+            emit_codes(f"{tag} obj{j}", c)
 
 
 if __name__ == "__main__":

@@ -21,12 +21,6 @@ constexpr int kA_ESC = 4744;    // 10 (+2 pad): encoding scales 2^(min_deg_point
 constexpr int kASmallFloats = 4756;
 constexpr int kALdsBytes = kRingBytes + kASmallFloats * 4;
 
-// parameter order of the articulated NeRFMLP (model_autodecoder.py:60-170):
-//   0..7   deformations_linear.{0..3}.{weight,bias}      8,9  deformation_layer.{weight,bias}
-//   10..25 pts_linears.{0..7}.{weight,bias}              26..33 views_linear.{0..3}.{weight,bias}
-//   34,35  bottleneck_layer   36,37 density_layer   38,39 rgb_layer
-constexpr int kNumArtParams = 40;
-
 // ---- chunk stream of one articulated MLP (execution order) ----
 constexpr int kAChD1 = 0;     // deformations_linear.1..3 : 4 chunks each, 4 output tiles (16 KiB)
 constexpr int kAChT0 = 12;    // pts_linears.0 : 2 pos-enc chunks (32 KiB)
@@ -67,5 +61,67 @@ constexpr int kABwFL0E = 80;
 constexpr int kABwFD3 = 88;
 constexpr int kABwFNumChunks = 100;
 
+// ---- latent gradients (the table: art_latent_entry, aon_params.h) ----
+// d latent[k] = sum over the latent's (W, db) pairs, sum_f W[f][col_off + k] * db[f], db the bias gradient of the layer.  One record for the
+// full backward's finishing kernels (aon_train_art.hip: db points at the bias gradients the weight-gradient launches wrote) and the
+// latent-only backward (aon_train_latent.hip: db is null, the kernel forms bias gradient `src` in LDS at lat_db_off(src)).
+struct LatentJob {
+  const float* W[kMaxLatentPairs]; const float* db[kMaxLatentPairs];
+  int ld[kMaxLatentPairs], col_off[kMaxLatentPairs], M[kMaxLatentPairs], src[kMaxLatentPairs];
+  int npairs; int L;
+  float* out;
+  const float* add;   // null, or the other level's result: out = add + this level's (both MLPs see the same latents; may alias out)
+};
+// the three jobs of one level (zero-initialised by the caller), pair by pair in table order; grads: the level's parameter gradients, or null
+inline void art_latent_jobs(const float* const* params, float* const* grads, int P, int V, LatentJob lat[kNumLatents]) {
+  for (int i = 0; i < kNumLatentEntries; ++i) {
+    const LatentEntry e = art_latent_entry(i, P, V);
+    LatentJob& j = lat[e.latent];
+    const int pi = j.npairs++;
+    j.W[pi] = params[e.w]; j.db[pi] = grads ? grads[e.b] : nullptr;
+    j.ld[pi] = e.ld; j.col_off[pi] = e.col; j.M[pi] = e.M; j.src[pi] = e.src;
+    j.L = e.L;
+  }
+}
+
+// W^T db of NL levels' jobs for one latent in lockstep (the levels' jobs have the same shape: L, pairs, M) -- NL independent chains of
+// multiply-adds, each in its own order, their loads in flight together: the finishing kernels are load latency from end to end.  A
+// 1,024-thread block: 8 row groups x 128 columns, group g takes rows f = g, g + 8, ... (independent loads, coalesced over k), the eight
+// group sums are added in group order through LDS (deterministic).  db_of(l, pi): the bias gradient of pair pi at level l.
+// store(k, t): called in the threads of row group 0 with k < L, t[l] level l's d latent[k].
+template <int NL, class DbOf, class Store>
+__device__ __forceinline__ void latent_wt_db(const LatentJob* const (&j)[NL], DbOf db_of, float (*red)[8][128], Store store) {
+  const int k = threadIdx.x & 127, g = threadIdx.x >> 7;
+  const int L = j[0]->L;
+  float s[NL];
+#pragma unroll
+  for (int l = 0; l < NL; ++l) s[l] = 0.f;
+  if (k < L) {
+    for (int pi = 0; pi < j[0]->npairs; ++pi) {
+      const float* W[NL]; const float* db[NL]; int ld[NL];
+#pragma unroll
+      for (int l = 0; l < NL; ++l) { W[l] = j[l]->W[pi] + j[l]->col_off[pi] + k; db[l] = db_of(l, pi); ld[l] = j[l]->ld[pi]; }
+#pragma unroll 4
+      for (int f = g; f < j[0]->M[pi]; f += 8) {
+#pragma unroll
+        for (int l = 0; l < NL; ++l) s[l] = __builtin_fmaf(W[l][(int64_t)f * ld[l]], db[l][f], s[l]);
+      }
+    }
+  }
+#pragma unroll
+  for (int l = 0; l < NL; ++l) red[l][g][k] = s[l];
+  __syncthreads();
+  if (g == 0 && k < L) {
+    float t[NL];
+#pragma unroll
+    for (int l = 0; l < NL; ++l) t[l] = red[l][0][k];
+#pragma unroll
+    for (int q = 1; q < 8; ++q) {
+#pragma unroll
+      for (int l = 0; l < NL; ++l) t[l] += red[l][q][k];
+    }
+    store(k, t);
+  }
+}
 
 }  // namespace aon

@@ -370,7 +370,7 @@ int aon_pack_vanilla_mlp_bwd_deg(const float* const* params_host, int min_deg_po
   const int L = max_deg_point - min_deg_point;
   if (L < 0 || L > 10 || deg_view < 0 || deg_view > 4)
     return fail(AON_E_INVALID, "aon_pack_vanilla_mlp_bwd_deg: up to 10 position and 4 view frequency levels");
-  return check(aon::launch_pack_vanilla_bwd(params_host, static_cast<float*>(packed_bwd), (hipStream_t)stream, 3 + 6 * L, 3 + 6 * deg_view),
+  return check(aon::launch_pack_vanilla_bwd(params_host, static_cast<float*>(packed_bwd), (hipStream_t)stream, aon::enc_width(L), aon::enc_width(deg_view)),
                "aon_pack_vanilla_mlp_bwd_deg");
 }
 
@@ -398,14 +398,14 @@ int aon_vanilla_pack_step(const float* const* params_coarse_host, const float* c
     int n = 0;
     for (int l = 0; l < 2; ++l) { aon::vanilla_fold_jobs_fwd(P[l], fwd[l], deg_view, jobs + n); n += 2; }
     for (int l = 0; l < 2; ++l)
-      if (bwd[l]) { aon::vanilla_fold_jobs_bwd(P[l], bwd[l], 3 + 6 * deg_view, jobs + n); n += 2; }
+      if (bwd[l]) { aon::vanilla_fold_jobs_bwd(P[l], bwd[l], aon::enc_width(deg_view), jobs + n); n += 2; }
     if (int rc = check(aon::launch_fold_gemms(jobs, n, stream), "aon_vanilla_pack_step")) return rc;
   }
   for (int l = 0; l < 2; ++l)
     if (int rc = check(aon::launch_pack_vanilla(P[l], fwd[l], stream, L, deg_view, folded), "aon_vanilla_pack_step")) return rc;
   for (int l = 0; l < 2; ++l)
     if (bwd[l])
-      if (int rc = check(aon::launch_pack_vanilla_bwd(P[l], bwd[l], stream, 3 + 6 * L, 3 + 6 * deg_view, folded), "aon_vanilla_pack_step")) return rc;
+      if (int rc = check(aon::launch_pack_vanilla_bwd(P[l], bwd[l], stream, aon::enc_width(L), aon::enc_width(deg_view), folded), "aon_vanilla_pack_step")) return rc;
   return AON_OK;
 }
 
@@ -477,7 +477,7 @@ int aon_pack_art_mlp_bwd(const float* const* params_host, void* packed_bwd, void
 }
 int aon_pack_art_mlp_bwd_deg(const float* const* params_host, int min_deg_point, int max_deg_point, int deg_view, void* packed_bwd, void* stream) {
   if (!params_host || !packed_bwd) return fail(AON_E_INVALID, "aon_pack_art_mlp_bwd: null pointer");
-  for (int i = 0; i < 40; ++i)
+  for (int i = 0; i < aon::kNumArtParams; ++i)
     if (!params_host[i]) return fail(AON_E_INVALID, "aon_pack_art_mlp_bwd: null parameter pointer");
   if (reinterpret_cast<uintptr_t>(packed_bwd) & 15) return fail(AON_E_INVALID, "aon_pack_art_mlp_bwd: buffer must be 16-byte aligned");
   if (const char* bad = art_degrees_ok(min_deg_point, max_deg_point, deg_view)) return fail(AON_E_INVALID, bad);
@@ -526,7 +526,7 @@ int aon_art_wgrad_deg(const float* planes, const float* dplanes, const float* d_
   if (!planes || !dplanes || !d_raw || !dxp || !params_host || !shape || !appearance || !articulation || !grads_host || !g_shape ||
       !g_appearance || !g_articulation || !workspace)
     return fail(AON_E_INVALID, "aon_art_wgrad: null pointer");
-  for (int i = 0; i < 40; ++i)
+  for (int i = 0; i < aon::kNumArtParams; ++i)
     if (!params_host[i] || !grads_host[i]) return fail(AON_E_INVALID, "aon_art_wgrad: null parameter / gradient pointer");
   if (workspace_bytes < aon::wgrad_workspace_bytes()) return fail(AON_E_WORKSPACE, "aon_art_wgrad: workspace too small");
   if (!packed_bwd && aon::fold_default() == aon::kFormFolded) return fail(AON_E_INVALID, kNullBwdMsg);
@@ -726,7 +726,7 @@ int aon_pack_art_mlp(const float* const* params_host, void* packed, void* stream
 int aon_pack_art_mlp_deg(const float* const* params_host, int min_deg_point, int max_deg_point, int deg_view, void* packed, void* stream) {
   if (const char* bad = art_degrees_ok(min_deg_point, max_deg_point, deg_view)) return fail(AON_E_INVALID, bad);
   if (!params_host || !packed) return fail(AON_E_INVALID, "aon_pack_art_mlp: null pointer");
-  for (int i = 0; i < 40; ++i)
+  for (int i = 0; i < aon::kNumArtParams; ++i)
     if (!params_host[i]) return fail(AON_E_INVALID, "aon_pack_art_mlp: null parameter pointer");
   if (reinterpret_cast<uintptr_t>(packed) & 15) return fail(AON_E_INVALID, "aon_pack_art_mlp: packed must be 16-byte aligned");
   return check(aon::launch_pack_art(params_host, static_cast<float*>(packed), (hipStream_t)stream, max_deg_point - min_deg_point, deg_view),
@@ -741,7 +741,7 @@ int aon_art_prepare_deg(const float* const* params_host, const float* shape, con
                         int min_deg_point, int max_deg_point, int deg_view, void* small, void* stream) {
   if (const char* bad = art_degrees_ok(min_deg_point, max_deg_point, deg_view)) return fail(AON_E_INVALID, bad);
   if (!params_host || !shape || !appearance || !articulation || !small) return fail(AON_E_INVALID, "aon_art_prepare: null pointer");
-  for (int i = 0; i < 40; ++i)
+  for (int i = 0; i < aon::kNumArtParams; ++i)
     if (!params_host[i]) return fail(AON_E_INVALID, "aon_art_prepare: null parameter pointer");
   if (reinterpret_cast<uintptr_t>(small) & 15) return fail(AON_E_INVALID, "aon_art_prepare: small must be 16-byte aligned");
   return check(aon::launch_prepare_art(params_host, shape, appearance, articulation, static_cast<float*>(small), (hipStream_t)stream, min_deg_point,
@@ -759,7 +759,7 @@ int aon_art_pack_step(const float* const* params_coarse_host, const float* const
   if (const char* bad = art_degrees_ok(min_deg_point, max_deg_point, deg_view)) return fail(AON_E_INVALID, bad);
   if (!params_coarse_host || !params_fine_host || !shape || !appearance || !articulation || !packed_coarse || !small_coarse || !packed_fine || !small_fine)
     return fail(AON_E_INVALID, "aon_art_pack_step: null pointer");
-  for (int i = 0; i < 40; ++i)
+  for (int i = 0; i < aon::kNumArtParams; ++i)
     if (!params_coarse_host[i] || !params_fine_host[i]) return fail(AON_E_INVALID, "aon_art_pack_step: null parameter pointer");
   for (const void* p : {(const void*)packed_coarse, (const void*)small_coarse, (const void*)packed_fine, (const void*)small_fine, (const void*)packed_bwd_coarse, (const void*)packed_bwd_fine})
     if (reinterpret_cast<uintptr_t>(p) & 15) return fail(AON_E_INVALID, "aon_art_pack_step: buffers must be 16-byte aligned");

@@ -41,7 +41,7 @@ struct TrainScratch {
   float* grad_tmp[2]; // other encoding degrees: the three encoding-fed weight gradients in the kernels' 63 / 27-column layout
   int64_t bytes;
 };
-constexpr int64_t kGradTmpFloats = 256 * 63 + 256 * (256 + 63) + 128 * (256 + 27);
+constexpr int64_t kGradTmpFloats = 256 * aon::vp_trunk0_ld(aon::kPosEnc) + 256 * aon::vp_trunk5_ld(aon::kPosEnc) + 128 * aon::vp_view0_ld(aon::kViewEnc);
 
 int64_t level_np(int64_t n, int l, const Geo& g) { return align_up(n * g.S(l), 128); }
 
@@ -388,7 +388,7 @@ static int train_bwd_impl(const char* who, bool art, const TrainNet* nets, const
   if (w.bytes > c.workspace_bytes) return bad(AON_E_WORKSPACE, "workspace smaller than aon_train_workspace_bytes()");
   const TrainScratch sc = carve_scratch(static_cast<char*>(c.scratch), n_rays, art, num_levels, g);
   if (sc.bytes > c.scratch_bytes) return bad(AON_E_WORKSPACE, "scratch smaller than aon_train_scratch_bytes()");
-  const int nparams = art ? 40 : aon::kNumVanillaParams;
+  const int nparams = art ? aon::kNumArtParams : aon::kNumVanillaParams;
   for (int l = 0; l < num_levels; ++l) {
     // the transposed stream's form is checked against its mate's: [vanilla] the forward stream, [articulated] the per-call block
     const void* pb = nets[l].packed_bwd;
@@ -494,10 +494,12 @@ static int train_bwd_impl(const char* who, bool art, const TrainNet* nets, const
       if (int rc = chain(&seg, 1, stream)) return rc;
     }
     KTimer timer(kWgrad, stream, L.Np);
-    float* gl[40];
+    float* gl[aon::kMaxNetParams];
     for (int i = 0; i < nparams; ++i) gl[i] = grads[l][i];
     if (g.other_degrees) {   // [vanilla] the three encoding-fed weights come out in the kernels' 63 / 27-column layout, then lose the empty slots
-      gl[0] = sc.grad_tmp[l]; gl[10] = gl[0] + 256 * 63; gl[16] = gl[10] + 256 * (256 + 63);
+      gl[aon::vp_trunk_w(0)] = sc.grad_tmp[l];
+      gl[aon::vp_trunk_w(5)] = gl[aon::vp_trunk_w(0)] + 256 * aon::vp_trunk0_ld(aon::kPosEnc);
+      gl[aon::kVpView0W] = gl[aon::vp_trunk_w(5)] + 256 * aon::vp_trunk5_ld(aon::kPosEnc);
     }
     const hipEvent_t wait_first = (!art && early_unjoined && l == 0 && !post_merged) ? side->join : nullptr;
     if (int rc = level_wgrad(l, stream, (merged && overlap_mode != 2) ? nullptr : fork.aux(l), side ? aon::kWgRest : aon::kWgAll, gl, wait_first)) {
@@ -510,14 +512,14 @@ static int train_bwd_impl(const char* who, bool art, const TrainNet* nets, const
     // stage has been told to wait for them -- or, merged second stage: still un-joined, joined in front of it below
     if (art || !post_merged) early_unjoined = false;
     if (g.other_degrees) {
-      const int Lp = g.max_deg - g.min_deg, P = 3 + 6 * Lp, V = 3 + 6 * g.deg_view;
+      const int Lp = g.max_deg - g.min_deg, P = aon::enc_width(Lp), V = aon::enc_width(g.deg_view);
       auto remap = [&](const float* src, float* dst, int rows, int hidden, int Lx, int Lfull, int cols) {
         const int64_t tot = (int64_t)rows * cols;
         remap_enc_cols_kernel<<<dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream>>>(src, dst, rows, hidden, Lx, Lfull);
       };
-      remap(gl[0], grads[l][0], 256, 0, Lp, 10, P);
-      remap(gl[10], grads[l][10], 256, 256, Lp, 10, 256 + P);
-      remap(gl[16], grads[l][16], 128, 256, g.deg_view, 4, 256 + V);
+      remap(gl[aon::vp_trunk_w(0)], grads[l][aon::vp_trunk_w(0)], 256, 0, Lp, 10, aon::vp_trunk0_ld(P));
+      remap(gl[aon::vp_trunk_w(5)], grads[l][aon::vp_trunk_w(5)], 256, aon::kTrunk5EncCol, Lp, 10, aon::vp_trunk5_ld(P));
+      remap(gl[aon::kVpView0W], grads[l][aon::kVpView0W], 128, aon::kView0EncCol, g.deg_view, 4, aon::vp_view0_ld(V));
       if (int rc = check(hipGetLastError(), who)) return rc;
     }
   }

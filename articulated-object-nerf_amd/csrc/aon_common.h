@@ -7,6 +7,8 @@
 
 #include <atomic>
 
+#include "aon_params.h"
+
 namespace aon {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -161,8 +163,6 @@ __device__ __forceinline__ float torch_min(float a, float b) {
 // which is exactly the A operand of v_mfma_f32_32x32x2_f32 for output tile Tp when the B operand is
 // accumulator register r = 4q+c of the producing layer's tile (rows (r&3)+8*(r>>2)+4*(lane>>5)).
 // ------------------------------------------------------------------------------------------------
-constexpr int kNetWidth = 256;
-constexpr int kCondWidth = 128;
 constexpr int kPosEnc = 63;    // 3 + 2*10*3
 constexpr int kViewEnc = 27;   // 3 + 2*4*3
 
@@ -241,15 +241,6 @@ __host__ __device__ constexpr int aplane_v(int l) { return kAPlVE + 32 + 128 * l
 constexpr int kAPlRows = kAPlVE + 32 + 4 * 128;              // 3456 rows = 13,824 B per sample
 constexpr int kAMaskLayers = 16;                             // slots: D0..3 -> 0..3, H0..7 -> 4..11, V0..3 -> 12..15
 
-// Parameter order of the `params` pointer array handed to aon_pack_vanilla_mlp (device pointers to the
-// unmodified torch nn.Linear storages, (out,in) row-major fp32):
-//   0..15  pts_linears.{0..7}.{weight,bias}
-//   16,17  views_linear.0.{weight,bias}
-//   18,19  bottleneck_layer.{weight,bias}
-//   20,21  density_layer.{weight,bias}
-//   22,23  rgb_layer.{weight,bias}
-constexpr int kNumVanillaParams = 24;
-
 // Output activations of a level (model.py:183-187, model_autodecoder.py:318-323) with the constructor's scalars as the reference's
 // fp32 tensor arithmetic sees them, shared by the compositing kernel and its backward:
 //   raw_sigma <- raw_sigma + noise * noise_std        when `noise` is given (the caller's torch.rand_like draw; model.py:183-184)
@@ -300,6 +291,15 @@ struct FwdSeg {
   // [vanilla] the trunk of the deferred view branch: the samples' marks and the live samples' layer-7 rows
   uint8_t* live_mark = nullptr; float* live_rows = nullptr;
 };
+
+// Sum of a double over the 64 lanes of a wave, the same value in every lane (the fp64 head / bias reductions of aon_wgrad.h and
+// aon_train_latent.hip, the ray gradients' norm term).  A butterfly: not the prefix tree of wave_inclusive_sum_f64, which associates
+// differently.
+__device__ __forceinline__ double wsum64d(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Exclusive prefix over the threads of a 256-thread workgroup, and the total (integers: exact, so the order of the sums does not

@@ -117,7 +117,7 @@ struct ArtLatentLevel {
   const float* dplanes;          // the level's gradient planes, written by the backward chain
   int64_t Np;
   const void* packed_bwd;        // the transposed stream that chain ran with (its form decides the level's layer list)
-  const float* const* params;    // the level's 40 parameters; read: [0], [10], [20], [26] (the weights a latent enters)
+  const float* const* params;    // the level's kNumArtParams parameters; read: the weights a latent enters (art_latent_entry, aon_params.h)
   float* ws;                     // art_latent_ws_bytes() of partial sums
 };
 int64_t art_latent_ws_bytes();
@@ -129,8 +129,8 @@ struct RayGradLevel {
   const float* dplanes;          // the level's gradient planes, written by the backward chain
   const float* dxp;              // [articulated] (Np,4): d x' per sample, written by the same launch; [vanilla] null: x is rebuilt from rays_o, rays_d and t
   int64_t Np;
-  // the level's parameters; read: [articulated, 40] [0] deformations_linear.0.weight, [26] views_linear.0.weight;
-  // [vanilla, 24] [0] pts_linears.0.weight, [10] pts_linears.5.weight, [16] views_linear.0.weight
+  // the level's parameters (aon_params.h); read: [articulated] deformations_linear.0.weight, views_linear.0.weight;
+  // [vanilla] pts_linears.0.weight, pts_linears.5.weight, views_linear.0.weight
   const float* const* params;
   float* rec;                    // ray_grad_record_bytes(n_rays * S) of per-sample records
   const float* t;                // (n_rays, S)

@@ -66,7 +66,7 @@ struct PackArgs {
 // kernel's own writes stay below kStreamBytesF, behind W' / b', or at / above kStreamBytes, so it never overwrites what it reads.
 template <bool FOLD>
 __global__ void pack_vanilla_kernel(PackArgs a, float* __restrict__ packed, int L, int Lv) {
-  const int P = 3 + 6 * L, V = 3 + 6 * Lv;
+  const int P = enc_width(L), V = enc_width(Lv);
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   constexpr int64_t stream_floats = kStreamBytes / 4;
   constexpr int64_t used_floats = FOLD ? kStreamBytesF / 4 : stream_floats;
@@ -79,13 +79,13 @@ __global__ void pack_vanilla_kernel(PackArgs a, float* __restrict__ packed, int 
   if (idx >= stream_floats) {  // resident small vectors
     const int s = (int)(idx - stream_floats);
     float v = 0.f;
-    if (s < kSmBiasBott) v = a.p[2 * (s >> 8) + 1][s & 255];
-    else if (s < kSmBiasView) v = a.p[19][s - kSmBiasBott];
-    else if (s < kSmWSigma) v = FOLD ? Wf[128 * 256 + s - kSmBiasView] : a.p[17][s - kSmBiasView];
-    else if (s < kSmWRgb) v = a.p[20][s - kSmWSigma];
-    else if (s < kSmBSigma) v = a.p[22][s - kSmWRgb];
-    else if (s < kSmBRgb) v = a.p[21][0];
-    else if (s < kSmBRgb + 3) v = a.p[23][s - kSmBRgb];
+    if (s < kSmBiasBott) v = a.p[vp_trunk_b(s >> 8)][s & 255];
+    else if (s < kSmBiasView) v = a.p[kVpBottB][s - kSmBiasBott];
+    else if (s < kSmWSigma) v = FOLD ? Wf[128 * 256 + s - kSmBiasView] : a.p[kVpView0B][s - kSmBiasView];
+    else if (s < kSmWRgb) v = a.p[kVpSigmaW][s - kSmWSigma];
+    else if (s < kSmBSigma) v = a.p[kVpRgbW][s - kSmWRgb];
+    else if (s < kSmBRgb) v = a.p[kVpSigmaB][0];
+    else if (s < kSmBRgb + 3) v = a.p[kVpRgbB][s - kSmBRgb];
     packed[idx] = v;
     return;
   }
@@ -107,18 +107,18 @@ __global__ void pack_vanilla_kernel(PackArgs a, float* __restrict__ packed, int 
   const int hid_col = 8 * q + 4 * h + cc;  // + 32*T
   auto pcol = [&](int c63) { return c63 < 0 ? -1 : pos_col_in(c63, L); };
   auto vcol = [&](int c27) { return c27 < 0 ? -1 : view_col_in(c27, Lv); };
-  if (c < kChL1) { W = a.p[0]; ld = P; col = pcol(posenc_col(c, q, cc, h)); }
-  else if (c < kChL5) { const int l = 1 + (c - kChL1) / 8; W = a.p[2 * l]; ld = 256; col = 32 * ((c - kChL1) % 8) + hid_col; }
-  else if (c < kChL5 + 8) { W = a.p[10]; ld = 256 + P; col = 32 * (c - kChL5) + hid_col; }
-  else if (c < kChL6) { W = a.p[10]; ld = 256 + P; col = pcol(posenc_col(c - kChL5 - 8, q, cc, h)); if (col >= 0) col += 256; }
-  else if (c < kChL7) { W = a.p[12]; ld = 256; col = 32 * (c - kChL6) + hid_col; }
-  else if (c < kChBott) { W = a.p[14]; ld = 256; col = 32 * (c - kChL7) + hid_col; }
-  else if (c < kChView) { W = a.p[18]; ld = 256; col = 32 * (c - kChBott) + hid_col; }
+  if (c < kChL1) { W = a.p[vp_trunk_w(0)]; ld = vp_trunk0_ld(P); col = pcol(posenc_col(c, q, cc, h)); }
+  else if (c < kChL5) { const int l = 1 + (c - kChL1) / 8; W = a.p[vp_trunk_w(l)]; ld = 256; col = 32 * ((c - kChL1) % 8) + hid_col; }
+  else if (c < kChL5 + 8) { W = a.p[vp_trunk_w(5)]; ld = vp_trunk5_ld(P); col = 32 * (c - kChL5) + hid_col; }
+  else if (c < kChL6) { W = a.p[vp_trunk_w(5)]; ld = vp_trunk5_ld(P); col = pcol(posenc_col(c - kChL5 - 8, q, cc, h)); if (col >= 0) col += kTrunk5EncCol; }
+  else if (c < kChL7) { W = a.p[vp_trunk_w(6)]; ld = 256; col = 32 * (c - kChL6) + hid_col; }
+  else if (c < kChBott) { W = a.p[vp_trunk_w(7)]; ld = 256; col = 32 * (c - kChL7) + hid_col; }
+  else if (c < kChView) { W = a.p[kVpBottW]; ld = 256; col = 32 * (c - kChBott) + hid_col; }
   else if (c < kChView + 8) {
-    W = a.p[16]; ld = 256 + V; n_out = kCondWidth; col = 32 * (c - kChView) + hid_col;
+    W = a.p[kVpView0W]; ld = vp_view0_ld(V); n_out = kCondWidth; col = 32 * (c - kChView) + hid_col;
     if constexpr (FOLD) { W = Wf; ld = 256; }
   }
-  else { W = a.p[16]; ld = 256 + V; n_out = kCondWidth; col = vcol(viewenc_col(q, cc, h)); if (col >= 0) col += 256; }
+  else { W = a.p[kVpView0W]; ld = vp_view0_ld(V); n_out = kCondWidth; col = vcol(viewenc_col(q, cc, h)); if (col >= 0) col += kView0EncCol; }
   packed[idx] = (col >= 0 && row < n_out) ? W[(int64_t)row * ld + col] : 0.f;
 }
 
@@ -330,7 +330,7 @@ __global__ void __launch_bounds__(256) mlp_fwd_kernel(MlpArgs args) {
 // W' and b' of one network into the fold area of its forward stream (the jobs launch_pack_vanilla runs unless told they have been run)
 void vanilla_fold_jobs_fwd(const float* const* params, float* packed, int view_levels, FoldGemm jobs[2]) {
   float* Wf = packed + kFoldTmpOff / 4;
-  fold_view_jobs(params[16], 256 + 3 + 6 * view_levels, params[17], params[18], params[19], Wf, Wf + 128 * 256, jobs);
+  fold_view_jobs(params[kVpView0W], vp_view0_ld(enc_width(view_levels)), params[kVpView0B], params[kVpBottW], params[kVpBottB], Wf, Wf + 128 * 256, jobs);
 }
 
 hipError_t launch_pack_vanilla(const float* const* params, float* packed, hipStream_t stream, int pos_levels, int view_levels, bool fold_done) {

@@ -8,7 +8,7 @@
 //   * the three latents (shape 128, appearance 128, articulation 32) are broadcast to every sample by the
 //     reference (einops.repeat, :186-194), i.e. every weight column that multiplies a latent contributes a
 //     per-call constant.  aon_art_prepare folds those columns into effective bias vectors once per call
-//     (163->3, 191->63, 447->319, 411->283 effective K), so the kernel never touches them.
+//     (the row strides of aon_params.h shrink to 3, 63, 319 and 283 effective columns), so the kernel never touches them.
 //   * the 3->128 first deformation layer and the 128->3 deformation head are VALU work on register tiles;
 //     the deformed point is encoded in registers exactly like the vanilla path.
 #include "aon_art_common.h"
@@ -51,12 +51,11 @@ struct ArtPackArgs {
   const float* p[kNumArtParams];
 };
 
-// L / Lv: frequency levels of the network (defaults 10 / 4); the weights' row strides follow: pts_linears.0 (256, P + 128),
-// pts_linears.5 (256, 256 + P + 128), views_linear.0 (128, 256 + V + 128) with P = 3 + 6 L, V = 3 + 6 Lv
+// L / Lv: frequency levels of the network (defaults 10 / 4); the row strides of the concatenating layers follow (aon_params.h)
 // FOLD: the folded form; W' was written to packed + kAFoldTmpOff by launch_fold_view on the same stream (b' belongs to the per-call block)
 template <bool FOLD, class Args>   // Args: anything with the 40 parameter pointers as `p` (kernel arguments: read in place, never copied)
 __device__ __forceinline__ void pack_art_element(const Args& a, float* __restrict__ packed, int L, int Lv, const int64_t idx) {
-  const int P = 3 + 6 * L, V = 3 + 6 * Lv;
+  const int P = enc_width(L), V = enc_width(Lv);
   auto pcol = [&](int c63) { return c63 < 0 ? -1 : pos_col_in(c63, L); };
   auto vcol = [&](int c27) { return c27 < 0 ? -1 : view_col_in(c27, Lv); };
   if (idx >= (FOLD ? kAStreamBytesF : kAStreamBytes) / 4) {   // [FOLD] W' (read below), then the unused tail of the literal-size buffer:
@@ -81,20 +80,20 @@ __device__ __forceinline__ void pack_art_element(const Args& a, float* __restric
   const int h = lane >> 5, row = 32 * tp + (lane & 31);
   const int hid = 8 * q + 4 * h + cc;
   const float* W; int ld, col;
-  if (c < kAChT0) { const int l = 1 + c / 4; W = a.p[2 * l]; ld = 128; col = 32 * (c % 4) + hid; }
-  else if (c < kAChT1) { W = a.p[10]; ld = P + 128; col = pcol(posenc_col(c - kAChT0, q, cc, h)); }          // cols 0..P-1
-  else if (c < kAChT5) { const int l = 1 + (c - kAChT1) / 8; W = a.p[10 + 2 * l]; ld = 256; col = 32 * ((c - kAChT1) % 8) + hid; }
-  else if (c < kAChT5 + 8) { W = a.p[20]; ld = 256 + P + 128; col = 32 * (c - kAChT5) + hid; }
-  else if (c < kAChT6) { W = a.p[20]; ld = 256 + P + 128; col = pcol(posenc_col(c - kAChT5 - 8, q, cc, h)); if (col >= 0) col += 256; }
-  else if (c < kAChT7) { W = a.p[22]; ld = 256; col = 32 * (c - kAChT6) + hid; }
-  else if (c < kAChBott) { W = a.p[24]; ld = 256; col = 32 * (c - kAChT7) + hid; }
-  else if (c < kAChV0) { W = a.p[34]; ld = 256; col = 32 * (c - kAChBott) + hid; }
+  if (c < kAChT0) { const int l = 1 + c / 4; W = a.p[ap_deform_w(l)]; ld = 128; col = 32 * (c % 4) + hid; }
+  else if (c < kAChT1) { W = a.p[ap_trunk_w(0)]; ld = ap_trunk0_ld(P); col = pcol(posenc_col(c - kAChT0, q, cc, h)); }          // cols 0..P-1
+  else if (c < kAChT5) { const int l = 1 + (c - kAChT1) / 8; W = a.p[ap_trunk_w(l)]; ld = 256; col = 32 * ((c - kAChT1) % 8) + hid; }
+  else if (c < kAChT5 + 8) { W = a.p[ap_trunk_w(5)]; ld = ap_trunk5_ld(P); col = 32 * (c - kAChT5) + hid; }
+  else if (c < kAChT6) { W = a.p[ap_trunk_w(5)]; ld = ap_trunk5_ld(P); col = pcol(posenc_col(c - kAChT5 - 8, q, cc, h)); if (col >= 0) col += kTrunk5EncCol; }
+  else if (c < kAChT7) { W = a.p[ap_trunk_w(6)]; ld = 256; col = 32 * (c - kAChT6) + hid; }
+  else if (c < kAChBott) { W = a.p[ap_trunk_w(7)]; ld = 256; col = 32 * (c - kAChT7) + hid; }
+  else if (c < kAChV0) { W = a.p[kApBottW]; ld = 256; col = 32 * (c - kAChBott) + hid; }
   else if (c < kAChV0 + 8) {
-    W = a.p[26]; ld = 256 + V + 128; col = 32 * (c - kAChV0) + hid;
+    W = a.p[ap_view_w(0)]; ld = ap_view0_ld(V); col = 32 * (c - kAChV0) + hid;
     if constexpr (FOLD) { W = packed + kAFoldTmpOff / 4; ld = 256; }
   }
-  else if (c < kAChV1) { W = a.p[26]; ld = 256 + V + 128; col = vcol(viewenc_col(q, cc, h)); if (col >= 0) col += 256; }
-  else { const int l = 1 + (c - kAChV1) / 4; W = a.p[26 + 2 * l]; ld = 128; col = 32 * ((c - kAChV1) % 4) + hid; }
+  else if (c < kAChV1) { W = a.p[ap_view_w(0)]; ld = ap_view0_ld(V); col = vcol(viewenc_col(q, cc, h)); if (col >= 0) col += kView0EncCol; }
+  else { const int l = 1 + (c - kAChV1) / 4; W = a.p[ap_view_w(l)]; ld = 128; col = 32 * ((c - kAChV1) % 4) + hid; }
   packed[idx] = col >= 0 ? W[(int64_t)row * ld + col] : 0.f;  // every layer here has a multiple of 32 outputs
 }
 template <bool FOLD>
@@ -115,7 +114,7 @@ struct ArtPrepArgs {
 // fp32 chain of the latent term, then once more with the fp64 sum on top), not once like the vanilla b' (the earlier wording
 // claimed one rounding; the un-folded gradients treat the bias as exact either way, and the second rounding is half an ulp of the bias)
 __device__ __forceinline__ void prepare_art_element(const ArtPrepArgs& a, float* __restrict__ small, int min_deg, int L, int Lv, int fold, const int s) {
-  const int P = 3 + 6 * L, V = 3 + 6 * Lv;
+  const int P = enc_width(L), V = enc_width(Lv);
   if (s >= kASmallFloats) return;
   float v = 0.f;
   if (s >= kA_ESC) {   // encoding scales (exact powers of two), 0 for the levels this network lacks and for the pad
@@ -123,46 +122,46 @@ __device__ __forceinline__ void prepare_art_element(const ArtPrepArgs& a, float*
     small[s] = l < L ? ldexpf(1.0f, min_deg + l) : 0.f;
     return;
   }
-  if (s < kA_WD0) {  // b + W[:,3:131].shape + W[:,131:163].art   (input = cat[pos, shape, articulation], :196-198)
-    const float* w = a.p[0] + (int64_t)s * 163;
-    float acc = a.p[1][s];
-    for (int k = 0; k < 128; ++k) acc = __builtin_fmaf(w[3 + k], a.shape[k], acc);
-    for (int k = 0; k < 32; ++k) acc = __builtin_fmaf(w[131 + k], a.art[k], acc);
+  if (s < kA_WD0) {  // b + W[:, shape cols].shape + W[:, articulation cols].art   (input = cat[pos, shape, articulation], :196-198)
+    const float* w = a.p[ap_deform_w(0)] + (int64_t)s * kApDeform0Ld;
+    float acc = a.p[ap_deform_b(0)][s];
+    for (int k = 0; k < kShapeDim; ++k) acc = __builtin_fmaf(w[kApDeform0ShapeCol + k], a.shape[k], acc);
+    for (int k = 0; k < kArtDim; ++k) acc = __builtin_fmaf(w[kApDeform0ArtCol + k], a.art[k], acc);
     v = acc;
-  } else if (s < kA_BD) { const int i = s - kA_WD0; v = a.p[0][(int64_t)(i & 127) * 163 + (i >> 7)]; }
-  else if (s < kA_WDL) { const int i = s - kA_BD; v = a.p[2 * (1 + (i >> 7)) + 1][i & 127]; }
-  else if (s < kA_BDL) { v = a.p[8][s - kA_WDL]; }
-  else if (s < kA_BT) { const int i = s - kA_BDL; v = i < 3 ? a.p[9][i] : 0.f; }
+  } else if (s < kA_BD) { const int i = s - kA_WD0; v = a.p[ap_deform_w(0)][(int64_t)(i & 127) * kApDeform0Ld + (i >> 7)]; }
+  else if (s < kA_WDL) { const int i = s - kA_BD; v = a.p[ap_deform_b(1 + (i >> 7))][i & 127]; }
+  else if (s < kA_BDL) { v = a.p[kApDeformOutW][s - kA_WDL]; }
+  else if (s < kA_BT) { const int i = s - kA_BDL; v = i < 3 ? a.p[kApDeformOutB][i] : 0.f; }
   else if (s < kA_BBOT) {
     const int i = s - kA_BT, l = i >> 8, f = i & 255;
-    float acc = a.p[10 + 2 * l + 1][f];
+    float acc = a.p[ap_trunk_b(l)][f];
     if (l == 0) {        // cat[enc(63), shape(128)]  (:210)
-      const float* w = a.p[10] + (int64_t)f * (P + 128) + P;
-      for (int k = 0; k < 128; ++k) acc = __builtin_fmaf(w[k], a.shape[k], acc);
+      const float* w = a.p[ap_trunk_w(0)] + (int64_t)f * ap_trunk0_ld(P) + ap_trunk0_shape_col(P);
+      for (int k = 0; k < kShapeDim; ++k) acc = __builtin_fmaf(w[k], a.shape[k], acc);
     } else if (l == 5) { // cat[h(256), enc(63), shape(128)]  (:216-217)
-      const float* w = a.p[20] + (int64_t)f * (256 + P + 128) + 256 + P;
-      for (int k = 0; k < 128; ++k) acc = __builtin_fmaf(w[k], a.shape[k], acc);
+      const float* w = a.p[ap_trunk_w(5)] + (int64_t)f * ap_trunk5_ld(P) + ap_trunk5_shape_col(P);
+      for (int k = 0; k < kShapeDim; ++k) acc = __builtin_fmaf(w[k], a.shape[k], acc);
     }
     v = acc;
-  } else if (s < kA_BV) { v = a.p[35][s - kA_BBOT]; }
+  } else if (s < kA_BV) { v = a.p[kApBottB][s - kA_BBOT]; }
   else if (s < kA_WSIG) {
     const int i = s - kA_BV, l = i >> 7, f = i & 127;
-    float acc = a.p[26 + 2 * l + 1][f];
+    float acc = a.p[ap_view_b(l)][f];
     if (l == 0) {        // cat[bottleneck(256), viewenc(27), appearance(128)]  (:228-230)
-      const float* w = a.p[26] + (int64_t)f * (256 + V + 128) + 256 + V;
-      for (int k = 0; k < 128; ++k) acc = __builtin_fmaf(w[k], a.app[k], acc);
+      const float* w = a.p[ap_view_w(0)] + (int64_t)f * ap_view0_ld(V) + ap_view0_app_col(V);
+      for (int k = 0; k < kAppDim; ++k) acc = __builtin_fmaf(w[k], a.app[k], acc);
       if (fold) {
-        const float* wb = a.p[26] + (int64_t)f * (256 + V + 128);
+        const float* wb = a.p[ap_view_w(0)] + (int64_t)f * ap_view0_ld(V);
         double t = 0.0;
-        for (int k = 0; k < 256; ++k) t = __builtin_fma((double)wb[k], (double)a.p[35][k], t);
+        for (int k = 0; k < 256; ++k) t = __builtin_fma((double)wb[k], (double)a.p[kApBottB][k], t);
         acc = (float)((double)acc + t);
       }
     }
     v = acc;
-  } else if (s < kA_WRGB) { v = a.p[36][s - kA_WSIG]; }
-  else if (s < kA_BSIG) { v = a.p[38][s - kA_WRGB]; }
-  else if (s < kA_BRGB) { v = a.p[37][0]; }
-  else if (s < kA_BRGB + 3) { v = a.p[39][s - kA_BRGB]; }
+  } else if (s < kA_WRGB) { v = a.p[kApSigmaW][s - kA_WSIG]; }
+  else if (s < kA_BSIG) { v = a.p[kApRgbW][s - kA_WRGB]; }
+  else if (s < kA_BRGB) { v = a.p[kApSigmaB][0]; }
+  else if (s < kA_BRGB + 3) { v = a.p[kApRgbB][s - kA_BRGB]; }
   small[s] = v;
 }
 __global__ void prepare_art_kernel(ArtPrepArgs a, float* __restrict__ small, int min_deg, int L, int Lv, int fold) {
@@ -392,7 +391,7 @@ __global__ void __launch_bounds__(256) art_mlp_fwd_kernel(ArtMlpArgs args) {
 // W' = W_v0[:, :256] W_b of one network into the fold area of its forward stream (the job launch_pack_art runs unless told it has been run)
 FoldGemm art_fold_job_fwd(const float* const* params, float* packed, int view_levels) {
   // (b' is the per-call block's business: prepare_art_kernel; the 128 floats it would take here are not written)
-  return FoldGemm{params[26], 256 + 3 + 6 * view_levels + 128, 1, params[34], 256, 1, packed + kAFoldTmpOff / 4, 256, 128, 256, 256, nullptr, nullptr};
+  return FoldGemm{params[ap_view_w(0)], ap_view0_ld(enc_width(view_levels)), 1, params[kApBottW], 256, 1, packed + kAFoldTmpOff / 4, 256, 128, 256, 256, nullptr, nullptr};
 }
 
 hipError_t launch_pack_art(const float* const* params, float* packed, hipStream_t stream, int pos_levels, int view_levels, bool fold_done) {

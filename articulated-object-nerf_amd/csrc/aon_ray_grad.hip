@@ -6,7 +6,7 @@
 //   x_i = o + t_i d (t is data: the coarse t depends on near / far only, the fine t is detached, helper.py:249):
 //     g_x_i = dxp_i + W_d0[:, 0:3]^T dZ_d0,i          g_o = sum_i g_x_i          g_d = sum_i t_i g_x_i + g_n d / |d|
 //   viewdirs enters through pos_enc(viewdirs, 0, deg_view), a constant of the ray:
-//     g_ve = sum_i W_v0[:, 256 : 256 + V]^T dZ_v0,i   g_viewdirs = g_ve pulled back through the encoding at the forward's rounded arguments
+//     g_ve = sum_i W_v0[:, view-encoding columns]^T dZ_v0,i   g_viewdirs = g_ve pulled back through the encoding at the forward's rounded arguments
 //   |d| scales the interval lengths of the compositing (helper.py:167):
 //     g_n = sum_i dL/dalpha_i (1 - alpha_i) sigma_i delta_i     (fp64 from raw, t, dirs and the upstream gradients: aon_composite_grad.h)
 //
@@ -35,8 +35,8 @@ constexpr int kWvCols = 28;       // 27 view-encoding columns padded to whole fl
 struct RgSampleSeg {
   const float* dplanes;   // the level's gradient planes (chain output)
   const float* dxp;       // (Np,4)
-  const float* Wd0;       // deformations_linear.0.weight (128, 163)
-  const float* Wv0;       // views_linear.0.weight (128, 256 + V + 128)
+  const float* Wd0;       // deformations_linear.0.weight (128, kApDeform0Ld)
+  const float* Wv0;       // views_linear.0.weight (128, ap_view0_ld(V))
   float* rec;             // (n * S, 32)
   int64_t nvalid;         // n * S: padding samples are neither read nor written
   int blk_begin;
@@ -52,11 +52,11 @@ __global__ void __launch_bounds__(256) ray_grad_sample_kernel(RgSampleArgs a) {
   const int tid = (int)threadIdx.x;
   const int si = (a.nsegs > 1 && (int)blockIdx.x >= a.seg[1].blk_begin) ? 1 : 0;
   const RgSampleSeg& S = a.seg[si];
-  const int ldv = 256 + a.V + 128;
-  for (int i = tid; i < 128 * 4; i += 256) wd[i] = (i & 3) < 3 ? S.Wd0[(i >> 2) * 163 + (i & 3)] : 0.f;
+  const int ldv = ap_view0_ld(a.V);
+  for (int i = tid; i < 128 * 4; i += 256) wd[i] = (i & 3) < 3 ? S.Wd0[(i >> 2) * kApDeform0Ld + (i & 3)] : 0.f;
   for (int i = tid; i < 128 * kWvCols; i += 256) {
     const int f = i / kWvCols, c = i % kWvCols;
-    wv[i] = c < a.V ? S.Wv0[(int64_t)f * ldv + 256 + c] : 0.f;
+    wv[i] = c < a.V ? S.Wv0[(int64_t)f * ldv + kView0EncCol + c] : 0.f;
   }
   __syncthreads();
   const int64_t n = (int64_t)((int)blockIdx.x - S.blk_begin) * 256 + tid;
@@ -117,13 +117,6 @@ struct RgReduceArgs {
   float* g_o; float* g_d; float* g_v;
 };
 
-// (a butterfly: not the prefix tree of wave_inclusive_sum_f64, which associates differently)
-__device__ __forceinline__ double rg_wsum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // g_n of one ray at one level: the compositing backward (aon_composite_grad.h) with dalpha_i / d|d| = (1 - alpha_i) sigma_i delta_i in the
 // place of dalpha_i / d raw_sigma_i.  fp64 on the forward's fp32 inputs; the same value in every lane.
 template <int NB>
@@ -167,7 +160,7 @@ __device__ __forceinline__ double rg_norm_term(const RgReduceLevel& L, const int
       if (b * 64 + lane < S) part += (tgw[b] - sfx / f[b]) * kn[b];   // dL/dalpha_i * dalpha_i/d|d|
     }
   }
-  return rg_wsum(part);
+  return wsum64d(part);
 }
 
 // The record loop both reduce kernels share: `rec` the ray's first record at this lane's component (a record is one 128-byte line: lanes
@@ -192,7 +185,7 @@ __device__ __forceinline__ void rg_sum_records(const float* rec, const float* tv
 // of the wave calls it and gets the same gv.
 __device__ __forceinline__ void rg_view_backward(const double acc, const float (&vd)[3], const int Lv, double (&gv)[3]) {
   gv[0] = 0.0; gv[1] = 0.0; gv[2] = 0.0;
-  const int V = 3 + 6 * Lv;
+  const int V = enc_width(Lv);
   for (int ci = 0; ci < V; ++ci) {
     const double g = __shfl(acc, kRecView + ci);
     int ax = ci;
@@ -271,9 +264,9 @@ __global__ void __launch_bounds__(256) ray_grad_reduce_plain_kernel(RgPlainArgs 
 // ---- the vanilla network ----
 // Position enters NeRFMLP twice -- the encoding is the input of pts_linears.0 and rides behind h into pts_linears.5 (model.py:95-103) --
 // and the chain leaves dZ0, dZ5 and dZ_v0 in the gradient planes for the weight-gradient stage.  Per sample, in row-vector notation:
-//   g_enc = dZ0 . W0 + dZ5 . W5[:, 256 : 256 + P]     (P = 3 + 6 (max_deg - min_deg) columns, each ONE fmaf chain from 0 over dZ0's 256
+//   g_enc = dZ0 . W0 + dZ5 . W5[:, encoding columns]   (P = 3 + 6 (max_deg - min_deg) columns from kTrunk5EncCol, each ONE fmaf chain from 0 over dZ0's 256
 //                                                      features in ascending order, then dZ5's 256 on the same accumulator)
-//   view partial = dZ_v0 . W_v0[:, 256 : 256 + V]     (one chain over 128 features, as ray_grad_sample_kernel's)
+//   view partial = dZ_v0 . W_v0[:, view-encoding columns]   (V columns from kView0EncCol; one chain over 128 features, as ray_grad_sample_kernel's)
 //   g_x[a] = g_enc[a] + sum_l 2^l cos(arg) g_enc[..]  at the forward's rounded arguments, x = o + t d in cast_rays' bits; fp64 in ascending
 //                                                      column order, rounded once.
 // The weights are uniform across a wave: W0, then W5's slice, then W_v0's slice are staged through ONE 64 KiB LDS buffer from the network's
@@ -286,8 +279,8 @@ constexpr int kVrgBlock = 256 * kVrgSpl;
 struct VrgSeg {
   const float* dplanes;   // the level's gradient planes (chain output)
   const float* W0;        // pts_linears.0.weight (256, P)
-  const float* W5;        // pts_linears.5.weight (256, 256 + P)
-  const float* Wv0;       // views_linear.0.weight (128, 256 + V)
+  const float* W5;        // pts_linears.5.weight (256, vp_trunk5_ld(P))
+  const float* Wv0;       // views_linear.0.weight (128, vp_view0_ld(V))
   const float* t;         // (n, S)
   float* rec;             // (n * S, 32)
   int64_t nvalid;         // n * S: padding samples are neither read nor written
@@ -336,7 +329,7 @@ __global__ void __launch_bounds__(256) vanilla_ray_grad_sample_kernel(VrgArgs a)
   const int tid = (int)threadIdx.x;
   const int si = (a.nsegs > 1 && (int)blockIdx.x >= a.seg[1].blk_begin) ? 1 : 0;
   const VrgSeg& S = a.seg[si];
-  const int P = 3 + 6 * a.Lp;
+  const int P = enc_width(a.Lp);
   int64_t n[kVrgSpl];
   bool valid[kVrgSpl];
   const float* base[kVrgSpl];
@@ -356,19 +349,19 @@ __global__ void __launch_bounds__(256) vanilla_ray_grad_sample_kernel(VrgArgs a)
     for (int c = 0; c < kVrgCols; ++c) acc[s][c] = 0.f;
   }
   const float* pz[kVrgSpl];
-  vrg_stage<kVrgCols>(w, S.W0, 256, P, 0, P, tid);
+  vrg_stage<kVrgCols>(w, S.W0, 256, vp_trunk0_ld(P), 0, P, tid);
   __syncthreads();
 #pragma unroll
   for (int s = 0; s < kVrgSpl; ++s) pz[s] = base[s] + (plane_h(0) / 4) * 128;
   vrg_accum<kVrgCols / 4, kVrgCols>(w, pz, 64, acc);
   __syncthreads();
-  vrg_stage<kVrgCols>(w, S.W5, 256, 256 + P, 256, P, tid);
+  vrg_stage<kVrgCols>(w, S.W5, 256, vp_trunk5_ld(P), kTrunk5EncCol, P, tid);
   __syncthreads();
 #pragma unroll
   for (int s = 0; s < kVrgSpl; ++s) pz[s] = base[s] + (plane_h(5) / 4) * 128;
   vrg_accum<kVrgCols / 4, kVrgCols>(w, pz, 64, acc);
   __syncthreads();
-  vrg_stage<kWvCols>(w, S.Wv0, 128, 256 + a.V, 256, a.V, tid);
+  vrg_stage<kWvCols>(w, S.Wv0, 128, vp_view0_ld(a.V), kView0EncCol, a.V, tid);
   // the encoding, backwards: columns [x ; sin(2^l x) (level-major, xyz-minor) ; sin(2^l x + fp32(pi/2))] in ascending order
   float gx[kVrgSpl][3];
 #pragma unroll
@@ -452,14 +445,14 @@ hipError_t launch_ray_grads(const RayGradLevel* lv, int nlevels, int64_t n_rays,
   if (nlevels < 1 || nlevels > 2 || n_rays <= 0 || view_levels < 0 || view_levels > 4) return hipErrorInvalidValue;
   if (!rays_d || !viewdirs || !g_rays_o || !g_rays_d || !g_viewdirs) return hipErrorInvalidValue;
   RgSampleArgs A{};
-  A.nsegs = nlevels; A.V = 3 + 6 * view_levels;
+  A.nsegs = nlevels; A.V = enc_width(view_levels);
   int64_t blk = 0;
   for (int l = 0; l < nlevels; ++l) {
     const RayGradLevel& L = lv[l];
-    if (!L.dplanes || !L.dxp || !L.params || !L.params[0] || !L.params[26] || !L.rec || !L.t || !L.raw || !L.g_rgb) return hipErrorInvalidValue;
+    if (!L.dplanes || !L.dxp || !L.params || !L.params[ap_deform_w(0)] || !L.params[ap_view_w(0)] || !L.rec || !L.t || !L.raw || !L.g_rgb) return hipErrorInvalidValue;
     const int64_t nvalid = n_rays * L.S;
     if (L.S < 1 || L.S > 512 || nvalid > L.Np) return hipErrorInvalidValue;
-    A.seg[l] = RgSampleSeg{L.dplanes, L.dxp, L.params[0], L.params[26], L.rec, nvalid, (int)blk};
+    A.seg[l] = RgSampleSeg{L.dplanes, L.dxp, L.params[ap_deform_w(0)], L.params[ap_view_w(0)], L.rec, nvalid, (int)blk};
     blk += (nvalid + 255) / 256;
     if (blk > 0x7fffffff) return hipErrorInvalidValue;
   }
@@ -477,7 +470,7 @@ hipError_t launch_art_ray_grads(const float* dplanes, const float* dxp, const fl
   const int64_t nvalid = n_rays * S, blk = (nvalid + 255) / 256;
   if (blk > 0x7fffffff) return hipErrorInvalidValue;
   RgSampleArgs A{};
-  A.nsegs = 1; A.V = 3 + 6 * view_levels;
+  A.nsegs = 1; A.V = enc_width(view_levels);
   A.seg[0] = RgSampleSeg{dplanes, dxp, Wd0, Wv0, rec, nvalid, 0};
   ray_grad_sample_kernel<<<dim3((unsigned)blk), dim3(256), 0, stream>>>(A);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
@@ -493,15 +486,15 @@ hipError_t launch_vanilla_ray_grads(const RayGradLevel* lv, int nlevels, int64_t
     return hipErrorInvalidValue;
   if (!rays_o || !rays_d || !viewdirs || !g_rays_o || !g_rays_d || !g_viewdirs) return hipErrorInvalidValue;
   VrgArgs A{};
-  A.nsegs = nlevels; A.min_deg = min_deg; A.Lp = pos_levels; A.V = 3 + 6 * view_levels;
+  A.nsegs = nlevels; A.min_deg = min_deg; A.Lp = pos_levels; A.V = enc_width(view_levels);
   A.rays_o = rays_o; A.rays_d = rays_d;
   int64_t blk = 0;
   for (int l = 0; l < nlevels; ++l) {
     const RayGradLevel& L = lv[l];
-    if (!L.dplanes || !L.params || !L.params[0] || !L.params[10] || !L.params[16] || !L.rec || !L.t || !L.raw || !L.g_rgb) return hipErrorInvalidValue;
+    if (!L.dplanes || !L.params || !L.params[vp_trunk_w(0)] || !L.params[vp_trunk_w(5)] || !L.params[kVpView0W] || !L.rec || !L.t || !L.raw || !L.g_rgb) return hipErrorInvalidValue;
     const int64_t nvalid = n_rays * L.S;
     if (L.S < 1 || L.S > 512 || nvalid > L.Np) return hipErrorInvalidValue;
-    A.seg[l] = VrgSeg{L.dplanes, L.params[0], L.params[10], L.params[16], L.t, L.rec, nvalid, L.S, (int)blk};
+    A.seg[l] = VrgSeg{L.dplanes, L.params[vp_trunk_w(0)], L.params[vp_trunk_w(5)], L.params[kVpView0W], L.t, L.rec, nvalid, L.S, (int)blk};
     blk += (nvalid + kVrgBlock - 1) / kVrgBlock;
     if (blk > 0x7fffffff) return hipErrorInvalidValue;
   }

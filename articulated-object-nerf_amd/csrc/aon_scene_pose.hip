@@ -100,14 +100,14 @@ int aon_art_ray_grads(const float* dplanes, const float* dxp, const void* const*
   if (n_rays < 0 || s < 1 || np < 0 || deg_view < 0 || deg_view > 4 || n_rays > INT32_MAX / (int64_t)s)
     return fail(AON_E_INVALID, "aon_art_ray_grads: bad size / view degree (s >= 1, 0 <= deg_view <= 4, n_rays * s <= 2^31 - 1)");
   if (n_rays == 0) return AON_OK;
-  if (!dplanes || !dxp || !params || !params[0] || !params[26] || !t_vals || !viewdirs || !records || !g_rays_o || !g_rays_d || !g_viewdirs)
+  if (!dplanes || !dxp || !params || !params[aon::ap_deform_w(0)] || !params[aon::ap_view_w(0)] || !t_vals || !viewdirs || !records || !g_rays_o || !g_rays_d || !g_viewdirs)
     return fail(AON_E_INVALID, "aon_art_ray_grads: null pointer");
   if (n_rays * s > np) return fail(AON_E_INVALID, "aon_art_ray_grads: n_rays * s exceeds the planes' np samples");
   if (record_bytes < aon::ray_grad_record_bytes(n_rays * s)) return fail(AON_E_WORKSPACE, "aon_art_ray_grads: record scratch too small");
   if (reinterpret_cast<uintptr_t>(dplanes) & 15) return fail(AON_E_INVALID, "aon_art_ray_grads: dplanes must be 16-byte aligned");
   if (reinterpret_cast<uintptr_t>(dxp) & 15) return fail(AON_E_INVALID, "aon_art_ray_grads: dxp must be 16-byte aligned");
   if (reinterpret_cast<uintptr_t>(records) & 15) return fail(AON_E_INVALID, "aon_art_ray_grads: records must be 16-byte aligned");
-  return check(aon::launch_art_ray_grads(dplanes, dxp, static_cast<const float*>(params[0]), static_cast<const float*>(params[26]), t_vals, viewdirs,
+  return check(aon::launch_art_ray_grads(dplanes, dxp, static_cast<const float*>(params[aon::ap_deform_w(0)]), static_cast<const float*>(params[aon::ap_view_w(0)]), t_vals, viewdirs,
                                          n_rays, s, deg_view, static_cast<float*>(records), g_rays_o, g_rays_d, g_viewdirs,
                                          static_cast<hipStream_t>(stream)), "aon_art_ray_grads");
 }

@@ -157,9 +157,9 @@ __global__ void pack_vanilla_bwd_kernel(PackArgs24 a, float* __restrict__ packed
   if constexpr (FOLD) {   // raw copies for launch_unfold_view, behind the stream
     const int64_t i = idx - kBwFOffWv / 4;
     if (i >= 0) {
-      if (i < 128 * 256) packed[idx] = a.p[16][(i >> 8) * (256 + V) + (i & 255)];
-      else if (i < 128 * 256 + 256 * 256) packed[idx] = a.p[18][i - 128 * 256];
-      else if (i < 128 * 256 + 256 * 256 + 256) packed[idx] = a.p[19][i - 128 * 256 - 256 * 256];
+      if (i < 128 * 256) packed[idx] = a.p[kVpView0W][(i >> 8) * vp_view0_ld(V) + (i & 255)];
+      else if (i < 128 * 256 + 256 * 256) packed[idx] = a.p[kVpBottW][i - 128 * 256];
+      else if (i < 128 * 256 + 256 * 256 + 256) packed[idx] = a.p[kVpBottB][i - 128 * 256 - 256 * 256];
       return;
     }
   }
@@ -176,13 +176,13 @@ __global__ void pack_vanilla_bwd_kernel(PackArgs24 a, float* __restrict__ packed
   const float* W; int ld, j;
   if constexpr (FOLD) { if (c >= kBwFL7) c += kBwL7 - kBwFL7; }   // the trunk's chunks take the literal branches below
   if (c < kBwBott) {
-    W = a.p[16]; ld = 256 + V; j = 32 * c + jo;
+    W = a.p[kVpView0W]; ld = vp_view0_ld(V); j = 32 * c + jo;
     if constexpr (FOLD) { W = packed + kBwFOffWf / 4; ld = 256; }   // W' (launch_fold_view, same stream, in front of this kernel)
   }
-  else if (c < kBwL7) { W = a.p[18]; ld = 256; j = 32 * (c - kBwBott) + jo; }
+  else if (c < kBwL7) { W = a.p[kVpBottW]; ld = 256; j = 32 * (c - kBwBott) + jo; }
   else {
     const int l = 7 - (c - kBwL7) / 8;  // 7,6,5,4,3,2,1
-    W = a.p[2 * l]; ld = l == 5 ? 256 + P : 256; j = 32 * ((c - kBwL7) % 8) + jo;
+    W = a.p[vp_trunk_w(l)]; ld = l == 5 ? vp_trunk5_ld(P) : 256; j = 32 * ((c - kBwL7) % 8) + jo;
   }
   packed[idx] = W[(int64_t)j * ld + f];
 }
@@ -331,7 +331,7 @@ __global__ void __launch_bounds__(256) mlp_bwd_chain_kernel(BwdArgs args) {
 // The form packed is the process default at the time of the call (aon_set_bottleneck_fold), remembered for `packed` (stream_form).
 void vanilla_fold_jobs_bwd(const float* const* params, float* packed, int view_size, FoldGemm jobs[2]) {
   float* Wf = packed + kBwFOffWf / 4;
-  fold_view_jobs(params[16], 256 + view_size, params[17], params[18], params[19], Wf, Wf + 128 * 256, jobs);
+  fold_view_jobs(params[kVpView0W], vp_view0_ld(view_size), params[kVpView0B], params[kVpBottW], params[kVpBottB], Wf, Wf + 128 * 256, jobs);
 }
 
 hipError_t launch_pack_vanilla_bwd(const float* const* params, float* packed, hipStream_t stream, int pos_size, int view_size, bool fold_done) {
@@ -487,7 +487,7 @@ hipError_t launch_wgrad_kind_bench(int kind, int nlayers, const float* planes, c
   return hipGetLastError();
 }
 
-// grads: 24 device pointers in the parameter order of aon_pack_vanilla_mlp (each the full (out,in) / (out,) tensor), overwritten.
+// grads: kNumVanillaParams device pointers in the parameter order of aon_pack_vanilla_mlp (each the full (out,in) / (out,) tensor), overwritten.
 // the weight-gradient jobs of one vanilla level
 // fold_tmp != null: the planes are the folded form's (no bottleneck rows).  The bottleneck and the view layer's hidden columns are ONE job
 // dW' = dZ_view . H7^T (128 x 256) into fold_tmp, db' = db_v0 straight into views_linear.0.bias; launch_unfold_view turns (dW', db') into
@@ -495,21 +495,21 @@ hipError_t launch_wgrad_kind_bench(int kind, int nlayers, const float* planes, c
 int vanilla_wgrad_layers(float* const* grads, WgLayerDesc* L, float* fold_tmp) {
   int n = 0;
   // trunk: dW_l = dZ_l . H_{l-1}^T  (+ the pos-enc columns for layers 0 and 5)
-  L[n++] = WgLayerDesc{kWg256x64, plane_h(0), kPlE, grads[0], kPosEnc, 0, kPosEnc, grads[1]};
+  L[n++] = WgLayerDesc{kWg256x64, plane_h(0), kPlE, grads[vp_trunk_w(0)], vp_trunk0_ld(kPosEnc), 0, kPosEnc, grads[vp_trunk_b(0)]};
   for (int l = 1; l < 8; ++l) {
-    const int ld = l == 5 ? 256 + kPosEnc : 256;
-    L[n++] = WgLayerDesc{kWg256x256, plane_h(l), plane_h(l - 1), grads[2 * l], ld, 0, 256, grads[2 * l + 1]};
-    if (l == 5) L[n++] = WgLayerDesc{kWg256x64, plane_h(5), kPlE, grads[10], ld, 256, kPosEnc, nullptr};
+    const int ld = l == 5 ? vp_trunk5_ld(kPosEnc) : 256;
+    L[n++] = WgLayerDesc{kWg256x256, plane_h(l), plane_h(l - 1), grads[vp_trunk_w(l)], ld, 0, 256, grads[vp_trunk_b(l)]};
+    if (l == 5) L[n++] = WgLayerDesc{kWg256x64, plane_h(5), kPlE, grads[vp_trunk_w(5)], ld, kTrunk5EncCol, kPosEnc, nullptr};
   }
   if (fold_tmp) {
-    L[n++] = WgLayerDesc{kWg128x256, kPlHV, plane_h(7), fold_tmp, 256, 0, 256, grads[17]};
+    L[n++] = WgLayerDesc{kWg128x256, kPlHV, plane_h(7), fold_tmp, 256, 0, 256, grads[kVpView0B]};
   } else {
     // bottleneck (input: post-ReLU layer-7 output)
-    L[n++] = WgLayerDesc{kWg256x256, kPlBot, plane_h(7), grads[18], 256, 0, 256, grads[19]};
+    L[n++] = WgLayerDesc{kWg256x256, kPlBot, plane_h(7), grads[kVpBottW], 256, 0, 256, grads[kVpBottB]};
     // view layer: cat[bottleneck(256), viewenc(27)]: two column blocks of one weight
-    L[n++] = WgLayerDesc{kWg128x256, kPlHV, kPlBot, grads[16], 256 + kViewEnc, 0, 256, grads[17]};
+    L[n++] = WgLayerDesc{kWg128x256, kPlHV, kPlBot, grads[kVpView0W], vp_view0_ld(kViewEnc), 0, 256, grads[kVpView0B]};
   }
-  L[n++] = WgLayerDesc{kWg128x32, kPlHV, kPlVE, grads[16], 256 + kViewEnc, 256, kViewEnc, nullptr};
+  L[n++] = WgLayerDesc{kWg128x32, kPlHV, kPlVE, grads[kVpView0W], vp_view0_ld(kViewEnc), kView0EncCol, kViewEnc, nullptr};
   return n;
 }
 int vanilla_wgrad_layers(float* const* grads, WgLayerDesc* L) { return vanilla_wgrad_layers(grads, L, nullptr); }
@@ -542,7 +542,7 @@ hipError_t launch_vanilla_wgrad(const float* planes, const float* dplanes, const
   const int n = vanilla_wgrad_layers(grads, L, fold_tmp);
   // heads and their biases: density_layer (1,256) <- H7 x d_raw.w, rgb_layer (3,128) <- HV x d_raw.xyz, bias sums of d_raw
   const HeadDesc H[3] = {{planes, plane_h(7), 256, d_raw, 128}, {planes, kPlHV, 128, d_raw, 128}, {nullptr, 0, 1, d_raw, 128}};
-  const HeadOut O[4] = {{0, 256, 3, 1, 256, 1, grads[20]}, {0, 128, 0, 3, 128, 1, grads[22]}, {0, 1, 3, 1, 1, 1, grads[21]}, {0, 1, 0, 3, 1, 1, grads[23]}};
+  const HeadOut O[4] = {{0, 256, 3, 1, 256, 1, grads[kVpSigmaW]}, {0, 128, 0, 3, 128, 1, grads[kVpRgbW]}, {0, 1, 3, 1, 1, 1, grads[kVpSigmaB]}, {0, 1, 0, 3, 1, 1, grads[kVpRgbB]}};
   const int OH[4] = {0, 1, 2, 2};
   // all three head jobs (density head on H7, rgb head on HV, the sums of d_raw) are independent of the chain: n_early = 3
   if (hipError_t e = run_wgrad_plan(L, n, H, 3, O, OH, 4, planes, dplanes, kPlRows, Np, ws, stream, aux, phase, 3, phase == kWgEarly ? nullptr : wait_first,
@@ -550,13 +550,13 @@ hipError_t launch_vanilla_wgrad(const float* planes, const float* dplanes, const
   if (defer) defer->n_unfold = 0;
   if (!fold || phase == kWgEarly) return hipSuccess;
   const float* raw = reinterpret_cast<const float*>(static_cast<const char*>(packed_bwd) + kBwFOffWv);
-  // (grads[16]'s row stride is the 27-slot layout's here: other view degrees write a slot-layout temporary first, train_bwd_impl)
+  // (views_linear.0.weight's row stride is the 27-slot layout's here: other view degrees write a slot-layout temporary first, train_bwd_impl)
   if (defer) {
     defer->n_unfold = 3;
-    unfold_view_jobs(fold_tmp, grads[17], raw, 256, raw + 128 * 256, raw + 128 * 256 + 256 * 256, grads[16], 256 + kViewEnc, grads[18], grads[19], defer->unfold);
+    unfold_view_jobs(fold_tmp, grads[kVpView0B], raw, 256, raw + 128 * 256, raw + 128 * 256 + 256 * 256, grads[kVpView0W], vp_view0_ld(kViewEnc), grads[kVpBottW], grads[kVpBottB], defer->unfold);
     return hipSuccess;
   }
-  return launch_unfold_view(fold_tmp, grads[17], raw, 256, raw + 128 * 256, raw + 128 * 256 + 256 * 256, grads[16], 256 + kViewEnc, grads[18], grads[19], stream);
+  return launch_unfold_view(fold_tmp, grads[kVpView0B], raw, 256, raw + 128 * 256, raw + 128 * 256 + 256 * 256, grads[kVpView0W], vp_view0_ld(kViewEnc), grads[kVpBottW], grads[kVpBottB], stream);
 }
 
 // the deferred second stages of two vanilla levels: one reduce launch, one launch of the (up to) six un-folding products; every block of
@@ -582,8 +582,8 @@ static int plan_layers(bool art, float* const* grads, WgLayerDesc* L) {
 
 int wgrad_plan_describe(bool art, int64_t Np, int cus, int32_t* out6, int max_jobs, int64_t* ws_bytes) {
   if (Np <= 0 || (Np & 31) || cus < 1) return -1;
-  float* grads[40];   // >= both parameter counts (24 vanilla, 40 articulated)
-  for (int i = 0; i < 40; ++i) grads[i] = reinterpret_cast<float*>((uintptr_t)0x1000 + 64 * i);   // never dereferenced
+  float* grads[kMaxNetParams];
+  for (int i = 0; i < kMaxNetParams; ++i) grads[i] = reinterpret_cast<float*>((uintptr_t)0x1000 + 64 * i);   // never dereferenced
   WgLayerDesc L[kWgMaxJobs];
   const int n = plan_layers(art, grads, L);
   WgPlan plan;
@@ -602,8 +602,8 @@ int wgrad_plan_describe(bool art, int64_t Np, int cus, int32_t* out6, int max_jo
 // the steps [begin, end) of job j that workgroup wg owns under the plan above (host restatement of the kernel's arithmetic: tests)
 int wgrad_plan_segment(bool art, int64_t Np, int cus, int j, int wg, int32_t* begin_end) {
   if (Np <= 0 || (Np & 31) || cus < 1) return -1;
-  float* grads[40];
-  for (int i = 0; i < 40; ++i) grads[i] = reinterpret_cast<float*>((uintptr_t)0x1000 + 64 * i);
+  float* grads[kMaxNetParams];
+  for (int i = 0; i < kMaxNetParams; ++i) grads[i] = reinterpret_cast<float*>((uintptr_t)0x1000 + 64 * i);
   WgLayerDesc L[kWgMaxJobs];
   const int n = plan_layers(art, grads, L);
   WgPlan plan;
@@ -611,13 +611,8 @@ int wgrad_plan_segment(bool art, int64_t Np, int cus, int j, int wg, int32_t* be
   if (j < 0 || j >= n || wg < 0 || wg >= plan.total_wgs) return -3;
   const WgArgs& A = plan.args;
   const WgJob& J = A.job[j];
-  auto first_step = [&](int64_t x) {
-    const int64_t d = x - J.p_begin;
-    if (d <= 0) return 0;
-    const int64_t q = (d + J.cost - 1) / J.cost;
-    return q < A.nsteps ? (int)q : A.nsteps;
-  };
-  begin_end[0] = first_step(A.w_total * wg / A.nwgs); begin_end[1] = first_step(A.w_total * (wg + 1) / A.nwgs);
+  begin_end[0] = wg_first_step(A.w_total * wg / A.nwgs, J.p_begin, J.cost, A.nsteps);
+  begin_end[1] = wg_first_step(A.w_total * (wg + 1) / A.nwgs, J.p_begin, J.cost, A.nsteps);
   return (wg >= J.first_wg && wg <= J.last_wg) ? 1 : 0;
 }
 

@@ -75,7 +75,7 @@ struct ChunkRuns {
 template <bool FOLD>
 __device__ __forceinline__ void pack_art_bwd_element(const ArtParams& a, float* __restrict__ packed, int L, int Lv, const int64_t idx0, const int64_t idx) {
   using N = std::conditional_t<FOLD, ArtBwdFoldNet, ArtBwdNet>;
-  const int P = 3 + 6 * L, V = 3 + 6 * Lv;   // (row strides of the three concatenating layers; the view-encoding columns are never read)
+  const int P = enc_width(L), V = enc_width(Lv);   // (row strides of the three concatenating layers; the view-encoding columns are never read)
   if (idx >= (FOLD ? kABwFStreamBytes : kABwStreamBytes) / 4) {   // [FOLD] W' (read below), then the unused tail of the literal-size buffer:
     if (FOLD && idx >= kABwFOffWf / 4 + 128 * 256 && idx < kABwStreamBytes / 4) packed[idx] = 0.f;   // zeroed: every byte of the buffer is defined
     return;
@@ -106,20 +106,20 @@ __device__ __forceinline__ void pack_art_bwd_element(const ArtParams& a, float* 
     const int c63 = posenc_col(tp, rr >> 2, rr & 3, hh);
     return c63 < 0 ? -1 : pos_col_in(c63, L);   // a level the network lacks: zero weight, zero gradient into its slot
   };
-  if (c < kABwV0) { const int l = 3 - c / 4; W = a.p[26 + 2 * l]; ld = 128; j = 32 * (c % 4) + jo; }
+  if (c < kABwV0) { const int l = 3 - c / 4; W = a.p[ap_view_w(l)]; ld = 128; j = 32 * (c % 4) + jo; }
   else if (c < kABwBott) {
-    W = a.p[26]; ld = 256 + V + 128; j = 32 * (c - kABwV0) + jo;
+    W = a.p[ap_view_w(0)]; ld = ap_view0_ld(V); j = 32 * (c - kABwV0) + jo;
     if constexpr (FOLD) { W = packed + kABwFOffWf / 4; ld = 256; }   // W' (launch_fold_gemms on the same stream, in front of this kernel)
   }
-  else if (c < kABwL7) { W = a.p[34]; ld = 256; j = 32 * (c - kABwBott) + jo; }
-  else if (c < kABwL5E) { const int l = 7 - (c - kABwL7) / 8; W = a.p[10 + 2 * l]; ld = 256; j = 32 * ((c - kABwL7) % 8) + jo; }
-  else if (c < kABwL5) { W = a.p[20]; ld = 256 + P + 128; j = 32 * (c - kABwL5E) + jo; col = enc_col(); if (col >= 0) col += 256; }
+  else if (c < kABwL7) { W = a.p[kApBottW]; ld = 256; j = 32 * (c - kABwBott) + jo; }
+  else if (c < kABwL5E) { const int l = 7 - (c - kABwL7) / 8; W = a.p[ap_trunk_w(l)]; ld = 256; j = 32 * ((c - kABwL7) % 8) + jo; }
+  else if (c < kABwL5) { W = a.p[ap_trunk_w(5)]; ld = ap_trunk5_ld(P); j = 32 * (c - kABwL5E) + jo; col = enc_col(); if (col >= 0) col += kTrunk5EncCol; }
   else if (c < kABwL0E) {
     const int l = 5 - (c - kABwL5) / 8;  // 5,4,3,2,1
-    W = a.p[10 + 2 * l]; ld = l == 5 ? 256 + P + 128 : 256; j = 32 * ((c - kABwL5) % 8) + jo;
+    W = a.p[ap_trunk_w(l)]; ld = l == 5 ? ap_trunk5_ld(P) : 256; j = 32 * ((c - kABwL5) % 8) + jo;
   }
-  else if (c < kABwD3) { W = a.p[10]; ld = P + 128; j = 32 * (c - kABwL0E) + jo; col = enc_col(); }
-  else { const int l = 3 - (c - kABwD3) / 4; W = a.p[2 * l]; ld = 128; j = 32 * ((c - kABwD3) % 4) + jo; }
+  else if (c < kABwD3) { W = a.p[ap_trunk_w(0)]; ld = ap_trunk0_ld(P); j = 32 * (c - kABwL0E) + jo; col = enc_col(); }
+  else { const int l = 3 - (c - kABwD3) / 4; W = a.p[ap_deform_w(l)]; ld = 128; j = 32 * ((c - kABwD3) % 4) + jo; }
   packed[idx] = col >= 0 ? W[(int64_t)j * ld + col] : 0.f;
 }
 template <bool FOLD>
@@ -354,30 +354,22 @@ __global__ void __launch_bounds__(256) art_bwd_chain_kernel(ArtBwdArgs args) {
 }
 
 // Everything that follows from the bias gradients, ONE launch (1,024-thread blocks):
-//   blocks 0..2   d latent[k] = sum over (W, db) pairs, sum_f W[f][col_off + k] * db[f]  (block = latent).  8 row groups x 128
-//                 columns: group g takes rows f = g, g+8, ... (independent loads, coalesced over k), the eight group sums are
-//                 added in group order through LDS (deterministic);
+//   blocks 0..2   d latent[k] = sum over (W, db) pairs, sum_f W[f][col_off + k] * db[f]  (block = latent; latent_wt_db, aon_art_common.h);
 //   blocks 3..    the latent columns of the weights, dW[f][col_off + k] = db[f] * latent[k]  (every latent is broadcast to all
 //                 samples by the reference, model_autodecoder.py:186-194).
-struct LatentJob {
-  const float* W[3]; const float* db[3]; int ld[3]; int col_off[3]; int M[3];
-  int npairs; int L;
-  float* out;
-  const float* add;   // null, or the other level's result: out = add + this level's (both MLPs see the same latents; may alias out)
-};
 struct OuterJob {
   const float* db; const float* latent; float* out;
   int M, L, ld, col_off, blk_begin;
 };
 struct ArtFinishArgs {
-  LatentJob lat[3];
-  OuterJob outer[5];
+  LatentJob lat[kNumLatents];
+  OuterJob outer[kNumLatentEntries];
 };
 // (blocks 3.. of a level's finishing launch; bx: the block's index in that launch)
 __device__ __forceinline__ void art_finish_outer(const ArtFinishArgs& a, const int bx) {
   int j = 0;
 #pragma unroll 1
-  for (int t = 1; t < 5; ++t)
+  for (int t = 1; t < kNumLatentEntries; ++t)
     if (bx >= a.outer[t].blk_begin) j = t;
   const OuterJob& O = a.outer[j];
   const int idx = (bx - O.blk_begin) * 1024 + threadIdx.x;
@@ -386,75 +378,27 @@ __device__ __forceinline__ void art_finish_outer(const ArtFinishArgs& a, const i
     O.out[(int64_t)f * O.ld + O.col_off + k] = O.db[f] * O.latent[k];
   }
 }
-// (blocks 0..2: this level's d latent[k], valid in the threads of row group 0 with k < L)
-__device__ __forceinline__ float art_finish_latent(const LatentJob& j, float (*red)[128]) {
-  const int k = threadIdx.x & 127, g = threadIdx.x >> 7;
-  float s = 0.f;
-  if (k < j.L) {
-    for (int pi = 0; pi < j.npairs; ++pi) {
-      const float* W = j.W[pi] + j.col_off[pi] + k;
-      const float* db = j.db[pi];
-      const int ld = j.ld[pi];
-#pragma unroll 4
-      for (int f = g; f < j.M[pi]; f += 8) s = __builtin_fmaf(W[(int64_t)f * ld], db[f], s);
-    }
-  }
-  red[g][k] = s;
-  __syncthreads();
-  float t = 0.f;
-  if (g == 0 && k < j.L) {
-    t = red[0][k];
-#pragma unroll
-    for (int q = 1; q < 8; ++q) t += red[q][k];
-  }
-  return t;
-}
 __global__ void __launch_bounds__(1024) art_finish_kernel(ArtFinishArgs a) {
-  __shared__ float red[8][128];
-  if (blockIdx.x >= 3) { art_finish_outer(a, (int)blockIdx.x); return; }
-  const LatentJob& j = a.lat[blockIdx.x];
-  const float t = art_finish_latent(j, red);
-  const int k = threadIdx.x & 127, g = threadIdx.x >> 7;
-  if (g == 0 && k < j.L) j.out[k] = j.add ? j.add[k] + t : t;
+  __shared__ float red[1][8][128];
+  if (blockIdx.x >= kNumLatents) { art_finish_outer(a, (int)blockIdx.x); return; }
+  const LatentJob* const j[1] = {&a.lat[blockIdx.x]};
+  latent_wt_db<1>(j, [&](int l, int pi) { return j[l]->db[pi]; }, red,
+                  [&](int k, const float (&t)[1]) { j[0]->out[k] = j[0]->add ? j[0]->add[k] + t[0] : t[0]; });
 }
-// The finishing kernels of TWO levels as one launch (round 6): blocks 0..2 take each latent through level 0 and then level 1 --
+// The finishing kernels of TWO levels as one launch (round 6): blocks 0..2 take each latent through level 0 and level 1 in lockstep --
 // out = (level 0's sum) + (level 1's sum), the value the two launches in a row leave there (level 0 stores its fp32 sum, level 1 adds
 // its own to it) -- blocks [3, n0) are level 0's latent-column blocks, the rest level 1's.
-// (the two levels' sums run in lockstep -- two independent chains of multiply-adds, each in its own order, their loads in flight together:
-// the kernel is load latency from end to end)
+// (launch_art_wgrad_post2 checked that the two levels' jobs have the same shape: L, pairs, M)
 __global__ void __launch_bounds__(1024) art_finish2_kernel(ArtFinishArgs a0, ArtFinishArgs a1, int n0) {
   __shared__ float red[2][8][128];
   const int bx = (int)blockIdx.x;
-  if (bx >= n0) { art_finish_outer(a1, bx - n0 + 3); return; }
-  if (bx >= 3) { art_finish_outer(a0, bx); return; }
-  const LatentJob& j0 = a0.lat[bx];
-  const LatentJob& j1 = a1.lat[bx];
-  const int k = threadIdx.x & 127, g = threadIdx.x >> 7;
-  float s0 = 0.f, s1 = 0.f;
-  if (k < j0.L) {   // (launch_art_wgrad_post2 checked that the two levels' jobs have the same shape: L, pairs, M)
-    for (int pi = 0; pi < j0.npairs; ++pi) {
-      const float* W0 = j0.W[pi] + j0.col_off[pi] + k;
-      const float* W1 = j1.W[pi] + j1.col_off[pi] + k;
-      const float* db0 = j0.db[pi];
-      const float* db1 = j1.db[pi];
-      const int ld0 = j0.ld[pi], ld1 = j1.ld[pi];
-#pragma unroll 4
-      for (int f = g; f < j0.M[pi]; f += 8) {
-        s0 = __builtin_fmaf(W0[(int64_t)f * ld0], db0[f], s0);
-        s1 = __builtin_fmaf(W1[(int64_t)f * ld1], db1[f], s1);
-      }
-    }
-  }
-  red[0][g][k] = s0;
-  red[1][g][k] = s1;
-  __syncthreads();
-  if (g == 0 && k < j0.L) {
-    float t0 = red[0][0][k], t1 = red[1][0][k];
-#pragma unroll
-    for (int q = 1; q < 8; ++q) { t0 += red[0][q][k]; t1 += red[1][q][k]; }
-    const float v0 = j0.add ? j0.add[k] + t0 : t0;
-    j1.out[k] = v0 + t1;
-  }
+  if (bx >= n0) { art_finish_outer(a1, bx - n0 + kNumLatents); return; }
+  if (bx >= kNumLatents) { art_finish_outer(a0, bx); return; }
+  const LatentJob* const j[2] = {&a0.lat[bx], &a1.lat[bx]};
+  latent_wt_db<2>(j, [&](int l, int pi) { return j[l]->db[pi]; }, red, [&](int k, const float (&t)[2]) {
+    const float v0 = j[0]->add ? j[0]->add[k] + t[0] : t[0];
+    j[1]->out[k] = v0 + t[1];
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -462,7 +406,7 @@ __global__ void __launch_bounds__(1024) art_finish2_kernel(ArtFinishArgs a0, Art
 // ---------------------------------------------------------------------------------------------
 // The form packed is the process default at the time of the call (aon_set_bottleneck_fold), remembered for `packed` (stream_form).
 FoldGemm art_fold_job_bwd(const float* const* params, float* packed, int view_levels) {
-  return FoldGemm{params[26], 256 + 3 + 6 * view_levels + 128, 1, params[34], 256, 1, packed + kABwFOffWf / 4, 256, 128, 256, 256, nullptr, nullptr};
+  return FoldGemm{params[ap_view_w(0)], ap_view0_ld(enc_width(view_levels)), 1, params[kApBottW], 256, 1, packed + kABwFOffWf / 4, 256, 128, 256, 256, nullptr, nullptr};
 }
 
 // both networks of a two-level model, one launch (the folded form's W' must be in place: aon_art_pack_step)
@@ -535,32 +479,32 @@ hipError_t launch_art_bwd_chain(const char* packed_bwd, const float* small, cons
 // dW' = dZ_V0 . H7^T (128 x 256) into fold_tmp, db' = db_v0 straight into views_linear.0.bias; launch_unfold_view makes the reference's gradients.
 int art_wgrad_layers(float* const* grads, WgLayerDesc* L, int Lp, int Lv, float* enc_tmp, float* fold_tmp) {
   const bool dflt = Lp == 10 && Lv == 4;
-  const int P = 3 + 6 * Lp, V = 3 + 6 * Lv;
+  const int P = enc_width(Lp), V = enc_width(Lv);
   int n = 0;
   // deformation MLP (model_autodecoder.py:196-203): layers 1..3 here; layer 0's three position columns go with the heads below
   // (its input is cat[pos(3), shape(128), articulation(32)]: a 16-byte record per sample, not a plane operand)
-  for (int l = 1; l < 4; ++l) L[n++] = WgLayerDesc{kWg128x128, aplane_d(l), aplane_d(l - 1), grads[2 * l], 128, 0, 128, grads[2 * l + 1]};
+  for (int l = 1; l < 4; ++l) L[n++] = WgLayerDesc{kWg128x128, aplane_d(l), aplane_d(l - 1), grads[ap_deform_w(l)], 128, 0, 128, grads[ap_deform_b(l)]};
   // trunk (:210-217): layer 0 input cat[enc(P), shape(128)], layer 5 input cat[h(256), enc(P), shape(128)]
-  if (dflt) L[n++] = WgLayerDesc{kWg256x64, aplane_h(0), kAPlE, grads[10], P + 128, 0, kPosEnc, grads[11]};
-  else L[n++] = WgLayerDesc{kWg256x64, aplane_h(0), kAPlE, enc_tmp, 64, 0, kPosEnc, grads[11]};
+  if (dflt) L[n++] = WgLayerDesc{kWg256x64, aplane_h(0), kAPlE, grads[ap_trunk_w(0)], ap_trunk0_ld(P), 0, kPosEnc, grads[ap_trunk_b(0)]};
+  else L[n++] = WgLayerDesc{kWg256x64, aplane_h(0), kAPlE, enc_tmp, 64, 0, kPosEnc, grads[ap_trunk_b(0)]};
   for (int l = 1; l < 8; ++l) {
-    const int ld = l == 5 ? 256 + P + 128 : 256;
-    L[n++] = WgLayerDesc{kWg256x256, aplane_h(l), aplane_h(l - 1), grads[10 + 2 * l], ld, 0, 256, grads[11 + 2 * l]};
+    const int ld = l == 5 ? ap_trunk5_ld(P) : 256;
+    L[n++] = WgLayerDesc{kWg256x256, aplane_h(l), aplane_h(l - 1), grads[ap_trunk_w(l)], ld, 0, 256, grads[ap_trunk_b(l)]};
     if (l == 5) {
-      if (dflt) L[n++] = WgLayerDesc{kWg256x64, aplane_h(5), kAPlE, grads[20], ld, 256, kPosEnc, nullptr};
+      if (dflt) L[n++] = WgLayerDesc{kWg256x64, aplane_h(5), kAPlE, grads[ap_trunk_w(5)], ld, kTrunk5EncCol, kPosEnc, nullptr};
       else L[n++] = WgLayerDesc{kWg256x64, aplane_h(5), kAPlE, enc_tmp + 256 * 64, 64, 0, kPosEnc, nullptr};
     }
   }
   if (fold_tmp) {
-    L[n++] = WgLayerDesc{kWg128x256, aplane_v(0), aplane_h(7), fold_tmp, 256, 0, 256, grads[27]};
+    L[n++] = WgLayerDesc{kWg128x256, aplane_v(0), aplane_h(7), fold_tmp, 256, 0, 256, grads[ap_view_b(0)]};
   } else {
-    L[n++] = WgLayerDesc{kWg256x256, kAPlBot, aplane_h(7), grads[34], 256, 0, 256, grads[35]};
+    L[n++] = WgLayerDesc{kWg256x256, kAPlBot, aplane_h(7), grads[kApBottW], 256, 0, 256, grads[kApBottB]};
     // view branch (:227-234): layer 0 input cat[bottleneck(256), viewenc(V), appearance(128)]: two column blocks from the planes
-    L[n++] = WgLayerDesc{kWg128x256, aplane_v(0), kAPlBot, grads[26], 256 + V + 128, 0, 256, grads[27]};
+    L[n++] = WgLayerDesc{kWg128x256, aplane_v(0), kAPlBot, grads[ap_view_w(0)], ap_view0_ld(V), 0, 256, grads[ap_view_b(0)]};
   }
-  if (dflt) L[n++] = WgLayerDesc{kWg128x32, aplane_v(0), kAPlVE, grads[26], 256 + V + 128, 256, kViewEnc, nullptr};
+  if (dflt) L[n++] = WgLayerDesc{kWg128x32, aplane_v(0), kAPlVE, grads[ap_view_w(0)], ap_view0_ld(V), kView0EncCol, kViewEnc, nullptr};
   else L[n++] = WgLayerDesc{kWg128x32, aplane_v(0), kAPlVE, enc_tmp + 2 * 256 * 64, 32, 0, kViewEnc, nullptr};
-  for (int l = 1; l < 4; ++l) L[n++] = WgLayerDesc{kWg128x128, aplane_v(l), aplane_v(l - 1), grads[26 + 2 * l], 128, 0, 128, grads[27 + 2 * l]};
+  for (int l = 1; l < 4; ++l) L[n++] = WgLayerDesc{kWg128x128, aplane_v(l), aplane_v(l - 1), grads[ap_view_w(l)], 128, 0, 128, grads[ap_view_b(l)]};
   return n;
 }
 int art_wgrad_layers(float* const* grads, WgLayerDesc* L) { return art_wgrad_layers(grads, L, 10, 4, nullptr, nullptr); }
@@ -568,7 +512,7 @@ int art_wgrad_layers(float* const* grads, WgLayerDesc* L) { return art_wgrad_lay
 // dst[r * ldd + col_off + c] = src[r * lds + slot(c)] for the c < 3 + 6 L columns of an encoding with L levels, taken out of the kernels'
 // Lfull-level slot layout [x ; first block of 3 Lfull ; shifted block of 3 Lfull]
 __global__ void art_remap_enc_kernel(const float* __restrict__ src, int lds, float* __restrict__ dst, int ldd, int col_off, int rows, int L, int Lfull) {
-  const int cols = 3 + 6 * L;
+  const int cols = enc_width(L);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows * cols) return;
   const int r = i / cols, c = i % cols;
@@ -576,7 +520,7 @@ __global__ void art_remap_enc_kernel(const float* __restrict__ src, int lds, flo
   dst[(int64_t)r * ldd + col_off + c] = src[(int64_t)r * lds + sc];
 }
 
-// grads: 40 parameter gradients (order of aon_pack_art_mlp, full shapes) + 3 latent gradients (shape 128, appearance 128,
+// grads: kNumArtParams parameter gradients (order of aon_pack_art_mlp, full shapes) + 3 latent gradients (shape 128, appearance 128,
 // articulation 32); params / latents: the forward's inputs (needed for the latent-column products).
 // Round 6: a level's second stage NOT launched by its own call but handed back, so that the two levels' grouped kernels run back to back
 // and ONE second stage serves both (launch_art_wgrad_post2): reduce -> un-folding products -> finishing kernel were three launches in a
@@ -601,7 +545,7 @@ hipError_t launch_art_wgrad(const float* planes, const float* dplanes, const flo
   const bool fold = packed_bwd && stream_form(packed_bwd) == kFormFolded;
   float* fold_tmp = fold ? wgrad_fold_tmp(ws) : nullptr;
   WgLayerDesc L[kWgMaxJobs];
-  const int P = 3 + 6 * Lp, V = 3 + 6 * Lv;
+  const int P = enc_width(Lp), V = enc_width(Lv);
   const bool dflt = Lp == 10 && Lv == 4;
   // (other degrees: the slot-layout blocks live in the last MiB of the weight-gradient workspace, which no plan reaches: 70 of 96 MiB
   // are used at 4096 x 193 samples, and run_wgrad_plan refuses plans beyond the workspace)
@@ -613,9 +557,9 @@ hipError_t launch_art_wgrad(const float* planes, const float* dplanes, const flo
   const HeadDesc H[6] = {{planes, aplane_h(7), 256, d_raw, 128}, {planes, aplane_v(3), 128, d_raw, 128}, {nullptr, 0, 1, d_raw, 128},
                          {planes, aplane_d(3), 128, dxp, 128},   {nullptr, 0, 1, dxp, 128},
                          {dplanes, aplane_d(0), 128, planes + (int64_t)(kAPlPos / 4) * 128, unit_step}};
-  const HeadOut O[8] = {{0, 256, 3, 1, 256, 1, grads[36]}, {0, 128, 0, 3, 128, 1, grads[38]}, {0, 1, 3, 1, 1, 1, grads[37]}, {0, 1, 0, 3, 1, 1, grads[39]},
-                        {0, 128, 0, 3, 128, 1, grads[8]},  {0, 1, 0, 3, 1, 1, grads[9]},
-                        {0, 128, 0, 3, 1, 163, grads[0]},  {0, 128, 4, 1, 1, 1, grads[1]}};
+  const HeadOut O[8] = {{0, 256, 3, 1, 256, 1, grads[kApSigmaW]}, {0, 128, 0, 3, 128, 1, grads[kApRgbW]}, {0, 1, 3, 1, 1, 1, grads[kApSigmaB]}, {0, 1, 0, 3, 1, 1, grads[kApRgbB]},
+                        {0, 128, 0, 3, 128, 1, grads[kApDeformOutW]},  {0, 1, 0, 3, 1, 1, grads[kApDeformOutB]},
+                        {0, 128, 0, 3, 1, kApDeform0Ld, grads[ap_deform_w(0)]},  {0, 128, 4, 1, 1, 1, grads[ap_deform_b(0)]}};
   const int OH[8] = {0, 1, 2, 2, 3, 4, 5, 5};
   // head jobs 0..2 (density head on H7, rgb head on V3, the sums of d_raw) read forward planes and d_raw only: independent of the chain
   if (defer && (phase == kWgEarly || !dflt)) return hipErrorInvalidValue;   // (other degrees: remap launches between the stages; not deferred)
@@ -625,43 +569,32 @@ hipError_t launch_art_wgrad(const float* planes, const float* dplanes, const flo
   if (phase == kWgEarly) return hipSuccess;
   if (!dflt) {
     auto remap = [&](const float* src, int lds, float* dst, int ldd, int col_off, int rows, int Lx, int Lfull) {
-      const int tot = rows * (3 + 6 * Lx);
+      const int tot = rows * enc_width(Lx);
       art_remap_enc_kernel<<<dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream>>>(src, lds, dst, ldd, col_off, rows, Lx, Lfull);
     };
-    remap(enc_tmp, 64, grads[10], P + 128, 0, 256, Lp, 10);
-    remap(enc_tmp + 256 * 64, 64, grads[20], 256 + P + 128, 256, 256, Lp, 10);
-    remap(enc_tmp + 2 * 256 * 64, 32, grads[26], 256 + V + 128, 256, 128, Lv, 4);
+    remap(enc_tmp, 64, grads[ap_trunk_w(0)], ap_trunk0_ld(P), 0, 256, Lp, 10);
+    remap(enc_tmp + 256 * 64, 64, grads[ap_trunk_w(5)], ap_trunk5_ld(P), kTrunk5EncCol, 256, Lp, 10);
+    remap(enc_tmp + 2 * 256 * 64, 32, grads[ap_view_w(0)], ap_view0_ld(V), kView0EncCol, 128, Lv, 4);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   }
   if (defer) {
     defer->n_unfold = fold ? 3 : 0;
-    if (fold) unfold_view_jobs(fold_tmp, grads[27], params[26], 256 + V + 128, params[34], params[35], grads[26], 256 + V + 128, grads[34], grads[35], defer->unfold);
+    if (fold) unfold_view_jobs(fold_tmp, grads[ap_view_b(0)], params[ap_view_w(0)], ap_view0_ld(V), params[kApBottW], params[kApBottB], grads[ap_view_w(0)], ap_view0_ld(V), grads[kApBottW], grads[kApBottB], defer->unfold);
   } else if (fold)   // bottleneck_layer's and views_linear.0[:, :256]'s gradients from (dW', db' = views_linear.0.bias's gradient)
-    if (hipError_t e = launch_unfold_view(fold_tmp, grads[27], params[26], 256 + V + 128, params[34], params[35], grads[26], 256 + V + 128, grads[34], grads[35], stream);
+    if (hipError_t e = launch_unfold_view(fold_tmp, grads[ap_view_b(0)], params[ap_view_w(0)], ap_view0_ld(V), params[kApBottW], params[kApBottB], grads[ap_view_w(0)], ap_view0_ld(V), grads[kApBottW], grads[kApBottB], stream);
         e != hipSuccess) return e;
-  // latent columns of the weights and the latent gradients, both from the bias gradients
+  // latent columns of the weights and the latent gradients, both from the bias gradients: one job per entry of the latent table
   ArtFinishArgs F{};
-  LatentJob& ls = F.lat[0];   // shape: deformation layer 0, trunk layers 0 and 5
-  ls.W[0] = params[0]; ls.db[0] = grads[1]; ls.ld[0] = 163; ls.col_off[0] = 3; ls.M[0] = 128;
-  ls.W[1] = params[10]; ls.db[1] = grads[11]; ls.ld[1] = P + 128; ls.col_off[1] = P; ls.M[1] = 256;
-  ls.W[2] = params[20]; ls.db[2] = grads[21]; ls.ld[2] = 256 + P + 128; ls.col_off[2] = 256 + P; ls.M[2] = 256;
-  ls.npairs = 3; ls.L = 128; ls.out = g_shape; ls.add = accumulate_latents ? g_shape : nullptr;
-  LatentJob& la = F.lat[1];   // appearance: view layer 0
-  la.W[0] = params[26]; la.db[0] = grads[27]; la.ld[0] = 256 + V + 128; la.col_off[0] = 256 + V; la.M[0] = 128;
-  la.npairs = 1; la.L = 128; la.out = g_app; la.add = accumulate_latents ? g_app : nullptr;
-  LatentJob& lt = F.lat[2];   // articulation: deformation layer 0
-  lt.W[0] = params[0]; lt.db[0] = grads[1]; lt.ld[0] = 163; lt.col_off[0] = 131; lt.M[0] = 128;
-  lt.npairs = 1; lt.L = 32; lt.out = g_art; lt.add = accumulate_latents ? g_art : nullptr;
-  int blk = 3;
-  auto outer = [&](int i, const float* db, const float* latent, float* out, int M, int Ll, int ld, int col_off) {
-    F.outer[i] = OuterJob{db, latent, out, M, Ll, ld, col_off, blk};
-    blk += (M * Ll + 1023) / 1024;
-  };
-  outer(0, grads[1], shape, grads[0], 128, 128, 163, 3);
-  outer(1, grads[1], art, grads[0], 128, 32, 163, 131);
-  outer(2, grads[11], shape, grads[10], 256, 128, P + 128, P);
-  outer(3, grads[21], shape, grads[20], 256, 128, 256 + P + 128, 256 + P);
-  outer(4, grads[27], app, grads[26], 128, 128, 256 + V + 128, 256 + V);
+  art_latent_jobs(params, grads, P, V, F.lat);
+  const float* const latents[kNumLatents] = {shape, app, art};   // (kLatShape, kLatApp, kLatArt)
+  float* const g_latents[kNumLatents] = {g_shape, g_app, g_art};
+  for (int k = 0; k < kNumLatents; ++k) { F.lat[k].out = g_latents[k]; F.lat[k].add = accumulate_latents ? g_latents[k] : nullptr; }
+  int blk = kNumLatents;
+  for (int i = 0; i < kNumLatentEntries; ++i) {
+    const LatentEntry e = art_latent_entry(i, P, V);
+    F.outer[i] = OuterJob{grads[e.b], latents[e.latent], grads[e.w], e.M, e.L, e.ld, e.col, blk};
+    blk += (e.M * e.L + 1023) / 1024;
+  }
   if (defer) {
     defer->finish = F;
     defer->finish_blocks = blk;
@@ -684,14 +617,14 @@ hipError_t launch_art_wgrad_post2(const ArtWgDeferred* d0, const ArtWgDeferred* 
     if (hipError_t e = launch_fold_gemms(jobs, n, stream); e != hipSuccess) return e;
   // one finishing launch when level 1 adds onto level 0's latent gradients in place (the training step's arrangement), else two
   bool chained = true;
-  for (int k = 0; k < 3; ++k)
+  for (int k = 0; k < kNumLatents; ++k)
   {
     const LatentJob &a = d0->finish.lat[k], &b = d1->finish.lat[k];
     chained = chained && b.add == a.out && b.out == a.out && b.L == a.L && b.npairs == a.npairs;
     for (int pi = 0; pi < a.npairs && chained; ++pi) chained = b.M[pi] == a.M[pi];
   }
-  if (chained && d0->finish_blocks >= 3 && d1->finish_blocks >= 3) {
-    art_finish2_kernel<<<dim3(d0->finish_blocks + d1->finish_blocks - 3), dim3(1024), 0, stream>>>(d0->finish, d1->finish, d0->finish_blocks);
+  if (chained && d0->finish_blocks >= kNumLatents && d1->finish_blocks >= kNumLatents) {
+    art_finish2_kernel<<<dim3(d0->finish_blocks + d1->finish_blocks - kNumLatents), dim3(1024), 0, stream>>>(d0->finish, d1->finish, d0->finish_blocks);
     return hipGetLastError();
   }
   for (const ArtWgDeferred* d : {d0, d1}) art_finish_kernel<<<dim3(d->finish_blocks), dim3(1024), 0, stream>>>(d->finish);

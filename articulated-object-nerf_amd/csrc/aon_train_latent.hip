@@ -2,7 +2,7 @@
 // without a single weight gradient.
 //
 // Every latent is broadcast to all samples (model_autodecoder.py:186-194), so  d latent = sum over (W, db) pairs of W[:, cols]^T db  where db is
-// the bias gradient of a layer the latent enters (aon_train_art.hip: LatentJob) -- five pairs over FOUR bias gradients:
+// the bias gradient of a layer the latent enters (the latent table of aon_params.h; LatentJob, aon_art_common.h) -- five pairs over FOUR bias gradients:
 //   deformations_linear.0 (shape, articulation), pts_linears.0 and .5 (shape), views_linear.0 (appearance).
 // The full backward gets those four as by-products of its weight-gradient launches.  Here they are taken from the chain's gradient planes
 // directly, and to the BIT as the full backward forms them, which fixes the order of every sum:
@@ -43,20 +43,6 @@ struct LatentDbArgs {
   LatHeadJob head[2];
   int nbias, nhead, head_blk_begin;
 };
-
-// (wg_first_step of aon_wgrad.h: the number of steps of a job whose start lies below x on the work line)
-__device__ __forceinline__ int lat_first_step(int64_t x, int64_t p_begin, int cost, int nsteps) {
-  const int64_t d = x - p_begin;
-  if (d <= 0) return 0;
-  const int64_t q = (d + cost - 1) / cost;
-  return q < nsteps ? (int)q : nsteps;
-}
-
-__device__ __forceinline__ double lat_wsum64d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // one chain: steps [c_begin, c_end), PW samples (stride two) of each.  The adds are one dependent fp32 sequence per row; the loads of 32 samples
 // (32 / PW steps) are issued together in front of their adds -- the kernel is as fast as it keeps bytes in flight.
@@ -124,7 +110,7 @@ __global__ void __launch_bounds__(64) latent_db_kernel(LatentDbArgs a) {
     for (int r = 0; r < 8; ++r) {
       double v[4];
 #pragma unroll
-      for (int w = 0; w < 4; ++w) v[w] = lat_wsum64d(s[w][r]);
+      for (int w = 0; w < 4; ++w) v[w] = wsum64d(s[w][r]);
       if (lane == 0) H.part[(int64_t)seg * 128 + rb * 8 + r] = (v[0] + v[1]) + (v[2] + v[3]);
     }
     return;
@@ -139,7 +125,7 @@ __global__ void __launch_bounds__(64) latent_db_kernel(LatentDbArgs a) {
   const int id = (b % J.blocks_per_wg) * 64 + lane;
   const int kh = id & 1, split = (id >> 1) % J.nsplit, g = id / (2 * J.nsplit);
   const int64_t lo = J.w_total * wg / J.nwgs, hi = J.w_total * (wg + 1) / J.nwgs;
-  const int c_begin = lat_first_step(lo, J.p_begin, J.cost, J.nsteps), c_end = lat_first_step(hi, J.p_begin, J.cost, J.nsteps);
+  const int c_begin = wg_first_step(lo, J.p_begin, J.cost, J.nsteps), c_end = wg_first_step(hi, J.p_begin, J.cost, J.nsteps);
   const int pw = 16 / J.nsplit;
   const float* base = J.a + (int64_t)g * 128 + (2 * split * pw + kh) * 4;
   const f32x4 s = J.nsplit == 1 ? lat_chain<16>(base, J.step_floats, c_begin, c_end) : lat_chain<8>(base, J.step_floats, c_begin, c_end);
@@ -154,22 +140,14 @@ struct LatDbSrc {
   const void* part;   // fp32 partial[nparts][M] of a weight-gradient job, or fp64 partial[nparts][M] of the head job
   int nparts, M, is_head;
 };
-struct LatFinJob {    // LatentJob of aon_train_art.hip with the bias gradients by index
-  const float* W[3];
-  int ld[3], col_off[3], src[3];
-  int npairs, L;
-};
 struct LatFinLevel {
-  LatDbSrc src[4];    // deformations_linear.0, pts_linears.0, pts_linears.5, views_linear.0
-  LatFinJob lat[3];   // shape, appearance, articulation
+  LatDbSrc src[kNumLatentBiases];   // deformations_linear.0, pts_linears.0, pts_linears.5, views_linear.0
+  LatentJob lat[kNumLatents];       // shape, appearance, articulation: the bias gradients by index (src), out in level 0's
 };
 struct LatentFinishArgs {
   LatFinLevel lvl[2];
   int nlevels;
-  float* out[3];
 };
-constexpr int kLatDbFloats = 128 + 256 + 256 + 128;   // offsets of the four bias gradients in the LDS copy: 0, 128, 384, 640
-__host__ __device__ constexpr int lat_db_off(int s) { return s == 0 ? 0 : s == 1 ? 128 : s == 2 ? 384 : 640; }
 
 __global__ void __launch_bounds__(1024) latent_finish_kernel(LatentFinishArgs a) {
   __shared__ float db[2][kLatDbFloats];
@@ -179,7 +157,7 @@ __global__ void __launch_bounds__(1024) latent_finish_kernel(LatentFinishArgs a)
   const int lat = (int)blockIdx.x;
   // the bias gradients this latent needs, as wgrad_reduce_block forms them (same sums, same order)
   for (int l = 0; l < a.nlevels; ++l) {
-    const LatFinJob& j = a.lvl[l].lat[lat];
+    const LatentJob& j = a.lvl[l].lat[lat];
     for (int pi = 0; pi < j.npairs; ++pi) {
       const LatDbSrc& S = a.lvl[l].src[j.src[pi]];
       float* out = db[l] + lat_db_off(j.src[pi]);
@@ -211,34 +189,13 @@ __global__ void __launch_bounds__(1024) latent_finish_kernel(LatentFinishArgs a)
     }
   }
   // blocks 0..2 of art_finish2_kernel (one level: of art_finish_kernel), the bias gradients read from LDS
-  const LatFinJob& j0 = a.lvl[0].lat[lat];
-  const LatFinJob& j1 = a.lvl[a.nlevels - 1].lat[lat];
-  const bool two = a.nlevels == 2;
-  const int k = tid & 127, g = tid >> 7;
-  float s0 = 0.f, s1 = 0.f;
-  if (k < j0.L) {
-    for (int pi = 0; pi < j0.npairs; ++pi) {
-      const float* W0 = j0.W[pi] + j0.col_off[pi] + k;
-      const float* W1 = j1.W[pi] + j1.col_off[pi] + k;
-      const float* db0 = db[0] + lat_db_off(j0.src[pi]);
-      const float* db1 = db[1] + lat_db_off(j1.src[pi]);
-      const int ld0 = j0.ld[pi], ld1 = j1.ld[pi];
-      const int M = a.lvl[0].src[j0.src[pi]].M;
-#pragma unroll 4
-      for (int f = g; f < M; f += 8) {
-        s0 = __builtin_fmaf(W0[(int64_t)f * ld0], db0[f], s0);
-        if (two) s1 = __builtin_fmaf(W1[(int64_t)f * ld1], db1[f], s1);
-      }
-    }
-  }
-  red[0][g][k] = s0;
-  red[1][g][k] = s1;
-  __syncthreads();
-  if (g == 0 && k < j0.L) {
-    float t0 = red[0][0][k], t1 = red[1][0][k];
-#pragma unroll
-    for (int q = 1; q < 8; ++q) { t0 += red[0][q][k]; t1 += red[1][q][k]; }
-    a.out[lat][k] = two ? t0 + t1 : t0;
+  const LatentJob* const j[2] = {&a.lvl[0].lat[lat], &a.lvl[a.nlevels - 1].lat[lat]};
+  auto db_of = [&](int l, int pi) { return db[l] + lat_db_off(j[l]->src[pi]); };
+  if (a.nlevels == 2) {
+    latent_wt_db<2>(j, db_of, red, [&](int k, const float (&t)[2]) { j[0]->out[k] = t[0] + t[1]; });
+  } else {
+    const LatentJob* const j0[1] = {j[0]};
+    latent_wt_db<1>(j0, db_of, red, [&](int k, const float (&t)[1]) { j[0]->out[k] = t[0]; });
   }
 }
 
@@ -252,11 +209,11 @@ hipError_t launch_art_latent_grads(const ArtLatentLevel* lv, int nlevels, int Lp
   if (nlevels < 1 || nlevels > 2 || !g_shape || !g_app || !g_art) return hipErrorInvalidValue;
   const int cus = num_cus();
   if (cus <= 0) return hipErrorInvalidDevice;
-  const int P = 3 + 6 * Lp, V = 3 + 6 * Lv;
+  const int P = enc_width(Lp), V = enc_width(Lv);
   LatentDbArgs D{};
   LatentFinishArgs F{};
   F.nlevels = nlevels;
-  F.out[0] = g_shape; F.out[1] = g_app; F.out[2] = g_art;
+  float* const g_latents[kNumLatents] = {g_shape, g_app, g_art};   // (kLatShape, kLatApp, kLatArt)
   int blk = 0;
   for (int l = 0; l < nlevels; ++l) {
     const ArtLatentLevel& A = lv[l];
@@ -272,11 +229,13 @@ hipError_t launch_art_latent_grads(const ArtLatentLevel* lv, int nlevels, int Lp
     if (!wg_make_plan(L, n, nullptr, A.dplanes, kAPlRows, A.Np, cus < 304 ? cus : 304, A.ws, 0, plan)) return hipErrorInvalidValue;
     int64_t off = 0;   // floats into this level's workspace
     LatFinLevel& FL = F.lvl[l];
-    const int want[3] = {11, 21, 27};   // pts_linears.0.bias, pts_linears.5.bias, views_linear.0.bias
-    for (int w = 0; w < 3; ++w) {
+    for (int i = 0; i < kNumLatentEntries; ++i) {
+      const LatentEntry e = art_latent_entry(i, P, V);
+      if (!A.params[e.w]) return hipErrorInvalidValue;
+      if (e.src == 0) continue;   // (deformations_linear.0's bias gradient is the head job's, below)
       int jf = -1;
       for (int j = 0; j < n; ++j)
-        if (L[j].bias_out == names[want[w]]) jf = j;
+        if (L[j].bias_out == names[e.b]) jf = j;
       if (jf < 0 || D.nbias >= 6) return hipErrorInvalidValue;
       const WgJob& J = plan.args.job[jf];
       const int nsplit = wg_nsplit(J.kind), M = wg_M(J.kind), span = J.last_wg - J.first_wg + 1;
@@ -290,7 +249,7 @@ hipError_t launch_art_latent_grads(const ArtLatentLevel* lv, int nlevels, int Lp
       B.nsplit = nsplit; B.M = M;
       B.blocks_per_wg = (M / 4) * 2 * nsplit / 64;
       B.blk_begin = blk; blk += span * B.blocks_per_wg;
-      FL.src[1 + w] = LatDbSrc{B.part, span * nsplit, M, 0};
+      FL.src[e.src] = LatDbSrc{B.part, span * nsplit, M, 0};
       off += (int64_t)span * nsplit * M;
     }
     off += off & 1;
@@ -305,19 +264,8 @@ hipError_t launch_art_latent_grads(const ArtLatentLevel* lv, int nlevels, int Lp
     off += (int64_t)nseg * 128 * 2;
     if (off * 4 > art_latent_ws_bytes()) return hipErrorInvalidValue;
     // the (W, db) pairs of launch_art_wgrad's LatentJobs
-    const float* const* p = A.params;
-    if (!p[0] || !p[10] || !p[20] || !p[26]) return hipErrorInvalidValue;
-    LatFinJob& ls = FL.lat[0];
-    ls.W[0] = p[0]; ls.src[0] = 0; ls.ld[0] = 163; ls.col_off[0] = 3;
-    ls.W[1] = p[10]; ls.src[1] = 1; ls.ld[1] = P + 128; ls.col_off[1] = P;
-    ls.W[2] = p[20]; ls.src[2] = 2; ls.ld[2] = 256 + P + 128; ls.col_off[2] = 256 + P;
-    ls.npairs = 3; ls.L = 128;
-    LatFinJob& la = FL.lat[1];
-    la.W[0] = p[26]; la.src[0] = 3; la.ld[0] = 256 + V + 128; la.col_off[0] = 256 + V;
-    la.npairs = 1; la.L = 128;
-    LatFinJob& lt = FL.lat[2];
-    lt.W[0] = p[0]; lt.src[0] = 0; lt.ld[0] = 163; lt.col_off[0] = 131;
-    lt.npairs = 1; lt.L = 32;
+    art_latent_jobs(A.params, nullptr, P, V, FL.lat);
+    for (int k = 0; k < kNumLatents; ++k) FL.lat[k].out = g_latents[k];
   }
   D.head_blk_begin = blk;
   for (int h = 0; h < D.nhead; ++h) {
@@ -327,7 +275,7 @@ hipError_t launch_art_latent_grads(const ArtLatentLevel* lv, int nlevels, int Lp
   }
   latent_db_kernel<<<dim3(blk), dim3(64), 0, stream>>>(D);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  latent_finish_kernel<<<dim3(3), dim3(1024), 0, stream>>>(F);
+  latent_finish_kernel<<<dim3(kNumLatents), dim3(1024), 0, stream>>>(F);
   return hipGetLastError();
 }
 

@@ -101,6 +101,14 @@ __host__ __device__ constexpr int wg_K(int kind) {
   return kind == kWg256x256 ? 256 : kind == kWg128x128 ? 128 : kind == kWg256x64 ? 64 : kind == kWg128x256 ? 256 : 32;
 }
 
+// number of steps of a job whose start lies below x on the work line: ceil((x - p_begin) / cost), clamped to [0, nsteps]
+__host__ __device__ __forceinline__ int wg_first_step(int64_t x, int64_t p_begin, int cost, int nsteps) {
+  const int64_t d = x - p_begin;
+  if (d <= 0) return 0;
+  const int64_t q = (d + cost - 1) / cost;
+  return q < nsteps ? (int)q : nsteps;
+}
+
 #ifdef AON_WGRAD_KERNELS   // the kernels are compiled once, in aon_train.hip (run_wgrad_plan is the only launcher)
 // workgroup barrier that leaves the N youngest vector-memory operations (LDS-DMA of later stages) in flight.  __syncthreads()
 // would drain them all (its release fence is an s_waitcnt vmcnt(0)); everything this barrier has to order is spelled out:
@@ -275,14 +283,6 @@ __device__ __forceinline__ void wgrad_job(const WgArgs& a, const WgJob& J, const
   }
 }
 
-__device__ __forceinline__ int wg_first_step(int64_t x, int64_t p_begin, int cost, int nsteps) {
-  // number of steps of the job whose start lies below x on the work line: ceil((x - p_begin) / cost), clamped to [0, nsteps]
-  const int64_t d = x - p_begin;
-  if (d <= 0) return 0;
-  const int64_t q = (d + cost - 1) / cost;
-  return q < nsteps ? (int)q : nsteps;
-}
-
 __global__ void __launch_bounds__(256) wgrad_grouped_kernel(WgArgs a) {
   extern __shared__ __attribute__((aligned(1024))) char wg_smem[];
   const int wg = (int)blockIdx.x;
@@ -341,12 +341,7 @@ struct HeadArgs {
 // trained field), so every stage accumulates in fp64: the product of two floats is exact in a double, the partials are
 // doubles, and the result is rounded to float ONCE, in the second stage.  The kernel is HBM-bound: the fp64 pipe is idle
 // otherwise.  (Rounds 1-3 summed in fp32: one constructor-fuzz seed in 150 had the coarse density bias 3e-3 from the fp64
-// truth where the reference's own fp32 sits at 9e-5.)
-__device__ __forceinline__ double wsum64d(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
+// truth where the reference's own fp32 sits at 9e-5.)  The wave sums are wsum64d's (aon_common.h).
 
 __global__ void __launch_bounds__(256) head_wgrad_kernel(HeadArgs a) {
   const int bx = (int)blockIdx.x + a.blk_offset;

@@ -86,6 +86,38 @@ def test_latent_gradients_bit_equal_to_full_backward(dev, fold_form, n, sizes, n
     _assert_same_bits(model, rays, target, t_rand, u, _codes(dev))
 
 
+# The full backward has two finishing forms for the latent gradients: the merged launch of both levels (art_finish2_kernel, merged
+# schedule, with the early head reductions or without) and the per-level form (set_bwd_merge off: art_finish_kernel once per level, level
+# 1's into a temporary that is added afterwards).  Sizes as above: n = 3 (one head segment, fewer steps than compute units) and n = 37 at
+# the default 65 / 193 samples (Np = 2,432 / 7,168: ragged against 128 and 1,024).
+@pytest.mark.parametrize("n", [3, 37])
+def test_latent_gradients_across_backward_schedules(dev, fold_form, n):
+    from aon_amd import ops
+
+    model = _model(dev)
+    rays, target, t_rand, u = _inputs(dev, model, n, seed=60 + n)
+    codes = _codes(dev)
+    runs = []
+    try:
+        for merge, early in ((True, True), (False, True), (True, False)):
+            ops.set_bwd_merge(merge)
+            ops.set_bwd_early_heads(early)
+            runs.append(_latent_grads(model, rays, target, t_rand, u, codes, False))
+            assert all(p.grad is not None for p in model.parameters())   # the full path ran
+    finally:
+        ops.set_bwd_merge(True)
+        ops.set_bwd_early_heads(True)
+    only, loss_only = _latent_grads(model, rays, target, t_rand, u, codes, True)
+    model.requires_grad_(True)
+    base, loss = runs[0]
+    for k in KEYS:
+        assert torch.isfinite(base[k]).all() and base[k].abs().max().item() > 0, k
+    for grads, other_loss in runs[1:] + [(only, loss_only)]:
+        assert torch.equal(loss, other_loss)
+        for k in KEYS:
+            assert torch.equal(base[k], grads[k]), (k, (base[k] - grads[k]).abs().max().item())
+
+
 def test_bit_equal_other_degrees(dev):
     model = _model(dev, min_deg_point=0, max_deg_point=6, deg_view=2)
     rays, target, t_rand, u = _inputs(dev, model, 70, seed=7)

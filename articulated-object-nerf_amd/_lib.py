@@ -264,7 +264,20 @@ _SCENE_POSE_SIGS = {
 }
 
 
-for _name, (_res, _args) in {**_SIGS, **_EXT_SIGS, **_SCENE_SIGS, **_SCENE_OCC_SIGS, **_SCENE_GRAD_SIGS, **_SCENE_POSE_SIGS}.items():
+class SceneListC(C.Structure):
+    """aon_scene_list (include/aon_hip_scene_lists.h)."""
+    _fields_ = [("act", C.c_int), ("rgb_scale", C.c_float), ("rgb_shift", C.c_float), ("sigma_bias", C.c_float), ("open_end", C.c_int)]
+
+
+# include/aon_hip_scene_lists.h (DESIGN.md section 4.21): a seventh table, kept out of the six lists above
+_SCENE_LISTS_SIGS = {
+    # raw, t_vals, slot, rays_d | n, k, pairs, s, white_bkgd | lists_host | rgb, acc, depth, obj_acc, weights | stream
+    "aon_scene_composite_lists": (_i, [_p] * 4 + [_l, _i, _l, _i, _i] + [_p] + [_p] * 5 + [_p]),
+}
+
+
+for _name, (_res, _args) in {**_SIGS, **_EXT_SIGS, **_SCENE_SIGS, **_SCENE_OCC_SIGS, **_SCENE_GRAD_SIGS, **_SCENE_POSE_SIGS,
+                             **_SCENE_LISTS_SIGS}.items():
     _fn = getattr(lib, _name)  # AttributeError here = the .so does not export what the header declares
     _fn.restype = _res
     _fn.argtypes = _args
@@ -317,3 +330,8 @@ def scene_grad_symbols():
 def scene_pose_symbols():
     """the names include/aon_hip_scene_pose.h declares"""
     return sorted(_SCENE_POSE_SIGS)
+
+
+def scene_lists_symbols():
+    """the names include/aon_hip_scene_lists.h declares"""
+    return sorted(_SCENE_LISTS_SIGS)

@@ -504,7 +504,7 @@ class LitNeRF_AutoDecoder(Harness):
         return fitted_poses, codes.clones(), losses
 
     @torch.no_grad()
-    def render_scene(self, batch, placements, occupancy=None):
+    def render_scene(self, batch, placements, occupancy=None, background=None):
         """Several instances of the library in ONE frame (scene.render_scene): ``placements`` is a list of up to 16
         ``(instance_id, articulation, pose, box)`` -- ``articulation`` a row index into get_interpolated_articulations (the 19 rows of the
         test epoch) or an explicit (32,) code, ``pose`` the (3, 4) rigid object-to-world matrix, ``box`` the object's box in its own
@@ -515,7 +515,9 @@ class LitNeRF_AutoDecoder(Harness):
         among the placements and the objects' empty space is skipped.  In eval mode the grids are kept on the module, keyed by those and the
         arguments, until train() / eval() or load_state_dict() is called or a parameter of the network or the code library changes (their
         version counters are compared on every call; clear_scene_grids() drops them by hand): a stale grid is a wrong picture.  The dict gains "occupied", the
-        (K,) samples of the last level that ran through the MLP."""
+        (K,) samples of the last level that ran through the MLP.
+        ``background``: None, or a scene.SceneBackground -- a vanilla NeRF standing behind the objects.  Then
+        ``placements`` may be empty (at most 15), and "obj_acc" is (N, K + 1) with the backdrop's opacity last."""
         from ... import occupancy as _occupancy
         from ...scene import SceneObject, render_scene
 
@@ -536,7 +538,8 @@ class LitNeRF_AutoDecoder(Harness):
                     self._scene_grids[key] = grid
             objects.append(SceneObject(latents, pose, box, grid))
         rays = {k: batch[k].reshape(-1, 3) for k in ("rays_o", "rays_d", "viewdirs")}
-        levels = render_scene(self.model, objects, rays, self.white_bkgd, chunk=self.hparams.chunk, want_occupied=occupancy is not None)
+        levels = render_scene(self.model, objects, rays, self.white_bkgd, chunk=self.hparams.chunk, want_occupied=occupancy is not None,
+                              background=background)
         if occupancy is not None:
             levels, occupied = levels
         if self.training:      # the weights may move before the next frame

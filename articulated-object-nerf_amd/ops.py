@@ -373,11 +373,18 @@ def pack_vanilla_mlp(params: dict, out: torch.Tensor | None = None, degrees=(0, 
     return _tag(out)
 
 
-def mlp_fwd(packed, rays_o, rays_d, viewdirs, t_vals):
-    """cast_rays + pos_enc + NeRFMLP.forward fused.  Returns raw (n,S,4) = (raw_rgb, raw_density)."""
+def mlp_fwd(packed, rays_o, rays_d, viewdirs, t_vals, out=None):
+    """cast_rays + pos_enc + NeRFMLP.forward fused.  Returns raw (n,S,4) = (raw_rgb, raw_density).
+    ``out``: a contiguous fp32 (n, S, 4) tensor to write instead of a fresh one (as art_mlp_fwd: the backdrop's rows of a scene's buffer)."""
     o, d, v, t = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs"), _f32(t_vals, "t_vals")
     n, S = t.shape
-    raw = torch.empty((n, S, 4), dtype=torch.float32, device=t.device)
+    if out is None:
+        raw = torch.empty((n, S, 4), dtype=torch.float32, device=t.device)
+    else:
+        raw = out
+        if not (isinstance(raw, torch.Tensor) and raw.dtype == torch.float32 and tuple(raw.shape) == (n, S, 4) and raw.device == t.device
+                and raw.is_contiguous()):
+            raise ValueError(f"mlp_fwd: out must be a contiguous float32 ({n}, {S}, 4) tensor on {t.device}")
     with torch.cuda.device(t.device):
         check(lib.aon_mlp_fwd(_pk(packed), _ptr(o), _ptr(d), _ptr(v), _ptr(t), n, S, _ptr(raw), _stream()), "aon_mlp_fwd")
     return raw
@@ -1986,6 +1993,43 @@ class ScenePairs:
     def segment(self, k: int) -> slice:
         return slice(self.starts[k], self.starts[k + 1])
 
+    @classmethod
+    def without_objects(cls, n: int, device) -> "ScenePairs":
+        """The pairs of n rays and NO object (aon_scene_pairs refuses k < 1): K = 0 lists and P = 0 rows, for `with_background`."""
+        e = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=device)   # noqa: E731
+        return cls(int(n), 0, torch.zeros((1,), dtype=torch.int64, device=device), [], e(int(n), 0, dtype=torch.int32), e(0, dtype=torch.int32),
+                   e(0, 3), e(0, 3), e(0, 3), e(0), e(0))
+
+    def with_background(self, rays_o, rays_d, viewdirs, near, far) -> "ScenePairs":
+        """These pairs with one more list, K, that EVERY ray has (the backdrop): its n rows follow object K - 1's,
+        row P + r is world ray r unchanged (`ray` = arange(n), rays_o / rays_d / viewdirs as given) with `near` / `far` as numbers or (n,)
+        tensors; `slot` gains the column P + arange(n), `offsets` / `counts` / `starts` one entry, and `segment(K)` is the backdrop.
+        Torch operations on the tensors' own device only: no kernel, no host read-back (CPU tensors work)."""
+        n, K, P = self.n, self.K, self.P
+        dev = self.slot.device
+        o, d, v = (x.detach().reshape(-1, 3) for x in (rays_o, rays_d, viewdirs))
+        for x, name in ((o, "rays_o"), (d, "rays_d"), (v, "viewdirs")):
+            if x.shape[0] != n or x.dtype != torch.float32 or x.device != dev:
+                raise ValueError(f"with_background: {name} must be float32 ({n}, 3) on {dev}, got {x.dtype} {tuple(x.shape)} on {x.device}")
+        if (P + n) > 0x7fffffff:
+            raise ValueError(f"with_background: {P} + {n} rows are more than 2^31 - 1")
+
+        def vec(x, name):
+            if not isinstance(x, torch.Tensor):
+                return torch.full((n,), float(x), dtype=torch.float32, device=dev)
+            t = x.detach().reshape(-1)
+            if t.numel() != n or t.dtype != torch.float32 or t.device != dev:
+                raise ValueError(f"with_background: a per-ray {name} must be float32 with one value per ray ({n}) on {dev}, got {x.dtype} "
+                                 f"{tuple(x.shape)} on {x.device}")
+            return t
+
+        nr, fr = vec(near, "near"), vec(far, "far")
+        rows = torch.arange(n, dtype=torch.int32, device=dev)
+        slot = torch.cat([self.slot, (rows + P)[:, None]], 1).contiguous()
+        offsets = torch.cat([self.offsets, self.offsets[-1:] + n])
+        return ScenePairs(n, K + 1, offsets, list(self.counts) + [n], slot, torch.cat([self.ray, rows]), torch.cat([self.rays_o, o]),
+                          torch.cat([self.rays_d, d]), torch.cat([self.viewdirs, v]), torch.cat([self.near, nr]), torch.cat([self.far, fr]))
+
 
 def scene_pairs(rays_o, rays_d, viewdirs, objects) -> ScenePairs:
     """Pair every world ray with the objects ([(pose (3, 4) object-to-world, box as ops._box3 takes it)], or scene.SceneObject) whose box
@@ -2036,6 +2080,55 @@ def scene_composite(raw, t_vals, pairs: ScenePairs, rays_d, white_bkgd, opts=Non
     return rgb, acc, depth, obj_acc, weights
 
 
+class SceneList:
+    """How ONE list of a scene's merged composite is read (aon_scene_list, include/aon_hip_scene_lists.h): ``act`` (ACT_*), the
+    activation scalars of ``opts`` (a RenderOpts, read for ACT_ARTICULATED only; None: the defaults) and ``open_end`` -- False: the list
+    ends where its box ends, True: its last interval is the reference's 1e10 * |d| (a backdrop is opaque where its last sample has density)."""
+
+    def __init__(self, act: int = ACT_ARTICULATED, open_end: bool = False, opts=None):
+        if act not in (ACT_NONE, ACT_VANILLA, ACT_ARTICULATED):
+            raise ValueError(f"SceneList: act must be 0 (none), 1 (vanilla) or 2 (articulated), got {act!r}")
+        self.act, self.open_end, self.opts = int(act), bool(open_end), _opts(opts)
+
+    def fill(self, rec) -> None:
+        st, _keep = self.opts.c_struct(1.0, 1.0)      # (the scalars rounded to fp32 exactly as the other calls round them)
+        rec.act, rec.open_end = self.act, int(self.open_end)
+        rec.rgb_scale, rec.rgb_shift, rec.sigma_bias = st.rgb_scale, st.rgb_shift, st.sigma_bias
+
+
+def scene_composite_lists(raw, t_vals, pairs: ScenePairs, rays_d, white_bkgd, lists, want_weights=True):
+    """scene_composite with one SceneList per list of `pairs` (include/aon_hip_scene_lists.h): each list's samples take ITS activation and
+    end rule.  raw (P, S, 4) and t_vals (P, S) in `pairs`' row layout, rays_d the WORLD directions (n, 3)
+    -> (rgb (n, 3), acc (n,), depth (n,), obj_acc (n, K), weights (P, S) or None)."""
+    d = _f32(rays_d.detach(), "rays_d").reshape(-1, 3)
+    n, K, P, dev = pairs.n, pairs.K, pairs.P, d.device
+    t = _f32(t_vals, "t_vals")
+    r = _f32(raw, "raw")
+    S = t.shape[-1]
+    if d.shape[0] != n or tuple(t.shape) != (P, S) or tuple(r.shape) != (P, S, 4):
+        raise ValueError(f"scene_composite_lists: expected rays_d ({n}, 3), t_vals ({P}, S) and raw ({P}, S, 4), got {tuple(d.shape)}, {tuple(t.shape)}, "
+                         f"{tuple(r.shape)}")
+    lists = list(lists)
+    if len(lists) != K or not all(isinstance(x, SceneList) for x in lists):
+        raise ValueError(f"scene_composite_lists: expected {K} ops.SceneList records, one per list of the pairs")
+    if not 1 <= K <= SCENE_MAX_OBJECTS:
+        raise ValueError(f"scene_composite_lists: a merged composite takes 1 to {SCENE_MAX_OBJECTS} lists, got {K}")
+    arr = (_lib.SceneListC * K)()
+    for k, x in enumerate(lists):
+        x.fill(arr[k])
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    acc, depth = (torch.empty((n,), dtype=torch.float32, device=dev) for _ in range(2))
+    obj_acc = torch.empty((n, K), dtype=torch.float32, device=dev)
+    weights = torch.empty((P, S), dtype=torch.float32, device=dev) if want_weights else None
+    if n == 0:      # nothing to launch (and no pointer to hand over)
+        return rgb, acc, depth, obj_acc, weights
+    with torch.cuda.device(dev):
+        check(lib.aon_scene_composite_lists(_ptr(r) if P else None, _ptr(t) if P else None, _ptr(pairs.slot), _ptr(d), n, K, P, S, int(bool(white_bkgd)),
+                                            arr, _ptr(rgb), _ptr(acc), _ptr(depth), _ptr(obj_acc), _ptr(weights), _stream()),
+              "aon_scene_composite_lists")
+    return rgb, acc, depth, obj_acc, weights
+
+
 def scene_composite_bwd(raw, t_vals, pairs: ScenePairs, rays_d, g_rgb, g_acc=None, g_depth=None, g_obj_acc=None, white_bkgd=True, opts=None,
                         act=ACT_ARTICULATED) -> torch.Tensor:
     """The backward of scene_composite on the same raw (P, S, 4), t_vals (P, S), pairs and WORLD rays_d (include/aon_hip_scene_grad.h,
@@ -2065,13 +2158,23 @@ def scene_composite_bwd(raw, t_vals, pairs: ScenePairs, rays_d, g_rgb, g_acc=Non
     return d_raw
 
 
-def scene_art_mlp_fwd(packed, smalls, pairs: ScenePairs, t_vals) -> torch.Tensor:
+def _scene_raw_out(out, P: int, S: int, dev, who: str) -> torch.Tensor:
+    """The (P, S, 4) buffer a scene's MLP stage writes: fresh, or the caller's `out` (the first P rows of a larger buffer)."""
+    if out is None:
+        return torch.empty((P, S, 4), dtype=torch.float32, device=dev)
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == (P, S, 4) and out.device == dev and out.is_contiguous()):
+        raise ValueError(f"{who}: out must be a contiguous float32 ({P}, {S}, 4) tensor on {dev}")
+    return out
+
+
+def scene_art_mlp_fwd(packed, smalls, pairs: ScenePairs, t_vals, out=None) -> torch.Tensor:
     """aon_art_mlp_fwd on every object's segment of `pairs` with that object's per-call block (`smalls[k]`, ops.art_prepare) -> one
-    (P, S, 4) buffer in the pairs' row layout.  An object without a pair costs no launch."""
+    (P, S, 4) buffer in the pairs' row layout (``out``: that buffer, to write instead of a fresh one).  An object without a pair costs no
+    launch."""
     t = _f32(t_vals, "t_vals")
     if len(smalls) != pairs.K or t.shape[0] != pairs.P:
         raise ValueError(f"scene_art_mlp_fwd: expected {pairs.K} per-call blocks and t_vals of {pairs.P} rows")
-    raw = torch.empty((pairs.P, t.shape[1], 4), dtype=torch.float32, device=t.device)
+    raw = _scene_raw_out(out, pairs.P, t.shape[1], t.device, "scene_art_mlp_fwd")
     for k in range(pairs.K):
         seg = pairs.segment(k)
         if seg.stop > seg.start:
@@ -2083,7 +2186,7 @@ def scene_art_mlp_fwd(packed, smalls, pairs: ScenePairs, t_vals) -> torch.Tensor
 _SCENE_OCC_WS = StreamCache()
 
 
-def scene_art_mlp_fwd_occ(packed, smalls, grids, pairs: ScenePairs, t_vals):
+def scene_art_mlp_fwd_occ(packed, smalls, grids, pairs: ScenePairs, t_vals, out=None):
     """scene_art_mlp_fwd with an optional OccupancyGrid per object (`grids[k]`, in object k's own frame -- the frame of `pairs.rays_o` /
     `pairs.rays_d`; None: dense): a sample in an empty cell of its object's grid gets the record (0, 0, 0, -inf) and never reaches the MLP
     (include/aon_hip_scene_occ.h).  One C call.  -> (raw (P, S, 4), occupied (K,) int64 on the device: the samples of each object that ran
@@ -2099,7 +2202,7 @@ def scene_art_mlp_fwd_occ(packed, smalls, grids, pairs: ScenePairs, t_vals):
         if g is not None and g.device != dev:
             raise ValueError(f"scene_art_mlp_fwd_occ: grids[{k}] is on {g.device}, the pairs on {dev}")
     S = t.shape[1]
-    raw = torch.empty((P, S, 4), dtype=torch.float32, device=dev)
+    raw = _scene_raw_out(out, P, S, dev, "scene_art_mlp_fwd_occ")      # (``out``: as scene_art_mlp_fwd)
     occupied = torch.zeros((K,), dtype=torch.int64, device=dev)
     if P == 0:      # nothing to launch (and no pointer to hand over)
         return raw, occupied

@@ -27,7 +27,14 @@ rays with their per-ray near / far), measured in the same run.
 (gradients to every object's (3, 4) pose, no weight-gradient stage) beside the code-and-weight step of --grad in the same run, device
 events, and the device time and share of ops.art_ray_grads and ops.scene_pose_grads inside the pose-only step.
 
-    python tools/scene_bench.py [--reps 5] [--occupancy] [--grad [--poses]] [--out profiles/scene_bench.json]
+--background measures a vanilla NeRF behind the objects INSTEAD and adds a "background" record to the file, leaving
+its other records as they are: on the whole frame at K = 0, 1, 3 the frame with the backdrop, the same frame without it (K >= 1), the
+backdrop network alone through NeRF.forward at the same 65 + 193 samples, and the device time of ops.scene_composite_lists inside the frame
+and its share of it; then an A/B of aon_scene_composite_lists against aon_scene_composite on identical homogeneous closed lists (the K = 3
+frame's pairs at 193 samples, seeded raw): the two calls alternate inside one run, each timed by device events around blocks of 20 launches,
+and the record holds each side's median and spread, and the A/A spread of the old entry against itself.
+
+    python tools/scene_bench.py [--reps 5] [--occupancy] [--grad [--poses]] [--background] [--out profiles/scene_bench.json]
 """
 import argparse
 import json
@@ -289,12 +296,81 @@ def pose_records(model, ro, vd, reps, dev):
     return recs
 
 
+def background_record(model, rays, n, reps, dev):
+    """the --background legs -> {"frames": [one record per K], "composite_ab": {...}}"""
+    from aon_amd.models.vanilla_nerf.model import NeRF
+
+    bg_model = NeRF().to(dev)
+    bg_model.load_state_dict(syn.make_smooth_nerf_state_dict(seed=7))
+    bg = scene.SceneBackground(bg_model, NEAR, FAR)
+    ms_alone = frame_time(lambda: bg_model(rays, False, True, NEAR, FAR), reps) * 1e3
+    frames = []
+    for K in (0, 1, 3):
+        objects = make_scene(K, dev)
+        with_bg = lambda: scene.render_scene(model, objects, rays, True, chunk=n, background=bg)   # noqa: E731
+        ms_with = frame_time(with_bg, reps) * 1e3
+        ms_without = frame_time(lambda: scene.render_scene(model, objects, rays, True, chunk=n), reps) * 1e3 if K else None
+        real = ops.scene_composite_lists
+        runs = []
+        try:
+            for _ in range(reps):
+                st = Stages()
+                ops.scene_composite_lists = lambda *a, **kw: st.run("composite", lambda: real(*a, **kw))
+                st.run("frame", with_bg)
+                runs.append(st.totals())
+        finally:
+            ops.scene_composite_lists = real
+        dev_ms = {k: statistics.median(r[k] for r in runs) for k in runs[0]}
+        rec = {"frame": f"{W}x{H}", "samples": "65 + 193", "objects": K, "reps": reps, "ms_frame_with_backdrop": round(ms_with, 3),
+               "ms_frame_without_backdrop": None if ms_without is None else round(ms_without, 3), "ms_backdrop_alone_nerf_forward": round(ms_alone, 3),
+               "frame_vs_sum_of_parts": round(ms_with / ((ms_without or 0.0) + ms_alone), 4), "ms_frame_device": round(dev_ms["frame"], 3),
+               "ms_composite_lists": round(dev_ms["composite"], 4), "share_composite_lists": round(dev_ms["composite"] / dev_ms["frame"], 5)}
+        print(json.dumps(rec), flush=True)
+        frames.append(rec)
+    # A/B: the new entry against the old one on identical homogeneous closed lists
+    objects = make_scene(3, dev)
+    pairs = ops.scene_pairs(rays["rays_o"], rays["rays_d"], rays["viewdirs"], objects)
+    S = 193
+    t, _ = ops.sample_along_rays(pairs.rays_o, pairs.rays_d, S - 1, pairs.near, pairs.far, want_coords=False)
+    raw = (syn.seeded_uniform(9, pairs.P, S, 4).to(dev) * 4.0 - 1.0).contiguous()
+    lists = [ops.SceneList(ops.ACT_ARTICULATED, False)] * 3
+    old = lambda: ops.scene_composite(raw, t, pairs, rays["rays_d"], True)                         # noqa: E731
+    new = lambda: ops.scene_composite_lists(raw, t, pairs, rays["rays_d"], True, lists)            # noqa: E731
+    same = all(torch.equal(a, b) for a, b in zip(old(), new()))
+    block, rounds = 20, max(4 * reps, 12)
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(block):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / block
+
+    for fn in (old, new):
+        timed(fn)                                              # warm-up of both
+    ms = {"old_a": [], "new": [], "old_b": []}
+    for _ in range(rounds):                                    # alternating: old, new, old, new ...
+        ms["old_a"].append(timed(old))
+        ms["new"].append(timed(new))
+        ms["old_b"].append(timed(old))
+    stat = lambda x: {"median": round(statistics.median(x), 5), "min": round(min(x), 5), "max": round(max(x), 5)}   # noqa: E731
+    ab = {"pairs": pairs.P, "samples": S, "lists": 3, "launches_per_timing": block, "rounds": rounds, "same_bits": bool(same),
+          "ms_scene_composite": stat(ms["old_a"]), "ms_scene_composite_lists": stat(ms["new"]), "ms_scene_composite_again": stat(ms["old_b"]),
+          "new_vs_old": round(statistics.median(ms["new"]) / statistics.median(ms["old_a"]), 4),
+          "old_vs_old": round(statistics.median(ms["old_b"]) / statistics.median(ms["old_a"]), 4)}
+    print(json.dumps(ab), flush=True)
+    return {"frames": frames, "composite_ab": ab}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--occupancy", action="store_true", help="add the occupancy-grid legs (DESIGN.md section 4.17)")
     ap.add_argument("--grad", action="store_true", help="measure gradients through scenes instead (DESIGN.md section 4.18)")
     ap.add_argument("--poses", action="store_true", help="with --grad: the pose-only step beside the code-and-weight step (DESIGN.md section 4.20), key grad_poses")
+    ap.add_argument("--background", action="store_true", help="measure a vanilla backdrop behind the objects instead (DESIGN.md section 4.21), key background")
     ap.add_argument("--objects", type=int, nargs="+", default=[1, 3, 8])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_bench.json"))
     args = ap.parse_args()
@@ -308,6 +384,15 @@ def main():
     ro, vd = ops.raygen(syn.look_at_pose(), H, W, syn.focal_from_fovy(H), device=dev)
     rays = {"rays_o": ro, "rays_d": vd, "viewdirs": vd}
     n = ro.shape[0]
+    if args.background:
+        doc = json.load(open(args.out)) if os.path.exists(args.out) else {"tool": "tools/scene_bench.py", "device": torch.cuda.get_device_name(0)}
+        with torch.no_grad():
+            doc["background"] = background_record(model, rays, n, args.reps, dev)
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+        return
     if args.grad:
         doc = json.load(open(args.out)) if os.path.exists(args.out) else {"tool": "tools/scene_bench.py", "device": torch.cuda.get_device_name(0)}
         if args.poses:

@@ -276,8 +276,15 @@ _SCENE_LISTS_SIGS = {
 }
 
 
+# include/aon_hip_scene_lists_grad.h: an eighth table, kept out of the seven lists above
+_SCENE_LISTS_GRAD_SIGS = {
+    # raw, t_vals, slot, rays_d | g_rgb, g_acc, g_depth, g_obj_acc | n, k, pairs, s, white_bkgd | lists_host | d_raw | stream
+    "aon_scene_composite_lists_bwd": (_i, [_p] * 4 + [_p] * 4 + [_l, _i, _l, _i, _i] + [_p] + [_p] + [_p]),
+}
+
+
 for _name, (_res, _args) in {**_SIGS, **_EXT_SIGS, **_SCENE_SIGS, **_SCENE_OCC_SIGS, **_SCENE_GRAD_SIGS, **_SCENE_POSE_SIGS,
-                             **_SCENE_LISTS_SIGS}.items():
+                             **_SCENE_LISTS_SIGS, **_SCENE_LISTS_GRAD_SIGS}.items():
     _fn = getattr(lib, _name)  # AttributeError here = the .so does not export what the header declares
     _fn.restype = _res
     _fn.argtypes = _args
@@ -335,3 +342,8 @@ def scene_pose_symbols():
 def scene_lists_symbols():
     """the names include/aon_hip_scene_lists.h declares"""
     return sorted(_SCENE_LISTS_SIGS)
+
+
+def scene_lists_grad_symbols():
+    """the names include/aon_hip_scene_lists_grad.h declares"""
+    return sorted(_SCENE_LISTS_GRAD_SIGS)

@@ -323,21 +323,35 @@ class RenderLevelScene(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, _g_weights):
-        g_codes, total, _ = _scene_level_backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, want_weights=True, rays=None)
+        g_codes, total, _, _ = _scene_level_backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, want_weights=True, rays=None)
         return (None,) * 8 + tuple(g_codes) + tuple(total[name] for name in ops.ART_PARAM_ORDER)
 
 
-def _scene_level_forward(ctx, who, pairs, t_vals, rays_d, white_bkgd, opts, packed_fwd, packed_bwd, degrees, tensors):
-    """The forward of the two scene-level Functions; tensors = 3 K codes, then the 40 parameters."""
+class SceneBackdrop:
+    """What one level of a scene's backdrop brings to the scene-level Functions: ``pairs`` = the objects' pairs
+    extended by the backdrop's list (ops.ScenePairs.with_background), the WORLD ``rays_o`` / ``viewdirs`` (n, 3) its n rows run on, and the
+    vanilla level's forward and transposed streams.  ``train``: its parameters receive gradients (the forward keeps activation planes)."""
+
+    def __init__(self, pairs, rays_o, viewdirs, packed_fwd, packed_bwd, train: bool):
+        self.pairs, self.rays_o, self.viewdirs = pairs, rays_o.detach(), viewdirs.detach()
+        self.packed_fwd, self.packed_bwd, self.train = packed_fwd, packed_bwd, bool(train)
+
+
+def _scene_level_forward(ctx, who, pairs, t_vals, rays_d, white_bkgd, opts, packed_fwd, packed_bwd, degrees, tensors, backdrop=None):
+    """The forward of the scene-level Functions; tensors = 3 K codes, then the 40 parameters -- and with a ``backdrop`` (a SceneBackdrop)
+    its level's parameters in ops.VANILLA_PARAM_ORDER.  ``pairs`` are the OBJECTS' pairs (P rows); with a backdrop t_vals is (P + n, S), its
+    n rows go through the vanilla stage into the last n rows of the raw buffer, and the merge is ops.scene_composite_lists."""
     K, n_par = pairs.K, len(ops.ART_PARAM_ORDER)
-    if len(tensors) != 3 * K + n_par:
-        raise ValueError(f"{who}: expected {3 * K} codes and {n_par} parameters, got {len(tensors)} tensors")
+    n_bg = len(ops.VANILLA_PARAM_ORDER) if backdrop is not None else 0
+    if len(tensors) != 3 * K + n_par + n_bg:
+        raise ValueError(f"{who}: expected {3 * K} codes and {n_par}{f' + {n_bg}' if n_bg else ''} parameters, got {len(tensors)} tensors")
     # codes and parameters are read again by the backward: saved the autograd way (an in-place update in between raises)
     ctx.save_for_backward(*tensors)
     ctx.set_materialize_grads(False)
-    params = dict(zip(ops.ART_PARAM_ORDER, (p.detach() for p in tensors[3 * K:])))
+    params = dict(zip(ops.ART_PARAM_ORDER, (p.detach() for p in tensors[3 * K: 3 * K + n_par])))
     t = t_vals.detach()
-    raw = torch.empty((pairs.P, t.shape[1], 4), dtype=torch.float32, device=t.device)
+    all_pairs = pairs if backdrop is None else backdrop.pairs
+    raw = torch.empty((all_pairs.P, t.shape[1], 4), dtype=torch.float32, device=t.device)
     per_object = []
     for k in range(K):
         seg = pairs.segment(k)
@@ -347,25 +361,41 @@ def _scene_level_forward(ctx, who, pairs, t_vals, rays_d, white_bkgd, opts, pack
         small = ops.art_prepare(params, dict(zip(_LATENT_KEYS, tensors[3 * k: 3 * k + 3])), out=None, degrees=degrees)
         _, planes, masks = ops.art_mlp_fwd_train(packed_fwd, small, pairs.rays_o[seg], pairs.rays_d[seg], pairs.viewdirs[seg], t[seg], out=raw[seg])
         per_object.append((small, planes, masks))
-    rgb, acc, depth, obj_acc, weights = ops.scene_composite(raw, t, pairs, rays_d, white_bkgd, opts=opts)
-    ctx.keep = (pairs, t, rays_d.detach(), raw, per_object, packed_bwd, opts, tuple(degrees))
+    lists, bg_planes = None, None
+    if backdrop is None:
+        rgb, acc, depth, obj_acc, weights = ops.scene_composite(raw, t, pairs, rays_d, white_bkgd, opts=opts)
+    else:
+        P = pairs.P
+        if pairs.n and backdrop.train:
+            _, planes, masks = ops.mlp_fwd_train(backdrop.packed_fwd, backdrop.rays_o, rays_d.detach(), backdrop.viewdirs, t[P:], out=raw[P:])
+            bg_planes = (planes, masks)
+        elif pairs.n:      # a frozen backdrop keeps no activation planes
+            ops.mlp_fwd(backdrop.packed_fwd, backdrop.rays_o, rays_d.detach(), backdrop.viewdirs, t[P:], out=raw[P:])
+        lists = [ops.SceneList(ops.ACT_ARTICULATED, False, opts)] * K + [ops.SceneList(ops.ACT_VANILLA, True)]
+        rgb, acc, depth, obj_acc, weights = ops.scene_composite_lists(raw, t, all_pairs, rays_d, white_bkgd, lists)
+    ctx.keep = (pairs, t, rays_d.detach(), raw, per_object, packed_bwd, opts, tuple(degrees), backdrop, lists, bg_planes)
     ctx.white_bkgd = white_bkgd
     ctx.mark_non_differentiable(weights)
     return rgb, acc, depth, obj_acc, weights
 
 
 def _scene_level_backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, want_weights, rays):
-    """The backward of the two scene-level Functions -> (code gradients, parameter gradients, g_pose (K, 12)), the first two None without
-    `want_weights` (no aon_art_wgrad launch), the last None without `rays` = (world rays_o, viewdirs, objects): with them every segment's
-    chain is followed by ops.art_ray_grads into one (P, 3) x 3 buffer, and ops.scene_pose_grads reduces that once."""
+    """The backward of the scene-level Functions -> (code gradients, parameter gradients, g_pose (K, 12), backdrop gradients), the first two
+    None without `want_weights` (no aon_art_wgrad launch), the third None without `rays` = (world rays_o, viewdirs, objects): with them
+    every segment's chain is followed by ops.art_ray_grads into one (P, 3) x 3 buffer, and ops.scene_pose_grads reduces that once on the
+    objects' pairs.  The last is the dict of a trainable backdrop's parameter gradients (its n rows of d_raw -> ops.mlp_bwd_chain ->
+    ops.vanilla_wgrad), None otherwise: a frozen backdrop launches neither."""
     _check_not_released(ctx)
-    pairs, t, rays_d, raw, per_object, packed_bwd, opts, degrees = ctx.keep
+    pairs, t, rays_d, raw, per_object, packed_bwd, opts, degrees, backdrop, lists, bg_planes = ctx.keep
     tensors = ctx.saved_tensors   # (raises if a code or a parameter was modified in place since the forward)
     K, S, dev = pairs.K, t.shape[1], t.device
-    params = dict(zip(ops.ART_PARAM_ORDER, tensors[3 * K:]))
+    params = dict(zip(ops.ART_PARAM_ORDER, tensors[3 * K: 3 * K + len(ops.ART_PARAM_ORDER)]))
     if g_rgb is None:
         g_rgb = torch.zeros((pairs.n, 3), dtype=torch.float32, device=dev)
-    d_raw = ops.scene_composite_bwd(raw, t, pairs, rays_d, g_rgb, g_acc, g_depth, g_obj_acc, ctx.white_bkgd, opts=opts)
+    if backdrop is None:
+        d_raw = ops.scene_composite_bwd(raw, t, pairs, rays_d, g_rgb, g_acc, g_depth, g_obj_acc, ctx.white_bkgd, opts=opts)
+    else:
+        d_raw = ops.scene_composite_lists_bwd(raw, t, backdrop.pairs, rays_d, g_rgb, g_acc, g_depth, g_obj_acc, ctx.white_bkgd, lists)
     total, g_codes = None, []
     g_pairs = torch.zeros((3, pairs.P, 3), dtype=torch.float32, device=dev) if rays is not None else None
     for k in range(K):
@@ -373,9 +403,11 @@ def _scene_level_backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, want_weights, r
         if per_object[k] is None:
             g_codes += [torch.zeros_like(c) for c in codes]
             continue
+        if not want_weights and g_pairs is None:      # only the backdrop's weights are asked for: the objects' chains are not needed
+            continue
         small, planes, masks = per_object[k]
         seg = pairs.segment(k)
-        rows = (seg.stop - seg.start) * S
+        rows =(seg.stop - seg.start) * S
         d_seg = torch.zeros((ops.plane_samples(planes), 4), dtype=torch.float32, device=dev)   # the chain reads the zero tail
         d_seg[:rows] = d_raw[seg].reshape(rows, 4)
         dplanes, dxp = ops.art_bwd_chain(packed_bwd, small, d_seg, masks, planes)
@@ -399,8 +431,18 @@ def _scene_level_backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, want_weights, r
     if rays is not None:
         rays_o, viewdirs, objects = rays
         g_pose = ops.scene_pose_grads(rays_o, rays_d, viewdirs, pairs, objects, g_pairs[0], g_pairs[1], g_pairs[2])
+    bg_grads = None
+    if bg_planes is not None:
+        planes, masks = bg_planes
+        rows = pairs.n * S
+        d_bg = torch.zeros((ops.plane_samples(planes), 4), dtype=torch.float32, device=dev)   # the chain reads the zero tail
+        d_bg[:rows] = d_raw[pairs.P:].reshape(rows, 4)
+        dplanes = ops.mlp_bwd_chain(backdrop.packed_bwd, backdrop.packed_fwd, d_bg, masks, planes.shape)
+        bg_grads = ops.vanilla_wgrad(planes, dplanes, d_bg, backdrop.packed_bwd)
+    elif backdrop is not None and backdrop.train:      # no ray at all
+        bg_grads = {name: torch.zeros_like(p) for name, p in zip(ops.VANILLA_PARAM_ORDER, tensors[3 * K + len(ops.ART_PARAM_ORDER):])}
     ctx.keep, ctx.released = None, True
-    return g_codes, total, g_pose
+    return g_codes, total, g_pose, bg_grads
 
 
 class RenderLevelScenePoses(torch.autograd.Function):
@@ -433,11 +475,64 @@ class RenderLevelScenePoses(torch.autograd.Function):
         head = RenderLevelScenePoses.N_HEAD
         want_poses, want_weights = any(need[head: head + K]), any(need[head + K:])
         n_rest = len(need) - head - K
-        g_codes, total, g_pose = _scene_level_backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, want_weights, ctx.rays if want_poses else None)
+        g_codes, total, g_pose, _ = _scene_level_backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, want_weights, ctx.rays if want_poses else None)
         ctx.rays = None
-        g_poses = (None,) * K
-        if want_poses:
-            g_poses = tuple(torch.cat([g_pose[k, :9].view(3, 3), g_pose[k, 9:].view(3, 1)], dim=1).to(device=dev, dtype=dt) if need[head + k] else None
-                            for k, (dev, dt) in enumerate(ctx.pose_like))
         rest = tuple(g_codes) + tuple(total[name] for name in ops.ART_PARAM_ORDER) if want_weights else (None,) * n_rest
-        return (None,) * head + g_poses + rest
+        return (None,) * head + _pose_grads_out(ctx, need, head, want_poses, g_pose) + rest
+
+
+def _pose_grads_out(ctx, need, head, want_poses, g_pose):
+    """(K, 12) rows [dL/dR | dL/dc] -> one (3, 4) gradient per pose input that needs one, on that pose's own device and dtype"""
+    if not want_poses:
+        return (None,) * len(ctx.pose_like)
+    return tuple(torch.cat([g_pose[k, :9].view(3, 3), g_pose[k, 9:].view(3, 1)], dim=1).to(device=dev, dtype=dt) if need[head + k] else None
+                 for k, (dev, dt) in enumerate(ctx.pose_like))
+
+
+class RenderLevelSceneLists(torch.autograd.Function):
+    """ONE level of a scene WITH A BACKDROP on given sample positions t (P + n, S): RenderLevelScenePoses' objects
+    -- per object with pairs aon_art_mlp_fwd_train into the first P rows of one raw buffer -- plus the backdrop's n rows through the
+    vanilla stage into the last n, merged by aon_scene_composite_lists with K articulated closed records and one vanilla open one.
+    Backward: aon_scene_composite_lists_bwd, then per object as RenderLevelScenePoses, and for a TRAINABLE backdrop its n rows of d_raw ->
+    aon_mlp_bwd_chain -> aon_vanilla_wgrad.  Gradients reach each object's three codes, the 40 articulated parameters, each pose that needs
+    one, and the backdrop level's parameters in ops.VANILLA_PARAM_ORDER.  Only what is asked is paid for: no aon_art_wgrad when no code and
+    no articulated weight needs a gradient; when no backdrop parameter does, the backdrop's forward is the plane-free ops.mlp_fwd and neither
+    its chain nor its weight-gradient kernel is launched.  t, the pairs' existence, near / far, the world rays and the world direction's
+    norm are data.
+
+    ``apply(pairs, t_vals, rays_o, rays_d, viewdirs, objects, white_bkgd, opts, packed_fwd, packed_bwd, degrees, bg_pairs, bg_packed_fwd,
+    bg_packed_bwd, *tensors)``: pairs the OBJECTS' ops.ScenePairs (ops.ScenePairs.without_objects for none), bg_pairs =
+    pairs.with_background(...), the WORLD rays, objects as ops.scene_pairs took them, tensors = the K poses (3, 4), the 3 K codes, the 40
+    parameters, the backdrop level's 24.  -> (rgb (n, 3), acc (n,), depth (n,), obj_acc (n, K + 1), weights (P + n, S))."""
+
+    N_HEAD = 14
+
+    @staticmethod
+    def forward(ctx, pairs, t_vals, rays_o, rays_d, viewdirs, objects, white_bkgd, opts, packed_fwd, packed_bwd, degrees, bg_pairs, bg_packed_fwd,
+                bg_packed_bwd, *tensors):
+        K = pairs.K
+        poses = tensors[:K]
+        if len(list(objects)) != K or any(tuple(p.shape) != (3, 4) for p in poses):
+            raise ValueError(f"RenderLevelSceneLists: expected {K} objects and {K} poses of shape (3, 4)")
+        if bg_pairs.K != K + 1 or bg_pairs.P != pairs.P + pairs.n or tuple(t_vals.shape[:1]) != (bg_pairs.P,):
+            raise ValueError(f"RenderLevelSceneLists: bg_pairs must be pairs.with_background(...) ({K + 1} lists, {pairs.P + pairs.n} rows) and t_vals "
+                             f"hold one row per row of it, got {bg_pairs.K} lists, {bg_pairs.P} rows and t_vals {tuple(t_vals.shape)}")
+        n_bg = len(ops.VANILLA_PARAM_ORDER)
+        ctx.rays = (rays_o.detach(), viewdirs.detach(), list(objects))
+        ctx.pose_like = [(p.device, p.dtype) for p in poses]
+        train = any(ctx.needs_input_grad[len(ctx.needs_input_grad) - n_bg:]) if len(tensors) >= n_bg else False
+        backdrop = SceneBackdrop(bg_pairs, rays_o, viewdirs, bg_packed_fwd, bg_packed_bwd, train)
+        return _scene_level_forward(ctx, "RenderLevelSceneLists", pairs, t_vals, rays_d, white_bkgd, opts, packed_fwd, packed_bwd, degrees, tensors[K:],
+                                    backdrop)
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, _g_weights):
+        K, need = len(ctx.pose_like), ctx.needs_input_grad
+        head, n_bg = RenderLevelSceneLists.N_HEAD, len(ops.VANILLA_PARAM_ORDER)
+        n_obj = len(need) - head - K - n_bg      # 3 K codes and the 40 parameters
+        want_poses, want_weights = any(need[head: head + K]), any(need[head + K: head + K + n_obj])
+        g_codes, total, g_pose, bg_grads = _scene_level_backward(ctx, g_rgb, g_acc, g_depth, g_obj_acc, want_weights, ctx.rays if want_poses else None)
+        ctx.rays = None
+        rest = tuple(g_codes) + tuple(total[name] for name in ops.ART_PARAM_ORDER) if want_weights else (None,) * n_obj
+        bg = tuple(bg_grads[name] for name in ops.VANILLA_PARAM_ORDER) if bg_grads is not None else (None,) * n_bg
+        return (None,) * head + _pose_grads_out(ctx, need, head, want_poses, g_pose) + rest + bg

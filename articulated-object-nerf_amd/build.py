@@ -17,12 +17,13 @@ CSRC = os.path.join(PKG, "csrc")
 _TAG = os.environ.get("AON_BUILD_TAG", "")
 OBJ = os.path.join(PKG, "build" + ("_" + _TAG if _TAG else ""))
 LIB = os.path.join(PKG, "libaon_hip" + ("_" + _TAG if _TAG else "") + ".so")
-SOURCES = ["aon_mlp.hip", "aon_mlp_art.hip", "aon_train.hip", "aon_train_art.hip", "aon_train_latent.hip", "aon_ray_grad.hip", "aon_render.hip", "aon_gmlp.hip", "aon_fold.hip", "aon_optim.hip", "aon_metrics.hip", "aon_mesh.hip", "aon_occ.hip", "aon_bounds.hip", "aon_scene.hip", "aon_scene_occ.hip", "aon_scene_grad.hip", "aon_scene_pose.hip", "aon_scene_lists.hip", "aon_capi.hip", "aon_capi_render.hip", "aon_capi_train.hip", "aon_capi_gmlp.hip"]
+SOURCES = ["aon_mlp.hip", "aon_mlp_art.hip", "aon_train.hip", "aon_train_art.hip", "aon_train_latent.hip", "aon_ray_grad.hip", "aon_render.hip", "aon_gmlp.hip", "aon_fold.hip", "aon_optim.hip", "aon_metrics.hip", "aon_mesh.hip", "aon_occ.hip", "aon_bounds.hip", "aon_scene.hip", "aon_scene_occ.hip", "aon_scene_grad.hip", "aon_scene_pose.hip", "aon_scene_lists.hip", "aon_scene_lists_grad.hip", "aon_capi.hip", "aon_capi_render.hip", "aon_capi_train.hip", "aon_capi_gmlp.hip"]
 HEADERS = [os.path.join(CSRC, "aon_common.h"), os.path.join(CSRC, "aon_params.h"), os.path.join(CSRC, "aon_launch.h"), os.path.join(CSRC, "aon_capi_util.h"), os.path.join(CSRC, "aon_mlp_core.h"), os.path.join(CSRC, "aon_pass.h"), os.path.join(CSRC, "aon_wgrad.h"), os.path.join(CSRC, "aon_art_common.h"), os.path.join(CSRC, "aon_ray_core.h"), os.path.join(CSRC, "aon_composite_grad.h"), os.path.join(CSRC, "aon_scene_merge.h"), os.path.join(CSRC, "aon_gmlp.h"), os.path.join(CSRC, "aon_fold.h"), os.path.join(CSRC, "aon_occ_lookup.h"),
            os.path.join(os.path.dirname(PKG), "include", "aon_hip.h"), os.path.join(os.path.dirname(PKG), "include", "aon_hip_inputs.h"),
            os.path.join(os.path.dirname(PKG), "include", "aon_hip_scene.h"), os.path.join(os.path.dirname(PKG), "include", "aon_hip_scene_occ.h"),
            os.path.join(os.path.dirname(PKG), "include", "aon_hip_scene_grad.h"), os.path.join(os.path.dirname(PKG), "include", "aon_hip_scene_pose.h"),
-           os.path.join(os.path.dirname(PKG), "include", "aon_hip_scene_lists.h")]
+           os.path.join(os.path.dirname(PKG), "include", "aon_hip_scene_lists.h"),
+           os.path.join(os.path.dirname(PKG), "include", "aon_hip_scene_lists_grad.h")]
 # -ffp-contract=off: the stage kernels reproduce the reference's un-fused mul/add sequences; FMAs are explicit.
 # Every file takes the same flags: the one per-file choice ever kept (rounds 1-3: a sched_barrier per MFMA step pinning the A-fragment
 # prefetch in aon_train.hip) spilled 3.5 KB per lane once the chain took two segments (round 4) and is gone (profiles/LAB_NOTEBOOK.md).

@@ -7,6 +7,8 @@
 #include "aon_common.h"
 #include "aon_fold.h"
 
+struct aon_scene_list;   // include/aon_hip_scene_lists.h
+
 namespace aon {
 
 // ---- aon_mlp.hip: the vanilla network's packs, forward kernels and density grid ----
@@ -231,5 +233,11 @@ int64_t scene_composite_bwd_wave_bytes(int K, int S);   // LDS of one wavefront 
 hipError_t launch_scene_composite_bwd(const float* raw, const float* t_vals, const int32_t* slot, const float* dirs, const float* g_rgb,
                                       const float* g_acc, const float* g_depth, const float* g_obj_acc, int64_t n, int K, int64_t pairs, int S,
                                       int white_bkgd, const ActParams& ap, float* d_raw, hipStream_t stream);
+
+// ---- aon_scene_lists_grad.hip: the backward of the per-list merged composite ----
+int64_t scene_composite_lists_bwd_wave_bytes(int K, int S);   // LDS of one wavefront (= one ray)
+hipError_t launch_scene_composite_lists_bwd(const float* raw, const float* t_vals, const int32_t* slot, const float* dirs, const float* g_rgb,
+                                            const float* g_acc, const float* g_depth, const float* g_obj_acc, int64_t n, int K, int64_t pairs,
+                                            int S, int white_bkgd, const aon_scene_list* lists_host, float* d_raw, hipStream_t stream);
 
 }  // namespace aon

@@ -5,6 +5,8 @@ same constructor defaults, parameter names (``deformations_linear.*``, ``deforma
 (deformation_mlp=True, enc_after=True, embed_deg=False, 4x128 deformation and view branches) has kernels."""
 from __future__ import annotations
 
+import contextlib
+
 import torch
 import torch.nn as nn
 import torch.nn.init as init
@@ -406,17 +408,33 @@ class LitNeRF_AutoDecoder(Harness):
             SceneObject(latents, pose, box)
         return placed
 
-    def _scene_fit_loss(self, objects, batch, dev, reg_codes=None):
-        """mse over the levels of `objects` rendered on the batch's rays against its target, plus the code-norm penalty of reg_codes."""
-        from ...scene import render_scene_grad
+    @staticmethod
+    def _scene_fit_background(who, background):
+        """background=None, or a scene.SceneBackground -> the module to freeze beside the scene network (None without a backdrop)"""
+        from ...scene import SceneBackground
+
+        if background is None:
+            return None
+        if not isinstance(background, SceneBackground):
+            raise TypeError(f"{who}: background must be a scene.SceneBackground or None, got {type(background)}")
+        return background.model
+
+    def _scene_fit_loss(self, objects, batch, dev, reg_codes=None, background=None):
+        """mse over the levels of `objects` rendered on the batch's rays against its target, plus the code-norm penalty of reg_codes.
+        background: a scene.SceneBackground standing behind the objects, or None."""
+        from ...scene import render_scene_background_grad, render_scene_grad
 
         rays = {k: batch[k].to(device=dev, dtype=torch.float32).reshape(-1, 3) for k in ("rays_o", "rays_d", "viewdirs")}
         target = batch["target"].to(device=dev, dtype=torch.float32).reshape(-1, 3)
-        levels = render_scene_grad(self.model, objects, rays, self.white_bkgd)
+        if background is None:
+            levels = render_scene_grad(self.model, objects, rays, self.white_bkgd)
+        else:
+            levels = render_scene_background_grad(self.model, objects, rays, self.white_bkgd, background)
         loss = helper.train_loss([lvl[:3] for lvl in levels], target, (), 1e-4)[0]
         return loss if reg_codes is None else loss + fit.code_norm_penalty(reg_codes)
 
-    def fit_scene_codes(self, batches, placements, steps: int, lr: float = 5.0e-3, fit_keys=("density", "color", "articulation"), seed: int = 0):
+    def fit_scene_codes(self, batches, placements, steps: int, lr: float = 5.0e-3, fit_keys=("density", "color", "articulation"), seed: int = 0,
+                        background=None):
         """Fit the codes of the K objects of ONE frame layout to observed frames with the network FROZEN: `steps` Adam
         steps against mse over the levels (helper.train_loss) + 1e-4 * sum over objects and codes of mean ||code||, batch `i % len(batches)`
         at step i.
@@ -429,9 +447,14 @@ class LitNeRF_AutoDecoder(Harness):
 
         The network's requires_grad flags are cleared for the duration and restored.  The codes of all K objects, their gradients and the
         Adam moments are one flat (4, 288 K) buffer stepped by ONE launch (aon_adam_step).  Every step pays the full weight-gradient stage
-        (scene.render_scene_grad has no latent-only shortcut)."""
+        (scene.render_scene_grad has no latent-only shortcut).
+
+        background: None, or a scene.SceneBackground -- the observed frames show the objects in front of that
+        backdrop, and the loss is rendered by scene.render_scene_background_grad with the backdrop network frozen for the duration too (it
+        keeps no activation planes and launches no backward of its own).  None: the calls and the bits of a fit without one."""
         from ...scene import SceneObject
 
+        bg_model = self._scene_fit_background("fit_scene_codes", background)
         batches, _ = self._fit_args("fit_scene_codes", steps, batches)
         if not (isinstance(lr, (int, float)) and lr > 0):
             raise ValueError(f"fit_scene_codes: lr must be positive, got {lr!r}")
@@ -445,17 +468,17 @@ class LitNeRF_AutoDecoder(Harness):
         objects = [SceneObject(leaves, pose, box) for leaves, (_, _, _, pose, box) in zip(codes.leaves, placed)]
 
         def forward(i):
-            return self._scene_fit_loss(objects, batches[i % len(batches)], dev, codes.leaves), codes.wrt
+            return self._scene_fit_loss(objects, batches[i % len(batches)], dev, codes.leaves, background), codes.wrt
 
         def apply(i, grads):
             codes.take(grads)
             codes.step(lr, i + 1)
 
-        with fit.frozen(self.model):
+        with fit.frozen(self.model), (fit.frozen(bg_model) if bg_model is not None else contextlib.nullcontext()):
             losses = fit.run(steps, dev, forward, apply)
         return codes.clones(), losses
 
-    def fit_scene_poses(self, batches, placements, steps: int, lr, fit_codes: bool = False, seed: int = 0):
+    def fit_scene_poses(self, batches, placements, steps: int, lr, fit_codes: bool = False, seed: int = 0, background=None):
         """Recover where the K objects of ONE frame layout ARE from observed frames with the network FROZEN, alone or
         together with their codes: `steps` Adam steps against mse over the levels (helper.train_loss), batch `i % len(batches)` at step i;
         with fit_codes the loss also carries fit_scene_codes' 1e-4 * sum over objects and codes of mean ||code||.
@@ -470,9 +493,12 @@ class LitNeRF_AutoDecoder(Harness):
         are one flat (4, 6 K) buffer, the codes one flat (4, 288 K) buffer when fit_codes; each is stepped by ONE launch (aon_adam_step).
         With fit_codes off no code and no weight requires grad, and a step launches no weight-gradient kernel
         (autograd.RenderLevelScenePoses).  The pairs' existence, near / far and the sample positions are data: a pose moves only through the
-        samples a ray already has inside the object's box, so start close enough for the boxes to overlap the object."""
+        samples a ray already has inside the object's box, so start close enough for the boxes to overlap the object.
+
+        background: as fit_scene_codes'  -- the objects stand in front of that frozen backdrop."""
         from ...scene import SceneObject
 
+        bg_model = self._scene_fit_background("fit_scene_poses", background)
         batches, _ = self._fit_args("fit_scene_poses", steps, batches)
         lrs = fit.lr_pair("fit_scene_poses", lr)
         placed = self._scene_fit_placed("fit_scene_poses", placements, batches)
@@ -488,7 +514,7 @@ class LitNeRF_AutoDecoder(Harness):
 
         def forward(i):
             objects = [SceneObject(leaves, pose, p[4]) for leaves, pose, p in zip(codes.leaves, current_poses(), placed)]
-            return self._scene_fit_loss(objects, batches[i % len(batches)], dev, codes.leaves if fit_codes else None), [corrections] + codes.wrt
+            return self._scene_fit_loss(objects, batches[i % len(batches)], dev, codes.leaves if fit_codes else None, background), [corrections] + codes.wrt
 
         def apply(i, grads):
             pose_buf.take(grads[:1])
@@ -497,7 +523,7 @@ class LitNeRF_AutoDecoder(Harness):
                 codes.take(grads[1:])
                 codes.step(lrs[1], i + 1)
 
-        with fit.frozen(self.model):
+        with fit.frozen(self.model), (fit.frozen(bg_model) if bg_model is not None else contextlib.nullcontext()):
             losses = fit.run(steps, dev, forward, apply)
         with torch.no_grad():
             fitted_poses = [p.clone() for p in current_poses()]

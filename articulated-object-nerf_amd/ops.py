@@ -919,13 +919,21 @@ def plane_rows_view(planes: torch.Tensor) -> torch.Tensor:
     return planes.permute(1, 3, 0, 2).reshape(ng * 4, nst * 32)
 
 
-def mlp_fwd_train(packed, rays_o, rays_d, viewdirs, t_vals):
+def mlp_fwd_train(packed, rays_o, rays_d, viewdirs, t_vals, out=None):
     """Fused forward that also stores the step-major activation planes and the ReLU bit masks
-    -> (raw (n,S,4), planes (Np/32, rows/4, 32, 4), masks)."""
+    -> (raw (n,S,4), planes (Np/32, rows/4, 32, 4), masks).
+    ``out``: as ops.art_mlp_fwd_train's -- a contiguous fp32 (n, S, 4) tensor to write ``raw`` into instead of a fresh one (the backdrop's rows
+    of a scene's buffer)."""
     o, d, v, t = _f32(rays_o, "rays_o"), _f32(rays_d, "rays_d"), _f32(viewdirs, "viewdirs"), _f32(t_vals, "t_vals")
     n, S = t.shape
     Np = padded_samples(n * S)
-    raw = torch.empty((n, S, 4), dtype=torch.float32, device=t.device)
+    if out is None:
+        raw = torch.empty((n, S, 4), dtype=torch.float32, device=t.device)
+    else:
+        raw = out
+        if not (isinstance(raw, torch.Tensor) and raw.dtype == torch.float32 and tuple(raw.shape) == (n, S, 4) and raw.device == t.device
+                and raw.is_contiguous()):
+            raise ValueError(f"mlp_fwd_train: out must be a contiguous float32 ({n}, {S}, 4) tensor on {t.device}")
     # every row the backward consumes is fully written by the kernel (padded columns included); the encoding pad rows
     # (63, and 27..31 of the view block) only ever feed gradient columns that are never emitted -> no zero fill needed
     planes = _new_planes(int(lib.aon_train_plane_rows()), Np, t.device)
@@ -2155,6 +2163,42 @@ def scene_composite_bwd(raw, t_vals, pairs: ScenePairs, rays_d, g_rgb, g_acc=Non
     with torch.cuda.device(dev):
         check(lib.aon_scene_composite_bwd(_ptr(r), _ptr(t), _ptr(pairs.slot), _ptr(d), _ptr(g), _ptr(opt[0]), _ptr(opt[1]), _ptr(opt[2]), n, K, P, S,
                                           int(bool(white_bkgd)), act, C.byref(st), _ptr(d_raw), _stream()), "aon_scene_composite_bwd")
+    return d_raw
+
+
+def scene_composite_lists_bwd(raw, t_vals, pairs: ScenePairs, rays_d, g_rgb, g_acc=None, g_depth=None, g_obj_acc=None, white_bkgd=True,
+                              lists=()) -> torch.Tensor:
+    """The backward of scene_composite_lists on the same raw (P, S, 4), t_vals (P, S), pairs, WORLD rays_d and SceneList records
+    (include/aon_hip_scene_lists_grad.h): upstream gradients g_rgb (n, 3), g_acc / g_depth (n,), g_obj_acc (n, K)
+    -- the last three None for zero -- -> d_raw (P, S, 4) = dL/d raw.  t, the pairs and rays_d are data: nothing flows to them."""
+    d = _f32(rays_d.detach(), "rays_d").reshape(-1, 3)
+    n, K, P, dev = pairs.n, pairs.K, pairs.P, d.device
+    t, r, g = _f32(t_vals, "t_vals"), _f32(raw, "raw"), _f32(g_rgb, "g_rgb")
+    S = t.shape[-1]
+    if d.shape[0] != n or tuple(t.shape) != (P, S) or tuple(r.shape) != (P, S, 4) or tuple(g.shape) != (n, 3):
+        raise ValueError(f"scene_composite_lists_bwd: expected rays_d ({n}, 3), t_vals ({P}, S), raw ({P}, S, 4) and g_rgb ({n}, 3), got "
+                         f"{tuple(d.shape)}, {tuple(t.shape)}, {tuple(r.shape)}, {tuple(g.shape)}")
+    lists = list(lists)
+    if len(lists) != K or not all(isinstance(x, SceneList) for x in lists):
+        raise ValueError(f"scene_composite_lists_bwd: expected {K} ops.SceneList records, one per list of the pairs")
+    if not 1 <= K <= SCENE_MAX_OBJECTS:
+        raise ValueError(f"scene_composite_lists_bwd: a merged composite takes 1 to {SCENE_MAX_OBJECTS} lists, got {K}")
+    opt = []
+    for x, name, shape in ((g_acc, "g_acc", (n,)), (g_depth, "g_depth", (n,)), (g_obj_acc, "g_obj_acc", (n, K))):
+        if x is not None:
+            x = _f32(x, name)
+            if tuple(x.shape) != shape:
+                raise ValueError(f"scene_composite_lists_bwd: expected {name} {shape} or None, got {tuple(x.shape)}")
+        opt.append(x)
+    arr = (_lib.SceneListC * K)()
+    for k, x in enumerate(lists):
+        x.fill(arr[k])
+    d_raw = torch.zeros((P, S, 4), dtype=torch.float32, device=dev)
+    if n == 0 or P == 0:      # nothing to launch (and no pointer to hand over)
+        return d_raw
+    with torch.cuda.device(dev):
+        check(lib.aon_scene_composite_lists_bwd(_ptr(r), _ptr(t), _ptr(pairs.slot), _ptr(d), _ptr(g), _ptr(opt[0]), _ptr(opt[1]), _ptr(opt[2]), n, K, P, S,
+                                                int(bool(white_bkgd)), arr, _ptr(d_raw), _stream()), "aon_scene_composite_lists_bwd")
     return d_raw
 
 

@@ -10,8 +10,9 @@ another object get few fine samples.
 
 An object may carry an occupancy grid in its own frame: its samples in empty cells get zero density and skip the MLP.
 
-A vanilla ``NeRF`` may stand behind the objects as the static backdrop (``SceneBackground``; inference only): one
-more sample list per ray, in world coordinates, merged with the objects' by ``ops.scene_composite_lists``."""
+A vanilla ``NeRF`` may stand behind the objects as the static backdrop (``SceneBackground``): one more sample list
+per ray, in world coordinates, merged with the objects' by ``ops.scene_composite_lists``.  ``render_scene_background_grad`` (DESIGN.md
+section 4.22) is that frame with gradients: to the objects' codes and poses, the scene network's weights and the backdrop's own."""
 from __future__ import annotations
 
 import torch
@@ -127,21 +128,27 @@ def _check_objects(objects, background=None) -> list:
     return objects
 
 
+def _check_background_levels(model, K, background):
+    """The checks a scene with a backdrop makes beyond _check_objects: matching level counts, (K + 1) * S merged samples within the limit"""
+    bg = background.model
+    if bg.num_levels != model.num_levels:
+        raise ValueError(f"the backdrop runs {bg.num_levels} level(s), the scene model {model.num_levels}: they must match (the backdrop is sampled "
+                         "with the scene model's sample counts, level by level)")
+    for level in range(model.num_levels):
+        S = model._opts.S(level)
+        if (K + 1) * S > ops.SCENE_MAX_MERGED:
+            raise ValueError(f"{K} objects and a backdrop of {S} samples each at level {level} are {(K + 1) * S} merged samples per ray; the merged "
+                             f"composite holds at most {ops.SCENE_MAX_MERGED}: use fewer samples or fewer objects")
+
+
 def _render_scene_background(model, objects, rays, white_bkgd, chunk, want_occupied, background):
     """render_scene with a backdrop: the objects' pairs as ever (none for an empty object list), extended by the
     backdrop's list; ONE sampler call for all rows; per level the objects' segments through the articulated MLP stage into the first P rows
     of one raw buffer and the backdrop's n rows through ops.mlp_fwd into the last n; the merge is ops.scene_composite_lists, and the fine t
     of all lists alike comes from the merged weights."""
     bg = background.model
-    if bg.num_levels != model.num_levels:
-        raise ValueError(f"the backdrop runs {bg.num_levels} level(s), the scene model {model.num_levels}: they must match (the backdrop is sampled "
-                         "with the scene model's sample counts, level by level)")
     K = len(objects)
-    for level in range(model.num_levels):
-        S = model._opts.S(level)
-        if (K + 1) * S > ops.SCENE_MAX_MERGED:
-            raise ValueError(f"{K} objects and a backdrop of {S} samples each at level {level} are {(K + 1) * S} merged samples per ray; the merged "
-                             f"composite holds at most {ops.SCENE_MAX_MERGED}: use fewer samples or fewer objects")
+    _check_background_levels(model, K, background)
     o, d, v = rays["rays_o"], rays["rays_d"], rays["viewdirs"]
     n = o.shape[0]
     mlps = [model.coarse_mlp, model.fine_mlp][: model.num_levels]
@@ -258,12 +265,13 @@ def render_scene_grad(model, objects, rays, white_bkgd, randomized: bool = False
     One chunk: the activation planes of every pair (13.8 KB per sample) live until the backward, and are released by it -- a second backward
     through the same forward raises.  Dense only: an object carrying a grid is refused (the training forward has no gather instance).  A
     frozen network still pays the full weight-gradient stage, unless a pose tensor is present and no code and no weight requires grad: a
-    pose-only backward launches no weight-gradient kernel.  ``background``: refused -- a backdrop is inference only."""
+    pose-only backward launches no weight-gradient kernel.  ``background``: refused here -- the frame with a backdrop and gradients is
+    ``render_scene_background_grad``."""
     from .autograd import RenderLevelScene, RenderLevelScenePoses
 
     if background is not None:
-        raise NotImplementedError("scene gradients take no background: a backdrop (scene.SceneBackground) is inference only, gradients through "
-                                  "it are not built")
+        raise NotImplementedError("scene gradients take no background: with a backdrop (scene.SceneBackground) this function is inference only; "
+                                  "the gradients through a scene with a backdrop are scene.render_scene_background_grad's")
     if randomized:
         raise ValueError("scene gradients sample without randomness: randomized=True is refused")
     if model.noise_std > 0:
@@ -291,6 +299,60 @@ def render_scene_grad(model, objects, rays, white_bkgd, randomized: bool = False
         else:
             rgb, acc, depth, obj_acc, weights = RenderLevelScene.apply(pairs, t, d, bool(white_bkgd), model._opts, mlp.packed(True), mlp.packed_bwd(True),
                                                                        mlp.degrees, *codes, *mlp.ordered_params())
+        levels.append((rgb, acc, depth, obj_acc))
+        if level + 1 < len(mlps):
+            with torch.no_grad():
+                t = ops.sample_pdf_t_n(t, weights, model.num_fine_samples)
+    return levels
+
+
+def render_scene_background_grad(model, objects, rays, white_bkgd, background, randomized: bool = False):
+    """``render_scene(..., background=background)`` with autograd history: -> ``[(rgb (N, 3), acc (N,), depth (N,),
+    obj_acc (N, K + 1))]`` per level, the bits ``render_scene`` returns with that backdrop, whose gradients reach every object's three codes,
+    the scene network's weights, the pose of every object whose ``pose_tensor`` is set (as ``render_scene_grad``) and the backdrop network's
+    parameters.  ``objects`` may be empty: the backdrop alone through the lists path.  The pairs' existence, near / far of objects and
+    backdrop, the sample positions of both levels (the fine draws of ALL lists come from the merged coarse weights, detached), the world
+    rays -- hence the backdrop's rays -- and the world direction's norm are data.
+
+    One chunk, dense objects only, no noise, one or two levels, as ``render_scene_grad``; a second backward through the same forward raises.
+    Only what is asked is paid for: no weight-gradient kernel of the scene network when no code and none of its weights requires grad, and a
+    backdrop none of whose parameters requires grad runs the plane-free forward (every one of the N rays carries S backdrop samples) and
+    launches neither its backward chain nor its weight-gradient kernel."""
+    from .autograd import RenderLevelSceneLists
+
+    if randomized:
+        raise ValueError("scene gradients sample without randomness: randomized=True is refused")
+    if model.noise_std > 0:
+        raise NotImplementedError("scene gradients take no density noise (noise_std > 0)")
+    if model.num_levels not in (1, 2):
+        raise NotImplementedError("scene gradients run one or two levels")
+    if background is None:
+        raise TypeError("render_scene_background_grad: background must be a scene.SceneBackground (without one, call render_scene_grad)")
+    objects = _check_objects(objects, background)
+    for k, ob in enumerate(objects):
+        if ob.grid is not None:
+            raise NotImplementedError(f"scene gradients are dense only: object {k} carries an occupancy grid")
+    K = len(objects)
+    _check_background_levels(model, K, background)
+    bg = background.model
+    o, d, v = rays["rays_o"], rays["rays_d"], rays["viewdirs"]
+    n = o.shape[0]
+    mlps = [model.coarse_mlp, model.fine_mlp][: model.num_levels]
+    bg_mlps = [bg.coarse_mlp, bg.fine_mlp][: model.num_levels]
+    codes = [ob.latents[key] for ob in objects for key in _LATENT_WIDTHS]
+    poses = [ob.pose_tensor if ob.pose_tensor is not None else ob.pose for ob in objects]
+    with torch.no_grad():
+        near, far = background.bounds(0, n, n)
+        obj_pairs = ops.scene_pairs(o, d, v, objects) if K else ops.ScenePairs.without_objects(n, o.device)
+        pairs = obj_pairs.with_background(o, d, v, near, far)
+        t, _ = ops.sample_along_rays(pairs.rays_o, pairs.rays_d, model.num_coarse_samples, pairs.near, pairs.far, want_coords=False, lindisp=model.lindisp)
+    levels = []
+    for level, (mlp, bg_mlp) in enumerate(zip(mlps, bg_mlps)):
+        # fresh streams: the backward reads them again, and a later forward must not overwrite what this graph still needs
+        rgb, acc, depth, obj_acc, weights = RenderLevelSceneLists.apply(obj_pairs, t, o, d, v, objects, bool(white_bkgd), model._opts, mlp.packed(True),
+                                                                        mlp.packed_bwd(True), mlp.degrees, pairs, bg_mlp.packed(True),
+                                                                        bg_mlp.packed_bwd(True), *poses, *codes, *mlp.ordered_params(),
+                                                                        *bg_mlp.ordered_params())
         levels.append((rgb, acc, depth, obj_acc))
         if level + 1 < len(mlps):
             with torch.no_grad():

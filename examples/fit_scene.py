@@ -5,6 +5,7 @@ print every object's code distance to the truth before and after.
 
     python examples/fit_scene.py --synthetic /tmp/multi --img_wh 32 24 --steps 300
     python examples/fit_scene.py --synthetic /tmp/multi --steps 300 --fit_steps 200 --render_wh 48 36
+    python examples/fit_scene.py --synthetic /tmp/multi --steps 300 --background        # ... in front of a vanilla NeRF as the frozen backdrop
 """
 import argparse
 import json
@@ -17,7 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from examples.render_scene import placement  # noqa: E402
+from examples.render_scene import placement, train_backdrop  # noqa: E402
 from examples.run_autodecoder import collate  # noqa: E402
 
 
@@ -32,6 +33,10 @@ def main():
     ap.add_argument("--lr", type=float, default=5e-3)
     ap.add_argument("--perturbation", type=float, default=0.3, help="standard deviation of the noise added to the articulation codes")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--background", action="store_true", help="the observed frame shows the objects in front of a vanilla NeRF trained on the synthetic "
+                    "single scene, and the fit renders them in front of that frozen backdrop (DESIGN.md section 4.22)")
+    ap.add_argument("--background-steps", type=int, default=300, help="training steps of the backdrop's LitNeRF")
+    ap.add_argument("--out", default="fit_scene_out", help="where the backdrop's synthetic scene is written without --synthetic")
     args = ap.parse_args()
     import random as _random
     _random.seed(args.seed); np.random.seed(args.seed); torch.manual_seed(args.seed)
@@ -61,16 +66,19 @@ def main():
     Wr, Hr = args.render_wh
     ro, vd = ops.raygen(syn.look_at_pose(5.0, 35.0, 30.0), Hr, Wr, syn.focal_from_fovy(Hr, 40.0), device=dev)
     batch = {"rays_o": ro, "rays_d": vd, "viewdirs": vd}
-    batch["target"] = lit.render_scene(batch, layout)["rgb"].clone()
+    background = train_backdrop(args, dev) if args.background else None
+    batch["target"] = lit.render_scene(batch, layout, background=background)["rgb"].clone()
     gen = torch.Generator().manual_seed(args.seed + 1)
     start = [(iid, truth[j] + args.perturbation * torch.randn(32, generator=gen).to(dev), pose, box) for j, (iid, _, pose, box) in enumerate(layout)]
-    codes, losses = lit.fit_scene_codes([batch], start, args.fit_steps, lr=args.lr, fit_keys=("articulation",))
+    codes, losses = lit.fit_scene_codes([batch], start, args.fit_steps, lr=args.lr, fit_keys=("articulation",), background=background)
     before = [float((s[1] - t).norm()) for s, t in zip(start, truth)]
     after = [float((c["articulation"].reshape(-1) - t).norm()) for c, t in zip(codes, truth)]
     for j, (b, a) in enumerate(zip(before, after)):
         print(f"object {j}: articulation code distance to the truth {b:.4f} -> {a:.4f}")
     rep = {"trained_steps": args.steps, "fit_steps": args.fit_steps, "frame": [Wr, Hr], "loss_first": float(losses[0]), "loss_last": float(losses[-1]),
            "code_distance_before": [round(b, 4) for b in before], "code_distance_after": [round(a, 4) for a in after]}
+    if background is not None:
+        rep["backdrop_steps"] = args.background_steps
     print(json.dumps(rep))
     return rep
 

@@ -5,6 +5,7 @@ poses -- and print every object's rotation and translation error before and afte
 
     python examples/fit_scene_poses.py --synthetic /tmp/multi --img_wh 32 24 --steps 300
     python examples/fit_scene_poses.py --synthetic /tmp/multi --steps 300 --fit_steps 300 --render_wh 48 36
+    python examples/fit_scene_poses.py --synthetic /tmp/multi --steps 300 --background  # ... in front of a vanilla NeRF as the frozen backdrop
 """
 import argparse
 import json
@@ -17,7 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from examples.render_scene import placement  # noqa: E402
+from examples.render_scene import placement, train_backdrop  # noqa: E402
 from examples.run_autodecoder import collate  # noqa: E402
 
 
@@ -40,6 +41,10 @@ def main():
     ap.add_argument("--degrees", type=float, default=2.0, help="rotation of the perturbation")
     ap.add_argument("--shift", type=float, default=0.05, help="translation of the perturbation")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--background", action="store_true", help="the observed frame shows the objects in front of a vanilla NeRF trained on the synthetic "
+                    "single scene, and the fit renders them in front of that frozen backdrop (DESIGN.md section 4.22)")
+    ap.add_argument("--background-steps", type=int, default=300, help="training steps of the backdrop's LitNeRF")
+    ap.add_argument("--out", default="fit_scene_out", help="where the backdrop's synthetic scene is written without --synthetic")
     args = ap.parse_args()
     import random as _random
     _random.seed(args.seed); np.random.seed(args.seed); torch.manual_seed(args.seed)
@@ -67,20 +72,23 @@ def main():
     Wr, Hr = args.render_wh
     ro, vd = ops.raygen(syn.look_at_pose(5.0, 35.0, 30.0), Hr, Wr, syn.focal_from_fovy(Hr, 40.0), device=dev)
     batch = {"rays_o": ro, "rays_d": vd, "viewdirs": vd}
-    batch["target"] = lit.render_scene(batch, layout)["rgb"].clone()
+    background = train_backdrop(args, dev) if args.background else None
+    batch["target"] = lit.render_scene(batch, layout, background=background)["rgb"].clone()
     gen = torch.Generator().manual_seed(args.seed + 1)
     start = []
     for iid, art, pose, box in layout:
         axis, move = torch.randn(3, generator=gen, dtype=torch.float64), torch.randn(3, generator=gen, dtype=torch.float64)
         corr = torch.cat([axis / axis.norm() * np.deg2rad(args.degrees), move / move.norm() * args.shift])
         start.append((iid, art, ops.apply_pose_correction(torch.as_tensor(pose, dtype=torch.float64), corr).float(), box))
-    poses, _, losses = lit.fit_scene_poses([batch], start, args.fit_steps, args.lr)
+    poses, _, losses = lit.fit_scene_poses([batch], start, args.fit_steps, args.lr, background=background)
     before = [pose_errors(s[2], torch.as_tensor(t[2])) for s, t in zip(start, layout)]
     after = [pose_errors(p, torch.as_tensor(t[2])) for p, t in zip(poses, layout)]
     for j, (b, a) in enumerate(zip(before, after)):
         print(f"object {j}: rotation error {b[0]:.3f} -> {a[0]:.3f} degrees, translation error {b[1]:.4f} -> {a[1]:.4f}")
     rep = {"trained_steps": args.steps, "fit_steps": args.fit_steps, "frame": [Wr, Hr], "loss_first": float(losses[0]), "loss_last": float(losses[-1]),
            "pose_error_before": [[round(x, 4) for x in b] for b in before], "pose_error_after": [[round(x, 4) for x in a] for a in after]}
+    if background is not None:
+        rep["backdrop_steps"] = args.background_steps
     print(json.dumps(rep))
     return rep
 

@@ -9,7 +9,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = ["aon_mlp.hip", "aon_mlp_art.hip", "aon_train.hip", "aon_train_art.hip", "aon_train_latent.hip", "aon_ray_grad.hip", "aon_render.hip", "aon_gmlp.hip", "aon_fold.hip", "aon_scene.hip", "aon_scene_grad.hip", "aon_scene_pose.hip", "aon_scene_lists.hip", "aon_occ.hip", "aon_scene_occ.hip", "aon_bounds.hip", "aon_optim.hip", "aon_metrics.hip", "aon_mesh.hip"]
+FILES = ["aon_mlp.hip", "aon_mlp_art.hip", "aon_train.hip", "aon_train_art.hip", "aon_train_latent.hip", "aon_ray_grad.hip", "aon_render.hip", "aon_gmlp.hip", "aon_fold.hip", "aon_scene.hip", "aon_scene_grad.hip", "aon_scene_pose.hip", "aon_scene_lists.hip", "aon_scene_lists_grad.hip", "aon_occ.hip", "aon_scene_occ.hip", "aon_bounds.hip", "aon_optim.hip", "aon_metrics.hip", "aon_mesh.hip"]
 PAT = re.compile(r"Name: (\S+).*?VGPRs: (\d+).*?AGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+)")
 
 

@@ -34,7 +34,12 @@ and its share of it; then an A/B of aon_scene_composite_lists against aon_scene_
 frame's pairs at 193 samples, seeded raw): the two calls alternate inside one run, each timed by device events around blocks of 20 launches,
 and the record holds each side's median and spread, and the A/A spread of the old entry against itself.
 
-    python tools/scene_bench.py [--reps 5] [--occupancy] [--grad [--poses]] [--background] [--out profiles/scene_bench.json]
+--grad --background adds a "background_grad" record instead: one step of scene.render_scene_background_grad on the
+4,096 rays of --grad at K = 0, 1, 3 with the backdrop frozen and trainable (host clock and device events, median and spread, and the share of
+ops.scene_composite_lists_bwd), then the A/B of aon_scene_composite_lists_bwd against aon_scene_composite_bwd on identical homogeneous closed
+lists, alternating in one run as above, with the old entry against itself as the noise floor.
+
+    python tools/scene_bench.py [--reps 5] [--occupancy] [--grad [--poses | --background]] [--background] [--out profiles/scene_bench.json]
 """
 import argparse
 import json
@@ -364,13 +369,111 @@ def background_record(model, rays, n, reps, dev):
     return {"frames": frames, "composite_ab": ab}
 
 
+def background_grad_record(model, ro, vd, reps, dev):
+    """the --grad --background legs -> {"steps": [one record per (K, frozen / trainable backdrop)], "composite_bwd_ab": {...}}"""
+    from aon_amd.models.vanilla_nerf.model import NeRF
+
+    idx = (torch.arange(GRAD_RAYS, device=dev) * (ro.shape[0] // GRAD_RAYS)).long()
+    rays = {"rays_o": ro[idx].contiguous(), "rays_d": vd[idx].contiguous(), "viewdirs": vd[idx].contiguous()}
+    target = syn.seeded_uniform(5, GRAD_RAYS, 3).to(dev)
+    keys = ("density", "color", "articulation")
+    nets = [p for m in (model.coarse_mlp, model.fine_mlp) for p in m.ordered_params()]
+    bg_model = NeRF().to(dev)
+    bg_model.load_state_dict(syn.make_smooth_nerf_state_dict(seed=7))
+    bg = scene.SceneBackground(bg_model, NEAR, FAR)
+    bg_nets = [p for m in (bg_model.coarse_mlp, bg_model.fine_mlp) for p in m.ordered_params()]
+    spread = lambda x: {"median": round(statistics.median(x), 4), "min": round(min(x), 4), "max": round(max(x), 4)}   # noqa: E731
+    steps = []
+    for K in (0, 1, 3):
+        objects = [scene.SceneObject({k: v.clone().requires_grad_(True) for k, v in ob.latents.items()}, ob.pose, ob.box) for ob in make_scene(K, dev)]
+        codes = [ob.latents[k] for ob in objects for k in keys]
+        for trainable in (False, True):
+            for p in bg_model.parameters():
+                p.requires_grad_(trainable)
+            wrt = codes + nets + (bg_nets if trainable else [])
+
+            def step():
+                levels = scene.render_scene_background_grad(model, objects, rays, True, bg)
+                loss = sum(torch.mean((lv[0] - target) ** 2) + 0.1 * lv[1].mean() + 0.05 * lv[2].mean() + 0.2 * (lv[3] ** 2).mean() for lv in levels)
+                return torch.autograd.grad(loss, wrt)
+
+            step()                                             # warm-up
+            host = []
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                step()
+                torch.cuda.synchronize()
+                host.append((time.perf_counter() - t0) * 1e3)
+            real_bwd, real_fwd = ops.scene_composite_lists_bwd, ops.scene_composite_lists
+            runs = []
+            try:
+                for _ in range(reps):
+                    st = Stages()
+                    ops.scene_composite_lists_bwd = lambda *a, **kw: st.run("composite_bwd", lambda: real_bwd(*a, **kw))
+                    ops.scene_composite_lists = lambda *a, **kw: st.run("composite", lambda: real_fwd(*a, **kw))
+                    st.run("step", step)
+                    runs.append(st.totals())
+            finally:
+                ops.scene_composite_lists_bwd, ops.scene_composite_lists = real_bwd, real_fwd
+            dev_ms = {k: statistics.median(r[k] for r in runs) for k in runs[0]}
+            with torch.no_grad():
+                P = ops.scene_pairs(rays["rays_o"], rays["rays_d"], rays["viewdirs"], objects).P if K else 0
+            rec = {"rays": GRAD_RAYS, "samples": "65 + 193", "objects": K, "backdrop": "trainable" if trainable else "frozen", "reps": reps,
+                   "rows": P + GRAD_RAYS, "mlp_samples": (P + GRAD_RAYS) * (65 + 193), "ms_step_host": spread(host),
+                   "ms_step_device": spread([r["step"] for r in runs]), "ms_composite_lists_bwd": round(dev_ms["composite_bwd"], 4),
+                   "ms_composite_lists_fwd": round(dev_ms["composite"], 4), "share_composite_lists_bwd": round(dev_ms["composite_bwd"] / dev_ms["step"], 5)}
+            print(json.dumps(rec), flush=True)
+            steps.append(rec)
+    # A/B: the new backward against the old one on identical homogeneous closed lists, alternating in one run
+    objects = make_scene(3, dev)
+    with torch.no_grad():
+        pairs = ops.scene_pairs(rays["rays_o"], rays["rays_d"], rays["viewdirs"], objects)
+        S = 193
+        t, _ = ops.sample_along_rays(pairs.rays_o, pairs.rays_d, S - 1, pairs.near, pairs.far, want_coords=False)
+    raw = (syn.seeded_uniform(9, pairs.P, S, 4).to(dev) * 4.0 - 1.0).contiguous()
+    g = [syn.seeded_uniform(11 + i, GRAD_RAYS, w).to(dev).reshape(shape) - 0.5 for i, (w, shape) in enumerate(((3, (GRAD_RAYS, 3)), (1, (GRAD_RAYS,)), (1, (GRAD_RAYS,)),
+                                                                                                            (3, (GRAD_RAYS, 3))))]
+    lists = [ops.SceneList(ops.ACT_ARTICULATED, False)] * 3
+    old = lambda: ops.scene_composite_bwd(raw, t, pairs, rays["rays_d"], g[0], g[1], g[2], g[3], True)                        # noqa: E731
+    new = lambda: ops.scene_composite_lists_bwd(raw, t, pairs, rays["rays_d"], g[0], g[1], g[2], g[3], True, lists)           # noqa: E731
+    same = bool(torch.equal(old().view(torch.int32), new().view(torch.int32)))
+    block, rounds = 20, max(4 * reps, 12)
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(block):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / block
+
+    for fn in (old, new):
+        timed(fn)                                              # warm-up of both
+    ms = {"old_a": [], "new": [], "old_b": []}
+    for _ in range(rounds):                                    # alternating: old, new, old, new ...
+        ms["old_a"].append(timed(old))
+        ms["new"].append(timed(new))
+        ms["old_b"].append(timed(old))
+    stat = lambda x: {"median": round(statistics.median(x), 5), "min": round(min(x), 5), "max": round(max(x), 5)}   # noqa: E731
+    ab = {"pairs": pairs.P, "samples": S, "lists": 3, "launches_per_timing": block, "rounds": rounds, "same_bits": same,
+          "note": "each launch includes the wrapper's torch.zeros of d_raw, the same in both",
+          "ms_scene_composite_bwd": stat(ms["old_a"]), "ms_scene_composite_lists_bwd": stat(ms["new"]), "ms_scene_composite_bwd_again": stat(ms["old_b"]),
+          "new_vs_old": round(statistics.median(ms["new"]) / statistics.median(ms["old_a"]), 4),
+          "old_vs_old": round(statistics.median(ms["old_b"]) / statistics.median(ms["old_a"]), 4)}
+    print(json.dumps(ab), flush=True)
+    return {"steps": steps, "composite_bwd_ab": ab}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--occupancy", action="store_true", help="add the occupancy-grid legs (DESIGN.md section 4.17)")
     ap.add_argument("--grad", action="store_true", help="measure gradients through scenes instead (DESIGN.md section 4.18)")
     ap.add_argument("--poses", action="store_true", help="with --grad: the pose-only step beside the code-and-weight step (DESIGN.md section 4.20), key grad_poses")
-    ap.add_argument("--background", action="store_true", help="measure a vanilla backdrop behind the objects instead (DESIGN.md section 4.21), key background")
+    ap.add_argument("--background", action="store_true", help="measure a vanilla backdrop behind the objects instead (DESIGN.md section 4.21), key background; "
+                    "with --grad: gradients through a scene with a backdrop (DESIGN.md section 4.22), key background_grad")
     ap.add_argument("--objects", type=int, nargs="+", default=[1, 3, 8])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "scene_bench.json"))
     args = ap.parse_args()
@@ -384,6 +487,14 @@ def main():
     ro, vd = ops.raygen(syn.look_at_pose(), H, W, syn.focal_from_fovy(H), device=dev)
     rays = {"rays_o": ro, "rays_d": vd, "viewdirs": vd}
     n = ro.shape[0]
+    if args.grad and args.background:
+        doc = json.load(open(args.out)) if os.path.exists(args.out) else {"tool": "tools/scene_bench.py", "device": torch.cuda.get_device_name(0)}
+        doc["background_grad"] = background_grad_record(model, ro, vd, args.reps, dev)
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+        return
     if args.background:
         doc = json.load(open(args.out)) if os.path.exists(args.out) else {"tool": "tools/scene_bench.py", "device": torch.cuda.get_device_name(0)}
         with torch.no_grad():
